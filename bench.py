@@ -37,13 +37,16 @@ this workload and these kernel sources) and `cpu_baseline` (the oracle's scalar 
 bounded sample of the same poses).
 """
 import argparse
+import atexit
 import hashlib
 import importlib
 import json
 import os
+import shutil
 import socket
 import subprocess
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -80,10 +83,13 @@ def parse_args(argv=None):
     ap.add_argument('--share', type=int, default=0, metavar='G',
                     help='strong-scaling proxy on ONE GPU: after the headline the same workload is timed with poses / G per level '
                          '(what one of G GPUs would render under --scaling strong); prints scaling_proxy')
-    ap.add_argument('--long', type=float, default=0.5, metavar='SECONDS',
+    ap.add_argument('--long', type=float, default=0.0, metavar='SECONDS',
                     help='raise the number of timed steps until the timed region lasts at least this long (from a calibration pass of --steps '
                          'steps; e.g. --long 2: an external sampler then sees the GPU busy); the line\'s `steps` is the number really timed, '
-                         '`steps_requested` what --steps said.  Default 0.5 (twenty 4 ms steps are too thin a region); 0: exactly --steps')
+                         '`steps_requested` what --steps said.  Default 0: exactly --steps timed steps')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='after the timed steps, write the frames the timed path left in its batches (its last step) to DIR as float32 .npy '
+                         'files: every pose when they fit in 60 MB, else a fixed seeded sample that frame_index.npy / row_index.npy name')
     ap.add_argument('--per-level-batches', action='store_true',
                     help='several levels (--levels): one batch per level alternating over the streams (round 5\'s way) instead of ONE level set '
                          'whose mixed poses are cut into one sub-batch per stream')
@@ -116,6 +122,20 @@ def level_list(args):
         else:
             out.append(int(part))
     return out
+
+
+def synthetic_wad(synthetic, kind=''):
+    """The seeded synthetic IWAD `kind` ('', 'big' or 'rich'): synthetic.ensure_<kind>_wad() writes it into tests/golden on first
+    use (build() generates all three).  A tree that lacks it and cannot be written to -- built earlier, run by another user -- gets
+    the same seeded file generated in a temporary directory of this process instead, removed at exit."""
+    prefix = kind + '_' if kind else ''
+    attr = prefix.upper() + 'WAD_PATH'
+    path = getattr(synthetic, attr)
+    if not os.path.exists(path) and not os.access(os.path.dirname(path), os.W_OK):
+        tmp = tempfile.mkdtemp(prefix='rdoom_wad_')
+        atexit.register(shutil.rmtree, tmp, True)
+        setattr(synthetic, attr, os.path.join(tmp, os.path.basename(path)))   # (ensure_*_wad() read the path when called)
+    return getattr(synthetic, 'ensure_%swad' % prefix)()
 
 
 def kernel_source_digest():
@@ -258,6 +278,40 @@ def collect_kernels(items, acc=None):
             acc['visible_triangles'] = acc.get('visible_triangles', 0) + t['visible_triangles'] * t['renders']
             acc['fixup_pixels'] = acc.get('fixup_pixels', 0) + t['fixup_pixels'] * t['renders']
     return acc
+
+
+DUMP_BYTES = 60_000_000   # --dump-outputs: the float32 frames written; with their index arrays the files stay under 64 MB
+DUMP_SEED = 0x19931210
+
+
+def dump_outputs(directory, items):
+    """--dump-outputs DIR: what the timed path computed in its last step, as a caller receives it -- the frames each batch holds
+    (rdoom_batch_read_framebuffer: palette indices), written as DIR/framebuffer.npy in float32.  Every pose of the step, in the
+    order of `items` (the sweep's order), when they fit in DUMP_BYTES; else a fixed seeded sample of the poses, and, should one
+    frame alone exceed it, a fixed seeded sample of its rows.  DIR/frame_index.npy holds the sampled poses' positions in the
+    step, DIR/row_index.npy the rows kept of every frame.  The same arguments give the same inputs, so two builds can be
+    compared file by file."""
+    parts, n = [], 0
+    for b, p, _l, _lop, _st in items:
+        if len(p):
+            parts.append((n, b))
+            n += len(p)
+    if not parts:
+        return
+    height, width = parts[0][1].height, parts[0][1].width
+    rng = np.random.default_rng(DUMP_SEED)
+    k = min(n, max(1, DUMP_BYTES // (4 * width * height)))
+    frames = np.arange(n) if k == n else np.sort(rng.choice(n, k, replace=False))
+    r = min(height, max(1, DUMP_BYTES // (4 * width * k)))
+    rows = np.arange(height) if r == height else np.sort(rng.choice(height, r, replace=False))
+    out = np.empty((k, r, width), np.float32)
+    for j, g in enumerate(frames):
+        lo, b = [pt for pt in parts if pt[0] <= g][-1]
+        out[j] = b.read_framebuffer(int(g) - lo, 1)[0][rows]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, 'framebuffer.npy'), out)
+    np.save(os.path.join(directory, 'frame_index.npy'), frames.astype(np.float64))
+    np.save(os.path.join(directory, 'row_index.npy'), rows.astype(np.float64))
 
 
 def texel_store_bytes(builts):
@@ -426,7 +480,7 @@ def dry_run(args, rank, world, rd, sharding, synthetic):
         dist.init_process_group('gloo')
     levels = level_list(args)
     lo, hi = sharding.shard_range(args.poses, rank, world) if args.scaling == 'strong' else (rank * args.poses, (rank + 1) * args.poses)
-    built = rd.Wad(args.iwad or (synthetic.ensure_big_wad() if args.big else synthetic.ensure_wad()),
+    built = rd.Wad(args.iwad or synthetic_wad(synthetic, 'big' if args.big else ''),
                    args.metadata or synthetic.META_PATH).build_level(levels[0])
     poses = sharding.pose_sweep(rd, built, hi - lo, args.width, args.height, first=lo)
     ranges = [None] * world
@@ -482,7 +536,7 @@ def run_threads(args):
     sharding = importlib.import_module('rust-doom_amd.sharding')
     synthetic = importlib.import_module('rust-doom_amd.synthetic')
     world, levels = args.gpus, level_list(args)
-    iwad = args.iwad or (synthetic.ensure_big_wad() if args.big else synthetic.ensure_wad())
+    iwad = args.iwad or synthetic_wad(synthetic, 'big' if args.big else '')
     meta = args.metadata or synthetic.META_PATH
     present = 0 if args.dry_run else rd.device_count()
     if not args.dry_run and present < 1:
@@ -528,6 +582,8 @@ def run_threads(args):
             steps(args.steps)
             elapsed[rank] = time.perf_counter() - t0
             barrier.wait()
+            if rank == 0 and args.dump_outputs:
+                dump_outputs(args.dump_outputs, items)
             if rank == 0:   # what rank 0 of the process launcher measures after the timed region
                 steps(args.warmup, full, True)
                 collect_kernels(full)
@@ -631,7 +687,7 @@ def main():
         name, _, value = item.partition('=')
         rd.debug_set(name, int(value or 1))
 
-    iwad = args.iwad or (synthetic.ensure_rich_wad() if args.rich else (synthetic.ensure_big_wad() if args.big else synthetic.ensure_wad()))
+    iwad = args.iwad or synthetic_wad(synthetic, 'rich' if args.rich else 'big' if args.big else '')
     meta = args.metadata or synthetic.META_PATH
     wad = rd.Wad(iwad, meta)
     levels = level_list(args)
@@ -710,6 +766,8 @@ def main():
     ends = [max(ev_start.elapsed_time(e) for e in marks) for marks in step_marks]   # ms since the start mark, per step
     step_ms = [b - a for a, b in zip([0.0] + ends[:-1], ends)]
     elapsed = sharding.max_over_ranks(elapsed_mine, dist, dist_device)
+    if args.dump_outputs and rank == 0:   # (rank 0's poses; read back before any later pass renders into the same batches)
+        dump_outputs(args.dump_outputs, work)
     # With several streams the kernels of different sub-batches run side by side: the step time above is what the metric
     # asks for, but a kernel's own duration cannot be read off overlapped events.  The same poses are therefore rendered
     # again on ONE stream (one level: as ONE batch, one launch per kernel and step; nothing overlapping), outside the timed
@@ -795,8 +853,8 @@ def main():
             'ms_per_step': round(elapsed / args.steps * 1e3, 3), 'higher_is_better': True, 'scaling': args.scaling,
             'vs_baseline': None, 'dtype': 'f32+u8 (triangle set-up f64)', 'data': 'synthetic',
             'frames_per_s': round(poses_per_step_global * args.steps / elapsed, 1),
-            # --steps K asks for AT LEAST K timed steps; the timed region is stretched to --long seconds (default 0.5: twenty steps
-            # of 4.4 ms are 88 ms, a fifth of which is the ramp of the first step) and `steps` is the number really timed
+            # --steps K times exactly K steps; with --long SECONDS the timed region is stretched to that long (twenty steps of
+            # 4.4 ms are 88 ms, a fifth of which is the ramp of the first step) and `steps` is the number really timed
             'steps_requested': steps_requested, 'timed_seconds': round(elapsed, 3),
             'config': {'workload': '%s %d-pose sweep at %dx%d %s, walls+flats+decor+sky%s'
                                    % (what, args.poses, args.width, args.height,
@@ -865,7 +923,7 @@ def main():
         # counts.  Then rank 0 ALONE renders the full batch the same way (the others wait): the one-GPU time of the same run, box and
         # library -- measured_speedup = that / the G-GPU step.
         spec = OTHER_WORKLOADS[0]
-        wad4 = rd.Wad(synthetic.ensure_wad(), synthetic.META_PATH)
+        wad4 = rd.Wad(synthetic_wad(synthetic), synthetic.META_PATH)
         line = quick_line(rd, torch, sharding, wad4, spec, args.streams, steps=20, warmup=3, kernels=False, rank=rank, world=world, dist=dist,
                           backend_device=dist_device)
         gathered = [None] * world
@@ -891,7 +949,7 @@ def main():
             for spec in OTHER_WORKLOADS:
                 key = bool(spec['big'])
                 if key not in wads:
-                    wads[key] = rd.Wad(synthetic.ensure_big_wad() if key else synthetic.ensure_wad(), synthetic.META_PATH)
+                    wads[key] = rd.Wad(synthetic_wad(synthetic, 'big' if key else ''), synthetic.META_PATH)
                 try:
                     ws = 1 if cli_streams == 1 else spec.get('streams', resolve_streams(0, len(spec['levels'])))   # (--streams 1: everything on one stream)
                     # (the line a strong-scaling share is compared with gets as many steps as the share: the first step after a
@@ -904,7 +962,7 @@ def main():
                     other_lines.append({'workload': spec['name'], 'error': repr(e)})
             if args.rich_line:   # the texture-rich stand-in (tools/mkwad.py --rich): a texel store beyond one XCD's L2
                 try:
-                    rwad = rd.Wad(synthetic.ensure_rich_wad(), synthetic.META_PATH)
+                    rwad = rd.Wad(synthetic_wad(synthetic, 'rich'), synthetic.META_PATH)
                     other_lines.append(quick_line(rd, torch, sharding, rwad, dict(name='texture-rich E1M1 stand-in (every wall and flat its own texture)', levels=[0], big=False,
                                                                                      width=1920, height=1080, poses=1024, tv=False, parity=2), 3))
                 except Exception as e:  # noqa: BLE001

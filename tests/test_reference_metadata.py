@@ -1,7 +1,7 @@
 """The reference's own metadata file (assets/meta/doom.toml: sky table, animations, linedef specials, things) read by
 the product's C++ TOML-subset reader (wad_meta.cpp, for wad/src/meta.rs) and by the oracle (tomllib): both must
-build identical levels from it.  Runs where /root/reference is mounted (this container); skipped elsewhere -- nothing
-on the GPU box reads the reference.  The file is used in place, never copied."""
+build identical levels from it.  The file is stored as a test fixture (tests/golden/doom.toml, the reference's text behind a
+provenance header), so this runs wherever the suite does."""
 import os
 
 import numpy as np
@@ -9,12 +9,11 @@ import pytest
 
 import rust_doom_amd as rd
 from oracle import wad_oracle
+from util import GOLDEN
 
-DOOM_TOML = '/root/reference/assets/meta/doom.toml'
+DOOM_TOML = os.path.join(GOLDEN, 'doom.toml')
 ARRAYS = ['static_vertices', 'static_indices', 'sky_vertices', 'sky_indices', 'decor_vertices', 'decor_indices',
           'draws', 'flat_atlas', 'wall_atlas', 'decor_atlas', 'sky_texture']
-
-pytestmark = pytest.mark.skipif(not os.path.exists(DOOM_TOML), reason='reference checkout not mounted')
 
 
 @pytest.mark.parametrize('index', [0, 3, 7])

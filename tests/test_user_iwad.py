@@ -5,7 +5,7 @@ image.  The day one is supplied:
     RDOOM_IWAD=/path/DOOM1.WAD [RDOOM_META=/path/rust-doom/assets/meta/doom.toml] python -m pytest tests/test_user_iwad.py -q -s            # CPU half
     RDOOM_IWAD=... python -m pytest tests/test_user_iwad.py -q -s -m gpu                                                                   # on an MI355X
 
-(skipped entirely unless RDOOM_IWAD is set; RDOOM_META defaults to the reference checkout's doom.toml, /root/reference/assets/meta/doom.toml;
+(skipped entirely unless RDOOM_IWAD is set; RDOOM_META defaults to the reference's doom.toml, stored as tests/golden/doom.toml;
 RDOOM_IWAD_LEVELS=0,3,8 restricts the levels.)  Per level of the file:
   * product == oracle, byte for byte: every array `game::level::Builder` hands to the renderer (wad/src/archive.rs:36-106,
     tex.rs:53-107, visitor.rs:541-1259, game/src/level.rs:275-794), counters, start, light tables;
@@ -35,7 +35,7 @@ import rust_doom_amd as rd
 from util import ROOT
 
 IWAD = os.environ.get('RDOOM_IWAD')
-META = os.environ.get('RDOOM_META', '/root/reference/assets/meta/doom.toml')
+META = os.environ.get('RDOOM_META', os.path.join(ROOT, 'tests', 'golden', 'doom.toml'))
 ARRAYS = ['static_vertices', 'static_indices', 'sky_vertices', 'sky_indices', 'decor_vertices', 'decor_indices',
           'draws', 'flat_atlas', 'wall_atlas', 'decor_atlas', 'sky_texture', 'colormap']
 COUNTERS = ('num_wall_quads', 'num_floor_polys', 'num_ceil_polys', 'num_sky_wall_quads', 'num_sky_floor_polys',

@@ -4,7 +4,7 @@
 builder (rdoom_wad_open / rdoom_wad_build_level / rdoom_built_counters) -- to be put next to the reference's own log
 (docs/RUST_CROSSCHECK.md).  No GPU needed.
 
-    python tools/print_counters.py DOOM1.WAD /root/reference/assets/meta/doom.toml [level index ...]
+    python tools/print_counters.py DOOM1.WAD tests/golden/doom.toml [level index ...]
 """
 import os
 import sys

@@ -115,7 +115,7 @@ if os.path.exists(trace):
         d = [(int(r['Start_Timestamp']), int(r['End_Timestamp']) - int(r['Start_Timestamp'])) for r in rows if key in r['Kernel_Name']]
         d.sort()
         dur = [x[1] for x in d]
-        k2 = bench.get('steps_requested', bench['steps'])  # the single-stream pass runs the requested steps (the timed region is stretched to 0.5 s)
+        k2 = bench.get('steps_requested', bench['steps'])  # the single-stream pass runs the requested steps (a --long timed region may run more)
         if len(dur) > k2:
             clean, over = dur[-k2:], dur[:-k2]
             md.append('| `%s` | %d | %.1f | %.1f |' % (key, len(dur), sum(over) / len(over) / 1e3, sum(clean) / len(clean) / 1e3))
