@@ -14,6 +14,8 @@
  *   - matrices are column-major float[16], exactly the GLSL uniforms u_modelview / u_projection
  *     (engine/src/uniforms.rs:273-280).
  *   - framebuffers are 8-bit palette indices, row 0 = bottom row (glReadPixels order), background 0.
+ *     rdoom_batch_resolve_rgb / rdoom_batch_read_rgb turn them into the colours the reference's window shows: PLAYPAL 0 of
+ *     the pose's level where a primitive was drawn, the GL clear colour RDOOM_CLEAR_R/G/B where none was.
  *   - a rdoom_level is immutable after create (shareable); a rdoom_batch is single-owner.
  */
 #ifndef RDOOM_H
@@ -103,7 +105,7 @@ typedef struct rdoom_level_desc {
   const uint16_t *sky_texture; /* game_shaders.rs:358-387 */
   uint32_t sky_w, sky_h;
   float sky_tiled_band_size;
-  const uint8_t *playpal;  /* 768 bytes, palette 0 (kept for RGB expansion by callers) */
+  const uint8_t *playpal;  /* 768 bytes, palette 0: copied to the device for rdoom_batch_resolve_rgb (NULL: that level cannot be resolved) */
   const uint8_t *colormap; /* 32*256 bytes: rows of build_palette_texture(0,0,32) before the PLAYPAL map (tex.rs:137-166) */
 } rdoom_level_desc;
 
@@ -243,6 +245,29 @@ rdoom_status rdoom_batch_framebuffer_pitch(const rdoom_batch *batch, uint32_t *o
 /* glReadPixels analogue: waits for the batch's last render (on its stream -- not for the device), copies frames
  * [first, first+count) to host memory, tightly packed (width bytes per row) */
 rdoom_status rdoom_batch_read_framebuffer(rdoom_batch *batch, uint32_t first, uint32_t count, uint8_t *host_out);
+/* RGB frames, as the reference's window shows them: its shaders end in texture(u_palette, ...).rgb (PLAYPAL 0) and the pixels
+ * no primitive covers keep the clear colour (0.06, 0.07, 0.09) of window.rs:40-44, i.e. (15, 18, 23) as 8-bit UNORM.  A pixel is
+ * clear exactly where rdoom_batch_read_primitive_ids would report 0xFFFFFFFF.  format = RDOOM_RGB8 or RDOOM_RGBA8, optionally
+ * | RDOOM_RGB_TOP_DOWN.  Rows are tight (width * bytes per pixel, no padding); row 0 is the bottom row (glReadPixels order)
+ * unless RDOOM_RGB_TOP_DOWN.  RGBA8: alpha 255 where a primitive was drawn (the shaders write vec3: opaque), 0 where the clear
+ * colour shows (its alpha, window.rs:42).  Poses of a level whose desc had no playpal cannot be resolved (RDOOM_BAD_ARG). */
+#define RDOOM_RGB8 3u          /* 3 bytes per pixel */
+#define RDOOM_RGBA8 4u         /* 4 bytes per pixel, alpha 255 drawn / 0 clear */
+#define RDOOM_RGB_TOP_DOWN 0x100u /* row 0 = the top row (default: the bottom row, glReadPixels order) */
+#define RDOOM_CLEAR_R 15u      /* window.rs:40-44 clear colour as 8-bit UNORM */
+#define RDOOM_CLEAR_G 18u
+#define RDOOM_CLEAR_B 23u
+/* Asynchronous, on `stream` (a hipStream_t, may be NULL): waits for the batch's last render, writes frames [first, first+count)
+ * of it to device_out -- count * height * width * bytes-per-pixel bytes of device memory on the batch's device -- and
+ * rdoom_batch_finish / the rdoom_batch_read_* then wait for it too.  The next render of this batch overwrites what the resolve
+ * reads: order it after the resolve (the same stream, or after rdoom_batch_finish).  Errors the device finds in the render are
+ * reported by rdoom_batch_finish. */
+rdoom_status rdoom_batch_resolve_rgb(rdoom_batch *batch, uint32_t first, uint32_t count, uint32_t format, void *device_out,
+                                     void *stream);
+/* Synchronous: the same frames copied to host memory (count * height * width * bytes-per-pixel bytes), resolved in chunks of
+ * frames through a bounded staging buffer the batch allocates on first use; reports the render's device errors like
+ * rdoom_batch_read_framebuffer. */
+rdoom_status rdoom_batch_read_rgb(rdoom_batch *batch, uint32_t first, uint32_t count, uint32_t format, uint8_t *host_out);
 /* Debug / test facility: capture the winning primitive id per pixel (triangle index in the draw order of the pose's level,
  * 0xFFFFFFFF = none) on the following renders, then read it back.  No GL counterpart. */
 rdoom_status rdoom_batch_enable_primitive_ids(rdoom_batch *batch);

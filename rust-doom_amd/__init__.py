@@ -21,6 +21,9 @@ LIB_PATH = os.path.join(_HERE, 'librdoom_hip.so')
 KIND_FLAT, KIND_WALL, KIND_DECOR, KIND_SKY = 0, 1, 2, 3
 ALL_KINDS = 0xF
 NO_PRIMITIVE = 0xFFFFFFFF
+# rdoom_batch_resolve_rgb / rdoom_batch_read_rgb formats (include/rdoom.h); CLEAR_RGB: the GL clear colour (window.rs:40-44)
+RGB8, RGBA8, RGB_TOP_DOWN = 3, 4, 0x100
+CLEAR_RGB = (15, 18, 23)
 
 STATIC_VERTEX = np.dtype([('a_pos', '<f4', 3), ('a_atlas_uv', '<f4', 2), ('a_tile_uv', '<f4', 2),
                           ('a_tile_size', '<f4', 2), ('a_scroll_rate', '<f4'), ('a_row_height', '<f4'),
@@ -87,7 +90,7 @@ API_SYMBOLS = [
     'rdoom_built_counters', 'rdoom_built_lights_at', 'rdoom_built_start', 'rdoom_built_floor_centroids',
     'rdoom_pose_look', 'rdoom_selftest_fastmath', 'rdoom_debug_set', 'rdoom_wad_walk', 'rdoom_wad_build_level_chained', 'rdoom_batch_render_objects', 'rdoom_level_num_objects', 'rdoom_batch_enable_primitive_ids',
     'rdoom_wad_timings', 'rdoom_built_timings', 'rdoom_pose_from_player', 'rdoom_batch_framebuffer_pitch', 'rdoom_batch_path_stats',
-    'rdoom_levelset_create', 'rdoom_level_num_levels', 'rdoom_batch_render_levels']
+    'rdoom_levelset_create', 'rdoom_level_num_levels', 'rdoom_batch_render_levels', 'rdoom_batch_resolve_rgb', 'rdoom_batch_read_rgb']
 
 _lib = None
 
@@ -567,6 +570,43 @@ class Batch:
         count = self.last_n - first if count is None else count
         out = np.zeros((count, self.height, self.width), np.uint8)
         _check(lib().rdoom_batch_read_framebuffer(self._h, int(first), int(count), out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def _rgb_args(self, first, count, alpha, top_down):
+        count = self.last_n - first if count is None else count
+        fmt = (RGBA8 if alpha else RGB8) | (RGB_TOP_DOWN if top_down else 0)
+        return int(first), int(count), fmt, (int(count), self.height, self.width, 4 if alpha else 3)
+
+    def read_rgb(self, first=0, count=None, alpha=False, top_down=False):
+        """rdoom_batch_read_rgb: frames [first, first+count) of the last render as (count, H, W, 3) RGB8 -- (.., 4) RGBA8 with
+        alpha=True (255 drawn, 0 clear) -- PLAYPAL 0 where a primitive was drawn, CLEAR_RGB elsewhere; row 0 = the bottom row
+        (glReadPixels order) unless top_down"""
+        first, count, fmt, shape = self._rgb_args(first, count, alpha, top_down)
+        out = np.zeros(shape, np.uint8)
+        _check(lib().rdoom_batch_read_rgb(self._h, first, count, fmt, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def resolve_rgb(self, out, first=0, count=None, alpha=False, top_down=False, stream=None):
+        """rdoom_batch_resolve_rgb: the same frames written to device memory, asynchronously on `stream` (a hipStream_t handle,
+        or a torch stream; None = the null stream).  out: a raw device pointer (int) of count*H*W*(3|4) bytes, or a contiguous
+        uint8 torch tensor of that many elements on the batch's device.  Returns out."""
+        first, count, fmt, shape = self._rgb_args(first, count, alpha, top_down)
+        if isinstance(out, int):
+            ptr = out
+        else:
+            import torch  # (only here: the package imports without torch)
+            if not isinstance(out, torch.Tensor):
+                raise TypeError('out must be a device pointer (int) or a torch tensor, not %s' % type(out).__name__)
+            if out.dtype != torch.uint8 or not out.is_contiguous() or out.device.type != 'cuda':
+                raise ValueError('out must be a contiguous torch.uint8 tensor on the GPU (got %s, %s, contiguous=%s)'
+                                 % (out.dtype, out.device, out.is_contiguous()))
+            need = int(np.prod(shape))
+            if out.numel() != need:
+                raise ValueError('out has %d elements, frames %d..%d need %s = %d' % (out.numel(), first, first + count, shape, need))
+            ptr = out.data_ptr()  # (the library checks that it lives on the batch's device)
+        if stream is not None and not isinstance(stream, int):
+            stream = stream.cuda_stream
+        _check(lib().rdoom_batch_resolve_rgb(self._h, first, count, fmt, ctypes.c_void_p(ptr or None), ctypes.c_void_p(stream or 0)))
         return out
 
     def enable_primitive_ids(self):

@@ -65,4 +65,24 @@ rdoom_status launch_fragment(hipStream_t st, uint32_t n_poses, const DeviceLevel
                              bool *frag_const_ready, const FragmentPlan &plan);  // d_frag_const: fragment_const_bytes() of device memory owned by the batch
 size_t fragment_const_bytes();
 
+// Kernels 5 + 6: frames [first, first + count) of the last render -> RGB8 / RGBA8, then the pixels of the fixup list (resolve.hip)
+struct ResolveArgs {
+  const uint8_t *fb;
+  const void *vis;
+  bool vis16;
+  const uint32_t *qtab;
+  bool use_qtab;  // the render's FragmentPlan::skip_described_vis: a described quadrant's visibility words are stale
+  const PoseConst *poses;
+  const uint32_t *palettes;  // per level of the set: 256 words R | G << 8 | B << 16 | 0xFF << 24
+  const uint32_t *fix_count;
+  const uint2 *fix_list;
+  uint32_t fix_cap;
+  uint32_t first, count;
+  int width, pitch, height;
+  uint32_t bpp;  // 3 or 4
+  bool top_down;
+  uint8_t *out;  // count x height x width x bpp bytes
+};
+rdoom_status launch_resolve(hipStream_t st, const ResolveArgs &args);
+
 }  // namespace rdoom_dev

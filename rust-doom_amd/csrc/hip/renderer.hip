@@ -47,6 +47,10 @@ struct rdoom_level {
   std::vector<uint32_t> slice_objects; // 1 + the largest object id each level draws
   uint32_t ntri = 0;        // the LARGEST level's triangle count: a pose's records and visible list have this stride
   uint32_t n_objects = 1;   // 1 + the largest object id any level of the set draws
+  // PLAYPAL 0 of every level, 256 words R | G << 8 | B << 16 | 0xFF << 24 per level: read by the resolve kernels only (they take it
+  // as an argument of their own, so no struct another kernel takes by value carries it)
+  uint32_t *d_palettes = nullptr;
+  std::vector<uint8_t> has_palette;  // the level's desc had a playpal (else its poses cannot be resolved to RGB)
 };
 
 struct rdoom_batch {
@@ -100,6 +104,10 @@ struct rdoom_batch {
   bool want_prim = false;
   bool vis16 = false;  // record indices fit 16 bits: visibility words are u16
   float *d_ndc = nullptr;  // (ix + 0.5) / (width / 2) - 1 for every column, then (iy + 0.5) / (height / 2) - 1 for every row
+  // the last render's FragmentPlan::skip_described_vis: a described quadrant's visibility words are another render's (resolve reads the table)
+  bool last_skip_vis = false;
+  uint8_t *d_rgb = nullptr;  // rdoom_batch_read_rgb's staging (allocated on first use, at most RGB_STAGING_BYTES or one frame)
+  size_t rgb_bytes = 0;
 };
 
 // Every entry point that touches a batch's memory or waits for its work first makes the level's device current: a host
@@ -146,7 +154,7 @@ rdoom_status rdoom_set_device(int32_t device) {
 
 void rdoom_level_destroy(rdoom_level *level) {
   if (!level) return;
-  for (void *p : {level->d_clusters, level->d_tris, level->d_texels, level->d_sky, level->d_cmap, level->d_slices})
+  for (void *p : {level->d_clusters, level->d_tris, level->d_texels, level->d_sky, level->d_cmap, level->d_slices, (void *)level->d_palettes})
     if (p) (void)hipFree(p);
   delete level;
 }
@@ -418,6 +426,18 @@ static rdoom_status levelset_create_impl(const rdoom_level_desc *const *descs, u
   if (e == hipSuccess) e = upload(&lv->d_sky, sky.data(), sky.size() * 2);
   if (e == hipSuccess) e = upload(&lv->d_cmap, descs[0]->colormap, 32 * 256);
   if (e == hipSuccess) e = upload(&lv->d_slices, lv->slices.data(), lv->slices.size() * sizeof(LevelSlice));
+  {  // PLAYPAL 0 of each level (no rule that they match: a level without one is created as before and cannot be resolved)
+    std::vector<uint32_t> pal((size_t)n_levels * 256u, 0u);
+    lv->has_palette.assign(n_levels, 0);
+    for (uint32_t k = 0; k < n_levels; k++) {
+      const uint8_t *pp = descs[k]->playpal;
+      if (!pp) continue;
+      lv->has_palette[k] = 1;
+      for (uint32_t i = 0; i < 256u; i++)
+        pal[(size_t)k * 256u + i] = (uint32_t)pp[3 * i] | ((uint32_t)pp[3 * i + 1] << 8) | ((uint32_t)pp[3 * i + 2] << 16) | 0xFF000000u;
+    }
+    if (e == hipSuccess) e = upload((void **)&lv->d_palettes, pal.data(), pal.size() * sizeof(uint32_t));
+  }
   if (e != hipSuccess) {
     rdoom_level_destroy(lv);
     return rdoom::fail(e == hipErrorOutOfMemory ? RDOOM_OOM : RDOOM_HIP_ERROR, "level upload failed: %s",
@@ -451,7 +471,7 @@ void rdoom_batch_destroy(rdoom_batch *b) {
 #endif
   for (void *p : {(void *)b->d_poses, (void *)b->d_recs, (void *)b->d_visible, (void *)b->d_tile_hdr, (void *)b->d_entries, (void *)b->d_hits,
                   (void *)b->d_overflow, (void *)b->d_zeroed, (void *)b->d_fix_list, (void *)b->d_vis,
-                  (void *)b->d_prim, (void *)b->d_fb, (void *)b->d_qtab, b->d_frag_const})
+                  (void *)b->d_prim, (void *)b->d_fb, (void *)b->d_qtab, b->d_frag_const, (void *)b->d_rgb})
     if (p) (void)hipFree(p);
   for (auto &e : b->ev)
     if (e) (void)hipEventDestroy(e);
@@ -660,6 +680,7 @@ static rdoom_status render_impl(rdoom_batch *b, const rdoom_pose *poses, const u
   uint32_t *prim_out = b->want_prim ? b->d_prim : nullptr;
   // one reading of the debug hooks for both kernels: who writes and who reads visibility words must not change in between
   const FragmentPlan plan = plan_fragment(W, PITCH, H, b->d_qtab != nullptr);
+  b->last_skip_vis = plan.skip_described_vis;
   // (the rasteriser's frame is PITCH pixels wide: the padding columns of a width that is not a multiple of 4 are pixels no
   // bounding box reaches -- they stay uncovered, and the quadrants they lie in simply never count as covered)
   if (rdoom_status rs = launch_raster(st, n, lv->view, b->d_recs, b->d_counts, b->cap, PITCH, H, tiles_x, tiles_y,
@@ -868,6 +889,83 @@ rdoom_status rdoom_batch_read_primitive_ids(rdoom_batch *b, uint32_t first, uint
   HIP_TRY(bind_device(b));
   if (count)
     HIP_TRY(read_back(b, host_out, b->d_prim + frame * first, sizeof(uint32_t) * b->width, (size_t)b->height * count, sizeof(uint32_t) * b->pitch));
+  return RDOOM_OK;
+}
+
+// ---- RGB resolve (resolve.hip) --------------------------------------------------------------------------------------
+// rdoom_batch_read_rgb's staging holds as many whole frames as fit in this (at least one)
+static constexpr size_t RGB_STAGING_BYTES = (size_t)64 << 20;
+
+// what both RGB entry points reject before they touch the device or wait for anything
+static rdoom_status rgb_args(const rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, const void *out) {
+  if (format & ~(0xFFu | (uint32_t)RDOOM_RGB_TOP_DOWN)) return rdoom::fail(RDOOM_BAD_ARG, "unknown format bits 0x%x", format);
+  if ((format & 0xFFu) != RDOOM_RGB8 && (format & 0xFFu) != RDOOM_RGBA8)
+    return rdoom::fail(RDOOM_BAD_ARG, "format 0x%x: RDOOM_RGB8 or RDOOM_RGBA8, optionally | RDOOM_RGB_TOP_DOWN", format);
+  if (!b || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (b->last_n == 0) return rdoom::fail(RDOOM_BAD_ARG, "nothing rendered yet");
+  if ((uint64_t)first + count > b->last_n) return rdoom::fail(RDOOM_BAD_ARG, "frame range outside the last render");
+  const rdoom_level *lv = b->level;
+  if (std::find(lv->has_palette.begin(), lv->has_palette.end(), 0) != lv->has_palette.end()) {
+    // the levels of the last render's poses: its pinned staging (the next render writes the other one)
+    const PoseConst *pc = b->h_poses[(b->stage + rdoom_batch::STAGES - 1u) % rdoom_batch::STAGES];
+    for (uint32_t p = first; p < first + count; p++)
+      if (!lv->has_palette[pc[p].level]) return rdoom::fail(RDOOM_BAD_ARG, "pose %u: its level %u was created without a playpal", p, pc[p].level);
+  }
+  return RDOOM_OK;
+}
+
+// queues the two resolve kernels on st behind the last render; ev_done then marks their end (finish / read_* wait for it)
+static rdoom_status resolve_impl(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint8_t *out, hipStream_t st) {
+  HIP_TRY(hipStreamWaitEvent(st, b->ev_done, 0));
+  ResolveArgs a{};
+  a.fb = b->d_fb, a.vis = b->d_vis, a.vis16 = b->vis16, a.qtab = b->d_qtab, a.use_qtab = b->last_skip_vis, a.poses = b->d_poses;
+  a.palettes = b->level->d_palettes, a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list, a.fix_cap = b->fix_cap;
+  a.first = first, a.count = count, a.width = (int)b->width, a.pitch = (int)b->pitch, a.height = (int)b->height;
+  a.bpp = format & 0xFFu, a.top_down = (format & RDOOM_RGB_TOP_DOWN) != 0u, a.out = out;
+  const rdoom_status rs = launch_resolve(st, a);
+  HIP_TRY(hipEventRecord(b->ev_done, st));  // (also after a failed launch: nothing waits for a render that is not the last)
+  return rs;
+}
+
+rdoom_status rdoom_batch_resolve_rgb(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, void *device_out, void *stream) {
+  if (rdoom_status rs = rgb_args(b, first, count, format, device_out)) return rs;
+  HIP_TRY(bind_device(b));
+  // device_out must be device memory of the batch's device with room for the frames: the kernels write there
+  const size_t bytes = (size_t)count * b->height * b->width * (format & 0xFFu);
+  hipPointerAttribute_t attr{};
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipPointerGetAttributes(&attr, device_out) != hipSuccess || attr.type != hipMemoryTypeDevice ||
+      hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)device_out) != hipSuccess) {
+    (void)hipGetLastError();  // (a failed query must not be reported by the next render's launch check)
+    return rdoom::fail(RDOOM_BAD_ARG, "device_out is not device memory");
+  }
+  if (attr.device != b->level->device) return rdoom::fail(RDOOM_BAD_ARG, "device_out is on device %d, the batch on %d", attr.device, b->level->device);
+  if ((const char *)device_out + bytes > (const char *)base + size)
+    return rdoom::fail(RDOOM_BAD_ARG, "device_out: %zu bytes needed, its allocation ends %zu bytes after it", bytes,
+                       (size_t)((const char *)base + size - (const char *)device_out));
+  return resolve_impl(b, first, count, format, (uint8_t *)device_out, (hipStream_t)stream);
+}
+
+rdoom_status rdoom_batch_read_rgb(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint8_t *host_out) {
+  if (rdoom_status rs = rgb_args(b, first, count, format, host_out)) return rs;
+  HIP_TRY(bind_device(b));
+  if (rdoom_status fs = device_flags(b)) return fs;
+  if (count == 0) return RDOOM_OK;
+  const size_t frame = (size_t)b->height * b->width * (format & 0xFFu);
+  const uint32_t chunk = (uint32_t)std::max<size_t>(1u, std::min<size_t>(count, RGB_STAGING_BYTES / frame));
+  if (b->rgb_bytes < chunk * frame) {
+    if (b->d_rgb) HIP_TRY(hipFree(b->d_rgb));
+    b->d_rgb = nullptr, b->rgb_bytes = 0;
+    HIP_TRY(hipMalloc((void **)&b->d_rgb, chunk * frame));
+    b->rgb_bytes = chunk * frame;
+  }
+  for (uint32_t f = first; f < first + count; f += chunk) {
+    const uint32_t n = std::min(chunk, first + count - f);
+    if (rdoom_status rs = resolve_impl(b, f, n, format, b->d_rgb, b->copy_stream)) return rs;
+    HIP_TRY(hipMemcpyAsync(host_out + (size_t)(f - first) * frame, b->d_rgb, n * frame, hipMemcpyDeviceToHost, b->copy_stream));
+    HIP_TRY(hipStreamSynchronize(b->copy_stream));
+  }
   return RDOOM_OK;
 }
 
