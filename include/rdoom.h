@@ -6,6 +6,7 @@
  *
  *   loader + builder  (host C++, mirrors `wad` + `game::level`):   rdoom_wad_*, rdoom_built_*
  *   device renderer   (hand-written HIP, gfx950):                   rdoom_level_*, rdoom_batch_*
+ *   collision world + player physics (host builder, HIP kernels):   rdoom_world_*, rdoom_player_*
  *
  * Conventions
  *   - every function returns rdoom_status (0 = ok, <0 = error); rdoom_last_error() gives a
@@ -404,6 +405,88 @@ rdoom_status rdoom_pose_look(const float eye[3], float yaw, float pitch, uint32_
  * units in the last place (tests/test_pose_helpers.py). */
 rdoom_status rdoom_pose_from_player(const float pos[3], float yaw, float pitch, uint32_t width, uint32_t height, float time,
                                     rdoom_pose *out);
+
+/* ---- collision world + player physics: game::world::World and game::player::Player --------------------------------
+ * The reference's camera is the head of a player that walks, falls, jumps and slides along walls: each 60 Hz tick
+ * Player::update (game/src/player.rs:359-408) sweeps spheres through the collision volume World (game/src/world.rs), built
+ * by WorldBuilder from the same level walk as the renderer's Builder (game/src/level.rs:378-382).  Here a rdoom_world holds
+ * that volume on the host and the current device; N players step K ticks in ONE launch.
+ * Arithmetic: binary32, no contraction, IEEE division and sqrt; the sine / cosine of yaw and pitch come from a project-owned
+ * binary32 sincos (csrc/hip/world.hip), not the device libm, so a step is reproducible bit for bit on any IEEE host. */
+typedef struct rdoom_world rdoom_world;
+typedef struct rdoom_world_node {      /* world.rs:139-143 Node: partition Line2f + Child::pack'ed children (world.rs:152-163): */
+  float origin[2], displace[2], length; /* > 0 a node index, <= 0 minus a chunk index; never linked = 0 = Leaf(0), as the reference */
+  int32_t positive, negative;
+} rdoom_world_node;
+typedef struct rdoom_world_chunk { uint32_t tri_start, tri_end; } rdoom_world_chunk;          /* world.rs:124-128 */
+typedef struct rdoom_world_triangle { uint32_t v1, v2, v3, normal; } rdoom_world_triangle;    /* world.rs:135-141: vertex indices */
+typedef struct rdoom_world_dynamic { uint32_t object_id, tri_start, tri_end; } rdoom_world_dynamic; /* DynamicChunk, world.rs:212-237 */
+/* borrowed pointers into a rdoom_world (valid until rdoom_world_destroy) */
+typedef struct rdoom_world_arrays {
+  const rdoom_world_node *nodes;
+  uint32_t n_nodes;
+  const rdoom_world_chunk *chunks;
+  uint32_t n_chunks;
+  const rdoom_world_triangle *triangles; /* the static world's n_static_triangles, then each dynamic chunk's (WorldBuilder::build) */
+  uint32_t n_triangles, n_static_triangles;
+  const float *verts;                    /* xyz triples */
+  uint32_t n_verts;
+  const rdoom_world_dynamic *dynamics;   /* by ascending object_id; only objects that have collision triangles */
+  uint32_t n_dynamics;
+  uint32_t n_objects;                    /* 1 + the largest object_id of a dynamic chunk (1 when there is none) */
+  uint32_t node_depth;                   /* nodes on the longest root-to-node path (sizes the sweep's node stack) */
+} rdoom_world_arrays;
+
+/* Player { velocity, fly, clip, last_height_diff } + the player entity's transform (player.rs:107-113, 118-133), 40 bytes.
+ * Orientation is (yaw, pitch), as rdoom_pose_from_player takes it.  flags: RDOOM_PLAYER_FLY / RDOOM_PLAYER_CLIP are the
+ * caller's (the reference's defaults: fly off, clip on, player.rs:347-353); RDOOM_PLAYER_DIVERGED is set by a step in which
+ * the collision loop ran 100 sweeps without settling -- the reference's error!("Failed to compute collisions.")
+ * (player.rs:162-165) -- and is never cleared by the library. */
+#define RDOOM_PLAYER_FLY 1u
+#define RDOOM_PLAYER_CLIP 2u
+#define RDOOM_PLAYER_DIVERGED 0x100u
+typedef struct rdoom_player_state {
+  float pos[3], vel[3], yaw, pitch, last_height_diff;
+  uint32_t flags;
+} rdoom_player_state;
+/* One tick's input: what Input::poll_analog2d(movement / look) and poll_gesture(jump) return (player.rs:190-192). */
+typedef struct rdoom_player_input {
+  float movement[2], look[2];
+  uint32_t jump; /* != 0: held */
+} rdoom_player_input;
+/* player.rs:56-92 Config, the physics half */
+typedef struct rdoom_player_config {
+  float move_force, spring_const_p, spring_const_d, radius, height, air_drag, ground_drag, friction;
+} rdoom_player_config;
+
+/* WorldBuilder::new, LevelWalker::walk, WorldBuilder::build (world.rs:211-409, level.rs:378-382), then the arrays are copied to
+ * the current device.  flags: RDOOM_WORLD_HOST_ONLY builds the host arrays only (no device is touched; rdoom_world_sweep /
+ * rdoom_world_step_players then return RDOOM_BAD_ARG).  A level without BSP nodes is RDOOM_BAD_LEVEL, and so is a tree deeper
+ * than RDOOM_WORLD_MAX_DEPTH nodes (the sweep's node stack lives in LDS, sized by the tree's depth). */
+#define RDOOM_WORLD_HOST_ONLY 1u
+#define RDOOM_WORLD_MAX_DEPTH 255u
+rdoom_status rdoom_world_create(const rdoom_wad *wad, uint32_t level_index, uint32_t flags, rdoom_world **out_world);
+void rdoom_world_destroy(rdoom_world *world);
+rdoom_status rdoom_world_host_arrays(const rdoom_world *world, rdoom_world_arrays *out);
+/* World::sweep_sphere (world.rs:40-82, math/src/sphere.rs:16-183) for n queries at once, asynchronous on `stream` (a
+ * hipStream_t, may be NULL); every pointer is device memory.  d_spheres: n x (cx, cy, cz, radius); d_vels: n x (x, y, z);
+ * d_out: n x (time, nx, ny, nz), time = +inf where the reference returns None.  d_object_offsets: NULL (every object at rest),
+ * or n x n_objects x (x, y, z): query q sees object o displaced by entry [q][o] (entry 0, the static world, is ignored) -- the
+ * `disp` that game/src/level.rs:203-255 moves; n_objects >= the world's.  Captured into a graph, it allocates and waits on nothing. */
+rdoom_status rdoom_world_sweep(const rdoom_world *world, const float *d_spheres, const float *d_vels, uint32_t n,
+                               const float *d_object_offsets, uint32_t n_objects, void *stream, float *d_out);
+/* n_ticks ticks of Player::update (player.rs:359-408: force() with the feet probe and move_force, then clip() or noclip(),
+ * then velocity += force * dt) for n_players players in one launch, asynchronous on `stream`.  d_states (device) is read and
+ * written in place; d_inputs (device): n_ticks x n_players, entry [t * n_players + p] is player p's input at tick t.
+ * cfg: NULL = rdoom_player_config_default.  dt: the tick (0 = 1/60, engine Tick's timestep).  d_object_offsets: as for
+ * rdoom_world_sweep, per player (constant over the ticks).  The look update is yaw -= look.x,
+ * pitch = clamp(pitch - look.y, +-(pi/2 - 1e-2)) -- in exact arithmetic the reference's quaternion composition
+ * (player.rs:194-205).  Triggers, teleports and level changes are not simulated. */
+rdoom_status rdoom_world_step_players(const rdoom_world *world, rdoom_player_state *d_states, const rdoom_player_input *d_inputs,
+                                      uint32_t n_players, uint32_t n_ticks, const rdoom_player_config *cfg, float dt,
+                                      const float *d_object_offsets, uint32_t n_objects, void *stream);
+/* Config::default (player.rs:73-92) */
+rdoom_status rdoom_player_config_default(rdoom_player_config *out);
 
 #ifdef __cplusplus
 }

@@ -33,6 +33,16 @@ SPRITE_VERTEX = np.dtype([('a_pos', '<f4', 3), ('a_atlas_uv', '<f4', 2), ('a_til
                           ('a_light', 'u1'), ('_pad', 'u1', 2)])
 POSE = np.dtype([('modelview', '<f4', 16), ('projection', '<f4', 16), ('time', '<f4'), ('_pad', '<f4')])
 assert STATIC_VERTEX.itemsize == 48 and SPRITE_VERTEX.itemsize == 44 and POSE.itemsize == 136
+# the collision world + player physics (include/rdoom.h): Player's state with the entity's position and (yaw, pitch), one tick's
+# input as Input::poll_analog2d / poll_gesture return it (game/src/player.rs:107-113, 190-192), Config's physics half (:56-92)
+PLAYER_STATE = np.dtype([('pos', '<f4', 3), ('vel', '<f4', 3), ('yaw', '<f4'), ('pitch', '<f4'), ('last_height_diff', '<f4'),
+                         ('flags', '<u4')])
+PLAYER_INPUT = np.dtype([('movement', '<f4', 2), ('look', '<f4', 2), ('jump', '<u4')])
+PLAYER_CONFIG = np.dtype([(n, '<f4') for n in ('move_force', 'spring_const_p', 'spring_const_d', 'radius', 'height', 'air_drag',
+                                               'ground_drag', 'friction')])
+PLAYER_FLY, PLAYER_CLIP, PLAYER_DIVERGED = 1, 2, 0x100
+WORLD_HOST_ONLY = 1
+assert PLAYER_STATE.itemsize == 40 and PLAYER_INPUT.itemsize == 20 and PLAYER_CONFIG.itemsize == 32
 
 
 class RdoomError(RuntimeError):
@@ -90,7 +100,9 @@ API_SYMBOLS = [
     'rdoom_built_counters', 'rdoom_built_lights_at', 'rdoom_built_start', 'rdoom_built_floor_centroids',
     'rdoom_pose_look', 'rdoom_selftest_fastmath', 'rdoom_debug_set', 'rdoom_wad_walk', 'rdoom_wad_build_level_chained', 'rdoom_batch_render_objects', 'rdoom_level_num_objects', 'rdoom_batch_enable_primitive_ids',
     'rdoom_wad_timings', 'rdoom_built_timings', 'rdoom_pose_from_player', 'rdoom_batch_framebuffer_pitch', 'rdoom_batch_path_stats',
-    'rdoom_levelset_create', 'rdoom_level_num_levels', 'rdoom_batch_render_levels', 'rdoom_batch_resolve_rgb', 'rdoom_batch_read_rgb']
+    'rdoom_levelset_create', 'rdoom_level_num_levels', 'rdoom_batch_render_levels', 'rdoom_batch_resolve_rgb', 'rdoom_batch_read_rgb',
+    'rdoom_world_create', 'rdoom_world_destroy', 'rdoom_world_host_arrays', 'rdoom_world_sweep', 'rdoom_world_step_players',
+    'rdoom_player_config_default']
 
 _lib = None
 
@@ -107,7 +119,7 @@ def lib():
         for name in API_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ('rdoom_last_error', 'rdoom_level_destroy', 'rdoom_batch_destroy', 'rdoom_wad_close',
-                            'rdoom_built_destroy'):
+                            'rdoom_built_destroy', 'rdoom_world_destroy'):
                 fn.restype = ctypes.c_int32
             elif name != 'rdoom_last_error':
                 fn.restype = None
@@ -326,6 +338,10 @@ class Wad:
     def build_level(self, index, gpu_tessellation=False, visitor=None):
         """visitor: an object with LevelVisitor methods, chained after the Builder (game/src/level.rs:378-382)"""
         return BuiltLevel(self, index, gpu_tessellation, visitor)
+
+    def build_world(self, index, device=True):
+        """game::world::WorldBuilder over level `index` (game/src/world.rs:211-409) -> World; device=False keeps it on the host"""
+        return World(self, index, device)
 
     def walk(self, index, visitor):
         """WadSystem::walk (game/src/wad_system.rs:47-56) with the caller's visitor only"""
@@ -618,3 +634,156 @@ class Batch:
         _check(lib().rdoom_batch_read_primitive_ids(self._h, int(first), int(count),
                                                     out.ctypes.data_as(ctypes.c_void_p)))
         return out
+
+
+# ---- the collision world + player physics (include/rdoom.h: rdoom_world_*, rdoom_player_*) ----------------------------------
+class WorldArrays(ctypes.Structure):
+    _fields_ = [('nodes', ctypes.c_void_p), ('n_nodes', ctypes.c_uint32), ('chunks', ctypes.c_void_p), ('n_chunks', ctypes.c_uint32),
+                ('triangles', ctypes.c_void_p), ('n_triangles', ctypes.c_uint32), ('n_static_triangles', ctypes.c_uint32),
+                ('verts', ctypes.c_void_p), ('n_verts', ctypes.c_uint32), ('dynamics', ctypes.c_void_p), ('n_dynamics', ctypes.c_uint32),
+                ('n_objects', ctypes.c_uint32), ('node_depth', ctypes.c_uint32)]
+
+
+WORLD_NODE = np.dtype([('origin', '<f4', 2), ('displace', '<f4', 2), ('length', '<f4'), ('positive', '<i4'), ('negative', '<i4')])
+
+
+def player_config_default():
+    """rdoom_player_config_default: Config::default's physics half (game/src/player.rs:73-92) as a PLAYER_CONFIG record"""
+    cfg = np.zeros(1, PLAYER_CONFIG)
+    _check(lib().rdoom_player_config_default(cfg.ctypes.data_as(ctypes.c_void_p)))
+    return cfg[0]
+
+
+def player_states(positions, yaws, pitch=1e-8, flags=PLAYER_CLIP):
+    """PLAYER_STATE records at rest, as Player::reset leaves them (player.rs:118-133: pitch 1e-8, no velocity); flags: PLAYER_CLIP
+    (the reference's default) and / or PLAYER_FLY, a scalar or one per player"""
+    pos = np.asarray(positions, np.float32).reshape(-1, 3)
+    out = np.zeros(len(pos), PLAYER_STATE)
+    out['pos'] = pos
+    out['yaw'] = np.broadcast_to(np.asarray(yaws, np.float32), len(pos))
+    out['pitch'] = np.broadcast_to(np.asarray(pitch, np.float32), len(pos))
+    out['flags'] = np.broadcast_to(np.asarray(flags, np.uint32), len(pos))
+    return out
+
+
+def poses_from_players(states, width, height, time=0.0):
+    """the camera of every player (rdoom_pose_from_player: the head at pos + 0.12, rotated by (yaw, pitch)) as a POSE array --
+    step, then this, then Batch.render"""
+    states = np.asarray(states, PLAYER_STATE).reshape(-1)
+    return np.array([pose_from_player(s['pos'], float(s['yaw']), float(s['pitch']), width, height, time) for s in states], POSE)
+
+
+def _stream_handle(stream):
+    if stream is None or isinstance(stream, int):
+        return stream or 0
+    return stream.cuda_stream
+
+
+def _device_tensor(a, what):
+    """(device pointer, keepalive, is_numpy): a torch tensor on the GPU is used as it is; a numpy array is copied to the current one"""
+    import torch  # (only here: the package imports without torch)
+    if isinstance(a, torch.Tensor):
+        if a.device.type != 'cuda' or not a.is_contiguous():
+            raise ValueError('%s must be a contiguous tensor on the GPU (got %s, contiguous=%s)' % (what, a.device, a.is_contiguous()))
+        return a.data_ptr(), a, False
+    raw = np.ascontiguousarray(a)
+    t = torch.from_numpy(raw.view(np.uint8).reshape(-1).copy()).cuda()
+    return t.data_ptr(), t, True
+
+
+class World:
+    """game::world::World on the host and the current device (rdoom_world_create): World::sweep_sphere for a batch of queries,
+    Player::update for a batch of players."""
+
+    def __init__(self, wad, index, device=True):
+        self._h = ctypes.c_void_p()
+        self._wad = wad
+        _check(lib().rdoom_world_create(wad._h, int(index), 0 if device else WORLD_HOST_ONLY, ctypes.byref(self._h)))
+        a = WorldArrays()
+        _check(lib().rdoom_world_host_arrays(self._h, ctypes.byref(a)))
+        self.n_objects, self.node_depth = a.n_objects, a.node_depth
+
+    def close(self):
+        if self._h:
+            lib().rdoom_world_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        _close_quietly(self)
+
+    def arrays(self):
+        """copies of rdoom_world_host_arrays: nodes (WORLD_NODE), chunks (n, 2), triangles (n, 4), verts (n, 3), dynamics (n, 3:
+        object id, first triangle, end), n_static_triangles, n_objects, node_depth"""
+        a = WorldArrays()
+        _check(lib().rdoom_world_host_arrays(self._h, ctypes.byref(a)))
+        v = BuiltLevel._view
+        return dict(nodes=v(None, a.nodes, a.n_nodes, WORLD_NODE), chunks=v(None, a.chunks, a.n_chunks * 2, np.uint32).reshape(-1, 2),
+                    triangles=v(None, a.triangles, a.n_triangles * 4, np.uint32).reshape(-1, 4),
+                    verts=v(None, a.verts, a.n_verts * 3, np.float32).reshape(-1, 3),
+                    dynamics=v(None, a.dynamics, a.n_dynamics * 3, np.uint32).reshape(-1, 3),
+                    n_static_triangles=a.n_static_triangles, n_objects=a.n_objects, node_depth=a.node_depth)
+
+    def _offsets(self, offsets, n):
+        if offsets is None:
+            return None, None, 0
+        shape = tuple(offsets.shape)
+        if len(shape) != 3 or shape[0] != n or shape[2] != 3:
+            raise ValueError('object offsets must be (n, n_objects, 3), got %s' % (shape,))
+        ptr, keep, _ = _device_tensor(offsets if not isinstance(offsets, np.ndarray) else np.asarray(offsets, np.float32), 'object offsets')
+        return ptr, keep, shape[1]
+
+    def sweep(self, spheres, vels, object_offsets=None, stream=None):
+        """rdoom_world_sweep: spheres (n, 4) = centre xyz + radius, vels (n, 3), object_offsets None or (n, n_objects, 3)
+        -> (n, 4) = time (+inf: no contact), normal xyz.  torch tensors on the GPU stay there (asynchronous on `stream`, the
+        result is a new tensor); numpy arrays are copied there and back (synchronous)."""
+        n = int(spheres.shape[0])
+        if tuple(spheres.shape) != (n, 4) or tuple(vels.shape) != (n, 3):
+            raise ValueError('spheres must be (n, 4) and vels (n, 3), got %s and %s' % (tuple(spheres.shape), tuple(vels.shape)))
+        conv = (lambda a: np.asarray(a, np.float32)) if isinstance(spheres, np.ndarray) else (lambda a: a)
+        ps, ks, host = _device_tensor(conv(spheres), 'spheres')
+        pv, kv, _ = _device_tensor(conv(vels), 'vels')
+        po, ko, n_obj = self._offsets(object_offsets, n)
+        import torch
+        out = torch.empty((n, 4), dtype=torch.float32, device=ks.device)
+        _check(lib().rdoom_world_sweep(self._h, ctypes.c_void_p(ps), ctypes.c_void_p(pv), n, ctypes.c_void_p(po), n_obj,
+                                       ctypes.c_void_p(_stream_handle(stream)), ctypes.c_void_p(out.data_ptr())))
+        if host:
+            torch.cuda.synchronize(ks.device)
+            return out.cpu().numpy()
+        return out
+
+    def step(self, states, inputs, n_ticks=None, config=None, dt=1.0 / 60.0, object_offsets=None, stream=None):
+        """rdoom_world_step_players: n_ticks ticks of Player::update for every player.  states: PLAYER_STATE records (numpy: a
+        stepped copy is returned) or a contiguous GPU tensor of n * 40 bytes (stepped in place, asynchronously on `stream`).
+        inputs: (n_ticks, n) PLAYER_INPUT records, or a GPU tensor of n_ticks * n * 20 bytes with n_ticks given.
+        config: a PLAYER_CONFIG record or None (the defaults); object_offsets None or (n, n_objects, 3)."""
+        is_np = isinstance(states, np.ndarray)
+        if is_np:
+            states = np.ascontiguousarray(states, PLAYER_STATE).reshape(-1)
+            n = len(states)
+        else:
+            if states.numel() * states.element_size() % PLAYER_STATE.itemsize:
+                raise ValueError('a states tensor must hold n * %d bytes' % PLAYER_STATE.itemsize)
+            n = states.numel() * states.element_size() // PLAYER_STATE.itemsize
+        if isinstance(inputs, np.ndarray):
+            inputs = np.ascontiguousarray(inputs, PLAYER_INPUT)
+            inputs = inputs.reshape(-1, n) if inputs.size else inputs.reshape(0, n)
+            if n_ticks is not None and n_ticks != inputs.shape[0]:
+                raise ValueError('n_ticks %d, but inputs for %d ticks' % (n_ticks, inputs.shape[0]))
+            n_ticks = inputs.shape[0]
+        elif n_ticks is None:
+            raise ValueError('n_ticks is needed with an input tensor')
+        ps, ks, _ = _device_tensor(states, 'states')
+        pi, ki, _ = _device_tensor(inputs, 'inputs')
+        po, ko, n_obj = self._offsets(object_offsets, n)
+        cfg = None
+        if config is not None:
+            cfg = np.ascontiguousarray(np.asarray(config, PLAYER_CONFIG).reshape(1))
+        _check(lib().rdoom_world_step_players(self._h, ctypes.c_void_p(ps), ctypes.c_void_p(pi), n, int(n_ticks),
+                                              cfg.ctypes.data_as(ctypes.c_void_p) if cfg is not None else None, ctypes.c_float(dt),
+                                              ctypes.c_void_p(po), n_obj, ctypes.c_void_p(_stream_handle(stream))))
+        if not is_np:
+            return states
+        import torch
+        torch.cuda.synchronize(ks.device)
+        return ks.cpu().numpy().view(PLAYER_STATE).copy()

@@ -1,0 +1,532 @@
+// The collision world on the device: World::sweep_sphere (game/src/world.rs:40-120, math/src/sphere.rs:16-183) for a batch
+// of queries, and K ticks of Player::update (game/src/player.rs:142-408) for a batch of players in one launch, with the C ABI
+// of both (include/rdoom.h "collision world + player physics").  The host half, WorldBuilder, is csrc/host/game_world.cpp.
+//
+// Arithmetic: binary32 in the reference's operation order (cgmath: dot = (x x' + y y') + z z', cross component by component,
+// vector / scalar divides every component, normalize_or_zero = v / max(|v|, f32::EPSILON)); the build passes
+// -ffp-contract=off and HIP divides and takes square roots correctly rounded, so every result is the one an IEEE host
+// computes with the same expressions.  No fastmath.hpp short forms, no device libm: sin / cos come from sincos_rd below.
+//
+// Shape: one lane per query / player -- the sweeps of one player are strictly sequential -- and one wave per workgroup.  Each
+// lane walks the BSP with its own node stack in LDS (word `slot * 64 + lane`: no bank conflicts), sized by the tree's depth at
+// create time, so nothing is spilled to scratch.  The world's arrays are read-only and shared by every lane.
+#include <hip/hip_runtime.h>
+
+#include <cstring>
+#include <memory>
+
+#include "../common.hpp"
+#include "../host/game_world.hpp"
+#include "kernels.hpp"
+
+namespace {
+
+constexpr uint32_t WAVE = 64;
+
+struct DevNode {  // Node (world.rs:139-143): the partition's origin + displace, then the packed children
+  float ox, oy, dx, dy;
+  int32_t positive, negative, _pad[2];
+};
+struct DevDynamic {
+  uint32_t object_id, tri_start, tri_end, _pad;
+};
+
+struct WorldView {
+  const DevNode *nodes;
+  const uint2 *chunks;
+  const uint4 *tris;  // v1, v2, v3, normal
+  const float *verts;
+  const DevDynamic *dynamics;
+  uint32_t n_dynamics;
+  uint32_t stack_cap;  // node_depth + 1: a depth-first walk that pushes at most two children holds at most one pending sibling
+                       // per level above the deepest, two at the deepest
+};
+
+struct V3 {
+  float x, y, z;
+};
+__device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
+__device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
+__device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
+__device__ __forceinline__ V3 operator-(V3 a) { return v3(-a.x, -a.y, -a.z); }
+__device__ __forceinline__ V3 operator*(V3 a, float s) { return v3(a.x * s, a.y * s, a.z * s); }
+__device__ __forceinline__ V3 operator/(V3 a, float s) { return v3(a.x / s, a.y / s, a.z / s); }
+__device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
+__device__ __forceinline__ V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
+__device__ __forceinline__ float magnitude(V3 a) { return __builtin_sqrtf(dot(a, a)); }
+__device__ __forceinline__ V3 normalize_or_zero(V3 a) {  // math/src/lib.rs:40-42 (f32::max: the other operand when one is NaN)
+  const float m = magnitude(a);
+  return a / (m > 1.1920929e-7f ? m : 1.1920929e-7f);
+}
+__device__ __forceinline__ V3 load3(const float *p) { return v3(p[0], p[1], p[2]); }
+
+struct Contact {
+  float time;
+  V3 normal;
+};
+
+// sphere.rs:178-183
+__device__ __forceinline__ bool inside_triangle(V3 a, V3 b, V3 c, V3 p) {
+  const V3 u = b - a, v = c - a, n = cross(u, v), w = p - a;
+  const float n2 = dot(n, n);
+  const float gamma = dot(cross(u, w), n) / n2;
+  const float beta = dot(cross(w, v), n) / n2;
+  const float alpha = 1.0f - gamma - beta;
+  return (0.0f <= alpha && alpha <= 1.0f) & (0.0f <= gamma && gamma <= 1.0f) & (0.0f <= beta && beta <= 1.0f);
+}
+
+// intersect_sphere_line + lowest_quadratic_root (sphere.rs:131-160); false = None
+__device__ __forceinline__ bool sphere_line(V3 center, float radius, V3 p1, V3 p2, float &out) {
+  const V3 edge = p2 - p1;
+  const float a = dot(edge, edge);
+  const float b = 2.0f * dot(edge, p1 - center);
+  const float c = dot(center, center) + dot(p1, p1) - 2.0f * dot(center, p1) - radius * radius;
+  float i = b * b - 4.0f * a * c;
+  if (i < 0.0f) return false;
+  i = __builtin_sqrtf(i);
+  const float a2 = 2.0f * a;
+  const float i1 = (-b + i) / a2, i2 = (-b - i) / a2;
+  out = i1 < i2 ? i1 : i2;
+  return true;
+}
+
+// intersect_line_line (sphere.rs:162-176) on 2-d points; false = None
+__device__ __forceinline__ bool line_line(float p1x, float p1y, float p2x, float p2y, float p3x, float p3y, float p4x, float p4y,
+                                          float &out) {
+  const float d1x = p2x - p1x, d1y = p2y - p1y, d2x = p3x - p4x, d2y = p3y - p4y;
+  const float denom = d2y * d1x - d2x * d1y;
+  if (denom == 0.0f) return false;
+  const float dist = d2x * (p1y - p3y) - d2y * (p1x - p3x);
+  out = dist / denom;
+  return true;
+}
+
+__device__ __forceinline__ float comp(V3 v, int i) { return i == 0 ? v.x : (i == 1 ? v.y : v.z); }
+
+__device__ __forceinline__ void sweep_vertex(V3 vertex, V3 center, float radius, V3 nvel, float &min_distance, V3 &contact_normal,
+                                             bool &collision) {
+  float d;
+  if (sphere_line(center, radius, vertex, vertex + (-nvel), d) && d >= 0.0f && d < min_distance) {
+    min_distance = d;
+    contact_normal = center - (vertex + nvel * (-d));
+    collision = true;
+  }
+}
+
+__device__ __forceinline__ void sweep_edge(V3 e1, V3 e2, V3 center, float radius, V3 nvel, float &min_distance, V3 &contact_normal,
+                                           bool &collision) {
+  const V3 edge = e2 - e1;
+  const V3 edge_normal = normalize_or_zero(cross(nvel, edge));
+  const float edge_intercept = -dot(e1, edge_normal);
+  const float edge_distance = dot(center, edge_normal) + edge_intercept;
+  if (__builtin_fabsf(edge_distance) > radius) return;
+  const float circle_radius = __builtin_sqrtf(radius * radius - edge_distance * edge_distance);
+  const V3 circle_center = center + edge_normal * (-edge_distance);
+  const V3 e1_to_circle_center = circle_center - e1;
+  const V3 disp = edge * (dot(e1_to_circle_center, edge) / dot(edge, edge));
+  const V3 on_line = e1 + disp;
+  const V3 circle_center_to_on_line = normalize_or_zero(on_line - circle_center);
+  const V3 candidate = circle_center + circle_center_to_on_line * circle_radius;
+  const float ax = __builtin_fabsf(edge_normal.x), ay = __builtin_fabsf(edge_normal.y), az = __builtin_fabsf(edge_normal.z);
+  int dim1, dim2;
+  if (ax > ay && ax > az) dim1 = 1, dim2 = 2;
+  else if (ay > az) dim1 = 0, dim2 = 2;
+  else dim1 = 0, dim2 = 1;
+  const V3 candidate_plus_nvel = candidate + nvel;
+  float t;
+  if (!line_line(comp(candidate, dim1), comp(candidate, dim2), comp(candidate_plus_nvel, dim1), comp(candidate_plus_nvel, dim2),
+                 comp(e1, dim1), comp(e1, dim2), comp(e2, dim1), comp(e2, dim2), t))
+    return;
+  if (!(t >= 0.0f && t < min_distance)) return;
+  const V3 intersection = candidate + nvel * t;
+  if (dot(e1 - intersection, e2 - intersection) > 0.0f) return;
+  min_distance = t;
+  contact_normal = center - candidate;
+  collision = true;
+}
+
+// Sphere::sweep_triangle (sphere.rs:16-127); false = None
+__device__ __forceinline__ bool sweep_triangle(V3 t0, V3 t1, V3 t2, V3 normal, V3 center, float radius, V3 vel, Contact &out) {
+  const float speed = magnitude(vel);
+  if (speed == 0.0f) return false;
+  const V3 nvel = vel / speed;
+  const float normal_dot_nvel = dot(normal, nvel);
+  if (normal_dot_nvel >= 0.0f) return false;
+  V3 contact_normal = v3(0.0f, 0.0f, 0.0f);
+  bool collision = false;
+  float min_distance = 1e4f;
+  const float intercept = -dot(t0, normal);
+  const float signed_plane_distance = dot(center, normal) + intercept;
+  if (signed_plane_distance < -radius) return false;
+  if (signed_plane_distance >= radius) {  // sphere against plane
+    const float distance = -(signed_plane_distance - radius) / normal_dot_nvel;
+    const V3 on_plane = center + nvel * distance;
+    if (inside_triangle(t0, t1, t2, on_plane)) {
+      min_distance = distance;
+      contact_normal = normal;
+      collision = true;
+    }
+  }
+  // (the vertices and edges one call each: an array of the three corners would be indexed in private memory)
+  sweep_vertex(t0, center, radius, nvel, min_distance, contact_normal, collision);  // sphere against vertices
+  sweep_vertex(t1, center, radius, nvel, min_distance, contact_normal, collision);
+  sweep_vertex(t2, center, radius, nvel, min_distance, contact_normal, collision);
+  sweep_edge(t0, t1, center, radius, nvel, min_distance, contact_normal, collision);  // sphere against edges
+  sweep_edge(t1, t2, center, radius, nvel, min_distance, contact_normal, collision);
+  sweep_edge(t2, t0, center, radius, nvel, min_distance, contact_normal, collision);
+  if (!collision) return false;
+  out.normal = normalize_or_zero(contact_normal);
+  out.time = min_distance / speed;
+  return true;
+}
+
+// World::sweep_chunk (world.rs:84-106): the fold keeps the later candidate on equal times
+__device__ __forceinline__ void sweep_chunk(const WorldView &w, Contact &first, uint32_t start, uint32_t end, V3 center, float radius,
+                                            V3 vel) {
+  for (uint32_t i = start; i < end; i++) {
+    const uint4 t = w.tris[i];
+    Contact c;
+    if (sweep_triangle(load3(w.verts + 3 * t.x), load3(w.verts + 3 * t.y), load3(w.verts + 3 * t.z), load3(w.verts + 3 * t.w), center,
+                       radius, vel, c)) {  // (field by field: a select of two structs becomes one of their addresses in scratch)
+      const bool keep = first.time < c.time;
+      first.time = keep ? first.time : c.time;
+      first.normal = v3(keep ? first.normal.x : c.normal.x, keep ? first.normal.y : c.normal.y, keep ? first.normal.z : c.normal.z);
+    }
+  }
+}
+
+// World::sweep_sphere (world.rs:40-82).  `stack`: this lane's first LDS word (stride WAVE).  `offsets`: this query's
+// n_objects x xyz object displacements, or null.  time = +inf: None.
+__device__ __forceinline__ Contact sweep_world(const WorldView &w, V3 center, float radius, V3 vel, const float *offsets,
+                                               uint32_t *stack) {
+  Contact first{__builtin_inff(), v3(0.0f, 0.0f, 0.0f)};
+  uint32_t sp = 0;
+  stack[0] = 0u;
+  sp = 1;
+  while (sp) {  // statics: positive child first; leaves are swept when met, nodes pushed
+    const DevNode node = w.nodes[stack[--sp * WAVE]];
+    // Line2::signed_distance (math/src/line.rs:43-45) of the centre and of centre + vel, in the xz plane
+    const float tx = center.x + vel.x, tz = center.z + vel.z;
+    const float dist1 = (center.x * node.dy - center.z * node.dx) + (node.dx * node.oy - node.dy * node.ox);
+    const float dist2 = (tx * node.dy - tz * node.dx) + (node.dx * node.oy - node.dy * node.ox);
+    const bool pos = dist1 >= -radius || dist2 >= -radius;
+    const bool neg = dist1 <= radius || dist2 <= radius;
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      if (!(k == 0 ? pos : neg)) continue;
+      const int32_t packed = k == 0 ? node.positive : node.negative;
+      if (packed > 0) {             // Child::Node
+        if (sp < w.stack_cap)       // (always: see WorldView::stack_cap; the test only keeps the LDS writes in bounds)
+          stack[sp++ * WAVE] = (uint32_t)packed;
+      } else {                      // Child::Leaf(-packed); a never-linked child is 0 = Leaf(0), as in the reference
+        const uint2 chunk = w.chunks[(uint32_t)(-packed)];
+        sweep_chunk(w, first, chunk.x, chunk.y, center, radius, vel);
+      }
+    }
+  }
+  for (uint32_t d = 0; d < w.n_dynamics; d++) {  // dynamics: the inverse of a pure translation is p + (-disp), v unchanged
+    const DevDynamic dyn = w.dynamics[d];
+    V3 off = v3(0.0f, 0.0f, 0.0f);
+    if (offsets) off = load3(offsets + 3 * dyn.object_id);
+    sweep_chunk(w, first, dyn.tri_start, dyn.tri_end, center + (-off), radius, vel);
+  }
+  return first;
+}
+
+// Project-owned binary32 sine and cosine: Cody-Waite reduction by pi/2 in three parts (the first two short enough that
+// j * part is exact for |j| < 2^12), then the minimax polynomials of the Cephes library's sinf / cosf on [-pi/4, pi/4].
+// Every operation is written out, so an IEEE host evaluating the same expressions gets the same bits.
+__device__ __forceinline__ void sincos_rd(float x, float &s, float &c) {
+  const float j = __builtin_floorf(x * 0.636619772f + 0.5f);
+  const float r = ((x - j * 1.5703125f) - j * 4.837512969970703125e-4f) - j * 7.54978995489188216e-8f;
+  const float z = r * r;
+  const float ps = ((-1.9515295891e-4f * z + 8.3321608736e-3f) * z - 1.6666654611e-1f) * z * r + r;
+  const float pc = ((2.443315711809948e-5f * z - 1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z * z - 0.5f * z + 1.0f;
+  const int q = (int)j & 3;
+  s = q == 0 ? ps : (q == 1 ? pc : (q == 2 ? -ps : -pc));
+  c = q == 0 ? pc : (q == 1 ? -ps : (q == 2 ? -pc : ps));
+}
+
+__global__ __launch_bounds__(WAVE) void sweep_kernel(WorldView w, const float *spheres, const float *vels, uint32_t n,
+                                                     const float *offsets, uint32_t n_objects, float *out) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+  const uint32_t q = blockIdx.x * WAVE + threadIdx.x;
+  if (q >= n) return;
+  const float *sp = spheres + 4 * (size_t)q;
+  const Contact c = sweep_world(w, v3(sp[0], sp[1], sp[2]), sp[3], load3(vels + 3 * (size_t)q),
+                                offsets ? offsets + (size_t)q * n_objects * 3 : nullptr, lds_stack + threadIdx.x);
+  float *o = out + 4 * (size_t)q;
+  o[0] = c.time, o[1] = c.normal.x, o[2] = c.normal.y, o[3] = c.normal.z;
+}
+
+__device__ __forceinline__ float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }  // player.rs:415-423
+
+__global__ __launch_bounds__(WAVE) void player_step_kernel(WorldView w, rdoom_player_state *states, const rdoom_player_input *inputs,
+                                                           uint32_t n, uint32_t n_ticks, rdoom_player_config cfg, float dt,
+                                                           const float *offsets, uint32_t n_objects) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+  const uint32_t p = blockIdx.x * WAVE + threadIdx.x;
+  if (p >= n) return;
+  uint32_t *stack = lds_stack + threadIdx.x;
+  const float *off = offsets ? offsets + (size_t)p * n_objects * 3 : nullptr;
+  rdoom_player_state *st = states + p;
+  V3 pos = load3(st->pos), vel = load3(st->vel);
+  float yaw = st->yaw, pitch = st->pitch, last_height_diff = st->last_height_diff;
+  uint32_t flags = st->flags;
+  const bool fly = flags & RDOOM_PLAYER_FLY, clip = flags & RDOOM_PLAYER_CLIP;
+  const float pitch_limit = 1.57079637f - 1e-2f;  // FRAC_PI_2 - 1e-2 in binary32 (player.rs:196-201)
+  for (uint32_t t = 0; t < n_ticks; t++) {
+    const rdoom_player_input in = inputs[(size_t)t * n + p];
+    // ---- force() (player.rs:243-315): the feet probe
+    float height = cfg.height;
+    bool grounded = false;
+    V3 ground_normal = v3(0.0f, 0.0f, 0.0f);
+    {
+      const Contact c = sweep_world(w, pos, 0.2f, v3(0.0f, -cfg.height, 0.0f), off, stack);
+      if (c.time < __builtin_inff() && c.time < 1.0f) height = cfg.height * c.time, ground_normal = c.normal, grounded = true;
+    }
+    // move_force (player.rs:182-241), orientation as (yaw, pitch)
+    yaw = yaw - in.look[0];
+    pitch = clampf(pitch - in.look[1], -pitch_limit, pitch_limit);
+    float sy, cy, sp, cp;
+    sincos_rd(yaw, sy, cy);
+    sincos_rd(pitch, sp, cp);
+    V3 force;
+    if (fly) {  // rot * (normalize_or_zero(move.x, up, move.y) * move_force), rot = Ry(yaw) Rx(pitch)
+      const V3 m = normalize_or_zero(v3(in.movement[0], in.jump ? 0.5f : 0.0f, in.movement[1])) * cfg.move_force;
+      const float y1 = m.y * cp - m.z * sp, z1 = m.y * sp + m.z * cp;
+      force = v3(m.x * cy + z1 * sy, y1, z1 * cy - m.x * sy);
+    } else {  // normalize(Ry(yaw) (move.x, 0, move.y cos pitch)): the y the pitch adds is dropped before normalising
+      const float a = in.movement[1] * cp;
+      V3 m = normalize_or_zero(v3(in.movement[0] * cy + a * sy, 0.0f, a * cy - in.movement[0] * sy)) * cfg.move_force;
+      if (grounded) {
+        if (in.jump && vel.y < 0.1f) m = v3(m.x, 5.0f / dt, m.z);
+      } else {
+        m = m * 0.1f;
+      }
+      force = m;
+    }
+    const float speed = magnitude(vel);
+    if (speed > 0.0f) {
+      V3 slowdown = v3(0.0f, 0.0f, 0.0f);
+      if (fly) {
+        slowdown = (-vel) * (cfg.friction / speed + cfg.ground_drag * speed);
+      } else if (grounded) {
+        const V3 tangential = vel - ground_normal * dot(vel, ground_normal);
+        const float ts = magnitude(tangential);
+        if (ts > 0.0f) slowdown = (-tangential) * (cfg.friction / ts + cfg.ground_drag * ts);
+      }
+      slowdown = slowdown - vel * cfg.air_drag * speed;
+      const float slowdown_norm = magnitude(slowdown);
+      if (slowdown_norm > 0.0f) {
+        const float max_slowdown = -dot(vel, slowdown) / slowdown_norm / dt;
+        if (slowdown_norm >= max_slowdown) slowdown = slowdown / slowdown_norm * max_slowdown;
+        force = force + slowdown;
+      }
+    }
+    const float height_diff = cfg.height - height;
+    const float derivative = (height_diff - last_height_diff) / dt;
+    last_height_diff = height_diff;
+    force.y = force.y + (height_diff * cfg.spring_const_p + derivative * cfg.spring_const_d);
+    if (!fly) force.y = force.y - 17.0f;
+    // ---- clip() (player.rs:142-166) or noclip() (player.rs:168-190)
+    if (clip) {
+      float time_left = dt;
+      bool armed = true;
+      for (int i = 0; i < 100; i++) {
+        const V3 displacement = vel * time_left;
+        const Contact c = sweep_world(w, pos, cfg.radius, displacement, off, stack);
+        if (c.time < __builtin_inff()) {
+          const float adjusted_time = c.time - 0.001f / magnitude(displacement);
+          if (adjusted_time < 1.0f) {
+            const float time = clampf(c.time, 0.0f, 1.0f);
+            pos = pos + displacement * adjusted_time;
+            vel = vel - c.normal * dot(c.normal, vel);
+            time_left = time_left * (1.0f - time);
+            continue;
+          }
+        }
+        pos = pos + displacement;
+        armed = false;
+        break;
+      }
+      if (armed) flags |= RDOOM_PLAYER_DIVERGED;
+    } else {
+      const float old_height = pos.y;
+      pos = pos + vel * dt;
+      if (!fly) {
+        const float probe_height = 2000.0f;
+        const V3 probe = pos + v3(0.0f, probe_height / 2.0f, 0.0f);
+        const Contact c = sweep_world(w, probe, cfg.radius, v3(0.0f, -probe_height, 0.0f), off, stack);
+        const float h = c.time < __builtin_inff() ? pos.y + probe_height * (0.5f - c.time) : old_height;
+        if (pos.y <= h) {
+          pos.y = h;
+          if (vel.y < 0.0f) vel.y = 0.0f;
+        }
+      }
+    }
+    vel = vel + force * dt;
+  }
+  st->pos[0] = pos.x, st->pos[1] = pos.y, st->pos[2] = pos.z;
+  st->vel[0] = vel.x, st->vel[1] = vel.y, st->vel[2] = vel.z;
+  st->yaw = yaw, st->pitch = pitch, st->last_height_diff = last_height_diff;
+  st->flags = flags;
+}
+
+}  // namespace
+
+struct rdoom_world {
+  rdoom::game::World host;
+  bool on_device = false;
+  int device = -1;
+  DevNode *d_nodes = nullptr;
+  uint2 *d_chunks = nullptr;
+  uint4 *d_tris = nullptr;
+  float *d_verts = nullptr;
+  DevDynamic *d_dynamics = nullptr;
+};
+
+static_assert(sizeof(rdoom_world_node) == sizeof(rdoom::game::WorldNode) && sizeof(rdoom_world_chunk) == sizeof(rdoom::game::WorldChunk) &&
+                  sizeof(rdoom_world_triangle) == sizeof(rdoom::game::WorldTriangle) &&
+                  sizeof(rdoom_world_dynamic) == sizeof(rdoom::game::WorldDynamic),
+              "the C ABI records are the host builder's");
+static_assert(sizeof(rdoom_player_state) == 40 && sizeof(rdoom_player_input) == 20 && sizeof(rdoom_player_config) == 32, "ABI sizes");
+
+namespace {
+template <class T>
+rdoom_status upload(T **dst, const void *src, size_t bytes) {
+  if (!bytes) bytes = 16;  // (a level without dynamic chunks: a valid, unread pointer)
+  HIP_TRY(hipMalloc((void **)dst, bytes));
+  if (src) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
+  return RDOOM_OK;
+}
+
+WorldView view(const rdoom_world *w) {
+  return WorldView{w->d_nodes, w->d_chunks, w->d_tris, w->d_verts, w->d_dynamics, (uint32_t)w->host.dynamics.size(),
+                   w->host.node_depth + 1};
+}
+
+rdoom_status check_device(const rdoom_world *w) {
+  if (!w->on_device) return rdoom::fail(RDOOM_BAD_ARG, "the world was created with RDOOM_WORLD_HOST_ONLY: it has no device copy");
+  int cur = -1;
+  HIP_TRY(hipGetDevice(&cur));
+  if (cur != w->device) return rdoom::fail(RDOOM_BAD_ARG, "the world lives on device %d, the current device is %d", w->device, cur);
+  return RDOOM_OK;
+}
+
+rdoom_status check_offsets(const rdoom_world *w, const float *offsets, uint32_t n_objects) {
+  if (offsets && n_objects < w->host.n_objects)
+    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the world's %u objects", n_objects, w->host.n_objects);
+  return RDOOM_OK;
+}
+}  // namespace
+
+extern "C" {
+
+void rdoom_world_destroy(rdoom_world *w) {
+  if (!w) return;
+  for (void *p : {(void *)w->d_nodes, (void *)w->d_chunks, (void *)w->d_tris, (void *)w->d_verts, (void *)w->d_dynamics})
+    if (p) (void)hipFree(p);
+  delete w;
+}
+
+rdoom_status rdoom_world_create(const rdoom_wad *wad, uint32_t level_index, uint32_t flags, rdoom_world **out_world) {
+  if (!wad || !out_world) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (flags & ~RDOOM_WORLD_HOST_ONLY) return rdoom::fail(RDOOM_BAD_ARG, "unknown flags 0x%x", flags);
+  *out_world = nullptr;
+  std::unique_ptr<rdoom_world, void (*)(rdoom_world *)> w(nullptr, rdoom_world_destroy);
+  try {  // nothing unwinds across the C ABI
+    w.reset(new rdoom_world);
+    w->host = rdoom::game::build_world(*rdoom::game::loaded_wad(wad), level_index);
+  } catch (const rdoom::wad::WadError &e) {
+    return rdoom::fail(e.code, "%s", e.what());
+  } catch (const std::bad_alloc &) {
+    return rdoom::fail(RDOOM_OOM, "out of host memory");
+  } catch (const std::exception &e) {
+    return rdoom::fail(RDOOM_BAD_LEVEL, "%s", e.what());
+  }
+  const rdoom::game::World &h = w->host;
+  if (h.node_depth > RDOOM_WORLD_MAX_DEPTH)
+    return rdoom::fail(RDOOM_BAD_LEVEL, "the level's BSP is %u nodes deep (at most %u)", h.node_depth, RDOOM_WORLD_MAX_DEPTH);
+  if (!(flags & RDOOM_WORLD_HOST_ONLY)) {
+    HIP_TRY(hipGetDevice(&w->device));
+    std::vector<DevNode> nodes(h.nodes.size());
+    for (size_t i = 0; i < nodes.size(); i++) {
+      const rdoom::game::WorldNode &s = h.nodes[i];
+      nodes[i] = DevNode{s.origin[0], s.origin[1], s.displace[0], s.displace[1], s.positive, s.negative, {0, 0}};
+    }
+    std::vector<DevDynamic> dyn(h.dynamics.size());
+    for (size_t i = 0; i < dyn.size(); i++) dyn[i] = DevDynamic{h.dynamics[i].object_id, h.dynamics[i].tri_start, h.dynamics[i].tri_end, 0};
+    if (rdoom_status s = upload(&w->d_nodes, nodes.data(), nodes.size() * sizeof(DevNode))) return s;
+    if (rdoom_status s = upload(&w->d_chunks, h.chunks.data(), h.chunks.size() * sizeof(uint2))) return s;
+    if (rdoom_status s = upload(&w->d_tris, h.triangles.data(), h.triangles.size() * sizeof(uint4))) return s;
+    if (rdoom_status s = upload(&w->d_verts, h.verts.data(), h.verts.size() * sizeof(float))) return s;
+    if (rdoom_status s = upload(&w->d_dynamics, dyn.data(), dyn.size() * sizeof(DevDynamic))) return s;
+    w->on_device = true;
+  }
+  *out_world = w.release();
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_world_host_arrays(const rdoom_world *w, rdoom_world_arrays *out) {
+  if (!w || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  const rdoom::game::World &h = w->host;
+  std::memset(out, 0, sizeof *out);
+  out->nodes = reinterpret_cast<const rdoom_world_node *>(h.nodes.data());
+  out->n_nodes = (uint32_t)h.nodes.size();
+  out->chunks = reinterpret_cast<const rdoom_world_chunk *>(h.chunks.data());
+  out->n_chunks = (uint32_t)h.chunks.size();
+  out->triangles = reinterpret_cast<const rdoom_world_triangle *>(h.triangles.data());
+  out->n_triangles = (uint32_t)h.triangles.size();
+  out->n_static_triangles = h.n_static_triangles;
+  out->verts = h.verts.data();
+  out->n_verts = (uint32_t)(h.verts.size() / 3);
+  out->dynamics = reinterpret_cast<const rdoom_world_dynamic *>(h.dynamics.data());
+  out->n_dynamics = (uint32_t)h.dynamics.size();
+  out->n_objects = h.n_objects;
+  out->node_depth = h.node_depth;
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_world_sweep(const rdoom_world *w, const float *d_spheres, const float *d_vels, uint32_t n,
+                               const float *d_object_offsets, uint32_t n_objects, void *stream, float *d_out) {
+  if (!w) return rdoom::fail(RDOOM_BAD_ARG, "null world");
+  if (n && (!d_spheres || !d_vels || !d_out)) return rdoom::fail(RDOOM_BAD_ARG, "null array with n = %u", n);
+  if (rdoom_status s = check_offsets(w, d_object_offsets, n_objects)) return s;
+  if (rdoom_status s = check_device(w)) return s;
+  if (!n) return RDOOM_OK;
+  const WorldView v = view(w);
+  hipLaunchKernelGGL(sweep_kernel, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t), (hipStream_t)stream, v,
+                     d_spheres, d_vels, n, d_object_offsets, n_objects, d_out);
+  HIP_TRY(hipGetLastError());
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_player_config_default(rdoom_player_config *out) {
+  if (!out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  *out = rdoom_player_config{60.0f, 200.0f, 22.4f, 0.19f, 0.21f, 0.02f, 0.7f, 30.0f};  // player.rs:73-92
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_world_step_players(const rdoom_world *w, rdoom_player_state *d_states, const rdoom_player_input *d_inputs,
+                                      uint32_t n_players, uint32_t n_ticks, const rdoom_player_config *cfg, float dt,
+                                      const float *d_object_offsets, uint32_t n_objects, void *stream) {
+  if (!w) return rdoom::fail(RDOOM_BAD_ARG, "null world");
+  if (n_players && (!d_states || (n_ticks && !d_inputs)))
+    return rdoom::fail(RDOOM_BAD_ARG, "null states or inputs with n_players = %u", n_players);
+  if (!(dt >= 0.0f) || dt == __builtin_inff()) return rdoom::fail(RDOOM_BAD_ARG, "dt %g is not a finite non-negative number", (double)dt);
+  if (rdoom_status s = check_offsets(w, d_object_offsets, n_objects)) return s;
+  if (rdoom_status s = check_device(w)) return s;
+  if (!n_players || !n_ticks) return RDOOM_OK;
+  rdoom_player_config c;
+  if (cfg) c = *cfg;
+  else rdoom_player_config_default(&c);
+  const WorldView v = view(w);
+  hipLaunchKernelGGL(player_step_kernel, dim3((n_players + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
+                     (hipStream_t)stream, v, d_states, d_inputs, n_players, n_ticks, c, dt == 0.0f ? 1.0f / 60.0f : dt, d_object_offsets,
+                     n_objects);
+  HIP_TRY(hipGetLastError());
+  return RDOOM_OK;
+}
+
+}  // extern "C"

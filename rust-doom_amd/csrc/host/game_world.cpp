@@ -1,0 +1,129 @@
+// game::world::WorldBuilder (game/src/world.rs:211-409) as a LevelVisitor.  See game_world.hpp.
+#include "game_world.hpp"
+
+#include <algorithm>
+#include <cmath>
+#include <map>
+
+namespace rdoom::game {
+using namespace rdoom::wad;
+
+namespace {
+class WorldBuilder : public LevelVisitor {
+ public:
+  void visit_bsp_root(const Line2f &line) override {  // world.rs:312-316
+    if (!nodes_.empty()) throw WadError(RDOOM_BAD_LEVEL, "world: a second BSP root");
+    nodes_.push_back(node(line));
+    stack_.push_back(0);
+    depth_ = std::max<uint32_t>(depth_, 1);
+  }
+  void visit_bsp_node(const Line2f &line, Branch branch) override {  // world.rs:318-323
+    const int32_t index = (int32_t)nodes_.size();
+    nodes_.push_back(node(line));
+    link_child(index, branch);
+    stack_.push_back((uint32_t)index);
+    depth_ = std::max<uint32_t>(depth_, (uint32_t)stack_.size());
+  }
+  void visit_bsp_leaf(Branch branch) override {  // world.rs:325-332
+    const uint32_t index = (uint32_t)chunks_.size();
+    const uint32_t n = (uint32_t)triangles_[0].size();
+    chunks_.push_back({n, n});
+    link_child(-(int32_t)index, branch);  // Child::Leaf(index).pack()
+  }
+  void visit_bsp_leaf_end() override {  // world.rs:334-337
+    if (chunks_.empty()) throw WadError(RDOOM_BAD_LEVEL, "world: leaf end without a leaf");
+    chunks_.back().tri_end = (uint32_t)triangles_[0].size();
+  }
+  void visit_bsp_node_end() override {  // world.rs:339-344
+    if (stack_.empty()) throw WadError(RDOOM_BAD_LEVEL, "world: too many BSP node ends");
+    stack_.pop_back();
+  }
+  void visit_floor_sky_poly(const SkyPoly &p) override { floor(p.object_id, p.vertices, p.n_vertices, p.height); }
+  void visit_ceil_sky_poly(const SkyPoly &p) override { ceil(p.object_id, p.vertices, p.n_vertices, p.height); }
+  void visit_floor_poly(const StaticPoly &p) override { floor(p.object_id, p.vertices, p.n_vertices, p.height); }
+  void visit_ceil_poly(const StaticPoly &p) override { ceil(p.object_id, p.vertices, p.n_vertices, p.height); }
+  void visit_wall_quad(const StaticQuad &q) override {  // world.rs:380-388: only blockers collide
+    if (q.blocker) quad(q.object_id, q.v1, q.v2, q.height_range);
+  }
+  void visit_sky_quad(const SkyQuad &q) override { quad(q.object_id, q.v1, q.v2, q.height_range); }
+
+  World build() {  // world.rs:230-258: object 0's triangles, then one dynamic chunk per other object, by ascending id
+    World w;
+    if (nodes_.empty()) throw WadError(RDOOM_BAD_LEVEL, "world: the level has no BSP nodes");
+    w.nodes = std::move(nodes_);
+    w.chunks = std::move(chunks_);
+    w.verts = std::move(verts_);
+    for (auto &kv : triangles_) {
+      const uint32_t start = (uint32_t)w.triangles.size();
+      w.triangles.insert(w.triangles.end(), kv.second.begin(), kv.second.end());
+      if (kv.first > 0) {
+        w.dynamics.push_back({kv.first, start, (uint32_t)w.triangles.size()});
+        w.n_objects = std::max(w.n_objects, kv.first + 1);
+      } else {
+        w.n_static_triangles = (uint32_t)w.triangles.size();
+      }
+    }
+    w.node_depth = depth_;
+    return w;
+  }
+
+ private:
+  static WorldNode node(const Line2f &l) {  // Node::new (world.rs:166-172)
+    return WorldNode{{l.origin.x, l.origin.y}, {l.displace.x, l.displace.y}, l.length, 0, 0};
+  }
+  void link_child(int32_t packed, Branch branch) {  // world.rs:261-279 (the reference asserts the slot is still 0)
+    if (stack_.empty()) throw WadError(RDOOM_BAD_LEVEL, "world: link_child on the root");
+    WorldNode &parent = nodes_[stack_.back()];
+    int32_t &slot = branch == Branch::Positive ? parent.positive : parent.negative;
+    if (slot != 0) throw WadError(RDOOM_BAD_LEVEL, "world: a BSP child linked twice");
+    slot = packed;
+  }
+  // add_polygon (world.rs:281-305): the vertices, then the normal as one more vertex, and a fan over them
+  void add_polygon(ObjectId object, const float *xyz, size_t n, const float normal[3]) {
+    std::vector<WorldTriangle> &tris = triangles_[object.v];
+    const uint32_t start = (uint32_t)(verts_.size() / 3);
+    verts_.insert(verts_.end(), xyz, xyz + 3 * n);
+    const uint32_t end = (uint32_t)(verts_.size() / 3);
+    verts_.insert(verts_.end(), normal, normal + 3);
+    for (uint32_t i = start + 2; i < end; i++) tris.push_back({start, i - 1, i, end});
+  }
+  void floor(ObjectId object, const Pnt2f *v, size_t n, float height) {  // world.rs:346-355
+    scratch_.clear();
+    for (size_t i = 0; i < n; i++) scratch_.insert(scratch_.end(), {v[i].x, height, v[i].y});
+    const float up[3] = {0.0f, 1.0f, 0.0f};
+    add_polygon(object, scratch_.data(), n, up);
+  }
+  void ceil(ObjectId object, const Pnt2f *v, size_t n, float height) {  // world.rs:357-367: reversed
+    scratch_.clear();
+    for (size_t i = n; i-- > 0;) scratch_.insert(scratch_.end(), {v[i].x, height, v[i].y});
+    const float down[3] = {0.0f, -1.0f, 0.0f};
+    add_polygon(object, scratch_.data(), n, down);
+  }
+  void quad(ObjectId object, Pnt2f v1, Pnt2f v2, const float range[2]) {  // world.rs:390-408
+    // (v2 - v1).normalize_or_zero(): v / max(|v|, f32::EPSILON) (math/src/lib.rs:40-42)
+    const float ex = v2.x - v1.x, ey = v2.y - v1.y;
+    const float m = std::sqrt(ex * ex + ey * ey);
+    const float d = m > 1.1920929e-7f ? m : 1.1920929e-7f;
+    const float nx = ex / d, ny = ey / d;
+    const float normal[3] = {-ny, 0.0f, nx};
+    const float low = range[0], high = range[1];
+    const float xyz[12] = {v1.x, low, v1.y, v2.x, low, v2.y, v2.x, high, v2.y, v1.x, high, v1.y};
+    add_polygon(object, xyz, 4, normal);
+  }
+
+  std::vector<WorldNode> nodes_;
+  std::vector<WorldChunk> chunks_;
+  std::vector<float> verts_, scratch_;
+  std::vector<uint32_t> stack_;
+  std::map<uint32_t, std::vector<WorldTriangle>> triangles_{{0u, {}}};  // VecMap<Vec<Triangle>>: iterated by ascending key
+  uint32_t depth_ = 0;
+};
+}  // namespace
+
+World build_world(const LoadedWad &w, size_t level_index) {
+  WorldBuilder b;
+  walk_level(w, level_index, b);
+  return b.build();
+}
+
+}  // namespace rdoom::game

@@ -1,0 +1,44 @@
+// game::world::WorldBuilder (game/src/world.rs:211-409): the collision volume the reference's player sweeps its head and
+// feet against, built by the same level walk that drives the renderer's Builder.  Host only: the device copy and the sweep /
+// player-step kernels live in csrc/hip/world.hip.
+#pragma once
+#include <cstdint>
+#include <vector>
+
+#include "game_level.hpp"
+
+namespace rdoom::game {
+
+// Node { partition: Line2f, positive: i32, negative: i32 } (world.rs:139-143) with the children as Child::pack writes them
+// (world.rs:152-163): a node index > 0, or minus a chunk index.  A child that was never linked stays 0 = Leaf(0).
+struct WorldNode {
+  float origin[2], displace[2], length;
+  int32_t positive, negative;
+};
+struct WorldChunk {  // world.rs:124-128
+  uint32_t tri_start, tri_end;
+};
+struct WorldTriangle {  // world.rs:135-141: indices into verts; `normal` too
+  uint32_t v1, v2, v3, normal;
+};
+struct WorldDynamic {  // one DynamicChunk per moving object with triangles (world.rs:212-237), by ascending ObjectId
+  uint32_t object_id, tri_start, tri_end;
+};
+
+struct World {
+  std::vector<WorldNode> nodes;
+  std::vector<WorldChunk> chunks;
+  std::vector<WorldTriangle> triangles;  // the static world's (object 0), then each dynamic chunk's, as build() orders them
+  std::vector<float> verts;              // xyz triples: polygon vertices, each polygon followed by its normal
+  std::vector<WorldDynamic> dynamics;
+  uint32_t n_static_triangles = 0;
+  uint32_t n_objects = 1;    // 1 + the largest ObjectId of a dynamic chunk
+  uint32_t node_depth = 0;   // nodes on the longest root-to-node path
+};
+
+// WorldBuilder::new + LevelWalker::walk + WorldBuilder::build.  Throws WadError(RDOOM_BAD_LEVEL) on a level without a BSP.
+World build_world(const LoadedWad &w, size_t level_index);
+// the archive behind a C handle (csrc/host/wad_api.cpp)
+const LoadedWad *loaded_wad(const rdoom_wad *wad);
+
+}  // namespace rdoom::game

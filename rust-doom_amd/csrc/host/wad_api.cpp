@@ -19,6 +19,10 @@ struct rdoom_built {
   std::unique_ptr<rdoom::game::BuiltLevel> b;
 };
 
+namespace rdoom::game {
+const LoadedWad *loaded_wad(const rdoom_wad *wad) { return wad ? &wad->w : nullptr; }  // (game_world.hpp; world.hip builds from it)
+}  // namespace rdoom::game
+
 namespace {
 // trait LevelVisitor implemented by a table of C callbacks (include/rdoom.h: rdoom_visitor_vtbl)
 class CallbackVisitor : public rdoom::wad::LevelVisitor {

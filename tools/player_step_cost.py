@@ -1,0 +1,77 @@
+#!/usr/bin/env python3
+"""What stepping players costs (rdoom_world_step_players, DESIGN section "Collision world and player physics"): 4 096 and 65 536
+players x 60 ticks (one second of the reference's 60 Hz tick) on E1M1 (synthetic IWAD) and on the 10x level, from the floor
+centroids with the scripted inputs of tests/test_gpu_world.py (walk, strafe, jump, look up, stand, turn).  The GPU time is one
+launch of all the ticks, bracketed by torch.cuda.synchronize (the median of --steps launches after --warmup); next to it, the
+test-side C restatement (tests/world_restatement.c, gcc -O2) on 16 host threads, timed once.  Prints a table and one JSON
+line per row: microseconds per player-tick.  Needs the GPU and torch.
+
+    python tools/player_step_cost.py [--steps K] [--warmup W] [--ticks T]
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, 'tests')):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--steps', type=int, default=5)
+    ap.add_argument('--warmup', type=int, default=1)
+    ap.add_argument('--ticks', type=int, default=60)
+    ap.add_argument('--threads', type=int, default=16)
+    a = ap.parse_args()
+    import numpy as np
+    import torch
+
+    import rust_doom_amd as rd
+    import world_ref
+    from test_gpu_world import _players, _script
+    from util import META_PATH, ensure_big_wad, ensure_wad
+    rd.set_device(0)
+    rows = []
+    for label, path in (('E1M1', ensure_wad()), ('10x', ensure_big_wad())):
+        wad = rd.Wad(path, META_PATH)
+        built = wad.build_level(0)
+        world, ref = wad.build_world(0), world_ref.RefWorld(wad, 0)
+        for n in (4096, 65536):
+            st = _players(built, n, seed=n)
+            inp = _script(n, a.ticks, seed=n)
+            s0 = torch.from_numpy(st.view(np.uint8).copy()).cuda()
+            i_dev = torch.from_numpy(np.ascontiguousarray(inp).view(np.uint8).copy()).cuda()
+            times = []
+            for k in range(a.warmup + a.steps):
+                s_dev = s0.clone()
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                world.step(s_dev, i_dev, n_ticks=a.ticks)
+                torch.cuda.synchronize()
+                if k >= a.warmup:
+                    times.append(time.perf_counter() - t0)
+            gpu = float(np.median(times))
+            t0 = time.perf_counter()
+            want = ref.step(st, inp, threads=a.threads)
+            cpu = time.perf_counter() - t0
+            same = bool(np.array_equal(s_dev.cpu().numpy(), np.ascontiguousarray(want).view(np.uint8)))
+            pt = n * a.ticks
+            rows.append(dict(level=label, players=n, ticks=a.ticks, gpu_us_per_player_tick=gpu * 1e6 / pt,
+                             cpu_us_per_player_tick=cpu * 1e6 / pt, cpu_threads=a.threads, gpu_ms=gpu * 1e3, cpu_ms=cpu * 1e3,
+                             bit_exact=same))
+    print('%-6s %8s %6s %14s %14s %8s %6s' % ('level', 'players', 'ticks', 'GPU us/p-tick', 'CPU us/p-tick', 'speedup', 'exact'))
+    for r in rows:
+        print('%-6s %8d %6d %14.4f %14.4f %8.1f %6s' % (r['level'], r['players'], r['ticks'], r['gpu_us_per_player_tick'],
+                                                       r['cpu_us_per_player_tick'], r['cpu_us_per_player_tick'] / r['gpu_us_per_player_tick'],
+                                                       r['bit_exact']))
+    for r in rows:
+        print(json.dumps(r))
+
+
+if __name__ == '__main__':
+    main()
