@@ -488,6 +488,87 @@ rdoom_status rdoom_world_step_players(const rdoom_world *world, rdoom_player_sta
 /* Config::default (player.rs:73-92) */
 rdoom_status rdoom_player_config_default(rdoom_player_config *out);
 
+/* ---- doors, lifts and exits: Level::poll_triggers and the move effects of Level::update --------------------------------
+ * The level reacting to the player (game/src/level.rs:77-167, 184-267), N independent games at once.  Every linedef with a
+ * special and both vertices is a trigger, in linedef order (wad/src/visitor.rs:341-500; none at all in a level without a
+ * tagged sector).  A trigger that fires copies its move effects into the player's active set, one per object (a later one
+ * replaces an earlier one on the same object); an active effect moves its object's height offset towards its first offset
+ * at `speed`, waits `wait` seconds, then moves on to its second offset if it has one, and ends.  One game tick for one
+ * player, in the reference's system order: Player::update's physics against the offsets as they stood at the start of the
+ * tick, then every active effect advances by dt in ascending object id, then the triggers are polled from the new position
+ * (walked line = -(velocity * dt) in the xz plane; a push / shoot action looks 0.5 / 100 along the camera's view).  An
+ * only_once trigger that fired is swap_remove'd from the player's list after the poll, so each game keeps its own order.
+ * Changing level on an exit trigger, teleports, monsters, damage and light effects are not simulated. */
+#define RDOOM_PLAYER_EXITED 0x200u /* sticky: an exit trigger fired for this player (set by rdoom_world_step_game only) */
+#define RDOOM_TRIGGER_WALK_OVER 0u /* rdoom_trigger.trigger_type (meta.rs TriggerType) */
+#define RDOOM_TRIGGER_PUSH 1u
+#define RDOOM_TRIGGER_SWITCH 2u
+#define RDOOM_TRIGGER_GUN 3u
+#define RDOOM_TRIGGER_ANY 4u
+#define RDOOM_TRIGGER_ONLY_ONCE 1u     /* rdoom_trigger.flags */
+#define RDOOM_TRIGGER_EXIT 2u
+#define RDOOM_TRIGGER_UNIMPLEMENTED 4u /* a special the metadata does not know: type ANY, no effects, never removed */
+#define RDOOM_ACTION_NONE 0u           /* rdoom_world_step_game's d_actions (player.rs:397-406: push before shoot) */
+#define RDOOM_ACTION_PUSH 1u
+#define RDOOM_ACTION_SHOOT 2u
+typedef struct rdoom_trigger {
+  float origin[2], displace[2], length; /* Line2f::from_two_points(start vertex, end vertex), world coordinates */
+  uint32_t trigger_type, flags, special_type;
+  uint32_t effect_start, effect_end;    /* its move effects: rdoom_world_trigger_arrays.effects[effect_start, effect_end) */
+} rdoom_trigger;
+typedef struct rdoom_move_effect {      /* MoveEffect (visitor.rs:212-236) */
+  uint32_t object_id;                   /* the floor or ceiling object it moves (>= 1) */
+  float first_height_offset, second_height_offset; /* from_wad_height(target - the sector's height); second valid iff has_second */
+  float speed, wait;                    /* speed: the metadata's / 8 * 0.7 per second; wait: seconds */
+  uint32_t has_second, repeat;          /* repeat: parsed, ignored by Level::update */
+} rdoom_move_effect;
+/* borrowed pointers into a rdoom_world (valid until rdoom_world_destroy) */
+typedef struct rdoom_world_trigger_arrays {
+  const rdoom_trigger *triggers;
+  uint32_t n_triggers;
+  const rdoom_move_effect *effects;
+  uint32_t n_effects;
+  uint32_t n_objects; /* the game's objects, max(1, LevelAnalysis::num_objects): >= the collision world's n_objects and
+                         >= rdoom_level_num_objects of the same level; the n_objects every game call needs at least */
+} rdoom_world_trigger_arrays;
+/* The trigger list and the move effects of the world's level.  Works on RDOOM_WORLD_HOST_ONLY worlds too. */
+rdoom_status rdoom_world_triggers(const rdoom_world *world, rdoom_world_trigger_arrays *out);
+/* The bytes of one player's game state (a multiple of 16).  N games live in one caller-owned device allocation of
+ * N * bytes_per_player bytes, 16-byte aligned, player p's at byte p * bytes_per_player; a game can be moved or copied
+ * bytewise.  Layout of one game, in 32-bit words, with T = n_triggers, O = n_objects, LW = ceil(T / 32), OW = ceil(O / 32):
+ *   [0]           the number of live triggers (the length of the player's list), [1..3] zero
+ *   live[LW]      bit t: trigger t (linedef order) is still in the list
+ *   fired[LW]     zero between calls (the poll's bookkeeping)
+ *   active[OW]    bit o: object o has an active effect
+ *   second[OW]    bit o: that effect still holds its second offset
+ *   order[T]      the list: entry i = the trigger at position i (the identity until an only_once trigger is removed)
+ *   (zero padding to 16 bytes)
+ *   effect[O]     4 floats per object: the active effect's first offset, second offset, wait left, speed */
+rdoom_status rdoom_world_game_bytes(const rdoom_world *world, uint64_t *bytes_per_player);
+/* A fresh level for player p of n wherever d_mask is NULL or d_mask[p] != 0 (d_mask: n bytes of device memory): every
+ * trigger live in linedef order, no active effect, and entries [p][0 .. n_objects) of d_object_offsets (n x n_objects x xyz,
+ * device memory) zero.  Other players' games and offsets are not touched.  Asynchronous on `stream`. */
+rdoom_status rdoom_world_game_reset(const rdoom_world *world, void *d_game, float *d_object_offsets, uint32_t n_objects, uint32_t n,
+                                    const uint8_t *d_mask, void *stream);
+/* n_ticks game ticks (see above) for n_players players in one launch, asynchronous on `stream`; every pointer is device memory.
+ * d_states, d_inputs, cfg, dt: as for rdoom_world_step_players.  d_actions: NULL (no action) or n_ticks x n_players bytes,
+ * entry [t * n_players + p] = RDOOM_ACTION_NONE / PUSH / SHOOT of player p at tick t (any other value is no action).
+ * d_game: n_players games (rdoom_world_game_bytes), read and written.  d_object_offsets: n_players x n_objects x xyz,
+ * n_objects >= rdoom_world_trigger_arrays.n_objects; the step reads every entry (the collision sweeps) and writes only the y
+ * of objects with an active effect, so the same array feeds rdoom_world_sweep, rdoom_world_step_players and
+ * rdoom_object_modelviews_from_player.  An exit trigger sets RDOOM_PLAYER_EXITED; the player keeps stepping in the same
+ * level.  Captured into a graph, it allocates and waits on nothing. */
+rdoom_status rdoom_world_step_game(const rdoom_world *world, rdoom_player_state *d_states, const rdoom_player_input *d_inputs,
+                                   const uint8_t *d_actions, void *d_game, float *d_object_offsets, uint32_t n_objects,
+                                   uint32_t n_players, uint32_t n_ticks, const rdoom_player_config *cfg, float dt, void *stream);
+/* The u_modelview of every object in the frame of a player at (pos, yaw, pitch), host arrays: out[o] (16 floats, column-major)
+ * = Matrix4::from(view.concat(model_o)) with model_o = Decomposed { scale 1, rot identity, disp = offsets[o] } in the
+ * reference's binary32 arithmetic (engine/src/renderer.rs:120-132), view as rdoom_pose_from_player builds it.  Object 0 (the
+ * static world) and every object whose offset is (0, 0, 0) get the pose's own modelview, bit for bit.  offsets: n_objects x xyz
+ * (one player's row of the step's d_object_offsets).  Ready for rdoom_batch_render_objects. */
+rdoom_status rdoom_object_modelviews_from_player(const float pos[3], float yaw, float pitch, const float *offsets, uint32_t n_objects,
+                                                 float *out);
+
 #ifdef __cplusplus
 }
 #endif

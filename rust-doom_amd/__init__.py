@@ -42,6 +42,16 @@ PLAYER_CONFIG = np.dtype([(n, '<f4') for n in ('move_force', 'spring_const_p', '
                                                'ground_drag', 'friction')])
 PLAYER_FLY, PLAYER_CLIP, PLAYER_DIVERGED = 1, 2, 0x100
 WORLD_HOST_ONLY = 1
+# doors, lifts and exits (include/rdoom.h rdoom_world_triggers / rdoom_world_step_game)
+PLAYER_EXITED = 0x200
+ACTION_NONE, ACTION_PUSH, ACTION_SHOOT = 0, 1, 2
+TRIGGER_WALK_OVER, TRIGGER_PUSH, TRIGGER_SWITCH, TRIGGER_GUN, TRIGGER_ANY = 0, 1, 2, 3, 4
+TRIGGER_ONLY_ONCE, TRIGGER_EXIT, TRIGGER_UNIMPLEMENTED = 1, 2, 4
+TRIGGER = np.dtype([('origin', '<f4', 2), ('displace', '<f4', 2), ('length', '<f4'), ('trigger_type', '<u4'), ('flags', '<u4'),
+                    ('special_type', '<u4'), ('effect_start', '<u4'), ('effect_end', '<u4')])
+MOVE_EFFECT = np.dtype([('object_id', '<u4'), ('first_height_offset', '<f4'), ('second_height_offset', '<f4'), ('speed', '<f4'),
+                        ('wait', '<f4'), ('has_second', '<u4'), ('repeat', '<u4')])
+assert TRIGGER.itemsize == 40 and MOVE_EFFECT.itemsize == 28
 assert PLAYER_STATE.itemsize == 40 and PLAYER_INPUT.itemsize == 20 and PLAYER_CONFIG.itemsize == 32
 
 
@@ -102,7 +112,8 @@ API_SYMBOLS = [
     'rdoom_wad_timings', 'rdoom_built_timings', 'rdoom_pose_from_player', 'rdoom_batch_framebuffer_pitch', 'rdoom_batch_path_stats',
     'rdoom_levelset_create', 'rdoom_level_num_levels', 'rdoom_batch_render_levels', 'rdoom_batch_resolve_rgb', 'rdoom_batch_read_rgb',
     'rdoom_world_create', 'rdoom_world_destroy', 'rdoom_world_host_arrays', 'rdoom_world_sweep', 'rdoom_world_step_players',
-    'rdoom_player_config_default']
+    'rdoom_player_config_default', 'rdoom_world_triggers', 'rdoom_world_game_bytes', 'rdoom_world_game_reset', 'rdoom_world_step_game',
+    'rdoom_object_modelviews_from_player']
 
 _lib = None
 
@@ -644,6 +655,11 @@ class WorldArrays(ctypes.Structure):
                 ('n_objects', ctypes.c_uint32), ('node_depth', ctypes.c_uint32)]
 
 
+class WorldTriggerArrays(ctypes.Structure):
+    _fields_ = [('triggers', ctypes.c_void_p), ('n_triggers', ctypes.c_uint32), ('effects', ctypes.c_void_p), ('n_effects', ctypes.c_uint32),
+                ('n_objects', ctypes.c_uint32)]
+
+
 WORLD_NODE = np.dtype([('origin', '<f4', 2), ('displace', '<f4', 2), ('length', '<f4'), ('positive', '<i4'), ('negative', '<i4')])
 
 
@@ -671,6 +687,26 @@ def poses_from_players(states, width, height, time=0.0):
     step, then this, then Batch.render"""
     states = np.asarray(states, PLAYER_STATE).reshape(-1)
     return np.array([pose_from_player(s['pos'], float(s['yaw']), float(s['pitch']), width, height, time) for s in states], POSE)
+
+
+def object_modelviews_from_players(states, offsets):
+    """the u_modelview of every object in every player's frame (rdoom_object_modelviews_from_player): states PLAYER_STATE records,
+    offsets (n, n_objects, 3) (numpy or a torch tensor, e.g. World.step_game's) -> (n, n_objects, 16) float32, ready for
+    Batch.render(object_modelviews=...)"""
+    states = np.asarray(states, PLAYER_STATE).reshape(-1)
+    if not isinstance(offsets, np.ndarray):
+        offsets = offsets.detach().cpu().numpy()
+    offsets = np.ascontiguousarray(offsets, np.float32)
+    if offsets.ndim != 3 or offsets.shape[0] != len(states) or offsets.shape[2] != 3:
+        raise ValueError('offsets must be (n, n_objects, 3) for %d players, got %s' % (len(states), offsets.shape))
+    n_obj = offsets.shape[1]
+    out = np.zeros((len(states), n_obj, 16), np.float32)
+    for i, s in enumerate(states):
+        pos = np.ascontiguousarray(s['pos'], np.float32)
+        _check(lib().rdoom_object_modelviews_from_player(pos.ctypes.data_as(ctypes.c_void_p), ctypes.c_float(s['yaw']),
+                                                         ctypes.c_float(s['pitch']), offsets[i].ctypes.data_as(ctypes.c_void_p), n_obj,
+                                                         out[i].ctypes.data_as(ctypes.c_void_p)))
+    return out
 
 
 def _stream_handle(stream):
@@ -702,6 +738,7 @@ class World:
         a = WorldArrays()
         _check(lib().rdoom_world_host_arrays(self._h, ctypes.byref(a)))
         self.n_objects, self.node_depth = a.n_objects, a.node_depth
+        self.game_objects = self.triggers()['n_objects']
 
     def close(self):
         if self._h:
@@ -787,3 +824,109 @@ class World:
         import torch
         torch.cuda.synchronize(ks.device)
         return ks.cpu().numpy().view(PLAYER_STATE).copy()
+
+    # ---- doors, lifts and exits --------------------------------------------------------------------------------------------
+    def triggers(self):
+        """copies of rdoom_world_triggers: triggers (TRIGGER records, linedef order), effects (MOVE_EFFECT records), n_objects
+        (the game's object count, the least n_objects of every game call)"""
+        a = WorldTriggerArrays()
+        _check(lib().rdoom_world_triggers(self._h, ctypes.byref(a)))
+        v = BuiltLevel._view
+        return dict(triggers=v(None, a.triggers, a.n_triggers, TRIGGER), effects=v(None, a.effects, a.n_effects, MOVE_EFFECT),
+                    n_objects=a.n_objects)
+
+    def game_bytes(self):
+        """rdoom_world_game_bytes: the bytes of one player's game state"""
+        b = ctypes.c_uint64()
+        _check(lib().rdoom_world_game_bytes(self._h, ctypes.byref(b)))
+        return b.value
+
+    def game_state(self, n, stream=None):
+        """(game, offsets) for n players on the current device, reset: game an int32 tensor of n * game_bytes / 4 words, offsets a
+        float32 (n, n_objects, 3) tensor"""
+        import torch
+        game = torch.zeros(n * self.game_bytes() // 4, dtype=torch.int32, device='cuda')
+        offsets = torch.zeros((n, self.game_objects, 3), dtype=torch.float32, device='cuda')
+        self.reset_game(game, offsets, stream=stream)
+        return game, offsets
+
+    def _game_args(self, game, offsets):
+        import torch
+        for t, what in ((game, 'game'), (offsets, 'offsets')):
+            if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or not t.is_contiguous():
+                raise ValueError('%s must be a contiguous tensor on the GPU' % what)
+        if offsets.dtype != torch.float32 or offsets.dim() != 3 or offsets.shape[2] != 3:
+            raise ValueError('offsets must be a float32 (n, n_objects, 3) tensor, got %s %s' % (offsets.dtype, tuple(offsets.shape)))
+        n = int(offsets.shape[0])
+        if game.numel() * game.element_size() != n * self.game_bytes():
+            raise ValueError('the game state must hold %d players x %d bytes' % (n, self.game_bytes()))
+        return n, int(offsets.shape[1])
+
+    def reset_game(self, game, offsets, mask=None, stream=None):
+        """rdoom_world_game_reset: a fresh level (all triggers live, no effect, zero offsets) for every player, or for those whose
+        mask entry is true (mask: n bools / bytes, numpy or a GPU tensor)"""
+        n, n_obj = self._game_args(game, offsets)
+        pm, km = None, None
+        if mask is not None:
+            if isinstance(mask, np.ndarray):
+                mask = np.ascontiguousarray(mask).astype(np.uint8)
+            pm, km, _ = _device_tensor(mask, 'mask')
+        _check(lib().rdoom_world_game_reset(self._h, ctypes.c_void_p(game.data_ptr()), ctypes.c_void_p(offsets.data_ptr()), n_obj, n,
+                                            ctypes.c_void_p(pm), ctypes.c_void_p(_stream_handle(stream))))
+        if km is not None:
+            import torch
+            torch.cuda.synchronize(km.device)
+
+    def step_game(self, states, inputs, game, offsets, actions=None, n_ticks=None, config=None, dt=1.0 / 60.0, stream=None):
+        """rdoom_world_step_game: n_ticks game ticks (physics, effects, triggers) for every player.  states / inputs / config / dt as
+        for step (numpy states: a stepped copy is returned; a GPU tensor is stepped in place, asynchronously).  game, offsets: from
+        game_state, on the GPU, read and written in place.  actions: None or (n_ticks, n) ACTION_* bytes (numpy or a GPU tensor)."""
+        if isinstance(actions, np.ndarray):
+            actions = np.ascontiguousarray(actions)
+            if actions.size and int(actions.max()) > ACTION_SHOOT:
+                raise RdoomError(-1, 'action %d is not ACTION_NONE / ACTION_PUSH / ACTION_SHOOT' % int(actions.max()))
+            actions = actions.astype(np.uint8)
+        is_np = isinstance(states, np.ndarray)
+        if is_np:
+            states = np.ascontiguousarray(states, PLAYER_STATE).reshape(-1)
+            n = len(states)
+        else:
+            if states.numel() * states.element_size() % PLAYER_STATE.itemsize:
+                raise ValueError('a states tensor must hold n * %d bytes' % PLAYER_STATE.itemsize)
+            n = states.numel() * states.element_size() // PLAYER_STATE.itemsize
+        if isinstance(inputs, np.ndarray):
+            inputs = np.ascontiguousarray(inputs, PLAYER_INPUT)
+            inputs = inputs.reshape(-1, n) if inputs.size else inputs.reshape(0, n)
+            if n_ticks is not None and n_ticks != inputs.shape[0]:
+                raise ValueError('n_ticks %d, but inputs for %d ticks' % (n_ticks, inputs.shape[0]))
+            n_ticks = inputs.shape[0]
+        elif n_ticks is None:
+            raise ValueError('n_ticks is needed with an input tensor')
+        if actions is not None:
+            size = actions.size if isinstance(actions, np.ndarray) else actions.numel() * actions.element_size()
+            if size != n_ticks * n:
+                raise ValueError('actions must be (n_ticks, n) = (%d, %d) bytes, got %d' % (n_ticks, n, size))
+        n_game, n_obj = self._game_args(game, offsets)
+        if n_game != n:
+            raise ValueError('%d players, but game state and offsets for %d' % (n, n_game))
+        ps, ks, _ = _device_tensor(states, 'states')
+        pi, ki, _ = _device_tensor(inputs, 'inputs')
+        pa, ka = None, None
+        if actions is not None:
+            pa, ka, _ = _device_tensor(actions, 'actions')
+        cfg = None
+        if config is not None:
+            cfg = np.ascontiguousarray(np.asarray(config, PLAYER_CONFIG).reshape(1))
+        _check(lib().rdoom_world_step_game(self._h, ctypes.c_void_p(ps), ctypes.c_void_p(pi), ctypes.c_void_p(pa),
+                                           ctypes.c_void_p(game.data_ptr()), ctypes.c_void_p(offsets.data_ptr()), n_obj, n, int(n_ticks),
+                                           cfg.ctypes.data_as(ctypes.c_void_p) if cfg is not None else None, ctypes.c_float(dt),
+                                           ctypes.c_void_p(_stream_handle(stream))))
+        if not is_np:
+            if ka is not None and isinstance(actions, np.ndarray):
+                import torch
+                torch.cuda.synchronize(ks.device)
+            return states
+        import torch
+        torch.cuda.synchronize(ks.device)
+        return ks.cpu().numpy().view(PLAYER_STATE).copy()
+

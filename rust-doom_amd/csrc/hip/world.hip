@@ -261,6 +261,7 @@ __global__ __launch_bounds__(WAVE) void sweep_kernel(WorldView w, const float *s
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }  // player.rs:415-423
 
+// (step_players below is a twin of this body for game_step_kernel: a change to the physics here belongs there too)
 __global__ __launch_bounds__(WAVE) void player_step_kernel(WorldView w, rdoom_player_state *states, const rdoom_player_input *inputs,
                                                            uint32_t n, uint32_t n_ticks, rdoom_player_config cfg, float dt,
                                                            const float *offsets, uint32_t n_objects) {
@@ -373,6 +374,342 @@ __global__ __launch_bounds__(WAVE) void player_step_kernel(WorldView w, rdoom_pl
   st->flags = flags;
 }
 
+// K ticks of Player::update (player.rs:359-396: force() with the feet probe and move_force, clip() or noclip(), then velocity
+// += force * dt) for player p: game_step_kernel's body.  After each tick `level.tick(t, pos, vel, yaw, pitch, flags)`
+// runs what the level does in the same tick (GameLevel below: effects and triggers).  The body is player_step_kernel's, which keeps
+// its own copy: calling this template from it changes its register allocation, and its code is meant to stay as it is.
+template <class Level>
+__device__ __forceinline__ void step_players(const WorldView &w, rdoom_player_state *states, const rdoom_player_input *inputs, uint32_t n,
+                                             uint32_t n_ticks, const rdoom_player_config &cfg, float dt, const float *offsets,
+                                             uint32_t n_objects, Level &level) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+  const uint32_t p = blockIdx.x * WAVE + threadIdx.x;
+  if (p >= n) return;
+  level.begin(p);
+  uint32_t *stack = lds_stack + threadIdx.x;
+  const float *off = offsets ? offsets + (size_t)p * n_objects * 3 : nullptr;
+  rdoom_player_state *st = states + p;
+  V3 pos = load3(st->pos), vel = load3(st->vel);
+  float yaw = st->yaw, pitch = st->pitch, last_height_diff = st->last_height_diff;
+  uint32_t flags = st->flags;
+  const bool fly = flags & RDOOM_PLAYER_FLY, clip = flags & RDOOM_PLAYER_CLIP;
+  const float pitch_limit = 1.57079637f - 1e-2f;  // FRAC_PI_2 - 1e-2 in binary32 (player.rs:196-201)
+  for (uint32_t t = 0; t < n_ticks; t++) {
+    const rdoom_player_input in = inputs[(size_t)t * n + p];
+    // ---- force() (player.rs:243-315): the feet probe
+    float height = cfg.height;
+    bool grounded = false;
+    V3 ground_normal = v3(0.0f, 0.0f, 0.0f);
+    {
+      const Contact c = sweep_world(w, pos, 0.2f, v3(0.0f, -cfg.height, 0.0f), off, stack);
+      if (c.time < __builtin_inff() && c.time < 1.0f) height = cfg.height * c.time, ground_normal = c.normal, grounded = true;
+    }
+    // move_force (player.rs:182-241), orientation as (yaw, pitch)
+    yaw = yaw - in.look[0];
+    pitch = clampf(pitch - in.look[1], -pitch_limit, pitch_limit);
+    float sy, cy, sp, cp;
+    sincos_rd(yaw, sy, cy);
+    sincos_rd(pitch, sp, cp);
+    V3 force;
+    if (fly) {  // rot * (normalize_or_zero(move.x, up, move.y) * move_force), rot = Ry(yaw) Rx(pitch)
+      const V3 m = normalize_or_zero(v3(in.movement[0], in.jump ? 0.5f : 0.0f, in.movement[1])) * cfg.move_force;
+      const float y1 = m.y * cp - m.z * sp, z1 = m.y * sp + m.z * cp;
+      force = v3(m.x * cy + z1 * sy, y1, z1 * cy - m.x * sy);
+    } else {  // normalize(Ry(yaw) (move.x, 0, move.y cos pitch)): the y the pitch adds is dropped before normalising
+      const float a = in.movement[1] * cp;
+      V3 m = normalize_or_zero(v3(in.movement[0] * cy + a * sy, 0.0f, a * cy - in.movement[0] * sy)) * cfg.move_force;
+      if (grounded) {
+        if (in.jump && vel.y < 0.1f) m = v3(m.x, 5.0f / dt, m.z);
+      } else {
+        m = m * 0.1f;
+      }
+      force = m;
+    }
+    const float speed = magnitude(vel);
+    if (speed > 0.0f) {
+      V3 slowdown = v3(0.0f, 0.0f, 0.0f);
+      if (fly) {
+        slowdown = (-vel) * (cfg.friction / speed + cfg.ground_drag * speed);
+      } else if (grounded) {
+        const V3 tangential = vel - ground_normal * dot(vel, ground_normal);
+        const float ts = magnitude(tangential);
+        if (ts > 0.0f) slowdown = (-tangential) * (cfg.friction / ts + cfg.ground_drag * ts);
+      }
+      slowdown = slowdown - vel * cfg.air_drag * speed;
+      const float slowdown_norm = magnitude(slowdown);
+      if (slowdown_norm > 0.0f) {
+        const float max_slowdown = -dot(vel, slowdown) / slowdown_norm / dt;
+        if (slowdown_norm >= max_slowdown) slowdown = slowdown / slowdown_norm * max_slowdown;
+        force = force + slowdown;
+      }
+    }
+    const float height_diff = cfg.height - height;
+    const float derivative = (height_diff - last_height_diff) / dt;
+    last_height_diff = height_diff;
+    force.y = force.y + (height_diff * cfg.spring_const_p + derivative * cfg.spring_const_d);
+    if (!fly) force.y = force.y - 17.0f;
+    // ---- clip() (player.rs:142-166) or noclip() (player.rs:168-190)
+    if (clip) {
+      float time_left = dt;
+      bool armed = true;
+      for (int i = 0; i < 100; i++) {
+        const V3 displacement = vel * time_left;
+        const Contact c = sweep_world(w, pos, cfg.radius, displacement, off, stack);
+        if (c.time < __builtin_inff()) {
+          const float adjusted_time = c.time - 0.001f / magnitude(displacement);
+          if (adjusted_time < 1.0f) {
+            const float time = clampf(c.time, 0.0f, 1.0f);
+            pos = pos + displacement * adjusted_time;
+            vel = vel - c.normal * dot(c.normal, vel);
+            time_left = time_left * (1.0f - time);
+            continue;
+          }
+        }
+        pos = pos + displacement;
+        armed = false;
+        break;
+      }
+      if (armed) flags |= RDOOM_PLAYER_DIVERGED;
+    } else {
+      const float old_height = pos.y;
+      pos = pos + vel * dt;
+      if (!fly) {
+        const float probe_height = 2000.0f;
+        const V3 probe = pos + v3(0.0f, probe_height / 2.0f, 0.0f);
+        const Contact c = sweep_world(w, probe, cfg.radius, v3(0.0f, -probe_height, 0.0f), off, stack);
+        const float h = c.time < __builtin_inff() ? pos.y + probe_height * (0.5f - c.time) : old_height;
+        if (pos.y <= h) {
+          pos.y = h;
+          if (vel.y < 0.0f) vel.y = 0.0f;
+        }
+      }
+    }
+    vel = vel + force * dt;
+    level.tick(t, pos, vel, yaw, pitch, flags);
+  }
+  st->pos[0] = pos.x, st->pos[1] = pos.y, st->pos[2] = pos.z;
+  st->vel[0] = vel.x, st->vel[1] = vel.y, st->vel[2] = vel.z;
+  st->yaw = yaw, st->pitch = pitch, st->last_height_diff = last_height_diff;
+  st->flags = flags;
+}
+
+
+// ---- doors, lifts and exits: Level::poll_triggers (game/src/level.rs:77-167) and the move effects of Level::update (:184-267)
+struct DevTrigger {  // rdoom_trigger's line, type, flags and effect range
+  float ox, oy, dx, dy, len;
+  uint32_t trigger_type, flags, effect_start, effect_end, _pad[3];
+};
+struct DevEffect {
+  uint32_t object_id, has_second;
+  float first, second, wait, speed, _pad[2];
+};
+struct GameView {  // the shared trigger list, and the word offsets of one game's fields (include/rdoom.h rdoom_world_game_bytes)
+  const DevTrigger *triggers;
+  const DevEffect *effects;
+  uint32_t n_triggers, n_objects;
+  uint32_t live, fired, active, second, order, effect, words;  // word offsets within a game; words per game
+};
+
+struct Line2 {  // Line2f (math/src/line.rs)
+  float ox, oy, dx, dy, len;
+};
+// Line2::from_origin_and_displace (line.rs:12-27)
+__device__ __forceinline__ Line2 line_from(float ox, float oy, float vx, float vy) {
+  const float len = __builtin_sqrtf(vx * vx + vy * vy);
+  if (__builtin_fabsf(len) >= 1e-16f) return Line2{ox, oy, vx / len, vy / len, len};
+  return Line2{ox, oy, 0.0f, 0.0f, 0.0f};
+}
+// a.segment_intersect_offset(b).is_some() (line.rs:47-84); a comparison with a NaN offset fails, as in the reference
+__device__ __forceinline__ bool segment_hits(const Line2 &a, float box, float boy, float bdx, float bdy, float blen) {
+  const float den = a.dx * bdy - a.dy * bdx;
+  if (__builtin_fabsf(den) < 1e-16f) return false;
+  const float off = ((box - a.ox) * bdy - (boy - a.oy) * bdx) / den;
+  if (off < 0.0f || off >= a.len) return false;
+  const float px = a.ox + a.dx * off, py = a.oy + a.dy * off;
+  const float other = __builtin_fabsf(bdx) > __builtin_fabsf(bdy) ? (px - box) / bdx : (py - boy) / bdy;
+  return !(other < 0.0f || other >= blen);
+}
+
+// One game's level: the per-player part of Level (effects, trigger list) in d_game, the offsets in the caller's array.  Trigger
+// lines and effect definitions are the same for every lane and read in linedef order (scalar loads); the list order is
+// resolved only on the rare tick when a lane fires two triggers or removes one.
+struct GameLevel {
+  GameView g;
+  uint32_t *games;
+  float *offsets;
+  const uint8_t *actions;
+  uint32_t n, n_objects;
+  float dt;
+  uint32_t *game;  // this lane's
+  float *off;
+  __device__ __forceinline__ void begin(uint32_t p) {
+    game = games + (size_t)p * g.words;
+    off = offsets + (size_t)p * n_objects * 3;
+    lane = p;
+  }
+  uint32_t lane;
+
+  // the loop of level.rs:203-255 for every active effect, ascending object id
+  __device__ __forceinline__ void advance() {
+    float4 *eff = reinterpret_cast<float4 *>(game + g.effect);
+    for (uint32_t wi = 0; wi * 32 < g.n_objects; wi++) {
+      uint32_t bits = game[g.active + wi];
+      if (!bits) continue;
+      uint32_t active = bits, second = game[g.second + wi];
+      while (bits) {
+        const uint32_t b = __builtin_ctz(bits);
+        bits &= bits - 1;
+        const uint32_t o = wi * 32 + b;
+        float4 e = eff[o];  // first, second, wait, speed
+        float *y = off + 3 * (size_t)o + 1;
+        float cur = *y, ts = dt;
+        bool has_second = (second >> b) & 1u, done = false;
+        for (;;) {
+          if (e.x != cur) {
+            const float diff = e.x - cur;
+            const float sign = __builtin_copysignf(1.0f, diff);
+            const float time_left = __builtin_fabsf(diff) / e.w;
+            if (time_left > ts) {
+              cur = cur + sign * e.w * ts;
+              break;
+            }
+            cur = e.x;
+            ts = ts - time_left;
+            e.x = cur;
+          }
+          if (e.z > ts) {
+            e.z = e.z - ts;
+            break;
+          }
+          ts = ts - e.z;
+          e.z = 0.0f;
+          if (has_second) {
+            e.x = e.y;
+            has_second = false;
+            continue;
+          }
+          done = true;
+          break;
+        }
+        *y = cur;
+        eff[o] = e;
+        if (done) active &= ~(1u << b);
+        if (!has_second) second &= ~(1u << b);
+      }
+      game[g.active + wi] = active;
+      game[g.second + wi] = second;
+    }
+  }
+
+  __device__ __forceinline__ void start_effects(uint32_t i) {  // self.effects.insert for each of trigger i's effects
+    const DevTrigger tr = g.triggers[i];
+    float4 *eff = reinterpret_cast<float4 *>(game + g.effect);
+    for (uint32_t k = tr.effect_start; k < tr.effect_end; k++) {
+      const DevEffect e = g.effects[k];
+      eff[e.object_id] = make_float4(e.first, e.second, e.wait, e.speed);
+      const uint32_t wi = e.object_id >> 5, bit = 1u << (e.object_id & 31);
+      game[g.active + wi] |= bit;
+      game[g.second + wi] = e.has_second ? game[g.second + wi] | bit : game[g.second + wi] & ~bit;
+    }
+  }
+
+  __device__ __forceinline__ void tick(uint32_t t, V3 pos, V3 vel, float yaw, float pitch, uint32_t &flags) {
+    advance();
+    // poll_triggers (level.rs:77-167) from the new position; moved = velocity * dt after this tick's update
+    const V3 moved = vel * dt;
+    const Line2 walked = line_from(pos.x, pos.z, -moved.x, -moved.z);
+    uint32_t action = actions ? actions[(size_t)t * n + lane] : 0u;
+    action = action <= RDOOM_ACTION_SHOOT ? action : RDOOM_ACTION_NONE;
+    Line2 act{pos.x, pos.z, 0.0f, 0.0f, 0.0f};
+    if (action) {  // look = rot.rotate_vector(-z), rot = Quaternion::from(Euler { pitch, yaw, 0 }) (api_common.cpp's cgmath formulas)
+      float sx, cx, sy, cy;
+      sincos_rd(pitch * 0.5f, sx, cx);
+      sincos_rd(yaw * 0.5f, sy, cy);
+      const float sz = 0.0f, cz = 1.0f;
+      const float qs = -sx * sy * sz + cx * cy * cz, qx = sx * cy * cz + sy * sz * cx, qy = -sx * sz * cy + sy * cx * cz,
+                  qz = sx * sy * cz + sz * cx * cy;
+      const V3 qv = v3(qx, qy, qz), v = v3(-0.0f, -0.0f, -1.0f);
+      const V3 tmp = cross(qv, v) + v * qs;
+      const V3 c2 = cross(qv, tmp);
+      const V3 look = v3(c2.x * 2.0f + v.x, c2.y * 2.0f + v.y, c2.z * 2.0f + v.z);
+      const float m = __builtin_sqrtf(look.x * look.x + look.z * look.z);
+      const float d = m > 1.1920929e-7f ? m : 1.1920929e-7f;
+      const float range = action == RDOOM_ACTION_PUSH ? 0.5f : 100.0f;
+      act = line_from(pos.x, pos.z, look.x / d * range, look.z / d * range);
+    }
+    const bool push = action == RDOOM_ACTION_PUSH, shoot = action == RDOOM_ACTION_SHOOT;
+    uint32_t n_fired = 0, first = 0;
+    bool reorder = false;
+    for (uint32_t i = 0; i < g.n_triggers; i++) {  // wave-uniform: every lane reads trigger i
+      const DevTrigger tr = g.triggers[i];
+      bool hit = false;
+      if (tr.trigger_type == RDOOM_TRIGGER_WALK_OVER || tr.trigger_type == RDOOM_TRIGGER_ANY) hit = segment_hits(walked, tr.ox, tr.oy, tr.dx, tr.dy, tr.len);
+      if (!hit && ((push && (tr.trigger_type == RDOOM_TRIGGER_PUSH || tr.trigger_type == RDOOM_TRIGGER_SWITCH || tr.trigger_type == RDOOM_TRIGGER_ANY)) ||
+                   (shoot && tr.trigger_type == RDOOM_TRIGGER_GUN)))
+        hit = segment_hits(act, tr.ox, tr.oy, tr.dx, tr.dy, tr.len);
+      if (!hit || !((game[g.live + (i >> 5)] >> (i & 31)) & 1u)) continue;
+      if (tr.flags & RDOOM_TRIGGER_EXIT) flags |= RDOOM_PLAYER_EXITED;
+      game[g.fired + (i >> 5)] |= 1u << (i & 31);
+      reorder |= n_fired > 0 || (tr.flags & RDOOM_TRIGGER_ONLY_ONCE);
+      first = n_fired ? first : i;
+      n_fired++;
+    }
+    if (!n_fired) return;
+    if (!reorder) {  // one trigger, not removed: its order does not matter
+      start_effects(first);
+      game[g.fired + (first >> 5)] = 0u;
+      return;
+    }
+    // the player's own order: effects in list order (a later trigger wins an object), then swap_remove descending
+    uint32_t count = game[0];
+    uint32_t *order = game + g.order;
+    for (uint32_t k = 0; k < count; k++) {
+      const uint32_t i = order[k];
+      if ((game[g.fired + (i >> 5)] >> (i & 31)) & 1u) start_effects(i);
+    }
+    for (uint32_t k = count; k-- > 0;) {
+      const uint32_t i = order[k];
+      if (!((game[g.fired + (i >> 5)] >> (i & 31)) & 1u)) continue;
+      game[g.fired + (i >> 5)] &= ~(1u << (i & 31));
+      if (g.triggers[i].flags & RDOOM_TRIGGER_ONLY_ONCE) {
+        order[k] = order[count - 1];
+        count--;
+        game[g.live + (i >> 5)] &= ~(1u << (i & 31));
+      }
+    }
+    game[0] = count;
+  }
+};
+
+// triggers / effects: level.g's, passed again as __restrict__ arguments -- nothing the kernel writes aliases them, so the
+// wave-uniform trigger loads of the poll can be scalar loads
+__global__ __launch_bounds__(WAVE) void game_step_kernel(WorldView w, GameLevel level, const DevTrigger *__restrict__ triggers,
+                                                         const DevEffect *__restrict__ effects, rdoom_player_state *states,
+                                                         const rdoom_player_input *inputs, uint32_t n_ticks, rdoom_player_config cfg) {
+  level.g.triggers = triggers;
+  level.g.effects = effects;
+  step_players(w, states, inputs, level.n, n_ticks, cfg, level.dt, level.offsets, level.n_objects, level);
+}
+
+// a fresh level for player blockIdx.x (if masked in): one workgroup per game, its lanes striding over the words
+__global__ __launch_bounds__(WAVE) void game_reset_kernel(GameView g, uint32_t *games, float *offsets, uint32_t n_objects,
+                                                          const uint8_t *mask) {
+  const uint32_t p = blockIdx.x;
+  if (mask && !mask[p]) return;
+  uint32_t *game = games + (size_t)p * g.words;
+  for (uint32_t k = threadIdx.x; k < g.words; k += WAVE) {
+    uint32_t v = 0u;
+    if (k == 0) v = g.n_triggers;
+    else if (k >= g.live && k < g.fired) {
+      const uint32_t first = (k - g.live) * 32;
+      v = g.n_triggers - first >= 32 ? ~0u : (1u << (g.n_triggers - first)) - 1u;
+    } else if (k >= g.order && k < g.order + g.n_triggers) v = k - g.order;
+    game[k] = v;
+  }
+  float *off = offsets + (size_t)p * n_objects * 3;
+  for (uint32_t k = threadIdx.x; k < n_objects * 3; k += WAVE) off[k] = 0.0f;
+}
+
 }  // namespace
 
 struct rdoom_world {
@@ -384,6 +721,8 @@ struct rdoom_world {
   uint4 *d_tris = nullptr;
   float *d_verts = nullptr;
   DevDynamic *d_dynamics = nullptr;
+  DevTrigger *d_triggers = nullptr;
+  DevEffect *d_effects = nullptr;
 };
 
 static_assert(sizeof(rdoom_world_node) == sizeof(rdoom::game::WorldNode) && sizeof(rdoom_world_chunk) == sizeof(rdoom::game::WorldChunk) &&
@@ -414,6 +753,24 @@ rdoom_status check_device(const rdoom_world *w) {
   return RDOOM_OK;
 }
 
+GameView game_view(const rdoom_world *w) {  // the layout include/rdoom.h documents at rdoom_world_game_bytes
+  const uint32_t t = (uint32_t)w->host.triggers.size(), o = w->host.game_objects;
+  const uint32_t lw = (t + 31) / 32, ow = (o + 31) / 32;
+  GameView g{w->d_triggers, w->d_effects, t, o, 4, 0, 0, 0, 0, 0, 0};
+  g.fired = g.live + lw, g.active = g.fired + lw, g.second = g.active + ow, g.order = g.second + ow;
+  g.effect = (g.order + t + 3) / 4 * 4;
+  g.words = g.effect + 4 * o;
+  return g;
+}
+
+rdoom_status check_game(const rdoom_world *w, const void *d_game, const float *d_offsets, uint32_t n_objects) {
+  if (!d_game || !d_offsets) return rdoom::fail(RDOOM_BAD_ARG, "null game state or object offsets");
+  if ((uintptr_t)d_game % 16) return rdoom::fail(RDOOM_BAD_ARG, "the game state is not 16-byte aligned");
+  if (n_objects < w->host.game_objects)
+    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the game's %u objects", n_objects, w->host.game_objects);
+  return RDOOM_OK;
+}
+
 rdoom_status check_offsets(const rdoom_world *w, const float *offsets, uint32_t n_objects) {
   if (offsets && n_objects < w->host.n_objects)
     return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the world's %u objects", n_objects, w->host.n_objects);
@@ -425,7 +782,8 @@ extern "C" {
 
 void rdoom_world_destroy(rdoom_world *w) {
   if (!w) return;
-  for (void *p : {(void *)w->d_nodes, (void *)w->d_chunks, (void *)w->d_tris, (void *)w->d_verts, (void *)w->d_dynamics})
+  for (void *p : {(void *)w->d_nodes, (void *)w->d_chunks, (void *)w->d_tris, (void *)w->d_verts, (void *)w->d_dynamics,
+                  (void *)w->d_triggers, (void *)w->d_effects})
     if (p) (void)hipFree(p);
   delete w;
 }
@@ -462,6 +820,18 @@ rdoom_status rdoom_world_create(const rdoom_wad *wad, uint32_t level_index, uint
     if (rdoom_status s = upload(&w->d_tris, h.triangles.data(), h.triangles.size() * sizeof(uint4))) return s;
     if (rdoom_status s = upload(&w->d_verts, h.verts.data(), h.verts.size() * sizeof(float))) return s;
     if (rdoom_status s = upload(&w->d_dynamics, dyn.data(), dyn.size() * sizeof(DevDynamic))) return s;
+    std::vector<DevTrigger> trig(h.triggers.size());
+    for (size_t i = 0; i < trig.size(); i++) {
+      const rdoom_trigger &t = h.triggers[i];
+      trig[i] = DevTrigger{t.origin[0], t.origin[1], t.displace[0], t.displace[1], t.length, t.trigger_type, t.flags, t.effect_start, t.effect_end, {0, 0, 0}};
+    }
+    std::vector<DevEffect> eff(h.effects.size());
+    for (size_t i = 0; i < eff.size(); i++) {
+      const rdoom_move_effect &e = h.effects[i];
+      eff[i] = DevEffect{e.object_id, e.has_second, e.first_height_offset, e.second_height_offset, e.wait, e.speed, {0.0f, 0.0f}};
+    }
+    if (rdoom_status s = upload(&w->d_triggers, trig.data(), trig.size() * sizeof(DevTrigger))) return s;
+    if (rdoom_status s = upload(&w->d_effects, eff.data(), eff.size() * sizeof(DevEffect))) return s;
     w->on_device = true;
   }
   *out_world = w.release();
@@ -525,6 +895,62 @@ rdoom_status rdoom_world_step_players(const rdoom_world *w, rdoom_player_state *
   hipLaunchKernelGGL(player_step_kernel, dim3((n_players + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
                      (hipStream_t)stream, v, d_states, d_inputs, n_players, n_ticks, c, dt == 0.0f ? 1.0f / 60.0f : dt, d_object_offsets,
                      n_objects);
+  HIP_TRY(hipGetLastError());
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_world_triggers(const rdoom_world *w, rdoom_world_trigger_arrays *out) {
+  if (!w || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  std::memset(out, 0, sizeof *out);
+  out->triggers = w->host.triggers.data();
+  out->n_triggers = (uint32_t)w->host.triggers.size();
+  out->effects = w->host.effects.data();
+  out->n_effects = (uint32_t)w->host.effects.size();
+  out->n_objects = w->host.game_objects;
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_world_game_bytes(const rdoom_world *w, uint64_t *bytes_per_player) {
+  if (!w || !bytes_per_player) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  *bytes_per_player = (uint64_t)game_view(w).words * sizeof(uint32_t);
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_world_game_reset(const rdoom_world *w, void *d_game, float *d_object_offsets, uint32_t n_objects, uint32_t n,
+                                    const uint8_t *d_mask, void *stream) {
+  if (!w) return rdoom::fail(RDOOM_BAD_ARG, "null world");
+  if (rdoom_status s = check_game(w, d_game, d_object_offsets, n_objects)) return s;
+  if (rdoom_status s = check_device(w)) return s;
+  if (!n) return RDOOM_OK;
+  hipLaunchKernelGGL(game_reset_kernel, dim3(n), dim3(WAVE), 0, (hipStream_t)stream, game_view(w), (uint32_t *)d_game, d_object_offsets,
+                     n_objects, d_mask);
+  HIP_TRY(hipGetLastError());
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_world_step_game(const rdoom_world *w, rdoom_player_state *d_states, const rdoom_player_input *d_inputs,
+                                   const uint8_t *d_actions, void *d_game, float *d_object_offsets, uint32_t n_objects,
+                                   uint32_t n_players, uint32_t n_ticks, const rdoom_player_config *cfg, float dt, void *stream) {
+  if (!w) return rdoom::fail(RDOOM_BAD_ARG, "null world");
+  if (n_players && (!d_states || (n_ticks && !d_inputs)))
+    return rdoom::fail(RDOOM_BAD_ARG, "null states or inputs with n_players = %u", n_players);
+  if (!(dt >= 0.0f) || dt == __builtin_inff()) return rdoom::fail(RDOOM_BAD_ARG, "dt %g is not a finite non-negative number", (double)dt);
+  if (rdoom_status s = check_game(w, d_game, d_object_offsets, n_objects)) return s;
+  if (rdoom_status s = check_device(w)) return s;
+  if (!n_players || !n_ticks) return RDOOM_OK;
+  rdoom_player_config c;
+  if (cfg) c = *cfg;
+  else rdoom_player_config_default(&c);
+  const WorldView v = view(w);
+  GameLevel level{};
+  level.g = game_view(w);
+  level.games = (uint32_t *)d_game;
+  level.offsets = d_object_offsets;
+  level.actions = d_actions;
+  level.n = n_players, level.n_objects = n_objects;
+  level.dt = dt == 0.0f ? 1.0f / 60.0f : dt;
+  hipLaunchKernelGGL(game_step_kernel, dim3((n_players + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
+                     (hipStream_t)stream, v, level, level.g.triggers, level.g.effects, d_states, d_inputs, n_ticks, c);
   HIP_TRY(hipGetLastError());
   return RDOOM_OK;
 }

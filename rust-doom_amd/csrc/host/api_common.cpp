@@ -113,9 +113,14 @@ Quat qmul(Quat a, Quat b) {  // impl Mul for Quaternion
 }
 }  // namespace
 
-rdoom_status rdoom_pose_from_player(const float pos[3], float yaw, float pitch, uint32_t width, uint32_t height, float time,
-                                    rdoom_pose *out) {
-  if (!pos || !out || width == 0 || height == 0) return rdoom::fail(RDOOM_BAD_ARG, "bad argument");
+namespace {
+struct View {  // Decomposed { scale s, rot r, disp d }
+  float s;
+  Quat r;
+  V3 d;
+};
+// the player's camera, inverted: view = (player.concat(camera)).inverse_transform()
+View player_view(const float pos[3], float yaw, float pitch) {
   // Quaternion::from(Euler { x: pitch, y: yaw, z: 0 })
   const float sx = sinf(pitch * 0.5f), cx = cosf(pitch * 0.5f), sy = sinf(yaw * 0.5f), cy = cosf(yaw * 0.5f), sz = sinf(0.0f * 0.5f),
               cz = cosf(0.0f * 0.5f);
@@ -135,16 +140,29 @@ rdoom_status rdoom_pose_from_player(const float pos[3], float yaw, float pitch, 
   const float mag2 = rot.s * rot.s + vv;
   const Quat r{rot.s / mag2, -rot.x / mag2, -rot.y / mag2, -rot.z / mag2};
   const V3 rd = rotate(r, disp);
-  const V3 d{rd.x * -s, rd.y * -s, rd.z * -s};
-  // Matrix4::from(Decomposed): Matrix3::from(rot) * scale, w = disp
+  return View{s, r, V3{rd.x * -s, rd.y * -s, rd.z * -s}};
+}
+// Matrix4::from(Decomposed): Matrix3::from(rot) * scale, w = disp
+void matrix_of(const View &v, float out[16]) {
+  const Quat &r = v.r;
+  const float s = v.s;
+  const V3 &d = v.d;
   const float x2 = r.x + r.x, y2 = r.y + r.y, z2 = r.z + r.z;
   const float xx2 = x2 * r.x, xy2 = x2 * r.y, xz2 = x2 * r.z, yy2 = y2 * r.y, yz2 = y2 * r.z, zz2 = z2 * r.z;
   const float sy2 = y2 * r.s, sz2 = z2 * r.s, sx2 = x2 * r.s;
   const float m3[9] = {1.0f - yy2 - zz2, xy2 + sz2, xz2 - sy2, xy2 - sz2, 1.0f - xx2 - zz2, yz2 + sx2, xz2 + sy2, yz2 - sx2, 1.0f - xx2 - yy2};
-  std::memset(out, 0, sizeof *out);
+  std::memset(out, 0, 16 * sizeof(float));
   for (int c = 0; c < 3; c++)
-    for (int rr = 0; rr < 3; rr++) out->modelview[c * 4 + rr] = m3[c * 3 + rr] * s;
-  out->modelview[12] = d.x, out->modelview[13] = d.y, out->modelview[14] = d.z, out->modelview[15] = 1.0f;
+    for (int rr = 0; rr < 3; rr++) out[c * 4 + rr] = m3[c * 3 + rr] * s;
+  out[12] = d.x, out[13] = d.y, out[14] = d.z, out[15] = 1.0f;
+}
+}  // namespace
+
+rdoom_status rdoom_pose_from_player(const float pos[3], float yaw, float pitch, uint32_t width, uint32_t height, float time,
+                                    rdoom_pose *out) {
+  if (!pos || !out || width == 0 || height == 0) return rdoom::fail(RDOOM_BAD_ARG, "bad argument");
+  std::memset(out, 0, sizeof *out);
+  matrix_of(player_view(pos, yaw, pitch), out->modelview);
   // cgmath::perspective: f = cot(fovy / 2) in binary32, fovy = Rad::from(Deg(65))
   const float fovy = 65.0f * (float)(M_PI / 180.0), near_ = 0.01f, far_ = 100.0f;
   const float aspect = ((float)width / (float)height) * 1.2f;
@@ -155,6 +173,28 @@ rdoom_status rdoom_pose_from_player(const float pos[3], float yaw, float pitch, 
   out->projection[11] = -1.0f;
   out->projection[14] = (2.0f * far_ * near_) / (near_ - far_);
   out->time = time;
+  return RDOOM_OK;
+}
+
+// view.concat(model_o) (engine/src/renderer.rs:120-132), model_o = Decomposed { scale 1, rot identity, disp offsets[o] }:
+// scale = s * 1, rot = r * identity, disp = r.rotate(disp_o * s) + d
+rdoom_status rdoom_object_modelviews_from_player(const float pos[3], float yaw, float pitch, const float *offsets, uint32_t n_objects,
+                                                 float *out) {
+  if (!pos || !out || (n_objects && !offsets)) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  const View view = player_view(pos, yaw, pitch);
+  float own[16];
+  matrix_of(view, own);
+  const Quat identity{1.0f, 0.0f, 0.0f, 0.0f};
+  for (uint32_t o = 0; o < n_objects; o++) {
+    const float *off = offsets + 3 * (size_t)o;
+    float *m = out + 16 * (size_t)o;
+    if (o == 0 || (off[0] == 0.0f && off[1] == 0.0f && off[2] == 0.0f)) {  // the static world / an object at rest: the view itself
+      std::memcpy(m, own, sizeof own);
+      continue;
+    }
+    const V3 rd = rotate(view.r, V3{off[0] * view.s, off[1] * view.s, off[2] * view.s});
+    matrix_of(View{view.s * 1.0f, qmul(view.r, identity), V3{rd.x + view.d.x, rd.y + view.d.y, rd.z + view.d.z}}, m);
+  }
   return RDOOM_OK;
 }
 

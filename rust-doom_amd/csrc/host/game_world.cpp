@@ -121,9 +121,30 @@ class WorldBuilder : public LevelVisitor {
 }  // namespace
 
 World build_world(const LoadedWad &w, size_t level_index) {
+  const Archive &archive = *w.archive;  // walk_level, keeping the analysis for the triggers
+  const Level level = Level::from_archive(archive, level_index);
+  const LevelAnalysis analysis(level, archive.metadata());
   WorldBuilder b;
-  walk_level(w, level_index, b);
-  return b.build();
+  LevelWalker(level, analysis, w.textures, archive.metadata(), b).walk();
+  World out = b.build();
+  out.game_objects = (uint32_t)std::max<size_t>(1, analysis.num_objects());
+  for (const Trigger &t : analysis.triggers()) {
+    rdoom_trigger r{};
+    r.origin[0] = t.line.origin.x, r.origin[1] = t.line.origin.y;
+    r.displace[0] = t.line.displace.x, r.displace[1] = t.line.displace.y;
+    r.length = t.line.length;
+    r.trigger_type = (uint32_t)t.type;
+    r.flags = (t.only_once ? RDOOM_TRIGGER_ONLY_ONCE : 0u) | (t.exit ? RDOOM_TRIGGER_EXIT : 0u) |
+              (t.unimplemented ? RDOOM_TRIGGER_UNIMPLEMENTED : 0u);
+    r.special_type = t.special_type;
+    r.effect_start = (uint32_t)out.effects.size();
+    for (const MoveEffect &e : t.effects)
+      out.effects.push_back(rdoom_move_effect{e.object_id.v, e.first_height_offset, e.second_height_offset.value_or(0.0f), e.speed, e.wait,
+                                              e.second_height_offset.has_value(), e.repeat});
+    r.effect_end = (uint32_t)out.effects.size();
+    out.triggers.push_back(r);
+  }
+  return out;
 }
 
 }  // namespace rdoom::game

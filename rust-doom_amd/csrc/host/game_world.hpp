@@ -34,6 +34,10 @@ struct World {
   uint32_t n_static_triangles = 0;
   uint32_t n_objects = 1;    // 1 + the largest ObjectId of a dynamic chunk
   uint32_t node_depth = 0;   // nodes on the longest root-to-node path
+  // the level's triggers and their move effects (LevelAnalysis of the same walk), as the C ABI lays them out
+  std::vector<rdoom_trigger> triggers;
+  std::vector<rdoom_move_effect> effects;
+  uint32_t game_objects = 1;  // max(1, LevelAnalysis::num_objects)
 };
 
 // WorldBuilder::new + LevelWalker::walk + WorldBuilder::build.  Throws WadError(RDOOM_BAD_LEVEL) on a level without a BSP.

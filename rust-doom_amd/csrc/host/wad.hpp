@@ -423,11 +423,30 @@ struct DynamicSectorInfo {  // visitor.rs:158-165
   std::optional<std::pair<int16_t, int16_t>> floor_range, ceiling_range;
 };
 
+// level.rs Trigger / MoveEffect (visitor.rs:63-100): what a linedef special does when the player walks over, pushes or shoots it
+enum class TriggerType : uint8_t { WalkOver, Push, Switch, Gun, Any };
+struct MoveEffect {  // visitor.rs:212-236: heights relative to the sector's own, from_wad_height of the i16 difference
+  ObjectId object_id;
+  float first_height_offset = 0.0f;
+  std::optional<float> second_height_offset;
+  float speed = 0.0f, wait = 0.0f;
+  bool repeat = false;
+};
+struct Trigger {  // linedef_to_trigger (visitor.rs:446-496) + the effects DynamicSectorInfo::update pushes
+  Line2f line;
+  TriggerType type = TriggerType::Any;
+  uint16_t special_type = 0;
+  bool only_once = false, exit = false, unimplemented = false;
+  std::vector<MoveEffect> effects;
+};
+
 class LevelAnalysis {  // visitor.rs:316-497
  public:
   LevelAnalysis(const Level &level, const WadMetadata &meta);
   size_t num_objects() const { return num_objects_; }
-  size_t num_triggers() const { return num_triggers_; }
+  size_t num_triggers() const { return triggers_.size(); }
+  // one per linedef with a special and both vertices, in linedef order; none at all when no sector is tagged (visitor.rs:360-364)
+  const std::vector<Trigger> &triggers() const { return triggers_; }
   const DynamicSectorInfo *dynamic(uint16_t sector_id) const {
     auto it = dynamic_info_.find(sector_id);
     return it == dynamic_info_.end() ? nullptr : &it->second;
@@ -435,7 +454,8 @@ class LevelAnalysis {  // visitor.rs:316-497
 
  private:
   std::map<uint16_t, DynamicSectorInfo> dynamic_info_;
-  size_t num_objects_ = 0, num_triggers_ = 0;
+  std::vector<Trigger> triggers_;
+  size_t num_objects_ = 0;
 };
 
 struct SectorInfo {  // visitor.rs:145-156

@@ -102,7 +102,7 @@ void merge_range(std::optional<std::pair<int16_t, int16_t>> &range, int16_t curr
 }
 
 void update_dynamic(DynamicSectorInfo &info, uint32_t &next_id, const Level &level, uint16_t sector_id,
-                    const std::optional<MoveEffectDef> &move) {  // DynamicSectorInfo::update :168-244
+                    const std::optional<MoveEffectDef> &move, Trigger &trigger) {  // DynamicSectorInfo::update :168-244
   if (!move) return;
   const WadSector &sector = level.sectors[sector_id];
   if (!info.neighbour_heights) {
@@ -124,6 +124,16 @@ void update_dynamic(DynamicSectorInfo &info, uint32_t &next_id, const Level &lev
   merge_range(info.ceiling_range, sector.ceiling_height, fc, sc);
   if (info.ceiling_range && info.ceiling_id.v == 0) info.ceiling_id.v = next_id++;
   if (info.floor_range && info.floor_id.v == 0) info.floor_id.v = next_id++;
+  auto effect = [&](ObjectId id, int16_t current, int16_t first, const std::optional<int16_t> &second) {  // :224-243
+    MoveEffect e;
+    e.object_id = id;
+    e.first_height_offset = from_wad_height((int16_t)(first - current));
+    if (second) e.second_height_offset = from_wad_height((int16_t)(*second - current));
+    e.speed = move->speed, e.wait = move->wait, e.repeat = move->repeat;
+    trigger.effects.push_back(e);
+  };
+  if (ff) effect(info.floor_id, sector.floor_height, *ff, sf);
+  if (fc) effect(info.ceiling_id, sector.ceiling_height, *fc, sc);
 }
 }  // namespace
 
@@ -136,22 +146,39 @@ LevelAnalysis::LevelAnalysis(const Level &level, const WadMetadata &meta) {
   uint32_t next_id = 1;
   for (const WadLinedef &ld : level.linedefs) {
     if (ld.special_type == 0) continue;
-    if (!level.vertex(ld.start_vertex) || !level.vertex(ld.end_vertex)) continue;
+    const std::optional<Pnt2f> start = level.vertex(ld.start_vertex), end = level.vertex(ld.end_vertex);
+    if (!start || !end) continue;
     auto it = meta.linedef.find(ld.special_type);
     const std::optional<MoveEffectDef> none;
     const std::optional<MoveEffectDef> &move = it != meta.linedef.end() ? it->second.move_effect : none;
-    num_triggers_++;
+    Trigger trigger;  // linedef_to_trigger (:446-496): an unknown special is an Any trigger without effects
+    trigger.line = Line2f::from_two_points(*start, *end);
+    trigger.special_type = ld.special_type;
+    if (it != meta.linedef.end()) {
+      const std::string &t = it->second.trigger;
+      trigger.type = t == "WalkOver" ? TriggerType::WalkOver
+                     : t == "Push"   ? TriggerType::Push
+                     : t == "Switch" ? TriggerType::Switch
+                     : t == "Gun"    ? TriggerType::Gun
+                                     : TriggerType::Any;
+      trigger.only_once = it->second.only_once;
+      trigger.exit = it->second.exit_effect.has_value();
+    } else {
+      trigger.unimplemented = true;
+    }
     if (ld.sector_tag == 0) {  // manual linedef: acts on its left sector (visitor.rs:385-404)
       // (a left side naming a sector that does not exist: the reference indexes level.sectors[id], visitor.rs:175 -- a
       // panic; defined here as the warn-and-skip the walker applies to every other dangling reference)
       if (const WadSidedef *left = level.side(ld.left_side))
         if (left->sector < level.sectors.size())
-          update_dynamic(dynamic_info_[left->sector], next_id, level, left->sector, move);
+          update_dynamic(dynamic_info_[left->sector], next_id, level, left->sector, move, trigger);
+      triggers_.push_back(std::move(trigger));
       continue;
     }
     auto first = std::lower_bound(tags.begin(), tags.end(), std::make_pair(ld.sector_tag, (uint16_t)0));
     for (; first != tags.end() && first->first == ld.sector_tag; ++first)
-      update_dynamic(dynamic_info_[first->second], next_id, level, first->second, move);
+      update_dynamic(dynamic_info_[first->second], next_id, level, first->second, move, trigger);
+    triggers_.push_back(std::move(trigger));
   }
   num_objects_ = next_id;
 }

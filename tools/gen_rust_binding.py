@@ -49,7 +49,7 @@ def rust_type(ctype, names):
 
 def parse(text):
     text = strip_comments(text)
-    consts = re.findall(r'^#define\s+(RDOOM_[A-Z0-9_]+)\s+\(?(-?(?:0x[0-9A-Fa-f]+|\d+))u?\)?\s*$', text, flags=re.M)
+    consts = re.findall(r'^#define\s+(RDOOM_[A-Z0-9_]+)\s+\(?(-?(?:0x[0-9A-Fa-f]+|\d+))(u?)\)?\s*$', text, flags=re.M)
     opaque = re.findall(r'^typedef struct (\w+) (\w+);\s*$', text, flags=re.M)
     structs = re.findall(r'typedef struct (\w+) \{(.*?)\} (\w+);', text, flags=re.S)
     enums = re.findall(r'enum \{(.*?)\};', text, flags=re.S)
@@ -98,8 +98,8 @@ def generate():
     names = set(opaque) | {s[2] for s in structs}
     lines = ['// rdoom-sys/src/lib.rs -- GENERATED from include/rdoom.h by tools/gen_rust_binding.py; do not edit',
              '#![allow(non_camel_case_types)]', 'use std::os::raw::{c_char, c_void};', '', 'pub type rdoom_status = i32;']
-    for name, value in consts:
-        ty = 'rdoom_status' if int(value, 0) <= 0 and 'KIND' not in name else 'u32'
+    for name, value, unsigned in consts:  # an unsigned-suffixed constant is a u32 even when it is 0; a bare one <= 0 is a status
+        ty = 'rdoom_status' if int(value, 0) <= 0 and not unsigned else 'u32'
         lines.append('pub const %s: %s = %s;' % (name, ty, value))
     for body in enums:
         for item in [i.strip() for i in body.split(',') if i.strip()]:

@@ -5,8 +5,11 @@ centroids with the scripted inputs of tests/test_gpu_world.py (walk, strafe, jum
 launch of all the ticks, bracketed by torch.cuda.synchronize (the median of --steps launches after --warmup); next to it, the
 test-side C restatement (tests/world_restatement.c, gcc -O2) on 16 host threads, timed once.  Prints a table and one JSON
 line per row: microseconds per player-tick.  Needs the GPU and torch.
+--game also times rdoom_world_step_game (doors, lifts and exits, DESIGN section "Doors, lifts and exits") on the same players and
+inputs with about 5 % push actions, each launch from a freshly reset level, next to the test-side restatement
+(tests/game_restatement.c) on the same host threads.
 
-    python tools/player_step_cost.py [--steps K] [--warmup W] [--ticks T]
+    python tools/player_step_cost.py [--steps K] [--warmup W] [--ticks T] [--game]
 """
 import argparse
 import importlib
@@ -27,6 +30,7 @@ def main():
     ap.add_argument('--warmup', type=int, default=1)
     ap.add_argument('--ticks', type=int, default=60)
     ap.add_argument('--threads', type=int, default=16)
+    ap.add_argument('--game', action='store_true')
     a = ap.parse_args()
     import numpy as np
     import torch
@@ -61,16 +65,55 @@ def main():
             cpu = time.perf_counter() - t0
             same = bool(np.array_equal(s_dev.cpu().numpy(), np.ascontiguousarray(want).view(np.uint8)))
             pt = n * a.ticks
-            rows.append(dict(level=label, players=n, ticks=a.ticks, gpu_us_per_player_tick=gpu * 1e6 / pt,
-                             cpu_us_per_player_tick=cpu * 1e6 / pt, cpu_threads=a.threads, gpu_ms=gpu * 1e3, cpu_ms=cpu * 1e3,
-                             bit_exact=same))
+            row = dict(level=label, players=n, ticks=a.ticks, gpu_us_per_player_tick=gpu * 1e6 / pt,
+                       cpu_us_per_player_tick=cpu * 1e6 / pt, cpu_threads=a.threads, gpu_ms=gpu * 1e3, cpu_ms=cpu * 1e3, bit_exact=same)
+            if a.game:
+                row.update(_game(a, world, ref, st, inp, s0, i_dev, n))
+            rows.append(row)
     print('%-6s %8s %6s %14s %14s %8s %6s' % ('level', 'players', 'ticks', 'GPU us/p-tick', 'CPU us/p-tick', 'speedup', 'exact'))
     for r in rows:
         print('%-6s %8d %6d %14.4f %14.4f %8.1f %6s' % (r['level'], r['players'], r['ticks'], r['gpu_us_per_player_tick'],
                                                        r['cpu_us_per_player_tick'], r['cpu_us_per_player_tick'] / r['gpu_us_per_player_tick'],
                                                        r['bit_exact']))
+    if a.game:
+        print('%-6s %8s %6s %14s %14s %10s %6s' % ('level', 'players', 'ticks', 'game us/p-t', 'CPU us/p-t', 'game/plain', 'exact'))
+        for r in rows:
+            print('%-6s %8d %6d %14.4f %14.4f %10.2f %6s' % (r['level'], r['players'], r['ticks'], r['game_gpu_us_per_player_tick'],
+                                                            r['game_cpu_us_per_player_tick'],
+                                                            r['game_gpu_us_per_player_tick'] / r['gpu_us_per_player_tick'], r['game_bit_exact']))
     for r in rows:
         print(json.dumps(r))
+
+
+def _game(a, world, ref, st, inp, s0, i_dev, n):
+    import numpy as np
+    import torch
+
+    import game_ref
+    act = (np.random.default_rng(n + 1).random((a.ticks, n)) < 0.05).astype(np.uint8)  # ACTION_PUSH on ~5 % of the ticks
+    a_dev = torch.from_numpy(act.reshape(-1).copy()).cuda()
+    game, offs = world.game_state(n)
+    times = []
+    for k in range(a.warmup + a.steps):
+        s_dev = s0.clone()
+        world.reset_game(game, offs)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        world.step_game(s_dev, i_dev, game, offs, actions=a_dev, n_ticks=a.ticks)
+        torch.cuda.synchronize()
+        if k >= a.warmup:
+            times.append(time.perf_counter() - t0)
+    gpu = float(np.median(times))
+    t = world.triggers()
+    rg = game_ref.RefGame(ref, t['triggers'], t['effects'], n, world.game_objects)
+    t0 = time.perf_counter()
+    want = rg.step(st, inp, act, threads=a.threads)
+    cpu = time.perf_counter() - t0
+    same = bool(np.array_equal(s_dev.cpu().numpy(), np.ascontiguousarray(want).view(np.uint8))) and \
+        bool(np.array_equal(offs.cpu().numpy(), rg.offsets))
+    pt = n * a.ticks
+    return dict(game_gpu_us_per_player_tick=gpu * 1e6 / pt, game_cpu_us_per_player_tick=cpu * 1e6 / pt, game_gpu_ms=gpu * 1e3,
+                game_cpu_ms=cpu * 1e3, game_bit_exact=same, triggers=len(t['triggers']))
 
 
 if __name__ == '__main__':
