@@ -498,8 +498,8 @@ rdoom_status rdoom_player_config_default(rdoom_player_config *out);
  * tick, then every active effect advances by dt in ascending object id, then the triggers are polled from the new position
  * (walked line = -(velocity * dt) in the xz plane; a push / shoot action looks 0.5 / 100 along the camera's view).  An
  * only_once trigger that fired is swap_remove'd from the player's list after the poll, so each game keeps its own order.
- * Changing level on an exit trigger, teleports, monsters, damage and light effects are not simulated. */
-#define RDOOM_PLAYER_EXITED 0x200u /* sticky: an exit trigger fired for this player (set by rdoom_world_step_game only) */
+ * Teleports, monsters, damage and light effects are not simulated; changing level on an exit is the world sets' (below). */
+#define RDOOM_PLAYER_EXITED 0x200u /* sticky: an exit trigger fired for this player (set by the game steps only) */
 #define RDOOM_TRIGGER_WALK_OVER 0u /* rdoom_trigger.trigger_type (meta.rs TriggerType) */
 #define RDOOM_TRIGGER_PUSH 1u
 #define RDOOM_TRIGGER_SWITCH 2u
@@ -561,6 +561,59 @@ rdoom_status rdoom_world_game_reset(const rdoom_world *world, void *d_game, floa
 rdoom_status rdoom_world_step_game(const rdoom_world *world, rdoom_player_state *d_states, const rdoom_player_input *d_inputs,
                                    const uint8_t *d_actions, void *d_game, float *d_object_offsets, uint32_t n_objects,
                                    uint32_t n_players, uint32_t n_ticks, const rdoom_player_config *cfg, float dt, void *stream);
+/* ---- world sets: several levels, and the exit that takes a player to the next -----------------------------------------
+ * A rdoom_worldset holds the collision worlds and trigger lists of several levels, each built as rdoom_world_create builds it;
+ * every player is in one of them (a device uint32 per player: its slot, the level_of_pose that rdoom_batch_render_levels takes
+ * for a level set of the same list).  A game tick is rdoom_world_step_game's tick on the player's level, plus the level change
+ * of the reference (game/src/level.rs:194-199, wad_system.rs:118-156, player.rs:118-133, 359-362): an exit trigger fires in
+ * the poll of tick t; tick t + 1 still runs in the old level (effects advance, triggers fire); at the start of tick t + 2 the
+ * player's slot becomes the destination, its game is fresh (every trigger live, no effect, offsets zero) and its state is
+ * Player::reset's (pos = start, yaw = start yaw, pitch = 1e-8, velocity 0, last_height_diff 0; FLY / CLIP kept), then the tick
+ * runs in the new level.  Slot s holds archive level level_indices[s]; its destination is the slot holding archive level
+ * level_indices[s] + 1.  A slot without one (the archive's last level, or a gap in the list) keeps its players: an exit there
+ * sets RDOOM_PLAYER_EXITED and nothing else, exactly as rdoom_world_step_game (the reference keeps its current level too, but
+ * with its Level already removed; that broken state is not reproduced). */
+typedef struct rdoom_worldset rdoom_worldset;
+#define RDOOM_WORLDSET_NO_DESTINATION 0xFFFFFFFFu
+typedef struct rdoom_worldset_level_info {
+  uint32_t archive_index;   /* the level's index in the archive */
+  uint32_t destination;     /* the slot an exit leads to, or RDOOM_WORLDSET_NO_DESTINATION */
+  float start_pos[3];       /* Player::reset's position and yaw: rdoom_built_start of the same level */
+  float start_yaw;
+  uint32_t n_triggers;
+  uint32_t n_objects;       /* the level's game objects (rdoom_world_trigger_arrays.n_objects) */
+  uint32_t node_depth;
+  rdoom_world_arrays world;                /* borrowed, valid until rdoom_worldset_destroy: the level's own arrays and indices, */
+  rdoom_world_trigger_arrays triggers;     /* equal to rdoom_world_host_arrays / rdoom_world_triggers of the level */
+} rdoom_worldset_level_info;
+/* n_levels distinct archive level indices (n_levels >= 1; an empty list, an index out of range or a duplicate is
+ * RDOOM_BAD_ARG).  flags: RDOOM_WORLD_HOST_ONLY builds the host arrays only (the game calls then return RDOOM_BAD_ARG). */
+rdoom_status rdoom_worldset_create(const rdoom_wad *wad, const uint32_t *level_indices, uint32_t n_levels, uint32_t flags,
+                                   rdoom_worldset **out_set);
+void rdoom_worldset_destroy(rdoom_worldset *set);
+/* out_n_objects: the set's game objects, the largest of its levels' (>= rdoom_level_num_objects of a level set of the same list);
+ * the n_objects every set game call needs at least.  Either output may be NULL. */
+rdoom_status rdoom_worldset_info(const rdoom_worldset *set, uint32_t *out_n_levels, uint32_t *out_n_objects);
+rdoom_status rdoom_worldset_level(const rdoom_worldset *set, uint32_t slot, rdoom_worldset_level_info *out);
+/* The bytes of one player's game in the set (a multiple of 16): the largest of its levels' rdoom_world_game_bytes.  A game holds
+ * the layout of rdoom_world_game_bytes for the player's current level, with that level's T and O, and zero words after it.
+ * Word 1 is the level change: 0 none, 1 an exit fired in the last tick, 2 the next tick loads the destination. */
+rdoom_status rdoom_worldset_game_bytes(const rdoom_worldset *set, uint64_t *bytes_per_player);
+/* A fresh game of its current level (d_levels[p]) for player p of n wherever d_mask is NULL or d_mask[p] != 0, and its
+ * d_object_offsets row zero.  d_levels: n uint32 of device memory; a player whose slot is >= the set's size is not touched.
+ * Asynchronous on `stream`. */
+rdoom_status rdoom_worldset_game_reset(const rdoom_worldset *set, void *d_game, float *d_object_offsets, uint32_t n_objects,
+                                       const uint32_t *d_levels, uint32_t n, const uint8_t *d_mask, void *stream);
+/* n_ticks game ticks for n_players players in one launch, asynchronous on `stream`; arguments as rdoom_world_step_game's, with
+ * d_game (rdoom_worldset_game_bytes per player) and n_objects >= rdoom_worldset_info's.  d_levels: n_players uint32 of device
+ * memory, read and written: each player's slot, changed by the level change above.  A player whose slot is >= the set's size is
+ * left untouched (state, game, offsets and slot).  K launches of one tick equal one launch of K ticks.  Captured into a graph,
+ * it allocates and waits on nothing. */
+rdoom_status rdoom_worldset_step_game(const rdoom_worldset *set, rdoom_player_state *d_states, const rdoom_player_input *d_inputs,
+                                      const uint8_t *d_actions, void *d_game, float *d_object_offsets, uint32_t n_objects,
+                                      uint32_t *d_levels, uint32_t n_players, uint32_t n_ticks, const rdoom_player_config *cfg,
+                                      float dt, void *stream);
+
 /* The u_modelview of every object in the frame of a player at (pos, yaw, pitch), host arrays: out[o] (16 floats, column-major)
  * = Matrix4::from(view.concat(model_o)) with model_o = Decomposed { scale 1, rot identity, disp = offsets[o] } in the
  * reference's binary32 arithmetic (engine/src/renderer.rs:120-132), view as rdoom_pose_from_player builds it.  Object 0 (the

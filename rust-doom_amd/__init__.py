@@ -52,6 +52,10 @@ TRIGGER = np.dtype([('origin', '<f4', 2), ('displace', '<f4', 2), ('length', '<f
 MOVE_EFFECT = np.dtype([('object_id', '<u4'), ('first_height_offset', '<f4'), ('second_height_offset', '<f4'), ('speed', '<f4'),
                         ('wait', '<f4'), ('has_second', '<u4'), ('repeat', '<u4')])
 assert TRIGGER.itemsize == 40 and MOVE_EFFECT.itemsize == 28
+# world sets (include/rdoom.h rdoom_worldset_*): one slot per level, and the level each exit leads to
+WORLDSET_NO_DESTINATION = 0xFFFFFFFF
+WORLDSET_LEVEL = np.dtype([('archive_index', '<u4'), ('destination', '<u4'), ('start_pos', '<f4', 3), ('start_yaw', '<f4'),
+                           ('n_triggers', '<u4'), ('n_objects', '<u4'), ('node_depth', '<u4')])
 assert PLAYER_STATE.itemsize == 40 and PLAYER_INPUT.itemsize == 20 and PLAYER_CONFIG.itemsize == 32
 
 
@@ -113,7 +117,8 @@ API_SYMBOLS = [
     'rdoom_levelset_create', 'rdoom_level_num_levels', 'rdoom_batch_render_levels', 'rdoom_batch_resolve_rgb', 'rdoom_batch_read_rgb',
     'rdoom_world_create', 'rdoom_world_destroy', 'rdoom_world_host_arrays', 'rdoom_world_sweep', 'rdoom_world_step_players',
     'rdoom_player_config_default', 'rdoom_world_triggers', 'rdoom_world_game_bytes', 'rdoom_world_game_reset', 'rdoom_world_step_game',
-    'rdoom_object_modelviews_from_player']
+    'rdoom_object_modelviews_from_player', 'rdoom_worldset_create', 'rdoom_worldset_destroy', 'rdoom_worldset_info',
+    'rdoom_worldset_level', 'rdoom_worldset_game_bytes', 'rdoom_worldset_game_reset', 'rdoom_worldset_step_game']
 
 _lib = None
 
@@ -130,7 +135,7 @@ def lib():
         for name in API_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ('rdoom_last_error', 'rdoom_level_destroy', 'rdoom_batch_destroy', 'rdoom_wad_close',
-                            'rdoom_built_destroy', 'rdoom_world_destroy'):
+                            'rdoom_built_destroy', 'rdoom_world_destroy', 'rdoom_worldset_destroy'):
                 fn.restype = ctypes.c_int32
             elif name != 'rdoom_last_error':
                 fn.restype = None
@@ -353,6 +358,10 @@ class Wad:
     def build_world(self, index, device=True):
         """game::world::WorldBuilder over level `index` (game/src/world.rs:211-409) -> World; device=False keeps it on the host"""
         return World(self, index, device)
+
+    def build_world_set(self, indices, device=True):
+        """a WorldSet of these archive levels (rdoom_worldset_create): slot s holds level indices[s]"""
+        return WorldSet(self, indices, device)
 
     def walk(self, index, visitor):
         """WadSystem::walk (game/src/wad_system.rs:47-56) with the caller's visitor only"""
@@ -727,6 +736,62 @@ def _device_tensor(a, what):
     return t.data_ptr(), t, True
 
 
+class _GameStepArgs:
+    """the arguments of a game step (World.step_game, WorldSet.step_game), checked and on the device: states PLAYER_STATE records
+    (numpy: a stepped copy is returned) or a GPU tensor of n * 40 bytes (stepped in place); inputs (n_ticks, n) PLAYER_INPUT
+    records, or a GPU tensor with n_ticks given; actions None or (n_ticks, n) ACTION_* bytes; config a PLAYER_CONFIG or None"""
+
+    def __init__(self, states, inputs, actions, n_ticks, config):
+        if isinstance(actions, np.ndarray):
+            actions = np.ascontiguousarray(actions)
+            if actions.size and int(actions.max()) > ACTION_SHOOT:
+                raise RdoomError(-1, 'action %d is not ACTION_NONE / ACTION_PUSH / ACTION_SHOOT' % int(actions.max()))
+            actions = actions.astype(np.uint8)
+        self.is_np = isinstance(states, np.ndarray)
+        if self.is_np:
+            states = np.ascontiguousarray(states, PLAYER_STATE).reshape(-1)
+            n = len(states)
+        else:
+            if states.numel() * states.element_size() % PLAYER_STATE.itemsize:
+                raise ValueError('a states tensor must hold n * %d bytes' % PLAYER_STATE.itemsize)
+            n = states.numel() * states.element_size() // PLAYER_STATE.itemsize
+        if isinstance(inputs, np.ndarray):
+            inputs = np.ascontiguousarray(inputs, PLAYER_INPUT)
+            inputs = inputs.reshape(-1, n) if inputs.size else inputs.reshape(0, n)
+            if n_ticks is not None and n_ticks != inputs.shape[0]:
+                raise ValueError('n_ticks %d, but inputs for %d ticks' % (n_ticks, inputs.shape[0]))
+            n_ticks = inputs.shape[0]
+        elif n_ticks is None:
+            raise ValueError('n_ticks is needed with an input tensor')
+        if actions is not None:
+            size = actions.size if isinstance(actions, np.ndarray) else actions.numel() * actions.element_size()
+            if size != n_ticks * n:
+                raise ValueError('actions must be (n_ticks, n) = (%d, %d) bytes, got %d' % (n_ticks, n, size))
+        self.states, self.n, self.n_ticks, self.actions = states, n, n_ticks, actions
+        self.ps, self.ks, _ = _device_tensor(states, 'states')
+        self.pi, self.ki, _ = _device_tensor(inputs, 'inputs')
+        self.pa, self.ka = None, None
+        if actions is not None:
+            self.pa, self.ka, _ = _device_tensor(actions, 'actions')
+        self.cfg = None
+        if config is not None:
+            self.cfg = np.ascontiguousarray(np.asarray(config, PLAYER_CONFIG).reshape(1))
+
+    def cfg_ptr(self):
+        return self.cfg.ctypes.data_as(ctypes.c_void_p) if self.cfg is not None else None
+
+    def result(self):
+        """after the launch: the states tensor, or a stepped numpy copy"""
+        if not self.is_np:
+            if self.ka is not None and isinstance(self.actions, np.ndarray):
+                import torch
+                torch.cuda.synchronize(self.ks.device)
+            return self.states
+        import torch
+        torch.cuda.synchronize(self.ks.device)
+        return self.ks.cpu().numpy().view(PLAYER_STATE).copy()
+
+
 class World:
     """game::world::World on the host and the current device (rdoom_world_create): World::sweep_sphere for a batch of queries,
     Player::update for a batch of players."""
@@ -881,52 +946,145 @@ class World:
         """rdoom_world_step_game: n_ticks game ticks (physics, effects, triggers) for every player.  states / inputs / config / dt as
         for step (numpy states: a stepped copy is returned; a GPU tensor is stepped in place, asynchronously).  game, offsets: from
         game_state, on the GPU, read and written in place.  actions: None or (n_ticks, n) ACTION_* bytes (numpy or a GPU tensor)."""
-        if isinstance(actions, np.ndarray):
-            actions = np.ascontiguousarray(actions)
-            if actions.size and int(actions.max()) > ACTION_SHOOT:
-                raise RdoomError(-1, 'action %d is not ACTION_NONE / ACTION_PUSH / ACTION_SHOOT' % int(actions.max()))
-            actions = actions.astype(np.uint8)
-        is_np = isinstance(states, np.ndarray)
-        if is_np:
-            states = np.ascontiguousarray(states, PLAYER_STATE).reshape(-1)
-            n = len(states)
-        else:
-            if states.numel() * states.element_size() % PLAYER_STATE.itemsize:
-                raise ValueError('a states tensor must hold n * %d bytes' % PLAYER_STATE.itemsize)
-            n = states.numel() * states.element_size() // PLAYER_STATE.itemsize
-        if isinstance(inputs, np.ndarray):
-            inputs = np.ascontiguousarray(inputs, PLAYER_INPUT)
-            inputs = inputs.reshape(-1, n) if inputs.size else inputs.reshape(0, n)
-            if n_ticks is not None and n_ticks != inputs.shape[0]:
-                raise ValueError('n_ticks %d, but inputs for %d ticks' % (n_ticks, inputs.shape[0]))
-            n_ticks = inputs.shape[0]
-        elif n_ticks is None:
-            raise ValueError('n_ticks is needed with an input tensor')
-        if actions is not None:
-            size = actions.size if isinstance(actions, np.ndarray) else actions.numel() * actions.element_size()
-            if size != n_ticks * n:
-                raise ValueError('actions must be (n_ticks, n) = (%d, %d) bytes, got %d' % (n_ticks, n, size))
+        a = _GameStepArgs(states, inputs, actions, n_ticks, config)
         n_game, n_obj = self._game_args(game, offsets)
-        if n_game != n:
-            raise ValueError('%d players, but game state and offsets for %d' % (n, n_game))
-        ps, ks, _ = _device_tensor(states, 'states')
-        pi, ki, _ = _device_tensor(inputs, 'inputs')
-        pa, ka = None, None
-        if actions is not None:
-            pa, ka, _ = _device_tensor(actions, 'actions')
-        cfg = None
-        if config is not None:
-            cfg = np.ascontiguousarray(np.asarray(config, PLAYER_CONFIG).reshape(1))
-        _check(lib().rdoom_world_step_game(self._h, ctypes.c_void_p(ps), ctypes.c_void_p(pi), ctypes.c_void_p(pa),
-                                           ctypes.c_void_p(game.data_ptr()), ctypes.c_void_p(offsets.data_ptr()), n_obj, n, int(n_ticks),
-                                           cfg.ctypes.data_as(ctypes.c_void_p) if cfg is not None else None, ctypes.c_float(dt),
-                                           ctypes.c_void_p(_stream_handle(stream))))
-        if not is_np:
-            if ka is not None and isinstance(actions, np.ndarray):
-                import torch
-                torch.cuda.synchronize(ks.device)
-            return states
-        import torch
-        torch.cuda.synchronize(ks.device)
-        return ks.cpu().numpy().view(PLAYER_STATE).copy()
+        if n_game != a.n:
+            raise ValueError('%d players, but game state and offsets for %d' % (a.n, n_game))
+        _check(lib().rdoom_world_step_game(self._h, ctypes.c_void_p(a.ps), ctypes.c_void_p(a.pi), ctypes.c_void_p(a.pa),
+                                           ctypes.c_void_p(game.data_ptr()), ctypes.c_void_p(offsets.data_ptr()), n_obj, a.n,
+                                           int(a.n_ticks), a.cfg_ptr(), ctypes.c_float(dt), ctypes.c_void_p(_stream_handle(stream))))
+        return a.result()
 
+
+class WorldSetLevelInfo(ctypes.Structure):
+    _fields_ = [('archive_index', ctypes.c_uint32), ('destination', ctypes.c_uint32), ('start_pos', ctypes.c_float * 3),
+                ('start_yaw', ctypes.c_float), ('n_triggers', ctypes.c_uint32), ('n_objects', ctypes.c_uint32),
+                ('node_depth', ctypes.c_uint32), ('world', WorldArrays), ('triggers', WorldTriggerArrays)]
+
+
+class WorldSet:
+    """several levels' collision worlds and trigger lists (rdoom_worldset_create), each player in one of them: the game step takes a
+    player who uses an exit to the slot of the next archive level, the way the reference changes level.  Slot s holds archive
+    level indices[s]; a player's slot is the level_of_pose of a DeviceLevelSet built from the same list."""
+
+    def __init__(self, wad, indices, device=True):
+        self._h = ctypes.c_void_p()
+        self._wad = wad
+        idx = np.ascontiguousarray(np.asarray(indices, np.int64).reshape(-1))
+        if idx.size and (idx.min() < 0 or idx.max() > 0xFFFFFFFF):
+            raise RdoomError(-1, 'level index out of range')
+        idx = idx.astype(np.uint32)
+        _check(lib().rdoom_worldset_create(wad._h, _ptr(idx), len(idx), 0 if device else WORLD_HOST_ONLY, ctypes.byref(self._h)))
+        n_levels, n_obj = ctypes.c_uint32(), ctypes.c_uint32()
+        _check(lib().rdoom_worldset_info(self._h, ctypes.byref(n_levels), ctypes.byref(n_obj)))
+        self.n_levels, self.n_objects = n_levels.value, n_obj.value
+
+    def close(self):
+        if self._h:
+            lib().rdoom_worldset_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        _close_quietly(self)
+
+    def _info(self, slot):
+        info = WorldSetLevelInfo()
+        _check(lib().rdoom_worldset_level(self._h, int(slot), ctypes.byref(info)))
+        return info
+
+    def levels(self):
+        """the per-level table: a WORLDSET_LEVEL record per slot (archive index, destination slot or WORLDSET_NO_DESTINATION, start
+        position and yaw, triggers, game objects, BSP depth)"""
+        out = np.zeros(self.n_levels, WORLDSET_LEVEL)
+        for s in range(self.n_levels):
+            i = self._info(s)
+            out[s] = (i.archive_index, i.destination, tuple(i.start_pos), i.start_yaw, i.n_triggers, i.n_objects, i.node_depth)
+        return out
+
+    def arrays(self, slot):
+        """copies of slot `slot`'s collision arrays, in its own indices: World.arrays of the same level"""
+        a = self._info(slot).world
+        v = BuiltLevel._view
+        return dict(nodes=v(None, a.nodes, a.n_nodes, WORLD_NODE), chunks=v(None, a.chunks, a.n_chunks * 2, np.uint32).reshape(-1, 2),
+                    triangles=v(None, a.triangles, a.n_triangles * 4, np.uint32).reshape(-1, 4),
+                    verts=v(None, a.verts, a.n_verts * 3, np.float32).reshape(-1, 3),
+                    dynamics=v(None, a.dynamics, a.n_dynamics * 3, np.uint32).reshape(-1, 3),
+                    n_static_triangles=a.n_static_triangles, n_objects=a.n_objects, node_depth=a.node_depth)
+
+    def triggers(self, slot):
+        """copies of slot `slot`'s trigger list and move effects: World.triggers of the same level"""
+        a = self._info(slot).triggers
+        v = BuiltLevel._view
+        return dict(triggers=v(None, a.triggers, a.n_triggers, TRIGGER), effects=v(None, a.effects, a.n_effects, MOVE_EFFECT),
+                    n_objects=a.n_objects)
+
+    def start_states(self, levels, flags=PLAYER_CLIP):
+        """PLAYER_STATE records at the start of each player's level, as Player::reset leaves them (pitch 1e-8, at rest)"""
+        levels = np.asarray(levels, np.int64).reshape(-1)
+        table = self.levels()
+        return player_states(table['start_pos'][levels], table['start_yaw'][levels], flags=flags)
+
+    def game_bytes(self):
+        """rdoom_worldset_game_bytes: the bytes of one player's game (the largest level's)"""
+        b = ctypes.c_uint64()
+        _check(lib().rdoom_worldset_game_bytes(self._h, ctypes.byref(b)))
+        return b.value
+
+    def game_state(self, levels, stream=None):
+        """(game, offsets, levels) for the players of `levels` (their slots: numpy or a GPU tensor), on the current device, reset:
+        game an int32 tensor of n * game_bytes / 4 words, offsets a float32 (n, n_objects, 3) tensor, levels an int32 tensor of
+        the slots (the step's and Batch.render's level_of_pose)"""
+        import torch
+        if isinstance(levels, torch.Tensor):
+            levels = levels.to(device='cuda', dtype=torch.int32).contiguous().clone()
+        else:
+            levels = torch.from_numpy(np.ascontiguousarray(np.asarray(levels, np.int64).reshape(-1).astype(np.int32))).cuda()
+        n = int(levels.numel())
+        game = torch.zeros(n * self.game_bytes() // 4, dtype=torch.int32, device='cuda')
+        offsets = torch.zeros((n, self.n_objects, 3), dtype=torch.float32, device='cuda')
+        self.reset_game(game, offsets, levels, stream=stream)
+        return game, offsets, levels
+
+    def _game_args(self, game, offsets, levels):
+        import torch
+        for t, what in ((game, 'game'), (offsets, 'offsets'), (levels, 'levels')):
+            if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or not t.is_contiguous():
+                raise ValueError('%s must be a contiguous tensor on the GPU' % what)
+        if offsets.dtype != torch.float32 or offsets.dim() != 3 or offsets.shape[2] != 3:
+            raise ValueError('offsets must be a float32 (n, n_objects, 3) tensor, got %s %s' % (offsets.dtype, tuple(offsets.shape)))
+        n = int(offsets.shape[0])
+        if game.numel() * game.element_size() != n * self.game_bytes():
+            raise ValueError('the game state must hold %d players x %d bytes' % (n, self.game_bytes()))
+        if levels.element_size() != 4 or levels.numel() != n:
+            raise ValueError('levels must hold one 32-bit slot per player (%d), got %s %s' % (n, levels.dtype, tuple(levels.shape)))
+        return n, int(offsets.shape[1])
+
+    def reset_game(self, game, offsets, levels, mask=None, stream=None):
+        """rdoom_worldset_game_reset: a fresh game of its current level for every player (levels: a GPU tensor of slots), or for
+        those whose mask entry is true (mask: n bools / bytes, numpy or a GPU tensor)"""
+        n, n_obj = self._game_args(game, offsets, levels)
+        pm, km = None, None
+        if mask is not None:
+            if isinstance(mask, np.ndarray):
+                mask = np.ascontiguousarray(mask).astype(np.uint8)
+            pm, km, _ = _device_tensor(mask, 'mask')
+        _check(lib().rdoom_worldset_game_reset(self._h, ctypes.c_void_p(game.data_ptr()), ctypes.c_void_p(offsets.data_ptr()), n_obj,
+                                               ctypes.c_void_p(levels.data_ptr()), n, ctypes.c_void_p(pm),
+                                               ctypes.c_void_p(_stream_handle(stream))))
+        if km is not None:
+            import torch
+            torch.cuda.synchronize(km.device)
+
+    def step_game(self, states, inputs, game, offsets, levels, actions=None, n_ticks=None, config=None, dt=1.0 / 60.0, stream=None):
+        """rdoom_worldset_step_game: n_ticks game ticks for every player on its level, with the level change on an exit.  states /
+        inputs / actions / config / dt as for World.step_game (numpy states: a stepped copy is returned; a GPU tensor is stepped in
+        place, asynchronously).  game, offsets, levels: from game_state, on the GPU, read and written in place."""
+        a = _GameStepArgs(states, inputs, actions, n_ticks, config)
+        n_game, n_obj = self._game_args(game, offsets, levels)
+        if n_game != a.n:
+            raise ValueError('%d players, but game state and offsets for %d' % (a.n, n_game))
+        _check(lib().rdoom_worldset_step_game(self._h, ctypes.c_void_p(a.ps), ctypes.c_void_p(a.pi), ctypes.c_void_p(a.pa),
+                                              ctypes.c_void_p(game.data_ptr()), ctypes.c_void_p(offsets.data_ptr()), n_obj,
+                                              ctypes.c_void_p(levels.data_ptr()), a.n, int(a.n_ticks), a.cfg_ptr(), ctypes.c_float(dt),
+                                              ctypes.c_void_p(_stream_handle(stream))))
+        return a.result()

@@ -12,6 +12,7 @@
 // create time, so nothing is spilled to scratch.  The world's arrays are read-only and shared by every lane.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <cstring>
 #include <memory>
 
@@ -197,11 +198,12 @@ __device__ __forceinline__ void sweep_chunk(const WorldView &w, Contact &first, 
 
 // World::sweep_sphere (world.rs:40-82).  `stack`: this lane's first LDS word (stride WAVE).  `offsets`: this query's
 // n_objects x xyz object displacements, or null.  time = +inf: None.
+// `root`: the root node (a world set's level starts at its node base).
 __device__ __forceinline__ Contact sweep_world(const WorldView &w, V3 center, float radius, V3 vel, const float *offsets,
-                                               uint32_t *stack) {
+                                               uint32_t *stack, uint32_t root = 0u) {
   Contact first{__builtin_inff(), v3(0.0f, 0.0f, 0.0f)};
   uint32_t sp = 0;
-  stack[0] = 0u;
+  stack[0] = root;
   sp = 1;
   while (sp) {  // statics: positive child first; leaves are swept when met, nodes pushed
     const DevNode node = w.nodes[stack[--sp * WAVE]];
@@ -375,9 +377,12 @@ __global__ __launch_bounds__(WAVE) void player_step_kernel(WorldView w, rdoom_pl
 }
 
 // K ticks of Player::update (player.rs:359-396: force() with the feet probe and move_force, clip() or noclip(), then velocity
-// += force * dt) for player p: game_step_kernel's body.  After each tick `level.tick(t, pos, vel, yaw, pitch, flags)`
-// runs what the level does in the same tick (GameLevel below: effects and triggers).  The body is player_step_kernel's, which keeps
-// its own copy: calling this template from it changes its register allocation, and its code is meant to stay as it is.
+// += force * dt) for player p: the body of game_step_kernel and worldset_game_step_kernel.  `level.begin(p)` false: player p is
+// left untouched.  When `level.start_tick()` is true, the player starts the tick afresh at `level.start_pos()` (SetGame below: a
+// level change); the tick's sweeps see `level.world(w)` from node `level.root()`.  After each tick
+// `level.tick(t, pos, vel, yaw, pitch, flags)` runs what the level does in the same tick (GameLevel below: effects and triggers).
+// The body is player_step_kernel's, which keeps its own copy: calling this template from it changes its register allocation, and
+// its code is meant to stay as it is.
 template <class Level>
 __device__ __forceinline__ void step_players(const WorldView &w, rdoom_player_state *states, const rdoom_player_input *inputs, uint32_t n,
                                              uint32_t n_ticks, const rdoom_player_config &cfg, float dt, const float *offsets,
@@ -385,7 +390,7 @@ __device__ __forceinline__ void step_players(const WorldView &w, rdoom_player_st
   extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
   const uint32_t p = blockIdx.x * WAVE + threadIdx.x;
   if (p >= n) return;
-  level.begin(p);
+  if (!level.begin(p)) return;
   uint32_t *stack = lds_stack + threadIdx.x;
   const float *off = offsets ? offsets + (size_t)p * n_objects * 3 : nullptr;
   rdoom_player_state *st = states + p;
@@ -395,13 +400,19 @@ __device__ __forceinline__ void step_players(const WorldView &w, rdoom_player_st
   const bool fly = flags & RDOOM_PLAYER_FLY, clip = flags & RDOOM_PLAYER_CLIP;
   const float pitch_limit = 1.57079637f - 1e-2f;  // FRAC_PI_2 - 1e-2 in binary32 (player.rs:196-201)
   for (uint32_t t = 0; t < n_ticks; t++) {
+    if (level.start_tick()) {  // Player::reset (player.rs:118-133) at the new level's start
+      pos = level.start_pos(), vel = v3(0.0f, 0.0f, 0.0f);
+      yaw = level.start_yaw(), pitch = 1e-8f, last_height_diff = 0.0f;
+    }
     const rdoom_player_input in = inputs[(size_t)t * n + p];
+    const WorldView &wt = level.world(w);
+    const uint32_t root = level.root();
     // ---- force() (player.rs:243-315): the feet probe
     float height = cfg.height;
     bool grounded = false;
     V3 ground_normal = v3(0.0f, 0.0f, 0.0f);
     {
-      const Contact c = sweep_world(w, pos, 0.2f, v3(0.0f, -cfg.height, 0.0f), off, stack);
+      const Contact c = sweep_world(wt, pos, 0.2f, v3(0.0f, -cfg.height, 0.0f), off, stack, root);
       if (c.time < __builtin_inff() && c.time < 1.0f) height = cfg.height * c.time, ground_normal = c.normal, grounded = true;
     }
     // move_force (player.rs:182-241), orientation as (yaw, pitch)
@@ -454,7 +465,7 @@ __device__ __forceinline__ void step_players(const WorldView &w, rdoom_player_st
       bool armed = true;
       for (int i = 0; i < 100; i++) {
         const V3 displacement = vel * time_left;
-        const Contact c = sweep_world(w, pos, cfg.radius, displacement, off, stack);
+        const Contact c = sweep_world(wt, pos, cfg.radius, displacement, off, stack, root);
         if (c.time < __builtin_inff()) {
           const float adjusted_time = c.time - 0.001f / magnitude(displacement);
           if (adjusted_time < 1.0f) {
@@ -476,7 +487,7 @@ __device__ __forceinline__ void step_players(const WorldView &w, rdoom_player_st
       if (!fly) {
         const float probe_height = 2000.0f;
         const V3 probe = pos + v3(0.0f, probe_height / 2.0f, 0.0f);
-        const Contact c = sweep_world(w, probe, cfg.radius, v3(0.0f, -probe_height, 0.0f), off, stack);
+        const Contact c = sweep_world(wt, probe, cfg.radius, v3(0.0f, -probe_height, 0.0f), off, stack, root);
         const float h = c.time < __builtin_inff() ? pos.y + probe_height * (0.5f - c.time) : old_height;
         if (pos.y <= h) {
           pos.y = h;
@@ -542,12 +553,19 @@ struct GameLevel {
   float dt;
   uint32_t *game;  // this lane's
   float *off;
-  __device__ __forceinline__ void begin(uint32_t p) {
+  __device__ __forceinline__ bool begin(uint32_t p) {
     game = games + (size_t)p * g.words;
     off = offsets + (size_t)p * n_objects * 3;
     lane = p;
+    return true;
   }
   uint32_t lane;
+  // one level for every tick (step_players' hooks)
+  __device__ __forceinline__ bool start_tick() { return false; }
+  __device__ __forceinline__ V3 start_pos() const { return v3(0.0f, 0.0f, 0.0f); }
+  __device__ __forceinline__ float start_yaw() const { return 0.0f; }
+  __device__ __forceinline__ const WorldView &world(const WorldView &w) const { return w; }
+  __device__ __forceinline__ uint32_t root() const { return 0u; }
 
   // the loop of level.rs:203-255 for every active effect, ascending object id
   __device__ __forceinline__ void advance() {
@@ -710,6 +728,127 @@ __global__ __launch_bounds__(WAVE) void game_reset_kernel(GameView g, uint32_t *
   for (uint32_t k = threadIdx.x; k < n_objects * 3; k += WAVE) off[k] = 0.0f;
 }
 
+
+// ---- a world set: several levels, each player in one of them, and the exit that takes a player to the next
+struct DevSetLevel {  // one slot of a world set: where its arrays start in the concatenation, its game layout, its start
+  uint32_t root, dyn_start, n_dynamics, destination;  // destination: a slot, or rdoom::game::NO_DESTINATION
+  uint32_t trig_start, n_triggers, n_objects, words;  // n_objects: the level's game objects; words: its own game's
+  uint32_t live, fired, active, second, order, effect, _pad[2];
+  float start[3], start_yaw;
+};
+
+__device__ __forceinline__ GameView level_view(const GameView &set, const DevSetLevel &l) {  // the level's layout within a game
+  return GameView{set.triggers + l.trig_start, set.effects, l.n_triggers, l.n_objects, l.live, l.fired, l.active, l.second, l.order,
+                  l.effect, l.words};
+}
+
+// word k of a fresh game of level l (game_reset_kernel's values); the words past the level's own are zero
+__device__ __forceinline__ uint32_t fresh_word(const DevSetLevel &l, uint32_t k) {
+  if (k == 0) return l.n_triggers;
+  if (k >= l.live && k < l.fired) {
+    const uint32_t first = (k - l.live) * 32;
+    return l.n_triggers - first >= 32 ? ~0u : (1u << (l.n_triggers - first)) - 1u;
+  }
+  if (k >= l.order && k < l.order + l.n_triggers) return k - l.order;
+  return 0u;
+}
+
+// Word 1 of a set's game: where the player is in the level change.  An exit fired in the poll of tick t (STAGE_EXITED); tick t + 1
+// requests the next level and still runs in the old one (STAGE_REQUESTED); tick t + 2 loads it, resets the player and runs in it.
+constexpr uint32_t STAGE_NONE = 0u, STAGE_EXITED = 1u, STAGE_REQUESTED = 2u;
+
+// A player's game in a world set: GameLevel's effects and triggers on the player's current level, and the level change.
+struct SetGame {
+  GameLevel gl;                // games, offsets, actions, n, dt; gl.n_objects and gl.g.words are the set's, gl.g.triggers /
+                               // effects the concatenated lists
+  const DevSetLevel *levels;
+  uint32_t *level_of;
+  uint32_t n_levels;
+  uint32_t lv, stage;          // this lane's level and change stage
+  uint32_t root_, dyn_start, n_dyn;
+
+  __device__ __forceinline__ bool begin(uint32_t p) {
+    lv = level_of[p];
+    if (lv >= n_levels) return false;  // not a slot: the player is left untouched
+    gl.begin(p);
+    stage = gl.game[1];
+    return true;
+  }
+  __device__ __forceinline__ bool start_tick() {
+    bool reset = false;
+    if (stage == STAGE_EXITED) {  // Level::update: exit_triggered -> change_level(current + 1) (level.rs:194-199)
+      stage = STAGE_REQUESTED;
+      gl.game[1] = stage;
+    } else if (stage == STAGE_REQUESTED) {  // WadSystem::update loads it, Level is rebuilt, Player::update resets (player.rs:359-362)
+      const uint32_t d = levels[lv].destination;
+      stage = STAGE_NONE;
+      if (d < n_levels) {
+        lv = d;
+        level_of[gl.lane] = d;
+        const DevSetLevel l = levels[d];
+        for (uint32_t k = 0; k < gl.g.words; k++) gl.game[k] = fresh_word(l, k);
+        for (uint32_t k = 0; k < gl.n_objects * 3; k++) gl.off[k] = 0.0f;
+        reset = true;
+      } else {
+        gl.game[1] = stage;
+      }
+    }
+    root_ = levels[lv].root, dyn_start = levels[lv].dyn_start, n_dyn = levels[lv].n_dynamics;
+    return reset;
+  }
+  __device__ __forceinline__ V3 start_pos() const { return load3(levels[lv].start); }
+  __device__ __forceinline__ float start_yaw() const { return levels[lv].start_yaw; }
+  __device__ __forceinline__ WorldView world(const WorldView &w) const {
+    return WorldView{w.nodes, w.chunks, w.tris, w.verts, w.dynamics + dyn_start, n_dyn, w.stack_cap};
+  }
+  __device__ __forceinline__ uint32_t root() const { return root_; }
+
+  __device__ __forceinline__ void tick(uint32_t t, V3 pos, V3 vel, float yaw, float pitch, uint32_t &flags) {
+    uint32_t fired = 0u;
+    GameLevel l = gl;
+    const uint32_t u = __builtin_amdgcn_readfirstlane(lv);
+    if (__builtin_amdgcn_ballot_w64(lv != u) == 0) {  // one level in the wave: its trigger loads stay scalar
+      l.g = level_view(gl.g, levels[u]);
+      l.tick(t, pos, vel, yaw, pitch, fired);
+    } else {
+      l.g = level_view(gl.g, levels[lv]);
+      l.tick(t, pos, vel, yaw, pitch, fired);
+    }
+    flags |= fired;
+    // an exit with a destination starts the change; one fired while a change is under way is lost with the rebuilt Level
+    if ((fired & RDOOM_PLAYER_EXITED) && stage == STAGE_NONE && levels[lv].destination < n_levels) {
+      stage = STAGE_EXITED;
+      gl.game[1] = stage;
+    }
+  }
+};
+
+// triggers / effects / levels: passed as __restrict__ arguments, as for game_step_kernel
+__global__ __launch_bounds__(WAVE) void worldset_game_step_kernel(WorldView w, SetGame set, const DevTrigger *__restrict__ triggers,
+                                                                  const DevEffect *__restrict__ effects,
+                                                                  const DevSetLevel *__restrict__ levels, rdoom_player_state *states,
+                                                                  const rdoom_player_input *inputs, uint32_t n_ticks, rdoom_player_config cfg) {
+  set.gl.g.triggers = triggers;
+  set.gl.g.effects = effects;
+  set.levels = levels;
+  step_players(w, states, inputs, set.gl.n, n_ticks, cfg, set.gl.dt, set.gl.offsets, set.gl.n_objects, set);
+}
+
+// a fresh game of its current level for player blockIdx.x (if masked in and on a slot): one workgroup per game
+__global__ __launch_bounds__(WAVE) void worldset_game_reset_kernel(const DevSetLevel *__restrict__ levels, uint32_t n_levels,
+                                                                   uint32_t words, uint32_t *games, float *offsets, uint32_t n_objects,
+                                                                   const uint32_t *level_of, const uint8_t *mask) {
+  const uint32_t p = blockIdx.x;
+  if (mask && !mask[p]) return;
+  const uint32_t lv = level_of[p];
+  if (lv >= n_levels) return;
+  const DevSetLevel l = levels[lv];
+  uint32_t *game = games + (size_t)p * words;
+  for (uint32_t k = threadIdx.x; k < words; k += WAVE) game[k] = fresh_word(l, k);
+  float *off = offsets + (size_t)p * n_objects * 3;
+  for (uint32_t k = threadIdx.x; k < n_objects * 3; k += WAVE) off[k] = 0.0f;
+}
+
 }  // namespace
 
 struct rdoom_world {
@@ -740,6 +879,48 @@ rdoom_status upload(T **dst, const void *src, size_t bytes) {
   return RDOOM_OK;
 }
 
+// the device arrays of a host World (rdoom_world_create; a world set's concatenation)
+struct DevArrays {
+  DevNode *nodes = nullptr;
+  uint2 *chunks = nullptr;
+  uint4 *tris = nullptr;
+  float *verts = nullptr;
+  DevDynamic *dynamics = nullptr;
+  DevTrigger *triggers = nullptr;
+  DevEffect *effects = nullptr;
+};
+rdoom_status upload_world(const rdoom::game::World &h, DevArrays &d) {
+  std::vector<DevNode> nodes(h.nodes.size());
+  for (size_t i = 0; i < nodes.size(); i++) {
+    const rdoom::game::WorldNode &s = h.nodes[i];
+    nodes[i] = DevNode{s.origin[0], s.origin[1], s.displace[0], s.displace[1], s.positive, s.negative, {0, 0}};
+  }
+  std::vector<DevDynamic> dyn(h.dynamics.size());
+  for (size_t i = 0; i < dyn.size(); i++) dyn[i] = DevDynamic{h.dynamics[i].object_id, h.dynamics[i].tri_start, h.dynamics[i].tri_end, 0};
+  if (rdoom_status s = upload(&d.nodes, nodes.data(), nodes.size() * sizeof(DevNode))) return s;
+  if (rdoom_status s = upload(&d.chunks, h.chunks.data(), h.chunks.size() * sizeof(uint2))) return s;
+  if (rdoom_status s = upload(&d.tris, h.triangles.data(), h.triangles.size() * sizeof(uint4))) return s;
+  if (rdoom_status s = upload(&d.verts, h.verts.data(), h.verts.size() * sizeof(float))) return s;
+  if (rdoom_status s = upload(&d.dynamics, dyn.data(), dyn.size() * sizeof(DevDynamic))) return s;
+  std::vector<DevTrigger> trig(h.triggers.size());
+  for (size_t i = 0; i < trig.size(); i++) {
+    const rdoom_trigger &t = h.triggers[i];
+    trig[i] = DevTrigger{t.origin[0], t.origin[1], t.displace[0], t.displace[1], t.length, t.trigger_type, t.flags, t.effect_start, t.effect_end, {0, 0, 0}};
+  }
+  std::vector<DevEffect> eff(h.effects.size());
+  for (size_t i = 0; i < eff.size(); i++) {
+    const rdoom_move_effect &e = h.effects[i];
+    eff[i] = DevEffect{e.object_id, e.has_second, e.first_height_offset, e.second_height_offset, e.wait, e.speed, {0.0f, 0.0f}};
+  }
+  if (rdoom_status s = upload(&d.triggers, trig.data(), trig.size() * sizeof(DevTrigger))) return s;
+  if (rdoom_status s = upload(&d.effects, eff.data(), eff.size() * sizeof(DevEffect))) return s;
+  return RDOOM_OK;
+}
+void free_world(DevArrays &d) {
+  for (void *p : {(void *)d.nodes, (void *)d.chunks, (void *)d.tris, (void *)d.verts, (void *)d.dynamics, (void *)d.triggers, (void *)d.effects})
+    if (p) (void)hipFree(p);
+}
+
 WorldView view(const rdoom_world *w) {
   return WorldView{w->d_nodes, w->d_chunks, w->d_tris, w->d_verts, w->d_dynamics, (uint32_t)w->host.dynamics.size(),
                    w->host.node_depth + 1};
@@ -753,13 +934,19 @@ rdoom_status check_device(const rdoom_world *w) {
   return RDOOM_OK;
 }
 
-GameView game_view(const rdoom_world *w) {  // the layout include/rdoom.h documents at rdoom_world_game_bytes
-  const uint32_t t = (uint32_t)w->host.triggers.size(), o = w->host.game_objects;
+GameView game_layout(const rdoom::game::World &h) {  // the layout include/rdoom.h documents at rdoom_world_game_bytes
+  const uint32_t t = (uint32_t)h.triggers.size(), o = h.game_objects;
   const uint32_t lw = (t + 31) / 32, ow = (o + 31) / 32;
-  GameView g{w->d_triggers, w->d_effects, t, o, 4, 0, 0, 0, 0, 0, 0};
+  GameView g{nullptr, nullptr, t, o, 4, 0, 0, 0, 0, 0, 0};
   g.fired = g.live + lw, g.active = g.fired + lw, g.second = g.active + ow, g.order = g.second + ow;
   g.effect = (g.order + t + 3) / 4 * 4;
   g.words = g.effect + 4 * o;
+  return g;
+}
+
+GameView game_view(const rdoom_world *w) {
+  GameView g = game_layout(w->host);
+  g.triggers = w->d_triggers, g.effects = w->d_effects;
   return g;
 }
 
@@ -774,6 +961,34 @@ rdoom_status check_game(const rdoom_world *w, const void *d_game, const float *d
 rdoom_status check_offsets(const rdoom_world *w, const float *offsets, uint32_t n_objects) {
   if (offsets && n_objects < w->host.n_objects)
     return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the world's %u objects", n_objects, w->host.n_objects);
+  return RDOOM_OK;
+}
+}  // namespace
+
+struct rdoom_worldset {
+  rdoom::game::WorldSet host;
+  std::vector<DevSetLevel> table;  // the device table's records
+  uint32_t words = 0;              // a game's words: the largest level's
+  bool on_device = false;
+  int device = -1;
+  DevArrays d;
+  DevSetLevel *d_table = nullptr;
+};
+
+namespace {
+rdoom_status check_device(const rdoom_worldset *s) {
+  if (!s->on_device) return rdoom::fail(RDOOM_BAD_ARG, "the world set was created with RDOOM_WORLD_HOST_ONLY: it has no device copy");
+  int cur = -1;
+  HIP_TRY(hipGetDevice(&cur));
+  if (cur != s->device) return rdoom::fail(RDOOM_BAD_ARG, "the world set lives on device %d, the current device is %d", s->device, cur);
+  return RDOOM_OK;
+}
+
+rdoom_status check_game(const rdoom_worldset *s, const void *d_game, const float *d_offsets, uint32_t n_objects, const uint32_t *d_levels) {
+  if (!d_game || !d_offsets || !d_levels) return rdoom::fail(RDOOM_BAD_ARG, "null game state, object offsets or levels");
+  if ((uintptr_t)d_game % 16) return rdoom::fail(RDOOM_BAD_ARG, "the game state is not 16-byte aligned");
+  if (n_objects < s->host.game_objects)
+    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the set's %u objects", n_objects, s->host.game_objects);
   return RDOOM_OK;
 }
 }  // namespace
@@ -808,30 +1023,11 @@ rdoom_status rdoom_world_create(const rdoom_wad *wad, uint32_t level_index, uint
     return rdoom::fail(RDOOM_BAD_LEVEL, "the level's BSP is %u nodes deep (at most %u)", h.node_depth, RDOOM_WORLD_MAX_DEPTH);
   if (!(flags & RDOOM_WORLD_HOST_ONLY)) {
     HIP_TRY(hipGetDevice(&w->device));
-    std::vector<DevNode> nodes(h.nodes.size());
-    for (size_t i = 0; i < nodes.size(); i++) {
-      const rdoom::game::WorldNode &s = h.nodes[i];
-      nodes[i] = DevNode{s.origin[0], s.origin[1], s.displace[0], s.displace[1], s.positive, s.negative, {0, 0}};
-    }
-    std::vector<DevDynamic> dyn(h.dynamics.size());
-    for (size_t i = 0; i < dyn.size(); i++) dyn[i] = DevDynamic{h.dynamics[i].object_id, h.dynamics[i].tri_start, h.dynamics[i].tri_end, 0};
-    if (rdoom_status s = upload(&w->d_nodes, nodes.data(), nodes.size() * sizeof(DevNode))) return s;
-    if (rdoom_status s = upload(&w->d_chunks, h.chunks.data(), h.chunks.size() * sizeof(uint2))) return s;
-    if (rdoom_status s = upload(&w->d_tris, h.triangles.data(), h.triangles.size() * sizeof(uint4))) return s;
-    if (rdoom_status s = upload(&w->d_verts, h.verts.data(), h.verts.size() * sizeof(float))) return s;
-    if (rdoom_status s = upload(&w->d_dynamics, dyn.data(), dyn.size() * sizeof(DevDynamic))) return s;
-    std::vector<DevTrigger> trig(h.triggers.size());
-    for (size_t i = 0; i < trig.size(); i++) {
-      const rdoom_trigger &t = h.triggers[i];
-      trig[i] = DevTrigger{t.origin[0], t.origin[1], t.displace[0], t.displace[1], t.length, t.trigger_type, t.flags, t.effect_start, t.effect_end, {0, 0, 0}};
-    }
-    std::vector<DevEffect> eff(h.effects.size());
-    for (size_t i = 0; i < eff.size(); i++) {
-      const rdoom_move_effect &e = h.effects[i];
-      eff[i] = DevEffect{e.object_id, e.has_second, e.first_height_offset, e.second_height_offset, e.wait, e.speed, {0.0f, 0.0f}};
-    }
-    if (rdoom_status s = upload(&w->d_triggers, trig.data(), trig.size() * sizeof(DevTrigger))) return s;
-    if (rdoom_status s = upload(&w->d_effects, eff.data(), eff.size() * sizeof(DevEffect))) return s;
+    DevArrays d;
+    const rdoom_status st = upload_world(h, d);
+    w->d_nodes = d.nodes, w->d_chunks = d.chunks, w->d_tris = d.tris, w->d_verts = d.verts, w->d_dynamics = d.dynamics;
+    w->d_triggers = d.triggers, w->d_effects = d.effects;
+    if (st) return st;
     w->on_device = true;
   }
   *out_world = w.release();
@@ -951,6 +1147,145 @@ rdoom_status rdoom_world_step_game(const rdoom_world *w, rdoom_player_state *d_s
   level.dt = dt == 0.0f ? 1.0f / 60.0f : dt;
   hipLaunchKernelGGL(game_step_kernel, dim3((n_players + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
                      (hipStream_t)stream, v, level, level.g.triggers, level.g.effects, d_states, d_inputs, n_ticks, c);
+  HIP_TRY(hipGetLastError());
+  return RDOOM_OK;
+}
+
+void rdoom_worldset_destroy(rdoom_worldset *s) {
+  if (!s) return;
+  free_world(s->d);
+  if (s->d_table) (void)hipFree(s->d_table);
+  delete s;
+}
+
+rdoom_status rdoom_worldset_create(const rdoom_wad *wad, const uint32_t *level_indices, uint32_t n_levels, uint32_t flags,
+                                   rdoom_worldset **out_set) {
+  if (!wad || !out_set || (n_levels && !level_indices)) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (flags & ~RDOOM_WORLD_HOST_ONLY) return rdoom::fail(RDOOM_BAD_ARG, "unknown flags 0x%x", flags);
+  *out_set = nullptr;
+  std::unique_ptr<rdoom_worldset, void (*)(rdoom_worldset *)> s(nullptr, rdoom_worldset_destroy);
+  try {  // nothing unwinds across the C ABI
+    s.reset(new rdoom_worldset);
+    s->host = rdoom::game::build_world_set(*rdoom::game::loaded_wad(wad), level_indices, n_levels);
+  } catch (const rdoom::wad::WadError &e) {
+    return rdoom::fail(e.code, "%s", e.what());
+  } catch (const std::bad_alloc &) {
+    return rdoom::fail(RDOOM_OOM, "out of host memory");
+  } catch (const std::exception &e) {
+    return rdoom::fail(RDOOM_BAD_LEVEL, "%s", e.what());
+  }
+  const rdoom::game::WorldSet &h = s->host;
+  if (h.node_depth > RDOOM_WORLD_MAX_DEPTH)
+    return rdoom::fail(RDOOM_BAD_LEVEL, "a level's BSP is %u nodes deep (at most %u)", h.node_depth, RDOOM_WORLD_MAX_DEPTH);
+  for (size_t i = 0; i < h.levels.size(); i++) {
+    const rdoom::game::World &l = h.levels[i];
+    const rdoom::game::WorldSetLevel &t = h.table[i];
+    const GameView g = game_layout(l);
+    DevSetLevel r{};
+    r.root = t.node_base, r.dyn_start = t.dynamic_base, r.n_dynamics = (uint32_t)l.dynamics.size(), r.destination = t.destination;
+    r.trig_start = t.trigger_base, r.n_triggers = g.n_triggers, r.n_objects = g.n_objects, r.words = g.words;
+    r.live = g.live, r.fired = g.fired, r.active = g.active, r.second = g.second, r.order = g.order, r.effect = g.effect;
+    std::memcpy(r.start, l.start_pos, sizeof r.start);
+    r.start_yaw = l.start_yaw;
+    s->table.push_back(r);
+    s->words = std::max(s->words, g.words);
+  }
+  if (!(flags & RDOOM_WORLD_HOST_ONLY)) {
+    HIP_TRY(hipGetDevice(&s->device));
+    if (rdoom_status st = upload_world(h.all, s->d)) return st;
+    if (rdoom_status st = upload(&s->d_table, s->table.data(), s->table.size() * sizeof(DevSetLevel))) return st;
+    s->on_device = true;
+  }
+  *out_set = s.release();
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_worldset_info(const rdoom_worldset *s, uint32_t *out_n_levels, uint32_t *out_n_objects) {
+  if (!s) return rdoom::fail(RDOOM_BAD_ARG, "null world set");
+  if (out_n_levels) *out_n_levels = (uint32_t)s->host.levels.size();
+  if (out_n_objects) *out_n_objects = s->host.game_objects;
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_worldset_level(const rdoom_worldset *s, uint32_t slot, rdoom_worldset_level_info *out) {
+  if (!s || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (slot >= s->host.levels.size()) return rdoom::fail(RDOOM_BAD_ARG, "slot %u of a set of %zu levels", slot, s->host.levels.size());
+  const rdoom::game::World &l = s->host.levels[slot];
+  std::memset(out, 0, sizeof *out);
+  out->archive_index = s->host.table[slot].archive_index;
+  out->destination = s->host.table[slot].destination;
+  std::memcpy(out->start_pos, l.start_pos, sizeof out->start_pos);
+  out->start_yaw = l.start_yaw;
+  out->n_triggers = (uint32_t)l.triggers.size();
+  out->n_objects = l.game_objects;
+  out->node_depth = l.node_depth;
+  rdoom_world_arrays &a = out->world;
+  a.nodes = reinterpret_cast<const rdoom_world_node *>(l.nodes.data());
+  a.n_nodes = (uint32_t)l.nodes.size();
+  a.chunks = reinterpret_cast<const rdoom_world_chunk *>(l.chunks.data());
+  a.n_chunks = (uint32_t)l.chunks.size();
+  a.triangles = reinterpret_cast<const rdoom_world_triangle *>(l.triangles.data());
+  a.n_triangles = (uint32_t)l.triangles.size();
+  a.n_static_triangles = l.n_static_triangles;
+  a.verts = l.verts.data();
+  a.n_verts = (uint32_t)(l.verts.size() / 3);
+  a.dynamics = reinterpret_cast<const rdoom_world_dynamic *>(l.dynamics.data());
+  a.n_dynamics = (uint32_t)l.dynamics.size();
+  a.n_objects = l.n_objects;
+  a.node_depth = l.node_depth;
+  rdoom_world_trigger_arrays &t = out->triggers;
+  t.triggers = l.triggers.data();
+  t.n_triggers = (uint32_t)l.triggers.size();
+  t.effects = l.effects.data();
+  t.n_effects = (uint32_t)l.effects.size();
+  t.n_objects = l.game_objects;
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_worldset_game_bytes(const rdoom_worldset *s, uint64_t *bytes_per_player) {
+  if (!s || !bytes_per_player) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  *bytes_per_player = (uint64_t)s->words * sizeof(uint32_t);
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_worldset_game_reset(const rdoom_worldset *s, void *d_game, float *d_object_offsets, uint32_t n_objects,
+                                       const uint32_t *d_levels, uint32_t n, const uint8_t *d_mask, void *stream) {
+  if (!s) return rdoom::fail(RDOOM_BAD_ARG, "null world set");
+  if (rdoom_status st = check_game(s, d_game, d_object_offsets, n_objects, d_levels)) return st;
+  if (rdoom_status st = check_device(s)) return st;
+  if (!n) return RDOOM_OK;
+  hipLaunchKernelGGL(worldset_game_reset_kernel, dim3(n), dim3(WAVE), 0, (hipStream_t)stream, s->d_table, (uint32_t)s->table.size(),
+                     s->words, (uint32_t *)d_game, d_object_offsets, n_objects, d_levels, d_mask);
+  HIP_TRY(hipGetLastError());
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_worldset_step_game(const rdoom_worldset *s, rdoom_player_state *d_states, const rdoom_player_input *d_inputs,
+                                      const uint8_t *d_actions, void *d_game, float *d_object_offsets, uint32_t n_objects,
+                                      uint32_t *d_levels, uint32_t n_players, uint32_t n_ticks, const rdoom_player_config *cfg,
+                                      float dt, void *stream) {
+  if (!s) return rdoom::fail(RDOOM_BAD_ARG, "null world set");
+  if (n_players && (!d_states || (n_ticks && !d_inputs)))
+    return rdoom::fail(RDOOM_BAD_ARG, "null states or inputs with n_players = %u", n_players);
+  if (!(dt >= 0.0f) || dt == __builtin_inff()) return rdoom::fail(RDOOM_BAD_ARG, "dt %g is not a finite non-negative number", (double)dt);
+  if (rdoom_status st = check_game(s, d_game, d_object_offsets, n_objects, d_levels)) return st;
+  if (rdoom_status st = check_device(s)) return st;
+  if (!n_players || !n_ticks) return RDOOM_OK;
+  rdoom_player_config c;
+  if (cfg) c = *cfg;
+  else rdoom_player_config_default(&c);
+  const WorldView v{s->d.nodes, s->d.chunks, s->d.tris, s->d.verts, s->d.dynamics, 0u, s->host.node_depth + 1};
+  SetGame set{};
+  set.gl.g = GameView{s->d.triggers, s->d.effects, 0, s->host.game_objects, 0, 0, 0, 0, 0, 0, s->words};
+  set.gl.games = (uint32_t *)d_game;
+  set.gl.offsets = d_object_offsets;
+  set.gl.actions = d_actions;
+  set.gl.n = n_players, set.gl.n_objects = n_objects;
+  set.gl.dt = dt == 0.0f ? 1.0f / 60.0f : dt;
+  set.level_of = d_levels;
+  set.n_levels = (uint32_t)s->table.size();
+  hipLaunchKernelGGL(worldset_game_step_kernel, dim3((n_players + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
+                     (hipStream_t)stream, v, set, s->d.triggers, s->d.effects, s->d_table, d_states, d_inputs, n_ticks, c);
   HIP_TRY(hipGetLastError());
   return RDOOM_OK;
 }

@@ -138,14 +138,16 @@ void Builder::visit_sky_quad(const SkyQuad &q) {  // level.rs:743-755
   any_quad(sky_vertices.size() / 3, object_indices[q.object_id.v].sky);
 }
 
-void Builder::visit_marker(const float pos[3], float yaw, Marker marker) {  // level.rs:757-762
-  if (marker.kind == MarkerKind::StartPos && marker.player == 0) {
-    start_pos[0] = pos[0] + 0.0f;
-    start_pos[1] = pos[1] + 0.5f;
-    start_pos[2] = pos[2] + 32.0f / 100.0f;
-    start_yaw = yaw;
-  }
+bool start_from_marker(const float pos[3], float yaw, Marker marker, float out_pos[3], float &out_yaw) {  // level.rs:757-762
+  if (marker.kind != MarkerKind::StartPos || marker.player != 0) return false;
+  out_pos[0] = pos[0] + 0.0f;
+  out_pos[1] = pos[1] + 0.5f;
+  out_pos[2] = pos[2] + 32.0f / 100.0f;
+  out_yaw = yaw;
+  return true;
 }
+
+void Builder::visit_marker(const float pos[3], float yaw, Marker marker) { start_from_marker(pos, yaw, marker, start_pos, start_yaw); }
 
 void Builder::visit_decor(const Decor &d) {  // level.rs:764-793
   counters.num_decors++;

@@ -27,6 +27,9 @@ struct LevelMaterials {  // the atlas bounds the Builder looks names up in (game
   wad::BoundsLookup flats, walls, decor;
 };
 
+// Builder::visit_marker's start pose (level.rs:757-762): false for any marker but player 1's start
+bool start_from_marker(const float pos[3], float yaw, wad::Marker marker, float out_pos[3], float &out_yaw);
+
 class Builder : public wad::LevelVisitor {  // game/src/level.rs:307-327, 648-794
  public:
   explicit Builder(const LevelMaterials &materials) : materials_(materials) {}

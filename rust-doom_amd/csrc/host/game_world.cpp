@@ -46,6 +46,7 @@ class WorldBuilder : public LevelVisitor {
     if (q.blocker) quad(q.object_id, q.v1, q.v2, q.height_range);
   }
   void visit_sky_quad(const SkyQuad &q) override { quad(q.object_id, q.v1, q.v2, q.height_range); }
+  void visit_marker(const float pos[3], float yaw, Marker marker) override { start_from_marker(pos, yaw, marker, start_pos_, start_yaw_); }
 
   World build() {  // world.rs:230-258: object 0's triangles, then one dynamic chunk per other object, by ascending id
     World w;
@@ -64,6 +65,8 @@ class WorldBuilder : public LevelVisitor {
       }
     }
     w.node_depth = depth_;
+    std::copy(start_pos_, start_pos_ + 3, w.start_pos);
+    w.start_yaw = start_yaw_;
     return w;
   }
 
@@ -117,6 +120,7 @@ class WorldBuilder : public LevelVisitor {
   std::vector<uint32_t> stack_;
   std::map<uint32_t, std::vector<WorldTriangle>> triangles_{{0u, {}}};  // VecMap<Vec<Triangle>>: iterated by ascending key
   uint32_t depth_ = 0;
+  float start_pos_[3] = {0, 0, 0}, start_yaw_ = 0.0f;
 };
 }  // namespace
 
@@ -145,6 +149,51 @@ World build_world(const LoadedWad &w, size_t level_index) {
     out.triggers.push_back(r);
   }
   return out;
+}
+
+WorldSet build_world_set(const LoadedWad &w, const uint32_t *level_indices, size_t n) {
+  if (!n || !level_indices) throw WadError(RDOOM_BAD_ARG, "world set: no levels");
+  const size_t n_archive = w.archive->num_levels();
+  std::map<uint32_t, uint32_t> slot_of;
+  for (size_t s = 0; s < n; s++) {
+    if (level_indices[s] >= n_archive) throw WadError(RDOOM_BAD_ARG, "world set: level index out of range");
+    if (!slot_of.emplace(level_indices[s], (uint32_t)s).second) throw WadError(RDOOM_BAD_ARG, "world set: a level index twice");
+  }
+  WorldSet set;
+  World &all = set.all;
+  all.n_objects = 0;
+  for (size_t s = 0; s < n; s++) {
+    set.levels.push_back(build_world(w, level_indices[s]));
+    const World &l = set.levels.back();
+    WorldSetLevel t{};
+    t.archive_index = level_indices[s];
+    const auto next = slot_of.find(level_indices[s] + 1);
+    t.destination = next == slot_of.end() ? NO_DESTINATION : next->second;
+    t.node_base = (uint32_t)all.nodes.size(), t.chunk_base = (uint32_t)all.chunks.size();
+    t.triangle_base = (uint32_t)all.triangles.size(), t.vert_base = (uint32_t)(all.verts.size() / 3);
+    t.dynamic_base = (uint32_t)all.dynamics.size(), t.trigger_base = (uint32_t)all.triggers.size();
+    t.effect_base = (uint32_t)all.effects.size();
+    for (WorldNode nd : l.nodes) {
+      for (int32_t *c : {&nd.positive, &nd.negative}) *c = *c > 0 ? *c + (int32_t)t.node_base : *c - (int32_t)t.chunk_base;
+      all.nodes.push_back(nd);
+    }
+    for (const WorldChunk &c : l.chunks) all.chunks.push_back({c.tri_start + t.triangle_base, c.tri_end + t.triangle_base});
+    for (const WorldTriangle &tr : l.triangles)
+      all.triangles.push_back({tr.v1 + t.vert_base, tr.v2 + t.vert_base, tr.v3 + t.vert_base, tr.normal + t.vert_base});
+    all.verts.insert(all.verts.end(), l.verts.begin(), l.verts.end());
+    for (const WorldDynamic &d : l.dynamics) all.dynamics.push_back({d.object_id, d.tri_start + t.triangle_base, d.tri_end + t.triangle_base});
+    for (rdoom_trigger tr : l.triggers) {
+      tr.effect_start += t.effect_base, tr.effect_end += t.effect_base;
+      all.triggers.push_back(tr);
+    }
+    all.effects.insert(all.effects.end(), l.effects.begin(), l.effects.end());
+    all.n_objects = std::max(all.n_objects, l.n_objects);
+    set.game_objects = std::max(set.game_objects, l.game_objects);
+    set.node_depth = std::max(set.node_depth, l.node_depth);
+    set.table.push_back(t);
+  }
+  all.game_objects = set.game_objects, all.node_depth = set.node_depth;
+  return set;
 }
 
 }  // namespace rdoom::game

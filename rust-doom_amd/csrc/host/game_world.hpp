@@ -38,7 +38,32 @@ struct World {
   std::vector<rdoom_trigger> triggers;
   std::vector<rdoom_move_effect> effects;
   uint32_t game_objects = 1;  // max(1, LevelAnalysis::num_objects)
+  float start_pos[3] = {0, 0, 0};  // the player's start, as the renderer's Builder takes it (rdoom_built_start)
+  float start_yaw = 0.0f;
 };
+
+// Several levels' worlds at once (a world set): each level's World as build_world makes it, and the levels concatenated with
+// every index rebased, for the device.  Slot s holds archive level archive_index[s]; its destination is the slot holding
+// archive_index[s] + 1, or NO_DESTINATION.
+constexpr uint32_t NO_DESTINATION = 0xFFFFFFFFu;
+struct WorldSetLevel {
+  uint32_t archive_index, destination;
+  uint32_t node_base, chunk_base, triangle_base, vert_base, dynamic_base, trigger_base, effect_base;  // in the concatenation
+};
+struct WorldSet {
+  std::vector<World> levels;
+  std::vector<WorldSetLevel> table;
+  // the concatenation: node children, chunk and dynamic triangle ranges, triangle vertex indices and trigger effect ranges
+  // rebased.  A child packed as 0 (Leaf(0), never linked or not) becomes minus its own level's chunk base, so it still reads as
+  // that level's leaf 0.
+  World all;
+  uint32_t game_objects = 1;  // the largest of the levels' game_objects
+  uint32_t node_depth = 0;    // the deepest level's
+};
+
+// build_world for each of n archive levels, then the concatenation.  Throws WadError(RDOOM_BAD_ARG) on an empty list, an
+// index out of range or a duplicate index, and what build_world throws.
+WorldSet build_world_set(const LoadedWad &w, const uint32_t *level_indices, size_t n);
 
 // WorldBuilder::new + LevelWalker::walk + WorldBuilder::build.  Throws WadError(RDOOM_BAD_LEVEL) on a level without a BSP.
 World build_world(const LoadedWad &w, size_t level_index);
