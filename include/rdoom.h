@@ -622,6 +622,37 @@ rdoom_status rdoom_worldset_step_game(const rdoom_worldset *set, rdoom_player_st
 rdoom_status rdoom_object_modelviews_from_player(const float pos[3], float yaw, float pitch, const float *offsets, uint32_t n_objects,
                                                  float *out);
 
+/* ---- player frames: render the players in device arrays, without a host round trip ----
+ * The cameras of n players whose states are in device memory, on the device: d_poses_out[p] is what rdoom_pose_from_player
+ * returns for player p (projection and time bit for bit), and, when d_object_modelviews_out != NULL, the n x n_objects x 16
+ * floats there are what rdoom_object_modelviews_from_player returns for player p's row of d_object_offsets (n x n_objects x
+ * xyz, required then).  Same formulas, binary32, no contraction; the one difference is that sine and cosine come from the
+ * project's sincos -- the world step's -- instead of libm sinf / cosf, so a modelview entry may differ from the host helpers'
+ * in the last places: on 10 000 random states (yaw in +-60 pi, pitch at and inside the step's clamp) by at most 2^-19 -- absolute
+ * for the rotation entries, relative to 1 + |x| + |y| + |z| of the position (plus offset) for the translation.  A test pins this
+ * bound (tests/test_player_frames_host.py; observed: 2^-20).  Object 0 and every object at offset (0, 0, 0)
+ * get the pose's modelview bit for bit.  Asynchronous on stream (a hipStream_t, may be NULL), on the current device. */
+rdoom_status rdoom_poses_from_players_device(const rdoom_player_state *d_states, uint32_t n, uint32_t width, uint32_t height,
+                                             float time, const float *d_object_offsets, uint32_t n_objects,
+                                             rdoom_pose *d_poses_out, float *d_object_modelviews_out, void *stream);
+/* rdoom_batch_render_levels for players whose state is on the device (all pointers here are device memory of the batch's
+ * device): pose p is player p's camera as rdoom_poses_from_players_device computes it (time `time`), and it views level
+ * d_levels[p] (NULL: level 0, allowed only on a batch of a single level).  Its objects sit at row p of d_object_offsets
+ * (n_players x n_objects x xyz, n_objects >= rdoom_level_num_objects; NULL = every object at rest).  Its lights are
+ * d_lights + d_levels[p] * lights_stride: one 256-byte table per level slot (lights_stride 256) or one shared table (0).
+ * Asynchronous: it never waits on the host, and it allocates nothing after the batch's first render with objects.  A level
+ * outside the set is rendered as level 0, and rdoom_batch_finish / rdoom_batch_read_* then report RDOOM_BAD_ARG naming the
+ * first such pose (the frames of the other poses are correct).  The frames are those rdoom_batch_render_levels gives for the
+ * same matrices, lights and levels, with one exception: the sky angle atan2(pm[8], pm[10]) (sky.vert) is correctly rounded
+ * here, where the host path uses libm atan2f, so on rare poses a column of sky may sit one texel apart.  rdoom_batch_resolve_rgb
+ * / rdoom_batch_read_rgb after such a render need a playpal for every level of the set.  flags: RDOOM_RENDER_PROFILED.
+ * d_poses_out (n_players poses) and d_object_modelviews_out (n_players x n_objects x 16 floats, needs d_object_offsets) are
+ * optional copies of what was rendered. */
+rdoom_status rdoom_batch_render_players(rdoom_batch *batch, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                        const float *d_object_offsets, uint32_t n_objects, const uint8_t *d_lights,
+                                        uint32_t lights_stride, float time, uint32_t n_players, uint32_t kinds_mask,
+                                        uint32_t flags, void *stream, rdoom_pose *d_poses_out, float *d_object_modelviews_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -118,7 +118,8 @@ API_SYMBOLS = [
     'rdoom_world_create', 'rdoom_world_destroy', 'rdoom_world_host_arrays', 'rdoom_world_sweep', 'rdoom_world_step_players',
     'rdoom_player_config_default', 'rdoom_world_triggers', 'rdoom_world_game_bytes', 'rdoom_world_game_reset', 'rdoom_world_step_game',
     'rdoom_object_modelviews_from_player', 'rdoom_worldset_create', 'rdoom_worldset_destroy', 'rdoom_worldset_info',
-    'rdoom_worldset_level', 'rdoom_worldset_game_bytes', 'rdoom_worldset_game_reset', 'rdoom_worldset_step_game']
+    'rdoom_worldset_level', 'rdoom_worldset_game_bytes', 'rdoom_worldset_game_reset', 'rdoom_worldset_step_game',
+    'rdoom_poses_from_players_device', 'rdoom_batch_render_players']
 
 _lib = None
 
@@ -581,6 +582,59 @@ class Batch:
         _check(lib().rdoom_batch_render_timed(*args, ctypes.byref(t)))
         return {n: getattr(t, n) for n, _ in Timings._fields_}
 
+    def render_players(self, states, lights, levels=None, offsets=None, time=0.0, kinds=ALL_KINDS, stream=None, poses_out=None,
+                       modelviews_out=None, profiled=False):
+        """rdoom_batch_render_players: render every player of a device states tensor (World.step_game / WorldSet.step_game's) from its
+        own camera, without a host round trip.  levels: the players' level slots (WorldSet.game_state's int32 tensor; None on a
+        batch of one level); offsets: the (n, n_objects, 3) float32 tensor of game_state (None: every object at rest); lights: a
+        uint8 (256,) table shared by every level, or (n_levels, 256), one per level of the batch's set.  Tensors on the GPU are used
+        as they are; numpy arrays are uploaded (and waited for).  poses_out / modelviews_out: optional tensors from
+        poses_from_players_device's shapes, filled with what was rendered.  Asynchronous on `stream`; profiled as render_profiled."""
+        keep = []
+
+        def dev(a, what):
+            if a is None:
+                return None
+            ptr, k, uploaded = _device_tensor(a, what)
+            keep.append((k, uploaded))
+            return ptr
+        ps, n = dev(states, 'states'), _n_players(states)
+        lights_n = lights.numel() if not isinstance(lights, np.ndarray) else lights.size
+        n_levels = ctypes.c_uint32()
+        _check(lib().rdoom_level_num_levels(self.level._h, ctypes.byref(n_levels)))
+        if lights_n == 256:
+            stride = 0
+        elif lights_n == 256 * n_levels.value:
+            stride = 256
+        else:
+            raise ValueError('lights must be (256,) or one 256-byte table per level of the set (%d), got %d bytes'
+                             % (n_levels.value, lights_n))
+        pl = dev(np.ascontiguousarray(lights, np.uint8) if isinstance(lights, np.ndarray) else lights, 'lights')
+        n_obj = 0
+        if offsets is not None:
+            if isinstance(offsets, np.ndarray):
+                offsets = np.ascontiguousarray(offsets, np.float32)
+            if tuple(offsets.shape[::2]) != (n, 3) or len(offsets.shape) != 3:
+                raise ValueError('offsets must be (n, n_objects, 3) for %d players, got %s' % (n, tuple(offsets.shape)))
+            n_obj = int(offsets.shape[1])
+        if levels is not None:
+            if isinstance(levels, np.ndarray):
+                levels = np.ascontiguousarray(levels, np.int64).astype(np.uint32)
+            size = levels.size if isinstance(levels, np.ndarray) else levels.numel()
+            item = levels.itemsize if isinstance(levels, np.ndarray) else levels.element_size()
+            if size != n or item != 4:
+                raise ValueError('levels must hold one 32-bit slot per player (%d)' % n)
+        po, pm = _out_tensor(poses_out, n * POSE.itemsize, 'poses_out'), _out_tensor(modelviews_out, n * n_obj * 64, 'modelviews_out')
+        pv, po_ = dev(levels, 'levels'), dev(offsets, 'offsets')
+        self.last_n = n
+        _check(lib().rdoom_batch_render_players(self._h, ctypes.c_void_p(ps), ctypes.c_void_p(pv), ctypes.c_void_p(po_), n_obj,
+                                                ctypes.c_void_p(pl), stride, ctypes.c_float(time), n, int(kinds),
+                                                1 if profiled else 0, ctypes.c_void_p(_stream_handle(stream)), ctypes.c_void_p(po),
+                                                ctypes.c_void_p(pm)))
+        if any(uploaded for _, uploaded in keep):
+            import torch
+            torch.cuda.synchronize()
+
     def finish(self):
         """rdoom_batch_finish: wait for the last render and raise if the device found a problem"""
         _check(lib().rdoom_batch_finish(self._h))
@@ -716,6 +770,52 @@ def object_modelviews_from_players(states, offsets):
                                                          ctypes.c_float(s['pitch']), offsets[i].ctypes.data_as(ctypes.c_void_p), n_obj,
                                                          out[i].ctypes.data_as(ctypes.c_void_p)))
     return out
+
+
+def _n_players(states):
+    size = states.nbytes if isinstance(states, np.ndarray) else states.numel() * states.element_size()
+    if size == 0 or size % PLAYER_STATE.itemsize:
+        raise ValueError('states must hold n >= 1 records of %d bytes' % PLAYER_STATE.itemsize)
+    return size // PLAYER_STATE.itemsize
+
+
+def _out_tensor(t, nbytes, what):
+    """the device pointer of an optional output tensor of exactly nbytes"""
+    if t is None:
+        return None
+    if t.device.type != 'cuda' or not t.is_contiguous() or t.numel() * t.element_size() != nbytes:
+        raise ValueError('%s must be a contiguous GPU tensor of %d bytes' % (what, nbytes))
+    return t.data_ptr()
+
+
+def poses_from_players_device(states, width, height, time=0.0, offsets=None, stream=None):
+    """rdoom_poses_from_players_device: the camera of every player, on the device.  states: a GPU tensor of PLAYER_STATE records
+    (numpy: uploaded); offsets: None or the (n, n_objects, 3) float32 tensor of game_state.  Returns (poses, modelviews): poses a
+    float32 (n, 34) tensor of POSE records (.cpu().numpy().view(POSE)), modelviews None or a float32 (n, n_objects, 16) tensor --
+    what poses_from_players / object_modelviews_from_players compute on the host, with the project's sincos.
+    Asynchronous on `stream`."""
+    import torch
+    n = _n_players(states)
+    ps, ks, uploaded = _device_tensor(states, 'states')
+    dev = ks.device
+    poses = torch.empty((n, POSE.itemsize // 4), dtype=torch.float32, device=dev)
+    mvs, po, n_obj, ko = None, None, 0, None
+    if offsets is not None:
+        if isinstance(offsets, np.ndarray):
+            offsets = np.ascontiguousarray(offsets, np.float32)
+        if len(offsets.shape) != 3 or offsets.shape[0] != n or offsets.shape[2] != 3:
+            raise ValueError('offsets must be (n, n_objects, 3) for %d players, got %s' % (n, tuple(offsets.shape)))
+        po, ko, up2 = _device_tensor(offsets, 'offsets')
+        uploaded = uploaded or up2
+        n_obj = int(offsets.shape[1])
+        mvs = torch.empty((n, n_obj, 16), dtype=torch.float32, device=dev)
+    _check(lib().rdoom_poses_from_players_device(ctypes.c_void_p(ps), n, int(width), int(height), ctypes.c_float(time),
+                                                 ctypes.c_void_p(po), n_obj, ctypes.c_void_p(poses.data_ptr()),
+                                                 ctypes.c_void_p(mvs.data_ptr() if mvs is not None else None),
+                                                 ctypes.c_void_p(_stream_handle(stream))))
+    if uploaded:
+        torch.cuda.synchronize(dev)
+    return poses, mvs
 
 
 def _stream_handle(stream):

@@ -85,4 +85,27 @@ struct ResolveArgs {
 };
 rdoom_status launch_resolve(hipStream_t st, const ResolveArgs &args);
 
+// Kernel 0 of rdoom_batch_render_players, and all of rdoom_poses_from_players_device: players' states -> cameras (frames.hip).
+// One lane per (player, object); every output is optional.
+struct PlayerFrameArgs {
+  const rdoom_player_state *states;
+  uint32_t n;                 // players
+  uint32_t lanes;             // lanes per player: the offsets' row length (n_objects), or 1 without offsets
+  const float *offsets;       // n x lanes x xyz, or null (lanes == 1)
+  float proj[16], zk, time;   // player_projection's, and u_time
+  const uint32_t *levels;     // level of each player, or null (level 0)
+  uint32_t n_slices;          // levels of the batch's set: a level >= n_slices is rendered as 0 and recorded in *error_word
+  uint32_t *error_word;
+  const uint8_t *lights;      // 256 bytes per level slot at lights_stride (0: one shared table)
+  uint32_t lights_stride;
+  PoseConst *pose_consts;     // n records, or null (then nothing below is written either)
+  ObjectConst *object_consts; // n x n_render_objects records, or null
+  uint32_t n_render_objects;
+  rdoom_pose *poses_out;      // n poses, or null
+  float *modelviews_out;      // n x lanes x 16 floats, or null
+};
+rdoom_status launch_player_frames(hipStream_t st, const PlayerFrameArgs &args);
+// the camera's projection for a width x height frame (rdoom_pose_from_player's, bit for bit) and render_impl's depth constant zk
+rdoom_status player_projection(uint32_t width, uint32_t height, float proj[16], float *zk);
+
 }  // namespace rdoom_dev

@@ -74,7 +74,8 @@ struct rdoom_batch {
   // kernels of a stream (the 1/8 share of config 4 queues 9 x 13 packets per step for a few hundred microseconds of work each).
   uint32_t *d_zeroed = nullptr;
   uint32_t *d_fix_count = nullptr;  // [0] = queued pixels, [1] = error flag (fixup list overflow), [2] = error flag (the set-up kernel
-                                    // disagreed with the cull kernel about a triangle: the counting sort's buckets would not add up)
+                                    // disagreed with the cull kernel about a triangle: the counting sort's buckets would not add up),
+                                    // [3] = rdoom_batch_render_players' level error word (level_error)
   uint2 *d_fix_list = nullptr;
   uint32_t fix_cap = 1u << 20;
   uint32_t *d_counts = nullptr, *d_vis = nullptr, *d_prim = nullptr;
@@ -108,6 +109,8 @@ struct rdoom_batch {
   bool last_skip_vis = false;
   uint8_t *d_rgb = nullptr;  // rdoom_batch_read_rgb's staging (allocated on first use, at most RGB_STAGING_BYTES or one frame)
   size_t rgb_bytes = 0;
+  // the last render was rdoom_batch_render_players: its levels are on the device only (the pinned staging is an older render's)
+  bool last_levels_on_device = false;
 };
 
 // Every entry point that touches a batch's memory or waits for its work first makes the level's device current: a host
@@ -128,13 +131,20 @@ static hipError_t read_back(const rdoom_batch *b, void *dst, const void *src, si
   return hipStreamSynchronize(b->copy_stream);
 }
 
+// fix[3] is rdoom_batch_render_players' error word: ~p for the first pose p whose level lay outside the set (0: none)
+static rdoom_status level_error(const rdoom_batch *b, uint32_t word) {
+  if (!word) return RDOOM_OK;
+  return rdoom::fail(RDOOM_BAD_ARG, "pose %u of the last render names a level outside the set of %u (rendered as level 0)", ~word,
+                     b->level->view.n_slices);
+}
+
 static rdoom_status device_flags(const rdoom_batch *b, uint32_t *out_fixups = nullptr) {
-  uint32_t fix[3] = {0, 0, 0};
+  uint32_t fix[4] = {0, 0, 0, 0};
   HIP_TRY(read_back(b, fix, b->d_fix_count, sizeof fix));
   if (out_fixups) *out_fixups = fix[0];
   if (fix[1]) return rdoom::fail(RDOOM_BAD_LEVEL, "alpha-leak fixup list overflow (%u pixels)", fix[0]);
   if (fix[2]) return rdoom::fail(RDOOM_HIP_ERROR, "internal: set-up and cull kernels disagree about a triangle (build flags changed?)");
-  return RDOOM_OK;
+  return level_error(b, fix[3]);
 }
 
 extern "C" {
@@ -586,81 +596,36 @@ struct DoneGuard {
 };
 }  // namespace
 
-static rdoom_status render_impl(rdoom_batch *b, const rdoom_pose *poses, const uint8_t *lights, uint32_t lights_stride,
-                                uint32_t n, uint32_t kinds_mask, hipStream_t st, rdoom_timings *tm,
-                                const float *object_modelviews = nullptr, uint32_t n_objects = 0, bool profiled = false,
-                                const uint32_t *level_of_pose = nullptr) {
-  if (!b || !poses || !lights) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
-  if (n == 0 || n > b->max_poses) return rdoom::fail(RDOOM_BAD_ARG, "n_poses %u outside 1..%u", n, b->max_poses);
-  const rdoom_level *lv = b->level;
-  if (level_of_pose)
-    for (uint32_t p = 0; p < n; p++)
-      if (level_of_pose[p] >= lv->view.n_slices)
-        return rdoom::fail(RDOOM_BAD_ARG, "pose %u names level %u of a set of %u", p, level_of_pose[p], lv->view.n_slices);
-  HIP_TRY(hipSetDevice(lv->device));  // level, scratch and kernels on one device (several GPUs driven from one process)
-  if (object_modelviews && n_objects < lv->n_objects)
-    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u but the level draws objects 0..%u", n_objects, lv->n_objects - 1);
-  HT_DECL
-  const uint32_t sg = b->stage;  // this render's staging buffers: the H2D copy that last read them is two renders back
-  b->stage = (sg + 1u) % rdoom_batch::STAGES;
-  HIP_TRY(hipEventSynchronize(b->ev_copy[sg]));
-  HT_MARK(0);
-  PoseConst *h_poses = b->h_poses[sg];
-  if (object_modelviews) {
-    const size_t count = (size_t)b->max_poses * lv->n_objects;
-    if (!b->d_objects) HIP_TRY(hipMalloc((void **)&b->d_objects, sizeof(ObjectConst) * count));
-    for (auto &h : b->h_objects)
-      if (!h) HIP_TRY(hipHostMalloc((void **)&h, sizeof(ObjectConst) * count, hipHostMallocDefault));
-    ObjectConst *h_objects = b->h_objects[sg];
-    for (uint32_t p = 0; p < n; p++)
-      for (uint32_t o = 0; o < lv->n_objects; o++) {
-        ObjectConst &oc = h_objects[(size_t)p * lv->n_objects + o];
-        const float *M = object_modelviews + ((size_t)p * n_objects + o) * 16;
-        mat_mul_v1(poses[p].projection, M, oc.pm);
-        std::memcpy(oc.mv, M, sizeof oc.mv);
-        oc.vr0 = atan2f(oc.pm[8], oc.pm[10]);  // sky.vert:10-12
-        oc.vr1 = oc.pm[9] / oc.pm[11];
-        oc.pad0 = oc.pad1 = 0;
-      }
-  }
-  for (uint32_t p = 0; p < n; p++) {  // V1: PM = P * M, plain multiply/add, left to right
-    PoseConst &pc = h_poses[p];
-    const float *P = poses[p].projection, *M = poses[p].modelview;
-    mat_mul_v1(P, M, pc.pm);
-    std::memcpy(pc.mv, M, sizeof pc.mv);
-    std::memcpy(pc.proj, P, sizeof pc.proj);
-    pc.time = poses[p].time;
-    pc.vr0 = atan2f(pc.pm[8], pc.pm[10]);  // sky.vert:10-12
-    pc.vr1 = pc.pm[9] / pc.pm[11];
-    pc.zk = pc.proj[11] != 0.0f ? pc.proj[10] / pc.proj[11] : 0.0f;  // S5: Z - zk * W is small for a perspective matrix
-    std::memcpy(pc.lights, lights + (size_t)p * lights_stride, 256);
-    pc.level = level_of_pose ? level_of_pose[p] : 0u;
-    pc.pad0 = pc.pad1 = pc.pad2 = 0u;
-  }
-  b->last_n = n;
-  HT_MARK(1);
-  hipEvent_t *ev = b->ev;  // the four marks of this render: the batch's own, or a slot of the ring when nobody waits
+// The four marks of a render: the batch's own, or a slot of the ring when nobody waits (RDOOM_RENDER_PROFILED)
+static rdoom_status render_marks(rdoom_batch *b, bool profiled, hipEvent_t **out) {
+  hipEvent_t *ev = b->ev;
   if (profiled) {
     if (b->ring_n == rdoom_batch::RING) return rdoom::fail(RDOOM_BAD_ARG, "%u profiled renders pending: collect the timings first", b->ring_n);
     ev = b->ring[b->ring_n];
     for (int k = 0; k < 4; k++)
       if (!ev[k]) HIP_TRY(hipEventCreate(&ev[k]));
   }
+  *out = ev;
+  return RDOOM_OK;
+}
+
+// The pipeline every render queues once its per-pose constants are (or are about to be) in b->d_poses / b->d_objects: one fill of
+// the zeroed words, then `constants` (the render's own launch that writes them, if any: it runs after the fill, so that it may set
+// an error word), then set-up -> bin -> raster -> fragment -> fixup, ev_done, and the profiling marks ev[1..3].  ev[0] and the
+// DoneGuard are the caller's, recorded and armed before anything of the render was queued.
+extern "C++" {  // (a template, inside the C ABI's extern "C" block)
+template <class Constants>
+static rdoom_status queue_pipeline(rdoom_batch *b, uint32_t n, uint32_t kinds_mask, hipStream_t st, rdoom_timings *tm,
+                                   bool objects, bool profiled, hipEvent_t *ev, DoneGuard &done, Constants &&constants) {
+  HT_DECL
+  const rdoom_level *lv = b->level;
   const bool marks = tm || profiled;
-  if (marks) HIP_TRY(hipEventRecord(ev[0], st));
-  DoneGuard done{b, st};
-  done.armed = true;  // from here on work of this render may be queued: whatever happens, ev_done is recorded after it
-  HIP_TRY(hipMemcpyAsync(b->d_poses, h_poses, sizeof(PoseConst) * n, hipMemcpyHostToDevice, st));
-  if (object_modelviews)
-    HIP_TRY(hipMemcpyAsync(b->d_objects, b->h_objects[sg], sizeof(ObjectConst) * (size_t)n * lv->n_objects,
-                           hipMemcpyHostToDevice, st));
-  HIP_TRY(hipEventRecord(b->ev_copy[sg], st));
-  HT_MARK(2);
   const int W = (int)b->width, H = (int)b->height, PITCH = (int)b->pitch;
-  // fix_count[0..2], the poses' visible-triangle counts and depth-bucket histograms (of the first n poses): one fill
+  // fix_count[0..3], the poses' visible-triangle counts and depth-bucket histograms (of the first n poses): one fill
   HIP_TRY(hipMemsetAsync(b->d_zeroed, 0, (size_t)((const char *)b->d_ghist - (const char *)b->d_zeroed) + setup_histogram_bytes(n), st));
+  if (rdoom_status rs = constants()) return rs;
   if (lv->ntri)
-    if (rdoom_status rs = launch_setup(st, n, lv->view, b->d_poses, object_modelviews ? (const ObjectConst *)b->d_objects : nullptr,
+    if (rdoom_status rs = launch_setup(st, n, lv->view, b->d_poses, objects ? (const ObjectConst *)b->d_objects : nullptr,
                                        lv->n_objects, W, H, kinds_mask, b->d_recs, b->d_visible, b->d_counts,
                                        b->d_ghist, b->cap, b->d_fix_count + 2))
       return rs;
@@ -726,6 +691,76 @@ static rdoom_status render_impl(rdoom_batch *b, const rdoom_pose *poses, const u
   }
   return RDOOM_OK;
 }
+}  // extern "C++"
+
+static rdoom_status render_impl(rdoom_batch *b, const rdoom_pose *poses, const uint8_t *lights, uint32_t lights_stride,
+                                uint32_t n, uint32_t kinds_mask, hipStream_t st, rdoom_timings *tm,
+                                const float *object_modelviews = nullptr, uint32_t n_objects = 0, bool profiled = false,
+                                const uint32_t *level_of_pose = nullptr) {
+  if (!b || !poses || !lights) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (n == 0 || n > b->max_poses) return rdoom::fail(RDOOM_BAD_ARG, "n_poses %u outside 1..%u", n, b->max_poses);
+  const rdoom_level *lv = b->level;
+  if (level_of_pose)
+    for (uint32_t p = 0; p < n; p++)
+      if (level_of_pose[p] >= lv->view.n_slices)
+        return rdoom::fail(RDOOM_BAD_ARG, "pose %u names level %u of a set of %u", p, level_of_pose[p], lv->view.n_slices);
+  HIP_TRY(hipSetDevice(lv->device));  // level, scratch and kernels on one device (several GPUs driven from one process)
+  if (object_modelviews && n_objects < lv->n_objects)
+    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u but the level draws objects 0..%u", n_objects, lv->n_objects - 1);
+  HT_DECL
+  const uint32_t sg = b->stage;  // this render's staging buffers: the H2D copy that last read them is two renders back
+  b->stage = (sg + 1u) % rdoom_batch::STAGES;
+  HIP_TRY(hipEventSynchronize(b->ev_copy[sg]));
+  HT_MARK(0);
+  PoseConst *h_poses = b->h_poses[sg];
+  if (object_modelviews) {
+    const size_t count = (size_t)b->max_poses * lv->n_objects;
+    if (!b->d_objects) HIP_TRY(hipMalloc((void **)&b->d_objects, sizeof(ObjectConst) * count));
+    for (auto &h : b->h_objects)
+      if (!h) HIP_TRY(hipHostMalloc((void **)&h, sizeof(ObjectConst) * count, hipHostMallocDefault));
+    ObjectConst *h_objects = b->h_objects[sg];
+    for (uint32_t p = 0; p < n; p++)
+      for (uint32_t o = 0; o < lv->n_objects; o++) {
+        ObjectConst &oc = h_objects[(size_t)p * lv->n_objects + o];
+        const float *M = object_modelviews + ((size_t)p * n_objects + o) * 16;
+        mat_mul_v1(poses[p].projection, M, oc.pm);
+        std::memcpy(oc.mv, M, sizeof oc.mv);
+        oc.vr0 = atan2f(oc.pm[8], oc.pm[10]);  // sky.vert:10-12
+        oc.vr1 = oc.pm[9] / oc.pm[11];
+        oc.pad0 = oc.pad1 = 0;
+      }
+  }
+  for (uint32_t p = 0; p < n; p++) {  // V1: PM = P * M, plain multiply/add, left to right
+    PoseConst &pc = h_poses[p];
+    const float *P = poses[p].projection, *M = poses[p].modelview;
+    mat_mul_v1(P, M, pc.pm);
+    std::memcpy(pc.mv, M, sizeof pc.mv);
+    std::memcpy(pc.proj, P, sizeof pc.proj);
+    pc.time = poses[p].time;
+    pc.vr0 = atan2f(pc.pm[8], pc.pm[10]);  // sky.vert:10-12
+    pc.vr1 = pc.pm[9] / pc.pm[11];
+    pc.zk = pc.proj[11] != 0.0f ? pc.proj[10] / pc.proj[11] : 0.0f;  // S5: Z - zk * W is small for a perspective matrix
+    std::memcpy(pc.lights, lights + (size_t)p * lights_stride, 256);
+    pc.level = level_of_pose ? level_of_pose[p] : 0u;
+    pc.pad0 = pc.pad1 = pc.pad2 = 0u;
+  }
+  b->last_n = n;
+  HT_MARK(1);
+  b->last_levels_on_device = false;
+  hipEvent_t *ev = nullptr;
+  if (rdoom_status rs = render_marks(b, profiled, &ev)) return rs;
+  const bool marks = tm || profiled;
+  if (marks) HIP_TRY(hipEventRecord(ev[0], st));
+  DoneGuard done{b, st};
+  done.armed = true;  // from here on work of this render may be queued: whatever happens, ev_done is recorded after it
+  HIP_TRY(hipMemcpyAsync(b->d_poses, h_poses, sizeof(PoseConst) * n, hipMemcpyHostToDevice, st));
+  if (object_modelviews)
+    HIP_TRY(hipMemcpyAsync(b->d_objects, b->h_objects[sg], sizeof(ObjectConst) * (size_t)n * lv->n_objects,
+                           hipMemcpyHostToDevice, st));
+  HIP_TRY(hipEventRecord(b->ev_copy[sg], st));
+  HT_MARK(2);
+  return queue_pipeline(b, n, kinds_mask, st, tm, object_modelviews != nullptr, profiled, ev, done, [] { return RDOOM_OK; });
+}
 
 rdoom_status rdoom_batch_render(rdoom_batch *batch, const rdoom_pose *poses, const uint8_t *lights,
                                 uint32_t lights_stride, uint32_t n_poses, uint32_t kinds_mask, void *stream) {
@@ -787,6 +822,50 @@ rdoom_status rdoom_batch_render_levels(rdoom_batch *batch, const rdoom_pose *pos
   if (flags & ~(uint32_t)RDOOM_RENDER_PROFILED) return rdoom::fail(RDOOM_BAD_ARG, "unknown flags 0x%x", flags);
   return render_impl(batch, poses, lights, lights_stride, n_poses, kinds_mask, (hipStream_t)stream, nullptr, object_modelviews,
                      n_objects, (flags & RDOOM_RENDER_PROFILED) != 0u, level_of_pose);
+}
+
+rdoom_status rdoom_batch_render_players(rdoom_batch *b, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                        const float *d_object_offsets, uint32_t n_objects, const uint8_t *d_lights,
+                                        uint32_t lights_stride, float time, uint32_t n_players, uint32_t kinds_mask,
+                                        uint32_t flags, void *stream, rdoom_pose *d_poses_out, float *d_object_modelviews_out) {
+  // every check before anything is queued or allocated
+  if (!b || !d_states || !d_lights) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (flags & ~(uint32_t)RDOOM_RENDER_PROFILED) return rdoom::fail(RDOOM_BAD_ARG, "unknown flags 0x%x", flags);
+  if (n_players == 0 || n_players > b->max_poses) return rdoom::fail(RDOOM_BAD_ARG, "n_players %u outside 1..%u", n_players, b->max_poses);
+  const rdoom_level *lv = b->level;
+  if (d_object_offsets && n_objects < lv->n_objects)
+    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u but the level draws objects 0..%u", n_objects, lv->n_objects - 1);
+  if (d_object_offsets && n_objects > 4096u) return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u (at most 4096)", n_objects);
+  if (d_object_modelviews_out && !d_object_offsets) return rdoom::fail(RDOOM_BAD_ARG, "object modelviews out without object offsets");
+  if (!d_levels && lv->view.n_slices > 1)
+    return rdoom::fail(RDOOM_BAD_ARG, "d_levels is null, but the batch's level set has %u levels", lv->view.n_slices);
+  if (lights_stride != 0 && lights_stride != 256) return rdoom::fail(RDOOM_BAD_ARG, "lights_stride %u: 0 or 256", lights_stride);
+  const bool profiled = (flags & RDOOM_RENDER_PROFILED) != 0u;
+  if (profiled && b->ring_n == rdoom_batch::RING)
+    return rdoom::fail(RDOOM_BAD_ARG, "%u profiled renders pending: collect the timings first", b->ring_n);
+  PlayerFrameArgs a{};
+  if (rdoom_status rs = player_projection(b->width, b->height, a.proj, &a.zk)) return rs;
+  HIP_TRY(hipSetDevice(lv->device));
+  if (d_object_offsets && !b->d_objects)  // (the one allocation of this path: on the batch's first render with objects)
+    HIP_TRY(hipMalloc((void **)&b->d_objects, sizeof(ObjectConst) * (size_t)b->max_poses * lv->n_objects));
+  const hipStream_t st = (hipStream_t)stream;
+  a.states = d_states, a.n = n_players, a.time = time;
+  a.offsets = d_object_offsets, a.lanes = d_object_offsets ? n_objects : 1u;
+  a.levels = d_levels, a.n_slices = lv->view.n_slices, a.error_word = b->d_fix_count + 3;
+  a.lights = d_lights, a.lights_stride = lights_stride;
+  a.pose_consts = b->d_poses;
+  a.object_consts = d_object_offsets ? b->d_objects : nullptr, a.n_render_objects = d_object_offsets ? lv->n_objects : 0u;
+  a.poses_out = d_poses_out, a.modelviews_out = d_object_modelviews_out;
+  // the pinned staging is not touched (no wait on ev_copy); the levels of this render live on the device only
+  b->last_n = n_players;
+  b->last_levels_on_device = true;
+  hipEvent_t *ev = nullptr;
+  if (rdoom_status rs = render_marks(b, profiled, &ev)) return rs;
+  if (profiled) HIP_TRY(hipEventRecord(ev[0], st));
+  DoneGuard done{b, st};
+  done.armed = true;
+  return queue_pipeline(b, n_players, kinds_mask, st, nullptr, d_object_offsets != nullptr, profiled, ev, done,
+                        [&] { return launch_player_frames(st, a); });
 }
 
 rdoom_status rdoom_level_num_levels(const rdoom_level *level, uint32_t *out) {
@@ -887,6 +966,9 @@ rdoom_status rdoom_batch_read_primitive_ids(rdoom_batch *b, uint32_t first, uint
   if ((uint64_t)first + count > b->last_n) return rdoom::fail(RDOOM_BAD_ARG, "frame range outside the last render");
   const size_t frame = (size_t)b->pitch * b->height;
   HIP_TRY(bind_device(b));
+  uint32_t level_word = 0;  // (the one device flag that concerns primitive ids: a level rendered as 0 instead of the one named)
+  HIP_TRY(read_back(b, &level_word, b->d_fix_count + 3, sizeof level_word));
+  if (rdoom_status rs = level_error(b, level_word)) return rs;
   if (count)
     HIP_TRY(read_back(b, host_out, b->d_prim + frame * first, sizeof(uint32_t) * b->width, (size_t)b->height * count, sizeof(uint32_t) * b->pitch));
   return RDOOM_OK;
@@ -906,6 +988,10 @@ static rdoom_status rgb_args(const rdoom_batch *b, uint32_t first, uint32_t coun
   if ((uint64_t)first + count > b->last_n) return rdoom::fail(RDOOM_BAD_ARG, "frame range outside the last render");
   const rdoom_level *lv = b->level;
   if (std::find(lv->has_palette.begin(), lv->has_palette.end(), 0) != lv->has_palette.end()) {
+    // rdoom_batch_render_players: the levels are on the device, so every level of the set must have a palette
+    if (b->last_levels_on_device)
+      return rdoom::fail(RDOOM_BAD_ARG, "level %u of the set was created without a playpal, and the last render's levels are on the device",
+                         (uint32_t)(std::find(lv->has_palette.begin(), lv->has_palette.end(), 0) - lv->has_palette.begin()));
     // the levels of the last render's poses: its pinned staging (the next render writes the other one)
     const PoseConst *pc = b->h_poses[(b->stage + rdoom_batch::STAGES - 1u) % rdoom_batch::STAGES];
     for (uint32_t p = first; p < first + count; p++)

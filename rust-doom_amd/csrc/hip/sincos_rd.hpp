@@ -1,0 +1,24 @@
+// The project's own binary32 sine and cosine, shared by the player step (world.hip) and the player cameras (frames.hip): one
+// definition, so that a camera computed from a state and the look direction the step computes from it read the same bits.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#pragma clang fp contract(off)
+
+namespace rdoom_dev {
+
+// Project-owned binary32 sine and cosine: Cody-Waite reduction by pi/2 in three parts (the first two short enough that
+// j * part is exact for |j| < 2^12), then the minimax polynomials of the Cephes library's sinf / cosf on [-pi/4, pi/4].
+// Every operation is written out, so an IEEE host evaluating the same expressions gets the same bits.
+__device__ __forceinline__ void sincos_rd(float x, float &s, float &c) {
+  const float j = __builtin_floorf(x * 0.636619772f + 0.5f);
+  const float r = ((x - j * 1.5703125f) - j * 4.837512969970703125e-4f) - j * 7.54978995489188216e-8f;
+  const float z = r * r;
+  const float ps = ((-1.9515295891e-4f * z + 8.3321608736e-3f) * z - 1.6666654611e-1f) * z * r + r;
+  const float pc = ((2.443315711809948e-5f * z - 1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z * z - 0.5f * z + 1.0f;
+  const int q = (int)j & 3;
+  s = q == 0 ? ps : (q == 1 ? pc : (q == 2 ? -ps : -pc));
+  c = q == 0 ? pc : (q == 1 ? -ps : (q == 2 ? -pc : ps));
+}
+
+}  // namespace rdoom_dev

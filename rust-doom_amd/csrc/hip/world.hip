@@ -5,7 +5,7 @@
 // Arithmetic: binary32 in the reference's operation order (cgmath: dot = (x x' + y y') + z z', cross component by component,
 // vector / scalar divides every component, normalize_or_zero = v / max(|v|, f32::EPSILON)); the build passes
 // -ffp-contract=off and HIP divides and takes square roots correctly rounded, so every result is the one an IEEE host
-// computes with the same expressions.  No fastmath.hpp short forms, no device libm: sin / cos come from sincos_rd below.
+// computes with the same expressions.  No fastmath.hpp short forms, no device libm: sin / cos come from sincos_rd (sincos_rd.hpp).
 //
 // Shape: one lane per query / player -- the sweeps of one player are strictly sequential -- and one wave per workgroup.  Each
 // lane walks the BSP with its own node stack in LDS (word `slot * 64 + lane`: no bank conflicts), sized by the tree's depth at
@@ -19,6 +19,7 @@
 #include "../common.hpp"
 #include "../host/game_world.hpp"
 #include "kernels.hpp"
+#include "sincos_rd.hpp"
 
 namespace {
 
@@ -235,19 +236,7 @@ __device__ __forceinline__ Contact sweep_world(const WorldView &w, V3 center, fl
   return first;
 }
 
-// Project-owned binary32 sine and cosine: Cody-Waite reduction by pi/2 in three parts (the first two short enough that
-// j * part is exact for |j| < 2^12), then the minimax polynomials of the Cephes library's sinf / cosf on [-pi/4, pi/4].
-// Every operation is written out, so an IEEE host evaluating the same expressions gets the same bits.
-__device__ __forceinline__ void sincos_rd(float x, float &s, float &c) {
-  const float j = __builtin_floorf(x * 0.636619772f + 0.5f);
-  const float r = ((x - j * 1.5703125f) - j * 4.837512969970703125e-4f) - j * 7.54978995489188216e-8f;
-  const float z = r * r;
-  const float ps = ((-1.9515295891e-4f * z + 8.3321608736e-3f) * z - 1.6666654611e-1f) * z * r + r;
-  const float pc = ((2.443315711809948e-5f * z - 1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z * z - 0.5f * z + 1.0f;
-  const int q = (int)j & 3;
-  s = q == 0 ? ps : (q == 1 ? pc : (q == 2 ? -ps : -pc));
-  c = q == 0 ? pc : (q == 1 ? -ps : (q == 2 ? -pc : ps));
-}
+using rdoom_dev::sincos_rd;  // (sincos_rd.hpp: shared with the player cameras of frames.hip)
 
 __global__ __launch_bounds__(WAVE) void sweep_kernel(WorldView w, const float *spheres, const float *vels, uint32_t n,
                                                      const float *offsets, uint32_t n_objects, float *out) {
