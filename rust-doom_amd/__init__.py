@@ -726,6 +726,23 @@ class WorldTriggerArrays(ctypes.Structure):
 WORLD_NODE = np.dtype([('origin', '<f4', 2), ('displace', '<f4', 2), ('length', '<f4'), ('positive', '<i4'), ('negative', '<i4')])
 
 
+def _world_arrays(a):
+    """World.arrays and WorldSet.arrays: copies of a WorldArrays' arrays"""
+    v = BuiltLevel._view
+    return dict(nodes=v(None, a.nodes, a.n_nodes, WORLD_NODE), chunks=v(None, a.chunks, a.n_chunks * 2, np.uint32).reshape(-1, 2),
+                triangles=v(None, a.triangles, a.n_triangles * 4, np.uint32).reshape(-1, 4),
+                verts=v(None, a.verts, a.n_verts * 3, np.float32).reshape(-1, 3),
+                dynamics=v(None, a.dynamics, a.n_dynamics * 3, np.uint32).reshape(-1, 3),
+                n_static_triangles=a.n_static_triangles, n_objects=a.n_objects, node_depth=a.node_depth)
+
+
+def _trigger_arrays(a):
+    """World.triggers and WorldSet.triggers: copies of a WorldTriggerArrays' arrays"""
+    v = BuiltLevel._view
+    return dict(triggers=v(None, a.triggers, a.n_triggers, TRIGGER), effects=v(None, a.effects, a.n_effects, MOVE_EFFECT),
+                n_objects=a.n_objects)
+
+
 def player_config_default():
     """rdoom_player_config_default: Config::default's physics half (game/src/player.rs:73-92) as a PLAYER_CONFIG record"""
     cfg = np.zeros(1, PLAYER_CONFIG)
@@ -837,9 +854,10 @@ def _device_tensor(a, what):
 
 
 class _GameStepArgs:
-    """the arguments of a game step (World.step_game, WorldSet.step_game), checked and on the device: states PLAYER_STATE records
-    (numpy: a stepped copy is returned) or a GPU tensor of n * 40 bytes (stepped in place); inputs (n_ticks, n) PLAYER_INPUT
-    records, or a GPU tensor with n_ticks given; actions None or (n_ticks, n) ACTION_* bytes; config a PLAYER_CONFIG or None"""
+    """the arguments of a step (World.step, World.step_game, WorldSet.step_game), checked and on the device: states
+    PLAYER_STATE records (numpy: a stepped copy is returned) or a GPU tensor of n * 40 bytes (stepped in place); inputs
+    (n_ticks, n) PLAYER_INPUT records, or a GPU tensor with n_ticks given; actions None or (n_ticks, n) ACTION_* bytes; config a
+    PLAYER_CONFIG or None"""
 
     def __init__(self, states, inputs, actions, n_ticks, config):
         if isinstance(actions, np.ndarray):
@@ -882,14 +900,44 @@ class _GameStepArgs:
 
     def result(self):
         """after the launch: the states tensor, or a stepped numpy copy"""
-        if not self.is_np:
-            if self.ka is not None and isinstance(self.actions, np.ndarray):
-                import torch
-                torch.cuda.synchronize(self.ks.device)
-            return self.states
+        if self.is_np or isinstance(self.actions, np.ndarray):  # (numpy actions: their upload is freed on return)
+            import torch
+            torch.cuda.synchronize(self.ks.device)
+        return self.ks.cpu().numpy().view(PLAYER_STATE).copy() if self.is_np else self.states
+
+
+def _game_args(game_bytes, game, offsets, *levels, players=None):
+    """(n, n_objects) of a game's device tensors, checked: game (n * game_bytes bytes), offsets and a world set's levels (a world
+    passes none); n must be `players` when given (a step's)"""
+    import torch
+    for t, what in zip((game, offsets) + levels, ('game', 'offsets', 'levels')):
+        if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous tensor on the GPU' % what)
+    if offsets.dtype != torch.float32 or offsets.dim() != 3 or offsets.shape[2] != 3:
+        raise ValueError('offsets must be a float32 (n, n_objects, 3) tensor, got %s %s' % (offsets.dtype, tuple(offsets.shape)))
+    n = int(offsets.shape[0])
+    if game.numel() * game.element_size() != n * game_bytes:
+        raise ValueError('the game state must hold %d players x %d bytes' % (n, game_bytes))
+    for lv in levels:
+        if lv.element_size() != 4 or lv.numel() != n:
+            raise ValueError('levels must hold one 32-bit slot per player (%d), got %s %s' % (n, lv.dtype, tuple(lv.shape)))
+    if players is not None and n != players:
+        raise ValueError('%d players, but game state and offsets for %d' % (players, n))
+    return n, int(offsets.shape[1])
+
+
+def _reset_masked(mask, reset):
+    """reset_game's call reset(mask pointer): mask None (every player), or n bools / bytes, numpy (copied to the device) or a GPU
+    tensor; returns once the launch no longer reads the mask's memory"""
+    pm, km = None, None
+    if mask is not None:
+        if isinstance(mask, np.ndarray):
+            mask = np.ascontiguousarray(mask).astype(np.uint8)
+        pm, km, _ = _device_tensor(mask, 'mask')
+    _check(reset(ctypes.c_void_p(pm)))
+    if km is not None:
         import torch
-        torch.cuda.synchronize(self.ks.device)
-        return self.ks.cpu().numpy().view(PLAYER_STATE).copy()
+        torch.cuda.synchronize(km.device)
 
 
 class World:
@@ -918,12 +966,7 @@ class World:
         object id, first triangle, end), n_static_triangles, n_objects, node_depth"""
         a = WorldArrays()
         _check(lib().rdoom_world_host_arrays(self._h, ctypes.byref(a)))
-        v = BuiltLevel._view
-        return dict(nodes=v(None, a.nodes, a.n_nodes, WORLD_NODE), chunks=v(None, a.chunks, a.n_chunks * 2, np.uint32).reshape(-1, 2),
-                    triangles=v(None, a.triangles, a.n_triangles * 4, np.uint32).reshape(-1, 4),
-                    verts=v(None, a.verts, a.n_verts * 3, np.float32).reshape(-1, 3),
-                    dynamics=v(None, a.dynamics, a.n_dynamics * 3, np.uint32).reshape(-1, 3),
-                    n_static_triangles=a.n_static_triangles, n_objects=a.n_objects, node_depth=a.node_depth)
+        return _world_arrays(a)
 
     def _offsets(self, offsets, n):
         if offsets is None:
@@ -959,36 +1002,11 @@ class World:
         stepped copy is returned) or a contiguous GPU tensor of n * 40 bytes (stepped in place, asynchronously on `stream`).
         inputs: (n_ticks, n) PLAYER_INPUT records, or a GPU tensor of n_ticks * n * 20 bytes with n_ticks given.
         config: a PLAYER_CONFIG record or None (the defaults); object_offsets None or (n, n_objects, 3)."""
-        is_np = isinstance(states, np.ndarray)
-        if is_np:
-            states = np.ascontiguousarray(states, PLAYER_STATE).reshape(-1)
-            n = len(states)
-        else:
-            if states.numel() * states.element_size() % PLAYER_STATE.itemsize:
-                raise ValueError('a states tensor must hold n * %d bytes' % PLAYER_STATE.itemsize)
-            n = states.numel() * states.element_size() // PLAYER_STATE.itemsize
-        if isinstance(inputs, np.ndarray):
-            inputs = np.ascontiguousarray(inputs, PLAYER_INPUT)
-            inputs = inputs.reshape(-1, n) if inputs.size else inputs.reshape(0, n)
-            if n_ticks is not None and n_ticks != inputs.shape[0]:
-                raise ValueError('n_ticks %d, but inputs for %d ticks' % (n_ticks, inputs.shape[0]))
-            n_ticks = inputs.shape[0]
-        elif n_ticks is None:
-            raise ValueError('n_ticks is needed with an input tensor')
-        ps, ks, _ = _device_tensor(states, 'states')
-        pi, ki, _ = _device_tensor(inputs, 'inputs')
-        po, ko, n_obj = self._offsets(object_offsets, n)
-        cfg = None
-        if config is not None:
-            cfg = np.ascontiguousarray(np.asarray(config, PLAYER_CONFIG).reshape(1))
-        _check(lib().rdoom_world_step_players(self._h, ctypes.c_void_p(ps), ctypes.c_void_p(pi), n, int(n_ticks),
-                                              cfg.ctypes.data_as(ctypes.c_void_p) if cfg is not None else None, ctypes.c_float(dt),
-                                              ctypes.c_void_p(po), n_obj, ctypes.c_void_p(_stream_handle(stream))))
-        if not is_np:
-            return states
-        import torch
-        torch.cuda.synchronize(ks.device)
-        return ks.cpu().numpy().view(PLAYER_STATE).copy()
+        a = _GameStepArgs(states, inputs, None, n_ticks, config)
+        po, ko, n_obj = self._offsets(object_offsets, a.n)
+        _check(lib().rdoom_world_step_players(self._h, ctypes.c_void_p(a.ps), ctypes.c_void_p(a.pi), a.n, int(a.n_ticks), a.cfg_ptr(),
+                                              ctypes.c_float(dt), ctypes.c_void_p(po), n_obj, ctypes.c_void_p(_stream_handle(stream))))
+        return a.result()
 
     # ---- doors, lifts and exits --------------------------------------------------------------------------------------------
     def triggers(self):
@@ -996,9 +1014,7 @@ class World:
         (the game's object count, the least n_objects of every game call)"""
         a = WorldTriggerArrays()
         _check(lib().rdoom_world_triggers(self._h, ctypes.byref(a)))
-        v = BuiltLevel._view
-        return dict(triggers=v(None, a.triggers, a.n_triggers, TRIGGER), effects=v(None, a.effects, a.n_effects, MOVE_EFFECT),
-                    n_objects=a.n_objects)
+        return _trigger_arrays(a)
 
     def game_bytes(self):
         """rdoom_world_game_bytes: the bytes of one player's game state"""
@@ -1015,41 +1031,20 @@ class World:
         self.reset_game(game, offsets, stream=stream)
         return game, offsets
 
-    def _game_args(self, game, offsets):
-        import torch
-        for t, what in ((game, 'game'), (offsets, 'offsets')):
-            if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or not t.is_contiguous():
-                raise ValueError('%s must be a contiguous tensor on the GPU' % what)
-        if offsets.dtype != torch.float32 or offsets.dim() != 3 or offsets.shape[2] != 3:
-            raise ValueError('offsets must be a float32 (n, n_objects, 3) tensor, got %s %s' % (offsets.dtype, tuple(offsets.shape)))
-        n = int(offsets.shape[0])
-        if game.numel() * game.element_size() != n * self.game_bytes():
-            raise ValueError('the game state must hold %d players x %d bytes' % (n, self.game_bytes()))
-        return n, int(offsets.shape[1])
-
     def reset_game(self, game, offsets, mask=None, stream=None):
         """rdoom_world_game_reset: a fresh level (all triggers live, no effect, zero offsets) for every player, or for those whose
         mask entry is true (mask: n bools / bytes, numpy or a GPU tensor)"""
-        n, n_obj = self._game_args(game, offsets)
-        pm, km = None, None
-        if mask is not None:
-            if isinstance(mask, np.ndarray):
-                mask = np.ascontiguousarray(mask).astype(np.uint8)
-            pm, km, _ = _device_tensor(mask, 'mask')
-        _check(lib().rdoom_world_game_reset(self._h, ctypes.c_void_p(game.data_ptr()), ctypes.c_void_p(offsets.data_ptr()), n_obj, n,
-                                            ctypes.c_void_p(pm), ctypes.c_void_p(_stream_handle(stream))))
-        if km is not None:
-            import torch
-            torch.cuda.synchronize(km.device)
+        n, n_obj = _game_args(self.game_bytes(), game, offsets)
+        _reset_masked(mask, lambda pm: lib().rdoom_world_game_reset(self._h, ctypes.c_void_p(game.data_ptr()),
+                                                                    ctypes.c_void_p(offsets.data_ptr()), n_obj, n, pm,
+                                                                    ctypes.c_void_p(_stream_handle(stream))))
 
     def step_game(self, states, inputs, game, offsets, actions=None, n_ticks=None, config=None, dt=1.0 / 60.0, stream=None):
         """rdoom_world_step_game: n_ticks game ticks (physics, effects, triggers) for every player.  states / inputs / config / dt as
         for step (numpy states: a stepped copy is returned; a GPU tensor is stepped in place, asynchronously).  game, offsets: from
         game_state, on the GPU, read and written in place.  actions: None or (n_ticks, n) ACTION_* bytes (numpy or a GPU tensor)."""
         a = _GameStepArgs(states, inputs, actions, n_ticks, config)
-        n_game, n_obj = self._game_args(game, offsets)
-        if n_game != a.n:
-            raise ValueError('%d players, but game state and offsets for %d' % (a.n, n_game))
+        _, n_obj = _game_args(self.game_bytes(), game, offsets, players=a.n)
         _check(lib().rdoom_world_step_game(self._h, ctypes.c_void_p(a.ps), ctypes.c_void_p(a.pi), ctypes.c_void_p(a.pa),
                                            ctypes.c_void_p(game.data_ptr()), ctypes.c_void_p(offsets.data_ptr()), n_obj, a.n,
                                            int(a.n_ticks), a.cfg_ptr(), ctypes.c_float(dt), ctypes.c_void_p(_stream_handle(stream))))
@@ -1103,20 +1098,11 @@ class WorldSet:
 
     def arrays(self, slot):
         """copies of slot `slot`'s collision arrays, in its own indices: World.arrays of the same level"""
-        a = self._info(slot).world
-        v = BuiltLevel._view
-        return dict(nodes=v(None, a.nodes, a.n_nodes, WORLD_NODE), chunks=v(None, a.chunks, a.n_chunks * 2, np.uint32).reshape(-1, 2),
-                    triangles=v(None, a.triangles, a.n_triangles * 4, np.uint32).reshape(-1, 4),
-                    verts=v(None, a.verts, a.n_verts * 3, np.float32).reshape(-1, 3),
-                    dynamics=v(None, a.dynamics, a.n_dynamics * 3, np.uint32).reshape(-1, 3),
-                    n_static_triangles=a.n_static_triangles, n_objects=a.n_objects, node_depth=a.node_depth)
+        return _world_arrays(self._info(slot).world)
 
     def triggers(self, slot):
         """copies of slot `slot`'s trigger list and move effects: World.triggers of the same level"""
-        a = self._info(slot).triggers
-        v = BuiltLevel._view
-        return dict(triggers=v(None, a.triggers, a.n_triggers, TRIGGER), effects=v(None, a.effects, a.n_effects, MOVE_EFFECT),
-                    n_objects=a.n_objects)
+        return _trigger_arrays(self._info(slot).triggers)
 
     def start_states(self, levels, flags=PLAYER_CLIP):
         """PLAYER_STATE records at the start of each player's level, as Player::reset leaves them (pitch 1e-8, at rest)"""
@@ -1145,44 +1131,21 @@ class WorldSet:
         self.reset_game(game, offsets, levels, stream=stream)
         return game, offsets, levels
 
-    def _game_args(self, game, offsets, levels):
-        import torch
-        for t, what in ((game, 'game'), (offsets, 'offsets'), (levels, 'levels')):
-            if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or not t.is_contiguous():
-                raise ValueError('%s must be a contiguous tensor on the GPU' % what)
-        if offsets.dtype != torch.float32 or offsets.dim() != 3 or offsets.shape[2] != 3:
-            raise ValueError('offsets must be a float32 (n, n_objects, 3) tensor, got %s %s' % (offsets.dtype, tuple(offsets.shape)))
-        n = int(offsets.shape[0])
-        if game.numel() * game.element_size() != n * self.game_bytes():
-            raise ValueError('the game state must hold %d players x %d bytes' % (n, self.game_bytes()))
-        if levels.element_size() != 4 or levels.numel() != n:
-            raise ValueError('levels must hold one 32-bit slot per player (%d), got %s %s' % (n, levels.dtype, tuple(levels.shape)))
-        return n, int(offsets.shape[1])
-
     def reset_game(self, game, offsets, levels, mask=None, stream=None):
         """rdoom_worldset_game_reset: a fresh game of its current level for every player (levels: a GPU tensor of slots), or for
         those whose mask entry is true (mask: n bools / bytes, numpy or a GPU tensor)"""
-        n, n_obj = self._game_args(game, offsets, levels)
-        pm, km = None, None
-        if mask is not None:
-            if isinstance(mask, np.ndarray):
-                mask = np.ascontiguousarray(mask).astype(np.uint8)
-            pm, km, _ = _device_tensor(mask, 'mask')
-        _check(lib().rdoom_worldset_game_reset(self._h, ctypes.c_void_p(game.data_ptr()), ctypes.c_void_p(offsets.data_ptr()), n_obj,
-                                               ctypes.c_void_p(levels.data_ptr()), n, ctypes.c_void_p(pm),
-                                               ctypes.c_void_p(_stream_handle(stream))))
-        if km is not None:
-            import torch
-            torch.cuda.synchronize(km.device)
+        n, n_obj = _game_args(self.game_bytes(), game, offsets, levels)
+        _reset_masked(mask, lambda pm: lib().rdoom_worldset_game_reset(self._h, ctypes.c_void_p(game.data_ptr()),
+                                                                       ctypes.c_void_p(offsets.data_ptr()), n_obj,
+                                                                       ctypes.c_void_p(levels.data_ptr()), n, pm,
+                                                                       ctypes.c_void_p(_stream_handle(stream))))
 
     def step_game(self, states, inputs, game, offsets, levels, actions=None, n_ticks=None, config=None, dt=1.0 / 60.0, stream=None):
         """rdoom_worldset_step_game: n_ticks game ticks for every player on its level, with the level change on an exit.  states /
         inputs / actions / config / dt as for World.step_game (numpy states: a stepped copy is returned; a GPU tensor is stepped in
         place, asynchronously).  game, offsets, levels: from game_state, on the GPU, read and written in place."""
         a = _GameStepArgs(states, inputs, actions, n_ticks, config)
-        n_game, n_obj = self._game_args(game, offsets, levels)
-        if n_game != a.n:
-            raise ValueError('%d players, but game state and offsets for %d' % (a.n, n_game))
+        _, n_obj = _game_args(self.game_bytes(), game, offsets, levels, players=a.n)
         _check(lib().rdoom_worldset_step_game(self._h, ctypes.c_void_p(a.ps), ctypes.c_void_p(a.pi), ctypes.c_void_p(a.pa),
                                               ctypes.c_void_p(game.data_ptr()), ctypes.c_void_p(offsets.data_ptr()), n_obj,
                                               ctypes.c_void_p(levels.data_ptr()), a.n, int(a.n_ticks), a.cfg_ptr(), ctypes.c_float(dt),

@@ -252,126 +252,24 @@ __global__ __launch_bounds__(WAVE) void sweep_kernel(WorldView w, const float *s
 
 __device__ __forceinline__ float clampf(float v, float lo, float hi) { return v < lo ? lo : (v > hi ? hi : v); }  // player.rs:415-423
 
-// (step_players below is a twin of this body for game_step_kernel: a change to the physics here belongs there too)
-__global__ __launch_bounds__(WAVE) void player_step_kernel(WorldView w, rdoom_player_state *states, const rdoom_player_input *inputs,
-                                                           uint32_t n, uint32_t n_ticks, rdoom_player_config cfg, float dt,
-                                                           const float *offsets, uint32_t n_objects) {
-  extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
-  const uint32_t p = blockIdx.x * WAVE + threadIdx.x;
-  if (p >= n) return;
-  uint32_t *stack = lds_stack + threadIdx.x;
-  const float *off = offsets ? offsets + (size_t)p * n_objects * 3 : nullptr;
-  rdoom_player_state *st = states + p;
-  V3 pos = load3(st->pos), vel = load3(st->vel);
-  float yaw = st->yaw, pitch = st->pitch, last_height_diff = st->last_height_diff;
-  uint32_t flags = st->flags;
-  const bool fly = flags & RDOOM_PLAYER_FLY, clip = flags & RDOOM_PLAYER_CLIP;
-  const float pitch_limit = 1.57079637f - 1e-2f;  // FRAC_PI_2 - 1e-2 in binary32 (player.rs:196-201)
-  for (uint32_t t = 0; t < n_ticks; t++) {
-    const rdoom_player_input in = inputs[(size_t)t * n + p];
-    // ---- force() (player.rs:243-315): the feet probe
-    float height = cfg.height;
-    bool grounded = false;
-    V3 ground_normal = v3(0.0f, 0.0f, 0.0f);
-    {
-      const Contact c = sweep_world(w, pos, 0.2f, v3(0.0f, -cfg.height, 0.0f), off, stack);
-      if (c.time < __builtin_inff() && c.time < 1.0f) height = cfg.height * c.time, ground_normal = c.normal, grounded = true;
-    }
-    // move_force (player.rs:182-241), orientation as (yaw, pitch)
-    yaw = yaw - in.look[0];
-    pitch = clampf(pitch - in.look[1], -pitch_limit, pitch_limit);
-    float sy, cy, sp, cp;
-    sincos_rd(yaw, sy, cy);
-    sincos_rd(pitch, sp, cp);
-    V3 force;
-    if (fly) {  // rot * (normalize_or_zero(move.x, up, move.y) * move_force), rot = Ry(yaw) Rx(pitch)
-      const V3 m = normalize_or_zero(v3(in.movement[0], in.jump ? 0.5f : 0.0f, in.movement[1])) * cfg.move_force;
-      const float y1 = m.y * cp - m.z * sp, z1 = m.y * sp + m.z * cp;
-      force = v3(m.x * cy + z1 * sy, y1, z1 * cy - m.x * sy);
-    } else {  // normalize(Ry(yaw) (move.x, 0, move.y cos pitch)): the y the pitch adds is dropped before normalising
-      const float a = in.movement[1] * cp;
-      V3 m = normalize_or_zero(v3(in.movement[0] * cy + a * sy, 0.0f, a * cy - in.movement[0] * sy)) * cfg.move_force;
-      if (grounded) {
-        if (in.jump && vel.y < 0.1f) m = v3(m.x, 5.0f / dt, m.z);
-      } else {
-        m = m * 0.1f;
-      }
-      force = m;
-    }
-    const float speed = magnitude(vel);
-    if (speed > 0.0f) {
-      V3 slowdown = v3(0.0f, 0.0f, 0.0f);
-      if (fly) {
-        slowdown = (-vel) * (cfg.friction / speed + cfg.ground_drag * speed);
-      } else if (grounded) {
-        const V3 tangential = vel - ground_normal * dot(vel, ground_normal);
-        const float ts = magnitude(tangential);
-        if (ts > 0.0f) slowdown = (-tangential) * (cfg.friction / ts + cfg.ground_drag * ts);
-      }
-      slowdown = slowdown - vel * cfg.air_drag * speed;
-      const float slowdown_norm = magnitude(slowdown);
-      if (slowdown_norm > 0.0f) {
-        const float max_slowdown = -dot(vel, slowdown) / slowdown_norm / dt;
-        if (slowdown_norm >= max_slowdown) slowdown = slowdown / slowdown_norm * max_slowdown;
-        force = force + slowdown;
-      }
-    }
-    const float height_diff = cfg.height - height;
-    const float derivative = (height_diff - last_height_diff) / dt;
-    last_height_diff = height_diff;
-    force.y = force.y + (height_diff * cfg.spring_const_p + derivative * cfg.spring_const_d);
-    if (!fly) force.y = force.y - 17.0f;
-    // ---- clip() (player.rs:142-166) or noclip() (player.rs:168-190)
-    if (clip) {
-      float time_left = dt;
-      bool armed = true;
-      for (int i = 0; i < 100; i++) {
-        const V3 displacement = vel * time_left;
-        const Contact c = sweep_world(w, pos, cfg.radius, displacement, off, stack);
-        if (c.time < __builtin_inff()) {
-          const float adjusted_time = c.time - 0.001f / magnitude(displacement);
-          if (adjusted_time < 1.0f) {
-            const float time = clampf(c.time, 0.0f, 1.0f);
-            pos = pos + displacement * adjusted_time;
-            vel = vel - c.normal * dot(c.normal, vel);
-            time_left = time_left * (1.0f - time);
-            continue;
-          }
-        }
-        pos = pos + displacement;
-        armed = false;
-        break;
-      }
-      if (armed) flags |= RDOOM_PLAYER_DIVERGED;
-    } else {
-      const float old_height = pos.y;
-      pos = pos + vel * dt;
-      if (!fly) {
-        const float probe_height = 2000.0f;
-        const V3 probe = pos + v3(0.0f, probe_height / 2.0f, 0.0f);
-        const Contact c = sweep_world(w, probe, cfg.radius, v3(0.0f, -probe_height, 0.0f), off, stack);
-        const float h = c.time < __builtin_inff() ? pos.y + probe_height * (0.5f - c.time) : old_height;
-        if (pos.y <= h) {
-          pos.y = h;
-          if (vel.y < 0.0f) vel.y = 0.0f;
-        }
-      }
-    }
-    vel = vel + force * dt;
-  }
-  st->pos[0] = pos.x, st->pos[1] = pos.y, st->pos[2] = pos.z;
-  st->vel[0] = vel.x, st->vel[1] = vel.y, st->vel[2] = vel.z;
-  st->yaw = yaw, st->pitch = pitch, st->last_height_diff = last_height_diff;
-  st->flags = flags;
-}
+// step_players' level policy for player_step_kernel: every player, one world from node 0, nothing besides the physics.  Its
+// level hooks are GameLevel's too.
+struct NoGame {
+  __device__ __forceinline__ bool begin(uint32_t) { return true; }
+  __device__ __forceinline__ bool start_tick() { return false; }
+  __device__ __forceinline__ V3 start_pos() const { return v3(0.0f, 0.0f, 0.0f); }
+  __device__ __forceinline__ float start_yaw() const { return 0.0f; }
+  __device__ __forceinline__ const WorldView &world(const WorldView &w) const { return w; }
+  __device__ __forceinline__ uint32_t root() const { return 0u; }
+  __device__ __forceinline__ void tick(uint32_t, V3, V3, float, float, uint32_t &) {}
+};
 
 // K ticks of Player::update (player.rs:359-396: force() with the feet probe and move_force, clip() or noclip(), then velocity
-// += force * dt) for player p: the body of game_step_kernel and worldset_game_step_kernel.  `level.begin(p)` false: player p is
-// left untouched.  When `level.start_tick()` is true, the player starts the tick afresh at `level.start_pos()` (SetGame below: a
-// level change); the tick's sweeps see `level.world(w)` from node `level.root()`.  After each tick
-// `level.tick(t, pos, vel, yaw, pitch, flags)` runs what the level does in the same tick (GameLevel below: effects and triggers).
-// The body is player_step_kernel's, which keeps its own copy: calling this template from it changes its register allocation, and
-// its code is meant to stay as it is.
+// += force * dt) for player p: the body of player_step_kernel, game_step_kernel and worldset_game_step_kernel, which differ only
+// in their `Level` policy (NoGame, GameLevel, SetGame).  `level.begin(p)` false: player p is left untouched.  When
+// `level.start_tick()` is true, the player starts the tick afresh at `level.start_pos()` (SetGame: a level change); the tick's
+// sweeps see `level.world(w)` from node `level.root()`.  After each tick `level.tick(t, pos, vel, yaw, pitch, flags)` runs what the
+// level does in the same tick (GameLevel: effects and triggers).
 template <class Level>
 __device__ __forceinline__ void step_players(const WorldView &w, rdoom_player_state *states, const rdoom_player_input *inputs, uint32_t n,
                                              uint32_t n_ticks, const rdoom_player_config &cfg, float dt, const float *offsets,
@@ -493,6 +391,12 @@ __device__ __forceinline__ void step_players(const WorldView &w, rdoom_player_st
   st->flags = flags;
 }
 
+__global__ __launch_bounds__(WAVE) void player_step_kernel(WorldView w, rdoom_player_state *states, const rdoom_player_input *inputs,
+                                                           uint32_t n, uint32_t n_ticks, rdoom_player_config cfg, float dt,
+                                                           const float *offsets, uint32_t n_objects) {
+  NoGame level;
+  step_players(w, states, inputs, n, n_ticks, cfg, dt, offsets, n_objects, level);
+}
 
 // ---- doors, lifts and exits: Level::poll_triggers (game/src/level.rs:77-167) and the move effects of Level::update (:184-267)
 struct DevTrigger {  // rdoom_trigger's line, type, flags and effect range
@@ -532,8 +436,8 @@ __device__ __forceinline__ bool segment_hits(const Line2 &a, float box, float bo
 
 // One game's level: the per-player part of Level (effects, trigger list) in d_game, the offsets in the caller's array.  Trigger
 // lines and effect definitions are the same for every lane and read in linedef order (scalar loads); the list order is
-// resolved only on the rare tick when a lane fires two triggers or removes one.
-struct GameLevel {
+// resolved only on the rare tick when a lane fires two triggers or removes one.  One level for every tick: NoGame's hooks.
+struct GameLevel : NoGame {
   GameView g;
   uint32_t *games;
   float *offsets;
@@ -549,12 +453,6 @@ struct GameLevel {
     return true;
   }
   uint32_t lane;
-  // one level for every tick (step_players' hooks)
-  __device__ __forceinline__ bool start_tick() { return false; }
-  __device__ __forceinline__ V3 start_pos() const { return v3(0.0f, 0.0f, 0.0f); }
-  __device__ __forceinline__ float start_yaw() const { return 0.0f; }
-  __device__ __forceinline__ const WorldView &world(const WorldView &w) const { return w; }
-  __device__ __forceinline__ uint32_t root() const { return 0u; }
 
   // the loop of level.rs:203-255 for every active effect, ascending object id
   __device__ __forceinline__ void advance() {
@@ -698,25 +596,29 @@ __global__ __launch_bounds__(WAVE) void game_step_kernel(WorldView w, GameLevel 
   step_players(w, states, inputs, level.n, n_ticks, cfg, level.dt, level.offsets, level.n_objects, level);
 }
 
+// word k of a fresh game of a level with layout l (a GameView or a DevSetLevel): all triggers live, in linedef order, no effect;
+// the words past the level's own are zero
+template <class Layout>
+__device__ __forceinline__ uint32_t fresh_word(const Layout &l, uint32_t k) {
+  if (k == 0) return l.n_triggers;
+  if (k >= l.live && k < l.fired) {
+    const uint32_t first = (k - l.live) * 32;
+    return l.n_triggers - first >= 32 ? ~0u : (1u << (l.n_triggers - first)) - 1u;
+  }
+  if (k >= l.order && k < l.order + l.n_triggers) return k - l.order;
+  return 0u;
+}
+
 // a fresh level for player blockIdx.x (if masked in): one workgroup per game, its lanes striding over the words
 __global__ __launch_bounds__(WAVE) void game_reset_kernel(GameView g, uint32_t *games, float *offsets, uint32_t n_objects,
                                                           const uint8_t *mask) {
   const uint32_t p = blockIdx.x;
   if (mask && !mask[p]) return;
   uint32_t *game = games + (size_t)p * g.words;
-  for (uint32_t k = threadIdx.x; k < g.words; k += WAVE) {
-    uint32_t v = 0u;
-    if (k == 0) v = g.n_triggers;
-    else if (k >= g.live && k < g.fired) {
-      const uint32_t first = (k - g.live) * 32;
-      v = g.n_triggers - first >= 32 ? ~0u : (1u << (g.n_triggers - first)) - 1u;
-    } else if (k >= g.order && k < g.order + g.n_triggers) v = k - g.order;
-    game[k] = v;
-  }
+  for (uint32_t k = threadIdx.x; k < g.words; k += WAVE) game[k] = fresh_word(g, k);
   float *off = offsets + (size_t)p * n_objects * 3;
   for (uint32_t k = threadIdx.x; k < n_objects * 3; k += WAVE) off[k] = 0.0f;
 }
-
 
 // ---- a world set: several levels, each player in one of them, and the exit that takes a player to the next
 struct DevSetLevel {  // one slot of a world set: where its arrays start in the concatenation, its game layout, its start
@@ -729,17 +631,6 @@ struct DevSetLevel {  // one slot of a world set: where its arrays start in the 
 __device__ __forceinline__ GameView level_view(const GameView &set, const DevSetLevel &l) {  // the level's layout within a game
   return GameView{set.triggers + l.trig_start, set.effects, l.n_triggers, l.n_objects, l.live, l.fired, l.active, l.second, l.order,
                   l.effect, l.words};
-}
-
-// word k of a fresh game of level l (game_reset_kernel's values); the words past the level's own are zero
-__device__ __forceinline__ uint32_t fresh_word(const DevSetLevel &l, uint32_t k) {
-  if (k == 0) return l.n_triggers;
-  if (k >= l.live && k < l.fired) {
-    const uint32_t first = (k - l.live) * 32;
-    return l.n_triggers - first >= 32 ? ~0u : (1u << (l.n_triggers - first)) - 1u;
-  }
-  if (k >= l.order && k < l.order + l.n_triggers) return k - l.order;
-  return 0u;
 }
 
 // Word 1 of a set's game: where the player is in the level change.  An exit fired in the poll of tick t (STAGE_EXITED); tick t + 1
@@ -840,19 +731,6 @@ __global__ __launch_bounds__(WAVE) void worldset_game_reset_kernel(const DevSetL
 
 }  // namespace
 
-struct rdoom_world {
-  rdoom::game::World host;
-  bool on_device = false;
-  int device = -1;
-  DevNode *d_nodes = nullptr;
-  uint2 *d_chunks = nullptr;
-  uint4 *d_tris = nullptr;
-  float *d_verts = nullptr;
-  DevDynamic *d_dynamics = nullptr;
-  DevTrigger *d_triggers = nullptr;
-  DevEffect *d_effects = nullptr;
-};
-
 static_assert(sizeof(rdoom_world_node) == sizeof(rdoom::game::WorldNode) && sizeof(rdoom_world_chunk) == sizeof(rdoom::game::WorldChunk) &&
                   sizeof(rdoom_world_triangle) == sizeof(rdoom::game::WorldTriangle) &&
                   sizeof(rdoom_world_dynamic) == sizeof(rdoom::game::WorldDynamic),
@@ -909,17 +787,78 @@ void free_world(DevArrays &d) {
   for (void *p : {(void *)d.nodes, (void *)d.chunks, (void *)d.tris, (void *)d.verts, (void *)d.dynamics, (void *)d.triggers, (void *)d.effects})
     if (p) (void)hipFree(p);
 }
+}  // namespace
 
-WorldView view(const rdoom_world *w) {
-  return WorldView{w->d_nodes, w->d_chunks, w->d_tris, w->d_verts, w->d_dynamics, (uint32_t)w->host.dynamics.size(),
-                   w->host.node_depth + 1};
+struct rdoom_world {
+  rdoom::game::World host;
+  bool on_device = false;
+  int device = -1;
+  DevArrays d;
+};
+
+struct rdoom_worldset {
+  rdoom::game::WorldSet host;
+  std::vector<DevSetLevel> table;  // the device table's records
+  uint32_t words = 0;              // a game's words: the largest level's
+  bool on_device = false;
+  int device = -1;
+  DevArrays d;
+  DevSetLevel *d_table = nullptr;
+};
+
+namespace {
+// the host build of rdoom_world_create / rdoom_worldset_create: what it throws becomes a status (nothing unwinds across the C ABI)
+template <class Build>
+rdoom_status build_host(Build &&build) {
+  try {
+    build();
+  } catch (const rdoom::wad::WadError &e) {
+    return rdoom::fail(e.code, "%s", e.what());
+  } catch (const std::bad_alloc &) {
+    return rdoom::fail(RDOOM_OOM, "out of host memory");
+  } catch (const std::exception &e) {
+    return rdoom::fail(RDOOM_BAD_LEVEL, "%s", e.what());
+  }
+  return RDOOM_OK;
 }
 
-rdoom_status check_device(const rdoom_world *w) {
-  if (!w->on_device) return rdoom::fail(RDOOM_BAD_ARG, "the world was created with RDOOM_WORLD_HOST_ONLY: it has no device copy");
+void fill_arrays(const rdoom::game::World &h, rdoom_world_arrays &a) {
+  std::memset(&a, 0, sizeof a);
+  a.nodes = reinterpret_cast<const rdoom_world_node *>(h.nodes.data());
+  a.n_nodes = (uint32_t)h.nodes.size();
+  a.chunks = reinterpret_cast<const rdoom_world_chunk *>(h.chunks.data());
+  a.n_chunks = (uint32_t)h.chunks.size();
+  a.triangles = reinterpret_cast<const rdoom_world_triangle *>(h.triangles.data());
+  a.n_triangles = (uint32_t)h.triangles.size();
+  a.n_static_triangles = h.n_static_triangles;
+  a.verts = h.verts.data();
+  a.n_verts = (uint32_t)(h.verts.size() / 3);
+  a.dynamics = reinterpret_cast<const rdoom_world_dynamic *>(h.dynamics.data());
+  a.n_dynamics = (uint32_t)h.dynamics.size();
+  a.n_objects = h.n_objects;
+  a.node_depth = h.node_depth;
+}
+
+void fill_triggers(const rdoom::game::World &h, rdoom_world_trigger_arrays &t) {
+  std::memset(&t, 0, sizeof t);
+  t.triggers = h.triggers.data();
+  t.n_triggers = (uint32_t)h.triggers.size();
+  t.effects = h.effects.data();
+  t.n_effects = (uint32_t)h.effects.size();
+  t.n_objects = h.game_objects;
+}
+
+WorldView view(const DevArrays &d, uint32_t n_dynamics, uint32_t node_depth) {
+  return WorldView{d.nodes, d.chunks, d.tris, d.verts, d.dynamics, n_dynamics, node_depth + 1};
+}
+
+// noun: "the world" or "the world set"
+template <class Handle>
+rdoom_status check_device(const Handle *h, const char *noun) {
+  if (!h->on_device) return rdoom::fail(RDOOM_BAD_ARG, "%s was created with RDOOM_WORLD_HOST_ONLY: it has no device copy", noun);
   int cur = -1;
   HIP_TRY(hipGetDevice(&cur));
-  if (cur != w->device) return rdoom::fail(RDOOM_BAD_ARG, "the world lives on device %d, the current device is %d", w->device, cur);
+  if (cur != h->device) return rdoom::fail(RDOOM_BAD_ARG, "%s lives on device %d, the current device is %d", noun, h->device, cur);
   return RDOOM_OK;
 }
 
@@ -935,15 +874,18 @@ GameView game_layout(const rdoom::game::World &h) {  // the layout include/rdoom
 
 GameView game_view(const rdoom_world *w) {
   GameView g = game_layout(w->host);
-  g.triggers = w->d_triggers, g.effects = w->d_effects;
+  g.triggers = w->d.triggers, g.effects = w->d.effects;
   return g;
 }
 
-rdoom_status check_game(const rdoom_world *w, const void *d_game, const float *d_offsets, uint32_t n_objects) {
-  if (!d_game || !d_offsets) return rdoom::fail(RDOOM_BAD_ARG, "null game state or object offsets");
+// the game arguments of a world's reset and step, or (set: d_levels too) a world set's
+rdoom_status check_game(bool set, uint32_t game_objects, const void *d_game, const float *d_offsets, uint32_t n_objects,
+                        const uint32_t *d_levels) {
+  if (!d_game || !d_offsets || (set && !d_levels))
+    return rdoom::fail(RDOOM_BAD_ARG, "%s", set ? "null game state, object offsets or levels" : "null game state or object offsets");
   if ((uintptr_t)d_game % 16) return rdoom::fail(RDOOM_BAD_ARG, "the game state is not 16-byte aligned");
-  if (n_objects < w->host.game_objects)
-    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the game's %u objects", n_objects, w->host.game_objects);
+  if (n_objects < game_objects)
+    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the %s's %u objects", n_objects, set ? "set" : "game", game_objects);
   return RDOOM_OK;
 }
 
@@ -952,33 +894,30 @@ rdoom_status check_offsets(const rdoom_world *w, const float *offsets, uint32_t 
     return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the world's %u objects", n_objects, w->host.n_objects);
   return RDOOM_OK;
 }
-}  // namespace
 
-struct rdoom_worldset {
-  rdoom::game::WorldSet host;
-  std::vector<DevSetLevel> table;  // the device table's records
-  uint32_t words = 0;              // a game's words: the largest level's
-  bool on_device = false;
-  int device = -1;
-  DevArrays d;
-  DevSetLevel *d_table = nullptr;
-};
-
-namespace {
-rdoom_status check_device(const rdoom_worldset *s) {
-  if (!s->on_device) return rdoom::fail(RDOOM_BAD_ARG, "the world set was created with RDOOM_WORLD_HOST_ONLY: it has no device copy");
-  int cur = -1;
-  HIP_TRY(hipGetDevice(&cur));
-  if (cur != s->device) return rdoom::fail(RDOOM_BAD_ARG, "the world set lives on device %d, the current device is %d", s->device, cur);
+// the arguments every step checks: states and inputs, and dt; resolves dt (0: 1/60) and the config (cfg null: the default) into c
+rdoom_status step_args(const rdoom_player_state *d_states, const rdoom_player_input *d_inputs, uint32_t n_players, uint32_t n_ticks,
+                       const rdoom_player_config *cfg, float &dt, rdoom_player_config &c) {
+  if (n_players && (!d_states || (n_ticks && !d_inputs)))
+    return rdoom::fail(RDOOM_BAD_ARG, "null states or inputs with n_players = %u", n_players);
+  if (!(dt >= 0.0f) || dt == __builtin_inff()) return rdoom::fail(RDOOM_BAD_ARG, "dt %g is not a finite non-negative number", (double)dt);
+  if (cfg) c = *cfg;
+  else rdoom_player_config_default(&c);
+  if (dt == 0.0f) dt = 1.0f / 60.0f;
   return RDOOM_OK;
 }
 
-rdoom_status check_game(const rdoom_worldset *s, const void *d_game, const float *d_offsets, uint32_t n_objects, const uint32_t *d_levels) {
-  if (!d_game || !d_offsets || !d_levels) return rdoom::fail(RDOOM_BAD_ARG, "null game state, object offsets or levels");
-  if ((uintptr_t)d_game % 16) return rdoom::fail(RDOOM_BAD_ARG, "the game state is not 16-byte aligned");
-  if (n_objects < s->host.game_objects)
-    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the set's %u objects", n_objects, s->host.game_objects);
-  return RDOOM_OK;
+// a game step's GameLevel, less the trigger and effect pointers (g's) the kernel takes as arguments of their own
+GameLevel game_level(const GameView &g, void *d_game, float *d_offsets, const uint8_t *d_actions, uint32_t n_players, uint32_t n_objects,
+                     float dt) {
+  GameLevel level{};
+  level.g = g;
+  level.games = (uint32_t *)d_game;
+  level.offsets = d_offsets;
+  level.actions = d_actions;
+  level.n = n_players, level.n_objects = n_objects;
+  level.dt = dt;
+  return level;
 }
 }  // namespace
 
@@ -986,9 +925,7 @@ extern "C" {
 
 void rdoom_world_destroy(rdoom_world *w) {
   if (!w) return;
-  for (void *p : {(void *)w->d_nodes, (void *)w->d_chunks, (void *)w->d_tris, (void *)w->d_verts, (void *)w->d_dynamics,
-                  (void *)w->d_triggers, (void *)w->d_effects})
-    if (p) (void)hipFree(p);
+  free_world(w->d);
   delete w;
 }
 
@@ -997,26 +934,17 @@ rdoom_status rdoom_world_create(const rdoom_wad *wad, uint32_t level_index, uint
   if (flags & ~RDOOM_WORLD_HOST_ONLY) return rdoom::fail(RDOOM_BAD_ARG, "unknown flags 0x%x", flags);
   *out_world = nullptr;
   std::unique_ptr<rdoom_world, void (*)(rdoom_world *)> w(nullptr, rdoom_world_destroy);
-  try {  // nothing unwinds across the C ABI
-    w.reset(new rdoom_world);
-    w->host = rdoom::game::build_world(*rdoom::game::loaded_wad(wad), level_index);
-  } catch (const rdoom::wad::WadError &e) {
-    return rdoom::fail(e.code, "%s", e.what());
-  } catch (const std::bad_alloc &) {
-    return rdoom::fail(RDOOM_OOM, "out of host memory");
-  } catch (const std::exception &e) {
-    return rdoom::fail(RDOOM_BAD_LEVEL, "%s", e.what());
-  }
+  if (rdoom_status st = build_host([&] {
+        w.reset(new rdoom_world);
+        w->host = rdoom::game::build_world(*rdoom::game::loaded_wad(wad), level_index);
+      }))
+    return st;
   const rdoom::game::World &h = w->host;
   if (h.node_depth > RDOOM_WORLD_MAX_DEPTH)
     return rdoom::fail(RDOOM_BAD_LEVEL, "the level's BSP is %u nodes deep (at most %u)", h.node_depth, RDOOM_WORLD_MAX_DEPTH);
   if (!(flags & RDOOM_WORLD_HOST_ONLY)) {
     HIP_TRY(hipGetDevice(&w->device));
-    DevArrays d;
-    const rdoom_status st = upload_world(h, d);
-    w->d_nodes = d.nodes, w->d_chunks = d.chunks, w->d_tris = d.tris, w->d_verts = d.verts, w->d_dynamics = d.dynamics;
-    w->d_triggers = d.triggers, w->d_effects = d.effects;
-    if (st) return st;
+    if (rdoom_status st = upload_world(h, w->d)) return st;
     w->on_device = true;
   }
   *out_world = w.release();
@@ -1025,21 +953,7 @@ rdoom_status rdoom_world_create(const rdoom_wad *wad, uint32_t level_index, uint
 
 rdoom_status rdoom_world_host_arrays(const rdoom_world *w, rdoom_world_arrays *out) {
   if (!w || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
-  const rdoom::game::World &h = w->host;
-  std::memset(out, 0, sizeof *out);
-  out->nodes = reinterpret_cast<const rdoom_world_node *>(h.nodes.data());
-  out->n_nodes = (uint32_t)h.nodes.size();
-  out->chunks = reinterpret_cast<const rdoom_world_chunk *>(h.chunks.data());
-  out->n_chunks = (uint32_t)h.chunks.size();
-  out->triangles = reinterpret_cast<const rdoom_world_triangle *>(h.triangles.data());
-  out->n_triangles = (uint32_t)h.triangles.size();
-  out->n_static_triangles = h.n_static_triangles;
-  out->verts = h.verts.data();
-  out->n_verts = (uint32_t)(h.verts.size() / 3);
-  out->dynamics = reinterpret_cast<const rdoom_world_dynamic *>(h.dynamics.data());
-  out->n_dynamics = (uint32_t)h.dynamics.size();
-  out->n_objects = h.n_objects;
-  out->node_depth = h.node_depth;
+  fill_arrays(w->host, *out);
   return RDOOM_OK;
 }
 
@@ -1048,9 +962,9 @@ rdoom_status rdoom_world_sweep(const rdoom_world *w, const float *d_spheres, con
   if (!w) return rdoom::fail(RDOOM_BAD_ARG, "null world");
   if (n && (!d_spheres || !d_vels || !d_out)) return rdoom::fail(RDOOM_BAD_ARG, "null array with n = %u", n);
   if (rdoom_status s = check_offsets(w, d_object_offsets, n_objects)) return s;
-  if (rdoom_status s = check_device(w)) return s;
+  if (rdoom_status s = check_device(w, "the world")) return s;
   if (!n) return RDOOM_OK;
-  const WorldView v = view(w);
+  const WorldView v = view(w->d, (uint32_t)w->host.dynamics.size(), w->host.node_depth);
   hipLaunchKernelGGL(sweep_kernel, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t), (hipStream_t)stream, v,
                      d_spheres, d_vels, n, d_object_offsets, n_objects, d_out);
   HIP_TRY(hipGetLastError());
@@ -1067,31 +981,21 @@ rdoom_status rdoom_world_step_players(const rdoom_world *w, rdoom_player_state *
                                       uint32_t n_players, uint32_t n_ticks, const rdoom_player_config *cfg, float dt,
                                       const float *d_object_offsets, uint32_t n_objects, void *stream) {
   if (!w) return rdoom::fail(RDOOM_BAD_ARG, "null world");
-  if (n_players && (!d_states || (n_ticks && !d_inputs)))
-    return rdoom::fail(RDOOM_BAD_ARG, "null states or inputs with n_players = %u", n_players);
-  if (!(dt >= 0.0f) || dt == __builtin_inff()) return rdoom::fail(RDOOM_BAD_ARG, "dt %g is not a finite non-negative number", (double)dt);
-  if (rdoom_status s = check_offsets(w, d_object_offsets, n_objects)) return s;
-  if (rdoom_status s = check_device(w)) return s;
-  if (!n_players || !n_ticks) return RDOOM_OK;
   rdoom_player_config c;
-  if (cfg) c = *cfg;
-  else rdoom_player_config_default(&c);
-  const WorldView v = view(w);
+  if (rdoom_status s = step_args(d_states, d_inputs, n_players, n_ticks, cfg, dt, c)) return s;
+  if (rdoom_status s = check_offsets(w, d_object_offsets, n_objects)) return s;
+  if (rdoom_status s = check_device(w, "the world")) return s;
+  if (!n_players || !n_ticks) return RDOOM_OK;
+  const WorldView v = view(w->d, (uint32_t)w->host.dynamics.size(), w->host.node_depth);
   hipLaunchKernelGGL(player_step_kernel, dim3((n_players + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
-                     (hipStream_t)stream, v, d_states, d_inputs, n_players, n_ticks, c, dt == 0.0f ? 1.0f / 60.0f : dt, d_object_offsets,
-                     n_objects);
+                     (hipStream_t)stream, v, d_states, d_inputs, n_players, n_ticks, c, dt, d_object_offsets, n_objects);
   HIP_TRY(hipGetLastError());
   return RDOOM_OK;
 }
 
 rdoom_status rdoom_world_triggers(const rdoom_world *w, rdoom_world_trigger_arrays *out) {
   if (!w || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
-  std::memset(out, 0, sizeof *out);
-  out->triggers = w->host.triggers.data();
-  out->n_triggers = (uint32_t)w->host.triggers.size();
-  out->effects = w->host.effects.data();
-  out->n_effects = (uint32_t)w->host.effects.size();
-  out->n_objects = w->host.game_objects;
+  fill_triggers(w->host, *out);
   return RDOOM_OK;
 }
 
@@ -1104,8 +1008,8 @@ rdoom_status rdoom_world_game_bytes(const rdoom_world *w, uint64_t *bytes_per_pl
 rdoom_status rdoom_world_game_reset(const rdoom_world *w, void *d_game, float *d_object_offsets, uint32_t n_objects, uint32_t n,
                                     const uint8_t *d_mask, void *stream) {
   if (!w) return rdoom::fail(RDOOM_BAD_ARG, "null world");
-  if (rdoom_status s = check_game(w, d_game, d_object_offsets, n_objects)) return s;
-  if (rdoom_status s = check_device(w)) return s;
+  if (rdoom_status s = check_game(false, w->host.game_objects, d_game, d_object_offsets, n_objects, nullptr)) return s;
+  if (rdoom_status s = check_device(w, "the world")) return s;
   if (!n) return RDOOM_OK;
   hipLaunchKernelGGL(game_reset_kernel, dim3(n), dim3(WAVE), 0, (hipStream_t)stream, game_view(w), (uint32_t *)d_game, d_object_offsets,
                      n_objects, d_mask);
@@ -1117,23 +1021,13 @@ rdoom_status rdoom_world_step_game(const rdoom_world *w, rdoom_player_state *d_s
                                    const uint8_t *d_actions, void *d_game, float *d_object_offsets, uint32_t n_objects,
                                    uint32_t n_players, uint32_t n_ticks, const rdoom_player_config *cfg, float dt, void *stream) {
   if (!w) return rdoom::fail(RDOOM_BAD_ARG, "null world");
-  if (n_players && (!d_states || (n_ticks && !d_inputs)))
-    return rdoom::fail(RDOOM_BAD_ARG, "null states or inputs with n_players = %u", n_players);
-  if (!(dt >= 0.0f) || dt == __builtin_inff()) return rdoom::fail(RDOOM_BAD_ARG, "dt %g is not a finite non-negative number", (double)dt);
-  if (rdoom_status s = check_game(w, d_game, d_object_offsets, n_objects)) return s;
-  if (rdoom_status s = check_device(w)) return s;
-  if (!n_players || !n_ticks) return RDOOM_OK;
   rdoom_player_config c;
-  if (cfg) c = *cfg;
-  else rdoom_player_config_default(&c);
-  const WorldView v = view(w);
-  GameLevel level{};
-  level.g = game_view(w);
-  level.games = (uint32_t *)d_game;
-  level.offsets = d_object_offsets;
-  level.actions = d_actions;
-  level.n = n_players, level.n_objects = n_objects;
-  level.dt = dt == 0.0f ? 1.0f / 60.0f : dt;
+  if (rdoom_status s = step_args(d_states, d_inputs, n_players, n_ticks, cfg, dt, c)) return s;
+  if (rdoom_status s = check_game(false, w->host.game_objects, d_game, d_object_offsets, n_objects, nullptr)) return s;
+  if (rdoom_status s = check_device(w, "the world")) return s;
+  if (!n_players || !n_ticks) return RDOOM_OK;
+  const WorldView v = view(w->d, (uint32_t)w->host.dynamics.size(), w->host.node_depth);
+  const GameLevel level = game_level(game_view(w), d_game, d_object_offsets, d_actions, n_players, n_objects, dt);
   hipLaunchKernelGGL(game_step_kernel, dim3((n_players + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
                      (hipStream_t)stream, v, level, level.g.triggers, level.g.effects, d_states, d_inputs, n_ticks, c);
   HIP_TRY(hipGetLastError());
@@ -1153,16 +1047,11 @@ rdoom_status rdoom_worldset_create(const rdoom_wad *wad, const uint32_t *level_i
   if (flags & ~RDOOM_WORLD_HOST_ONLY) return rdoom::fail(RDOOM_BAD_ARG, "unknown flags 0x%x", flags);
   *out_set = nullptr;
   std::unique_ptr<rdoom_worldset, void (*)(rdoom_worldset *)> s(nullptr, rdoom_worldset_destroy);
-  try {  // nothing unwinds across the C ABI
-    s.reset(new rdoom_worldset);
-    s->host = rdoom::game::build_world_set(*rdoom::game::loaded_wad(wad), level_indices, n_levels);
-  } catch (const rdoom::wad::WadError &e) {
-    return rdoom::fail(e.code, "%s", e.what());
-  } catch (const std::bad_alloc &) {
-    return rdoom::fail(RDOOM_OOM, "out of host memory");
-  } catch (const std::exception &e) {
-    return rdoom::fail(RDOOM_BAD_LEVEL, "%s", e.what());
-  }
+  if (rdoom_status st = build_host([&] {
+        s.reset(new rdoom_worldset);
+        s->host = rdoom::game::build_world_set(*rdoom::game::loaded_wad(wad), level_indices, n_levels);
+      }))
+    return st;
   const rdoom::game::WorldSet &h = s->host;
   if (h.node_depth > RDOOM_WORLD_MAX_DEPTH)
     return rdoom::fail(RDOOM_BAD_LEVEL, "a level's BSP is %u nodes deep (at most %u)", h.node_depth, RDOOM_WORLD_MAX_DEPTH);
@@ -1208,26 +1097,8 @@ rdoom_status rdoom_worldset_level(const rdoom_worldset *s, uint32_t slot, rdoom_
   out->n_triggers = (uint32_t)l.triggers.size();
   out->n_objects = l.game_objects;
   out->node_depth = l.node_depth;
-  rdoom_world_arrays &a = out->world;
-  a.nodes = reinterpret_cast<const rdoom_world_node *>(l.nodes.data());
-  a.n_nodes = (uint32_t)l.nodes.size();
-  a.chunks = reinterpret_cast<const rdoom_world_chunk *>(l.chunks.data());
-  a.n_chunks = (uint32_t)l.chunks.size();
-  a.triangles = reinterpret_cast<const rdoom_world_triangle *>(l.triangles.data());
-  a.n_triangles = (uint32_t)l.triangles.size();
-  a.n_static_triangles = l.n_static_triangles;
-  a.verts = l.verts.data();
-  a.n_verts = (uint32_t)(l.verts.size() / 3);
-  a.dynamics = reinterpret_cast<const rdoom_world_dynamic *>(l.dynamics.data());
-  a.n_dynamics = (uint32_t)l.dynamics.size();
-  a.n_objects = l.n_objects;
-  a.node_depth = l.node_depth;
-  rdoom_world_trigger_arrays &t = out->triggers;
-  t.triggers = l.triggers.data();
-  t.n_triggers = (uint32_t)l.triggers.size();
-  t.effects = l.effects.data();
-  t.n_effects = (uint32_t)l.effects.size();
-  t.n_objects = l.game_objects;
+  fill_arrays(l, out->world);
+  fill_triggers(l, out->triggers);
   return RDOOM_OK;
 }
 
@@ -1240,8 +1111,8 @@ rdoom_status rdoom_worldset_game_bytes(const rdoom_worldset *s, uint64_t *bytes_
 rdoom_status rdoom_worldset_game_reset(const rdoom_worldset *s, void *d_game, float *d_object_offsets, uint32_t n_objects,
                                        const uint32_t *d_levels, uint32_t n, const uint8_t *d_mask, void *stream) {
   if (!s) return rdoom::fail(RDOOM_BAD_ARG, "null world set");
-  if (rdoom_status st = check_game(s, d_game, d_object_offsets, n_objects, d_levels)) return st;
-  if (rdoom_status st = check_device(s)) return st;
+  if (rdoom_status st = check_game(true, s->host.game_objects, d_game, d_object_offsets, n_objects, d_levels)) return st;
+  if (rdoom_status st = check_device(s, "the world set")) return st;
   if (!n) return RDOOM_OK;
   hipLaunchKernelGGL(worldset_game_reset_kernel, dim3(n), dim3(WAVE), 0, (hipStream_t)stream, s->d_table, (uint32_t)s->table.size(),
                      s->words, (uint32_t *)d_game, d_object_offsets, n_objects, d_levels, d_mask);
@@ -1254,23 +1125,15 @@ rdoom_status rdoom_worldset_step_game(const rdoom_worldset *s, rdoom_player_stat
                                       uint32_t *d_levels, uint32_t n_players, uint32_t n_ticks, const rdoom_player_config *cfg,
                                       float dt, void *stream) {
   if (!s) return rdoom::fail(RDOOM_BAD_ARG, "null world set");
-  if (n_players && (!d_states || (n_ticks && !d_inputs)))
-    return rdoom::fail(RDOOM_BAD_ARG, "null states or inputs with n_players = %u", n_players);
-  if (!(dt >= 0.0f) || dt == __builtin_inff()) return rdoom::fail(RDOOM_BAD_ARG, "dt %g is not a finite non-negative number", (double)dt);
-  if (rdoom_status st = check_game(s, d_game, d_object_offsets, n_objects, d_levels)) return st;
-  if (rdoom_status st = check_device(s)) return st;
-  if (!n_players || !n_ticks) return RDOOM_OK;
   rdoom_player_config c;
-  if (cfg) c = *cfg;
-  else rdoom_player_config_default(&c);
-  const WorldView v{s->d.nodes, s->d.chunks, s->d.tris, s->d.verts, s->d.dynamics, 0u, s->host.node_depth + 1};
+  if (rdoom_status st = step_args(d_states, d_inputs, n_players, n_ticks, cfg, dt, c)) return st;
+  if (rdoom_status st = check_game(true, s->host.game_objects, d_game, d_object_offsets, n_objects, d_levels)) return st;
+  if (rdoom_status st = check_device(s, "the world set")) return st;
+  if (!n_players || !n_ticks) return RDOOM_OK;
+  const WorldView v = view(s->d, 0u, s->host.node_depth);
   SetGame set{};
-  set.gl.g = GameView{s->d.triggers, s->d.effects, 0, s->host.game_objects, 0, 0, 0, 0, 0, 0, s->words};
-  set.gl.games = (uint32_t *)d_game;
-  set.gl.offsets = d_object_offsets;
-  set.gl.actions = d_actions;
-  set.gl.n = n_players, set.gl.n_objects = n_objects;
-  set.gl.dt = dt == 0.0f ? 1.0f / 60.0f : dt;
+  set.gl = game_level(GameView{s->d.triggers, s->d.effects, 0, s->host.game_objects, 0, 0, 0, 0, 0, 0, s->words}, d_game,
+                      d_object_offsets, d_actions, n_players, n_objects, dt);
   set.level_of = d_levels;
   set.n_levels = (uint32_t)s->table.size();
   hipLaunchKernelGGL(worldset_game_step_kernel, dim3((n_players + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
