@@ -7,8 +7,6 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
-#include <cstdio>
-#include <cstdlib>
 #include <type_traits>
 
 #include "kernels.hpp"
@@ -43,28 +41,12 @@ namespace {
 // to a per-wave LDS list and shaded afterwards by the general per-pixel body, lane per pixel -- same
 // results, one code path for everything unusual.
 // =================================================================================================
-#ifdef RDOOM_FRAG_STATS  // census build (tools/variant.sh fstats fragment -DRDOOM_FRAG_STATS): where do the runs go?
-__device__ unsigned long long g_frag_stats[16];
-#endif
-#ifndef RDOOM_FRAG_MAGIC
-#define RDOOM_FRAG_MAGIC 0  // texel addresses through the round-down magic-number floor (0: four v_cvt_flr_i32_f32 per pixel pair)
-#endif
-#ifndef RDOOM_FRAG_ADDR2
-#define RDOOM_FRAG_ADDR2 1  // texel byte offsets from scaled coordinates (two and-s and an or per texel)
-#endif
-#ifndef RDOOM_FRAG_CHUNK
-#define RDOOM_FRAG_CHUNK 16
-#endif
-constexpr int FRAG_CHUNK = RDOOM_FRAG_CHUNK;
-#ifndef RDOOM_FRAG_WAVES
-#define RDOOM_FRAG_WAVES 4
-#endif
-constexpr uint32_t FRAG_WAVES = RDOOM_FRAG_WAVES;  // waves per workgroup (they share the LDS copy of COLORMAP)
+// Launch shape, measured with the quadrant table in place (profiles/r03_ab.txt, run 9): 2 or 4 waves per workgroup alike, 8 slower;
+// a register budget for 4-6 waves per SIMD alike, 7 slower; 16 or 32 wave blocks per wave alike, 4, 8 and 64 slower.
+constexpr int FRAG_CHUNK = 16;
+constexpr uint32_t FRAG_WAVES = 4;  // waves per workgroup (they share the LDS copy of COLORMAP)
+constexpr int FRAG_OCC = 6;         // waves per SIMD the register allocation must allow: at most 80 VGPRs
 typedef uint32_t TexelWord __attribute__((aligned(2)));
-#ifndef RDOOM_FRAG_OCC
-#define RDOOM_FRAG_OCC 6  // waves per SIMD the register allocation must allow: at most 80 VGPRs
-#endif
-#define FRAG_OCCUPANCY __attribute__((amdgpu_waves_per_eu(RDOOM_FRAG_OCC, 8)))
 constexpr int FRAG_WLIST = 160;  // per-wave list of unfinished quads: at most 15 carried over + 64 x 2 new
 
 __device__ __forceinline__ uint32_t shade_sky(const LevelSlice &lv, const uint16_t *__restrict__ sky_texels, const uint8_t *cmap, float px, float py,
@@ -130,9 +112,9 @@ struct FragConst {
   uint32_t fix_cap, div_m, div_sh, pad;
 };
 
-template <int NQ, int DBG, bool VIS16>  // NQ: adjacent quads per lane (1 or 2; the frame width is a multiple of 4 NQ);
-                                        // DBG: timing experiments only; VIS16: 16-bit visibility words (0xFFFF = none)
-__global__ __launch_bounds__(64 * RDOOM_FRAG_WAVES) FRAG_OCCUPANCY void fragment_kernel(const FragConst *__restrict__ fc,
+template <int NQ, bool VIS16>  // NQ: adjacent quads per lane (1 or 2; the frame width is a multiple of 4 NQ);
+                               // VIS16: 16-bit visibility words (0xFFFF = none)
+__global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu(FRAG_OCC, 8))) void fragment_kernel(const FragConst *__restrict__ fc,
                                                        const uint16_t *__restrict__ texels, const uint8_t *__restrict__ colormap,
                                                        const TriRec *__restrict__ recs,
                                                        uint32_t cap, const PoseConst *__restrict__ poses,
@@ -154,19 +136,13 @@ __global__ __launch_bounds__(64 * RDOOM_FRAG_WAVES) FRAG_OCCUPANCY void fragment
     for (uint32_t k = threadIdx.x; k < 512u; k += 64u * FRAG_WAVES) dst[k] = src[k];
   }
   __syncthreads();
-  // blockIdx -> (pose, chunk): all chunks of a pose on one XCD (b % 8), like the rasteriser
-#ifdef RDOOM_FRAG_CHUNKS_OUTER
-  // (round 5 experiment, NOT the default: the rasteriser gained 11 % from dispatching its heavy tile rows first, raster.hip; the
-  // same order here -- a two-dimensional grid, the frame's chunks the slow dimension, the middle ones first -- measured 5 %
-  // SLOWER at 1080p and 9 % at 4K: a pose's visibility words and records are no longer walked while they are in its XCD's L2)
-  const uint32_t pose = blockIdx.x;
-  const uint32_t yk = blockIdx.y, yc = chunks_per_pose >> 1;
-  const uint32_t chunk = (yk & 1u) ? yc - ((yk + 1u) >> 1) : yc + (yk >> 1);  // c, c - 1, c + 1, c - 2, ...
-#else
+  // blockIdx -> (pose, chunk): all chunks of a pose on one XCD (b % 8), like the rasteriser.  (The rasteriser gained 11 % from
+  // dispatching its heavy tile rows first; the same order here -- a two-dimensional grid, the frame's chunks the slow dimension,
+  // the middle ones first -- measured 5 % SLOWER at 1080p and 9 % at 4K: a pose's visibility words and records are no longer
+  // walked while they are in its XCD's L2.  profiles/r05_ab.txt)
   const uint32_t g = blockIdx.x >> 3;
   const uint32_t pose = (g / chunks_per_pose) * 8u + (blockIdx.x & 7u);
   const uint32_t chunk = g % chunks_per_pose;
-#endif
   if (pose >= n_poses) return;
   const TriRec *prec = recs + (size_t)pose * cap;
   constexpr uint32_t NONE_ID = VIS16 ? 0xFFFFu : NONE;
@@ -259,27 +235,16 @@ __global__ __launch_bounds__(64 * RDOOM_FRAG_WAVES) FRAG_OCCUPANCY void fragment
       // the entry like any other described quadrant -- same record, same operations, same bytes.
       if (qtab_mode == 1u) {
         const uint32_t one = e[(bx0 >> 5) & 1u];
-#ifdef RDOOM_FRAG_STATS
-        if (lane == 0u) atomicAdd(&g_frag_stats[qtab_handled(one) ? 1 : 0], 1ull);
-#endif
         if (qtab_handled(one)) continue;
         tq = one;
       } else {
         const uint2 two = *reinterpret_cast<const uint2 *>(e);
         const bool right_out = bx0 + 32u >= (uint32_t)width;
-#ifdef RDOOM_FRAG_STATS
-        if (lane == 0u) {
-          atomicAdd(&g_frag_stats[(qtab_handled(two.x) & (right_out | qtab_handled(two.y))) ? 1 : 0], 1ull);
-          if (qtab_handled(two.x) != (right_out | qtab_handled(two.y))) atomicAdd(&g_frag_stats[2], 1ull);
-        }
-#endif
         if (qtab_handled(two.x) & (right_out | qtab_handled(two.y))) continue;
         const uint32_t left = qtab_record(two.x), right = qtab_record(two.y);
         const bool same = left == right || right_out;
         tq = same ? left : NONE;
-#ifndef RDOOM_FRAG_NO_TL  // (A/B builds only: without the per-lane entries every visibility word must be there -- keep_vis)
         tl = same ? NONE : (((lane_col * (uint32_t)NPX) & 32u) ? right : left);
-#endif
       }
     }
     tq = (uint32_t)__builtin_amdgcn_readfirstlane((int)tq);
@@ -347,18 +312,10 @@ __global__ __launch_bounds__(64 * RDOOM_FRAG_WAVES) FRAG_OCCUPANCY void fragment
       const uint32_t wm = tex & 0xFFFFu, hm = tex >> 16, lw = (flags >> 8) & 15u, base = (flags >> 16) << 10;
       const uint32_t base2 = base * 2u;  // byte offsets < 2^27: one 32-bit VGPR offset from the uniform base pointer
       const char *tb = reinterpret_cast<const char *>(texels);
-#if RDOOM_FRAG_ADDR2 && !RDOOM_FRAG_MAGIC
       const uint32_t wm2a = wm << 1, hms = hm << (lw + 1u);
       const float ysc = __uint_as_float((128u + lw) << 23);  // 2 W = 2^(lw + 1)
       const float au2 = atlas_u * 2.0f, avs = atlas_v * ysc;
       const char *tba = ONE ? tb + base2 : tb;  // (wave-uniform record: the store's base is scalar pointer arithmetic)
-#endif
-#if RDOOM_FRAG_MAGIC
-      const uint32_t wm2 = wm << 1;
-      // the store's base: with a wave-uniform record the pointer arithmetic is scalar; per-lane records keep a 32-bit offset
-      const char *tb2 = ONE ? tb + base2 : tb;
-      const uint32_t lane_base2 = ONE ? 0u : base2;
-#endif
       // Certificate for integer (non-power-of-two) tile sizes, evaluated only in waves that hold such a record
       // (fastmath.hpp, mod_cert): with guard >= 2^-20 * max(|x|, y), guard <= r <= y - guard and |x| < 2^23 imply that
       // no integer lies between x * RN(1/y) and RN(x / y) and that y * floor is exact.  One guard per run and axis:
@@ -402,47 +359,20 @@ __global__ __launch_bounds__(64 * RDOOM_FRAG_WAVES) FRAG_OCCUPANCY void fragment
         if (any_np2)
           mod_ok = mod_ok & (p2x | ((rx.x >= lox) & (rx.x <= hix) & (rx.y >= lox) & (rx.y <= hix))) &
                    (p2y | ((ry.x >= loy) & (ry.x <= hiy) & (ry.y >= loy) & (ry.y <= hiy)));
-        const f32x2 ux = rx + splat(atlas_u), uy = ry + splat(atlas_v);  // F3
-#if RDOOM_FRAG_MAGIC
-        // floor() of four coordinates with two packed instructions: for 0 <= x < 2^22, x + 2^23 rounded TOWARDS MINUS
-        // INFINITY is 2^23 + floor(x) exactly (the sum lies in [2^23, 2^24), where binary32 has unit spacing), i.e. the
-        // bits 0x4B000000 + floor(x); the REPEAT masks below strip the exponent.  The horizontal coordinate goes through
-        // fma(x, 2, 2^23): floor(2x) = 2 floor(x) + {0, 1}, and the mask (wm << 1) drops the odd bit -- the byte offset of
-        // the 16-bit texel without a shift.  The rounding mode is switched for exactly these two instructions (one asm
-        // statement: nothing can be scheduled in between).  Coordinates are >= 0 in every lane whose result is used
-        // (mod results lie in [0, size], atlas positions are >= 0); other lanes produce masked, in-range garbage as before.
-        f32x2 fxb, fyb;
-        asm volatile(
-            "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 2\n\t"
-            "v_pk_fma_f32 %0, %2, 2.0, %4 op_sel_hi:[1,0,1]\n\t"
-            "v_pk_add_f32 %1, %3, %4\n\t"
-            "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 0, 2), 0"
-            : "=&v"(fxb), "=v"(fyb)
-            : "v"(ux), "v"(uy), "s"(f32x2{0x1p23f, 0x1p23f}));
-        const uint32_t o0 = ((__float_as_uint(fyb.x) & hm) << (lw + 1u)) | (__float_as_uint(fxb.x) & wm2);
-        const uint32_t o1 = ((__float_as_uint(fyb.y) & hm) << (lw + 1u)) | (__float_as_uint(fxb.y) & wm2);
-        texel[2 * p] = (DBG & 2) ? (o0 & 255u) : *reinterpret_cast<const TexelWord *>(tb2 + (ONE ? o0 : o0 + lane_base2));
-        texel[2 * p + 1] = (DBG & 2) ? (o1 & 255u) : *reinterpret_cast<const TexelWord *>(tb2 + (ONE ? o1 : o1 + lane_base2));
-#elif RDOOM_FRAG_ADDR2
-        // the texel's BYTE offset from two and-s and an or (as fragment_quadrant_kernel forms it): the atlas origin is added
+        // F3: the texel's BYTE offset from two and-s and an or (as fragment_quadrant_kernel forms it): the atlas origin is added
         // with fma(r, 2, 2 atlas_u) = 2 RN(r + atlas_u) and fma(r, 2 W, 2 W atlas_v) = 2 W RN(r + atlas_v) -- scaling by a power
         // of two commutes with the rounding --, floor of those is 2 floor(x) + {0, 1} and 2 W floor(y) + {0 .. 2 W - 1}, and the
-        // masks (W - 1) << 1 and (H - 1) << (log2 W + 1) drop exactly the surplus bits (coordinates are >= 0)
-        (void)ux, (void)uy;
+        // masks (W - 1) << 1 and (H - 1) << (log2 W + 1) drop exactly the surplus bits (coordinates are >= 0).  2 % fewer
+        // instructions and 1 % less time than texel indices shifted into byte offsets (profiles/r04_ab.txt, item 6); a magic-number
+        // floor under a switched rounding mode saved 16 VALU instructions per block and no time (profiles/r03_ab.txt, run 1).
         const f32x2 ux2 = pk_fma(rx, splat(2.0f), splat(au2)), uys = pk_fma(ry, splat(ysc), splat(avs));
         const uint32_t b0 = ((uint32_t)cvt_floor_i32(uys.x) & hms) | ((uint32_t)cvt_floor_i32(ux2.x) & wm2a);
         const uint32_t b1 = ((uint32_t)cvt_floor_i32(uys.y) & hms) | ((uint32_t)cvt_floor_i32(ux2.y) & wm2a);
-        texel[2 * p] = (DBG & 2) ? (b0 & 255u) : *reinterpret_cast<const TexelWord *>(tba + (ONE ? b0 : b0 + base2));
-        texel[2 * p + 1] = (DBG & 2) ? (b1 & 255u) : *reinterpret_cast<const TexelWord *>(tba + (ONE ? b1 : b1 + base2));
-#else
-        const uint32_t o0 = (((uint32_t)cvt_floor_i32(uy.x) & hm) << lw) | ((uint32_t)cvt_floor_i32(ux.x) & wm);
-        const uint32_t o1 = (((uint32_t)cvt_floor_i32(uy.y) & hm) << lw) | ((uint32_t)cvt_floor_i32(ux.y) & wm);
         // (a 32-bit load at the texel's 2-byte-aligned address: bits 0..7 = palette index and bit 15 = transparent are
         // all that is read from it, the upper half is the next texel -- the array ends with a padding texel.  A 16-bit
         // load would be zero-extended again wherever it is used in another basic block: eight more instructions per run)
-        texel[2 * p] = (DBG & 2) ? (o0 & 255u) : *reinterpret_cast<const TexelWord *>(tb + (o0 * 2u + base2));
-        texel[2 * p + 1] = (DBG & 2) ? (o1 & 255u) : *reinterpret_cast<const TexelWord *>(tb + (o1 * 2u + base2));
-#endif
+        texel[2 * p] = *reinterpret_cast<const TexelWord *>(tba + (ONE ? b0 : b0 + base2));
+        texel[2 * p + 1] = *reinterpret_cast<const TexelWord *>(tba + (ONE ? b1 : b1 + base2));
       }
       // rw is monotone along the run: both ends inside the verified range of the exact reciprocal forms
       // (one unsigned compare per end: the bit patterns of [2^-100, 2^100] are the integers [0x0D800000, 0x71800000];
@@ -460,13 +390,6 @@ __global__ __launch_bounds__(64 * RDOOM_FRAG_WAVES) FRAG_OCCUPANCY void fragment
       };
       const f32x2 rf_ends = rows_of(f32x2{w_first, w_last});
       uint32_t ci[NPX];  // COLORMAP index = row * 256 + texel
-#ifdef RDOOM_FRAG_STATS
-      {  // census: how often does the per-pixel row evaluation below run (it runs for the whole wave when one run needs it)?
-        const unsigned long long dm = __ballot(rf_ends.x != rf_ends.y);
-        if (lane == 0u) atomicAdd(&g_frag_stats[14], 1ull);
-        if (lane == 0u && dm) atomicAdd(&g_frag_stats[15], 1ull), atomicAdd(&g_frag_stats[2], (unsigned long long)__popcll(dm));
-      }
-#endif
       if (rf_ends.x == rf_ends.y) {
         const uint32_t r8 = (uint32_t)(int)rf_ends.x << 8;
 #pragma unroll
@@ -483,15 +406,10 @@ __global__ __launch_bounds__(64 * RDOOM_FRAG_WAVES) FRAG_OCCUPANCY void fragment
         }
       }
       const bool opaque = (any_texel & 0x8000u) == 0u;
-#ifdef RDOOM_FRAG_STATS
-      if (!in_range) atomicAdd(&g_frag_stats[11], 1ull);
-      if (!mod_ok) atomicAdd(&g_frag_stats[12], 1ull);
-      if (!opaque) atomicAdd(&g_frag_stats[13], 1ull);
-#endif
       if (in_range & mod_ok & opaque) {
 #pragma unroll
         for (int p = 0; p < NP; p++) {
-          const uint32_t c0 = (DBG & 8) ? (ci[2 * p] & 0xFFu) : cmap[ci[2 * p]], c1 = (DBG & 8) ? (ci[2 * p + 1] & 0xFFu) : cmap[ci[2 * p + 1]];
+          const uint32_t c0 = cmap[ci[2 * p]], c1 = cmap[ci[2 * p + 1]];
           out[p >> 1] |= (c0 | (c1 << 8)) << (16 * (p & 1));
         }
         done = true;
@@ -553,20 +471,12 @@ __global__ __launch_bounds__(64 * RDOOM_FRAG_WAVES) FRAG_OCCUPANCY void fragment
         done = true;
       }
     }
-    if (done & valid & (!(DBG & 4) || out[0] == 0x12345679u)) {  // (DBG & 4, timing experiment: practically never)
-      if (DBG & 16) {  // timing experiment (wrong image): the block's 512 bytes as ONE contiguous run -- what would whole-line stores cost?
-        *reinterpret_cast<uint2 *>(pfb_bytes + (size_t)wb * 512u + lane * 8u) = make_uint2(out[0], out[NQ - 1]);
-      } else
+    if (done & valid) {
       if (NQ == 2)
         *reinterpret_cast<uint2 *>(pfb_bytes + q0 * 4u) = make_uint2(out[0], out[NQ - 1]);
       else
         *reinterpret_cast<uint32_t *>(pfb_bytes + q0 * 4u) = out[0];
     }
-#ifdef RDOOM_FRAG_STATS
-    if (valid) atomicAdd(&g_frag_stats[8], 1ull);
-    if (valid && !done) atomicAdd(&g_frag_stats[9], 1ull);
-    if (valid && !uniform) atomicAdd(&g_frag_stats[10], 1ull);
-#endif
     const unsigned long long sm = __ballot(!done);
     if (sm) {  // ordered append of this wave's unfinished quads, then shade full groups of 16
       if (!done) {
@@ -615,17 +525,10 @@ __global__ __launch_bounds__(64 * RDOOM_FRAG_WAVES) FRAG_OCCUPANCY void fragment
 // here gets QTAB_HANDLED in its table entry; fragment_kernel, launched next on the same stream, skips the blocks whose
 // quadrants are handled and treats every other entry as before.
 // =================================================================================================
-#ifndef RDOOM_QUAD_TILES
-#define RDOOM_QUAD_TILES 4
-#endif
-#ifndef RDOOM_QUAD_NP2
-#define RDOOM_QUAD_NP2 1  // 0: quadrants whose record has a non-power-of-two tile size are left to fragment_kernel (two instantiations of the body fewer: 64 VGPRs)
-#endif
-#ifndef RDOOM_QUAD_OCC
-#define RDOOM_QUAD_OCC 5  // waves per SIMD the register allocation must allow (96 VGPRs; 8 with RDOOM_QUAD_NP2 = 0: measured alike)
-#endif
-#define QUAD_OCCUPANCY __attribute__((amdgpu_waves_per_eu(RDOOM_QUAD_OCC, 8)))
-constexpr uint32_t QUAD_TILES_PER_WAVE = RDOOM_QUAD_TILES;  // a workgroup = 4 waves x this many tiles shares one LDS copy of COLORMAP
+// Launch shape (profiles/r04_ab.txt, item 1): a register budget for 5 waves per SIMD beat 4 and 6 (6 spills); 2, 4 or 8 tiles per
+// wave alike.  (Without the non-power-of-two class the body needs 64 VGPRs; budgets for 5 to 8 waves then measured alike: run r04f.)
+constexpr uint32_t QUAD_TILES_PER_WAVE = 4;  // a workgroup = 4 waves x this many tiles shares one LDS copy of COLORMAP
+constexpr int QUAD_OCC = 5;                  // waves per SIMD the register allocation must allow (96 VGPRs)
 
 __device__ __forceinline__ f32x2 colormap_rows(f32x2 dist, float light2) {  // F4, F5 for two pixels
   const f32x2 dterm = splat(1.0f) - exact_div09_2(dist + splat(0.9f));
@@ -720,16 +623,8 @@ __device__ __forceinline__ void shade_quadrant(const FragConst *__restrict__ fc,
       const f32x2 uys = pk_fma(ry, splat(ys), splat(avs));
       const uint32_t b0 = ((uint32_t)cvt_floor_i32(uys.x) & hms) | ((uint32_t)cvt_floor_i32(ux2.x) & wm2);
       const uint32_t b1 = ((uint32_t)cvt_floor_i32(uys.y) & hms) | ((uint32_t)cvt_floor_i32(ux2.y) & wm2);
-#if defined(RDOOM_TIMING_EXPERIMENTS) && defined(RDOOM_Q_FOLD)  // wrong images by design: what do the gathers cost?
-      texel[2 * p] = RDOOM_Q_FOLD ? *reinterpret_cast<const uint8_t *>(tbase + (b0 & 0x1FEu)) : (b0 & 0xFFu);
-      texel[2 * p + 1] = RDOOM_Q_FOLD ? *reinterpret_cast<const uint8_t *>(tbase + (b1 & 0x1FEu)) : (b1 & 0xFFu);
-#else
-#ifdef RDOOM_Q_LOAD32  // (A/B: 32-bit loads at the texel's 2-byte-aligned address, as fragment_kernel issues them)
-      if (true) {
-        texel[2 * p] = *reinterpret_cast<const TexelWord *>(tbase + b0) & 0xFFFFu;
-        texel[2 * p + 1] = *reinterpret_cast<const TexelWord *>(tbase + b1) & 0xFFFFu;
-      } else
-#endif
+      // (32-bit loads at the texel's 2-byte-aligned address, as fragment_kernel issues them, measured 1 % slower here:
+      // profiles/r04_ab.txt, run r04e)
       if (MASKED) {
         texel[2 * p] = *reinterpret_cast<const uint16_t *>(tbase + b0);
         texel[2 * p + 1] = *reinterpret_cast<const uint16_t *>(tbase + b1);
@@ -737,7 +632,6 @@ __device__ __forceinline__ void shade_quadrant(const FragConst *__restrict__ fc,
         texel[2 * p] = *reinterpret_cast<const uint8_t *>(tbase + b0);
         texel[2 * p + 1] = *reinterpret_cast<const uint8_t *>(tbase + b1);
       }
-#endif
     }
     if (MASKED) {
 #pragma unroll
@@ -780,7 +674,7 @@ __device__ __forceinline__ void shade_quadrant(const FragConst *__restrict__ fc,
   }
 }
 
-__global__ __launch_bounds__(256) QUAD_OCCUPANCY void fragment_quadrant_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(QUAD_OCC, 8))) void fragment_quadrant_kernel(
     const FragConst *__restrict__ fc, const uint16_t *__restrict__ texels, const uint8_t *__restrict__ colormap,
     const TriRec *__restrict__ recs, uint32_t cap, uint32_t *__restrict__ qtab, uint32_t n_poses, uint32_t groups_per_pose,
     uint32_t tiles_x, uint32_t n_tiles, int width, int height, uint8_t *__restrict__ fb) {
@@ -813,22 +707,12 @@ __global__ __launch_bounds__(256) QUAD_OCCUPANCY void fragment_quadrant_kernel(
     for (uint32_t q = 0; q < 4u; q++) {
       const uint32_t ent = (uint32_t)__builtin_amdgcn_readfirstlane((int)(q == 0u ? e4.x : (q == 1u ? e4.y : (q == 2u ? e4.z : e4.w))));
       const uint32_t qx0 = tx * 64u + (q & 1u) * 32u, qy0 = ty * 64u + (q >> 1) * 32u;
-#ifdef RDOOM_FRAG_STATS
-      if (lane == 0u && qx0 < (uint32_t)width && qy0 < (uint32_t)height) atomicAdd(&g_frag_stats[ent == NONE ? 3 : 4], 1ull);
-#endif
       // (the rasteriser writes no entry for a quadrant outside the frame: position first, then the entry)
       if (qx0 >= (uint32_t)width || qy0 >= (uint32_t)height || ent == NONE) continue;
       const uint4 *rp = reinterpret_cast<const uint4 *>(&prec[ent].s);
       const uint4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
       const uint32_t rflags = prec[ent].r.flags;
       const uint32_t flags = r3.z;
-#ifdef RDOOM_FRAG_STATS
-      if (lane == 0u) {
-        if (!(flags & SHADE_FAST)) atomicAdd(&g_frag_stats[5], 1ull);
-        else if (flags & SHADE_NP2) atomicAdd(&g_frag_stats[6], 1ull);
-        else if (rflags & RASTER_MASKED_ANY) atomicAdd(&g_frag_stats[7], 1ull);
-      }
-#endif
       if ((flags & SHADE_FAST) == 0u) continue;  // sky, decor, tile sizes the packed arithmetic does not cover
       // 1/w at the four corner pixels, evaluated as the pixels evaluate it
       const float wa = __uint_as_float(r0.x), wb = __uint_as_float(r0.y), wc = __uint_as_float(r0.z);
@@ -839,17 +723,12 @@ __global__ __launch_bounds__(256) QUAD_OCCUPANCY void fragment_quadrant_kernel(
       // (the bit patterns of [2^-100, 2^100] are the integers [0x0D800000, 0x71800000]; negative numbers and NaNs land above)
       if ((uint32_t)__builtin_amdgcn_readfirstlane((int)max(max(o0, o1), max(o2, o3))) > 0x71800000u - 0x0D800000u) continue;
       const bool masked = (rflags & RASTER_MASKED_ANY) != 0u;
-#if RDOOM_QUAD_NP2
       if (flags & SHADE_NP2) {
         if (masked)
           shade_quadrant<true, true>(fc, cmap, tb, pfb, pose, r0, r1, r2, r3, qx0, qy0, lane, width, height);
         else
           shade_quadrant<true, false>(fc, cmap, tb, pfb, pose, r0, r1, r2, r3, qx0, qy0, lane, width, height);
-      } else
-#else
-      if (flags & SHADE_NP2) continue;  // integer tile sizes that are not powers of two: fragment_kernel certifies their mod
-#endif
-      {
+      } else {
         if (masked)
           shade_quadrant<false, true>(fc, cmap, tb, pfb, pose, r0, r1, r2, r3, qx0, qy0, lane, width, height);
         else
@@ -1027,23 +906,8 @@ rdoom_status launch_fragment(hipStream_t st, uint32_t n_poses, const DeviceLevel
   // (fix_count[0..1] arrive zeroed: the caller's one fill at the start of the render)
   const uint64_t fgrid = (uint64_t)((n + 7) / 8) * 8ull * fblocks;
   if (fgrid > 0x7FFFFFFFull) return rdoom::fail(RDOOM_BAD_ARG, "batch too large for one launch");
-  auto frag = nq == 2 ? (vis16 ? fragment_kernel<2, 0, true> : fragment_kernel<2, 0, false>)
-                      : (vis16 ? fragment_kernel<1, 0, true> : fragment_kernel<1, 0, false>);
-#ifdef RDOOM_TIMING_EXPERIMENTS  // wrong images by design: never in the shipped library
-  // RDOOM_FRAG_DBG = bit set: 2 no texel loads, 4 no framebuffer stores, 8 no COLORMAP look-ups in LDS (two quads per lane, 16-bit words only)
-  if (getenv("RDOOM_FRAG_DBG") && nq == 2 && vis16) {
-    switch (atoi(getenv("RDOOM_FRAG_DBG"))) {
-      case 2: frag = fragment_kernel<2, 2, true>; break;
-      case 4: frag = fragment_kernel<2, 4, true>; break;
-      case 8: frag = fragment_kernel<2, 8, true>; break;
-      case 6: frag = fragment_kernel<2, 6, true>; break;
-      case 10: frag = fragment_kernel<2, 10, true>; break;
-      case 14: frag = fragment_kernel<2, 14, true>; break;
-      case 16: frag = fragment_kernel<2, 16, true>; break;
-      default: break;
-    }
-  }
-#endif
+  auto frag = nq == 2 ? (vis16 ? fragment_kernel<2, true> : fragment_kernel<2, false>)
+                      : (vis16 ? fragment_kernel<1, true> : fragment_kernel<1, false>);
   const uint32_t qtab_mode = qtab ? plan.qtab_mode : 0u;
   if (!*frag_const_ready) {  // constant for the life of the batch: written once
     FragConst h{};
@@ -1058,29 +922,12 @@ rdoom_status launch_fragment(hipStream_t st, uint32_t n_poses, const DeviceLevel
     hipLaunchKernelGGL(fragment_quadrant_kernel, dim3((uint32_t)qgrid), dim3(256), 0, st, static_cast<const FragConst *>(d_frag_const), lv.texels,
                        lv.colormap, recs, cap, qtab, n, groups, (uint32_t)tiles_x, n_tiles, W, H, fb);
   }
-#ifdef RDOOM_FRAG_CHUNKS_OUTER
-  if (fblocks > 65535u) return rdoom::fail(RDOOM_BAD_ARG, "frame too large for one launch");
-  const dim3 fgrid_dim(((n + 7u) / 8u) * 8u, fblocks);
-#else
-  const dim3 fgrid_dim((uint32_t)fgrid);
-#endif
-  hipLaunchKernelGGL(frag, fgrid_dim, dim3(64 * FRAG_WAVES), 0, st, static_cast<const FragConst *>(d_frag_const), lv.texels,
+  hipLaunchKernelGGL(frag, dim3((uint32_t)fgrid), dim3(64 * FRAG_WAVES), 0, st, static_cast<const FragConst *>(d_frag_const), lv.texels,
                      lv.colormap, recs, cap, poses, vis, n, fblocks, frag_chunk, qpp, qpr, wbpr, wbpp, bwl, W, H, fb, debug_leak_mod, qtab,
                      qtab_mode, (uint32_t)tiles_x, (uint32_t)(tiles_x * tiles_y));
   hipLaunchKernelGGL(fixup_kernel, dim3(64), dim3(256), 0, st, lv, recs, counts, cap, poses, W, pitch, H, tiles_x, tiles_y,
                      tile_hdr, entries, entry_cap, overflow, fix_count, fix_list, fix_cap, vis, vis16 ? 1u : 0u, prim_out, fb,
                      fix_count + 1);
-#ifdef RDOOM_FRAG_STATS
-  {
-    unsigned long long h[16];
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_frag_stats), sizeof h);
-    fprintf(stderr, "[frag stats] quadrants in the frame: undescribed %llu, described %llu (not shaded by the quadrant kernel: sky / decor / ineligible sizes %llu, non-power-of-two size %llu, masked texture %llu) | blocks of fragment_kernel: walked %llu, skipped %llu, walked with one handled half %llu\n",
-            h[3], h[4], h[5], h[6], h[7], h[0], h[1], h[2]);
-    fprintf(stderr, "[frag stats] packed-body invocations (waves) %llu, of which with some run whose COLORMAP rows differ at its ends %llu (%.1f %%; such runs %llu)\n", h[14], h[15], h[14] ? 100.0 * h[15] / h[14] : 0.0, h[2]);
-    fprintf(stderr, "[frag stats] runs %llu: to the general body %llu (%.2f %%): mixed %llu, rw out of range %llu, mod uncertified %llu, transparent texel %llu, other (decor, ineligible sizes) %llu\n", h[8], h[9], 100.0 * h[9] / h[8], h[10], h[11], h[12], h[13], h[9] - h[10] - h[11] - h[12] - h[13]);
-  }
-#endif
   return RDOOM_OK;
 }
 

@@ -19,28 +19,6 @@
 namespace rdoom_dev {
 namespace {
 
-// Section timers (tools/variant.sh NAME raster -DRDOOM_RASTER_TIMERS; never in the shipped library): where does a wave's
-// time go?  Every mark waits for the wave's outstanding memory operations, reads the shader clock (s_memtime) and
-// charges the cycles since the previous mark to a section; lane 0 adds the wave's sums to g_raster_t at the end.  The
-// waits serialise what would overlap and the reads cost cycles themselves: the SHARES are the result, not the total.
-#ifdef RDOOM_CENSUS_TWO
-__device__ unsigned long long g_raster_census[64];
-#endif
-#ifdef RDOOM_RASTER_TIMERS
-__device__ unsigned long long g_raster_t[16];
-__device__ __forceinline__ unsigned long long rt_now() {
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  return __builtin_readcyclecounter();
-}
-#define RT_DECL uint32_t rt_acc[10] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0}; unsigned long long rt_last = rt_now();
-#define RT_MARK(i) do { const unsigned long long n_ = rt_now(); rt_acc[i] += (uint32_t)(n_ - rt_last); rt_last = n_; } while (0)
-#define RT_FLUSH() do { if (lane == 0) { for (int k_ = 0; k_ < 10; k_++) atomicAdd(&g_raster_t[k_], (unsigned long long)rt_acc[k_]); atomicAdd(&g_raster_t[15], 1ull); } } while (0)
-#else
-#define RT_DECL
-#define RT_MARK(i) do { } while (0)
-#define RT_FLUSH() do { } while (0)
-#endif
-
 // =================================================================================================
 // Rasteriser, per-entry part.  Rejection is hierarchical and exact: fmaf is monotone in each argument, so the
 // extreme of a *computed* edge function, depth plane or 1/w plane over a pixel rectangle sits at a corner --
@@ -340,11 +318,7 @@ __global__ __launch_bounds__(256) void settle_kernel(const TriRec *__restrict__ 
       const float n1 = fmaf(e1a, pos(e1a) ? xl : xh, fmaf(e1b, pos(e1b) ? yl : yh, e1c));
       const float n2 = fmaf(e2a, pos(e2a) ? xl : xh, fmaf(e2b, pos(e2b) ? yl : yh, e2c));
       const float rwn = fmaf(wa, pos(wa) ? xl : xh, fmaf(wb, pos(wb) ? yl : yh, wc));
-#ifndef RDOOM_NO_EDGE_COVER
       const int qx1 = min(rx0 + 31, width - 1), qy1 = min(ry0 + 31, height - 1);
-#else
-      const int qx1 = rx0 + 31, qy1 = ry0 + 31;
-#endif
       const bool cover = (zn >= 0.0f) & (zf <= 1.0f) & (rwn > 0.0f) & (x0 <= rx0) & (x1 >= qx1) & (y0 <= ry0) & (y1 >= qy1) &
                          ((c4.y & RASTER_MASKED_INTERIOR) == 0u) & (n0 > 0.0f) & (n1 > 0.0f) & (n2 > 0.0f);
       if (cover) {
@@ -356,20 +330,11 @@ __global__ __launch_bounds__(256) void settle_kernel(const TriRec *__restrict__ 
   qtab[((size_t)pose * T + tile) * 4u + q] = out;
 }
 
-#ifndef RDOOM_RANK_LIMIT
-#define RDOOM_RANK_LIMIT 0  // a batch of a binned list with more entries than this is walked in list order, unranked (0: always --
-                            // ranking every batch by record index measured 1 % slower at 1080p and 8 % slower on the large level)
-#endif
-#ifndef RDOOM_SETTLE_MAX
-#define RDOOM_SETTLE_MAX 32  // settle_kernel examines whole lists of at most this many entries (a lane walks the list: longer ones are the rasteriser's)
-#endif
-#ifndef RDOOM_RASTER_OCC
-#define RDOOM_RASTER_OCC 4  // waves per SIMD the register allocation aims at (128 VGPRs)
-#endif
-#ifndef RDOOM_RASTER_WAVES
-#define RDOOM_RASTER_WAVES 1
-#endif
-constexpr uint32_t RASTER_WAVES = RDOOM_RASTER_WAVES;  // tiles (= waves) per workgroup
+constexpr uint32_t SETTLE_MAX = 32;  // settle_kernel examines whole lists of at most this many entries (a lane walks the list: longer ones are the rasteriser's)
+// Measured in round 2 (docs/HISTORY.md): one tile per workgroup 2.49 ms, two 2.56, four 2.90; a register budget for 5 waves per
+// SIMD spills 81 registers (3.83 ms)
+constexpr int RASTER_OCC = 4;         // waves per SIMD the register allocation aims at (128 VGPRs)
+constexpr uint32_t RASTER_WAVES = 1;  // tiles (= waves) per workgroup
 
 // VIS16: 16-bit visibility words (record indices below 65 535; 0xFFFF = none) -- a compile-time choice: as a run-time
 // flag the compiler kept it as a per-lane boolean and spilled that register to scratch
@@ -380,7 +345,7 @@ constexpr uint32_t RASTER_WAVES = RDOOM_RASTER_WAVES;  // tiles (= waves) per wo
 // SPLIT: the binning kernel may have stored long lists per quadrant (bin.hip); without it the instantiation is the kernel as
 // it was before such lists existed (the caller chooses per render: renderer.hip)
 template <bool STATS, bool VIS16, bool PRIM, bool SKIPVIS, bool SPLIT>
-__global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void raster_wave_kernel(DeviceLevelView lv, const TriRec *__restrict__ recs,
+__global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_kernel(DeviceLevelView lv, const TriRec *__restrict__ recs,
                                                              const uint32_t *__restrict__ counts, uint32_t cap,
                                                              uint32_t n_poses, int width, int height, int tiles_x,
                                                              int tiles_y, const uint2 *__restrict__ tile_hdr,
@@ -400,23 +365,18 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
   // so blockIdx.x & 7 is the XCD and all tiles of a pose land on one of them; no division is needed to find (pose, tile)
   static_assert(RASTER_WAVES == 1, "the 3-D grid maps one tile to one workgroup");
   const uint32_t T = (uint32_t)(tiles_x * tiles_y);
-#ifndef RDOOM_RASTER_ROWS_INNER
   // Tile ROWS are the slowest grid dimension, the frame's middle rows first (workgroups are dispatched x-fastest, then y, then z):
   // the horizon rows hold the long lists, and a wave that walks 60 entries through four quadrants lives ten times longer than the
   // average one -- dispatched with the last pose group it WAS the kernel's tail (a fixed ~0.1 ms per launch whatever the batch
   // size, which the 128-pose renders of a strong-scaling share paid nine times per step).  Now every pose's heavy rows start
   // first and the launch ends with the cheap rows (floor, ceiling, sky: mostly settled, their waves end after one load).
+  // Rows first: 11 % faster at 1080p, 15 % on the large level (profiles/r05_ab.txt, item 7).
   const uint32_t pose = blockIdx.y * 8u + (blockIdx.x & 7u);
   const uint32_t zk = blockIdx.z, zc = (uint32_t)tiles_y >> 1;
   const uint32_t tile_y = (zk & 1u) ? zc - ((zk + 1u) >> 1) : zc + (zk >> 1);  // c, c - 1, c + 1, c - 2, ...
-#else
-  const uint32_t pose = blockIdx.z * 8u + (blockIdx.x & 7u);
-  const uint32_t tile_y = blockIdx.y;
-#endif
   const int tid = threadIdx.x, wave = 0, lane = tid & 63;
   const uint32_t tile_x = blockIdx.x >> 3, tile = tile_y * (uint32_t)tiles_x + tile_x;
   if (pose >= n_poses) return;
-  RT_DECL
   const int tx0 = (int)tile_x * TILE_W, ty0 = (int)tile_y * TILE_H;
   const int lx = (lane & 7) * 4, ly = (lane >> 3) * 4;  // this lane's 4x4 block inside a quadrant
   const TriRec *prec = recs + (size_t)pose * cap;
@@ -472,11 +432,12 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
     const unsigned long long rm = __ballot(qb != 0u);
     n = (uint32_t)__popcll(rm);
     if (n != 0u) {
-      // rank of my entry among the relevant ones (record index = depth rank; the lists are near-sorted already).  A batch of
-      // more than RDOOM_RANK_LIMIT entries of a binned list is taken in list order instead (every entry of such a list is
-      // relevant, lane s already holds the s-th; the binning kernel's lists are near to far up to its window of 256 records).
+      // rank of my entry among the relevant ones (record index = depth rank; the lists are near-sorted already).  A binned list
+      // is taken in list order instead (every entry of such a list is relevant, lane s already holds the s-th; the binning
+      // kernel's lists are near to far up to its window of 256 records): ranking its batches measured 1 % slower at 1080p and 8 %
+      // slower on the large level (profiles/r04_ab.txt, item 8).
       uint32_t e = cand | (qb << 28);
-      if (!binned || n <= RDOOM_RANK_LIMIT) {
+      if (!binned) {
         uint32_t rank = 0;
         for (unsigned long long m = rm; m; m &= m - 1ull) {
           const uint32_t kj = (uint32_t)__builtin_amdgcn_readlane((int)cand, (int)__builtin_ctzll(m));
@@ -527,12 +488,8 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
           const float rwn = fmaf(wa, pos(wa) ? xl : xh, fmaf(wb, pos(wb) ? yl : yh, wc));
           // (the bbox is clipped to the frame: a quadrant that crosses the frame's right or bottom edge is covered when the
           // bbox reaches that edge -- the pixels beyond it do not exist; the corner values above are those of the whole
-          // quadrant, which only asks for more)
-#ifndef RDOOM_NO_EDGE_COVER
+          // quadrant, which only asks for more.  Small but positive on every workload: profiles/r03_ab.txt, run 16)
           const int qx1 = min(rx0 + 31, width - 1), qy1 = min(ry0 + 31, height - 1);
-#else
-          const int qx1 = rx0 + 31, qy1 = ry0 + 31;
-#endif
           const bool common = (zn >= 0.0f) & (zf <= 1.0f) & (rwn > 0.0f) & (x0 <= rx0) & (x1 >= qx1) & (y0 <= ry0) & (y1 >= qy1) &
                               ((c4.y & RASTER_MASKED_INTERIOR) == 0u);
           const bool p0 = n0 > 0.0f, p1 = n1 > 0.0f, p2 = n2 > 0.0f;
@@ -553,31 +510,17 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     }
   };
-#ifdef RDOOM_RASTER_TIMERS
-  asm volatile("" ::"s"(count));
-#endif
-  RT_MARK(0);  // header, overflow flag, count
   if (single && count != 0u) gather(0u, -1);
-  RT_MARK(1);  // list gather: entries, ranking, records, per-quadrant nearest depths and cover flags
-#ifdef RDOOM_TIMING_EXPERIMENTS  // the list gather and record set-up run twice: the difference in kernel time is their cost
-  asm volatile("" ::: "memory");
-  if (single && count != 0u) gather(0u, -1);
-#endif
-#ifndef RDOOM_NO_TILE_SHORTCUT
   // The same shortcut one level up: the tile's nearest entry (by its nearest depth over the quadrants it touches, not by its
   // place in the ranked list) covers all four quadrants and every other entry lies, in every quadrant it touches, strictly
-  // behind that entry's farthest depth over the whole tile.
+  // behind that entry's farthest depth over the whole tile.  (Kept: rasteriser 2.36 -> 2.30 ms, profiles/r03_ab.txt, run 10.)
   // (Whole tiles only: its stores carry no frame checks.  The quadrants of a tile that crosses the frame's edge take the
   // quadrant-level shortcut below.)
   if (!split && single && n != 0u && todo == 0xFu && tx0 + TILE_W <= width && ty0 + TILE_H <= height) {
     // my entry's nearest depth over the quadrants it touches (lanes without an entry hold NONE everywhere)
     const uint32_t tq = myrq >> 24;
     const uint32_t near_all = min(min((tq & 1u) ? dnq0 : NONE, (tq & 2u) ? dnq1 : NONE), min((tq & 4u) ? dnq2 : NONE, (tq & 8u) ? dnq3 : NONE));
-#ifndef RDOOM_RANKED_SHORTCUT
     const uint32_t sc = (uint32_t)__builtin_ctzll(__ballot(near_all == wave_min_u32(near_all)));  // the nearest entry of the tile
-#else
-    const uint32_t sc = 0u;  // the first of the ranked list
-#endif
     const uint32_t rq0 = (uint32_t)__builtin_amdgcn_readlane((int)myrq, (int)sc);
     if ((rq0 >> 28) == 0xFu) {
       const float za0 = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)zpa, (int)sc)),
@@ -611,14 +554,10 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
         }
         if (STATS && lane == 0)
           for (int k = 0; k < 20; k++) atomicAdd(&stats[k], st[k]);
-        RT_MARK(2);  // tile-level shortcut, taken
-        RT_FLUSH();
         return;
       }
     }
   }
-#endif
-  RT_MARK(3);  // tile-level shortcut, not taken
 #pragma unroll 1
   for (int q = 0; q < 4; q++) {
     const int qx0 = tx0 + (q & 1) * 32, qy0 = ty0 + (q >> 1) * 32;  // this quadrant
@@ -643,14 +582,11 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
       const unsigned long long touch_s = __ballot(((myrq >> (24 + q)) & 1u) != 0u);
       const unsigned long long cover_s = __ballot(((myrq >> (28 + q)) & 1u) != 0u);
       if (touch_s != 0ull) {
-#ifndef RDOOM_RANKED_SHORTCUT
         // the entry with the nearest depth over THIS quadrant, wherever it stands in the tile's ranking (the ranking is by
-        // the triangles' depth as a whole: a floor triangle that starts at the camera's feet precedes the wall it ends at)
+        // the triangles' depth as a whole: a floor triangle that starts at the camera's feet precedes the wall it ends at).
+        // Rather than the first entry of the ranking: shortcut quadrants 61.7 -> 69.5 % at 1080p (profiles/r03_ab.txt, run 17)
         const uint32_t near_q = wave_min_u32(((myrq >> (24 + q)) & 1u) ? dnq_s : NONE);
         const uint32_t s0 = (uint32_t)__builtin_ctzll(__ballot(dnq_s == near_q) & touch_s);
-#else
-        const uint32_t s0 = (uint32_t)__builtin_ctzll(touch_s);
-#endif
         if ((cover_s >> s0) & 1ull) {
           const float za0 = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)zpa, (int)s0)),
                       zb0 = __uint_as_float((uint32_t)__builtin_amdgcn_readlane((int)zpb, (int)s0)),
@@ -681,11 +617,9 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
                 }
               }
             }
-            RT_MARK(4);  // quadrant shortcut, taken
             continue;
           }
         }
-#ifndef RDOOM_NO_PAIR_SHORTCUT
         // The two-entry shortcut.  A third of the quadrants that show more than one triangle show exactly TWO that share an edge
         // -- the diagonal of a wall quad, a spoke of a floor fan (census with the oracle's winners: 9.6 % of all quadrants at
         // 1080p).  Set-up gives a shared edge exactly negated coefficients in the two triangles (S3), so e_B(pixel) = -e_A(pixel)
@@ -695,6 +629,7 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
         // every other entry lies strictly behind the farther of their farthest depths, the winner of a pixel is decided by the
         // sign of ONE edge function: no depth is evaluated, nothing is initialised.  A = the entry that is nearest over the
         // quadrant, B = a touching entry one of whose edge hashes equals one of A's (verified exactly below).
+        // (Kept: rasteriser 1.896 -> 1.812 ms at 1080p, profiles/r04_ab.txt, item 4.)
         const uint4 hA4 = whash[wave][s0];
         const uint32_t cxA = ((uint32_t)__builtin_amdgcn_readfirstlane((int)hA4.w) >> q) & 0x111u;  // A covers but for edge 0 / 1 / 2: bits 0 / 4 / 8
         if (cxA != 0u && __popcll(touch_s) >= 2) {  // (most quadrants that show several triangles leave here: no edge of A to share)
@@ -772,22 +707,10 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
               }
             }
           }
-          if (paired) {
-            RT_MARK(4);
-            continue;
-          }
-#ifdef RDOOM_CENSUS_TWO  // census build only (tools/variant.sh rcensus raster -DRDOOM_CENSUS_TWO): what do the remaining full passes look like?
-          {
-            const uint32_t nt = min((uint32_t)__popcll(touch_s), 7u);
-            const uint32_t ncx = min((uint32_t)__popcll(__ballot(((hme.w >> q) & 0x111u) != 0u) & touch_s), 3u);   // entries that cover but for one edge
-            if (lane == 0) atomicAdd(&g_raster_census[nt * 4u + ncx], 1ull);
-          }
-#endif
+          if (paired) continue;
         }
-#endif
       }
     }
-    RT_MARK(5);  // quadrant shortcut, not taken
     uint32_t best_d[16], best_r[16];
 #pragma unroll
     for (int k = 0; k < 16; k++) {
@@ -823,23 +746,15 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
       uint32_t wave_far = wave_max_u32(lane_far);
       unsigned long long wm = touch & __ballot(dnq <= wave_far);
       if (STATS) st[0] += (unsigned long long)__popcll(touch), st[15] += (unsigned long long)__popcll(touch & ~wm);
-#ifndef RDOOM_RANKED_WALK
       // The covering entry that is nearest over this quadrant goes first, wherever it stands in the ranking (the winner does
       // not depend on the order): its depth-only body then puts a bound on every lane, and entries ranked before it that lie
-      // behind it are dropped by the compare below instead of being rasterised.
+      // behind it are dropped by the compare below instead of being rasterised (profiles/r03_ab.txt, run 18).
       uint32_t s_first = 64u;
       if (qcm & wm) s_first = (uint32_t)__builtin_ctzll(__ballot(dnq == wave_min_u32(((qcm >> lane) & 1ull) ? dnq : NONE)) & qcm & wm);
-#endif
-      RT_MARK(6);  // quadrant pass set-up: initialisation, wave-wide farthest depth, first covering entry
       while (wm) {
-#ifndef RDOOM_RANKED_WALK
         const uint32_t s = s_first < 64u ? s_first : (uint32_t)__builtin_ctzll(wm);
         s_first = 64u;
         wm &= ~(1ull << s);
-#else
-        const uint32_t s = (uint32_t)__builtin_ctzll(wm);
-        wm &= wm - 1ull;
-#endif
         const uint32_t far_before = lane_far;
         auto refresh = [&]() {  // after a body: drop what is hidden now
           if (__any(lane_far != far_before)) {
@@ -884,7 +799,6 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
           }
           if (!__any(tiez == 0u)) {
             refresh();
-            RT_MARK(7);  // covering entry: depth-only body
             continue;
           }
         }
@@ -899,7 +813,6 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
                                  uf(r3.x), za, zb, zc, uf(r2.x), uf(r2.y), uf(r2.z), x0, y0, x1, y1, flags, ridx, bx, by, pxlo,
                                  pxhi, pylo, pyhi, best_d, best_r, lane_far, [&]() -> ShadeRec { return prec[ridx].s; }, st);
         refresh();
-        RT_MARK(8);  // other entry: record broadcast, rejection tests, pixel bodies
       }
     }
     if (STATS) {  // the census a per-lane choice of entries would be judged by: the pass's bodies (st[2]) against the most any ONE lane needed
@@ -910,8 +823,9 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
     // One record after all?  (The shortcut above needs the winner to lie strictly in front of everything else over the whole
     // quadrant; a quadrant can still end up with one winner.)  Lane 0's first pixel lies inside the frame; lanes whose block
     // lies outside it do not count -- the table speaks about the pixels of the frame.
+    // (Checked only where some entry covers the quadrant: the fragment kernel gains what the rasteriser pays and a little more,
+    // profiles/r03_ab.txt, run 14.)
     uint32_t described = NONE;
-#ifndef RDOOM_NO_LATE_TABLE
     if (qtab && had_cover) {  // (one winner needs a triangle that covers the quadrant: without one the check is skipped)
       const uint32_t rf = (uint32_t)__builtin_amdgcn_readfirstlane((int)best_r[0]);
       uint32_t lo = best_r[0], hi = best_r[0];  // (three-operand min / max: 16 instructions for the 16 winners)
@@ -932,7 +846,6 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
       const bool outside_lane = (bx >= width) | (by >= height);
       if (rf != NONE && __all(outside_lane | ((lo == rf) & (hi == rf)))) described = rf;
     }
-#endif
     if (STATS && described != NONE) st[11]++;
     if (qtab && lane == 0) qtab[((size_t)pose * T + tile) * 4u + (uint32_t)q] = described;  // NONE: not known to be uniform
     const bool want_vis = !SKIPVIS || described == NONE;  // (uniform) a described quadrant needs no visibility words
@@ -960,9 +873,7 @@ __global__ __launch_bounds__(64 * RDOOM_RASTER_WAVES, RDOOM_RASTER_OCC) void ras
         }
       }
     }
-    RT_MARK(9);  // one-winner check, table entry, visibility words
   }
-  RT_FLUSH();
   if (STATS && lane == 0)
     for (int k = 0; k < 20; k++) atomicAdd(&stats[k], st[k]);
 }
@@ -997,46 +908,17 @@ rdoom_status launch_raster(hipStream_t st, uint32_t n_poses, const DeviceLevelVi
   auto rk = split_lists ? pick2(std::true_type{}) : pick2(std::false_type{});
   // settle_kernel first (see there): only where the rasteriser may skip what it settles -- the table is in use, no visibility
   // words or primitive ids are owed for described quadrants, the one-entry shortcut is not switched off by a hook
-  const uint32_t max_list = dbg.settle_max > 0 ? (uint32_t)dbg.settle_max : RDOOM_SETTLE_MAX;
+  const uint32_t max_list = dbg.settle_max > 0 ? (uint32_t)dbg.settle_max : SETTLE_MAX;
   const bool settle = skip && !prim_out && !dbg.no_settle && !dbg.no_cover && !dbg.raster_stats && bins_launched;
   if (settle) {
     const uint32_t T4 = (uint32_t)(tiles_x * tiles_y) * 4u;
     hipLaunchKernelGGL(settle_kernel, dim3(((T4 + 255u) / 256u) * 8u, 1, groups), dim3(256), 0, st, recs, cap, n, width, height, tiles_x, tiles_y, tile_hdr,
                        entries, entry_cap, overflow, qtab, max_list);
   }
-#ifndef RDOOM_RASTER_ROWS_INNER
-  const dim3 rgrid((uint32_t)tiles_x * 8u, groups, (uint32_t)tiles_y);
-#else
-  const dim3 rgrid((uint32_t)tiles_x * 8u, (uint32_t)tiles_y, groups);
-#endif
+  const dim3 rgrid((uint32_t)tiles_x * 8u, groups, (uint32_t)tiles_y);  // tile rows the slowest dimension (raster_wave_kernel)
   hipLaunchKernelGGL(rk, rgrid, dim3(64 * RASTER_WAVES), 0, st, lv, recs, counts, cap, n, width, height, tiles_x,
                      tiles_y, tile_hdr, entries, entry_cap, overflow, vis, prim_out, (dbg.no_cover ? 1u : 0u) | (dbg.no_pair ? 2u : 0u),
                      qtab, settle ? 1u : 0u, d_stats);
-#ifdef RDOOM_CENSUS_TWO
-  {
-    unsigned long long h[64], zero[64] = {};
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_raster_census), sizeof h);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_raster_census), zero, sizeof zero);
-    fprintf(stderr, "[raster census] passes that reach the two-entry test with an edge of the nearest entry to share, by touching entries (rows 0..7+) x entries that cover but for one edge (0..3+):\n");
-    for (int t = 0; t < 8; t++) fprintf(stderr, "   %d: %llu %llu %llu %llu\n", t, h[4 * t], h[4 * t + 1], h[4 * t + 2], h[4 * t + 3]);
-  }
-#endif
-#ifdef RDOOM_RASTER_TIMERS
-  {
-    unsigned long long h[16], zero[16] = {};
-    (void)hipStreamSynchronize(st);
-    (void)hipMemcpyFromSymbol(h, HIP_SYMBOL(g_raster_t), sizeof h);
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_raster_t), zero, sizeof zero);
-    unsigned long long total = 0;
-    for (int k = 0; k < 10; k++) total += h[k];
-    static const char *names[10] = {"header", "gather", "tile shortcut taken", "tile shortcut not taken", "quadrant shortcut taken",
-                                    "quadrant shortcut not taken", "pass set-up", "cover body", "other entry", "final check + stores"};
-    fprintf(stderr, "[raster timers] %llu waves, %.0f cycles per wave:", h[15], h[15] ? (double)total / (double)h[15] : 0.0);
-    for (int k = 0; k < 10; k++) fprintf(stderr, "  %s %.1f %%", names[k], total ? 100.0 * (double)h[k] / (double)total : 0.0);
-    fprintf(stderr, "\n");
-  }
-#endif
   if (d_stats) {
     unsigned long long h[20];
     HIP_TRY(hipMemcpy(h, d_stats, sizeof h, hipMemcpyDeviceToHost));

@@ -191,10 +191,6 @@ __device__ __forceinline__ bool rect_may_touch(const uint4 c0, const uint4 c1, c
   const float zf = fmaf(za, za > 0.0f ? xh : xl, fmaf(zb, zb > 0.0f ? yh : yl, zc));
   return (m0 >= 0.0f) & (m1 >= 0.0f) & (m2 >= 0.0f) & (zn <= 1.0f) & (zf >= 0.0f);
 }
-__device__ __forceinline__ bool tile_may_touch(const uint4 c0, const uint4 c1, const uint4 c2, int tx0, int ty0) {
-  return rect_may_touch(c0, c1, c2, (float)tx0 + 0.5f, (float)tx0 + 63.5f, (float)ty0 + 0.5f, (float)ty0 + 63.5f);
-}
-
 
 // F1..F3: perspective-correct tile coordinates -> atlas texel coordinates (shared by the alpha test
 // R6 and the fragment stage).  `row_u`/`row_v`/`row_w` are fmaf(B, py, C) of the three planes.

@@ -24,19 +24,6 @@ namespace {
 bool is_pow2(uint32_t x) { return x != 0 && (x & (x - 1)) == 0; }
 }  // namespace
 
-// Host-side section timers of rdoom_batch_render (tools/variant.sh NAME renderer -DRDOOM_HOST_TIMERS; never in the shipped
-// library): where does the host's time per render go?  Sums are printed when a batch is destroyed.
-#ifdef RDOOM_HOST_TIMERS
-#include <chrono>
-static double g_host_t[12];
-static unsigned long long g_host_n;
-#define HT_DECL auto ht_last = std::chrono::steady_clock::now();
-#define HT_MARK(i) do { const auto n_ = std::chrono::steady_clock::now(); g_host_t[i] += std::chrono::duration<double, std::micro>(n_ - ht_last).count(); ht_last = n_; } while (0)
-#else
-#define HT_DECL
-#define HT_MARK(i) do { } while (0)
-#endif
-
 // A resident SET of levels (rdoom_levelset_create); rdoom_level_create makes a set of one.
 struct rdoom_level {
   int device = 0;
@@ -44,7 +31,6 @@ struct rdoom_level {
   void *d_clusters = nullptr;
   void *d_tris = nullptr, *d_texels = nullptr, *d_sky = nullptr, *d_cmap = nullptr, *d_slices = nullptr;
   std::vector<LevelSlice> slices;      // host copy of the slice table
-  std::vector<uint32_t> slice_objects; // 1 + the largest object id each level draws
   uint32_t ntri = 0;        // the LARGEST level's triangle count: a pose's records and visible list have this stride
   uint32_t n_objects = 1;   // 1 + the largest object id any level of the set draws
   // PLAYPAL 0 of every level, 256 words R | G << 8 | B << 16 | 0xFF << 24 per level: read by the resolve kernels only (they take it
@@ -405,7 +391,6 @@ static rdoom_status levelset_create_impl(const rdoom_level_desc *const *descs, u
     sky.insert(sky.end(), h.sky.begin(), h.sky.end());
     lv->ntri = std::max(lv->ntri, sl.ntri);
     lv->n_objects = std::max(lv->n_objects, h.n_objects);
-    lv->slice_objects.push_back(h.n_objects);
     max_clusters = std::max(max_clusters, sl.n_clusters);
     h = HostLevel{};  // (released: a set of many levels would otherwise hold every atlas twice)
   }
@@ -468,17 +453,6 @@ static rdoom_status levelset_create_impl(const rdoom_level_desc *const *descs, u
 
 void rdoom_batch_destroy(rdoom_batch *b) {
   if (!b) return;
-#ifdef RDOOM_HOST_TIMERS
-  if (g_host_n) {
-    static const char *names[12] = {"wait for the staging buffer", "per-pose constants", "H2D + event", "flag memset + set-up launches", "binning launch", "rasteriser launch",
-                                    "fragment + fixup launches", "closing event", "", "", "", ""};
-    fprintf(stderr, "[host timers] %llu renders, microseconds per render:", g_host_n);
-    for (int k = 0; k < 8; k++) fprintf(stderr, "  %s %.1f", names[k], g_host_t[k] / (double)g_host_n);
-    fprintf(stderr, "\n");
-    g_host_n = 0;
-    for (auto &t : g_host_t) t = 0;
-  }
-#endif
   for (void *p : {(void *)b->d_poses, (void *)b->d_recs, (void *)b->d_visible, (void *)b->d_tile_hdr, (void *)b->d_entries, (void *)b->d_hits,
                   (void *)b->d_overflow, (void *)b->d_zeroed, (void *)b->d_fix_list, (void *)b->d_vis,
                   (void *)b->d_prim, (void *)b->d_fb, (void *)b->d_qtab, b->d_frag_const, (void *)b->d_rgb})
@@ -617,7 +591,6 @@ extern "C++" {  // (a template, inside the C ABI's extern "C" block)
 template <class Constants>
 static rdoom_status queue_pipeline(rdoom_batch *b, uint32_t n, uint32_t kinds_mask, hipStream_t st, rdoom_timings *tm,
                                    bool objects, bool profiled, hipEvent_t *ev, DoneGuard &done, Constants &&constants) {
-  HT_DECL
   const rdoom_level *lv = b->level;
   const bool marks = tm || profiled;
   const int W = (int)b->width, H = (int)b->height, PITCH = (int)b->pitch;
@@ -629,7 +602,6 @@ static rdoom_status queue_pipeline(rdoom_batch *b, uint32_t n, uint32_t kinds_ma
                                        lv->n_objects, W, H, kinds_mask, b->d_recs, b->d_visible, b->d_counts,
                                        b->d_ghist, b->cap, b->d_fix_count + 2))
       return rs;
-  HT_MARK(3);
   const int tiles_x = (W + TILE_W - 1) / TILE_W, tiles_y = (H + TILE_H - 1) / TILE_H;
   bool split_lists = false;  // long tile lists stored per quadrant this render (binning kernel and rasteriser must agree)
   bool bins = false;
@@ -641,7 +613,6 @@ static rdoom_status queue_pipeline(rdoom_batch *b, uint32_t n, uint32_t kinds_ma
     HIP_TRY(hipMemsetAsync(b->d_overflow, 0xFF, sizeof(uint32_t) * n, st));
   }
   if (marks) HIP_TRY(hipEventRecord(ev[1], st));
-  HT_MARK(4);
   uint32_t *prim_out = b->want_prim ? b->d_prim : nullptr;
   // one reading of the debug hooks for both kernels: who writes and who reads visibility words must not change in between
   const FragmentPlan plan = plan_fragment(W, PITCH, H, b->d_qtab != nullptr);
@@ -653,20 +624,14 @@ static rdoom_status queue_pipeline(rdoom_batch *b, uint32_t n, uint32_t kinds_ma
                                       plan.skip_described_vis, split_lists, bins))
     return rs;
   if (marks) HIP_TRY(hipEventRecord(ev[2], st));
-  HT_MARK(5);
   if (rdoom_status rs = launch_fragment(st, n, lv->view, b->d_recs, b->d_counts, b->cap, b->d_poses, W, PITCH, H, tiles_x,
                                         tiles_y, b->d_tile_hdr, b->d_entries, b->entry_cap, b->d_overflow, b->d_vis, b->vis16,
                                         prim_out, b->d_ndc, b->d_fb, b->d_fix_count, b->d_fix_list, b->fix_cap, b->d_qtab, b->d_frag_const,
                                         &b->frag_const_ready, plan))
     return rs;
   HIP_TRY(hipGetLastError());
-  HT_MARK(6);
   done.armed = false;
   HIP_TRY(hipEventRecord(b->ev_done, st));
-  HT_MARK(7);
-#ifdef RDOOM_HOST_TIMERS
-  g_host_n++;
-#endif
   if (profiled) {
     HIP_TRY(hipEventRecord(ev[3], st));
     b->ring_n++;
@@ -707,11 +672,9 @@ static rdoom_status render_impl(rdoom_batch *b, const rdoom_pose *poses, const u
   HIP_TRY(hipSetDevice(lv->device));  // level, scratch and kernels on one device (several GPUs driven from one process)
   if (object_modelviews && n_objects < lv->n_objects)
     return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u but the level draws objects 0..%u", n_objects, lv->n_objects - 1);
-  HT_DECL
   const uint32_t sg = b->stage;  // this render's staging buffers: the H2D copy that last read them is two renders back
   b->stage = (sg + 1u) % rdoom_batch::STAGES;
   HIP_TRY(hipEventSynchronize(b->ev_copy[sg]));
-  HT_MARK(0);
   PoseConst *h_poses = b->h_poses[sg];
   if (object_modelviews) {
     const size_t count = (size_t)b->max_poses * lv->n_objects;
@@ -745,7 +708,6 @@ static rdoom_status render_impl(rdoom_batch *b, const rdoom_pose *poses, const u
     pc.pad0 = pc.pad1 = pc.pad2 = 0u;
   }
   b->last_n = n;
-  HT_MARK(1);
   b->last_levels_on_device = false;
   hipEvent_t *ev = nullptr;
   if (rdoom_status rs = render_marks(b, profiled, &ev)) return rs;
@@ -758,7 +720,6 @@ static rdoom_status render_impl(rdoom_batch *b, const rdoom_pose *poses, const u
     HIP_TRY(hipMemcpyAsync(b->d_objects, b->h_objects[sg], sizeof(ObjectConst) * (size_t)n * lv->n_objects,
                            hipMemcpyHostToDevice, st));
   HIP_TRY(hipEventRecord(b->ev_copy[sg], st));
-  HT_MARK(2);
   return queue_pipeline(b, n, kinds_mask, st, tm, object_modelviews != nullptr, profiled, ev, done, [] { return RDOOM_OK; });
 }
 

@@ -234,13 +234,10 @@ __device__ __forceinline__ uint32_t depth_bucket(float wmin) {
   return min(b, SORT_BUCKETS - 1u);
 }
 
-#ifndef RDOOM_CULL_OCC
-#define RDOOM_CULL_OCC 1
-#endif
-#ifndef RDOOM_SETUP_OCC
-#define RDOOM_SETUP_OCC 1
-#endif
-__global__ __launch_bounds__(256, RDOOM_CULL_OCC) void cull_kernel(DeviceLevelView lv, const PoseConst *__restrict__ poses,
+// No register budget for the set-up kernels: the set-up kernel held to 96 / 80 VGPRs spills 2 / 29 registers and is slower
+// (profiles/r04_ab.txt, item 10)
+constexpr int CULL_OCC = 1, SETUP_OCC = 1;
+__global__ __launch_bounds__(256, CULL_OCC) void cull_kernel(DeviceLevelView lv, const PoseConst *__restrict__ poses,
                                                    const ObjectConst *__restrict__ objects, uint32_t n_objects,
                                                    int width, int height, uint32_t kinds_mask,
                                                    uint32_t *__restrict__ visible, uint32_t *__restrict__ counts,
@@ -398,7 +395,7 @@ __global__ __launch_bounds__(256) void sort_scan_kernel(uint32_t *__restrict__ g
 // near-to-far position (scanned histogram + one atomic): record index == position in the sorted list from here on (bin /
 // raster / fragment gather records by that index).  The order inside a bucket is whatever the atomics hand out (nothing
 // depends on it).  A few workgroups per pose, each striding over the pose's list of visible triangles.
-__global__ __launch_bounds__(256, RDOOM_SETUP_OCC) void setup_kernel(DeviceLevelView lv, const PoseConst *__restrict__ poses,
+__global__ __launch_bounds__(256, SETUP_OCC) void setup_kernel(DeviceLevelView lv, const PoseConst *__restrict__ poses,
                                                     const ObjectConst *__restrict__ objects, uint32_t n_objects,
                                                     int width, int height, uint32_t kinds_mask,
                                                     const uint32_t *__restrict__ visible, TriRec *__restrict__ recs,
@@ -434,7 +431,6 @@ __global__ __launch_bounds__(256, RDOOM_SETUP_OCC) void setup_kernel(DeviceLevel
       // and reported by rdoom_batch_finish / the read functions instead of drawing from overwritten records.
       if (!setup_triangle(ls, pc, objs, t, tri, width, height, kinds_mask, rec.r, rec.s, wkey)) *mismatch_flag = 1u;
       bucket = depth_bucket(wkey);
-#ifndef RDOOM_NO_EMPTY_CULL
       // A triangle whose bbox holds at most 3 x 3 pixel centres and covers none of them (the rasteriser's own edge
       // functions, operation order and fill rule: R1, R2) draws nothing: its bbox is made empty, so the binning kernel
       // lists it in no tile (far geometry at small frame sizes: most of the visible triangles are of this kind).
@@ -460,7 +456,6 @@ __global__ __launch_bounds__(256, RDOOM_SETUP_OCC) void setup_kernel(DeviceLevel
           if (!any) rec.r.bb0 = 0x0000FFFFu, rec.r.bb1 = 0u;  // x0 = 65535 > x1 = 0
         }
       }
-#endif
       lrank = atomicAdd(&lcount[bucket], 1u);
     }
     __syncthreads();
