@@ -269,8 +269,43 @@ rdoom_status rdoom_batch_resolve_rgb(rdoom_batch *batch, uint32_t first, uint32_
  * frames through a bounded staging buffer the batch allocates on first use; reports the render's device errors like
  * rdoom_batch_read_framebuffer. */
 rdoom_status rdoom_batch_read_rgb(rdoom_batch *batch, uint32_t first, uint32_t count, uint32_t format, uint8_t *host_out);
+/* Per-pixel planes of the batch's LAST render, resolved on demand for frames [first, first+count) from what the render leaves
+ * on the device (quadrant table, visibility words, fixup list, the poses' triangle records): nothing is switched on before the
+ * render and a render costs the same whether planes are asked for or not.  plane = one RDOOM_PLANE_*, optionally
+ * | RDOOM_RGB_TOP_DOWN.  Rows are tight (width elements, no padding); row 0 is the bottom row unless RDOOM_RGB_TOP_DOWN.
+ *
+ *   plane                  element   where a flat / wall / decor fragment won             sky pixel                 nothing drawn
+ *   RDOOM_PLANE_DEPTH      float32   v_dist of the winning fragment (static.vert:42,      +inf (sky.frag has no     +inf
+ *                                    sprite.vert:44): the clip-space w, i.e. the linear   v_dist)
+ *                                    view-space depth in the reference's world units (the
+ *                                    units of rdoom_player_state.pos), evaluated as
+ *                                    1.0f / fmaf(wp[0], x + 0.5f, fmaf(wp[1], y + 0.5f, wp[2]))
+ *                                    with the record's 1/w plane wp, IEEE division, no
+ *                                    contraction -- the bits the fragment stage computes
+ *   RDOOM_PLANE_LABEL      uint16    kind | object_id << 4  (kind: RDOOM_KIND_*, 0..3;   RDOOM_KIND_SKY |          RDOOM_LABEL_NONE
+ *                                    object_id: rdoom_draw.object_id, 12 bits, 0 = the    object_id << 4
+ *                                    static level)
+ *   RDOOM_PLANE_PRIMITIVE  uint32    the winning primitive id (triangle index in the draw  the same                 0xFFFFFFFF
+ *                                    order of the pose's level), exactly what
+ *                                    rdoom_batch_read_primitive_ids reports
+ *
+ * No palette is needed: a level created without a playpal resolves, also after rdoom_batch_render_players. */
+#define RDOOM_PLANE_DEPTH 1u
+#define RDOOM_PLANE_LABEL 2u
+#define RDOOM_PLANE_PRIMITIVE 3u
+#define RDOOM_LABEL_NONE 0xFFFFu /* label of a pixel nothing was drawn to */
+/* Asynchronous, on `stream` (a hipStream_t, may be NULL), ordered like rdoom_batch_resolve_rgb: waits for the batch's last render,
+ * writes count * height * width elements to device_out -- device memory on the batch's device, aligned to the element -- and
+ * rdoom_batch_finish / the rdoom_batch_read_* then wait for it too.  Order the batch's next render after it. */
+rdoom_status rdoom_batch_resolve_plane(rdoom_batch *batch, uint32_t first, uint32_t count, uint32_t plane, void *device_out,
+                                       void *stream);
+/* Synchronous: the same plane copied to host memory, resolved in chunks of frames through the batch's bounded staging buffer;
+ * reports the render's device errors like rdoom_batch_read_framebuffer. */
+rdoom_status rdoom_batch_read_plane(rdoom_batch *batch, uint32_t first, uint32_t count, uint32_t plane, void *host_out);
 /* Debug / test facility: capture the winning primitive id per pixel (triangle index in the draw order of the pose's level,
- * 0xFFFFFFFF = none) on the following renders, then read it back.  No GL counterpart. */
+ * 0xFFFFFFFF = none) on the following renders, then read it back.  No GL counterpart.  It selects a slower instantiation of the
+ * rasteriser and keeps 4 bytes per pixel for the whole batch: RDOOM_PLANE_PRIMITIVE above gives the same ids after any render,
+ * on the device or the host, without either. */
 rdoom_status rdoom_batch_enable_primitive_ids(rdoom_batch *batch);
 rdoom_status rdoom_batch_read_primitive_ids(rdoom_batch *batch, uint32_t first, uint32_t count, uint32_t *host_out);
 

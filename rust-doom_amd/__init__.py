@@ -24,6 +24,10 @@ NO_PRIMITIVE = 0xFFFFFFFF
 # rdoom_batch_resolve_rgb / rdoom_batch_read_rgb formats (include/rdoom.h); CLEAR_RGB: the GL clear colour (window.rs:40-44)
 RGB8, RGBA8, RGB_TOP_DOWN = 3, 4, 0x100
 CLEAR_RGB = (15, 18, 23)
+# rdoom_batch_resolve_plane / rdoom_batch_read_plane: per-pixel planes of the last render (include/rdoom.h has the contract)
+PLANE_DEPTH, PLANE_LABEL, PLANE_PRIMITIVE = 1, 2, 3
+LABEL_NONE = 0xFFFF
+PLANE_DTYPES = {PLANE_DEPTH: np.float32, PLANE_LABEL: np.uint16, PLANE_PRIMITIVE: np.uint32}
 
 STATIC_VERTEX = np.dtype([('a_pos', '<f4', 3), ('a_atlas_uv', '<f4', 2), ('a_tile_uv', '<f4', 2),
                           ('a_tile_size', '<f4', 2), ('a_scroll_rate', '<f4'), ('a_row_height', '<f4'),
@@ -119,7 +123,7 @@ API_SYMBOLS = [
     'rdoom_player_config_default', 'rdoom_world_triggers', 'rdoom_world_game_bytes', 'rdoom_world_game_reset', 'rdoom_world_step_game',
     'rdoom_object_modelviews_from_player', 'rdoom_worldset_create', 'rdoom_worldset_destroy', 'rdoom_worldset_info',
     'rdoom_worldset_level', 'rdoom_worldset_game_bytes', 'rdoom_worldset_game_reset', 'rdoom_worldset_step_game',
-    'rdoom_poses_from_players_device', 'rdoom_batch_render_players']
+    'rdoom_poses_from_players_device', 'rdoom_batch_render_players', 'rdoom_batch_resolve_plane', 'rdoom_batch_read_plane']
 
 _lib = None
 
@@ -698,6 +702,56 @@ class Batch:
             stream = stream.cuda_stream
         _check(lib().rdoom_batch_resolve_rgb(self._h, first, count, fmt, ctypes.c_void_p(ptr or None), ctypes.c_void_p(stream or 0)))
         return out
+
+    def _plane_args(self, plane, first, count, top_down):
+        if plane not in PLANE_DTYPES:
+            raise ValueError('plane must be PLANE_DEPTH, PLANE_LABEL or PLANE_PRIMITIVE, not %r' % (plane,))
+        count = self.last_n - first if count is None else count
+        return int(first), int(count), int(plane) | (RGB_TOP_DOWN if top_down else 0), (int(count), self.height, self.width)
+
+    def read_plane(self, plane, first=0, count=None, top_down=False):
+        """rdoom_batch_read_plane: one per-pixel plane of frames [first, first+count) of the last render as (count, H, W) --
+        PLANE_DEPTH float32 (the winning fragment's view-space depth in world units, +inf for sky and where nothing was drawn),
+        PLANE_LABEL uint16 (kind | object id << 4, LABEL_NONE where nothing was drawn), PLANE_PRIMITIVE uint32 (what
+        read_primitive_ids reports, without enable_primitive_ids); row 0 = the bottom row unless top_down"""
+        first, count, arg, shape = self._plane_args(plane, first, count, top_down)
+        out = np.zeros(shape, PLANE_DTYPES[plane])
+        _check(lib().rdoom_batch_read_plane(self._h, first, count, arg, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def resolve_plane(self, out, plane, first=0, count=None, top_down=False, stream=None):
+        """rdoom_batch_resolve_plane: the same plane written to device memory, asynchronously on `stream` (a hipStream_t handle,
+        or a torch stream; None = the null stream).  out: a raw device pointer (int) of count*H*W elements, or a contiguous torch
+        tensor of the plane's dtype (float32 / uint16 / uint32; int16 / int32 are taken as their bits) with that many elements
+        on the batch's device.  Returns out."""
+        first, count, arg, shape = self._plane_args(plane, first, count, top_down)
+        if isinstance(out, int):
+            ptr = out
+        else:
+            import torch  # (only here: the package imports without torch)
+            if not isinstance(out, torch.Tensor):
+                raise TypeError('out must be a device pointer (int) or a torch tensor, not %s' % type(out).__name__)
+            names = {PLANE_DEPTH: ('float32',), PLANE_LABEL: ('uint16', 'int16'), PLANE_PRIMITIVE: ('uint32', 'int32')}[plane]
+            ok = [getattr(torch, n) for n in names if hasattr(torch, n)]
+            if out.dtype not in ok or not out.is_contiguous() or out.device.type != 'cuda':
+                raise ValueError('out must be a contiguous %s tensor on the GPU (got %s, %s, contiguous=%s)'
+                                 % (' / '.join('torch.' + n for n in names), out.dtype, out.device, out.is_contiguous()))
+            need = int(np.prod(shape))
+            if out.numel() != need:
+                raise ValueError('out has %d elements, frames %d..%d need %s = %d' % (out.numel(), first, first + count, shape, need))
+            ptr = out.data_ptr()  # (the library checks that it lives on the batch's device)
+        if stream is not None and not isinstance(stream, int):
+            stream = stream.cuda_stream
+        _check(lib().rdoom_batch_resolve_plane(self._h, first, count, arg, ctypes.c_void_p(ptr or None), ctypes.c_void_p(stream or 0)))
+        return out
+
+    def read_depth(self, first=0, count=None, top_down=False):
+        """read_plane(PLANE_DEPTH, ...): (count, H, W) float32"""
+        return self.read_plane(PLANE_DEPTH, first, count, top_down)
+
+    def resolve_depth(self, out, first=0, count=None, top_down=False, stream=None):
+        """resolve_plane(out, PLANE_DEPTH, ...): out a float32 tensor (or device pointer) of count*H*W elements"""
+        return self.resolve_plane(out, PLANE_DEPTH, first, count, top_down, stream)
 
     def enable_primitive_ids(self):
         _check(lib().rdoom_batch_enable_primitive_ids(self._h))

@@ -83,6 +83,30 @@ struct ResolveArgs {
 };
 rdoom_status launch_resolve(hipStream_t st, const ResolveArgs &args);
 
+// Kernels 7 + 8: one per-pixel plane (RDOOM_PLANE_*) of frames [first, first + count) of the last render, from the quadrant table,
+// the visibility words and the pose's records, then the pixels of the fixup list (planes.hip)
+struct PlaneArgs {
+  const void *vis;
+  bool vis16;
+  const uint32_t *qtab;
+  bool use_qtab;  // the render's FragmentPlan::skip_described_vis, as ResolveArgs
+  const PoseConst *poses;
+  const TriRec *recs;  // cap records per pose
+  uint32_t cap;
+  const LevelTri *tris;  // the label's object ids: LevelTri::packed of slices[pose.level].first_tri + primitive id
+  const LevelSlice *slices;
+  const uint32_t *fix_count;
+  const uint2 *fix_list;
+  uint32_t fix_cap;
+  uint32_t first, count;
+  int width, pitch, height;
+  uint32_t plane;  // RDOOM_PLANE_DEPTH / LABEL / PRIMITIVE
+  bool top_down;
+  void *out;  // count x height x width elements of plane_element_bytes(plane), aligned to the element
+};
+size_t plane_element_bytes(uint32_t plane);
+rdoom_status launch_plane(hipStream_t st, const PlaneArgs &args);
+
 // Kernel 0 of rdoom_batch_render_players, and all of rdoom_poses_from_players_device: players' states -> cameras (frames.hip).
 // One lane per (player, object); every output is optional.
 struct PlayerFrameArgs {

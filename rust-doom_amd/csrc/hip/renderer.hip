@@ -961,6 +961,34 @@ static rdoom_status rgb_args(const rdoom_batch *b, uint32_t first, uint32_t coun
   return RDOOM_OK;
 }
 
+// device_out of the resolve entry points must be device memory of the batch's device with room for what the kernels write there
+static rdoom_status device_out_check(const rdoom_batch *b, const void *device_out, size_t bytes) {
+  hipPointerAttribute_t attr{};
+  hipDeviceptr_t base = nullptr;
+  size_t size = 0;
+  if (hipPointerGetAttributes(&attr, device_out) != hipSuccess || attr.type != hipMemoryTypeDevice ||
+      hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)device_out) != hipSuccess) {
+    (void)hipGetLastError();  // (a failed query must not be reported by the next render's launch check)
+    return rdoom::fail(RDOOM_BAD_ARG, "device_out is not device memory");
+  }
+  if (attr.device != b->level->device) return rdoom::fail(RDOOM_BAD_ARG, "device_out is on device %d, the batch on %d", attr.device, b->level->device);
+  if ((const char *)device_out + bytes > (const char *)base + size)
+    return rdoom::fail(RDOOM_BAD_ARG, "device_out: %zu bytes needed, its allocation ends %zu bytes after it", bytes,
+                       (size_t)((const char *)base + size - (const char *)device_out));
+  return RDOOM_OK;
+}
+
+// the batch's bounded staging buffer of the synchronous read functions: at least `bytes` of device memory
+static rdoom_status staging(rdoom_batch *b, size_t bytes) {
+  if (b->rgb_bytes < bytes) {
+    if (b->d_rgb) HIP_TRY(hipFree(b->d_rgb));
+    b->d_rgb = nullptr, b->rgb_bytes = 0;
+    HIP_TRY(hipMalloc((void **)&b->d_rgb, bytes));
+    b->rgb_bytes = bytes;
+  }
+  return RDOOM_OK;
+}
+
 // queues the two resolve kernels on st behind the last render; ev_done then marks their end (finish / read_* wait for it)
 static rdoom_status resolve_impl(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint8_t *out, hipStream_t st) {
   HIP_TRY(hipStreamWaitEvent(st, b->ev_done, 0));
@@ -977,20 +1005,7 @@ static rdoom_status resolve_impl(rdoom_batch *b, uint32_t first, uint32_t count,
 rdoom_status rdoom_batch_resolve_rgb(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, void *device_out, void *stream) {
   if (rdoom_status rs = rgb_args(b, first, count, format, device_out)) return rs;
   HIP_TRY(bind_device(b));
-  // device_out must be device memory of the batch's device with room for the frames: the kernels write there
-  const size_t bytes = (size_t)count * b->height * b->width * (format & 0xFFu);
-  hipPointerAttribute_t attr{};
-  hipDeviceptr_t base = nullptr;
-  size_t size = 0;
-  if (hipPointerGetAttributes(&attr, device_out) != hipSuccess || attr.type != hipMemoryTypeDevice ||
-      hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)device_out) != hipSuccess) {
-    (void)hipGetLastError();  // (a failed query must not be reported by the next render's launch check)
-    return rdoom::fail(RDOOM_BAD_ARG, "device_out is not device memory");
-  }
-  if (attr.device != b->level->device) return rdoom::fail(RDOOM_BAD_ARG, "device_out is on device %d, the batch on %d", attr.device, b->level->device);
-  if ((const char *)device_out + bytes > (const char *)base + size)
-    return rdoom::fail(RDOOM_BAD_ARG, "device_out: %zu bytes needed, its allocation ends %zu bytes after it", bytes,
-                       (size_t)((const char *)base + size - (const char *)device_out));
+  if (rdoom_status rs = device_out_check(b, device_out, (size_t)count * b->height * b->width * (format & 0xFFu))) return rs;
   return resolve_impl(b, first, count, format, (uint8_t *)device_out, (hipStream_t)stream);
 }
 
@@ -1001,16 +1016,63 @@ rdoom_status rdoom_batch_read_rgb(rdoom_batch *b, uint32_t first, uint32_t count
   if (count == 0) return RDOOM_OK;
   const size_t frame = (size_t)b->height * b->width * (format & 0xFFu);
   const uint32_t chunk = (uint32_t)std::max<size_t>(1u, std::min<size_t>(count, RGB_STAGING_BYTES / frame));
-  if (b->rgb_bytes < chunk * frame) {
-    if (b->d_rgb) HIP_TRY(hipFree(b->d_rgb));
-    b->d_rgb = nullptr, b->rgb_bytes = 0;
-    HIP_TRY(hipMalloc((void **)&b->d_rgb, chunk * frame));
-    b->rgb_bytes = chunk * frame;
-  }
+  if (rdoom_status rs = staging(b, chunk * frame)) return rs;
   for (uint32_t f = first; f < first + count; f += chunk) {
     const uint32_t n = std::min(chunk, first + count - f);
     if (rdoom_status rs = resolve_impl(b, f, n, format, b->d_rgb, b->copy_stream)) return rs;
     HIP_TRY(hipMemcpyAsync(host_out + (size_t)(f - first) * frame, b->d_rgb, n * frame, hipMemcpyDeviceToHost, b->copy_stream));
+    HIP_TRY(hipStreamSynchronize(b->copy_stream));
+  }
+  return RDOOM_OK;
+}
+
+// ---- depth / label / primitive planes (planes.hip) ------------------------------------------------------------------------
+// what both plane entry points reject before they touch the device or wait for anything
+static rdoom_status plane_args(const rdoom_batch *b, uint32_t first, uint32_t count, uint32_t plane, const void *out) {
+  if (plane & ~(0xFFu | (uint32_t)RDOOM_RGB_TOP_DOWN)) return rdoom::fail(RDOOM_BAD_ARG, "unknown plane bits 0x%x", plane);
+  const uint32_t which = plane & 0xFFu;
+  if (which != RDOOM_PLANE_DEPTH && which != RDOOM_PLANE_LABEL && which != RDOOM_PLANE_PRIMITIVE)
+    return rdoom::fail(RDOOM_BAD_ARG, "plane 0x%x: RDOOM_PLANE_DEPTH, _LABEL or _PRIMITIVE, optionally | RDOOM_RGB_TOP_DOWN", plane);
+  if (!b || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (b->last_n == 0) return rdoom::fail(RDOOM_BAD_ARG, "nothing rendered yet");
+  if ((uint64_t)first + count > b->last_n) return rdoom::fail(RDOOM_BAD_ARG, "frame range outside the last render");
+  if ((uintptr_t)out % plane_element_bytes(which)) return rdoom::fail(RDOOM_BAD_ARG, "output is not aligned to the plane's %zu-byte element", plane_element_bytes(which));
+  return RDOOM_OK;
+}
+
+// queues the two plane kernels on st behind the last render; ev_done then marks their end, as resolve_impl
+static rdoom_status plane_impl(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t plane, void *out, hipStream_t st) {
+  HIP_TRY(hipStreamWaitEvent(st, b->ev_done, 0));
+  PlaneArgs a{};
+  a.vis = b->d_vis, a.vis16 = b->vis16, a.qtab = b->d_qtab, a.use_qtab = b->last_skip_vis, a.poses = b->d_poses;
+  a.recs = b->d_recs, a.cap = b->cap, a.tris = b->level->view.tris, a.slices = b->level->view.slices;
+  a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list, a.fix_cap = b->fix_cap;
+  a.first = first, a.count = count, a.width = (int)b->width, a.pitch = (int)b->pitch, a.height = (int)b->height;
+  a.plane = plane & 0xFFu, a.top_down = (plane & RDOOM_RGB_TOP_DOWN) != 0u, a.out = out;
+  const rdoom_status rs = launch_plane(st, a);
+  HIP_TRY(hipEventRecord(b->ev_done, st));
+  return rs;
+}
+
+rdoom_status rdoom_batch_resolve_plane(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t plane, void *device_out, void *stream) {
+  if (rdoom_status rs = plane_args(b, first, count, plane, device_out)) return rs;
+  HIP_TRY(bind_device(b));
+  if (rdoom_status rs = device_out_check(b, device_out, (size_t)count * b->height * b->width * plane_element_bytes(plane & 0xFFu))) return rs;
+  return plane_impl(b, first, count, plane, device_out, (hipStream_t)stream);
+}
+
+rdoom_status rdoom_batch_read_plane(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t plane, void *host_out) {
+  if (rdoom_status rs = plane_args(b, first, count, plane, host_out)) return rs;
+  HIP_TRY(bind_device(b));
+  if (rdoom_status fs = device_flags(b)) return fs;
+  if (count == 0) return RDOOM_OK;
+  const size_t frame = (size_t)b->height * b->width * plane_element_bytes(plane & 0xFFu);
+  const uint32_t chunk = (uint32_t)std::max<size_t>(1u, std::min<size_t>(count, RGB_STAGING_BYTES / frame));
+  if (rdoom_status rs = staging(b, chunk * frame)) return rs;
+  for (uint32_t f = first; f < first + count; f += chunk) {
+    const uint32_t n = std::min(chunk, first + count - f);
+    if (rdoom_status rs = plane_impl(b, f, n, plane, b->d_rgb, b->copy_stream)) return rs;
+    HIP_TRY(hipMemcpyAsync((uint8_t *)host_out + (size_t)(f - first) * frame, b->d_rgb, n * frame, hipMemcpyDeviceToHost, b->copy_stream));
     HIP_TRY(hipStreamSynchronize(b->copy_stream));
   }
   return RDOOM_OK;

@@ -1,0 +1,31 @@
+"""The plane kernels (rust-doom_amd/csrc/hip/planes.hip) as shipped: every instantiation found in the library uses no scratch
+memory and spills no register, and every plane has at least one.  A bandwidth-bound pass has no excuse for either."""
+import importlib.util
+import os
+import re
+import shutil
+
+import pytest
+
+from util import ROOT
+
+_spec = importlib.util.spec_from_file_location('kernel_resources', os.path.join(ROOT, 'tools', 'kernel_resources.py'))
+kr = importlib.util.module_from_spec(_spec)
+_spec.loader.exec_module(kr)
+
+HEADER = open(os.path.join(ROOT, 'include', 'rdoom.h')).read()
+
+
+@pytest.mark.skipif(not (os.path.exists(os.path.join(kr.LLVM, 'llvm-objdump')) and shutil.which('c++filt')), reason='needs the ROCm LLVM tools')
+def test_plane_kernels_are_shipped_without_scratch_or_spills():
+    res = {kr.short(k): v for k, v in kr.kernel_resources().items()}
+    ours = {k: v for k, v in res.items() if re.match(r'plane_(fix_)?kernel<', k)}
+    assert ours, sorted(res)
+    for k, r in ours.items():
+        assert r['private_segment_fixed_size'] == 0 and r['vgpr_spill_count'] == 0, (k, r)
+        assert r['group_segment_fixed_size'] == 0, (k, r)  # no LDS either
+    for name in ('DEPTH', 'LABEL', 'PRIMITIVE'):
+        plane = int(re.search(r'^#define\s+RDOOM_PLANE_%s\s+(\d+)u' % name, HEADER, flags=re.M).group(1))
+        for kernel in ('plane_kernel', 'plane_fix_kernel'):
+            found = [k for k in ours if re.match(r'%s<%du?, (true|false)>' % (kernel, plane), k)]
+            assert found, (name, kernel, sorted(ours))
