@@ -688,6 +688,40 @@ rdoom_status rdoom_batch_render_players(rdoom_batch *batch, const rdoom_player_s
                                         uint32_t lights_stride, float time, uint32_t n_players, uint32_t kinds_mask,
                                         uint32_t flags, void *stream, rdoom_pose *d_poses_out, float *d_object_modelviews_out);
 
+/* ---- ray casts: range-sensor rays from player states through the world --------------------------------
+ * n players x n_rays rays in one launch, asynchronous on `stream`; every pointer is device memory, nothing is copied to the
+ * host and nothing waits.  d_states: the n states a step leaves.  d_dirs: ONE table of n_rays camera-frame directions (xyz
+ * float32, -z is forward), shared by every player; it need not be normalised.
+ * Origin: ray (p, r) starts at player p's camera eye, the `disp` of player.concat(camera): rotate(q_player, (0, 0.12, 0)) + pos
+ * with q_player = Quaternion::from(Euler { x: pitch, y: yaw, z: 0 }) -- what rdoom_poses_from_players_device computes, in its
+ * operation order, sine and cosine from the project's sincos.  Direction: dir = rotate(q_player, d_dirs[r]), vel = dir * max_range.
+ * Ray against triangle: the plane branch of Sphere::sweep_triangle (math/src/sphere.rs:16-53) at radius 0 and nothing else:
+ * speed = |vel|, nvel = vel / speed; normal . nvel >= 0 rejects the triangle; signed_plane_distance < 0 rejects it;
+ * distance = -signed_plane_distance / (normal . nvel); is_point_inside_triangle(origin + nvel * distance) decides the hit;
+ * time = distance / speed.  Binary32, no contraction, IEEE division and square root, rdoom_world_sweep's operand order.  The
+ * vertex and edge branches are left out on purpose: at radius 0 they can fire only through rounding.
+ * Traversal: World::sweep_sphere at radius 0 (world.rs:40-82): Node::intersect_sphere with radius 0, the positive child first,
+ * leaves swept when met, then the dynamic chunks with the origin moved by minus the object's offset (row p of d_object_offsets,
+ * n x n_objects x xyz as for rdoom_world_sweep with one row per PLAYER; NULL = every object at rest); the fold keeps the later
+ * candidate on equal times.  The result is defined as that fold.
+ * d_frac_out[p * n_rays + r] (float32): time when time <= 1, else +inf -- the fraction of max_range, +inf = nothing within
+ * range.  d_hit_out (uint32, may be NULL): the winning triangle's index in the level's own rdoom_world_arrays.triangles, or
+ * 0xFFFFFFFF where the fraction is +inf; for a world set the index within that slot's arrays (rdoom_worldset_level), the set's
+ * rebasing undone.  d_origin_out / d_vel_out (xyz float32 per ray, may be NULL): the origin and vel the kernel used, so that the
+ * very same rays can be handed to rdoom_world_sweep with radius 0.
+ * Errors, all checked before anything is queued (RDOOM_BAD_ARG): a NULL handle, d_dirs, or (n > 0) d_states / d_frac_out /
+ * d_levels; n_rays == 0; max_range not finite or not positive; d_object_offsets with n_objects smaller than the world's (the
+ * set's: its largest level's); a world created with RDOOM_WORLD_HOST_ONLY.  n == 0 queues nothing.  A level slot >= the set's
+ * size is seen on the device only: that player's rays get +inf / 0xFFFFFFFF and nothing else of them is written. */
+#define RDOOM_RAY_NO_HIT 0xFFFFFFFFu
+rdoom_status rdoom_world_cast_rays(const rdoom_world *world, const rdoom_player_state *d_states, uint32_t n, const float *d_dirs,
+                                   uint32_t n_rays, float max_range, const float *d_object_offsets, uint32_t n_objects,
+                                   float *d_frac_out, uint32_t *d_hit_out, float *d_origin_out, float *d_vel_out, void *stream);
+rdoom_status rdoom_worldset_cast_rays(const rdoom_worldset *set, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                      uint32_t n, const float *d_dirs, uint32_t n_rays, float max_range,
+                                      const float *d_object_offsets, uint32_t n_objects, float *d_frac_out, uint32_t *d_hit_out,
+                                      float *d_origin_out, float *d_vel_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

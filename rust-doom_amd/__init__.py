@@ -61,6 +61,7 @@ WORLDSET_NO_DESTINATION = 0xFFFFFFFF
 WORLDSET_LEVEL = np.dtype([('archive_index', '<u4'), ('destination', '<u4'), ('start_pos', '<f4', 3), ('start_yaw', '<f4'),
                            ('n_triggers', '<u4'), ('n_objects', '<u4'), ('node_depth', '<u4')])
 assert PLAYER_STATE.itemsize == 40 and PLAYER_INPUT.itemsize == 20 and PLAYER_CONFIG.itemsize == 32
+RAY_NO_HIT = 0xFFFFFFFF  # rdoom_world_cast_rays' hit index where nothing is within range
 
 
 class RdoomError(RuntimeError):
@@ -123,7 +124,8 @@ API_SYMBOLS = [
     'rdoom_player_config_default', 'rdoom_world_triggers', 'rdoom_world_game_bytes', 'rdoom_world_game_reset', 'rdoom_world_step_game',
     'rdoom_object_modelviews_from_player', 'rdoom_worldset_create', 'rdoom_worldset_destroy', 'rdoom_worldset_info',
     'rdoom_worldset_level', 'rdoom_worldset_game_bytes', 'rdoom_worldset_game_reset', 'rdoom_worldset_step_game',
-    'rdoom_poses_from_players_device', 'rdoom_batch_render_players', 'rdoom_batch_resolve_plane', 'rdoom_batch_read_plane']
+    'rdoom_poses_from_players_device', 'rdoom_batch_render_players', 'rdoom_batch_resolve_plane', 'rdoom_batch_read_plane',
+    'rdoom_world_cast_rays', 'rdoom_worldset_cast_rays']
 
 _lib = None
 
@@ -994,6 +996,65 @@ def _reset_masked(mask, reset):
         torch.cuda.synchronize(km.device)
 
 
+def ray_fan(n_rays, fov, pitch=0.0):
+    """a direction table for cast_rays: n_rays unit directions in the camera frame (-z forward), evenly spaced in yaw across `fov`
+    radians and centred on -z (ray 0 is the leftmost, at +fov / 2; an odd n_rays has a ray straight ahead), all raised by `pitch` radians"""
+    n_rays = int(n_rays)
+    if n_rays < 1:
+        raise ValueError('n_rays must be at least 1')
+    yaw = np.linspace(0.5 * fov, -0.5 * fov, n_rays) if n_rays > 1 else np.zeros(1)
+    cp, sp = np.cos(float(pitch)), np.sin(float(pitch))
+    return np.stack([-np.sin(yaw) * cp, np.full(n_rays, sp), -np.cos(yaw) * cp], 1).astype(np.float32)
+
+
+def _triangle_objects(arrays):
+    """the object id of every triangle of a World.arrays dict: 0 for the statics, a dynamic chunk's object id for its triangles"""
+    out = np.zeros(len(arrays['triangles']), np.uint32)
+    for obj, start, end in arrays['dynamics']:
+        out[start:end] = obj
+    return out
+
+
+def _cast_rays(call, states, levels, dirs, max_range, offsets, frac_out, hit_out, origin_out, vel_out, stream):
+    """World.cast_rays / WorldSet.cast_rays: the checks and the launch; call(states, levels, n, dirs, n_rays, max_range, offsets,
+    n_objects, frac, hit, origin, vel, stream) is the C entry point with its handle bound"""
+    import torch
+    for t, what in ((states, 'states'), (dirs, 'dirs')) + (((levels, 'levels'),) if levels is not None else ()) + \
+            (((offsets, 'offsets'),) if offsets is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous tensor on the GPU' % what)
+    n = _n_players(states)
+    if dirs.dtype != torch.float32 or dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] == 0:
+        raise ValueError('dirs must be a float32 (n_rays, 3) tensor with n_rays >= 1, got %s %s' % (dirs.dtype, tuple(dirs.shape)))
+    n_rays = int(dirs.shape[0])
+    if levels is not None and (levels.element_size() != 4 or levels.numel() != n):
+        raise ValueError('levels must hold one 32-bit slot per player (%d), got %s %s' % (n, levels.dtype, tuple(levels.shape)))
+    n_obj = 0
+    if offsets is not None:
+        if offsets.dtype != torch.float32 or offsets.dim() != 3 or offsets.shape[0] != n or offsets.shape[2] != 3:
+            raise ValueError('offsets must be a float32 (n, n_objects, 3) tensor for %d players, got %s %s'
+                             % (n, offsets.dtype, tuple(offsets.shape)))
+        n_obj = int(offsets.shape[1])
+    want_hit = hit_out is not None
+    if hit_out is True:
+        hit_out = torch.empty((n, n_rays), dtype=torch.int32, device=states.device)
+    if frac_out is None:
+        frac_out = torch.empty((n, n_rays), dtype=torch.float32, device=states.device)
+    elif frac_out.dtype != torch.float32:
+        raise ValueError('frac_out must be float32')
+    pf = _out_tensor(frac_out, n * n_rays * 4, 'frac_out')
+    ph = _out_tensor(hit_out, n * n_rays * 4, 'hit_out') if want_hit else None
+    po, pv = _out_tensor(origin_out, n * n_rays * 12, 'origin_out'), _out_tensor(vel_out, n * n_rays * 12, 'vel_out')
+    for t, what in ((origin_out, 'origin_out'), (vel_out, 'vel_out')):
+        if t is not None and t.dtype != torch.float32:
+            raise ValueError('%s must be float32' % what)
+    v = ctypes.c_void_p
+    _check(call(v(states.data_ptr()), v(levels.data_ptr()) if levels is not None else None, n, v(dirs.data_ptr()), n_rays,
+                ctypes.c_float(max_range), v(offsets.data_ptr()) if offsets is not None else None, n_obj, v(pf), v(ph), v(po), v(pv),
+                v(_stream_handle(stream))))
+    return (frac_out, hit_out) if want_hit else frac_out
+
+
 class World:
     """game::world::World on the host and the current device (rdoom_world_create): World::sweep_sphere for a batch of queries,
     Player::update for a batch of players."""
@@ -1104,6 +1165,24 @@ class World:
                                            int(a.n_ticks), a.cfg_ptr(), ctypes.c_float(dt), ctypes.c_void_p(_stream_handle(stream))))
         return a.result()
 
+    # ---- range-sensor rays -------------------------------------------------------------------------------------------------
+    def cast_rays(self, states, dirs, max_range, offsets=None, frac_out=None, hit_out=None, origin_out=None, vel_out=None, stream=None):
+        """rdoom_world_cast_rays: n_rays rays from every player's camera eye, along the player's rotation of the shared (n_rays, 3)
+        float32 direction table `dirs` (ray_fan), for `max_range`.  Tensors in, tensors out, all on the GPU; asynchronous on
+        `stream`, nothing is copied to the host.  states: the tensor a step leaves (n * 40 bytes); offsets: None or step_game's
+        (n, n_objects, 3) tensor.  Returns frac, a float32 (n, n_rays) tensor of fractions of max_range (+inf: nothing within
+        range), or (frac, hit) when hit_out is given (True: a new int32 (n, n_rays) tensor; RAY_NO_HIT as -1): the triangle hit, an
+        index into arrays()['triangles'] and triangle_objects().  frac_out / origin_out / vel_out: optional preallocated outputs
+        ((n, n_rays) and (n, n_rays, 3) float32); origin and vel are the rays as World.sweep takes them."""
+        L = lib()
+        return _cast_rays(lambda st, lv, *rest: L.rdoom_world_cast_rays(self._h, st, *rest), states, None, dirs, max_range, offsets,
+                          frac_out, hit_out, origin_out, vel_out, stream)
+
+    def triangle_objects(self):
+        """a host uint32 array with the object id of each triangle of arrays()['triangles']: 0 for the statics, the dynamic chunk's
+        object id for a door's or lift's -- triangle_objects()[hit] names what a ray of cast_rays ended on"""
+        return _triangle_objects(self.arrays())
+
 
 class WorldSetLevelInfo(ctypes.Structure):
     _fields_ = [('archive_index', ctypes.c_uint32), ('destination', ctypes.c_uint32), ('start_pos', ctypes.c_float * 3),
@@ -1205,3 +1284,16 @@ class WorldSet:
                                               ctypes.c_void_p(levels.data_ptr()), a.n, int(a.n_ticks), a.cfg_ptr(), ctypes.c_float(dt),
                                               ctypes.c_void_p(_stream_handle(stream))))
         return a.result()
+
+    def cast_rays(self, states, levels, dirs, max_range, offsets=None, frac_out=None, hit_out=None, origin_out=None, vel_out=None,
+                  stream=None):
+        """rdoom_worldset_cast_rays: World.cast_rays for players spread over the set's levels (levels: game_state's tensor of
+        slots).  A hit is an index into arrays(slot)['triangles'] of the player's slot; a player whose slot is not in the set gets
+        +inf / RAY_NO_HIT."""
+        L = lib()
+        return _cast_rays(lambda st, lv, *rest: L.rdoom_worldset_cast_rays(self._h, st, lv, *rest), states, levels, dirs, max_range,
+                          offsets, frac_out, hit_out, origin_out, vel_out, stream)
+
+    def triangle_objects(self, slot):
+        """World.triangle_objects of slot `slot`: the object id of each triangle of arrays(slot)['triangles']"""
+        return _triangle_objects(self.arrays(slot))

@@ -1,6 +1,7 @@
 // The collision world on the device: World::sweep_sphere (game/src/world.rs:40-120, math/src/sphere.rs:16-183) for a batch
 // of queries, and K ticks of Player::update (game/src/player.rs:142-408) for a batch of players in one launch, with the C ABI
 // of both (include/rdoom.h "collision world + player physics").  The host half, WorldBuilder, is csrc/host/game_world.cpp.
+// Also the range-sensor rays cast from player states (include/rdoom.h "ray casts"): cast_rays_kernel and its world-set form.
 //
 // Arithmetic: binary32 in the reference's operation order (cgmath: dot = (x x' + y y') + z z', cross component by component,
 // vector / scalar divides every component, normalize_or_zero = v / max(|v|, f32::EPSILON)); the build passes
@@ -714,6 +715,156 @@ __global__ __launch_bounds__(WAVE) void worldset_game_step_kernel(WorldView w, S
   step_players(w, states, inputs, set.gl.n, n_ticks, cfg, set.gl.dt, set.gl.offsets, set.gl.n_objects, set);
 }
 
+// ---- range-sensor rays from player states (include/rdoom.h "ray casts") ----
+// Ray (p, r) starts at player p's camera eye and runs along the player's rotation of the shared camera-frame direction r, for
+// max_range.  Against a triangle it is the plane branch of Sphere::sweep_triangle (sphere.rs:16-53) at radius 0 and nothing
+// else; through the world it is World::sweep_sphere at radius 0 (world.rs:40-82), and the result is that fold.  Nothing is
+// pruned: a ray visits exactly the nodes, chunks and triangles the radius-0 sweep visits, in its order.
+//
+// Shape: one lane per ray, flat index q = p * n_rays + r, so a wave holds the rays of one player or of a few neighbours and its
+// lanes walk nearly the same nodes and chunks.  The node stack is sweep_world's (LDS, word `slot * 64 + lane`).
+
+struct Quat {
+  float s, x, y, z;
+};
+// impl Mul<Vector3> for Quaternion (cgmath), as frames.hip's rotate
+__device__ __forceinline__ V3 rotate(Quat q, V3 v) {
+  const V3 qv = v3(q.x, q.y, q.z);
+  const V3 c = cross(qv, v);
+  const V3 tmp = v3(c.x + v.x * q.s, c.y + v.y * q.s, c.z + v.z * q.s);
+  const V3 c2 = cross(qv, tmp);
+  return v3(c2.x * 2.0f + v.x, c2.y * 2.0f + v.y, c2.z * 2.0f + v.z);
+}
+
+struct RayHit {
+  float time;
+  uint32_t tri;
+};
+
+// World::sweep_chunk for a ray: `speed` and `nvel` are the triangle test's own (the same expression for every triangle)
+__device__ __forceinline__ void cast_chunk(const WorldView &w, RayHit &first, uint32_t start, uint32_t end, V3 origin, V3 nvel, float speed) {
+  for (uint32_t i = start; i < end; i++) {
+    const uint4 t = w.tris[i];
+    const V3 normal = load3(w.verts + 3 * t.w);
+    const float normal_dot_nvel = dot(normal, nvel);
+    if (normal_dot_nvel >= 0.0f) continue;
+    const V3 t0 = load3(w.verts + 3 * t.x);
+    const float intercept = -dot(t0, normal);
+    const float signed_plane_distance = dot(origin, normal) + intercept;
+    if (signed_plane_distance < 0.0f) continue;
+    const float distance = -signed_plane_distance / normal_dot_nvel;
+    const V3 on_plane = origin + nvel * distance;
+    if (!inside_triangle(t0, load3(w.verts + 3 * t.y), load3(w.verts + 3 * t.z), on_plane)) continue;
+    const float time = distance / speed;
+    const bool keep = first.time < time;  // the later candidate on equal times
+    first.time = keep ? first.time : time;
+    first.tri = keep ? first.tri : i;
+  }
+}
+
+__device__ __forceinline__ RayHit cast_world(const WorldView &w, V3 origin, V3 vel, const float *offsets, uint32_t *stack, uint32_t root) {
+  RayHit first{__builtin_inff(), 0xFFFFFFFFu};
+  const float speed = magnitude(vel);
+  if (speed == 0.0f) return first;  // sweep_triangle returns None for every triangle
+  const V3 nvel = vel / speed;
+  const float tx = origin.x + vel.x, tz = origin.z + vel.z;
+  uint32_t sp = 1;
+  stack[0] = root;
+  while (sp) {  // Node::intersect_sphere with radius 0: positive child first; leaves are cast when met, nodes pushed
+    const DevNode node = w.nodes[stack[--sp * WAVE]];
+    const float dist1 = (origin.x * node.dy - origin.z * node.dx) + (node.dx * node.oy - node.dy * node.ox);
+    const float dist2 = (tx * node.dy - tz * node.dx) + (node.dx * node.oy - node.dy * node.ox);
+    const bool pos = dist1 >= -0.0f || dist2 >= -0.0f;
+    const bool neg = dist1 <= 0.0f || dist2 <= 0.0f;
+#pragma unroll
+    for (int k = 0; k < 2; k++) {
+      if (!(k == 0 ? pos : neg)) continue;
+      const int32_t packed = k == 0 ? node.positive : node.negative;
+      if (packed > 0) {
+        if (sp < w.stack_cap)  // (always: see WorldView::stack_cap; the test only keeps the LDS writes in bounds)
+          stack[sp++ * WAVE] = (uint32_t)packed;
+      } else {
+        const uint2 chunk = w.chunks[(uint32_t)(-packed)];
+        cast_chunk(w, first, chunk.x, chunk.y, origin, nvel, speed);
+      }
+    }
+  }
+  for (uint32_t d = 0; d < w.n_dynamics; d++) {
+    const DevDynamic dyn = w.dynamics[d];
+    V3 off = v3(0.0f, 0.0f, 0.0f);
+    if (offsets) off = load3(offsets + 3 * dyn.object_id);
+    cast_chunk(w, first, dyn.tri_start, dyn.tri_end, origin + (-off), nvel, speed);
+  }
+  return first;
+}
+
+struct RayArgs {
+  const rdoom_player_state *states;
+  const float *dirs;     // n_rays x xyz, camera frame
+  const float *offsets;  // n x n_objects x xyz, or null
+  float *frac;
+  uint32_t *hit;         // may be null, as origin and vel
+  float *origin, *vel;
+  uint32_t n_rays, n_objects, total;  // total = n * n_rays
+  float max_range;
+};
+
+// ray q of a.total through `w` from node `root`; hits are reported less `tri_start`
+__device__ __forceinline__ void cast_ray(const WorldView &w, const RayArgs &a, uint32_t q, uint32_t p, uint32_t root, uint32_t tri_start,
+                                         uint32_t *stack) {
+  const rdoom_player_state *st = a.states + p;
+  // Quaternion::from(Euler { x: pitch, y: yaw, z: 0 }) and the eye of player.concat(camera), as frames.hip's player_view
+  float sx, cx, sy, cy;
+  sincos_rd(st->pitch * 0.5f, sx, cx);
+  sincos_rd(st->yaw * 0.5f, sy, cy);
+  const float sz = 0.0f, cz = 1.0f;
+  const Quat player{-sx * sy * sz + cx * cy * cz, sx * cy * cz + sy * sz * cx, -sx * sz * cy + sy * cx * cz, sx * sy * cz + sz * cx * cy};
+  const V3 rc = rotate(player, v3(0.0f * 1.0f, 0.12f * 1.0f, 0.0f * 1.0f));
+  const V3 origin = v3(rc.x + st->pos[0], rc.y + st->pos[1], rc.z + st->pos[2]);
+  const V3 dir = rotate(player, load3(a.dirs + 3 * (size_t)(q - p * a.n_rays)));
+  const V3 vel = dir * a.max_range;
+  const RayHit h = cast_world(w, origin, vel, a.offsets ? a.offsets + (size_t)p * a.n_objects * 3 : nullptr, stack, root);
+  const bool in_range = h.time <= 1.0f;
+  a.frac[q] = in_range ? h.time : __builtin_inff();
+  if (a.hit) a.hit[q] = in_range ? h.tri - tri_start : 0xFFFFFFFFu;
+  if (a.origin) a.origin[3 * (size_t)q] = origin.x, a.origin[3 * (size_t)q + 1] = origin.y, a.origin[3 * (size_t)q + 2] = origin.z;
+  if (a.vel) a.vel[3 * (size_t)q] = vel.x, a.vel[3 * (size_t)q + 1] = vel.y, a.vel[3 * (size_t)q + 2] = vel.z;
+}
+
+__global__ __launch_bounds__(WAVE) void cast_rays_kernel(WorldView w, RayArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+  const uint32_t q = blockIdx.x * WAVE + threadIdx.x;
+  if (q >= a.total) return;
+  cast_ray(w, a, q, q / a.n_rays, 0u, 0u, lds_stack + threadIdx.x);
+}
+
+// the world set's: player p's rays run through level level_of[p]; a slot outside the set gives +inf / no hit, nothing else
+// tri_starts: each level's first triangle in the concatenation (a hit is reported in the level's own indices)
+__global__ __launch_bounds__(WAVE) void worldset_cast_rays_kernel(WorldView w, RayArgs a, const DevSetLevel *__restrict__ levels,
+                                                                  const uint32_t *__restrict__ tri_starts,
+                                                                  const uint32_t *__restrict__ level_of, uint32_t n_levels) {
+  extern __shared__ __attribute__((aligned(16))) uint32_t lds_stack[];
+  const uint32_t q = blockIdx.x * WAVE + threadIdx.x;
+  if (q >= a.total) return;
+  const uint32_t p = q / a.n_rays;
+  const uint32_t lv = level_of[p];
+  if (lv >= n_levels) {
+    a.frac[q] = __builtin_inff();
+    if (a.hit) a.hit[q] = 0xFFFFFFFFu;
+    return;
+  }
+  const uint32_t u = __builtin_amdgcn_readfirstlane(lv);
+  uint32_t root, dyn_start, n_dyn, tri_start;
+  if (__builtin_amdgcn_ballot_w64(lv != u) == 0) {  // one level in the wave (always, when n_rays is a multiple of 64): scalar loads
+    root = levels[u].root, dyn_start = levels[u].dyn_start, n_dyn = levels[u].n_dynamics, tri_start = tri_starts[u];
+  } else {
+    root = levels[lv].root, dyn_start = levels[lv].dyn_start, n_dyn = levels[lv].n_dynamics, tri_start = tri_starts[lv];
+  }
+  const WorldView wl{w.nodes, w.chunks, w.tris, w.verts, w.dynamics + dyn_start, n_dyn, w.stack_cap};
+  cast_ray(wl, a, q, p, root, tri_start, lds_stack + threadIdx.x);
+}
+
+// (defined last: the code object's final kernel, as before the ray casts)
 // a fresh game of its current level for player blockIdx.x (if masked in and on a slot): one workgroup per game
 __global__ __launch_bounds__(WAVE) void worldset_game_reset_kernel(const DevSetLevel *__restrict__ levels, uint32_t n_levels,
                                                                    uint32_t words, uint32_t *games, float *offsets, uint32_t n_objects,
@@ -804,6 +955,7 @@ struct rdoom_worldset {
   int device = -1;
   DevArrays d;
   DevSetLevel *d_table = nullptr;
+  uint32_t *d_tri_starts = nullptr;  // each level's triangle base in the concatenation (the ray cast's)
 };
 
 namespace {
@@ -918,6 +1070,21 @@ GameLevel game_level(const GameView &g, void *d_game, float *d_offsets, const ui
   level.n = n_players, level.n_objects = n_objects;
   level.dt = dt;
   return level;
+}
+// the arguments of a ray cast, checked, as the kernel takes them.  world_objects: the world's (or the set's) collision objects
+rdoom_status ray_args(const rdoom_player_state *d_states, uint32_t n, const float *d_dirs, uint32_t n_rays, float max_range,
+                      const float *d_offsets, uint32_t n_objects, uint32_t world_objects, const char *noun, float *d_frac, uint32_t *d_hit,
+                      float *d_origin, float *d_vel, RayArgs &a) {
+  if (n_rays == 0) return rdoom::fail(RDOOM_BAD_ARG, "n_rays is 0");
+  if (!(max_range > 0.0f) || max_range == __builtin_inff())
+    return rdoom::fail(RDOOM_BAD_ARG, "max_range %g is not a finite positive number", (double)max_range);
+  if (!d_dirs) return rdoom::fail(RDOOM_BAD_ARG, "null ray directions");
+  if (n && (!d_states || !d_frac)) return rdoom::fail(RDOOM_BAD_ARG, "null states or fraction output with n = %u", n);
+  if (d_offsets && n_objects < world_objects)
+    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the %s's %u objects", n_objects, noun, world_objects);
+  if ((uint64_t)n * n_rays > 0xFFFFFFFFull - WAVE) return rdoom::fail(RDOOM_BAD_ARG, "%u players x %u rays: too many for one launch", n, n_rays);
+  a = RayArgs{d_states, d_dirs, d_offsets, d_frac, d_hit, d_origin, d_vel, n_rays, n_objects, n * n_rays, max_range};
+  return RDOOM_OK;
 }
 }  // namespace
 
@@ -1038,6 +1205,7 @@ void rdoom_worldset_destroy(rdoom_worldset *s) {
   if (!s) return;
   free_world(s->d);
   if (s->d_table) (void)hipFree(s->d_table);
+  if (s->d_tri_starts) (void)hipFree(s->d_tri_starts);
   delete s;
 }
 
@@ -1072,6 +1240,9 @@ rdoom_status rdoom_worldset_create(const rdoom_wad *wad, const uint32_t *level_i
     HIP_TRY(hipGetDevice(&s->device));
     if (rdoom_status st = upload_world(h.all, s->d)) return st;
     if (rdoom_status st = upload(&s->d_table, s->table.data(), s->table.size() * sizeof(DevSetLevel))) return st;
+    std::vector<uint32_t> tri_starts;
+    for (const rdoom::game::WorldSetLevel &t : h.table) tri_starts.push_back(t.triangle_base);
+    if (rdoom_status st = upload(&s->d_tri_starts, tri_starts.data(), tri_starts.size() * sizeof(uint32_t))) return st;
     s->on_device = true;
   }
   *out_set = s.release();
@@ -1138,6 +1309,42 @@ rdoom_status rdoom_worldset_step_game(const rdoom_worldset *s, rdoom_player_stat
   set.n_levels = (uint32_t)s->table.size();
   hipLaunchKernelGGL(worldset_game_step_kernel, dim3((n_players + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
                      (hipStream_t)stream, v, set, s->d.triggers, s->d.effects, s->d_table, d_states, d_inputs, n_ticks, c);
+  HIP_TRY(hipGetLastError());
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_world_cast_rays(const rdoom_world *w, const rdoom_player_state *d_states, uint32_t n, const float *d_dirs,
+                                   uint32_t n_rays, float max_range, const float *d_object_offsets, uint32_t n_objects,
+                                   float *d_frac_out, uint32_t *d_hit_out, float *d_origin_out, float *d_vel_out, void *stream) {
+  if (!w) return rdoom::fail(RDOOM_BAD_ARG, "null world");
+  RayArgs a;
+  if (rdoom_status s = ray_args(d_states, n, d_dirs, n_rays, max_range, d_object_offsets, n_objects, w->host.n_objects, "world", d_frac_out,
+                                d_hit_out, d_origin_out, d_vel_out, a))
+    return s;
+  if (rdoom_status s = check_device(w, "the world")) return s;
+  if (!n) return RDOOM_OK;
+  const WorldView v = view(w->d, (uint32_t)w->host.dynamics.size(), w->host.node_depth);
+  hipLaunchKernelGGL(cast_rays_kernel, dim3((a.total + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
+                     (hipStream_t)stream, v, a);
+  HIP_TRY(hipGetLastError());
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_worldset_cast_rays(const rdoom_worldset *s, const rdoom_player_state *d_states, const uint32_t *d_levels, uint32_t n,
+                                      const float *d_dirs, uint32_t n_rays, float max_range, const float *d_object_offsets,
+                                      uint32_t n_objects, float *d_frac_out, uint32_t *d_hit_out, float *d_origin_out, float *d_vel_out,
+                                      void *stream) {
+  if (!s) return rdoom::fail(RDOOM_BAD_ARG, "null world set");
+  if (n && !d_levels) return rdoom::fail(RDOOM_BAD_ARG, "null levels with n = %u", n);
+  RayArgs a;
+  if (rdoom_status st = ray_args(d_states, n, d_dirs, n_rays, max_range, d_object_offsets, n_objects, s->host.all.n_objects, "world set",
+                                 d_frac_out, d_hit_out, d_origin_out, d_vel_out, a))
+    return st;
+  if (rdoom_status st = check_device(s, "the world set")) return st;
+  if (!n) return RDOOM_OK;
+  const WorldView v = view(s->d, 0u, s->host.node_depth);
+  hipLaunchKernelGGL(worldset_cast_rays_kernel, dim3((a.total + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
+                     (hipStream_t)stream, v, a, s->d_table, s->d_tri_starts, d_levels, (uint32_t)s->table.size());
   HIP_TRY(hipGetLastError());
   return RDOOM_OK;
 }
