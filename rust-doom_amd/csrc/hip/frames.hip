@@ -16,7 +16,7 @@
 #include <cstring>
 
 #include "kernels.hpp"
-#include "sincos_rd.hpp"
+#include "player_quat.hpp"
 
 #pragma clang fp contract(off)
 
@@ -25,44 +25,19 @@ namespace {
 
 constexpr uint32_t WAVE = 64;
 
-struct Quat {
-  float s, x, y, z;
-};
-struct V3 {
-  float x, y, z;
-};
 struct View {  // Decomposed { scale s, rot r, disp d }
   float s;
   Quat r;
   V3 d;
 };
 
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-__device__ __forceinline__ V3 rotate(Quat q, V3 v) {  // impl Mul<Vector3> for Quaternion
-  const V3 qv{q.x, q.y, q.z};
-  const V3 c = cross(qv, v);
-  const V3 tmp{c.x + v.x * q.s, c.y + v.y * q.s, c.z + v.z * q.s};
-  const V3 c2 = cross(qv, tmp);
-  return {c2.x * 2.0f + v.x, c2.y * 2.0f + v.y, c2.z * 2.0f + v.z};
-}
-__device__ __forceinline__ Quat qmul(Quat a, Quat b) {  // impl Mul for Quaternion
-  return {a.s * b.s - a.x * b.x - a.y * b.y - a.z * b.z, a.s * b.x + a.x * b.s + a.y * b.z - a.z * b.y,
-          a.s * b.y + a.y * b.s + a.z * b.x - a.x * b.z, a.s * b.z + a.z * b.s + a.x * b.y - a.y * b.x};
-}
-
-// api_common.cpp player_view: (player.concat(camera)).inverse_transform(), sin / cos from sincos_rd
+// api_common.cpp player_view: (player.concat(camera)).inverse_transform(), orientation and eye from player_quat.hpp
 __device__ __forceinline__ View player_view(float px, float py, float pz, float yaw, float pitch) {
-  float sx, cx, sy, cy;
-  sincos_rd(pitch * 0.5f, sx, cx);
-  sincos_rd(yaw * 0.5f, sy, cy);
-  const float sz = 0.0f, cz = 1.0f;  // (sinf / cosf of 0 * 0.5: exact on every implementation)
-  const Quat player{-sx * sy * sz + cx * cy * cz, sx * cy * cz + sy * sz * cx, -sx * sz * cy + sy * cx * cz, sx * sy * cz + sz * cx * cy};
+  const Quat player = player_orientation(yaw, pitch);
   const Quat identity{1.0f, 0.0f, 0.0f, 0.0f};
   const float scale = 1.0f * 1.0f;
   const Quat rot = qmul(player, identity);
-  const V3 cam{0.0f * 1.0f, 0.12f * 1.0f, 0.0f * 1.0f};
-  const V3 rc = rotate(player, cam);
-  const V3 disp{rc.x + px, rc.y + py, rc.z + pz};
+  const V3 disp = player_eye(player, V3{px, py, pz});
   const float s = 1.0f / scale;
   const float vv = (rot.x * rot.x + rot.y * rot.y) + rot.z * rot.z;
   const float mag2 = rot.s * rot.s + vv;

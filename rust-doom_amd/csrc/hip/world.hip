@@ -6,7 +6,8 @@
 // Arithmetic: binary32 in the reference's operation order (cgmath: dot = (x x' + y y') + z z', cross component by component,
 // vector / scalar divides every component, normalize_or_zero = v / max(|v|, f32::EPSILON)); the build passes
 // -ffp-contract=off and HIP divides and takes square roots correctly rounded, so every result is the one an IEEE host
-// computes with the same expressions.  No fastmath.hpp short forms, no device libm: sin / cos come from sincos_rd (sincos_rd.hpp).
+// computes with the same expressions.  No fastmath.hpp short forms, no device libm: sin / cos come from sincos_rd (sincos_rd.hpp),
+// a player's orientation quaternion and camera eye from player_quat.hpp.
 //
 // Shape: one lane per query / player -- the sweeps of one player are strictly sequential -- and one wave per workgroup.  Each
 // lane walks the BSP with its own node stack in LDS (word `slot * 64 + lane`: no bank conflicts), sized by the tree's depth at
@@ -20,7 +21,7 @@
 #include "../common.hpp"
 #include "../host/game_world.hpp"
 #include "kernels.hpp"
-#include "sincos_rd.hpp"
+#include "player_quat.hpp"
 
 namespace {
 
@@ -45,9 +46,14 @@ struct WorldView {
                        // per level above the deepest, two at the deepest
 };
 
-struct V3 {
-  float x, y, z;
-};
+// V3, Quat, cross and rotate are player_quat.hpp's (shared with the player cameras of frames.hip); the operators are the world's
+using rdoom_dev::cross;
+using rdoom_dev::player_eye;
+using rdoom_dev::player_orientation;
+using rdoom_dev::Quat;
+using rdoom_dev::rotate;
+using rdoom_dev::sincos_rd;
+using rdoom_dev::V3;
 __device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
 __device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
@@ -55,7 +61,6 @@ __device__ __forceinline__ V3 operator-(V3 a) { return v3(-a.x, -a.y, -a.z); }
 __device__ __forceinline__ V3 operator*(V3 a, float s) { return v3(a.x * s, a.y * s, a.z * s); }
 __device__ __forceinline__ V3 operator/(V3 a, float s) { return v3(a.x / s, a.y / s, a.z / s); }
 __device__ __forceinline__ float dot(V3 a, V3 b) { return (a.x * b.x + a.y * b.y) + a.z * b.z; }
-__device__ __forceinline__ V3 cross(V3 a, V3 b) { return v3(a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x); }
 __device__ __forceinline__ float magnitude(V3 a) { return __builtin_sqrtf(dot(a, a)); }
 __device__ __forceinline__ V3 normalize_or_zero(V3 a) {  // math/src/lib.rs:40-42 (f32::max: the other operand when one is NaN)
   const float m = magnitude(a);
@@ -236,8 +241,6 @@ __device__ __forceinline__ Contact sweep_world(const WorldView &w, V3 center, fl
   }
   return first;
 }
-
-using rdoom_dev::sincos_rd;  // (sincos_rd.hpp: shared with the player cameras of frames.hip)
 
 __global__ __launch_bounds__(WAVE) void sweep_kernel(WorldView w, const float *spheres, const float *vels, uint32_t n,
                                                      const float *offsets, uint32_t n_objects, float *out) {
@@ -527,17 +530,8 @@ struct GameLevel : NoGame {
     uint32_t action = actions ? actions[(size_t)t * n + lane] : 0u;
     action = action <= RDOOM_ACTION_SHOOT ? action : RDOOM_ACTION_NONE;
     Line2 act{pos.x, pos.z, 0.0f, 0.0f, 0.0f};
-    if (action) {  // look = rot.rotate_vector(-z), rot = Quaternion::from(Euler { pitch, yaw, 0 }) (api_common.cpp's cgmath formulas)
-      float sx, cx, sy, cy;
-      sincos_rd(pitch * 0.5f, sx, cx);
-      sincos_rd(yaw * 0.5f, sy, cy);
-      const float sz = 0.0f, cz = 1.0f;
-      const float qs = -sx * sy * sz + cx * cy * cz, qx = sx * cy * cz + sy * sz * cx, qy = -sx * sz * cy + sy * cx * cz,
-                  qz = sx * sy * cz + sz * cx * cy;
-      const V3 qv = v3(qx, qy, qz), v = v3(-0.0f, -0.0f, -1.0f);
-      const V3 tmp = cross(qv, v) + v * qs;
-      const V3 c2 = cross(qv, tmp);
-      const V3 look = v3(c2.x * 2.0f + v.x, c2.y * 2.0f + v.y, c2.z * 2.0f + v.z);
+    if (action) {  // look = rot.rotate_vector(-z), rot = Quaternion::from(Euler { pitch, yaw, 0 })
+      const V3 look = rotate(player_orientation(yaw, pitch), v3(-0.0f, -0.0f, -1.0f));
       const float m = __builtin_sqrtf(look.x * look.x + look.z * look.z);
       const float d = m > 1.1920929e-7f ? m : 1.1920929e-7f;
       const float range = action == RDOOM_ACTION_PUSH ? 0.5f : 100.0f;
@@ -638,6 +632,19 @@ __device__ __forceinline__ GameView level_view(const GameView &set, const DevSet
 // requests the next level and still runs in the old one (STAGE_REQUESTED); tick t + 2 loads it, resets the player and runs in it.
 constexpr uint32_t STAGE_NONE = 0u, STAGE_EXITED = 1u, STAGE_REQUESTED = 2u;
 
+// `use(slot)` for the level record of a lane on level `lv`: the wave's one slot as a wave-uniform value when every lane of the
+// wave is on the same level, so that what `use` loads from that record are scalar loads; the lane's own otherwise
+template <class Use>
+__device__ __forceinline__ void with_level(uint32_t lv, Use use) {
+  const uint32_t u = __builtin_amdgcn_readfirstlane(lv);
+  if (__builtin_amdgcn_ballot_w64(lv != u) == 0) use(u);
+  else use(lv);
+}
+// the set's world seen from one level: its own dynamic chunks (its nodes start at the level's root)
+__device__ __forceinline__ WorldView level_world(const WorldView &w, uint32_t dyn_start, uint32_t n_dynamics) {
+  return WorldView{w.nodes, w.chunks, w.tris, w.verts, w.dynamics + dyn_start, n_dynamics, w.stack_cap};
+}
+
 // A player's game in a world set: GameLevel's effects and triggers on the player's current level, and the level change.
 struct SetGame {
   GameLevel gl;                // games, offsets, actions, n, dt; gl.n_objects and gl.g.words are the set's, gl.g.triggers /
@@ -679,22 +686,16 @@ struct SetGame {
   }
   __device__ __forceinline__ V3 start_pos() const { return load3(levels[lv].start); }
   __device__ __forceinline__ float start_yaw() const { return levels[lv].start_yaw; }
-  __device__ __forceinline__ WorldView world(const WorldView &w) const {
-    return WorldView{w.nodes, w.chunks, w.tris, w.verts, w.dynamics + dyn_start, n_dyn, w.stack_cap};
-  }
+  __device__ __forceinline__ WorldView world(const WorldView &w) const { return level_world(w, dyn_start, n_dyn); }
   __device__ __forceinline__ uint32_t root() const { return root_; }
 
   __device__ __forceinline__ void tick(uint32_t t, V3 pos, V3 vel, float yaw, float pitch, uint32_t &flags) {
     uint32_t fired = 0u;
     GameLevel l = gl;
-    const uint32_t u = __builtin_amdgcn_readfirstlane(lv);
-    if (__builtin_amdgcn_ballot_w64(lv != u) == 0) {  // one level in the wave: its trigger loads stay scalar
-      l.g = level_view(gl.g, levels[u]);
+    with_level(lv, [&](uint32_t slot) __attribute__((always_inline)) {  // (one level in the wave: its trigger loads stay scalar)
+      l.g = level_view(gl.g, levels[slot]);
       l.tick(t, pos, vel, yaw, pitch, fired);
-    } else {
-      l.g = level_view(gl.g, levels[lv]);
-      l.tick(t, pos, vel, yaw, pitch, fired);
-    }
+    });
     flags |= fired;
     // an exit with a destination starts the change; one fired while a change is under way is lost with the rebuilt Level
     if ((fired & RDOOM_PLAYER_EXITED) && stage == STAGE_NONE && levels[lv].destination < n_levels) {
@@ -723,18 +724,6 @@ __global__ __launch_bounds__(WAVE) void worldset_game_step_kernel(WorldView w, S
 //
 // Shape: one lane per ray, flat index q = p * n_rays + r, so a wave holds the rays of one player or of a few neighbours and its
 // lanes walk nearly the same nodes and chunks.  The node stack is sweep_world's (LDS, word `slot * 64 + lane`).
-
-struct Quat {
-  float s, x, y, z;
-};
-// impl Mul<Vector3> for Quaternion (cgmath), as frames.hip's rotate
-__device__ __forceinline__ V3 rotate(Quat q, V3 v) {
-  const V3 qv = v3(q.x, q.y, q.z);
-  const V3 c = cross(qv, v);
-  const V3 tmp = v3(c.x + v.x * q.s, c.y + v.y * q.s, c.z + v.z * q.s);
-  const V3 c2 = cross(qv, tmp);
-  return v3(c2.x * 2.0f + v.x, c2.y * 2.0f + v.y, c2.z * 2.0f + v.z);
-}
 
 struct RayHit {
   float time;
@@ -813,14 +802,8 @@ struct RayArgs {
 __device__ __forceinline__ void cast_ray(const WorldView &w, const RayArgs &a, uint32_t q, uint32_t p, uint32_t root, uint32_t tri_start,
                                          uint32_t *stack) {
   const rdoom_player_state *st = a.states + p;
-  // Quaternion::from(Euler { x: pitch, y: yaw, z: 0 }) and the eye of player.concat(camera), as frames.hip's player_view
-  float sx, cx, sy, cy;
-  sincos_rd(st->pitch * 0.5f, sx, cx);
-  sincos_rd(st->yaw * 0.5f, sy, cy);
-  const float sz = 0.0f, cz = 1.0f;
-  const Quat player{-sx * sy * sz + cx * cy * cz, sx * cy * cz + sy * sz * cx, -sx * sz * cy + sy * cx * cz, sx * sy * cz + sz * cx * cy};
-  const V3 rc = rotate(player, v3(0.0f * 1.0f, 0.12f * 1.0f, 0.0f * 1.0f));
-  const V3 origin = v3(rc.x + st->pos[0], rc.y + st->pos[1], rc.z + st->pos[2]);
+  const Quat player = player_orientation(st->yaw, st->pitch);
+  const V3 origin = player_eye(player, load3(st->pos));
   const V3 dir = rotate(player, load3(a.dirs + 3 * (size_t)(q - p * a.n_rays)));
   const V3 vel = dir * a.max_range;
   const RayHit h = cast_world(w, origin, vel, a.offsets ? a.offsets + (size_t)p * a.n_objects * 3 : nullptr, stack, root);
@@ -853,15 +836,11 @@ __global__ __launch_bounds__(WAVE) void worldset_cast_rays_kernel(WorldView w, R
     if (a.hit) a.hit[q] = 0xFFFFFFFFu;
     return;
   }
-  const uint32_t u = __builtin_amdgcn_readfirstlane(lv);
   uint32_t root, dyn_start, n_dyn, tri_start;
-  if (__builtin_amdgcn_ballot_w64(lv != u) == 0) {  // one level in the wave (always, when n_rays is a multiple of 64): scalar loads
-    root = levels[u].root, dyn_start = levels[u].dyn_start, n_dyn = levels[u].n_dynamics, tri_start = tri_starts[u];
-  } else {
-    root = levels[lv].root, dyn_start = levels[lv].dyn_start, n_dyn = levels[lv].n_dynamics, tri_start = tri_starts[lv];
-  }
-  const WorldView wl{w.nodes, w.chunks, w.tris, w.verts, w.dynamics + dyn_start, n_dyn, w.stack_cap};
-  cast_ray(wl, a, q, p, root, tri_start, lds_stack + threadIdx.x);
+  with_level(lv, [&](uint32_t slot) __attribute__((always_inline)) {  // (one level in the wave always, when n_rays is a multiple of 64)
+    root = levels[slot].root, dyn_start = levels[slot].dyn_start, n_dyn = levels[slot].n_dynamics, tri_start = tri_starts[slot];
+  });
+  cast_ray(level_world(w, dyn_start, n_dyn), a, q, p, root, tri_start, lds_stack + threadIdx.x);
 }
 
 // (defined last: the code object's final kernel, as before the ray casts)
@@ -1004,6 +983,15 @@ WorldView view(const DevArrays &d, uint32_t n_dynamics, uint32_t node_depth) {
   return WorldView{d.nodes, d.chunks, d.tris, d.verts, d.dynamics, n_dynamics, node_depth + 1};
 }
 
+// kernel(v, args...) with one lane per query, player or ray: one wave per workgroup, each lane's node stack in LDS
+template <class Kernel, class... Args>
+rdoom_status launch_lanes(Kernel kernel, uint32_t n_lanes, const WorldView &v, void *stream, Args... args) {
+  hipLaunchKernelGGL(kernel, dim3((n_lanes + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t), (hipStream_t)stream, v,
+                     args...);
+  HIP_TRY(hipGetLastError());
+  return RDOOM_OK;
+}
+
 // noun: "the world" or "the world set"
 template <class Handle>
 rdoom_status check_device(const Handle *h, const char *noun) {
@@ -1131,11 +1119,8 @@ rdoom_status rdoom_world_sweep(const rdoom_world *w, const float *d_spheres, con
   if (rdoom_status s = check_offsets(w, d_object_offsets, n_objects)) return s;
   if (rdoom_status s = check_device(w, "the world")) return s;
   if (!n) return RDOOM_OK;
-  const WorldView v = view(w->d, (uint32_t)w->host.dynamics.size(), w->host.node_depth);
-  hipLaunchKernelGGL(sweep_kernel, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t), (hipStream_t)stream, v,
-                     d_spheres, d_vels, n, d_object_offsets, n_objects, d_out);
-  HIP_TRY(hipGetLastError());
-  return RDOOM_OK;
+  return launch_lanes(sweep_kernel, n, view(w->d, (uint32_t)w->host.dynamics.size(), w->host.node_depth), stream, d_spheres, d_vels, n,
+                      d_object_offsets, n_objects, d_out);
 }
 
 rdoom_status rdoom_player_config_default(rdoom_player_config *out) {
@@ -1153,11 +1138,8 @@ rdoom_status rdoom_world_step_players(const rdoom_world *w, rdoom_player_state *
   if (rdoom_status s = check_offsets(w, d_object_offsets, n_objects)) return s;
   if (rdoom_status s = check_device(w, "the world")) return s;
   if (!n_players || !n_ticks) return RDOOM_OK;
-  const WorldView v = view(w->d, (uint32_t)w->host.dynamics.size(), w->host.node_depth);
-  hipLaunchKernelGGL(player_step_kernel, dim3((n_players + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
-                     (hipStream_t)stream, v, d_states, d_inputs, n_players, n_ticks, c, dt, d_object_offsets, n_objects);
-  HIP_TRY(hipGetLastError());
-  return RDOOM_OK;
+  return launch_lanes(player_step_kernel, n_players, view(w->d, (uint32_t)w->host.dynamics.size(), w->host.node_depth), stream, d_states,
+                      d_inputs, n_players, n_ticks, c, dt, d_object_offsets, n_objects);
 }
 
 rdoom_status rdoom_world_triggers(const rdoom_world *w, rdoom_world_trigger_arrays *out) {
@@ -1193,12 +1175,9 @@ rdoom_status rdoom_world_step_game(const rdoom_world *w, rdoom_player_state *d_s
   if (rdoom_status s = check_game(false, w->host.game_objects, d_game, d_object_offsets, n_objects, nullptr)) return s;
   if (rdoom_status s = check_device(w, "the world")) return s;
   if (!n_players || !n_ticks) return RDOOM_OK;
-  const WorldView v = view(w->d, (uint32_t)w->host.dynamics.size(), w->host.node_depth);
   const GameLevel level = game_level(game_view(w), d_game, d_object_offsets, d_actions, n_players, n_objects, dt);
-  hipLaunchKernelGGL(game_step_kernel, dim3((n_players + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
-                     (hipStream_t)stream, v, level, level.g.triggers, level.g.effects, d_states, d_inputs, n_ticks, c);
-  HIP_TRY(hipGetLastError());
-  return RDOOM_OK;
+  return launch_lanes(game_step_kernel, n_players, view(w->d, (uint32_t)w->host.dynamics.size(), w->host.node_depth), stream, level,
+                      level.g.triggers, level.g.effects, d_states, d_inputs, n_ticks, c);
 }
 
 void rdoom_worldset_destroy(rdoom_worldset *s) {
@@ -1301,16 +1280,13 @@ rdoom_status rdoom_worldset_step_game(const rdoom_worldset *s, rdoom_player_stat
   if (rdoom_status st = check_game(true, s->host.game_objects, d_game, d_object_offsets, n_objects, d_levels)) return st;
   if (rdoom_status st = check_device(s, "the world set")) return st;
   if (!n_players || !n_ticks) return RDOOM_OK;
-  const WorldView v = view(s->d, 0u, s->host.node_depth);
   SetGame set{};
   set.gl = game_level(GameView{s->d.triggers, s->d.effects, 0, s->host.game_objects, 0, 0, 0, 0, 0, 0, s->words}, d_game,
                       d_object_offsets, d_actions, n_players, n_objects, dt);
   set.level_of = d_levels;
   set.n_levels = (uint32_t)s->table.size();
-  hipLaunchKernelGGL(worldset_game_step_kernel, dim3((n_players + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
-                     (hipStream_t)stream, v, set, s->d.triggers, s->d.effects, s->d_table, d_states, d_inputs, n_ticks, c);
-  HIP_TRY(hipGetLastError());
-  return RDOOM_OK;
+  return launch_lanes(worldset_game_step_kernel, n_players, view(s->d, 0u, s->host.node_depth), stream, set, s->d.triggers, s->d.effects,
+                      s->d_table, d_states, d_inputs, n_ticks, c);
 }
 
 rdoom_status rdoom_world_cast_rays(const rdoom_world *w, const rdoom_player_state *d_states, uint32_t n, const float *d_dirs,
@@ -1323,11 +1299,7 @@ rdoom_status rdoom_world_cast_rays(const rdoom_world *w, const rdoom_player_stat
     return s;
   if (rdoom_status s = check_device(w, "the world")) return s;
   if (!n) return RDOOM_OK;
-  const WorldView v = view(w->d, (uint32_t)w->host.dynamics.size(), w->host.node_depth);
-  hipLaunchKernelGGL(cast_rays_kernel, dim3((a.total + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
-                     (hipStream_t)stream, v, a);
-  HIP_TRY(hipGetLastError());
-  return RDOOM_OK;
+  return launch_lanes(cast_rays_kernel, a.total, view(w->d, (uint32_t)w->host.dynamics.size(), w->host.node_depth), stream, a);
 }
 
 rdoom_status rdoom_worldset_cast_rays(const rdoom_worldset *s, const rdoom_player_state *d_states, const uint32_t *d_levels, uint32_t n,
@@ -1342,11 +1314,8 @@ rdoom_status rdoom_worldset_cast_rays(const rdoom_worldset *s, const rdoom_playe
     return st;
   if (rdoom_status st = check_device(s, "the world set")) return st;
   if (!n) return RDOOM_OK;
-  const WorldView v = view(s->d, 0u, s->host.node_depth);
-  hipLaunchKernelGGL(worldset_cast_rays_kernel, dim3((a.total + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t),
-                     (hipStream_t)stream, v, a, s->d_table, s->d_tri_starts, d_levels, (uint32_t)s->table.size());
-  HIP_TRY(hipGetLastError());
-  return RDOOM_OK;
+  return launch_lanes(worldset_cast_rays_kernel, a.total, view(s->d, 0u, s->host.node_depth), stream, a, s->d_table, s->d_tri_starts, d_levels,
+                      (uint32_t)s->table.size());
 }
 
 }  // extern "C"

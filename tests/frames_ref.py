@@ -2,40 +2,24 @@
 compiled with gcc -O2 -ffp-contract=off -fno-fast-math and loaded through ctypes, like tests/world_ref.py."""
 import ctypes
 import os
-import subprocess
-import tempfile
 import threading
 
 import numpy as np
 
 import rust_doom_amd as rd
+from util import restatement_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, 'frames_restatement.c')
-DEPS = [SRC, os.path.join(HERE, 'world_restatement.c')]
 _lib = None
 _lock = threading.Lock()
-
-
-def _compile(out):
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    tmp = '%s.%d.tmp' % (out, os.getpid())
-    subprocess.check_call(['gcc', '-shared', '-fPIC', '-O2', '-ffp-contract=off', '-fno-fast-math', '-I', HERE, '-o', tmp, SRC, '-lm'])
-    os.replace(tmp, out)
 
 
 def lib():
     global _lib
     with _lock:
         if _lib is None:
-            out = os.path.join(HERE, '_build', 'libframes_restatement.so')
-            if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in DEPS):
-                try:
-                    _compile(out)
-                except OSError:  # a read-only checkout
-                    out = os.path.join(tempfile.mkdtemp(prefix='frames_restatement_'), 'libframes_restatement.so')
-                    _compile(out)
-            L = ctypes.CDLL(out)
+            L = restatement_lib(SRC, [os.path.join(HERE, 'world_restatement.c')])
             L.fr_cameras.restype = None
             L.fr_cameras.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint32,
                                      ctypes.c_void_p, ctypes.c_void_p]

@@ -4,8 +4,6 @@ from oracle.wad_oracle's level reader and metadata (wad/src/visitor.rs:341-500) 
 import ctypes
 import os
 import struct
-import subprocess
-import tempfile
 import threading
 
 import numpy as np
@@ -13,6 +11,7 @@ import numpy as np
 import rust_doom_amd as rd
 import world_ref
 from oracle import wad_oracle as wo
+from util import restatement_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, 'game_restatement.c')
@@ -23,27 +22,12 @@ TYPES = {'WalkOver': rd.TRIGGER_WALK_OVER, 'Push': rd.TRIGGER_PUSH, 'Switch': rd
          'Any': rd.TRIGGER_ANY}
 
 
-def _compile(out):
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    tmp = '%s.%d.tmp' % (out, os.getpid())
-    subprocess.check_call(['gcc', '-shared', '-fPIC', '-O2', '-ffp-contract=off', '-fno-fast-math', '-I', HERE, '-o', tmp, SRC, '-lm'])
-    os.replace(tmp, out)
-
-
 def lib():
-    """the restatement as a shared library: tests/_build/ when it is writable, else a temporary directory"""
+    """the restatement as a shared library, its prototypes declared"""
     global _lib
     with _lock:
         if _lib is None:
-            out = os.path.join(HERE, '_build', 'libgame_restatement.so')
-            newest = max(os.path.getmtime(SRC), os.path.getmtime(world_ref.SRC))
-            if not os.path.exists(out) or os.path.getmtime(out) < newest:
-                try:
-                    _compile(out)
-                except OSError:  # a read-only checkout
-                    out = os.path.join(tempfile.mkdtemp(prefix='game_restatement_'), 'libgame_restatement.so')
-                    _compile(out)
-            L = ctypes.CDLL(out)
+            L = restatement_lib(SRC, [world_ref.SRC])
             L.rs_game_step.restype = None
             L.rs_game_step.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_uint32] + [ctypes.c_void_p] * 4 + [ctypes.c_uint32] * 4 + \
                 [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 4

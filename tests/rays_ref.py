@@ -3,43 +3,27 @@ world_restatement.c's world and traversal, with a camera eye and quaternion of i
 (gcc -O2 -ffp-contract=off -fno-fast-math) and loaded through ctypes."""
 import ctypes
 import os
-import subprocess
-import tempfile
 import threading
 
 import numpy as np
 
 import rust_doom_amd as rd
 import world_ref
+from util import restatement_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, 'rays_restatement.c')
-DEPS = [SRC, world_ref.SRC]
 NO_HIT = 0xFFFFFFFF
 _lib = None
 _lock = threading.Lock()
 
 
-def _compile(out):
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    tmp = '%s.%d.tmp' % (out, os.getpid())
-    subprocess.check_call(['gcc', '-shared', '-fPIC', '-O2', '-ffp-contract=off', '-fno-fast-math', '-I', HERE, '-o', tmp, SRC, '-lm'])
-    os.replace(tmp, out)
-
-
 def lib():
-    """the restatement as a shared library: tests/_build/ when it is writable, else a temporary directory"""
+    """the restatement as a shared library, its prototypes declared"""
     global _lib
     with _lock:
         if _lib is None:
-            out = os.path.join(HERE, '_build', 'librays_restatement.so')
-            if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in DEPS):
-                try:
-                    _compile(out)
-                except OSError:  # a read-only checkout
-                    out = os.path.join(tempfile.mkdtemp(prefix='rays_restatement_'), 'librays_restatement.so')
-                    _compile(out)
-            L = ctypes.CDLL(out)
+            L = restatement_lib(SRC, [world_ref.SRC])
             v, u = ctypes.c_void_p, ctypes.c_uint32
             L.ry_cast.restype = None
             L.ry_cast.argtypes = [v, v, u, u, u, v, u, ctypes.c_float, v, u, v, v, v, v, v, v]

@@ -336,6 +336,10 @@ WORLD_KERNELS = {
     '_ZN12_GLOBAL__N_125worldset_game_step_kernelENS_9WorldViewENS_7SetGameEPKNS_10DevTriggerEPKNS_9DevEffectEPKNS_11DevSetLevelEP18rdoom_player_statePK18rdoom_player_inputj19rdoom_player_config':
         'cbcd23b349071a304f9bdff7d0c413da7f365d7795a9aae3ab265cdd05c033ee',
     '_ZN12_GLOBAL__N_126worldset_game_reset_kernelEPKNS_11DevSetLevelEjjPjPfjPKjPKh': '6e7c5ccb3bcdf1993354b0504bc1babb8e2e73e6b323c055d10ca70c7a488e0a',
+    # the two ray kernels, pinned since they take the player's orientation and eye from player_quat.hpp
+    '_ZN12_GLOBAL__N_116cast_rays_kernelENS_9WorldViewENS_7RayArgsE': '02d6b5c3a74911bd018371c6218ce5a4fbc87d7dffed5471ad3ed589fb3ce0d6',
+    '_ZN12_GLOBAL__N_125worldset_cast_rays_kernelENS_9WorldViewENS_7RayArgsEPKNS_11DevSetLevelEPKjS6_j':
+        '5fc964c776fc63a7414ef8d5755010de3a92a0b70854366e154661a452ffd77f',
 }
 
 

@@ -1,8 +1,12 @@
 """Shared test helpers: synthetic IWAD location, pose generation (numpy f32), PNG dump."""
+import ctypes
 import hashlib
 import os
 import struct
+import subprocess
 import sys
+import tempfile
+import threading
 import zlib
 
 import numpy as np
@@ -16,6 +20,36 @@ _syn = importlib.import_module('rust-doom_amd.synthetic')
 GOLDEN, WAD_PATH, BIG_WAD_PATH, META_PATH = _syn.GOLDEN, _syn.WAD_PATH, _syn.BIG_WAD_PATH, _syn.META_PATH
 ensure_wad, ensure_big_wad, wad_digest = _syn.ensure_wad, _syn.ensure_big_wad, _syn.wad_digest
 F = np.float32
+
+
+_restatements = {}
+_restatements_lock = threading.Lock()
+
+
+def restatement_lib(src, deps=()):
+    """tests/<name>.c, one of the C restatements, as a ctypes library (loaded once): compiled with gcc -O2 -ffp-contract=off
+    -fno-fast-math into tests/_build/ when that is missing or older than `src` or one of `deps` (the sources it includes), or into a
+    temporary directory when the checkout is read-only"""
+    here = os.path.dirname(os.path.abspath(src))
+    name = os.path.splitext(os.path.basename(src))[0]
+
+    def compile_to(out):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        tmp = '%s.%d.tmp' % (out, os.getpid())
+        subprocess.check_call(['gcc', '-shared', '-fPIC', '-O2', '-ffp-contract=off', '-fno-fast-math', '-I', here, '-o', tmp, src, '-lm'])
+        os.replace(tmp, out)
+
+    with _restatements_lock:
+        if src not in _restatements:
+            out = os.path.join(here, '_build', 'lib%s.so' % name)
+            if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in [src, *deps]):
+                try:
+                    compile_to(out)
+                except OSError:  # a read-only checkout
+                    out = os.path.join(tempfile.mkdtemp(prefix=name + '_'), 'lib%s.so' % name)
+                    compile_to(out)
+            _restatements[src] = ctypes.CDLL(out)
+        return _restatements[src]
 
 
 def perspective(fovy_deg, aspect, near, far):

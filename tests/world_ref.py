@@ -3,14 +3,13 @@ game::player, sharing no code with the product) compiled with gcc -O2 -ffp-contr
 ctypes, fed from the product's level walk (rdoom_wad_walk) by a Python visitor."""
 import ctypes
 import os
-import subprocess
-import tempfile
 import threading
 from concurrent.futures import ThreadPoolExecutor
 
 import numpy as np
 
 import rust_doom_amd as rd
+from util import restatement_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, 'world_restatement.c')
@@ -21,26 +20,12 @@ NODE = np.dtype([('origin', '<f4', 2), ('displace', '<f4', 2), ('length', '<f4')
 assert NODE == rd.WORLD_NODE
 
 
-def _compile(out):
-    os.makedirs(os.path.dirname(out), exist_ok=True)
-    tmp = '%s.%d.tmp' % (out, os.getpid())
-    subprocess.check_call(['gcc', '-shared', '-fPIC', '-O2', '-ffp-contract=off', '-fno-fast-math', '-o', tmp, SRC, '-lm'])
-    os.replace(tmp, out)
-
-
 def lib():
-    """the restatement as a shared library: tests/_build/ when it is writable, else a temporary directory"""
+    """the restatement as a shared library, its prototypes declared"""
     global _lib
     with _lock:
         if _lib is None:
-            out = os.path.join(HERE, '_build', 'libworld_restatement.so')
-            if not os.path.exists(out) or os.path.getmtime(out) < os.path.getmtime(SRC):
-                try:
-                    _compile(out)
-                except OSError:  # a read-only checkout
-                    out = os.path.join(tempfile.mkdtemp(prefix='world_restatement_'), 'libworld_restatement.so')
-                    _compile(out)
-            L = ctypes.CDLL(out)
+            L = restatement_lib(SRC)
             L.wb_new.restype = ctypes.c_void_p
             for name in ('wb_free', 'wb_leaf_end', 'wb_node_end', 'wb_build', 'wb_counts', 'wb_copy', 'rs_sweep', 'rs_step'):
                 getattr(L, name).restype = None
