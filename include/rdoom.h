@@ -421,6 +421,10 @@ rdoom_status rdoom_built_counters(const rdoom_built *built, rdoom_counters *out)
 rdoom_status rdoom_built_timings(const rdoom_built *built, rdoom_host_timings *out); /* how long the build's phases took */
 /* Lights::fill_buffer_at (game/src/lights.rs:26-30) */
 rdoom_status rdoom_built_lights_at(const rdoom_built *built, float time, uint8_t out_lights[256]);
+/* The level's Lights list itself (game/src/lights.rs:3-24), in push order: entry i is the info of light index i (a_light of the
+ * vertices), the list rdoom_built_lights_at iterates over.  Borrowed, valid until rdoom_built_destroy; *out_n <= 255.  An entry
+ * with has_effect == 0 has its effect fields zero.  Feeds rdoom_lightset_create. */
+rdoom_status rdoom_built_light_infos(const rdoom_built *built, const rdoom_light_info **out, uint32_t *out_n);
 /* Builder::visit_marker start pose (game/src/level.rs:757-762) */
 rdoom_status rdoom_built_start(const rdoom_built *built, float out_pos[3], float *out_yaw);
 /* bounds of the sub-sector floor polygons, for pose generators: n polygons, centroid xz + floor y */
@@ -687,6 +691,55 @@ rdoom_status rdoom_batch_render_players(rdoom_batch *batch, const rdoom_player_s
                                         const float *d_object_offsets, uint32_t n_objects, const uint8_t *d_lights,
                                         uint32_t lights_stride, float time, uint32_t n_players, uint32_t kinds_mask,
                                         uint32_t flags, void *stream, rdoom_pose *d_poses_out, float *d_object_modelviews_out);
+
+/* ---- device light set: every player's clock, and the sector lights at it, on the device ---------------
+ * A rdoom_lightset holds the light infos of n_levels levels on the current device: infos[l] points at counts[l] infos (at most
+ * 255; 0 is allowed, infos[l] may then be NULL), slot l of a level set or world set of the same list.  The infos are copied.  Any
+ * table may be given, not only what rdoom_built_light_infos returns.  RDOOM_BAD_ARG: n_levels == 0, more than 255 infos in a
+ * level, an info with has_effect != 0 whose effect_kind is not 0, 1 or 2. */
+typedef struct rdoom_lightset rdoom_lightset;
+rdoom_status rdoom_lightset_create(const rdoom_light_info *const *infos, const uint32_t *counts, uint32_t n_levels,
+                                   rdoom_lightset **out);
+void rdoom_lightset_destroy(rdoom_lightset *set);
+/* The light tables of n players, asynchronous on `stream` (a hipStream_t, may be NULL); every pointer is device memory, nothing
+ * is copied to the host and nothing waits.  Row p of d_out (n x 256 bytes, 4-byte aligned) is Lights::fill_buffer_at(d_times[p])
+ * of level d_levels[p] (d_levels NULL: slot 0 for everyone): entry i < the level's count is
+ *   (clamp(light_level_at(info_i, d_times[p])) * 255.0) as u8
+ * and entries from the count upwards are 0.  A slot outside the set is seen on the device only: that player's row is 256 zeros,
+ * and nothing else is written for it.  n == 0 queues nothing.
+ * Arithmetic -- light_level_at, noise, fract, clamp of game/src/lights.rs:33-78, restated operation for operation in binary32, no
+ * contraction, IEEE division and floor:
+ *   no effect:  level
+ *   Glow:       scale = level - alt_level; phase = time * speed / scale; |0.5 - fract(phase)| * 2 * scale + alt_level
+ *   Random:     noise(sync, floor(time * speed)) < duration ? alt_level : level
+ *   Alternate:  fract(time * speed + sync * 3.5435) < duration ? alt_level : level
+ *   noise(s, t) = fract(1 + sin((s + t / 1000) * 12.9898 + s * 78.233) * 43758.547);  fract(x) = x - floor(x)
+ *   clamp(x) = x < 0 ? 0 : (x > 1 ? 1 : x)   (a NaN passes through)
+ * `as u8` is Rust's: truncation towards zero, saturation at 0 and 255, NaN gives 0.  A Glow light with level == alt_level divides
+ * by zero: phase is +-inf or NaN, fract of it NaN, the entry 0 -- what Rust gives; the host's rdoom_built_lights_at casts that NaN
+ * in C++, which is undefined, so this case is defined here and not by the host.
+ * The one deliberate difference from rdoom_built_lights_at: the sine in noise is the binary64 sine of the binary32 argument,
+ * rounded once to binary32 (the correctly rounded sine, unless the binary64 value lies within its own error of the midpoint of
+ * two binary32 numbers).  The host calls libm sinf, which is not correctly rounded and which no device library reproduces.  So a
+ * row equals rdoom_built_lights_at(d_times[p]) except at Random entries whose sinf differs from the correctly rounded sine at
+ * that argument (about 1 % of arguments), and there only if the noise value then falls on the other side of `duration`. */
+rdoom_status rdoom_lightset_tables(const rdoom_lightset *set, const uint32_t *d_levels, const float *d_times, uint32_t n,
+                                   uint8_t *d_out, void *stream);
+/* rdoom_poses_from_players_device with a clock per player: pose p's time is d_times[p] (n floats of device memory). */
+rdoom_status rdoom_poses_from_players_device_clocked(const rdoom_player_state *d_states, uint32_t n, uint32_t width, uint32_t height,
+                                                     const float *d_times, const float *d_object_offsets, uint32_t n_objects,
+                                                     rdoom_pose *d_poses_out, float *d_object_modelviews_out, void *stream);
+/* rdoom_batch_render_players with a clock per player: pose p's u_time is d_times[p] and its light table is row p of
+ * rdoom_lightset_tables(lights, d_levels, d_times, ...), written straight into the batch's per-pose constants -- the caller owns
+ * no n x 256 buffer and the host computes nothing per render.  Everything else (arguments, frames, the sky angle, a level outside
+ * the set rendered as level 0 -- with level 0's lights -- and reported by rdoom_batch_finish) is rdoom_batch_render_players'.
+ * It queues that render's launches plus one, the light tables; it never waits, allocates nothing after the batch's first render
+ * with objects, and can be captured into a graph.  Checked on the host before anything is queued (RDOOM_BAD_ARG): a NULL light
+ * set or NULL d_times; a light set whose level count differs from the batch's level set's, or that lives on another device. */
+rdoom_status rdoom_batch_render_players_clocked(rdoom_batch *batch, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                                const float *d_object_offsets, uint32_t n_objects, const rdoom_lightset *lights,
+                                                const float *d_times, uint32_t n_players, uint32_t kinds_mask, uint32_t flags,
+                                                void *stream, rdoom_pose *d_poses_out, float *d_object_modelviews_out);
 
 /* ---- ray casts: range-sensor rays from player states through the world --------------------------------
  * n players x n_rays rays in one launch, asynchronous on `stream`; every pointer is device memory, nothing is copied to the

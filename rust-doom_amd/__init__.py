@@ -62,6 +62,11 @@ WORLDSET_LEVEL = np.dtype([('archive_index', '<u4'), ('destination', '<u4'), ('s
                            ('n_triggers', '<u4'), ('n_objects', '<u4'), ('node_depth', '<u4')])
 assert PLAYER_STATE.itemsize == 40 and PLAYER_INPUT.itemsize == 20 and PLAYER_CONFIG.itemsize == 32
 RAY_NO_HIT = 0xFFFFFFFF  # rdoom_world_cast_rays' hit index where nothing is within range
+# rdoom_light_info (wad/src/light.rs:8-25 LightInfo): what BuiltLevel.light_infos returns and DeviceLights takes
+LIGHT_INFO = np.dtype([('level', '<f4'), ('has_effect', '<i4'), ('effect_kind', '<i4'), ('alt_level', '<f4'), ('speed', '<f4'),
+                       ('duration', '<f4'), ('sync', '<f4')])
+LIGHT_GLOW, LIGHT_RANDOM, LIGHT_ALTERNATE = 0, 1, 2
+assert LIGHT_INFO.itemsize == 28
 
 
 class RdoomError(RuntimeError):
@@ -125,7 +130,8 @@ API_SYMBOLS = [
     'rdoom_object_modelviews_from_player', 'rdoom_worldset_create', 'rdoom_worldset_destroy', 'rdoom_worldset_info',
     'rdoom_worldset_level', 'rdoom_worldset_game_bytes', 'rdoom_worldset_game_reset', 'rdoom_worldset_step_game',
     'rdoom_poses_from_players_device', 'rdoom_batch_render_players', 'rdoom_batch_resolve_plane', 'rdoom_batch_read_plane',
-    'rdoom_world_cast_rays', 'rdoom_worldset_cast_rays']
+    'rdoom_world_cast_rays', 'rdoom_worldset_cast_rays', 'rdoom_built_light_infos', 'rdoom_lightset_create', 'rdoom_lightset_destroy',
+    'rdoom_lightset_tables', 'rdoom_poses_from_players_device_clocked', 'rdoom_batch_render_players_clocked']
 
 _lib = None
 
@@ -142,7 +148,7 @@ def lib():
         for name in API_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ('rdoom_last_error', 'rdoom_level_destroy', 'rdoom_batch_destroy', 'rdoom_wad_close',
-                            'rdoom_built_destroy', 'rdoom_world_destroy', 'rdoom_worldset_destroy'):
+                            'rdoom_built_destroy', 'rdoom_world_destroy', 'rdoom_worldset_destroy', 'rdoom_lightset_destroy'):
                 fn.restype = ctypes.c_int32
             elif name != 'rdoom_last_error':
                 fn.restype = None
@@ -442,6 +448,13 @@ class BuiltLevel:
         _check(lib().rdoom_built_lights_at(self._h, ctypes.c_float(time), out.ctypes.data_as(ctypes.c_void_p)))
         return out
 
+    def light_infos(self):
+        """rdoom_built_light_infos: the level's Lights list in push order, as LIGHT_INFO records (entry i = light index i)"""
+        p = ctypes.c_void_p()
+        n = ctypes.c_uint32()
+        _check(lib().rdoom_built_light_infos(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return self._view(p.value, n.value, LIGHT_INFO)
+
     def start(self):
         pos = (ctypes.c_float * 3)()
         yaw = ctypes.c_float()
@@ -505,6 +518,52 @@ class DeviceLevelSet(DeviceLevel):
         n = ctypes.c_uint32()
         _check(lib().rdoom_level_num_levels(self._h, ctypes.byref(n)))
         return n.value
+
+
+class DeviceLights:
+    """The light infos of one or more levels resident on the device (rdoom_lightset_create): slot l holds levels[l], a BuiltLevel
+    (its light_infos()) or an array of LIGHT_INFO records.  tables() evaluates every player's 256-byte light table at that
+    player's own time on the GPU; Batch.render_players(states, device_lights, ..., times=...) renders with them."""
+
+    def __init__(self, levels):
+        if isinstance(levels, (BuiltLevel, np.ndarray)):
+            levels = [levels]
+        arrays = [np.ascontiguousarray(lv.light_infos() if isinstance(lv, BuiltLevel) else lv, LIGHT_INFO).reshape(-1) for lv in levels]
+        self.n_levels = len(arrays)
+        ptrs = (ctypes.c_void_p * max(1, len(arrays)))(*[_ptr(a) for a in arrays])
+        counts = (ctypes.c_uint32 * max(1, len(arrays)))(*[len(a) for a in arrays])
+        self._h = ctypes.c_void_p()
+        _check(lib().rdoom_lightset_create(ptrs, counts, len(arrays), ctypes.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().rdoom_lightset_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        _close_quietly(self)
+
+    def tables(self, times, levels=None, out=None, stream=None):
+        """rdoom_lightset_tables: times a float32 GPU tensor of n entries; levels None (slot 0) or a GPU tensor of n 32-bit slots;
+        out None or a contiguous uint8 GPU tensor of n * 256 entries.  Returns the (n, 256) uint8 tensor: row p is level
+        levels[p]'s light table at times[p], zeros for a slot outside the set.  Asynchronous on `stream`."""
+        import torch
+        n = int(times.numel())
+        pt = _times_tensor(times, n)
+        pv = None
+        if levels is not None:
+            if not isinstance(levels, torch.Tensor) or levels.device.type != 'cuda' or not levels.is_contiguous() or \
+                    levels.numel() != n or levels.element_size() != 4:
+                raise ValueError('levels must be a contiguous GPU tensor of one 32-bit slot per player (%d)' % n)
+            pv = levels.data_ptr()
+        if out is None:
+            out = torch.empty((n, 256), dtype=torch.uint8, device=times.device)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.uint8 or out.device.type != 'cuda' or not out.is_contiguous() \
+                or out.numel() != n * 256:
+            raise ValueError('out must be a contiguous uint8 GPU tensor of %d x 256 entries' % n)
+        _check(lib().rdoom_lightset_tables(self._h, ctypes.c_void_p(pv), ctypes.c_void_p(pt), n,
+                                           ctypes.c_void_p(out.data_ptr() if n else None), ctypes.c_void_p(_stream_handle(stream))))
+        return out
 
 
 class Batch:
@@ -589,13 +648,19 @@ class Batch:
         return {n: getattr(t, n) for n, _ in Timings._fields_}
 
     def render_players(self, states, lights, levels=None, offsets=None, time=0.0, kinds=ALL_KINDS, stream=None, poses_out=None,
-                       modelviews_out=None, profiled=False):
+                       modelviews_out=None, profiled=False, times=None):
         """rdoom_batch_render_players: render every player of a device states tensor (World.step_game / WorldSet.step_game's) from its
         own camera, without a host round trip.  levels: the players' level slots (WorldSet.game_state's int32 tensor; None on a
         batch of one level); offsets: the (n, n_objects, 3) float32 tensor of game_state (None: every object at rest); lights: a
         uint8 (256,) table shared by every level, or (n_levels, 256), one per level of the batch's set.  Tensors on the GPU are used
         as they are; numpy arrays are uploaded (and waited for).  poses_out / modelviews_out: optional tensors from
-        poses_from_players_device's shapes, filled with what was rendered.  Asynchronous on `stream`; profiled as render_profiled."""
+        poses_from_players_device's shapes, filled with what was rendered.  Asynchronous on `stream`; profiled as render_profiled.
+        The clocked render (rdoom_batch_render_players_clocked): times, a float32 GPU tensor of n entries, with lights a
+        DeviceLights -- player p is rendered at times[p] with its level's light table at that time, computed on the device; `time`
+        is not used.  times without a DeviceLights, or a DeviceLights without times, is a ValueError."""
+        if (times is not None) != isinstance(lights, DeviceLights):
+            raise ValueError('the clocked render takes times and a DeviceLights together (times: %s, lights: %s)'
+                             % ('given' if times is not None else 'None', type(lights).__name__))
         keep = []
 
         def dev(a, what):
@@ -605,17 +670,20 @@ class Batch:
             keep.append((k, uploaded))
             return ptr
         ps, n = dev(states, 'states'), _n_players(states)
-        lights_n = lights.numel() if not isinstance(lights, np.ndarray) else lights.size
-        n_levels = ctypes.c_uint32()
-        _check(lib().rdoom_level_num_levels(self.level._h, ctypes.byref(n_levels)))
-        if lights_n == 256:
-            stride = 0
-        elif lights_n == 256 * n_levels.value:
-            stride = 256
+        if times is None:
+            lights_n = lights.numel() if not isinstance(lights, np.ndarray) else lights.size
+            n_levels = ctypes.c_uint32()
+            _check(lib().rdoom_level_num_levels(self.level._h, ctypes.byref(n_levels)))
+            if lights_n == 256:
+                stride = 0
+            elif lights_n == 256 * n_levels.value:
+                stride = 256
+            else:
+                raise ValueError('lights must be (256,) or one 256-byte table per level of the set (%d), got %d bytes'
+                                 % (n_levels.value, lights_n))
+            pl = dev(np.ascontiguousarray(lights, np.uint8) if isinstance(lights, np.ndarray) else lights, 'lights')
         else:
-            raise ValueError('lights must be (256,) or one 256-byte table per level of the set (%d), got %d bytes'
-                             % (n_levels.value, lights_n))
-        pl = dev(np.ascontiguousarray(lights, np.uint8) if isinstance(lights, np.ndarray) else lights, 'lights')
+            pt = _times_tensor(times, n)
         n_obj = 0
         if offsets is not None:
             if isinstance(offsets, np.ndarray):
@@ -633,10 +701,16 @@ class Batch:
         po, pm = _out_tensor(poses_out, n * POSE.itemsize, 'poses_out'), _out_tensor(modelviews_out, n * n_obj * 64, 'modelviews_out')
         pv, po_ = dev(levels, 'levels'), dev(offsets, 'offsets')
         self.last_n = n
-        _check(lib().rdoom_batch_render_players(self._h, ctypes.c_void_p(ps), ctypes.c_void_p(pv), ctypes.c_void_p(po_), n_obj,
-                                                ctypes.c_void_p(pl), stride, ctypes.c_float(time), n, int(kinds),
-                                                1 if profiled else 0, ctypes.c_void_p(_stream_handle(stream)), ctypes.c_void_p(po),
-                                                ctypes.c_void_p(pm)))
+        if times is None:
+            _check(lib().rdoom_batch_render_players(self._h, ctypes.c_void_p(ps), ctypes.c_void_p(pv), ctypes.c_void_p(po_), n_obj,
+                                                    ctypes.c_void_p(pl), stride, ctypes.c_float(time), n, int(kinds),
+                                                    1 if profiled else 0, ctypes.c_void_p(_stream_handle(stream)), ctypes.c_void_p(po),
+                                                    ctypes.c_void_p(pm)))
+        else:
+            _check(lib().rdoom_batch_render_players_clocked(self._h, ctypes.c_void_p(ps), ctypes.c_void_p(pv), ctypes.c_void_p(po_),
+                                                            n_obj, lights._h, ctypes.c_void_p(pt), n, int(kinds), 1 if profiled else 0,
+                                                            ctypes.c_void_p(_stream_handle(stream)), ctypes.c_void_p(po),
+                                                            ctypes.c_void_p(pm)))
         if any(uploaded for _, uploaded in keep):
             import torch
             torch.cuda.synchronize()
@@ -861,12 +935,22 @@ def _out_tensor(t, nbytes, what):
     return t.data_ptr()
 
 
-def poses_from_players_device(states, width, height, time=0.0, offsets=None, stream=None):
+def _times_tensor(times, n):
+    """the device pointer of a clocked call's times: a contiguous float32 GPU tensor of n entries"""
+    import torch
+    if not isinstance(times, torch.Tensor) or times.dtype != torch.float32 or times.device.type != 'cuda' or \
+            not times.is_contiguous() or times.numel() != n:
+        raise ValueError('times must be a contiguous float32 tensor of %d entries on the GPU' % n)
+    return times.data_ptr()
+
+
+def poses_from_players_device(states, width, height, time=0.0, offsets=None, stream=None, times=None):
     """rdoom_poses_from_players_device: the camera of every player, on the device.  states: a GPU tensor of PLAYER_STATE records
     (numpy: uploaded); offsets: None or the (n, n_objects, 3) float32 tensor of game_state.  Returns (poses, modelviews): poses a
     float32 (n, 34) tensor of POSE records (.cpu().numpy().view(POSE)), modelviews None or a float32 (n, n_objects, 16) tensor --
     what poses_from_players / object_modelviews_from_players compute on the host, with the project's sincos.
-    Asynchronous on `stream`."""
+    times: None, or a float32 GPU tensor of n entries -- pose p's time is times[p] instead of `time`
+    (rdoom_poses_from_players_device_clocked).  Asynchronous on `stream`."""
     import torch
     n = _n_players(states)
     ps, ks, uploaded = _device_tensor(states, 'states')
@@ -882,10 +966,13 @@ def poses_from_players_device(states, width, height, time=0.0, offsets=None, str
         uploaded = uploaded or up2
         n_obj = int(offsets.shape[1])
         mvs = torch.empty((n, n_obj, 16), dtype=torch.float32, device=dev)
-    _check(lib().rdoom_poses_from_players_device(ctypes.c_void_p(ps), n, int(width), int(height), ctypes.c_float(time),
-                                                 ctypes.c_void_p(po), n_obj, ctypes.c_void_p(poses.data_ptr()),
-                                                 ctypes.c_void_p(mvs.data_ptr() if mvs is not None else None),
-                                                 ctypes.c_void_p(_stream_handle(stream))))
+    tail = (ctypes.c_void_p(po), n_obj, ctypes.c_void_p(poses.data_ptr()), ctypes.c_void_p(mvs.data_ptr() if mvs is not None else None),
+            ctypes.c_void_p(_stream_handle(stream)))
+    if times is None:
+        _check(lib().rdoom_poses_from_players_device(ctypes.c_void_p(ps), n, int(width), int(height), ctypes.c_float(time), *tail))
+    else:
+        _check(lib().rdoom_poses_from_players_device_clocked(ctypes.c_void_p(ps), n, int(width), int(height),
+                                                             ctypes.c_void_p(_times_tensor(times, n)), *tail))
     if uploaded:
         torch.cuda.synchronize(dev)
     return poses, mvs

@@ -104,11 +104,13 @@ __global__ __launch_bounds__(WAVE) void player_frames_kernel(PlayerFrameArgs a) 
 #pragma unroll
     for (int k = 0; k < 16; k++) dst[k] = M[k];
   }
+  float time = a.time;  // u_time: the render's, or this player's own clock (only lane (p, 0) writes it anywhere)
+  if (o == 0 && a.times) time = a.times[p];
   if (o == 0 && a.poses_out) {
     rdoom_pose *dst = a.poses_out + p;
 #pragma unroll
     for (int k = 0; k < 16; k++) dst->modelview[k] = M[k], dst->projection[k] = a.proj[k];
-    dst->time = a.time, dst->_pad = 0.0f;
+    dst->time = time, dst->_pad = 0.0f;
   }
   if (!a.pose_consts) return;
   float pm[16];
@@ -130,15 +132,17 @@ __global__ __launch_bounds__(WAVE) void player_frames_kernel(PlayerFrameArgs a) 
   }
   PoseConst *pc = a.pose_consts + p;
   store16(pc->pm, pm);
-  *reinterpret_cast<float4 *>(&pc->time) = make_float4(a.time, vr0, vr1, a.zk);
-  const uint8_t *lights = a.lights + (size_t)level * a.lights_stride;
-  uint4 *ld = reinterpret_cast<uint4 *>(pc->lights);
-  if (((uintptr_t)lights & 15u) == 0u) {
-    const uint4 *ls = reinterpret_cast<const uint4 *>(lights);
+  *reinterpret_cast<float4 *>(&pc->time) = make_float4(time, vr0, vr1, a.zk);
+  if (a.lights) {  // (null: the clocked render, whose light kernel writes the table after this launch)
+    const uint8_t *lights = a.lights + (size_t)level * a.lights_stride;
+    uint4 *ld = reinterpret_cast<uint4 *>(pc->lights);
+    if (((uintptr_t)lights & 15u) == 0u) {
+      const uint4 *ls = reinterpret_cast<const uint4 *>(lights);
 #pragma unroll
-    for (int k = 0; k < 16; k++) ld[k] = ls[k];
-  } else {
-    for (int k = 0; k < 256; k++) pc->lights[k] = lights[k];
+      for (int k = 0; k < 16; k++) ld[k] = ls[k];
+    } else {
+      for (int k = 0; k < 256; k++) pc->lights[k] = lights[k];
+    }
   }
   store16(pc->mv, M);
   store16(pc->proj, a.proj);
@@ -167,9 +171,10 @@ rdoom_status player_projection(uint32_t width, uint32_t height, float proj[16], 
 
 }  // namespace rdoom_dev
 
-extern "C" rdoom_status rdoom_poses_from_players_device(const rdoom_player_state *d_states, uint32_t n, uint32_t width, uint32_t height,
-                                                        float time, const float *d_object_offsets, uint32_t n_objects,
-                                                        rdoom_pose *d_poses_out, float *d_object_modelviews_out, void *stream) {
+// rdoom_poses_from_players_device and its clocked form: one time for every player (d_times null), or one per player
+static rdoom_status poses_from_players(const rdoom_player_state *d_states, uint32_t n, uint32_t width, uint32_t height, float time,
+                                       const float *d_times, const float *d_object_offsets, uint32_t n_objects,
+                                       rdoom_pose *d_poses_out, float *d_object_modelviews_out, void *stream) {
   using namespace rdoom_dev;
   if (!d_states || !d_poses_out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   if (n == 0 || width == 0 || height == 0) return rdoom::fail(RDOOM_BAD_ARG, "n %u, frame %ux%u: none may be 0", n, width, height);
@@ -178,9 +183,25 @@ extern "C" rdoom_status rdoom_poses_from_players_device(const rdoom_player_state
   if (n_objects > 4096u) return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u (at most 4096)", n_objects);
   PlayerFrameArgs a{};
   if (rdoom_status rs = player_projection(width, height, a.proj, &a.zk)) return rs;
-  a.states = d_states, a.n = n, a.time = time;
+  a.states = d_states, a.n = n, a.time = time, a.times = d_times;
   a.offsets = d_object_modelviews_out ? d_object_offsets : nullptr;
   a.lanes = d_object_modelviews_out ? n_objects : 1u;
   a.poses_out = d_poses_out, a.modelviews_out = d_object_modelviews_out;
   return launch_player_frames((hipStream_t)stream, a);
+}
+
+extern "C" rdoom_status rdoom_poses_from_players_device(const rdoom_player_state *d_states, uint32_t n, uint32_t width, uint32_t height,
+                                                        float time, const float *d_object_offsets, uint32_t n_objects,
+                                                        rdoom_pose *d_poses_out, float *d_object_modelviews_out, void *stream) {
+  return poses_from_players(d_states, n, width, height, time, nullptr, d_object_offsets, n_objects, d_poses_out,
+                            d_object_modelviews_out, stream);
+}
+
+extern "C" rdoom_status rdoom_poses_from_players_device_clocked(const rdoom_player_state *d_states, uint32_t n, uint32_t width,
+                                                                uint32_t height, const float *d_times, const float *d_object_offsets,
+                                                                uint32_t n_objects, rdoom_pose *d_poses_out,
+                                                                float *d_object_modelviews_out, void *stream) {
+  if (!d_times) return rdoom::fail(RDOOM_BAD_ARG, "d_times is null");
+  return poses_from_players(d_states, n, width, height, 0.0f, d_times, d_object_offsets, n_objects, d_poses_out,
+                            d_object_modelviews_out, stream);
 }

@@ -125,9 +125,32 @@ struct PlayerFrameArgs {
   uint32_t n_render_objects;
   rdoom_pose *poses_out;      // n poses, or null
   float *modelviews_out;      // n x lanes x 16 floats, or null
+  const float *times;         // per-player u_time (the clocked entry points), or null: `time` for every player.  With `times`,
+                              // `lights` is null and PoseConst::lights is left to launch_light_tables
 };
 rdoom_status launch_player_frames(hipStream_t st, const PlayerFrameArgs &args);
 // the camera's projection for a width x height frame (rdoom_pose_from_player's, bit for bit) and render_impl's depth constant zk
 rdoom_status player_projection(uint32_t width, uint32_t height, float proj[16], float *zk);
+
+
+// Kernel 9: 256-byte light tables of n players from their clocks (lights.hip; include/rdoom.h "device light set" has the contract).
+// Row p -- `stride` bytes after row p - 1, 4-byte aligned -- is Lights::fill_buffer_at(times[p]) of level levels[p] of the set.
+struct LightSetView {
+  const rdoom_light_info *infos;  // device: the levels' info lists, one after the other
+  const uint2 *ranges;            // device: per level (first info, count <= 255)
+  uint32_t n_levels;
+  int device;
+};
+const LightSetView *lightset_view(const rdoom_lightset *set);
+struct LightTableArgs {
+  LightSetView set;
+  const uint32_t *levels;  // or null: slot 0
+  const float *times;
+  uint32_t n;
+  uint8_t *out;
+  uint32_t stride;         // bytes between rows: 256 (rdoom_lightset_tables) or sizeof(PoseConst) (the clocked render)
+  uint32_t fallback;       // the slot a player outside the set takes: >= n_levels gives a row of zeros, 0 what the render shows
+};
+rdoom_status launch_light_tables(hipStream_t st, const LightTableArgs &args);
 
 }  // namespace rdoom_dev

@@ -785,12 +785,26 @@ rdoom_status rdoom_batch_render_levels(rdoom_batch *batch, const rdoom_pose *pos
                      n_objects, (flags & RDOOM_RENDER_PROFILED) != 0u, level_of_pose);
 }
 
-rdoom_status rdoom_batch_render_players(rdoom_batch *b, const rdoom_player_state *d_states, const uint32_t *d_levels,
+// rdoom_batch_render_players (clock null: d_lights / lights_stride / time) and rdoom_batch_render_players_clocked (clock: a light
+// set and the players' times; d_lights null) -- the clocked render queues one more launch, the light tables, after the frames'
+namespace {
+struct PlayerClock {
+  const LightSetView *lights;
+  const float *d_times;
+};
+}  // namespace
+static rdoom_status render_players_impl(rdoom_batch *b, const rdoom_player_state *d_states, const uint32_t *d_levels,
                                         const float *d_object_offsets, uint32_t n_objects, const uint8_t *d_lights,
-                                        uint32_t lights_stride, float time, uint32_t n_players, uint32_t kinds_mask,
-                                        uint32_t flags, void *stream, rdoom_pose *d_poses_out, float *d_object_modelviews_out) {
+                                        uint32_t lights_stride, float time, const PlayerClock *clock, uint32_t n_players,
+                                        uint32_t kinds_mask, uint32_t flags, void *stream, rdoom_pose *d_poses_out,
+                                        float *d_object_modelviews_out) {
   // every check before anything is queued or allocated
-  if (!b || !d_states || !d_lights) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (!b || !d_states || (!clock && !d_lights)) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (clock && clock->lights->n_levels != b->level->view.n_slices)
+    return rdoom::fail(RDOOM_BAD_ARG, "the light set holds %u levels, the batch's level set %u", clock->lights->n_levels,
+                       b->level->view.n_slices);
+  if (clock && clock->lights->device != b->level->device)
+    return rdoom::fail(RDOOM_BAD_ARG, "the light set lives on device %d, the batch on device %d", clock->lights->device, b->level->device);
   if (flags & ~(uint32_t)RDOOM_RENDER_PROFILED) return rdoom::fail(RDOOM_BAD_ARG, "unknown flags 0x%x", flags);
   if (n_players == 0 || n_players > b->max_poses) return rdoom::fail(RDOOM_BAD_ARG, "n_players %u outside 1..%u", n_players, b->max_poses);
   const rdoom_level *lv = b->level;
@@ -813,7 +827,7 @@ rdoom_status rdoom_batch_render_players(rdoom_batch *b, const rdoom_player_state
   a.states = d_states, a.n = n_players, a.time = time;
   a.offsets = d_object_offsets, a.lanes = d_object_offsets ? n_objects : 1u;
   a.levels = d_levels, a.n_slices = lv->view.n_slices, a.error_word = b->d_fix_count + 3;
-  a.lights = d_lights, a.lights_stride = lights_stride;
+  a.lights = d_lights, a.lights_stride = lights_stride, a.times = clock ? clock->d_times : nullptr;
   a.pose_consts = b->d_poses;
   a.object_consts = d_object_offsets ? b->d_objects : nullptr, a.n_render_objects = d_object_offsets ? lv->n_objects : 0u;
   a.poses_out = d_poses_out, a.modelviews_out = d_object_modelviews_out;
@@ -825,8 +839,38 @@ rdoom_status rdoom_batch_render_players(rdoom_batch *b, const rdoom_player_state
   if (profiled) HIP_TRY(hipEventRecord(ev[0], st));
   DoneGuard done{b, st};
   done.armed = true;
-  return queue_pipeline(b, n_players, kinds_mask, st, nullptr, d_object_offsets != nullptr, profiled, ev, done,
-                        [&] { return launch_player_frames(st, a); });
+  if (!clock)
+    return queue_pipeline(b, n_players, kinds_mask, st, nullptr, d_object_offsets != nullptr, profiled, ev, done,
+                          [&] { return launch_player_frames(st, a); });
+  // every pose's table goes straight into its PoseConst; a level outside the set shows level 0's, as its geometry
+  LightTableArgs lt{};
+  lt.set = *clock->lights, lt.levels = d_levels, lt.times = clock->d_times, lt.n = n_players;
+  lt.out = reinterpret_cast<uint8_t *>(b->d_poses) + offsetof(PoseConst, lights), lt.stride = (uint32_t)sizeof(PoseConst), lt.fallback = 0u;
+  return queue_pipeline(b, n_players, kinds_mask, st, nullptr, d_object_offsets != nullptr, profiled, ev, done, [&] {
+    if (rdoom_status rs = launch_player_frames(st, a)) return rs;
+    return launch_light_tables(st, lt);
+  });
+}
+
+rdoom_status rdoom_batch_render_players(rdoom_batch *b, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                        const float *d_object_offsets, uint32_t n_objects, const uint8_t *d_lights,
+                                        uint32_t lights_stride, float time, uint32_t n_players, uint32_t kinds_mask,
+                                        uint32_t flags, void *stream, rdoom_pose *d_poses_out, float *d_object_modelviews_out) {
+  if (!d_lights) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  return render_players_impl(b, d_states, d_levels, d_object_offsets, n_objects, d_lights, lights_stride, time, nullptr, n_players,
+                             kinds_mask, flags, stream, d_poses_out, d_object_modelviews_out);
+}
+
+rdoom_status rdoom_batch_render_players_clocked(rdoom_batch *b, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                                const float *d_object_offsets, uint32_t n_objects, const rdoom_lightset *lights,
+                                                const float *d_times, uint32_t n_players, uint32_t kinds_mask, uint32_t flags,
+                                                void *stream, rdoom_pose *d_poses_out, float *d_object_modelviews_out) {
+  if (!lights || !d_times)
+    return rdoom::fail(RDOOM_BAD_ARG, "the clocked render needs both a light set and the players' times (%s is null)",
+                       lights ? "d_times" : "the light set");
+  const PlayerClock clock{lightset_view(lights), d_times};
+  return render_players_impl(b, d_states, d_levels, d_object_offsets, n_objects, nullptr, 0u, 0.0f, &clock, n_players, kinds_mask,
+                             flags, stream, d_poses_out, d_object_modelviews_out);
 }
 
 rdoom_status rdoom_level_num_levels(const rdoom_level *level, uint32_t *out) {

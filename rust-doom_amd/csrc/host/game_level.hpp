@@ -14,6 +14,7 @@ class Lights {  // game/src/lights.rs
   uint8_t push(const wad::LightInfo &info);            // lights.rs:14-24
   void fill_buffer_at(float time, uint8_t out[256]) const;  // lights.rs:26-30
   size_t size() const { return lights_.size(); }
+  const std::vector<wad::LightInfo> &infos() const { return lights_; }  // in push order: entry i is light index i
 
  private:
   std::vector<wad::LightInfo> lights_;

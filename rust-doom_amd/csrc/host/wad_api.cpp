@@ -17,6 +17,7 @@ struct rdoom_wad {
 };
 struct rdoom_built {
   std::unique_ptr<rdoom::game::BuiltLevel> b;
+  std::vector<rdoom_light_info> light_infos;  // b->lights as plain data, in push order (rdoom_built_light_infos)
 };
 
 namespace rdoom::game {
@@ -24,6 +25,19 @@ const LoadedWad *loaded_wad(const rdoom_wad *wad) { return wad ? &wad->w : nullp
 }  // namespace rdoom::game
 
 namespace {
+// wad::LightInfo as the header's plain rdoom_light_info (has_effect 0: the effect fields are zero)
+rdoom_light_info plain_light(const rdoom::wad::LightInfo &in) {
+  rdoom_light_info out{};
+  out.level = in.level;
+  if (in.effect) {
+    out.has_effect = 1;
+    out.effect_kind = (int32_t)in.effect->kind;
+    out.alt_level = in.effect->alt_level, out.speed = in.effect->speed, out.duration = in.effect->duration,
+    out.sync = in.effect->sync;
+  }
+  return out;
+}
+
 // trait LevelVisitor implemented by a table of C callbacks (include/rdoom.h: rdoom_visitor_vtbl)
 class CallbackVisitor : public rdoom::wad::LevelVisitor {
  public:
@@ -95,14 +109,7 @@ class CallbackVisitor : public rdoom::wad::LevelVisitor {
   }
   static const rdoom_light_info *light(rdoom_light_info &out, const rdoom::wad::LightInfo *in) {
     if (!in) return nullptr;
-    out = rdoom_light_info{};
-    out.level = in->level;
-    if (in->effect) {
-      out.has_effect = 1;
-      out.effect_kind = (int32_t)in->effect->kind;
-      out.alt_level = in->effect->alt_level, out.speed = in->effect->speed, out.duration = in->effect->duration,
-      out.sync = in->effect->sync;
-    }
+    out = plain_light(*in);
     return &out;
   }
   void poly(void (*fn)(void *, const rdoom_static_poly *), const rdoom::wad::StaticPoly &p) {
@@ -130,6 +137,10 @@ class CallbackVisitor : public rdoom::wad::LevelVisitor {
   const rdoom_visitor_vtbl v_;
   void *user_;
 };
+
+void keep_light_infos(rdoom_built &b) {
+  for (const rdoom::wad::LightInfo &info : b.b->lights.infos()) b.light_infos.push_back(plain_light(info));
+}
 
 template <class F>
 rdoom_status guarded(F f) {
@@ -206,6 +217,7 @@ rdoom_status rdoom_wad_build_level(const rdoom_wad *wad, uint32_t level_index, i
     b->b = rdoom::game::build_level(wad->w, level_index,
                                     use_gpu_tessellation ? &rdoom::game::tessellate_on_device : nullptr,
                                     use_gpu_tessellation ? &rdoom::game::tessellate_segs_on_device : nullptr);
+    keep_light_infos(*b);
     *out_built = b.release();
     return RDOOM_OK;
   });
@@ -221,6 +233,7 @@ rdoom_status rdoom_wad_build_level_chained(const rdoom_wad *wad, uint32_t level_
     b->b = rdoom::game::build_level(wad->w, level_index,
                                     use_gpu_tessellation ? &rdoom::game::tessellate_on_device : nullptr,
                                     use_gpu_tessellation ? &rdoom::game::tessellate_segs_on_device : nullptr, &second);
+    keep_light_infos(*b);
     *out_built = b.release();
     return RDOOM_OK;
   });
@@ -288,6 +301,13 @@ rdoom_status rdoom_built_timings(const rdoom_built *built, rdoom_host_timings *o
 rdoom_status rdoom_built_lights_at(const rdoom_built *built, float time, uint8_t out_lights[256]) {
   if (!built || !out_lights) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   built->b->lights.fill_buffer_at(time, out_lights);
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_built_light_infos(const rdoom_built *built, const rdoom_light_info **out, uint32_t *out_n) {
+  if (!built || !out || !out_n) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  *out = built->light_infos.data();
+  *out_n = (uint32_t)built->light_infos.size();
   return RDOOM_OK;
 }
 
