@@ -775,6 +775,95 @@ rdoom_status rdoom_worldset_cast_rays(const rdoom_worldset *set, const rdoom_pla
                                       const float *d_object_offsets, uint32_t n_objects, float *d_frac_out, uint32_t *d_hit_out,
                                       float *d_origin_out, float *d_vel_out, void *stream);
 
+/* ---- top-down maps: every player's automap, drawn on the device from its game state --------------------
+ * The level's line table: one record per linedef whose two vertex indices are valid (Level::vertex, wad/src/level.rs:83-87), in
+ * linedef order.  a, b: the start and end vertex in world xz (from_wad_coords, wad/src/util.rs:20-22: x = -wad_y / 100,
+ * z = -wad_x / 100).  flags, special_type: WadLinedef's, verbatim (wad/src/types.rs:49-57).  front is the right side, back the
+ * left (Level::right_sidedef / left_sidedef / sidedef_sector, level.rs:131-151): present = 1 when the linedef has that sidedef and
+ * the sidedef's sector exists, else the record is zero; floor / ceiling: from_wad_height of the sector's heights (util.rs:12-14);
+ * floor_id / ceiling_id: the objects SectorInfo gives the sector's floor and ceiling (wad/src/visitor.rs:145-156, 569-588) as the
+ * game numbers them -- the ids that index d_object_offsets and that rdoom_move_effect.object_id names -- 0 for a sector no
+ * DynamicSectorInfo moves. */
+typedef struct rdoom_map_side {
+  uint32_t present;
+  float floor, ceiling;
+  uint32_t floor_id, ceiling_id;
+} rdoom_map_side;
+typedef struct rdoom_map_line {
+  uint32_t linedef;      /* its index in LINEDEFS */
+  float a[2], b[2];
+  uint32_t flags, special_type;
+  rdoom_map_side front, back;
+} rdoom_map_line;
+/* borrowed pointers into a rdoom_world / rdoom_worldset (valid until it is destroyed) */
+typedef struct rdoom_map_lines {
+  const rdoom_map_line *lines;
+  uint32_t n_lines;
+} rdoom_map_lines;
+/* The line table of the world's level, and of slot `slot` of a set (equal to the single world's of the same level).  Both work on
+ * RDOOM_WORLD_HOST_ONLY handles. */
+rdoom_status rdoom_world_map_lines(const rdoom_world *world, rdoom_map_lines *out);
+rdoom_status rdoom_worldset_level_map_lines(const rdoom_worldset *set, uint32_t slot, rdoom_map_lines *out);
+
+/* The classes of a map pixel, and the view of a map.  width x height pixels; scale: world units per pixel; half_width: half the
+ * thickness of a line in pixels; marker: the size of the player marker in pixels (0: none).  flags: RDOOM_MAP_ROTATE the player's
+ * view direction is up (else map north); RDOOM_MAP_SHOW_FLAT draws FLAT lines; RDOOM_MAP_SHOW_HIDDEN draws linedefs with flag 0x80;
+ * RDOOM_MAP_TOP_DOWN row 0 of the output is the top row (else the bottom row). */
+#define RDOOM_MAP_NONE 0u
+#define RDOOM_MAP_FLAT 1u
+#define RDOOM_MAP_CEILING_STEP 2u
+#define RDOOM_MAP_FLOOR_STEP 3u
+#define RDOOM_MAP_CLOSED 4u
+#define RDOOM_MAP_ONE_SIDED 5u
+#define RDOOM_MAP_PLAYER 8u
+#define RDOOM_MAP_ROTATE 1u
+#define RDOOM_MAP_SHOW_FLAT 2u
+#define RDOOM_MAP_SHOW_HIDDEN 4u
+#define RDOOM_MAP_TOP_DOWN 8u
+typedef struct rdoom_map_view {
+  uint32_t width, height;
+  float scale, half_width, marker;
+  uint32_t flags;
+} rdoom_map_view;
+/* n players' maps in one launch, asynchronous on `stream` (a hipStream_t, may be NULL); every pointer but `view` is device memory,
+ * nothing is allocated, nothing is copied to the host and nothing waits, so the call can be captured into a graph.  d_states: the n
+ * states a step leaves; d_object_offsets: NULL (every object at rest) or n x n_objects x xyz, the step's; d_levels: each player's
+ * slot.  d_out: n x height x width bytes, map p at byte p * height * width, row-major, one class code per pixel.
+ * Every float below is binary32, every operation is rounded once and none is contracted; a + b * c means round(a + round(b * c)).
+ * Pixel to world.  The byte at row `row`, column i of map p is pixel (i, j) with j = row, or j = height - 1 - row with
+ * RDOOM_MAP_TOP_DOWN.  hw = (float)width * 0.5f, hh = (float)height * 0.5f (exact);
+ *   u = (((float)i + 0.5f) - hw) * scale;  v = (((float)j + 0.5f) - hh) * scale;
+ * without RDOOM_MAP_ROTATE map north is up and map east is right: q = (pos.x - v, pos.z - u), pos the player's position, q in
+ * world xz.  With it, (s, c) = the project's sincos of yaw (csrc/hip/sincos_rd.hpp, the step's), the forward f = (-s, -c) is up and
+ * r = (c, -s) is right: q.x = (pos.x + c * u) + (-s) * v;  q.z = (pos.z + (-s) * u) + (-c) * v.
+ * Segment distance, dist2(q, a, b, &ok): dx = b.x - a.x; dz = b.z - a.z; len2 = dx * dx + dz * dz; ok = len2 > 0; inv = 1.0f / len2
+ * (IEEE division); wx = q.x - a.x; wz = q.z - a.z; t = (wx * dx + wz * dz) * inv; t = t < 0 ? 0 : (t > 1 ? 1 : t);
+ * ex = wx - t * dx; ez = wz - t * dz; dist2 = ex * ex + ez * ez.
+ * Lines.  Line l of the player's level is skipped when its len2 is not > 0, or when flags & 0x80 without RDOOM_MAP_SHOW_HIDDEN.  Its
+ * class for player p: RDOOM_MAP_ONE_SIDED if front.present and back.present are not both 1 or flags & 0x20 (secret).  Otherwise, with
+ * the live heights ff = front.floor + off(front.floor_id), fc = front.ceiling + off(front.ceiling_id), bf and bc alike from back,
+ * off(o) = d_object_offsets[(p * n_objects + o) * 3 + 1] and 0 for o == 0, o >= n_objects or a NULL d_object_offsets:
+ *   RDOOM_MAP_CLOSED if fc <= ff or bc <= bf (a shut door); else RDOOM_MAP_FLOOR_STEP if ff != bf; else RDOOM_MAP_CEILING_STEP if
+ *   fc != bc; else RDOOM_MAP_FLAT, which is skipped without RDOOM_MAP_SHOW_FLAT.
+ * A line covers q when ok and dist2(q, a, b) <= w2, w2 = (half_width * scale) * (half_width * scale).
+ * Marker.  With marker > 0: m = marker * scale; e = (pos.x + f.x * (2.0f * m), pos.z + f.z * (2.0f * m)), f as above (under either
+ * orientation); the marker covers q when ok and dist2(q, pos.xz, e) <= m * m.
+ * Pixel value: RDOOM_MAP_PLAYER where the marker covers q; else the largest class among the lines that cover q; else
+ * RDOOM_MAP_NONE.  A maximum, so the value does not depend on the order in which lines are visited.  A comparison with a NaN is
+ * false: a player at a NaN position gets an all-zero map.
+ * A level slot >= the set's size is seen on the device only: that player's map is all RDOOM_MAP_NONE.
+ * Errors, all checked before anything is queued (RDOOM_BAD_ARG): a NULL handle or view, or (n > 0) NULL d_states / d_out / d_levels;
+ * width or height 0 or above 16384; scale or half_width not finite or not > 0; marker not finite or < 0; unknown flags;
+ * d_object_offsets with n_objects smaller than the game's objects (rdoom_world_trigger_arrays.n_objects; the set's:
+ * rdoom_worldset_info's); n x the view's 32 x 32 pixel tiles above 2^31 - 1; a handle created with RDOOM_WORLD_HOST_ONLY or living on
+ * another device.  n == 0 queues nothing. */
+rdoom_status rdoom_world_draw_maps(const rdoom_world *world, const rdoom_player_state *d_states, uint32_t n,
+                                   const float *d_object_offsets, uint32_t n_objects, const rdoom_map_view *view, uint8_t *d_out,
+                                   void *stream);
+rdoom_status rdoom_worldset_draw_maps(const rdoom_worldset *set, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                      uint32_t n, const float *d_object_offsets, uint32_t n_objects, const rdoom_map_view *view,
+                                      uint8_t *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -62,6 +62,27 @@ WORLDSET_LEVEL = np.dtype([('archive_index', '<u4'), ('destination', '<u4'), ('s
                            ('n_triggers', '<u4'), ('n_objects', '<u4'), ('node_depth', '<u4')])
 assert PLAYER_STATE.itemsize == 40 and PLAYER_INPUT.itemsize == 20 and PLAYER_CONFIG.itemsize == 32
 RAY_NO_HIT = 0xFFFFFFFF  # rdoom_world_cast_rays' hit index where nothing is within range
+# rdoom_map_line: one linedef of a level's line table (World.map_lines), and the class codes of a map pixel (World.draw_maps)
+MAP_SIDE = np.dtype([('present', '<u4'), ('floor', '<f4'), ('ceiling', '<f4'), ('floor_id', '<u4'), ('ceiling_id', '<u4')])
+MAP_LINE = np.dtype([('linedef', '<u4'), ('a', '<f4', 2), ('b', '<f4', 2), ('flags', '<u4'), ('special_type', '<u4'),
+                     ('front', MAP_SIDE), ('back', MAP_SIDE)])
+MAP_NONE, MAP_FLAT, MAP_CEILING_STEP, MAP_FLOOR_STEP, MAP_CLOSED, MAP_ONE_SIDED, MAP_PLAYER = 0, 1, 2, 3, 4, 5, 8
+MAP_ROTATE, MAP_SHOW_FLAT, MAP_SHOW_HIDDEN, MAP_TOP_DOWN = 1, 2, 4, 8
+LINE_SECRET, LINE_HIDDEN = 0x20, 0x80  # the linedef flags the map reads: drawn as one-sided; never on the map
+
+
+def _map_colors():
+    t = np.zeros((256, 3), np.uint8)
+    t[MAP_FLAT] = (96, 96, 96)            # grey: no height differs
+    t[MAP_CEILING_STEP] = (252, 252, 0)   # yellow
+    t[MAP_FLOOR_STEP] = (188, 120, 72)    # brown
+    t[MAP_CLOSED] = (0, 200, 200)         # a shut door: cyan, not one of Doom's
+    t[MAP_ONE_SIDED] = (252, 0, 0)        # red
+    t[MAP_PLAYER] = (255, 255, 255)
+    return t
+
+
+MAP_COLORS = _map_colors()  # (256, 3) uint8: torch.from_numpy(MAP_COLORS).cuda()[maps.long()] is an RGB map
 # rdoom_light_info (wad/src/light.rs:8-25 LightInfo): what BuiltLevel.light_infos returns and DeviceLights takes
 LIGHT_INFO = np.dtype([('level', '<f4'), ('has_effect', '<i4'), ('effect_kind', '<i4'), ('alt_level', '<f4'), ('speed', '<f4'),
                        ('duration', '<f4'), ('sync', '<f4')])
@@ -131,7 +152,8 @@ API_SYMBOLS = [
     'rdoom_worldset_level', 'rdoom_worldset_game_bytes', 'rdoom_worldset_game_reset', 'rdoom_worldset_step_game',
     'rdoom_poses_from_players_device', 'rdoom_batch_render_players', 'rdoom_batch_resolve_plane', 'rdoom_batch_read_plane',
     'rdoom_world_cast_rays', 'rdoom_worldset_cast_rays', 'rdoom_built_light_infos', 'rdoom_lightset_create', 'rdoom_lightset_destroy',
-    'rdoom_lightset_tables', 'rdoom_poses_from_players_device_clocked', 'rdoom_batch_render_players_clocked']
+    'rdoom_lightset_tables', 'rdoom_poses_from_players_device_clocked', 'rdoom_batch_render_players_clocked',
+    'rdoom_world_map_lines', 'rdoom_worldset_level_map_lines', 'rdoom_world_draw_maps', 'rdoom_worldset_draw_maps']
 
 _lib = None
 
@@ -1142,6 +1164,56 @@ def _cast_rays(call, states, levels, dirs, max_range, offsets, frac_out, hit_out
     return (frac_out, hit_out) if want_hit else frac_out
 
 
+class MapLines(ctypes.Structure):
+    _fields_ = [('lines', ctypes.c_void_p), ('n_lines', ctypes.c_uint32)]
+
+
+class MapView(ctypes.Structure):
+    _fields_ = [('width', ctypes.c_uint32), ('height', ctypes.c_uint32), ('scale', ctypes.c_float), ('half_width', ctypes.c_float),
+                ('marker', ctypes.c_float), ('flags', ctypes.c_uint32)]
+
+
+def _map_lines(get):
+    """World.map_lines / WorldSet.map_lines: a copy of the table get(&rdoom_map_lines) lends"""
+    a = MapLines()
+    _check(get(ctypes.byref(a)))
+    return BuiltLevel._view(None, a.lines, a.n_lines, MAP_LINE)
+
+
+def _draw_maps(call, states, levels, width, height, scale, offsets, half_width, marker, rotate, show_flat, show_hidden, top_down, out,
+               stream):
+    """World.draw_maps / WorldSet.draw_maps: the checks and the launch; call(states, levels, n, offsets, n_objects, view, out,
+    stream) is the C entry point with its handle bound"""
+    import torch
+    for t, what in ((states, 'states'),) + (((levels, 'levels'),) if levels is not None else ()) + \
+            (((offsets, 'offsets'),) if offsets is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous tensor on the GPU' % what)
+    n = _n_players(states)
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError('a map needs at least 1 x 1 pixels, got %d x %d' % (width, height))
+    if levels is not None and (levels.element_size() != 4 or levels.numel() != n):
+        raise ValueError('levels must hold one 32-bit slot per player (%d), got %s %s' % (n, levels.dtype, tuple(levels.shape)))
+    n_obj = 0
+    if offsets is not None:
+        if offsets.dtype != torch.float32 or offsets.dim() != 3 or offsets.shape[0] != n or offsets.shape[2] != 3:
+            raise ValueError('offsets must be a float32 (n, n_objects, 3) tensor for %d players, got %s %s'
+                             % (n, offsets.dtype, tuple(offsets.shape)))
+        n_obj = int(offsets.shape[1])
+    if out is None:
+        out = torch.empty((n, height, width), dtype=torch.uint8, device=states.device)
+    elif out.dtype != torch.uint8:
+        raise ValueError('out must be uint8')
+    po = _out_tensor(out, n * height * width, 'out')
+    view = MapView(width, height, scale, half_width, marker, (MAP_ROTATE if rotate else 0) | (MAP_SHOW_FLAT if show_flat else 0) |
+                   (MAP_SHOW_HIDDEN if show_hidden else 0) | (MAP_TOP_DOWN if top_down else 0))
+    v = ctypes.c_void_p
+    _check(call(v(states.data_ptr()), v(levels.data_ptr()) if levels is not None else None, n,
+                v(offsets.data_ptr()) if offsets is not None else None, n_obj, ctypes.byref(view), v(po), v(_stream_handle(stream))))
+    return out
+
+
 class World:
     """game::world::World on the host and the current device (rdoom_world_create): World::sweep_sphere for a batch of queries,
     Player::update for a batch of players."""
@@ -1270,6 +1342,25 @@ class World:
         object id for a door's or lift's -- triangle_objects()[hit] names what a ray of cast_rays ended on"""
         return _triangle_objects(self.arrays())
 
+    # ---- top-down maps -----------------------------------------------------------------------------------------------------
+    def map_lines(self):
+        """a copy of rdoom_world_map_lines: the level's line table, a MAP_LINE record per linedef with both vertices, in linedef
+        order (end points in world xz, flags, special, and per side the sector's heights and its floor and ceiling object ids)"""
+        return _map_lines(lambda a: lib().rdoom_world_map_lines(self._h, a))
+
+    def draw_maps(self, states, width, height, scale, offsets=None, half_width=0.75, marker=3.0, rotate=False, show_flat=False,
+                  show_hidden=False, top_down=False, out=None, stream=None):
+        """rdoom_world_draw_maps: every player's top-down map, a uint8 (n, height, width) GPU tensor of MAP_* class codes, centred
+        on the player, `scale` world units per pixel.  states: the tensor a step leaves (n * 40 bytes); offsets: None or
+        step_game's (n, n_objects, 3) tensor, so that a door a player opened shows open in that player's map.  half_width: half
+        a line's thickness in pixels; marker: the player marker's size in pixels (0: none); rotate: the player's view direction is
+        up (else map north); show_flat / show_hidden: draw lines between equal sectors / linedefs flagged never-on-the-map;
+        top_down: row 0 is the top row (else the bottom row, as Batch frames).  out: an optional preallocated tensor.  Asynchronous
+        on `stream`; nothing is copied to the host.  torch.from_numpy(MAP_COLORS).cuda()[maps.long()] colours the maps."""
+        L = lib()
+        return _draw_maps(lambda st, lv, *rest: L.rdoom_world_draw_maps(self._h, st, *rest), states, None, width, height, scale, offsets,
+                          half_width, marker, rotate, show_flat, show_hidden, top_down, out, stream)
+
 
 class WorldSetLevelInfo(ctypes.Structure):
     _fields_ = [('archive_index', ctypes.c_uint32), ('destination', ctypes.c_uint32), ('start_pos', ctypes.c_float * 3),
@@ -1384,3 +1475,15 @@ class WorldSet:
     def triangle_objects(self, slot):
         """World.triangle_objects of slot `slot`: the object id of each triangle of arrays(slot)['triangles']"""
         return _triangle_objects(self.arrays(slot))
+
+    def map_lines(self, slot):
+        """World.map_lines of slot `slot`"""
+        return _map_lines(lambda a: lib().rdoom_worldset_level_map_lines(self._h, int(slot), a))
+
+    def draw_maps(self, states, levels, width, height, scale, offsets=None, half_width=0.75, marker=3.0, rotate=False, show_flat=False,
+                  show_hidden=False, top_down=False, out=None, stream=None):
+        """rdoom_worldset_draw_maps: World.draw_maps for players spread over the set's levels (levels: game_state's tensor of
+        slots); a player whose slot is not in the set gets an all-zero map"""
+        L = lib()
+        return _draw_maps(lambda st, lv, *rest: L.rdoom_worldset_draw_maps(self._h, st, lv, *rest), states, levels, width, height, scale,
+                          offsets, half_width, marker, rotate, show_flat, show_hidden, top_down, out, stream)

@@ -7,7 +7,8 @@
 // vector / scalar divides every component, normalize_or_zero = v / max(|v|, f32::EPSILON)); the build passes
 // -ffp-contract=off and HIP divides and takes square roots correctly rounded, so every result is the one an IEEE host
 // computes with the same expressions.  No fastmath.hpp short forms, no device libm: sin / cos come from sincos_rd (sincos_rd.hpp),
-// a player's orientation quaternion and camera eye from player_quat.hpp.
+// a player's orientation quaternion and camera eye from player_quat.hpp.  The level pick, the checked launch and the device check
+// are world_shared.hpp's, shared with the map kernels (automap.hip), whose device line table the handles here own.
 //
 // Shape: one lane per query / player -- the sweeps of one player are strictly sequential -- and one wave per workgroup.  Each
 // lane walks the BSP with its own node stack in LDS (word `slot * 64 + lane`: no bank conflicts), sized by the tree's depth at
@@ -22,6 +23,7 @@
 #include "../host/game_world.hpp"
 #include "kernels.hpp"
 #include "player_quat.hpp"
+#include "world_shared.hpp"
 
 namespace {
 
@@ -54,6 +56,7 @@ using rdoom_dev::Quat;
 using rdoom_dev::rotate;
 using rdoom_dev::sincos_rd;
 using rdoom_dev::V3;
+using rdoom_dev::with_level;  // world_shared.hpp: the level pick, shared with the map kernels
 __device__ __forceinline__ V3 v3(float x, float y, float z) { return V3{x, y, z}; }
 __device__ __forceinline__ V3 operator+(V3 a, V3 b) { return v3(a.x + b.x, a.y + b.y, a.z + b.z); }
 __device__ __forceinline__ V3 operator-(V3 a, V3 b) { return v3(a.x - b.x, a.y - b.y, a.z - b.z); }
@@ -632,14 +635,6 @@ __device__ __forceinline__ GameView level_view(const GameView &set, const DevSet
 // requests the next level and still runs in the old one (STAGE_REQUESTED); tick t + 2 loads it, resets the player and runs in it.
 constexpr uint32_t STAGE_NONE = 0u, STAGE_EXITED = 1u, STAGE_REQUESTED = 2u;
 
-// `use(slot)` for the level record of a lane on level `lv`: the wave's one slot as a wave-uniform value when every lane of the
-// wave is on the same level, so that what `use` loads from that record are scalar loads; the lane's own otherwise
-template <class Use>
-__device__ __forceinline__ void with_level(uint32_t lv, Use use) {
-  const uint32_t u = __builtin_amdgcn_readfirstlane(lv);
-  if (__builtin_amdgcn_ballot_w64(lv != u) == 0) use(u);
-  else use(lv);
-}
 // the set's world seen from one level: its own dynamic chunks (its nodes start at the level's root)
 __device__ __forceinline__ WorldView level_world(const WorldView &w, uint32_t dyn_start, uint32_t n_dynamics) {
   return WorldView{w.nodes, w.chunks, w.tris, w.verts, w.dynamics + dyn_start, n_dynamics, w.stack_cap};
@@ -924,6 +919,7 @@ struct rdoom_world {
   bool on_device = false;
   int device = -1;
   DevArrays d;
+  rdoom::MapDevice map;  // the level's line table, as automap.hip lays it out
 };
 
 struct rdoom_worldset {
@@ -935,7 +931,13 @@ struct rdoom_worldset {
   DevArrays d;
   DevSetLevel *d_table = nullptr;
   uint32_t *d_tri_starts = nullptr;  // each level's triangle base in the concatenation (the ray cast's)
+  rdoom::MapDevice map;              // the levels' line tables, one after the other
 };
+
+namespace rdoom {
+MapSource map_source(const rdoom_world *w) { return MapSource{&w->map, w->host.game_objects, w->on_device, w->device}; }
+MapSource map_source(const rdoom_worldset *s) { return MapSource{&s->map, s->host.game_objects, s->on_device, s->device}; }
+}  // namespace rdoom
 
 namespace {
 // the host build of rdoom_world_create / rdoom_worldset_create: what it throws becomes a status (nothing unwinds across the C ABI)
@@ -986,21 +988,10 @@ WorldView view(const DevArrays &d, uint32_t n_dynamics, uint32_t node_depth) {
 // kernel(v, args...) with one lane per query, player or ray: one wave per workgroup, each lane's node stack in LDS
 template <class Kernel, class... Args>
 rdoom_status launch_lanes(Kernel kernel, uint32_t n_lanes, const WorldView &v, void *stream, Args... args) {
-  hipLaunchKernelGGL(kernel, dim3((n_lanes + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t), (hipStream_t)stream, v,
-                     args...);
-  HIP_TRY(hipGetLastError());
-  return RDOOM_OK;
+  return rdoom::launch_checked(kernel, dim3((n_lanes + WAVE - 1) / WAVE), dim3(WAVE), WAVE * v.stack_cap * sizeof(uint32_t), stream, v,
+                               args...);
 }
-
-// noun: "the world" or "the world set"
-template <class Handle>
-rdoom_status check_device(const Handle *h, const char *noun) {
-  if (!h->on_device) return rdoom::fail(RDOOM_BAD_ARG, "%s was created with RDOOM_WORLD_HOST_ONLY: it has no device copy", noun);
-  int cur = -1;
-  HIP_TRY(hipGetDevice(&cur));
-  if (cur != h->device) return rdoom::fail(RDOOM_BAD_ARG, "%s lives on device %d, the current device is %d", noun, h->device, cur);
-  return RDOOM_OK;
-}
+using rdoom::check_device;  // world_shared.hpp
 
 GameView game_layout(const rdoom::game::World &h) {  // the layout include/rdoom.h documents at rdoom_world_game_bytes
   const uint32_t t = (uint32_t)h.triggers.size(), o = h.game_objects;
@@ -1081,6 +1072,7 @@ extern "C" {
 void rdoom_world_destroy(rdoom_world *w) {
   if (!w) return;
   free_world(w->d);
+  rdoom::map_free(w->map);
   delete w;
 }
 
@@ -1100,6 +1092,7 @@ rdoom_status rdoom_world_create(const rdoom_wad *wad, uint32_t level_index, uint
   if (!(flags & RDOOM_WORLD_HOST_ONLY)) {
     HIP_TRY(hipGetDevice(&w->device));
     if (rdoom_status st = upload_world(h, w->d)) return st;
+    if (rdoom_status st = rdoom::map_upload(h.map_lines, {make_uint2(0u, (uint32_t)h.map_lines.size())}, w->map)) return st;
     w->on_device = true;
   }
   *out_world = w.release();
@@ -1148,6 +1141,12 @@ rdoom_status rdoom_world_triggers(const rdoom_world *w, rdoom_world_trigger_arra
   return RDOOM_OK;
 }
 
+rdoom_status rdoom_world_map_lines(const rdoom_world *w, rdoom_map_lines *out) {
+  if (!w || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  *out = rdoom_map_lines{w->host.map_lines.data(), (uint32_t)w->host.map_lines.size()};
+  return RDOOM_OK;
+}
+
 rdoom_status rdoom_world_game_bytes(const rdoom_world *w, uint64_t *bytes_per_player) {
   if (!w || !bytes_per_player) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   *bytes_per_player = (uint64_t)game_view(w).words * sizeof(uint32_t);
@@ -1183,6 +1182,7 @@ rdoom_status rdoom_world_step_game(const rdoom_world *w, rdoom_player_state *d_s
 void rdoom_worldset_destroy(rdoom_worldset *s) {
   if (!s) return;
   free_world(s->d);
+  rdoom::map_free(s->map);
   if (s->d_table) (void)hipFree(s->d_table);
   if (s->d_tri_starts) (void)hipFree(s->d_tri_starts);
   delete s;
@@ -1222,6 +1222,9 @@ rdoom_status rdoom_worldset_create(const rdoom_wad *wad, const uint32_t *level_i
     std::vector<uint32_t> tri_starts;
     for (const rdoom::game::WorldSetLevel &t : h.table) tri_starts.push_back(t.triangle_base);
     if (rdoom_status st = upload(&s->d_tri_starts, tri_starts.data(), tri_starts.size() * sizeof(uint32_t))) return st;
+    std::vector<uint2> map_ranges;
+    for (size_t i = 0; i < h.levels.size(); i++) map_ranges.push_back(make_uint2(h.table[i].map_base, (uint32_t)h.levels[i].map_lines.size()));
+    if (rdoom_status st = rdoom::map_upload(h.all.map_lines, map_ranges, s->map)) return st;
     s->on_device = true;
   }
   *out_set = s.release();
@@ -1249,6 +1252,14 @@ rdoom_status rdoom_worldset_level(const rdoom_worldset *s, uint32_t slot, rdoom_
   out->node_depth = l.node_depth;
   fill_arrays(l, out->world);
   fill_triggers(l, out->triggers);
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_worldset_level_map_lines(const rdoom_worldset *s, uint32_t slot, rdoom_map_lines *out) {
+  if (!s || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (slot >= s->host.levels.size()) return rdoom::fail(RDOOM_BAD_ARG, "slot %u of a set of %zu levels", slot, s->host.levels.size());
+  const std::vector<rdoom_map_line> &lines = s->host.levels[slot].map_lines;
+  *out = rdoom_map_lines{lines.data(), (uint32_t)lines.size()};
   return RDOOM_OK;
 }
 

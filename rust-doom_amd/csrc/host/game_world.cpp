@@ -148,6 +148,29 @@ World build_world(const LoadedWad &w, size_t level_index) {
     r.effect_end = (uint32_t)out.effects.size();
     out.triggers.push_back(r);
   }
+  // the map's line table: every linedef whose two vertices exist, in linedef order (wad/src/types.rs:49-57 WadLinedef;
+  // wad/src/level.rs:83-87, 131-151 vertex / left_sidedef / right_sidedef / sidedef_sector), each side with its sector's heights and the
+  // floor and ceiling objects SectorInfo gives it (wad/src/visitor.rs:145-156, 569-588: 0 unless a DynamicSectorInfo moves it)
+  for (size_t i = 0; i < level.linedefs.size(); i++) {
+    const WadLinedef &l = level.linedefs[i];
+    const auto a = level.vertex(l.start_vertex), b = level.vertex(l.end_vertex);
+    if (!a || !b) continue;
+    rdoom_map_line m{};
+    m.linedef = (uint32_t)i;
+    m.a[0] = a->x, m.a[1] = a->y, m.b[0] = b->x, m.b[1] = b->y;
+    m.flags = l.flags, m.special_type = l.special_type;
+    const auto side = [&](int16_t index) {
+      rdoom_map_side s{};
+      const WadSector *sector = level.sidedef_sector(level.side(index));
+      if (!sector) return s;
+      s.present = 1;
+      s.floor = from_wad_height(sector->floor_height), s.ceiling = from_wad_height(sector->ceiling_height);
+      if (const DynamicSectorInfo *d = analysis.dynamic(level.sector_id(sector))) s.floor_id = d->floor_id.v, s.ceiling_id = d->ceiling_id.v;
+      return s;
+    };
+    m.front = side(l.right_side), m.back = side(l.left_side);
+    out.map_lines.push_back(m);
+  }
   return out;
 }
 
@@ -172,7 +195,7 @@ WorldSet build_world_set(const LoadedWad &w, const uint32_t *level_indices, size
     t.node_base = (uint32_t)all.nodes.size(), t.chunk_base = (uint32_t)all.chunks.size();
     t.triangle_base = (uint32_t)all.triangles.size(), t.vert_base = (uint32_t)(all.verts.size() / 3);
     t.dynamic_base = (uint32_t)all.dynamics.size(), t.trigger_base = (uint32_t)all.triggers.size();
-    t.effect_base = (uint32_t)all.effects.size();
+    t.effect_base = (uint32_t)all.effects.size(), t.map_base = (uint32_t)all.map_lines.size();
     for (WorldNode nd : l.nodes) {
       for (int32_t *c : {&nd.positive, &nd.negative}) *c = *c > 0 ? *c + (int32_t)t.node_base : *c - (int32_t)t.chunk_base;
       all.nodes.push_back(nd);
@@ -187,6 +210,7 @@ WorldSet build_world_set(const LoadedWad &w, const uint32_t *level_indices, size
       all.triggers.push_back(tr);
     }
     all.effects.insert(all.effects.end(), l.effects.begin(), l.effects.end());
+    all.map_lines.insert(all.map_lines.end(), l.map_lines.begin(), l.map_lines.end());
     all.n_objects = std::max(all.n_objects, l.n_objects);
     set.game_objects = std::max(set.game_objects, l.game_objects);
     set.node_depth = std::max(set.node_depth, l.node_depth);

@@ -38,6 +38,8 @@ struct World {
   std::vector<rdoom_trigger> triggers;
   std::vector<rdoom_move_effect> effects;
   uint32_t game_objects = 1;  // max(1, LevelAnalysis::num_objects)
+  // the level's line table for the top-down map (include/rdoom.h rdoom_map_line): one record per linedef with both vertices
+  std::vector<rdoom_map_line> map_lines;
   float start_pos[3] = {0, 0, 0};  // the player's start, as the renderer's Builder takes it (rdoom_built_start)
   float start_yaw = 0.0f;
 };
@@ -48,13 +50,13 @@ struct World {
 constexpr uint32_t NO_DESTINATION = 0xFFFFFFFFu;
 struct WorldSetLevel {
   uint32_t archive_index, destination;
-  uint32_t node_base, chunk_base, triangle_base, vert_base, dynamic_base, trigger_base, effect_base;  // in the concatenation
+  uint32_t node_base, chunk_base, triangle_base, vert_base, dynamic_base, trigger_base, effect_base, map_base;  // in the concatenation
 };
 struct WorldSet {
   std::vector<World> levels;
   std::vector<WorldSetLevel> table;
   // the concatenation: node children, chunk and dynamic triangle ranges, triangle vertex indices and trigger effect ranges
-  // rebased.  A child packed as 0 (Leaf(0), never linked or not) becomes minus its own level's chunk base, so it still reads as
+  // rebased (the map lines are concatenated as they are: their object ids are each level's own).  A child packed as 0 (Leaf(0), never linked or not) becomes minus its own level's chunk base, so it still reads as
   // that level's leaf 0.
   World all;
   uint32_t game_objects = 1;  // the largest of the levels' game_objects
