@@ -864,6 +864,59 @@ rdoom_status rdoom_worldset_draw_maps(const rdoom_worldset *set, const rdoom_pla
                                       uint32_t n, const float *d_object_offsets, uint32_t n_objects, const rdoom_map_view *view,
                                       uint8_t *d_out, void *stream);
 
+/* ---- seen lines: each player's map revealed as it explores -----------------------------------------------------
+ * Doom's automap draws a line only once the player has had it in view; its visibility is two-dimensional -- solid-seg clipping on
+ * map lines, solid meaning one-sided or shut -- and eye height plays no part.  This is that idea made exact: a fan of 2-D rays from
+ * the player through the line table, a set of seen lines per player kept on the device as a row of bits, and the maps drawn
+ * through it.  Every float below is binary32, every operation is rounded once and none is contracted; divisions are IEEE;
+ * a * b - c * d means round(round(a * b) - round(c * d)).
+ * Fan.  d_dirs: ONE table of n_rays directions (right, forward), two floats per ray, shared by every player; it need not be
+ * normalised.  With (s, c) = the project's sincos of the player's yaw (csrc/hip/sincos_rd.hpp), the map contract's r = (c, -s) and
+ * f = (-s, -c):  dir.x = c * right + (-s) * forward;  dir.z = (-s) * right + (-c) * forward;  vel.x = dir.x * max_range;
+ * vel.z = dir.z * max_range;  o = (pos.x, pos.z).  The ray is o + t * vel, t in [0, 1].
+ * Ray against line l, a and b its end points:  dx = b.x - a.x;  dz = b.z - a.z;  len2 = dx * dx + dz * dz;  wx = a.x - o.x;
+ * wz = a.z - o.z;  den = vel.x * dz - vel.z * dx;  t = (wx * dz - wz * dx) / den;  u = (wx * vel.z - wz * vel.x) / den.
+ * The ray hits the line when len2 > 0, den != 0, u >= 0, u <= 1, t >= 0 and t <= 1.  (A zero den gives a NaN or an infinity, a NaN
+ * fails every comparison: no hit.)
+ * Blocking.  Line l blocks player p's sight when front.present and back.present are not both 1, or when its opening is empty under
+ * the live heights: with ff, fc, bf, bc as the map contract defines them (height + off(id) from row p of d_object_offsets),
+ * lo = ff > bf ? ff : bf;  hi = fc < bc ? fc : bc;  the line blocks when !(hi > lo).  So a shut door blocks in the game of the
+ * player who has not opened it, and only there.  No flag blocks: a secret line (0x20) is seen through like any other two-sided one.
+ * Seen.  For ray r, T_r is the smallest t among the blocking lines it hits, or 1 if it hits none.  Line l is seen by r when r hits
+ * l with t <= T_r, t being the value that entered the minimum: the blocking line itself is seen, and every line tied with it.
+ * A line is seen by the player when one of the n_rays rays sees it.
+ * Accumulation.  d_seen: n rows of `stride` uint32 words.  Bit l % 32 of word p * stride + l / 32 is OR-ed in when player p sees
+ * line l, l the index in the level's own table (rdoom_world_map_lines / rdoom_worldset_level_map_lines).  Bits are never cleared;
+ * words of a row beyond the level's ceil(n_lines / 32) and bits beyond n_lines are never written; the caller zeroes a row to start
+ * an episode.  A minimum followed by an OR: the result does not depend on the order in which rays or lines are visited.
+ * d_new_out (n uint32, may be NULL): d_new_out[p] = the number of bits this call set in row p that were clear before.
+ * A comparison with a NaN is false: a player at a NaN position marks nothing and counts 0.  A level slot >= the set's size is seen
+ * on the device only: that player's row is untouched and its count is 0.
+ * One launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so the call can be
+ * captured into a graph.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): a NULL handle, or (n > 0) NULL d_states /
+ * d_seen / d_dirs / d_levels; n_rays == 0; max_range not finite or not > 0; a stride smaller than ceil(n_lines / 32) of the world's
+ * table (the set's: of its largest level's); d_object_offsets with n_objects smaller than the game's objects (as for
+ * rdoom_world_draw_maps); a handle created with RDOOM_WORLD_HOST_ONLY or living on another device.  n == 0 queues nothing. */
+rdoom_status rdoom_world_reveal_lines(const rdoom_world *world, const rdoom_player_state *d_states, uint32_t n, const float *d_dirs,
+                                      uint32_t n_rays, float max_range, const float *d_object_offsets, uint32_t n_objects,
+                                      uint32_t *d_seen, uint32_t stride, uint32_t *d_new_out, void *stream);
+rdoom_status rdoom_worldset_reveal_lines(const rdoom_worldset *set, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                         uint32_t n, const float *d_dirs, uint32_t n_rays, float max_range,
+                                         const float *d_object_offsets, uint32_t n_objects, uint32_t *d_seen, uint32_t stride,
+                                         uint32_t *d_new_out, void *stream);
+/* The maps drawn through the set: rdoom_world_draw_maps / rdoom_worldset_draw_maps in every respect, except that player p's map
+ * additionally skips line l unless bit l of row p of d_seen (rows of `stride` words, as above) is set or the linedef carries
+ * RDOOM_LINE_MAPPED, Doom's "already on the map" flag (WadLinedef flags, in the table verbatim).  The marker is always drawn.  A NULL
+ * d_seen gives the omniscient map, the bytes of rdoom_world_draw_maps.  One more error (RDOOM_BAD_ARG): a non-NULL d_seen with a
+ * stride smaller than the table's words. */
+#define RDOOM_LINE_MAPPED 0x100u
+rdoom_status rdoom_world_draw_maps_seen(const rdoom_world *world, const rdoom_player_state *d_states, uint32_t n,
+                                        const float *d_object_offsets, uint32_t n_objects, const rdoom_map_view *view,
+                                        const uint32_t *d_seen, uint32_t stride, uint8_t *d_out, void *stream);
+rdoom_status rdoom_worldset_draw_maps_seen(const rdoom_worldset *set, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                           uint32_t n, const float *d_object_offsets, uint32_t n_objects, const rdoom_map_view *view,
+                                           const uint32_t *d_seen, uint32_t stride, uint8_t *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,7 @@ MAP_LINE = np.dtype([('linedef', '<u4'), ('a', '<f4', 2), ('b', '<f4', 2), ('fla
 MAP_NONE, MAP_FLAT, MAP_CEILING_STEP, MAP_FLOOR_STEP, MAP_CLOSED, MAP_ONE_SIDED, MAP_PLAYER = 0, 1, 2, 3, 4, 5, 8
 MAP_ROTATE, MAP_SHOW_FLAT, MAP_SHOW_HIDDEN, MAP_TOP_DOWN = 1, 2, 4, 8
 LINE_SECRET, LINE_HIDDEN = 0x20, 0x80  # the linedef flags the map reads: drawn as one-sided; never on the map
+LINE_MAPPED = 0x100  # RDOOM_LINE_MAPPED, Doom's "already on the map": drawn through a seen set whether seen or not
 
 
 def _map_colors():
@@ -153,7 +154,8 @@ API_SYMBOLS = [
     'rdoom_poses_from_players_device', 'rdoom_batch_render_players', 'rdoom_batch_resolve_plane', 'rdoom_batch_read_plane',
     'rdoom_world_cast_rays', 'rdoom_worldset_cast_rays', 'rdoom_built_light_infos', 'rdoom_lightset_create', 'rdoom_lightset_destroy',
     'rdoom_lightset_tables', 'rdoom_poses_from_players_device_clocked', 'rdoom_batch_render_players_clocked',
-    'rdoom_world_map_lines', 'rdoom_worldset_level_map_lines', 'rdoom_world_draw_maps', 'rdoom_worldset_draw_maps']
+    'rdoom_world_map_lines', 'rdoom_worldset_level_map_lines', 'rdoom_world_draw_maps', 'rdoom_worldset_draw_maps',
+    'rdoom_world_reveal_lines', 'rdoom_worldset_reveal_lines', 'rdoom_world_draw_maps_seen', 'rdoom_worldset_draw_maps_seen']
 
 _lib = None
 
@@ -1180,10 +1182,19 @@ def _map_lines(get):
     return BuiltLevel._view(None, a.lines, a.n_lines, MAP_LINE)
 
 
+def _seen_rows(seen, n, words):
+    """(pointer, stride in words) of a caller's rows of seen bits: a contiguous 32-bit (n, stride) GPU tensor with stride >= words"""
+    import torch
+    if not isinstance(seen, torch.Tensor) or seen.device.type != 'cuda' or not seen.is_contiguous() or seen.dim() != 2 or \
+            seen.element_size() != 4 or seen.dtype.is_floating_point or seen.shape[0] != n or seen.shape[1] < words:
+        raise ValueError('seen must be a contiguous 32-bit integer (n, words) tensor on the GPU for %d players with words >= %d' % (n, words))
+    return seen.data_ptr(), int(seen.shape[1])
+
+
 def _draw_maps(call, states, levels, width, height, scale, offsets, half_width, marker, rotate, show_flat, show_hidden, top_down, out,
-               stream):
-    """World.draw_maps / WorldSet.draw_maps: the checks and the launch; call(states, levels, n, offsets, n_objects, view, out,
-    stream) is the C entry point with its handle bound"""
+               stream, seen=None, words=0):
+    """World.draw_maps / WorldSet.draw_maps: the checks and the launch; call(states, levels, n, offsets, n_objects, view, seen,
+    stride, out, stream) is the C entry point with its handle bound"""
     import torch
     for t, what in ((states, 'states'),) + (((levels, 'levels'),) if levels is not None else ()) + \
             (((offsets, 'offsets'),) if offsets is not None else ()):
@@ -1208,10 +1219,67 @@ def _draw_maps(call, states, levels, width, height, scale, offsets, half_width, 
     po = _out_tensor(out, n * height * width, 'out')
     view = MapView(width, height, scale, half_width, marker, (MAP_ROTATE if rotate else 0) | (MAP_SHOW_FLAT if show_flat else 0) |
                    (MAP_SHOW_HIDDEN if show_hidden else 0) | (MAP_TOP_DOWN if top_down else 0))
+    ps, stride = _seen_rows(seen, n, words) if seen is not None else (None, 0)
     v = ctypes.c_void_p
     _check(call(v(states.data_ptr()), v(levels.data_ptr()) if levels is not None else None, n,
-                v(offsets.data_ptr()) if offsets is not None else None, n_obj, ctypes.byref(view), v(po), v(_stream_handle(stream))))
+                v(offsets.data_ptr()) if offsets is not None else None, n_obj, ctypes.byref(view), v(ps), stride, v(po),
+                v(_stream_handle(stream))))
     return out
+
+
+def map_fan(n_rays, fov):
+    """a direction table for reveal_lines: n_rays unit directions (right, forward) in the player's map frame, a float32 (n_rays, 2)
+    array, evenly spaced across `fov` radians and centred on straight ahead (ray 0 is the leftmost, at fov / 2 to the left; an odd
+    n_rays has the ray (0, 1))"""
+    n_rays = int(n_rays)
+    if n_rays < 1:
+        raise ValueError('n_rays must be at least 1')
+    angle = np.linspace(-0.5 * fov, 0.5 * fov, n_rays) if n_rays > 1 else np.zeros(1)
+    return np.stack([np.sin(angle), np.cos(angle)], 1).astype(np.float32)
+
+
+def unpack_seen(row, n_lines):
+    """a row of reveal_lines' bits (a numpy array or tensor of 32-bit words) as a bool array of n_lines: [l] = line l is seen"""
+    if not isinstance(row, np.ndarray):
+        row = row.cpu().numpy()
+    words = np.ascontiguousarray(row).reshape(-1).view(np.uint32)
+    n_lines = int(n_lines)
+    if len(words) * 32 < n_lines:
+        raise ValueError('%d words hold fewer than %d lines' % (len(words), n_lines))
+    l = np.arange(n_lines)
+    return ((words[l >> 5] >> (l & 31).astype(np.uint32)) & 1).astype(bool)
+
+
+def _reveal_lines(call, words, states, levels, fan, max_range, offsets, seen, new_out, stream):
+    """World.reveal_lines / WorldSet.reveal_lines: the checks and the launch; call(states, levels, n, dirs, n_rays, max_range,
+    offsets, n_objects, seen, stride, new_out, stream) is the C entry point with its handle bound"""
+    import torch
+    for t, what in ((states, 'states'), (fan, 'fan')) + (((levels, 'levels'),) if levels is not None else ()) + \
+            (((offsets, 'offsets'),) if offsets is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous tensor on the GPU' % what)
+    n = _n_players(states)
+    if fan.dtype != torch.float32 or fan.dim() != 2 or fan.shape[1] != 2 or fan.shape[0] == 0:
+        raise ValueError('fan must be a float32 (n_rays, 2) tensor with n_rays >= 1, got %s %s' % (fan.dtype, tuple(fan.shape)))
+    if levels is not None and (levels.element_size() != 4 or levels.numel() != n):
+        raise ValueError('levels must hold one 32-bit slot per player (%d), got %s %s' % (n, levels.dtype, tuple(levels.shape)))
+    n_obj = 0
+    if offsets is not None:
+        if offsets.dtype != torch.float32 or offsets.dim() != 3 or offsets.shape[0] != n or offsets.shape[2] != 3:
+            raise ValueError('offsets must be a float32 (n, n_objects, 3) tensor for %d players, got %s %s'
+                             % (n, offsets.dtype, tuple(offsets.shape)))
+        n_obj = int(offsets.shape[1])
+    if seen is None:
+        seen = torch.zeros((n, words), dtype=torch.int32, device=states.device)
+    ps, stride = _seen_rows(seen, n, words)
+    if new_out is not None and (new_out.element_size() != 4 or new_out.dtype.is_floating_point):
+        raise ValueError('new_out must hold 32-bit integers')
+    pn = _out_tensor(new_out, n * 4, 'new_out')
+    v = ctypes.c_void_p
+    _check(call(v(states.data_ptr()), v(levels.data_ptr()) if levels is not None else None, n, v(fan.data_ptr()), int(fan.shape[0]),
+                ctypes.c_float(max_range), v(offsets.data_ptr()) if offsets is not None else None, n_obj, v(ps), stride, v(pn),
+                v(_stream_handle(stream))))
+    return seen
 
 
 class World:
@@ -1349,17 +1417,37 @@ class World:
         return _map_lines(lambda a: lib().rdoom_world_map_lines(self._h, a))
 
     def draw_maps(self, states, width, height, scale, offsets=None, half_width=0.75, marker=3.0, rotate=False, show_flat=False,
-                  show_hidden=False, top_down=False, out=None, stream=None):
+                  show_hidden=False, top_down=False, out=None, stream=None, seen=None):
         """rdoom_world_draw_maps: every player's top-down map, a uint8 (n, height, width) GPU tensor of MAP_* class codes, centred
         on the player, `scale` world units per pixel.  states: the tensor a step leaves (n * 40 bytes); offsets: None or
         step_game's (n, n_objects, 3) tensor, so that a door a player opened shows open in that player's map.  half_width: half
         a line's thickness in pixels; marker: the player marker's size in pixels (0: none); rotate: the player's view direction is
         up (else map north); show_flat / show_hidden: draw lines between equal sectors / linedefs flagged never-on-the-map;
         top_down: row 0 is the top row (else the bottom row, as Batch frames).  out: an optional preallocated tensor.  Asynchronous
-        on `stream`; nothing is copied to the host.  torch.from_numpy(MAP_COLORS).cuda()[maps.long()] colours the maps."""
+        on `stream`; nothing is copied to the host.  torch.from_numpy(MAP_COLORS).cuda()[maps.long()] colours the maps.
+        seen: None (every line of the level: the cheat map) or reveal_lines' (n, words) tensor: player p's map then shows only
+        the lines whose bit is set in row p and the linedefs flagged LINE_MAPPED (rdoom_world_draw_maps_seen)."""
         L = lib()
-        return _draw_maps(lambda st, lv, *rest: L.rdoom_world_draw_maps(self._h, st, *rest), states, None, width, height, scale, offsets,
-                          half_width, marker, rotate, show_flat, show_hidden, top_down, out, stream)
+        return _draw_maps(lambda st, lv, *rest: L.rdoom_world_draw_maps_seen(self._h, st, *rest), states, None, width, height, scale,
+                          offsets, half_width, marker, rotate, show_flat, show_hidden, top_down, out, stream, seen, self.seen_words())
+
+    # ---- seen lines --------------------------------------------------------------------------------------------------------
+    def seen_words(self):
+        """the 32-bit words a row of seen bits takes: a bit per line of map_lines()"""
+        a = MapLines()
+        _check(lib().rdoom_world_map_lines(self._h, ctypes.byref(a)))
+        return (a.n_lines + 31) // 32
+
+    def reveal_lines(self, states, fan, max_range, offsets=None, seen=None, new_out=None, stream=None):
+        """rdoom_world_reveal_lines: marks the lines every player has in view -- a fan of 2-D rays (map_fan, a float32 (n_rays, 2)
+        GPU tensor shared by all players) of length max_range from the player through the line table, stopped by one-sided lines
+        and by two-sided ones whose opening is empty in that player's game (offsets: None or step_game's tensor, so a shut door
+        blocks until that player opens it).  seen: an int32 (n, words >= seen_words()) GPU tensor whose bits are OR-ed into, bit
+        l % 32 of word l // 32 of row p for line l of map_lines(); None allocates a zeroed one.  Returns seen.  new_out: an
+        optional 32-bit integer tensor of n that receives how many bits of each row this call set.  Asynchronous on `stream`."""
+        L = lib()
+        return _reveal_lines(lambda st, lv, *rest: L.rdoom_world_reveal_lines(self._h, st, *rest), self.seen_words(), states, None, fan,
+                             max_range, offsets, seen, new_out, stream)
 
 
 class WorldSetLevelInfo(ctypes.Structure):
@@ -1481,9 +1569,22 @@ class WorldSet:
         return _map_lines(lambda a: lib().rdoom_worldset_level_map_lines(self._h, int(slot), a))
 
     def draw_maps(self, states, levels, width, height, scale, offsets=None, half_width=0.75, marker=3.0, rotate=False, show_flat=False,
-                  show_hidden=False, top_down=False, out=None, stream=None):
+                  show_hidden=False, top_down=False, out=None, stream=None, seen=None):
         """rdoom_worldset_draw_maps: World.draw_maps for players spread over the set's levels (levels: game_state's tensor of
-        slots); a player whose slot is not in the set gets an all-zero map"""
+        slots); a player whose slot is not in the set gets an all-zero map.  seen: as for World.draw_maps, rows of at least
+        seen_words() words, a row's bits numbering the lines of the player's own level"""
         L = lib()
-        return _draw_maps(lambda st, lv, *rest: L.rdoom_worldset_draw_maps(self._h, st, lv, *rest), states, levels, width, height, scale,
-                          offsets, half_width, marker, rotate, show_flat, show_hidden, top_down, out, stream)
+        return _draw_maps(lambda st, lv, *rest: L.rdoom_worldset_draw_maps_seen(self._h, st, lv, *rest), states, levels, width, height,
+                          scale, offsets, half_width, marker, rotate, show_flat, show_hidden, top_down, out, stream, seen, self.seen_words())
+
+    def seen_words(self):
+        """the 32-bit words a row of seen bits takes in this set: its largest level's World.seen_words()"""
+        return max((len(self.map_lines(s)) + 31) // 32 for s in range(self.n_levels)) if self.n_levels else 0
+
+    def reveal_lines(self, states, levels, fan, max_range, offsets=None, seen=None, new_out=None, stream=None):
+        """rdoom_worldset_reveal_lines: World.reveal_lines for players spread over the set's levels (levels: game_state's tensor of
+        slots).  A row's bits number the lines of the player's own level (map_lines(slot)); a player whose slot is not in the set
+        keeps its row and counts 0 new lines.  A player who changes level needs its row zeroed by the caller."""
+        L = lib()
+        return _reveal_lines(lambda st, lv, *rest: L.rdoom_worldset_reveal_lines(self._h, st, lv, *rest), self.seen_words(), states,
+                             levels, fan, max_range, offsets, seen, new_out, stream)

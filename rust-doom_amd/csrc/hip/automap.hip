@@ -1,5 +1,6 @@
 // Every player's top-down map, drawn on the device from its game state (include/rdoom.h "top-down maps"):
-// rdoom_world_draw_maps, rdoom_worldset_draw_maps and the device copy of a level's line table.
+// rdoom_world_draw_maps, rdoom_worldset_draw_maps, their _seen forms (a map drawn through a player's set of seen lines, which
+// reveal.hip keeps) and the device copy of a level's line table.
 //
 // Arithmetic: binary32, the contract's operations in the contract's order; the build passes -ffp-contract=off and HIP divides
 // correctly rounded, so an IEEE host evaluating the header's expressions gets the same bytes (tests/automap_restatement.c does).
@@ -24,6 +25,13 @@
 
 namespace {
 
+using rdoom_dev::BOTH_SIDES;
+using rdoom_dev::dist2;
+using rdoom_dev::live_height;
+using rdoom_dev::Segment;
+using rdoom_dev::segment;
+using rdoom_dev::SIDE_BACK;
+using rdoom_dev::SIDE_FRONT;
 using rdoom_dev::sincos_rd;
 using rdoom_dev::with_level;
 
@@ -32,7 +40,6 @@ constexpr uint32_t TILE = 32;                             // pixels a side
 constexpr uint32_t PIXELS = TILE * TILE / THREADS;        // per thread: rows (tid / 32) + 8 k of column tid % 32
 constexpr uint32_t ROW_STEP = THREADS / TILE;
 constexpr uint32_t LIST_CAP = 512;                        // lines the LDS list holds: 512 x 24 bytes = 12 KiB
-constexpr uint32_t SIDE_FRONT = 1u << 16, SIDE_BACK = 1u << 17;  // MapDevice::flags above the linedef's 16
 constexpr uint32_t LINE_SECRET = 0x20u, LINE_HIDDEN = 0x80u;
 // Half the diagonal of a tile's pixel centres, in pixels: 15.5 * sqrt(2) = 21.92, rounded up.
 constexpr float TILE_RADIUS = 22.0f;
@@ -44,6 +51,8 @@ struct MapArgs {
   const rdoom_player_state *states;
   const float *offsets;  // n x n_objects x xyz, or null
   uint8_t *out;
+  const uint32_t *seen;  // n rows of seen_stride words, a bit per line of the player's level (reveal.hip), or null: every line
+  uint32_t seen_stride;
   const float4 *seg;
   const float4 *heights;
   const uint4 *ids;
@@ -52,24 +61,6 @@ struct MapArgs {
   float scale, rad, w2, marker;                       // rad = half_width * scale, w2 = rad * rad
   uint32_t view_flags;
 };
-
-// a segment as the contract's dist2 reads it: a, d = b - a, inv = 1 / |d|^2; ok: |d|^2 > 0
-struct Segment {
-  float ax, az, dx, dz, inv;
-  bool ok;
-};
-__device__ __forceinline__ Segment segment(float ax, float az, float bx, float bz) {
-  const float dx = bx - ax, dz = bz - az;
-  const float len2 = dx * dx + dz * dz;
-  return Segment{ax, az, dx, dz, 1.0f / len2, len2 > 0.0f};
-}
-__device__ __forceinline__ float dist2(float qx, float qz, float ax, float az, float dx, float dz, float inv) {
-  const float wx = qx - ax, wz = qz - az;
-  float t = (wx * dx + wz * dz) * inv;
-  t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
-  const float ex = wx - t * dx, ez = wz - t * dz;
-  return ex * ex + ez * ez;
-}
 
 // the map of player p, tile `tile`, from lines [first, first + n_lines) of the table; blank: no lines and no marker
 __device__ __forceinline__ void draw_tile(const MapArgs &a, uint32_t p, uint32_t tile, uint32_t first, uint32_t n_lines, bool blank) {
@@ -115,9 +106,8 @@ __device__ __forceinline__ void draw_tile(const MapArgs &a, uint32_t p, uint32_t
   const float player_size = (__builtin_fabsf(px) + __builtin_fabsf(pz)) + (float)(a.width + a.height) * a.scale;
 
   const float *off = a.offsets ? a.offsets + (size_t)p * a.n_objects * 3 : nullptr;
-  const auto live = [&](float height, uint32_t object) __attribute__((always_inline)) {
-    return height + ((off && object != 0 && object < a.n_objects) ? off[(size_t)object * 3 + 1] : 0.0f);
-  };
+  const auto live = [&](float height, uint32_t object) __attribute__((always_inline)) { return live_height(height, object, off, a.n_objects); };
+  const uint32_t *seen = a.seen ? a.seen + (size_t)p * a.seen_stride : nullptr;
 
   uint32_t count = 0;
   for (uint32_t base = 0; base < n_lines; base += THREADS) {
@@ -132,7 +122,8 @@ __device__ __forceinline__ void draw_tile(const MapArgs &a, uint32_t p, uint32_t
       const float size = player_size + ((__builtin_fabsf(e.x) + __builtin_fabsf(e.y)) + (__builtin_fabsf(e.z) + __builtin_fabsf(e.w)));
       const float limit = reach + size * CULL_MARGIN;
       keep = g.ok && dist2(cx, cz, g.ax, g.az, g.dx, g.dz, g.inv) <= limit * limit && (show_hidden || !(fl & LINE_HIDDEN));
-      if (keep && (fl & (SIDE_FRONT | SIDE_BACK)) == (SIDE_FRONT | SIDE_BACK) && !(fl & LINE_SECRET)) {
+      if (keep && seen) keep = (fl & RDOOM_LINE_MAPPED) || ((seen[l >> 5] >> (l & 31u)) & 1u);  // drawn through the seen set
+      if (keep && (fl & BOTH_SIDES) == BOTH_SIDES && !(fl & LINE_SECRET)) {
         const float4 h = a.heights[first + l];
         const uint4 o = a.ids[first + l];
         const float ff = live(h.x, o.x), fc = live(h.y, o.y), bf = live(h.z, o.z), bc = live(h.w, o.w);
@@ -222,7 +213,8 @@ constexpr uint32_t KNOWN_FLAGS = RDOOM_MAP_ROTATE | RDOOM_MAP_SHOW_FLAT | RDOOM_
 
 // the arguments of a draw, checked, as the kernel takes them.  noun: "world" or "world set"
 rdoom_status map_args(const rdoom::MapSource &src, const char *noun, const rdoom_player_state *d_states, uint32_t n,
-                      const float *d_offsets, uint32_t n_objects, const rdoom_map_view *view, uint8_t *d_out, MapArgs &a) {
+                      const float *d_offsets, uint32_t n_objects, const rdoom_map_view *view, const uint32_t *d_seen, uint32_t stride,
+                      uint8_t *d_out, MapArgs &a) {
   if (!view) return rdoom::fail(RDOOM_BAD_ARG, "null view");
   if (n && (!d_states || !d_out)) return rdoom::fail(RDOOM_BAD_ARG, "null states or output with n = %u", n);
   if (!view->width || !view->height || view->width > MAX_SIDE || view->height > MAX_SIDE)
@@ -236,12 +228,14 @@ rdoom_status map_args(const rdoom::MapSource &src, const char *noun, const rdoom
   if (view->flags & ~KNOWN_FLAGS) return rdoom::fail(RDOOM_BAD_ARG, "unknown map flags 0x%x", view->flags);
   if (d_offsets && n_objects < src.game_objects)
     return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the %s's %u objects", n_objects, noun, src.game_objects);
+  if (d_seen)
+    if (rdoom_status s = rdoom::check_seen_stride(src, noun, stride)) return s;
   const uint32_t tiles_x = (view->width + TILE - 1) / TILE, tiles_y = (view->height + TILE - 1) / TILE;
   if ((uint64_t)n * tiles_x * tiles_y > 0x7FFFFFFFull)
     return rdoom::fail(RDOOM_BAD_ARG, "%u maps of %u x %u tiles: too many for one launch", n, tiles_x, tiles_y);
   const float rad = view->half_width * view->scale;
   const rdoom::MapDevice &d = *src.map;
-  a = MapArgs{d_states, d_offsets, d_out, d.seg, d.heights, d.ids, d.flags, n_objects, view->width, view->height, tiles_x,
+  a = MapArgs{d_states, d_offsets, d_out, d_seen, stride, d.seg, d.heights, d.ids, d.flags, n_objects, view->width, view->height, tiles_x,
               tiles_x * tiles_y, view->scale, rad, rad * rad, view->marker, view->flags};
   return RDOOM_OK;
 }
@@ -281,29 +275,42 @@ static_assert(sizeof(rdoom_map_side) == 20 && sizeof(rdoom_map_line) == 68 && si
 
 extern "C" {
 
-rdoom_status rdoom_world_draw_maps(const rdoom_world *w, const rdoom_player_state *d_states, uint32_t n, const float *d_object_offsets,
-                                   uint32_t n_objects, const rdoom_map_view *view, uint8_t *d_out, void *stream) {
+rdoom_status rdoom_world_draw_maps_seen(const rdoom_world *w, const rdoom_player_state *d_states, uint32_t n, const float *d_object_offsets,
+                                        uint32_t n_objects, const rdoom_map_view *view, const uint32_t *d_seen, uint32_t stride,
+                                        uint8_t *d_out, void *stream) {
   if (!w) return rdoom::fail(RDOOM_BAD_ARG, "null world");
   const rdoom::MapSource src = rdoom::map_source(w);
   MapArgs a;
-  if (rdoom_status s = map_args(src, "world", d_states, n, d_object_offsets, n_objects, view, d_out, a)) return s;
+  if (rdoom_status s = map_args(src, "world", d_states, n, d_object_offsets, n_objects, view, d_seen, stride, d_out, a)) return s;
   if (rdoom_status s = rdoom::check_device(&src, "the world")) return s;
   if (!n) return RDOOM_OK;
   return rdoom::launch_checked(draw_maps_kernel, dim3(n * a.tiles), dim3(THREADS), 0, stream, a, src.map->n_lines);
 }
 
-rdoom_status rdoom_worldset_draw_maps(const rdoom_worldset *set, const rdoom_player_state *d_states, const uint32_t *d_levels, uint32_t n,
-                                      const float *d_object_offsets, uint32_t n_objects, const rdoom_map_view *view, uint8_t *d_out,
-                                      void *stream) {
+rdoom_status rdoom_worldset_draw_maps_seen(const rdoom_worldset *set, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                           uint32_t n, const float *d_object_offsets, uint32_t n_objects, const rdoom_map_view *view,
+                                           const uint32_t *d_seen, uint32_t stride, uint8_t *d_out, void *stream) {
   if (!set) return rdoom::fail(RDOOM_BAD_ARG, "null world set");
   if (n && !d_levels) return rdoom::fail(RDOOM_BAD_ARG, "null levels with n = %u", n);
   const rdoom::MapSource src = rdoom::map_source(set);
   MapArgs a;
-  if (rdoom_status s = map_args(src, "world set", d_states, n, d_object_offsets, n_objects, view, d_out, a)) return s;
+  if (rdoom_status s = map_args(src, "world set", d_states, n, d_object_offsets, n_objects, view, d_seen, stride, d_out, a)) return s;
   if (rdoom_status s = rdoom::check_device(&src, "the world set")) return s;
   if (!n) return RDOOM_OK;
   return rdoom::launch_checked(worldset_draw_maps_kernel, dim3(n * a.tiles), dim3(THREADS), 0, stream, a, (const uint2 *)src.map->levels,
                                d_levels, src.map->n_levels);
+}
+
+// the omniscient maps: the _seen forms with no set
+rdoom_status rdoom_world_draw_maps(const rdoom_world *w, const rdoom_player_state *d_states, uint32_t n, const float *d_object_offsets,
+                                   uint32_t n_objects, const rdoom_map_view *view, uint8_t *d_out, void *stream) {
+  return rdoom_world_draw_maps_seen(w, d_states, n, d_object_offsets, n_objects, view, nullptr, 0, d_out, stream);
+}
+
+rdoom_status rdoom_worldset_draw_maps(const rdoom_worldset *set, const rdoom_player_state *d_states, const uint32_t *d_levels, uint32_t n,
+                                      const float *d_object_offsets, uint32_t n_objects, const rdoom_map_view *view, uint8_t *d_out,
+                                      void *stream) {
+  return rdoom_worldset_draw_maps_seen(set, d_states, d_levels, n, d_object_offsets, n_objects, view, nullptr, 0, d_out, stream);
 }
 
 }  // extern "C"

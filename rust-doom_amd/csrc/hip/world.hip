@@ -935,8 +935,14 @@ struct rdoom_worldset {
 };
 
 namespace rdoom {
-MapSource map_source(const rdoom_world *w) { return MapSource{&w->map, w->host.game_objects, w->on_device, w->device}; }
-MapSource map_source(const rdoom_worldset *s) { return MapSource{&s->map, s->host.game_objects, s->on_device, s->device}; }
+MapSource map_source(const rdoom_world *w) {
+  return MapSource{&w->map, w->host.game_objects, (uint32_t)w->host.map_lines.size(), w->on_device, w->device};
+}
+MapSource map_source(const rdoom_worldset *s) {
+  size_t most = 0;
+  for (const rdoom::game::World &l : s->host.levels) most = std::max(most, l.map_lines.size());
+  return MapSource{&s->map, s->host.game_objects, (uint32_t)most, s->on_device, s->device};
+}
 }  // namespace rdoom
 
 namespace {

@@ -1,5 +1,6 @@
-// What the world's kernels (world.hip) and the map's (automap.hip) share: the pick of a lane's level, the checked launch, the
-// device check of a handle, and the map's side of a world handle.  One definition each, for player_quat.hpp's reason.
+// What the world's kernels (world.hip), the map's (automap.hip) and the seen lines' (reveal.hip) share: the pick of a lane's level,
+// the checked launch, the device check of a handle, the map's side of a world handle, and what both map units read of a line.
+// One definition each, for player_quat.hpp's reason.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +18,34 @@ __device__ __forceinline__ void with_level(uint32_t lv, Use use) {
   const uint32_t u = __builtin_amdgcn_readfirstlane(lv);
   if (__builtin_amdgcn_ballot_w64(lv != u) == 0) use(u);
   else use(lv);
+}
+
+// ---- a line of the table as the map contracts read it (include/rdoom.h "top-down maps", "seen lines") ----
+constexpr uint32_t SIDE_FRONT = 1u << 16, SIDE_BACK = 1u << 17;  // MapDevice::flags above the linedef's 16
+constexpr uint32_t BOTH_SIDES = SIDE_FRONT | SIDE_BACK;
+
+// a segment as the contract's dist2 reads it: a, d = b - a, inv = 1 / |d|^2; ok: |d|^2 > 0
+struct Segment {
+  float ax, az, dx, dz, inv;
+  bool ok;
+};
+__device__ __forceinline__ Segment segment(float ax, float az, float bx, float bz) {
+  const float dx = bx - ax, dz = bz - az;
+  const float len2 = dx * dx + dz * dz;
+  return Segment{ax, az, dx, dz, 1.0f / len2, len2 > 0.0f};
+}
+__device__ __forceinline__ float dist2(float qx, float qz, float ax, float az, float dx, float dz, float inv) {
+  const float wx = qx - ax, wz = qz - az;
+  float t = (wx * dx + wz * dz) * inv;
+  t = t < 0.0f ? 0.0f : (t > 1.0f ? 1.0f : t);
+  const float ex = wx - t * dx, ez = wz - t * dz;
+  return ex * ex + ez * ez;
+}
+
+// a sector height as a player's game has it: height + off(object), off = the y of the object's row in the player's offsets
+// (`off`: that player's n_objects x xyz, or null), 0 for object 0 and objects beyond the row
+__device__ __forceinline__ float live_height(float height, uint32_t object, const float *off, uint32_t n_objects) {
+  return height + ((off && object != 0 && object < n_objects) ? off[(size_t)object * 3 + 1] : 0.0f);
 }
 
 }  // namespace rdoom_dev
@@ -41,7 +70,7 @@ rdoom_status check_device(const Handle *h, const char *noun) {
   return RDOOM_OK;
 }
 
-// The device copy of a line table (rdoom_map_line), a structure of arrays private to automap.hip: a world's, or a world set's
+// The device copy of a line table (rdoom_map_line), a structure of arrays private to automap.hip and reveal.hip: a world's, or a world set's
 // levels one after the other with `levels[slot]` = (first line, number of lines).
 struct MapDevice {
   float4 *seg = nullptr;      // a.x, a.z, b.x, b.z
@@ -55,14 +84,24 @@ struct MapDevice {
 rdoom_status map_upload(const std::vector<rdoom_map_line> &lines, const std::vector<uint2> &levels, MapDevice &out);
 void map_free(MapDevice &d);
 
-// what automap.hip needs of a world or world-set handle (world.hip owns the handles)
+// what automap.hip and reveal.hip need of a world or world-set handle (world.hip owns the handles)
 struct MapSource {
   const MapDevice *map;
   uint32_t game_objects;  // the n_objects its game calls need at least
+  uint32_t max_lines;     // the lines of its table; a set's: of its largest level's (known on host-only handles too)
   bool on_device;
   int device;
 };
 MapSource map_source(const rdoom_world *w);
 MapSource map_source(const rdoom_worldset *s);
+// the 32-bit words a row of seen bits needs for that table
+inline uint32_t seen_words(const MapSource &src) { return (src.max_lines + 31u) / 32u; }
+// the d_seen / stride of a draw or a reveal against the handle's table.  noun: "world" or "world set"
+inline rdoom_status check_seen_stride(const MapSource &src, const char *noun, uint32_t stride) {
+  if (stride < seen_words(src))
+    return rdoom::fail(RDOOM_BAD_ARG, "a stride of %u words is smaller than the %u a row of the %s's %u lines takes", stride, seen_words(src), noun,
+                       src.max_lines);
+  return RDOOM_OK;
+}
 
 }  // namespace rdoom
