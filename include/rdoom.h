@@ -917,6 +917,103 @@ rdoom_status rdoom_worldset_draw_maps_seen(const rdoom_worldset *set, const rdoo
                                            uint32_t n, const float *d_object_offsets, uint32_t n_objects, const rdoom_map_view *view,
                                            const uint32_t *d_seen, uint32_t stride, uint8_t *d_out, void *stream);
 
+/* ---- sectors: the sector under a player, and every player's filled top-down map -------------------------------
+ * The level's sector table.  sectors: one record per SECTORS entry, in lump order.  floor / ceiling: from_wad_height of the
+ * sector's heights, the values rdoom_map_side carries; floor_id / ceiling_id: the objects SectorInfo gives them, as in the line table
+ * (they index d_object_offsets, rdoom_move_effect.object_id names them), 0 for a sector nothing moves; light_level, sector_type,
+ * tag: WadSector's 16-bit fields, verbatim (wad/src/types.rs:98-108).
+ * Leaves.  The collision world's BSP (rdoom_world_node, children packed: > 0 a node, <= 0 minus a chunk) has one chunk per leaf, in
+ * walk order.  leaf_sector[chunk]: the sector of the sub-sector that produced the chunk -- the sector of its first seg, as
+ * LevelWalker::subsector picks it (wad/src/visitor.rs:621-640) -- or RDOOM_SECTOR_NONE for a leaf the walk skipped, and for chunk 0
+ * of a level whose walk met no leaf (a child that was never linked reads as chunk 0).  n_leaves = max(1, the world's n_chunks).
+ * leaf_edges[chunk] = (first, count): the leaf's solid edges, edges[first .. first + count) -- those segs of its sub-sector whose
+ * linedef has no sidedef on the seg's other side (Level::seg_back_sidedef), in seg order.  An edge is a = the seg's start vertex and
+ * d = its end vertex - a, each component rounded once, in world xz.  The sub-sector lies where
+ * cross = (q.x - a.x) * d.z - (q.z - a.z) * d.x is <= 0; cross > 0 is the outside of the edge.
+ *
+ * The sector at a point q = (q.x, q.z), the authority for everything below.  Every value is binary32, every operation is rounded
+ * once, nothing is contracted, there is no division; a * b - c * d means round(round(a * b) - round(c * d)).
+ * Descent.  From node 0 of the level (its root): with the node's origin o and displace d (rdoom_world_node, both in xz),
+ *   dist = (q.x * d.y - q.z * d.x) + (d.x * o.y - d.y * o.x)
+ * (Line2::signed_distance, the expression the sweep evaluates); take child `positive` when dist >= 0, else `negative`; repeat
+ * while the child is > 0.  A child <= 0 names the leaf, chunk -child.
+ * Void.  q is void when some solid edge of the leaf has cross > 0, cross as above.  A point exactly on an edge is inside.
+ * Result.  leaf_sector[leaf], or RDOOM_SECTOR_NONE when q is void.  It is RDOOM_SECTOR_NONE too when q.x or q.z is a NaN (whose
+ * comparisons, all false, would otherwise lead down the negative children into some leaf).
+ * A function of the point and the tables alone: an implementation may start the descent below the root wherever that cannot change
+ * the result. */
+#define RDOOM_SECTOR_NONE 0xFFFFFFFFu
+#define RDOOM_SECTOR_NONE16 0xFFFFu
+typedef struct rdoom_map_sector {
+  float floor, ceiling;
+  uint32_t floor_id, ceiling_id;
+  uint32_t light_level, sector_type, tag;
+} rdoom_map_sector;
+typedef struct rdoom_map_edge {
+  float a[2], d[2];
+} rdoom_map_edge;
+typedef struct rdoom_map_leaf_edges {
+  uint32_t first, count;
+} rdoom_map_leaf_edges;
+/* borrowed pointers into a rdoom_world / rdoom_worldset (valid until it is destroyed) */
+typedef struct rdoom_map_sectors {
+  const rdoom_map_sector *sectors;
+  const uint32_t *leaf_sector;
+  const rdoom_map_leaf_edges *leaf_edges;
+  const rdoom_map_edge *edges;
+  uint32_t n_sectors, n_leaves, n_edges;
+} rdoom_map_sectors;
+/* The sector table of the world's level, and of slot `slot` of a set (equal to the single world's of the same level, in the level's
+ * own indices).  Both work on RDOOM_WORLD_HOST_ONLY handles. */
+rdoom_status rdoom_world_map_sectors(const rdoom_world *world, rdoom_map_sectors *out);
+rdoom_status rdoom_worldset_level_map_sectors(const rdoom_worldset *set, uint32_t slot, rdoom_map_sectors *out);
+
+/* The sector under each of n players, in one launch, asynchronous on `stream`; every pointer is device memory, nothing is allocated,
+ * nothing is copied to the host and nothing waits, so the call can be captured into a graph.  d_states, d_object_offsets / n_objects,
+ * d_levels: as for rdoom_world_draw_maps.
+ * d_sector_out[p]: the sector at (pos.x, pos.z) of player p, an index into its level's own table, or RDOOM_SECTOR_NONE.
+ * d_heights_out (n x 2 floats, may be NULL): the sector's live floor and ceiling, floor + off(floor_id) and ceiling +
+ *   off(ceiling_id) with the map contract's off() on row p of d_object_offsets; (+inf, -inf) where the sector is none.
+ * d_visited (n rows of `stride` uint32 words, may be NULL): bit s % 32 of word p * stride + s / 32 is OR-ed in for the sector s
+ *   player p stands in.  Bits are never cleared; words beyond the level's ceil(n_sectors / 32) and bits beyond n_sectors are never
+ *   written; the caller zeroes a row to start an episode.
+ * d_new_out (n uint32, may be NULL): 1 when this call set a bit of row p that was clear, else 0; 0 with a NULL d_visited and where
+ *   the sector is none.
+ * A level slot >= the set's size is seen on the device only: the sector is none, the row is untouched and d_new_out is 0.
+ * Errors, all checked before anything is queued (RDOOM_BAD_ARG): a NULL handle, or (n > 0) NULL d_states / d_sector_out / d_levels;
+ * d_visited with a stride smaller than ceil(n_sectors / 32) of the world's table (the set's: of its largest level's);
+ * d_object_offsets with n_objects smaller than the game's objects; a handle created with RDOOM_WORLD_HOST_ONLY or living on another
+ * device.  n == 0 queues nothing. */
+rdoom_status rdoom_world_locate_players(const rdoom_world *world, const rdoom_player_state *d_states, uint32_t n,
+                                        const float *d_object_offsets, uint32_t n_objects, uint32_t *d_sector_out, float *d_heights_out,
+                                        uint32_t *d_visited, uint32_t stride, uint32_t *d_new_out, void *stream);
+rdoom_status rdoom_worldset_locate_players(const rdoom_worldset *set, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                           uint32_t n, const float *d_object_offsets, uint32_t n_objects, uint32_t *d_sector_out,
+                                           float *d_heights_out, uint32_t *d_visited, uint32_t stride, uint32_t *d_new_out,
+                                           void *stream);
+
+/* Every player's filled top-down map: per pixel of the map contract's grid, the sector at the pixel's point.  view: width, height
+ * and scale are read, RDOOM_MAP_ROTATE and RDOOM_MAP_TOP_DOWN honoured, any other flag is an error; half_width and marker are not
+ * read.  The pixel's point q is the map contract's ("Pixel to world" above), operation for operation, so a sector map and a line map
+ * of the same view register exactly.  With s = the sector at q in the player's level:
+ * d_sector_out (n x height x width uint16, may be NULL): s, or RDOOM_SECTOR_NONE16 for none and for any s >= 0xFFFF.
+ * d_floor_out / d_ceiling_out (n x height x width floats, may be NULL): the live floor / ceiling of s for player p, as
+ *   rdoom_world_locate_players defines them; +inf / -inf for none.
+ * At least one of the three is given.  d_visited / stride (may be NULL): rows as rdoom_world_locate_players keeps them; a pixel
+ * whose sector's bit is clear in row p is written as none in every plane -- the filled map revealed as the player explores.
+ * A level slot >= the set's size is seen on the device only: that player's planes are all none.
+ * Errors, all checked before anything is queued (RDOOM_BAD_ARG): those of rdoom_world_draw_maps that concern what is read here
+ * (handle, view, d_states, d_levels, width, height, scale, flags, n_objects, the tile count, host-only, the device); all three
+ * outputs NULL (n > 0); d_visited with a stride smaller than the table's words.  n == 0 queues nothing. */
+rdoom_status rdoom_world_draw_sector_maps(const rdoom_world *world, const rdoom_player_state *d_states, uint32_t n,
+                                          const float *d_object_offsets, uint32_t n_objects, const rdoom_map_view *view,
+                                          const uint32_t *d_visited, uint32_t stride, uint16_t *d_sector_out, float *d_floor_out,
+                                          float *d_ceiling_out, void *stream);
+rdoom_status rdoom_worldset_draw_sector_maps(const rdoom_worldset *set, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                             uint32_t n, const float *d_object_offsets, uint32_t n_objects, const rdoom_map_view *view,
+                                             const uint32_t *d_visited, uint32_t stride, uint16_t *d_sector_out, float *d_floor_out,
+                                             float *d_ceiling_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -10,6 +10,7 @@ There is NO CPU fallback: if librdoom_hip.so is missing or a HIP call fails, thi
 (The directory name contains '-', so import it with importlib.import_module('rust-doom_amd') or via
 the `rust_doom_amd` shim at the repository root.)
 """
+import collections
 import ctypes
 import os
 
@@ -69,6 +70,10 @@ MAP_LINE = np.dtype([('linedef', '<u4'), ('a', '<f4', 2), ('b', '<f4', 2), ('fla
 MAP_NONE, MAP_FLAT, MAP_CEILING_STEP, MAP_FLOOR_STEP, MAP_CLOSED, MAP_ONE_SIDED, MAP_PLAYER = 0, 1, 2, 3, 4, 5, 8
 MAP_ROTATE, MAP_SHOW_FLAT, MAP_SHOW_HIDDEN, MAP_TOP_DOWN = 1, 2, 4, 8
 LINE_SECRET, LINE_HIDDEN = 0x20, 0x80  # the linedef flags the map reads: drawn as one-sided; never on the map
+MAP_SECTOR = np.dtype([('floor', '<f4'), ('ceiling', '<f4'), ('floor_id', '<u4'), ('ceiling_id', '<u4'), ('light_level', '<u4'),
+                       ('sector_type', '<u4'), ('tag', '<u4')])  # rdoom_map_sector
+MAP_EDGE = np.dtype([('a', '<f4', 2), ('d', '<f4', 2)])  # rdoom_map_edge
+SECTOR_NONE, SECTOR_NONE16 = 0xFFFFFFFF, 0xFFFF
 LINE_MAPPED = 0x100  # RDOOM_LINE_MAPPED, Doom's "already on the map": drawn through a seen set whether seen or not
 
 
@@ -155,7 +160,9 @@ API_SYMBOLS = [
     'rdoom_world_cast_rays', 'rdoom_worldset_cast_rays', 'rdoom_built_light_infos', 'rdoom_lightset_create', 'rdoom_lightset_destroy',
     'rdoom_lightset_tables', 'rdoom_poses_from_players_device_clocked', 'rdoom_batch_render_players_clocked',
     'rdoom_world_map_lines', 'rdoom_worldset_level_map_lines', 'rdoom_world_draw_maps', 'rdoom_worldset_draw_maps',
-    'rdoom_world_reveal_lines', 'rdoom_worldset_reveal_lines', 'rdoom_world_draw_maps_seen', 'rdoom_worldset_draw_maps_seen']
+    'rdoom_world_reveal_lines', 'rdoom_worldset_reveal_lines', 'rdoom_world_draw_maps_seen', 'rdoom_worldset_draw_maps_seen',
+    'rdoom_world_map_sectors', 'rdoom_worldset_level_map_sectors', 'rdoom_world_locate_players', 'rdoom_worldset_locate_players',
+    'rdoom_world_draw_sector_maps', 'rdoom_worldset_draw_sector_maps']
 
 _lib = None
 
@@ -1282,6 +1289,102 @@ def _reveal_lines(call, words, states, levels, fan, max_range, offsets, seen, ne
     return seen
 
 
+class MapSectorArrays(ctypes.Structure):
+    _fields_ = [('sectors', ctypes.c_void_p), ('leaf_sector', ctypes.c_void_p), ('leaf_edges', ctypes.c_void_p), ('edges', ctypes.c_void_p),
+                ('n_sectors', ctypes.c_uint32), ('n_leaves', ctypes.c_uint32), ('n_edges', ctypes.c_uint32)]
+
+
+class MapSectors(collections.namedtuple('MapSectors', 'sectors leaf_sector leaf_edges edges')):
+    """copies of a level's sector table (rdoom_map_sectors): sectors, a MAP_SECTOR record per SECTORS entry; leaf_sector, per chunk
+    of the collision BSP its sector or SECTOR_NONE; leaf_edges, per chunk (first, count) into edges; edges, MAP_EDGE records (a, d) of
+    the solid segs, the sub-sector where (q - a) x d <= 0"""
+
+
+def _map_sectors(get):
+    """World.map_sectors / WorldSet.map_sectors: copies of the tables get(&rdoom_map_sectors) lends"""
+    a = MapSectorArrays()
+    _check(get(ctypes.byref(a)))
+    view = lambda ptr, n, dtype: BuiltLevel._view(None, ptr, n, dtype)
+    return MapSectors(view(a.sectors, a.n_sectors, MAP_SECTOR), view(a.leaf_sector, a.n_leaves, np.uint32),
+                      view(a.leaf_edges, a.n_leaves * 2, np.uint32).reshape(-1, 2), view(a.edges, a.n_edges, MAP_EDGE))
+
+
+def _player_tensors(states, levels, offsets):
+    """what the sector calls check of states, levels and offsets: (n, n_objects)"""
+    import torch
+    for t, what in ((states, 'states'),) + (((levels, 'levels'),) if levels is not None else ()) + \
+            (((offsets, 'offsets'),) if offsets is not None else ()):
+        if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or not t.is_contiguous():
+            raise ValueError('%s must be a contiguous tensor on the GPU' % what)
+    n = _n_players(states)
+    if levels is not None and (levels.element_size() != 4 or levels.numel() != n):
+        raise ValueError('levels must hold one 32-bit slot per player (%d), got %s %s' % (n, levels.dtype, tuple(levels.shape)))
+    n_obj = 0
+    if offsets is not None:
+        if offsets.dtype != torch.float32 or offsets.dim() != 3 or offsets.shape[0] != n or offsets.shape[2] != 3:
+            raise ValueError('offsets must be a float32 (n, n_objects, 3) tensor for %d players, got %s %s'
+                             % (n, offsets.dtype, tuple(offsets.shape)))
+        n_obj = int(offsets.shape[1])
+    return n, n_obj
+
+
+def _locate_players(call, words, states, levels, offsets, heights_out, visited, new_out, out, stream):
+    """World.locate_players / WorldSet.locate_players: the checks and the launch; call(states, levels, n, offsets, n_objects,
+    sector_out, heights_out, visited, stride, new_out, stream) is the C entry point with its handle bound"""
+    import torch
+    n, n_obj = _player_tensors(states, levels, offsets)
+    if out is None:
+        out = torch.empty(n, dtype=torch.int32, device=states.device)
+    elif out.element_size() != 4 or out.dtype.is_floating_point:
+        raise ValueError('out must hold 32-bit integers')
+    po = _out_tensor(out, n * 4, 'out')
+    if heights_out is not None and heights_out.dtype != torch.float32:
+        raise ValueError('heights_out must be float32')
+    ph = _out_tensor(heights_out, n * 8, 'heights_out')
+    pv, stride = _seen_rows(visited, n, words) if visited is not None else (None, 0)
+    if new_out is not None and (new_out.element_size() != 4 or new_out.dtype.is_floating_point):
+        raise ValueError('new_out must hold 32-bit integers')
+    pn = _out_tensor(new_out, n * 4, 'new_out')
+    v = ctypes.c_void_p
+    _check(call(v(states.data_ptr()), v(levels.data_ptr()) if levels is not None else None, n,
+                v(offsets.data_ptr()) if offsets is not None else None, n_obj, v(po), v(ph), v(pv), stride, v(pn), v(_stream_handle(stream))))
+    return out
+
+
+def _draw_sector_maps(call, words, states, levels, width, height, scale, offsets, rotate, top_down, sector_out, floor, ceiling, visited,
+                      stream):
+    """World.draw_sector_maps / WorldSet.draw_sector_maps: the checks and the launch; call(states, levels, n, offsets, n_objects,
+    view, visited, stride, sector_out, floor_out, ceiling_out, stream) is the C entry point with its handle bound.  Returns the
+    planes asked for, in the order sector, floor, ceiling: one tensor, or a tuple of them"""
+    import torch
+    n, n_obj = _player_tensors(states, levels, offsets)
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError('a map needs at least 1 x 1 pixels, got %d x %d' % (width, height))
+    planes = []
+    for want, dtype, what in ((sector_out, torch.int16, 'sector_out'), (floor, torch.float32, 'floor'), (ceiling, torch.float32, 'ceiling')):
+        if want is None or want is False:
+            planes.append(None)
+            continue
+        if want is True:
+            want = torch.empty((n, height, width), dtype=dtype, device=states.device)
+        elif not isinstance(want, torch.Tensor) or want.element_size() != (2 if dtype == torch.int16 else 4) or \
+                want.dtype.is_floating_point != (dtype == torch.float32):
+            raise ValueError('%s must be True or a %s tensor' % (what, '16-bit integer' if dtype == torch.int16 else 'float32'))
+        _out_tensor(want, n * height * width * want.element_size(), what)
+        planes.append(want)
+    if all(t is None for t in planes):
+        raise ValueError('no plane asked for: sector_out, floor and ceiling are all off')
+    view = MapView(width, height, scale, 0.0, 0.0, (MAP_ROTATE if rotate else 0) | (MAP_TOP_DOWN if top_down else 0))
+    pv, stride = _seen_rows(visited, n, words) if visited is not None else (None, 0)
+    v = ctypes.c_void_p
+    _check(call(v(states.data_ptr()), v(levels.data_ptr()) if levels is not None else None, n,
+                v(offsets.data_ptr()) if offsets is not None else None, n_obj, ctypes.byref(view), v(pv), stride,
+                *[v(t.data_ptr()) if t is not None else None for t in planes], v(_stream_handle(stream))))
+    given = tuple(t for t in planes if t is not None)
+    return given[0] if len(given) == 1 else given
+
+
 class World:
     """game::world::World on the host and the current device (rdoom_world_create): World::sweep_sphere for a batch of queries,
     Player::update for a batch of players."""
@@ -1449,6 +1552,44 @@ class World:
         return _reveal_lines(lambda st, lv, *rest: L.rdoom_world_reveal_lines(self._h, st, *rest), self.seen_words(), states, None, fan,
                              max_range, offsets, seen, new_out, stream)
 
+    # ---- sectors -----------------------------------------------------------------------------------------------------------
+    def map_sectors(self):
+        """a copy of rdoom_world_map_sectors: the level's sector table, a MapSectors of (sectors, leaf_sector, leaf_edges, edges)"""
+        return _map_sectors(lambda a: lib().rdoom_world_map_sectors(self._h, a))
+
+    def visited_words(self):
+        """the 32-bit words a row of visited bits takes: a bit per sector of map_sectors()"""
+        a = MapSectorArrays()
+        _check(lib().rdoom_world_map_sectors(self._h, ctypes.byref(a)))
+        return (a.n_sectors + 31) // 32
+
+    def locate_players(self, states, offsets=None, heights_out=None, visited=None, new_out=None, out=None, stream=None):
+        """rdoom_world_locate_players: the sector every player stands in, an int32 tensor of n indices into
+        map_sectors().sectors, -1 (SECTOR_NONE as int32) outside every sector.  states: the tensor a step leaves; offsets: None or
+        step_game's tensor.  heights_out: an optional float32 (n, 2) tensor for the sector's live floor and ceiling in that player's
+        game (a lift that carried the player down shows here), +inf / -inf outside.  visited: an optional int32 (n, words >=
+        visited_words()) tensor whose bit s % 32 of word s // 32 of row p is OR-ed in for the player's sector s (unpack_seen unpacks
+        a row); new_out: an optional 32-bit integer tensor of n that receives 1 where this call set a new bit -- with the table's
+        sector_type column on the device, (types[sector] == 9) & new counts secrets found.  out: an optional preallocated tensor.
+        Asynchronous on `stream`."""
+        L = lib()
+        return _locate_players(lambda st, lv, *rest: L.rdoom_world_locate_players(self._h, st, *rest), self.visited_words(), states, None, offsets,
+                               heights_out, visited, new_out, out, stream)
+
+    def draw_sector_maps(self, states, width, height, scale, offsets=None, rotate=False, top_down=False, sector_out=None, floor=False,
+                         ceiling=False, visited=None, stream=None):
+        """rdoom_world_draw_sector_maps: every player's filled top-down map on draw_maps' grid (same width, height, scale,
+        rotate, top_down: the two register pixel for pixel): per pixel the sector there.  sector_out: True or an int16 / uint16
+        (n, height, width) tensor for the sector index, SECTOR_NONE16 (-1 as int16) in the void; floor / ceiling: True or a float32
+        tensor for the sector's live floor / ceiling in that player's game, +inf / -inf in the void.  With none of the three asked
+        for, the sector plane is drawn.  visited: None or locate_players' rows: only sectors the player has entered show.  Returns
+        the planes asked for, in the order sector, floor, ceiling (one tensor, or a tuple).  Asynchronous on `stream`."""
+        L = lib()
+        if sector_out is None and floor is False and ceiling is False:
+            sector_out = True
+        return _draw_sector_maps(lambda st, lv, *rest: L.rdoom_world_draw_sector_maps(self._h, st, *rest), self.visited_words(), states, None, width,
+                                 height, scale, offsets, rotate, top_down, sector_out, floor, ceiling, visited, stream)
+
 
 class WorldSetLevelInfo(ctypes.Structure):
     _fields_ = [('archive_index', ctypes.c_uint32), ('destination', ctypes.c_uint32), ('start_pos', ctypes.c_float * 3),
@@ -1588,3 +1729,37 @@ class WorldSet:
         L = lib()
         return _reveal_lines(lambda st, lv, *rest: L.rdoom_worldset_reveal_lines(self._h, st, lv, *rest), self.seen_words(), states,
                              levels, fan, max_range, offsets, seen, new_out, stream)
+
+    # ---- sectors -----------------------------------------------------------------------------------------------------------
+    def map_sectors(self, slot):
+        """a copy of rdoom_worldset_level_map_sectors: the level's sector table, a MapSectors of (sectors, leaf_sector, leaf_edges, edges)"""
+        return _map_sectors(lambda a: lib().rdoom_worldset_level_map_sectors(self._h, int(slot), a))
+
+    def visited_words(self):
+        """the 32-bit words a row of visited bits takes: a bit per sector of the set's largest level"""
+        if getattr(self, '_visited_words', None) is None:  # the tables do not change: counted once, without copying them
+            most = 0
+            for s in range(self.n_levels):
+                a = MapSectorArrays()
+                _check(lib().rdoom_worldset_level_map_sectors(self._h, s, ctypes.byref(a)))
+                most = max(most, a.n_sectors)
+            self._visited_words = (most + 31) // 32
+        return self._visited_words
+
+    def locate_players(self, states, levels, offsets=None, heights_out=None, visited=None, new_out=None, out=None, stream=None):
+        """rdoom_worldset_locate_players: World.locate_players for players spread over the set's levels (levels: game_state's
+        tensor of slots).  A sector is an index into map_sectors(slot) of the player's slot, a row's bits number that level's sectors;
+        a player whose slot is not in the set gets SECTOR_NONE, keeps its row and has 0 in new_out."""
+        L = lib()
+        return _locate_players(lambda st, lv, *rest: L.rdoom_worldset_locate_players(self._h, st, lv, *rest), self.visited_words(), states, levels, offsets,
+                               heights_out, visited, new_out, out, stream)
+
+    def draw_sector_maps(self, states, levels, width, height, scale, offsets=None, rotate=False, top_down=False, sector_out=None, floor=False,
+                         ceiling=False, visited=None, stream=None):
+        """rdoom_worldset_draw_sector_maps: World.draw_sector_maps for players spread over the set's levels; a player whose
+        slot is not in the set gets planes of none"""
+        L = lib()
+        if sector_out is None and floor is False and ceiling is False:
+            sector_out = True
+        return _draw_sector_maps(lambda st, lv, *rest: L.rdoom_worldset_draw_sector_maps(self._h, st, lv, *rest), self.visited_words(), states, levels, width,
+                                 height, scale, offsets, rotate, top_down, sector_out, floor, ceiling, visited, stream)

@@ -32,7 +32,6 @@ using rdoom_dev::Segment;
 using rdoom_dev::segment;
 using rdoom_dev::SIDE_BACK;
 using rdoom_dev::SIDE_FRONT;
-using rdoom_dev::sincos_rd;
 using rdoom_dev::with_level;
 
 constexpr uint32_t WAVE = 64, THREADS = 256, WAVES = THREADS / WAVE;
@@ -69,38 +68,26 @@ __device__ __forceinline__ void draw_tile(const MapArgs &a, uint32_t p, uint32_t
   __shared__ uint32_t wave_kept[WAVES];
 
   const uint32_t tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
-  const rdoom_player_state *st = a.states + p;
-  const float px = st->pos[0], pz = st->pos[2];
-  float s, c;
-  sincos_rd(st->yaw, s, c);
-  const float fx = -s, fz = -c;  // the forward ray_fan's -z turns into
-  const bool rotate = a.view_flags & RDOOM_MAP_ROTATE, top_down = a.view_flags & RDOOM_MAP_TOP_DOWN;
+  const rdoom_dev::MapFrame frame = rdoom_dev::map_frame(a.states + p, a.width, a.height, a.scale, a.view_flags);
+  const float px = frame.px, pz = frame.pz, fx = frame.fx, fz = frame.fz;  // (fx, fz): the forward ray_fan's -z turns into
   const bool show_flat = a.view_flags & RDOOM_MAP_SHOW_FLAT, show_hidden = a.view_flags & RDOOM_MAP_SHOW_HIDDEN;
-  const float hw = (float)a.width * 0.5f, hh = (float)a.height * 0.5f;
-  const auto to_world = [&](float u, float v, float &qx, float &qz) __attribute__((always_inline)) {
-    if (rotate) qx = (px + c * u) + fx * v, qz = (pz + fx * u) + fz * v;
-    else qx = px - v, qz = pz - u;
-  };
 
   const uint32_t x0 = (tile % a.tiles_x) * TILE, y0 = (tile / a.tiles_x) * TILE;
   const uint32_t i = x0 + (tid & (TILE - 1)), row0 = y0 + tid / TILE;
   float qx[PIXELS], qz[PIXELS];
   uint32_t best[PIXELS];
-  const float u = (((float)i + 0.5f) - hw) * a.scale;
+  const float u = rdoom_dev::map_u(frame, i);
 #pragma unroll
   for (uint32_t k = 0; k < PIXELS; k++) {
-    const uint32_t row = row0 + ROW_STEP * k;
-    const int32_t j = top_down ? (int32_t)a.height - 1 - (int32_t)row : (int32_t)row;
-    const float v = (((float)j + 0.5f) - hh) * a.scale;
-    to_world(u, v, qx[k], qz[k]);
+    rdoom_dev::map_to_world(frame, u, rdoom_dev::map_v(frame, row0 + ROW_STEP * k), qx[k], qz[k]);
     best[k] = RDOOM_MAP_NONE;
   }
 
   // the tile's centre, the radius around it that holds every pixel centre, and the magnitude the margin scales with
   float cx, cz;
   {
-    const float ci = (float)(x0 + TILE / 2), cj = top_down ? (float)a.height - (float)(y0 + TILE / 2) : (float)(y0 + TILE / 2);
-    to_world((ci - hw) * a.scale, (cj - hh) * a.scale, cx, cz);
+    const float ci = (float)(x0 + TILE / 2), cj = frame.top_down ? (float)a.height - (float)(y0 + TILE / 2) : (float)(y0 + TILE / 2);
+    rdoom_dev::map_to_world(frame, (ci - frame.hw) * a.scale, (cj - frame.hh) * a.scale, cx, cz);
   }
   const float reach = TILE_RADIUS * a.scale + a.rad;
   const float player_size = (__builtin_fabsf(px) + __builtin_fabsf(pz)) + (float)(a.width + a.height) * a.scale;

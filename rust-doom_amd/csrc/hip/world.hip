@@ -920,6 +920,7 @@ struct rdoom_world {
   int device = -1;
   DevArrays d;
   rdoom::MapDevice map;  // the level's line table, as automap.hip lays it out
+  rdoom::SectorDevice sectors;  // its sector table, as sectors.hip lays it out
 };
 
 struct rdoom_worldset {
@@ -932,16 +933,18 @@ struct rdoom_worldset {
   DevSetLevel *d_table = nullptr;
   uint32_t *d_tri_starts = nullptr;  // each level's triangle base in the concatenation (the ray cast's)
   rdoom::MapDevice map;              // the levels' line tables, one after the other
+  rdoom::SectorDevice sectors;       // and their sector tables
 };
 
 namespace rdoom {
 MapSource map_source(const rdoom_world *w) {
-  return MapSource{&w->map, w->host.game_objects, (uint32_t)w->host.map_lines.size(), w->on_device, w->device};
+  return MapSource{&w->map, &w->sectors, (uint32_t)w->host.map_sectors.size(), w->host.game_objects, (uint32_t)w->host.map_lines.size(),
+                   w->on_device, w->device};
 }
 MapSource map_source(const rdoom_worldset *s) {
-  size_t most = 0;
-  for (const rdoom::game::World &l : s->host.levels) most = std::max(most, l.map_lines.size());
-  return MapSource{&s->map, s->host.game_objects, (uint32_t)most, s->on_device, s->device};
+  size_t most = 0, most_sectors = 0;
+  for (const rdoom::game::World &l : s->host.levels) most = std::max(most, l.map_lines.size()), most_sectors = std::max(most_sectors, l.map_sectors.size());
+  return MapSource{&s->map, &s->sectors, (uint32_t)most_sectors, s->host.game_objects, (uint32_t)most, s->on_device, s->device};
 }
 }  // namespace rdoom
 
@@ -976,6 +979,11 @@ void fill_arrays(const rdoom::game::World &h, rdoom_world_arrays &a) {
   a.n_dynamics = (uint32_t)h.dynamics.size();
   a.n_objects = h.n_objects;
   a.node_depth = h.node_depth;
+}
+
+void fill_sectors(const rdoom::game::World &h, rdoom_map_sectors &m) {
+  m = rdoom_map_sectors{h.map_sectors.data(), h.leaf_sector.data(), h.leaf_edges.data(), h.map_edges.data(), (uint32_t)h.map_sectors.size(),
+                        (uint32_t)h.leaf_sector.size(), (uint32_t)h.map_edges.size()};
 }
 
 void fill_triggers(const rdoom::game::World &h, rdoom_world_trigger_arrays &t) {
@@ -1079,6 +1087,7 @@ void rdoom_world_destroy(rdoom_world *w) {
   if (!w) return;
   free_world(w->d);
   rdoom::map_free(w->map);
+  rdoom::sector_free(w->sectors);
   delete w;
 }
 
@@ -1099,6 +1108,7 @@ rdoom_status rdoom_world_create(const rdoom_wad *wad, uint32_t level_index, uint
     HIP_TRY(hipGetDevice(&w->device));
     if (rdoom_status st = upload_world(h, w->d)) return st;
     if (rdoom_status st = rdoom::map_upload(h.map_lines, {make_uint2(0u, (uint32_t)h.map_lines.size())}, w->map)) return st;
+    if (rdoom_status st = rdoom::sector_upload({&h}, w->sectors)) return st;
     w->on_device = true;
   }
   *out_world = w.release();
@@ -1153,6 +1163,12 @@ rdoom_status rdoom_world_map_lines(const rdoom_world *w, rdoom_map_lines *out) {
   return RDOOM_OK;
 }
 
+rdoom_status rdoom_world_map_sectors(const rdoom_world *w, rdoom_map_sectors *out) {
+  if (!w || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  fill_sectors(w->host, *out);
+  return RDOOM_OK;
+}
+
 rdoom_status rdoom_world_game_bytes(const rdoom_world *w, uint64_t *bytes_per_player) {
   if (!w || !bytes_per_player) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   *bytes_per_player = (uint64_t)game_view(w).words * sizeof(uint32_t);
@@ -1189,6 +1205,7 @@ void rdoom_worldset_destroy(rdoom_worldset *s) {
   if (!s) return;
   free_world(s->d);
   rdoom::map_free(s->map);
+  rdoom::sector_free(s->sectors);
   if (s->d_table) (void)hipFree(s->d_table);
   if (s->d_tri_starts) (void)hipFree(s->d_tri_starts);
   delete s;
@@ -1231,6 +1248,9 @@ rdoom_status rdoom_worldset_create(const rdoom_wad *wad, const uint32_t *level_i
     std::vector<uint2> map_ranges;
     for (size_t i = 0; i < h.levels.size(); i++) map_ranges.push_back(make_uint2(h.table[i].map_base, (uint32_t)h.levels[i].map_lines.size()));
     if (rdoom_status st = rdoom::map_upload(h.all.map_lines, map_ranges, s->map)) return st;
+    std::vector<const rdoom::game::World *> each;
+    for (const rdoom::game::World &l : h.levels) each.push_back(&l);
+    if (rdoom_status st = rdoom::sector_upload(each, s->sectors)) return st;
     s->on_device = true;
   }
   *out_set = s.release();
@@ -1266,6 +1286,13 @@ rdoom_status rdoom_worldset_level_map_lines(const rdoom_worldset *s, uint32_t sl
   if (slot >= s->host.levels.size()) return rdoom::fail(RDOOM_BAD_ARG, "slot %u of a set of %zu levels", slot, s->host.levels.size());
   const std::vector<rdoom_map_line> &lines = s->host.levels[slot].map_lines;
   *out = rdoom_map_lines{lines.data(), (uint32_t)lines.size()};
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_worldset_level_map_sectors(const rdoom_worldset *s, uint32_t slot, rdoom_map_sectors *out) {
+  if (!s || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (slot >= s->host.levels.size()) return rdoom::fail(RDOOM_BAD_ARG, "slot %u of a set of %zu levels", slot, s->host.levels.size());
+  fill_sectors(s->host.levels[slot], *out);
   return RDOOM_OK;
 }
 

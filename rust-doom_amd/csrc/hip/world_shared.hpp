@@ -1,4 +1,4 @@
-// What the world's kernels (world.hip), the map's (automap.hip) and the seen lines' (reveal.hip) share: the pick of a lane's level,
+// What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip) and the sectors' (sectors.hip) share: the pick of a lane's level,
 // the checked launch, the device check of a handle, the map's side of a world handle, and what both map units read of a line.
 // One definition each, for player_quat.hpp's reason.
 #pragma once
@@ -8,6 +8,7 @@
 
 #include "../common.hpp"
 #include "kernels.hpp"
+#include "player_quat.hpp"
 
 namespace rdoom_dev {
 
@@ -42,6 +43,33 @@ __device__ __forceinline__ float dist2(float qx, float qz, float ax, float az, f
   return ex * ex + ez * ez;
 }
 
+// ---- the map contract's pixel-to-world mapping (include/rdoom.h "top-down maps"), the one definition the line maps (automap.hip)
+// and the sector maps (sectors.hip) share, so that the two register exactly: the operations of the contract, in its order ----
+struct MapFrame {
+  float px, pz;     // the player's position
+  float c, fx, fz;  // the cosine of the yaw and the forward f = (-s, -c); the right is (c, fx)
+  float hw, hh, scale;
+  uint32_t height;
+  bool rotate, top_down;
+};
+__device__ __forceinline__ MapFrame map_frame(const rdoom_player_state *st, uint32_t width, uint32_t height, float scale, uint32_t view_flags) {
+  float s, c;
+  sincos_rd(st->yaw, s, c);
+  return MapFrame{st->pos[0], st->pos[2], c, -s, -c, (float)width * 0.5f, (float)height * 0.5f, scale, height,
+                  (view_flags & RDOOM_MAP_ROTATE) != 0, (view_flags & RDOOM_MAP_TOP_DOWN) != 0};
+}
+// the world point of map coordinates (u, v): u to the right, v up, in world units from the player
+__device__ __forceinline__ void map_to_world(const MapFrame &f, float u, float v, float &qx, float &qz) {
+  if (f.rotate) qx = (f.px + f.c * u) + f.fx * v, qz = (f.pz + f.fx * u) + f.fz * v;
+  else qx = f.px - v, qz = f.pz - u;
+}
+// u of column i, and v of output row `row` (row 0 is the bottom row of pixels unless top_down)
+__device__ __forceinline__ float map_u(const MapFrame &f, uint32_t i) { return (((float)i + 0.5f) - f.hw) * f.scale; }
+__device__ __forceinline__ float map_v(const MapFrame &f, uint32_t row) {
+  const int32_t j = f.top_down ? (int32_t)f.height - 1 - (int32_t)row : (int32_t)row;
+  return (((float)j + 0.5f) - f.hh) * f.scale;
+}
+
 // a sector height as a player's game has it: height + off(object), off = the y of the object's row in the player's offsets
 // (`off`: that player's n_objects x xyz, or null), 0 for object 0 and objects beyond the row
 __device__ __forceinline__ float live_height(float height, uint32_t object, const float *off, uint32_t n_objects) {
@@ -49,6 +77,10 @@ __device__ __forceinline__ float live_height(float height, uint32_t object, cons
 }
 
 }  // namespace rdoom_dev
+
+namespace rdoom::game {
+struct World;
+}
 
 namespace rdoom {
 
@@ -84,9 +116,27 @@ struct MapDevice {
 rdoom_status map_upload(const std::vector<rdoom_map_line> &lines, const std::vector<uint2> &levels, MapDevice &out);
 void map_free(MapDevice &d);
 
-// what automap.hip and reveal.hip need of a world or world-set handle (world.hip owns the handles)
+// The device copy of a sector table (rdoom_map_sectors) and of the BSP that leads to it, a structure of arrays private to
+// sectors.hip: a world's, or a world set's levels one after the other, every index inside a level the level's own.
+struct SectorDevice {
+  float4 *nodes = nullptr;    // d.x, d.y, c = d.x * o.y - d.y * o.x, and as bits the children: positive in the low 16, negative in the
+                              // high 16, each an int16 as Child::pack writes it (> 0 a node, <= 0 minus a leaf)
+  uint4 *leaves = nullptr;    // the leaf's sector or RDOOM_SECTOR_NONE, its first solid edge (in `edges`), their number, 0
+  float4 *edges = nullptr;    // a.x, a.z, d.x, d.z
+  float4 *sectors = nullptr;  // floor, ceiling, and as bits floor_id, ceiling_id
+  uint4 *levels = nullptr;    // a slot's first node, first leaf, first sector, number of sectors
+  uint32_t n_levels = 0;
+};
+// sectors.hip: the tables of `levels` on the current device (RDOOM_BAD_LEVEL: a level with more nodes or leaves than 16 bits
+// address); releases what it allocated
+rdoom_status sector_upload(const std::vector<const game::World *> &levels, SectorDevice &out);
+void sector_free(SectorDevice &d);
+
+// what automap.hip, reveal.hip and sectors.hip need of a world or world-set handle (world.hip owns the handles)
 struct MapSource {
   const MapDevice *map;
+  const SectorDevice *sectors;
+  uint32_t max_sectors;   // the sectors of its table; a set's: of its largest level's (known on host-only handles too)
   uint32_t game_objects;  // the n_objects its game calls need at least
   uint32_t max_lines;     // the lines of its table; a set's: of its largest level's (known on host-only handles too)
   bool on_device;
@@ -94,6 +144,8 @@ struct MapSource {
 };
 MapSource map_source(const rdoom_world *w);
 MapSource map_source(const rdoom_worldset *s);
+// the 32-bit words a row of visited bits needs for that sector table
+inline uint32_t visited_words(const MapSource &src) { return (src.max_sectors + 31u) / 32u; }
 // the 32-bit words a row of seen bits needs for that table
 inline uint32_t seen_words(const MapSource &src) { return (src.max_lines + 31u) / 32u; }
 // the d_seen / stride of a draw or a reveal against the handle's table.  noun: "world" or "world set"

@@ -129,7 +129,12 @@ World build_world(const LoadedWad &w, size_t level_index) {
   const Level level = Level::from_archive(archive, level_index);
   const LevelAnalysis analysis(level, archive.metadata());
   WorldBuilder b;
-  LevelWalker(level, analysis, w.textures, archive.metadata(), b).walk();
+  std::vector<uint32_t> leaf_subsectors;  // per chunk, in walk order
+  {
+    LevelWalker walker(level, analysis, w.textures, archive.metadata(), b);
+    walker.record_leaf_subsectors = &leaf_subsectors;
+    walker.walk();
+  }
   World out = b.build();
   out.game_objects = (uint32_t)std::max<size_t>(1, analysis.num_objects());
   for (const Trigger &t : analysis.triggers()) {
@@ -170,6 +175,32 @@ World build_world(const LoadedWad &w, size_t level_index) {
     };
     m.front = side(l.right_side), m.back = side(l.left_side);
     out.map_lines.push_back(m);
+  }
+  // the sector table: every sector in lump order, with the heights and objects the line table gives its sides
+  for (const WadSector &sc : level.sectors) {
+    rdoom_map_sector r{};
+    r.floor = from_wad_height(sc.floor_height), r.ceiling = from_wad_height(sc.ceiling_height);
+    if (const DynamicSectorInfo *d = analysis.dynamic(level.sector_id(&sc))) r.floor_id = d->floor_id.v, r.ceiling_id = d->ceiling_id.v;
+    r.light_level = (uint16_t)sc.light, r.sector_type = sc.sector_type, r.tag = sc.tag;
+    out.map_sectors.push_back(r);
+  }
+  // per chunk the sector of its sub-sector -- of its first seg, as LevelWalker::subsector picks it -- and the solid edges: the segs
+  // with nothing behind them, start vertex and end - start.  Chunk 0 exists for the descent even when the walk met no leaf.
+  const size_t n_leaves = std::max<size_t>(1, out.chunks.size());
+  out.leaf_sector.assign(n_leaves, RDOOM_SECTOR_NONE);
+  out.leaf_edges.assign(n_leaves, rdoom_map_leaf_edges{0, 0});
+  for (size_t k = 0; k < leaf_subsectors.size() && k < n_leaves; k++) {
+    out.leaf_edges[k].first = (uint32_t)out.map_edges.size();
+    if (leaf_subsectors[k] == LevelWalker::NO_SUBSECTOR) continue;
+    const WadSubsector ss = level.subsectors[leaf_subsectors[k]];
+    const WadSeg *segs = &level.segs[ss.first_seg];
+    out.leaf_sector[k] = level.sector_id(level.seg_sector(segs[0]));
+    for (size_t i = 0; i < ss.num_segs; i++) {
+      if (!level.seg_linedef(segs[i]) || level.seg_back_sidedef(segs[i])) continue;
+      const Pnt2f a = *level.vertex(segs[i].start_vertex), e = *level.vertex(segs[i].end_vertex);
+      out.map_edges.push_back(rdoom_map_edge{{a.x, a.y}, {e.x - a.x, e.y - a.y}});
+    }
+    out.leaf_edges[k].count = (uint32_t)out.map_edges.size() - out.leaf_edges[k].first;
   }
   return out;
 }

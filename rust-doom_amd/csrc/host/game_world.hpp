@@ -40,6 +40,12 @@ struct World {
   uint32_t game_objects = 1;  // max(1, LevelAnalysis::num_objects)
   // the level's line table for the top-down map (include/rdoom.h rdoom_map_line): one record per linedef with both vertices
   std::vector<rdoom_map_line> map_lines;
+  // the level's sector table (include/rdoom.h rdoom_map_sectors): a record per SECTORS entry; per chunk (at least one entry) the
+  // sector of the sub-sector behind it and its range of solid edges
+  std::vector<rdoom_map_sector> map_sectors;
+  std::vector<uint32_t> leaf_sector;
+  std::vector<rdoom_map_leaf_edges> leaf_edges;
+  std::vector<rdoom_map_edge> map_edges;
   float start_pos[3] = {0, 0, 0};  // the player's start, as the renderer's Builder takes it (rdoom_built_start)
   float start_yaw = 0.0f;
 };
@@ -58,6 +64,7 @@ struct WorldSet {
   // the concatenation: node children, chunk and dynamic triangle ranges, triangle vertex indices and trigger effect ranges
   // rebased (the map lines are concatenated as they are: their object ids are each level's own).  A child packed as 0 (Leaf(0), never linked or not) becomes minus its own level's chunk base, so it still reads as
   // that level's leaf 0.
+  // The sector tables are not concatenated here: they stay with `levels`, and the device copy lays them out one after the other.
   World all;
   uint32_t game_objects = 1;  // the largest of the levels' game_objects
   uint32_t node_depth = 0;    // the deepest level's

@@ -519,6 +519,11 @@ class LevelWalker {  // visitor.rs:499-1138
     std::vector<Line2f> bsp_lines;
   };
   std::vector<LeafInput> *record_leaves = nullptr;
+  // Records one entry per visit_bsp_leaf, in walk order (the order in which a WorldBuilder numbers its chunks): the sub-sector
+  // whose segs the leaf emitted all of, or NO_SUBSECTOR for a leaf subsector() gave up on (no such sub-sector, no segs, no sector,
+  // a seg without a vertex).
+  static constexpr uint32_t NO_SUBSECTOR = 0xFFFFFFFFu;
+  std::vector<uint32_t> *record_leaf_subsectors = nullptr;
   // Same for the SEG -> wall-quad half: record_segs (sized level.segs.size()) collects the per-seg inputs
   // instead of emitting quads; precomputed_segs (same indexing) replaces the host arithmetic of seg() /
   // wall_quad() / sky_quad() by the device's results.

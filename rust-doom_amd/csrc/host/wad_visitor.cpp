@@ -300,6 +300,7 @@ void LevelWalker::node(uint16_t id, Branch branch) {  // visitor.rs:590-609
   const size_t idx = id & 0x7FFF;
   if (id & 0x8000) {
     visitor_.visit_bsp_leaf(branch);
+    if (record_leaf_subsectors) record_leaf_subsectors->push_back(NO_SUBSECTOR);
     subsector(idx);
     visitor_.visit_bsp_leaf_end();
     return;
@@ -341,6 +342,7 @@ void LevelWalker::subsector(size_t id) {  // visitor.rs:621-709
     seg(sector, info, segs[i], *v1, *v2);
   }
   if (record_leaves) record_leaves->push_back({(uint32_t)id, bsp_lines_});
+  if (record_leaf_subsectors) record_leaf_subsectors->back() = (uint32_t)id;
   if (precomputed_polygons) {
     subsector_points_ = (*precomputed_polygons)[id];
   } else {
