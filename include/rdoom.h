@@ -302,6 +302,44 @@ rdoom_status rdoom_batch_resolve_plane(rdoom_batch *batch, uint32_t first, uint3
 /* Synchronous: the same plane copied to host memory, resolved in chunks of frames through the batch's bounded staging buffer;
  * reports the render's device errors like rdoom_batch_read_framebuffer. */
 rdoom_status rdoom_batch_read_plane(rdoom_batch *batch, uint32_t first, uint32_t count, uint32_t plane, void *host_out);
+/* Reduced-size observations of the batch's LAST render: frames [first, first+count) reduced by fx x fy on the device before
+ * anything is stored -- what a policy network takes (80 x 50, 160 x 100, often grey, often channel-first, with a depth channel of
+ * the same size) from a render that is large enough not to alias.  Nothing is switched on before the render.
+ *
+ *   fx, fy   each one of 1, 2, 4, 8, independently (so a cell never straddles a 32 x 32 quadrant); anything else: RDOOM_BAD_ARG
+ *   size     ow = width / fx, oh = height / fy (integer division; ow == 0 or oh == 0: RDOOM_BAD_ARG).  Cell (cx, cy) covers
+ *            framebuffer columns [cx*fx, cx*fx + fx) and rows [cy*fy, cy*fy + fy), row 0 the bottom row as stored; columns >= ow*fx
+ *            and rows >= oh*fy belong to no cell.  RDOOM_RGB_TOP_DOWN or-ed into `format` reverses the order of the OUTPUT rows
+ *            only: it does not move the cells.
+ *   inputs   per pixel, the colour is exactly rdoom_batch_resolve_rgb's RGB8 (PLAYPAL 0 of the pose's level where drawn,
+ *            RDOOM_CLEAR_R/G/B where not) and the depth exactly the RDOOM_PLANE_DEPTH element (+inf for sky and where nothing
+ *            was drawn).
+ *
+ * With n = fx*fy and S_c the sum of channel c over the cell, all in unsigned integers:
+ *
+ *   format                  output                                   element
+ *   RDOOM_OBS_RGB8          count x oh x ow x 3 uint8, interleaved   (2*S_c + n) / (2*n): the exact mean, a half rounds up
+ *   RDOOM_OBS_RGB8_PLANAR   count x 3 x oh x ow uint8                the same bytes, channel-first
+ *   RDOOM_OBS_GRAY8         count x oh x ow uint8                    (77*S_r + 150*S_g + 29*S_b + 128*n) / (256*n)
+ *   RDOOM_OBS_DEPTH_MIN     count x oh x ow float32                  the smallest depth of the cell: m = +inf, then
+ *                                                                    m = d < m ? d : m over the cell (a NaN is never taken)
+ *
+ * Rows are tight; an ow that is not a multiple of 4 is fine.  The colour formats need the levels' playpals, like
+ * rdoom_batch_resolve_rgb; RDOOM_OBS_DEPTH_MIN needs none.  An unknown format, or any other bit set in it, is RDOOM_BAD_ARG.
+ * At fx = fy = 1 the RGB8 bytes equal rdoom_batch_resolve_rgb's and the depth bits rdoom_batch_resolve_plane(RDOOM_PLANE_DEPTH)'s. */
+#define RDOOM_OBS_RGB8 1u
+#define RDOOM_OBS_RGB8_PLANAR 2u
+#define RDOOM_OBS_GRAY8 3u
+#define RDOOM_OBS_DEPTH_MIN 4u
+/* Asynchronous, on `stream` (a hipStream_t, may be NULL), ordered exactly like rdoom_batch_resolve_rgb / rdoom_batch_resolve_plane:
+ * waits for the batch's last render, writes the table's output to device_out -- device memory on the batch's device, aligned to
+ * the element -- and rdoom_batch_finish / the rdoom_batch_read_* then wait for it too.  Order the batch's next render after it. */
+rdoom_status rdoom_batch_resolve_observation(rdoom_batch *batch, uint32_t first, uint32_t count, uint32_t format,
+                                             uint32_t fx, uint32_t fy, void *device_out, void *stream);
+/* Synchronous: the same observations copied to host memory, resolved in chunks of frames through the batch's bounded staging
+ * buffer; reports the render's device errors like rdoom_batch_read_framebuffer. */
+rdoom_status rdoom_batch_read_observation(rdoom_batch *batch, uint32_t first, uint32_t count, uint32_t format,
+                                          uint32_t fx, uint32_t fy, void *host_out);
 /* Debug / test facility: capture the winning primitive id per pixel (triangle index in the draw order of the pose's level,
  * 0xFFFFFFFF = none) on the following renders, then read it back.  No GL counterpart.  It selects a slower instantiation of the
  * rasteriser and keeps 4 bytes per pixel for the whole batch: RDOOM_PLANE_PRIMITIVE above gives the same ids after any render,

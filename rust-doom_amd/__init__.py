@@ -29,6 +29,9 @@ CLEAR_RGB = (15, 18, 23)
 PLANE_DEPTH, PLANE_LABEL, PLANE_PRIMITIVE = 1, 2, 3
 LABEL_NONE = 0xFFFF
 PLANE_DTYPES = {PLANE_DEPTH: np.float32, PLANE_LABEL: np.uint16, PLANE_PRIMITIVE: np.uint32}
+# rdoom_batch_resolve_observation / rdoom_batch_read_observation: reduced-size observations (include/rdoom.h has the contract)
+OBS_RGB8, OBS_RGB8_PLANAR, OBS_GRAY8, OBS_DEPTH_MIN = 1, 2, 3, 4
+OBS_DTYPES = {OBS_RGB8: np.uint8, OBS_RGB8_PLANAR: np.uint8, OBS_GRAY8: np.uint8, OBS_DEPTH_MIN: np.float32}
 
 STATIC_VERTEX = np.dtype([('a_pos', '<f4', 3), ('a_atlas_uv', '<f4', 2), ('a_tile_uv', '<f4', 2),
                           ('a_tile_size', '<f4', 2), ('a_scroll_rate', '<f4'), ('a_row_height', '<f4'),
@@ -162,7 +165,8 @@ API_SYMBOLS = [
     'rdoom_world_map_lines', 'rdoom_worldset_level_map_lines', 'rdoom_world_draw_maps', 'rdoom_worldset_draw_maps',
     'rdoom_world_reveal_lines', 'rdoom_worldset_reveal_lines', 'rdoom_world_draw_maps_seen', 'rdoom_worldset_draw_maps_seen',
     'rdoom_world_map_sectors', 'rdoom_worldset_level_map_sectors', 'rdoom_world_locate_players', 'rdoom_worldset_locate_players',
-    'rdoom_world_draw_sector_maps', 'rdoom_worldset_draw_sector_maps']
+    'rdoom_world_draw_sector_maps', 'rdoom_worldset_draw_sector_maps', 'rdoom_batch_resolve_observation',
+    'rdoom_batch_read_observation']
 
 _lib = None
 
@@ -194,6 +198,26 @@ def _check(status):
 
 def _ptr(a):
     return a.ctypes.data_as(ctypes.c_void_p) if a is not None and a.size else None
+
+
+def _factors(factor):
+    fx, fy = (factor, factor) if isinstance(factor, (int, np.integer)) else factor
+    fx, fy = int(fx), int(fy)
+    if fx not in (1, 2, 4, 8) or fy not in (1, 2, 4, 8):
+        raise ValueError('factor must be 1, 2, 4 or 8, or a pair (fx, fy) of them, not %r' % (factor,))
+    return fx, fy
+
+
+def observation_shape(format, width, height, factor):
+    """shape of ONE frame's observation: (oh, ow, 3) OBS_RGB8, (3, oh, ow) OBS_RGB8_PLANAR, (oh, ow) OBS_GRAY8 (uint8) and
+    OBS_DEPTH_MIN (float32), with ow = width // fx, oh = height // fy; factor: an int or (fx, fy), each 1, 2, 4 or 8"""
+    if format not in OBS_DTYPES:
+        raise ValueError('format must be OBS_RGB8, OBS_RGB8_PLANAR, OBS_GRAY8 or OBS_DEPTH_MIN, not %r' % (format,))
+    fx, fy = _factors(factor)
+    ow, oh = int(width) // fx, int(height) // fy
+    if ow == 0 or oh == 0:
+        raise ValueError('factors %d x %d leave no cell of a %d x %d frame' % (fx, fy, width, height))
+    return {OBS_RGB8: (oh, ow, 3), OBS_RGB8_PLANAR: (3, oh, ow)}.get(format, (oh, ow))
 
 
 def device_count():
@@ -859,6 +883,48 @@ class Batch:
     def resolve_depth(self, out, first=0, count=None, top_down=False, stream=None):
         """resolve_plane(out, PLANE_DEPTH, ...): out a float32 tensor (or device pointer) of count*H*W elements"""
         return self.resolve_plane(out, PLANE_DEPTH, first, count, top_down, stream)
+
+    def _observation_args(self, format, factor, first, count, top_down):
+        shape = observation_shape(format, self.width, self.height, factor)
+        fx, fy = _factors(factor)
+        count = self.last_n - first if count is None else count
+        return int(first), int(count), int(format) | (RGB_TOP_DOWN if top_down else 0), fx, fy, (int(count),) + shape
+
+    def read_observation(self, format=OBS_RGB8, factor=4, first=0, count=None, top_down=False):
+        """rdoom_batch_read_observation: frames [first, first+count) of the last render reduced by `factor` (an int or (fx, fy),
+        each 1, 2, 4 or 8) as (count,) + observation_shape(format, W, H, factor): the exact mean colour of every cell (OBS_RGB8,
+        OBS_RGB8_PLANAR), its grey value (OBS_GRAY8) or its smallest depth (OBS_DEPTH_MIN, float32); row 0 = the bottom row of
+        cells unless top_down"""
+        first, count, fmt, fx, fy, shape = self._observation_args(format, factor, first, count, top_down)
+        out = np.zeros(shape, OBS_DTYPES[format])
+        _check(lib().rdoom_batch_read_observation(self._h, first, count, fmt, fx, fy, out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def resolve_observation(self, out, format=OBS_RGB8, factor=4, first=0, count=None, top_down=False, stream=None):
+        """rdoom_batch_resolve_observation: the same observations written to device memory, asynchronously on `stream` (a
+        hipStream_t handle, or a torch stream; None = the null stream).  out: a raw device pointer (int), or a contiguous torch
+        tensor on the batch's device with count * prod(observation_shape(...)) elements -- uint8 for the colour formats, float32
+        for OBS_DEPTH_MIN.  Returns out."""
+        first, count, fmt, fx, fy, shape = self._observation_args(format, factor, first, count, top_down)
+        if isinstance(out, int):
+            ptr = out
+        else:
+            import torch  # (only here: the package imports without torch)
+            if not isinstance(out, torch.Tensor):
+                raise TypeError('out must be a device pointer (int) or a torch tensor, not %s' % type(out).__name__)
+            want = torch.float32 if format == OBS_DEPTH_MIN else torch.uint8
+            if out.dtype != want or not out.is_contiguous() or out.device.type != 'cuda':
+                raise ValueError('out must be a contiguous %s tensor on the GPU (got %s, %s, contiguous=%s)'
+                                 % (want, out.dtype, out.device, out.is_contiguous()))
+            need = int(np.prod(shape))
+            if out.numel() != need:
+                raise ValueError('out has %d elements, frames %d..%d need %s = %d' % (out.numel(), first, first + count, shape, need))
+            ptr = out.data_ptr()  # (the library checks that it lives on the batch's device)
+        if stream is not None and not isinstance(stream, int):
+            stream = stream.cuda_stream
+        _check(lib().rdoom_batch_resolve_observation(self._h, first, count, fmt, fx, fy, ctypes.c_void_p(ptr or None),
+                                                     ctypes.c_void_p(stream or 0)))
+        return out
 
     def enable_primitive_ids(self):
         _check(lib().rdoom_batch_enable_primitive_ids(self._h))

@@ -107,6 +107,32 @@ struct PlaneArgs {
 size_t plane_element_bytes(uint32_t plane);
 rdoom_status launch_plane(hipStream_t st, const PlaneArgs &args);
 
+// Kernels 10 + 11: reduced-size observations (RDOOM_OBS_*) of frames [first, first + count) of the last render -- the mean colour,
+// its grey value or the smallest depth of every fx x fy cell -- from what kernels 5 to 8 read, then the cells that hold a pixel of
+// the fixup list (observe.hip)
+struct ObserveArgs {
+  const uint8_t *fb;
+  const void *vis;
+  bool vis16;
+  const uint32_t *qtab;
+  bool use_qtab;  // the render's FragmentPlan::skip_described_vis, as ResolveArgs
+  const PoseConst *poses;
+  const uint32_t *palettes;  // as ResolveArgs; not read by RDOOM_OBS_DEPTH_MIN
+  const TriRec *recs;        // cap records per pose; read by RDOOM_OBS_DEPTH_MIN only
+  uint32_t cap;
+  const uint32_t *fix_count;
+  const uint2 *fix_list;
+  uint32_t fix_cap;
+  uint32_t first, count;
+  int width, pitch, height;
+  uint32_t format;  // RDOOM_OBS_*
+  uint32_t fx, fy;  // 1, 2, 4 or 8 each
+  bool top_down;
+  void *out;  // count frames of (height / fy) x (width / fx) cells, aligned to the element
+};
+size_t observation_cell_bytes(uint32_t format);  // bytes per cell: 3 (both RGB8 layouts), 1 (grey), 4 (depth)
+rdoom_status launch_observe(hipStream_t st, const ObserveArgs &args);
+
 // Kernel 0 of rdoom_batch_render_players, and all of rdoom_poses_from_players_device: players' states -> cameras (frames.hip).
 // One lane per (player, object); every output is optional.
 struct PlayerFrameArgs {

@@ -18,6 +18,7 @@
 #include <hip/hip_runtime.h>
 
 #include "kernels.hpp"
+#include "plane_record.hpp"  // RecVal, fetch_record, plane_value, DEPTH_FAR: shared with observe.hip
 
 #pragma clang fp contract(off)
 
@@ -26,7 +27,6 @@ namespace {
 
 constexpr uint32_t PLANE_QROWS = 4;  // quadrant rows per workgroup, as resolve.hip
 constexpr uint32_t PF_QTAB = 1u, PF_TOP_DOWN = 2u, PF_DWORD = 4u;
-constexpr uint32_t DEPTH_FAR = 0x7F800000u;  // +inf: sky (sky.frag has no v_dist) and pixels nothing was drawn to
 
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 u32x4_a4 __attribute__((aligned(4)));  // 16-byte accesses at dword alignment (tight rows of any width)
@@ -48,37 +48,6 @@ struct PlaneOf<RDOOM_PLANE_PRIMITIVE> {
   typedef uint32_t elem;
   static constexpr uint32_t none = NONE;
 };
-
-// what a plane keeps of a record: depth the 1/w plane and the kind, the other two their finished value
-struct RecVal {
-  float w0, w1, w2;
-  uint32_t v;
-};
-
-// `tris`: the first triangle of the pose's level.  With a wave-uniform `rec` every load here is a scalar load.
-template <uint32_t PLANE>
-__device__ __forceinline__ RecVal fetch_record(const TriRec *__restrict__ prec, uint32_t rec, const LevelTri *__restrict__ tris) {
-  RecVal r{0.0f, 0.0f, 0.0f, 0u};
-  const uint32_t rf = prec[rec].r.flags;
-  const uint32_t kind = (rf >> 27) & 3u, prim = rf & 0xFFFFFFu;
-  if (PLANE == RDOOM_PLANE_DEPTH) {
-    const uint4 w = *reinterpret_cast<const uint4 *>(&prec[rec].s);  // (wp[0], wp[1], wp[2], up[0])
-    r.w0 = __uint_as_float(w.x), r.w1 = __uint_as_float(w.y), r.w2 = __uint_as_float(w.z);
-    r.v = kind;
-  } else if (PLANE == RDOOM_PLANE_LABEL) {
-    r.v = kind | ((tris[prim].packed >> 20) << 4);
-  } else {
-    r.v = prim;
-  }
-  return r;
-}
-
-template <uint32_t PLANE>
-__device__ __forceinline__ uint32_t plane_value(const RecVal &r, float px, float py) {
-  if (PLANE != RDOOM_PLANE_DEPTH) return r.v;
-  const float d = 1.0f / fmaf(r.w0, px, fmaf(r.w1, py, r.w2));  // F1: IEEE division, as texel_coords without RCP_EXACT
-  return r.v == RDOOM_KIND_SKY ? DEPTH_FAR : __float_as_uint(d);
-}
 
 template <uint32_t PLANE>
 __device__ __forceinline__ void store_run(typename PlaneOf<PLANE>::elem *dst, const uint32_t (&c)[16], bool dword) {

@@ -983,14 +983,8 @@ rdoom_status rdoom_batch_read_primitive_ids(rdoom_batch *b, uint32_t first, uint
 // rdoom_batch_read_rgb's staging holds as many whole frames as fit in this (at least one)
 static constexpr size_t RGB_STAGING_BYTES = (size_t)64 << 20;
 
-// what both RGB entry points reject before they touch the device or wait for anything
-static rdoom_status rgb_args(const rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, const void *out) {
-  if (format & ~(0xFFu | (uint32_t)RDOOM_RGB_TOP_DOWN)) return rdoom::fail(RDOOM_BAD_ARG, "unknown format bits 0x%x", format);
-  if ((format & 0xFFu) != RDOOM_RGB8 && (format & 0xFFu) != RDOOM_RGBA8)
-    return rdoom::fail(RDOOM_BAD_ARG, "format 0x%x: RDOOM_RGB8 or RDOOM_RGBA8, optionally | RDOOM_RGB_TOP_DOWN", format);
-  if (!b || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
-  if (b->last_n == 0) return rdoom::fail(RDOOM_BAD_ARG, "nothing rendered yet");
-  if ((uint64_t)first + count > b->last_n) return rdoom::fail(RDOOM_BAD_ARG, "frame range outside the last render");
+// the colour entry points: every level the poses of frames [first, first + count) of the last render belong to needs its playpal
+static rdoom_status playpal_check(const rdoom_batch *b, uint32_t first, uint32_t count) {
   const rdoom_level *lv = b->level;
   if (std::find(lv->has_palette.begin(), lv->has_palette.end(), 0) != lv->has_palette.end()) {
     // rdoom_batch_render_players: the levels are on the device, so every level of the set must have a palette
@@ -1003,6 +997,17 @@ static rdoom_status rgb_args(const rdoom_batch *b, uint32_t first, uint32_t coun
       if (!lv->has_palette[pc[p].level]) return rdoom::fail(RDOOM_BAD_ARG, "pose %u: its level %u was created without a playpal", p, pc[p].level);
   }
   return RDOOM_OK;
+}
+
+// what both RGB entry points reject before they touch the device or wait for anything
+static rdoom_status rgb_args(const rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, const void *out) {
+  if (format & ~(0xFFu | (uint32_t)RDOOM_RGB_TOP_DOWN)) return rdoom::fail(RDOOM_BAD_ARG, "unknown format bits 0x%x", format);
+  if ((format & 0xFFu) != RDOOM_RGB8 && (format & 0xFFu) != RDOOM_RGBA8)
+    return rdoom::fail(RDOOM_BAD_ARG, "format 0x%x: RDOOM_RGB8 or RDOOM_RGBA8, optionally | RDOOM_RGB_TOP_DOWN", format);
+  if (!b || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (b->last_n == 0) return rdoom::fail(RDOOM_BAD_ARG, "nothing rendered yet");
+  if ((uint64_t)first + count > b->last_n) return rdoom::fail(RDOOM_BAD_ARG, "frame range outside the last render");
+  return playpal_check(b, first, count);
 }
 
 // device_out of the resolve entry points must be device memory of the batch's device with room for what the kernels write there
@@ -1116,6 +1121,70 @@ rdoom_status rdoom_batch_read_plane(rdoom_batch *b, uint32_t first, uint32_t cou
   for (uint32_t f = first; f < first + count; f += chunk) {
     const uint32_t n = std::min(chunk, first + count - f);
     if (rdoom_status rs = plane_impl(b, f, n, plane, b->d_rgb, b->copy_stream)) return rs;
+    HIP_TRY(hipMemcpyAsync((uint8_t *)host_out + (size_t)(f - first) * frame, b->d_rgb, n * frame, hipMemcpyDeviceToHost, b->copy_stream));
+    HIP_TRY(hipStreamSynchronize(b->copy_stream));
+  }
+  return RDOOM_OK;
+}
+
+// ---- reduced-size observations (observe.hip) -------------------------------------------------------------------------------
+// what both observation entry points reject before they touch the device or wait for anything
+static rdoom_status observation_args(const rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint32_t fx, uint32_t fy,
+                                     const void *out) {
+  if (format & ~(0xFFu | (uint32_t)RDOOM_RGB_TOP_DOWN)) return rdoom::fail(RDOOM_BAD_ARG, "unknown format bits 0x%x", format);
+  const uint32_t which = format & 0xFFu;
+  if (which != RDOOM_OBS_RGB8 && which != RDOOM_OBS_RGB8_PLANAR && which != RDOOM_OBS_GRAY8 && which != RDOOM_OBS_DEPTH_MIN)
+    return rdoom::fail(RDOOM_BAD_ARG, "format 0x%x: RDOOM_OBS_RGB8, _RGB8_PLANAR, _GRAY8 or _DEPTH_MIN, optionally | RDOOM_RGB_TOP_DOWN", format);
+  for (uint32_t v : {fx, fy})
+    if (v != 1u && v != 2u && v != 4u && v != 8u) return rdoom::fail(RDOOM_BAD_ARG, "factors %u x %u: each must be 1, 2, 4 or 8", fx, fy);
+  if (!b || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (b->last_n == 0) return rdoom::fail(RDOOM_BAD_ARG, "nothing rendered yet");
+  if ((uint64_t)first + count > b->last_n) return rdoom::fail(RDOOM_BAD_ARG, "frame range outside the last render");
+  if (b->width / fx == 0 || b->height / fy == 0)
+    return rdoom::fail(RDOOM_BAD_ARG, "factors %u x %u leave no cell of a %u x %u frame", fx, fy, b->width, b->height);
+  if (which == RDOOM_OBS_DEPTH_MIN && (uintptr_t)out % 4u) return rdoom::fail(RDOOM_BAD_ARG, "output is not aligned to the format's 4-byte element");
+  return which == RDOOM_OBS_DEPTH_MIN ? RDOOM_OK : playpal_check(b, first, count);
+}
+
+static size_t observation_frame_bytes(const rdoom_batch *b, uint32_t format, uint32_t fx, uint32_t fy) {
+  return (size_t)(b->height / fy) * (b->width / fx) * observation_cell_bytes(format & 0xFFu);
+}
+
+// queues the two observation kernels on st behind the last render; ev_done then marks their end, as resolve_impl
+static rdoom_status observation_impl(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint32_t fx, uint32_t fy, void *out,
+                                     hipStream_t st) {
+  HIP_TRY(hipStreamWaitEvent(st, b->ev_done, 0));
+  ObserveArgs a{};
+  a.fb = b->d_fb, a.vis = b->d_vis, a.vis16 = b->vis16, a.qtab = b->d_qtab, a.use_qtab = b->last_skip_vis, a.poses = b->d_poses;
+  a.palettes = b->level->d_palettes, a.recs = b->d_recs, a.cap = b->cap;
+  a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list, a.fix_cap = b->fix_cap;
+  a.first = first, a.count = count, a.width = (int)b->width, a.pitch = (int)b->pitch, a.height = (int)b->height;
+  a.format = format & 0xFFu, a.fx = fx, a.fy = fy, a.top_down = (format & RDOOM_RGB_TOP_DOWN) != 0u, a.out = out;
+  const rdoom_status rs = launch_observe(st, a);
+  HIP_TRY(hipEventRecord(b->ev_done, st));
+  return rs;
+}
+
+rdoom_status rdoom_batch_resolve_observation(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint32_t fx, uint32_t fy,
+                                             void *device_out, void *stream) {
+  if (rdoom_status rs = observation_args(b, first, count, format, fx, fy, device_out)) return rs;
+  HIP_TRY(bind_device(b));
+  if (rdoom_status rs = device_out_check(b, device_out, (size_t)count * observation_frame_bytes(b, format, fx, fy))) return rs;
+  return observation_impl(b, first, count, format, fx, fy, device_out, (hipStream_t)stream);
+}
+
+rdoom_status rdoom_batch_read_observation(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint32_t fx, uint32_t fy,
+                                          void *host_out) {
+  if (rdoom_status rs = observation_args(b, first, count, format, fx, fy, host_out)) return rs;
+  HIP_TRY(bind_device(b));
+  if (rdoom_status fs = device_flags(b)) return fs;
+  if (count == 0) return RDOOM_OK;
+  const size_t frame = observation_frame_bytes(b, format, fx, fy);
+  const uint32_t chunk = (uint32_t)std::max<size_t>(1u, std::min<size_t>(count, RGB_STAGING_BYTES / frame));
+  if (rdoom_status rs = staging(b, chunk * frame)) return rs;
+  for (uint32_t f = first; f < first + count; f += chunk) {
+    const uint32_t n = std::min(chunk, first + count - f);
+    if (rdoom_status rs = observation_impl(b, f, n, format, fx, fy, b->d_rgb, b->copy_stream)) return rs;
     HIP_TRY(hipMemcpyAsync((uint8_t *)host_out + (size_t)(f - first) * frame, b->d_rgb, n * frame, hipMemcpyDeviceToHost, b->copy_stream));
     HIP_TRY(hipStreamSynchronize(b->copy_stream));
   }
