@@ -1052,6 +1052,43 @@ rdoom_status rdoom_worldset_draw_sector_maps(const rdoom_worldset *set, const rd
                                              const uint32_t *d_visited, uint32_t stride, uint16_t *d_sector_out, float *d_floor_out,
                                              float *d_ceiling_out, void *stream);
 
+/* ---- flood: every player's sector map flooded from a seed cell, the walking distance to each cell ----------------
+ * Where a player can go from where it stands, and in how many steps: a shortest-path flood over the floor and ceiling planes of a
+ * filled map.  A pure function of the two planes: no handle, no table.  Every float below is binary32, every operation is rounded
+ * once and none is contracted.
+ * Inputs.  d_floor, d_ceiling: n x height x width floats each, exactly what rdoom_world_draw_sector_maps stores -- row r, column c,
+ * either row order, a void cell +inf / -inf.  The flood works on stored rows: flipping the rows flips the result, so there is no
+ * orientation flag.
+ * Open.  With f the floor and g the ceiling of a cell, the cell is open when f < +inf && f > -inf && g - f >= clearance.  A NaN makes
+ * every comparison false: that cell is closed.
+ * Moves.  A move from cell a to a 4-neighbour b inside the grid is allowed when both cells are open, f_b - f_a <= max_step,
+ * f_a - f_b <= max_drop, and fminf(g_a, g_b) - fmaxf(f_a, f_b) >= clearance.  max_drop may be +inf.  Moves are directed: a ledge can
+ * be dropped from but not climbed.
+ * Seeds.  d_seeds: n x 2 int32 (column, row) in stored order; NULL: (width / 2, height / 2) for every player -- the cell at, or with
+ * a corner at, the player's point of the map contract.
+ * d_dist_out (n x height x width uint16): the smallest number of allowed moves from player p's seed to the cell, 0 at the seed;
+ *   RDOOM_FLOOD_UNREACHED where there is no path, where the cell is closed, and everywhere when the seed is closed or outside the
+ *   grid.
+ * d_count_out (n uint32, may be NULL): the number of cells of player p with a distance below RDOOM_FLOOD_UNREACHED.
+ * params: max_step, max_drop, clearance as above; flags must be 0.  The limits model walking -- Doom's 24-unit step and 56-unit
+ * body are 0.24 and 0.56 at this library's scale -- and nothing ties them to the sphere-and-spring physics of
+ * rdoom_world_step_players.
+ * width * height is at most rdoom_flood_max_cells' *cells_out, a constant of the library chosen from the kernel's LDS layout: at
+ * least 19 200 (160 x 120) and below 65 535, so that a distance always fits.
+ * One launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so the call can be
+ * captured into a graph.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): NULL params; (n > 0) NULL d_floor /
+ * d_ceiling / d_dist_out; a zero width or height; more cells than rdoom_flood_max_cells; non-zero flags; a NaN or negative max_step,
+ * max_drop or clearance; NULL cells_out.  n == 0 queues nothing. */
+#define RDOOM_FLOOD_UNREACHED 0xFFFFu
+typedef struct rdoom_flood_params {
+  float max_step, max_drop, clearance;
+  uint32_t flags;
+} rdoom_flood_params;
+rdoom_status rdoom_flood_max_cells(uint32_t *cells_out);
+rdoom_status rdoom_flood_maps(const float *d_floor, const float *d_ceiling, uint32_t n, uint32_t width, uint32_t height,
+                              const int32_t *d_seeds, const rdoom_flood_params *params, uint16_t *d_dist_out, uint32_t *d_count_out,
+                              void *stream);
+
 #ifdef __cplusplus
 }
 #endif

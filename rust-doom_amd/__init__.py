@@ -77,6 +77,7 @@ MAP_SECTOR = np.dtype([('floor', '<f4'), ('ceiling', '<f4'), ('floor_id', '<u4')
                        ('sector_type', '<u4'), ('tag', '<u4')])  # rdoom_map_sector
 MAP_EDGE = np.dtype([('a', '<f4', 2), ('d', '<f4', 2)])  # rdoom_map_edge
 SECTOR_NONE, SECTOR_NONE16 = 0xFFFFFFFF, 0xFFFF
+FLOOD_UNREACHED = 0xFFFF  # RDOOM_FLOOD_UNREACHED: flood_maps' distance of a cell no allowed path leads to
 LINE_MAPPED = 0x100  # RDOOM_LINE_MAPPED, Doom's "already on the map": drawn through a seen set whether seen or not
 
 
@@ -166,7 +167,7 @@ API_SYMBOLS = [
     'rdoom_world_reveal_lines', 'rdoom_worldset_reveal_lines', 'rdoom_world_draw_maps_seen', 'rdoom_worldset_draw_maps_seen',
     'rdoom_world_map_sectors', 'rdoom_worldset_level_map_sectors', 'rdoom_world_locate_players', 'rdoom_worldset_locate_players',
     'rdoom_world_draw_sector_maps', 'rdoom_worldset_draw_sector_maps', 'rdoom_batch_resolve_observation',
-    'rdoom_batch_read_observation']
+    'rdoom_batch_read_observation', 'rdoom_flood_max_cells', 'rdoom_flood_maps']
 
 _lib = None
 
@@ -1449,6 +1450,66 @@ def _draw_sector_maps(call, words, states, levels, width, height, scale, offsets
                 *[v(t.data_ptr()) if t is not None else None for t in planes], v(_stream_handle(stream))))
     given = tuple(t for t in planes if t is not None)
     return given[0] if len(given) == 1 else given
+
+
+class FloodParams(ctypes.Structure):
+    """rdoom_flood_params"""
+    _fields_ = [('max_step', ctypes.c_float), ('max_drop', ctypes.c_float), ('clearance', ctypes.c_float), ('flags', ctypes.c_uint32)]
+
+
+def flood_max_cells():
+    """rdoom_flood_max_cells: the most cells (width * height) of a map flood_maps takes, a constant of the library"""
+    cells = ctypes.c_uint32(0)
+    _check(lib().rdoom_flood_max_cells(ctypes.byref(cells)))
+    return cells.value
+
+
+def flood_maps(floor, ceiling, seeds=None, max_step=0.24, max_drop=float('inf'), clearance=0.56, dist_out=None, count_out=None, stream=None):
+    """rdoom_flood_maps: every player's filled map flooded from a seed cell.  floor, ceiling: the float32 (n, H, W) GPU tensors
+    draw_sector_maps(floor=True, ceiling=True) returns, in either row order (the flood works on stored rows); H * W is at most
+    flood_max_cells().  A cell is open when its floor is finite and ceiling - floor >= clearance; a move to a 4-neighbour is allowed
+    when both are open, the floor rises by at most max_step and falls by at most max_drop, and the opening the two share
+    (min ceiling - max floor) is at least clearance -- so moves are directed, a ledge is dropped from and not climbed, and a door a
+    player has not opened blocks that player's flood.  seeds: None -- the cell (W // 2, H // 2), the player's own -- or an int32
+    (n, 2) tensor of (column, row) in stored order.  Returns the (n, H, W) uint16 tensor of distances in moves, 0 at the seed and
+    FLOOD_UNREACHED where no path leads, where the cell is closed, and everywhere when the seed is closed or outside the grid
+    (dist_out: a 16-bit integer tensor, or a raw device pointer, to write instead of a new one); with count_out True, an (n,)
+    32-bit integer tensor or a raw device pointer, returns (distances, counts), counts[p] the number of cells player p reaches.  The defaults are Doom's 24-unit step and 56-unit
+    body at this project's 1/100 scale: a model of walking, which nothing ties to the sphere-and-spring physics of World.step.
+    One launch, asynchronous on `stream` (None, a torch stream or a raw handle); it can be captured into a graph."""
+    import torch
+    for t, what in ((floor, 'floor'), (ceiling, 'ceiling')):
+        if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or not t.is_contiguous() or t.dtype != torch.float32 or t.dim() != 3:
+            raise ValueError('%s must be a contiguous float32 (n, height, width) tensor on the GPU' % what)
+    if floor.shape != ceiling.shape:
+        raise ValueError('floor %s and ceiling %s differ in shape' % (tuple(floor.shape), tuple(ceiling.shape)))
+    n, height, width = (int(x) for x in floor.shape)
+    if seeds is not None and (not isinstance(seeds, torch.Tensor) or seeds.device.type != 'cuda' or not seeds.is_contiguous() or
+                              seeds.dtype != torch.int32 or tuple(seeds.shape) != (n, 2)):
+        raise ValueError('seeds must be a contiguous int32 (%d, 2) tensor of (column, row) on the GPU' % n)
+    if dist_out is None:
+        dist_out = torch.empty((n, height, width), dtype=torch.uint16, device=floor.device)
+    if isinstance(dist_out, int) and not isinstance(dist_out, bool):
+        pd = dist_out  # a raw device pointer to n * height * width uint16
+    elif not isinstance(dist_out, torch.Tensor) or dist_out.element_size() != 2 or dist_out.dtype.is_floating_point:
+        raise ValueError('dist_out must be a 16-bit integer tensor or a device pointer')
+    else:
+        pd = _out_tensor(dist_out, n * height * width * 2, 'dist_out')
+    if count_out is None or count_out is False:
+        count_out = None
+    elif count_out is True:
+        count_out = torch.empty(n, dtype=torch.int32, device=floor.device)
+    if isinstance(count_out, int) and not isinstance(count_out, bool):
+        pc = count_out  # a raw device pointer to n uint32
+    elif count_out is not None and (not isinstance(count_out, torch.Tensor) or count_out.element_size() != 4 or count_out.dtype.is_floating_point):
+        raise ValueError('count_out must be True, a 32-bit integer tensor or a device pointer')
+    else:
+        pc = _out_tensor(count_out, n * 4, 'count_out')
+    params = FloodParams(max_step, max_drop, clearance, 0)
+    v = ctypes.c_void_p
+    _check(lib().rdoom_flood_maps(v(floor.data_ptr()), v(ceiling.data_ptr()), n, width, height, v(seeds.data_ptr()) if seeds is not None else None,
+                                  ctypes.byref(params), v(pd), v(pc), v(_stream_handle(stream))))
+    return dist_out if count_out is None else (dist_out, count_out)
 
 
 class World:

@@ -179,4 +179,16 @@ struct LightTableArgs {
 };
 rdoom_status launch_light_tables(hipStream_t st, const LightTableArgs &args);
 
+// Kernel 12: every player's sector map flooded from its seed (flood.hip; include/rdoom.h "flood" has the contract).  One workgroup
+// per player; dynamic LDS: a 16-bit distance and a byte of move bits per cell.
+struct FloodArgs {
+  const float *floor, *ceiling;  // n x height x width each, as rdoom_world_draw_sector_maps stores them
+  const int32_t *seeds;          // n x (column, row), or null: (width / 2, height / 2)
+  uint16_t *dist_out;            // n x height x width
+  uint32_t *count_out;           // n, or null
+  uint32_t width, height, cells; // cells = width * height <= rdoom_flood_max_cells
+  uint32_t seg;                  // cells of a row or column one thread sweeps in a phase
+  float max_step, max_drop, clearance;
+};
+
 }  // namespace rdoom_dev
