@@ -1089,6 +1089,80 @@ rdoom_status rdoom_flood_maps(const float *d_floor, const float *d_ceiling, uint
                               const int32_t *d_seeds, const rdoom_flood_params *params, uint16_t *d_dist_out, uint32_t *d_count_out,
                               void *stream);
 
+/* ---- spawn: players reset on the device, at seeded random points of their level's walkable floor ---------------
+ * One launch writes a fresh rdoom_player_state for every player whose mask byte is set: a pseudo-random point of the level's floor
+ * where a body fits, reproducible from a seed, or the level's start.  The reference project has no counterpart of this: nothing
+ * here restates it.
+ * Spawn table.  One per level, a pure function of rdoom_world_arrays: the triangles whose normal vertex has y > 0 (the floors of
+ * WorldBuilder::floor, static and dynamic alike), in the order of the triangle array.  With a, b, c = the triangle's v1, v2, v3, its
+ * area is 0.5 * fabs((b.x - a.x) * (c.z - a.z) - (b.z - a.z) * (c.x - a.x)) in binary64 (the vertices converted, every operation
+ * rounded once, nothing contracted); a triangle whose area is not > 0 has no entry.  cumulative: the binary64 sum of the areas up to
+ * and including the entry, in table order, rounded once to binary32.  total = the last entry's cumulative, 0 for an empty table.
+ * start_pos / start_yaw: the level's start (rdoom_worldset_level_info's), the state a fallback writes.
+ * Generator.  Philox4x32-10 (Salmon et al., SC'11), integer only and stateless.  Key k = (seed & 0xFFFFFFFF, seed >> 32); counter
+ * x = (p, e, t, 0) with p the player's index in the call, e = d_episode[p] (0 with a NULL d_episode) and t the try, 1 .. 8.  Ten
+ * rounds of: (h0, l0) = the high and low 32 bits of 0xD2511F53 * x0, (h1, l1) = those of 0xCD9E8D57 * x2,
+ * x = (h1 ^ x1 ^ k0, l1, h0 ^ x3 ^ k1, l0); between rounds (nine times) k0 += 0x9E3779B9, k1 += 0xBB67AE85, all modulo 2^32.  The four
+ * draws of a try are u_i = (float)(x_i >> 8) * 0x1p-24f, exact and in [0, 1).  The same (seed, p, e) gives the same state in any batch.
+ * Candidate (binary32, every operation rounded once, nothing contracted).  target = u0 * total.  The entry is the first whose
+ * cumulative > target, found as: lo = 0, hi = n_entries; while lo < hi { mid = (lo + hi) >> 1; if cumulative[mid] > target
+ * hi = mid; else lo = mid + 1; }; the entry is lo, or n_entries - 1 when lo == n_entries (target rounded up to total).  If
+ * u1 + u2 > 1, u1 = 1 - u1 and u2 = 1 - u2.  q = (a + u1 * (b - a)) + u2 * (c - a), x, y and z alike.
+ * Validity.  With s(x, z) the sector at a point ("sectors" above), and f(s), g(s) its live floor and ceiling for player p exactly as
+ * rdoom_world_locate_players gives them (height + off(id) on row p of d_object_offsets), a point (x, z) is clear when s(x, z) is not
+ * RDOOM_SECTOR_NONE and g - f >= clearance.  The candidate is valid when q is clear, fabsf(f(s(q)) - q.y) <= max_step (a floor
+ * triangle lying under another floor is not stood on), and each of the eight points (q.x + margin, q.z), (q.x - margin, q.z),
+ * (q.x, q.z + margin), (q.x, q.z - margin), (q.x + k, q.z + k), (q.x - k, q.z + k), (q.x + k, q.z - k), (q.x - k, q.z - k) with
+ * k = margin * 0.70710677f is clear and, with rise = its f - f(s(q)), has fabsf(rise) <= max_step and not
+ * (rise > 0 && rise < RDOOM_SPAWN_RISE - margin).  The last term is the landing rule: the body starts with its centre
+ * RDOOM_SPAWN_RISE above the floor, so a floor beside it that is higher by less than RDOOM_SPAWN_RISE - margin lies under the body's
+ * sphere, which would come down on that floor's edge and slide off it; a higher one is a wall to it.  A NaN in fabsf(rise) <= max_step
+ * or in a clearance makes the comparison false: not valid.  A shut door (ceiling == floor) is excluded by the clearance, in the game
+ * of the player who has not opened it only.
+ * Tries.  t = 1, 2 .. RDOOM_SPAWN_TRIES; the first valid candidate wins.  An empty table has no candidate.
+ * The state written.  pos = (q.x, f(s(q)) + RDOOM_SPAWN_RISE, q.z): as high above the live floor as the start is above the floor at
+ * the start marker; vel = 0; yaw = u3 * 6.2831855f (the try's fourth draw, one binary32 product); pitch = 1e-8f;
+ * last_height_diff = 0; flags = params->flags.  Without a valid candidate: pos = start_pos, yaw = start_yaw, the rest the same --
+ * byte for byte the state the level's start gives.
+ * d_tries_out (n uint32, may be NULL): the winning try, 1 .. RDOOM_SPAWN_TRIES, or 0 for the start state.
+ * d_mask (n bytes, may be NULL: every player): where the byte is 0 neither the state nor d_tries_out[p] is written.
+ * d_episode (n uint32, may be NULL) is read and never written: the caller adds the mask to it to get other points at the next reset.
+ * d_states, d_object_offsets / n_objects, d_levels: as for rdoom_world_locate_players.  A level slot >= the set's size is seen on
+ * the device only: that state is untouched and d_tries_out[p] is 0.
+ * One launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so the call can be
+ * captured into a graph.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): a NULL handle or params; (n > 0) NULL
+ * d_states / d_levels; a NaN or negative margin, clearance or max_step; d_object_offsets with n_objects smaller than the game's
+ * objects; a handle created with RDOOM_WORLD_HOST_ONLY or living on another device.  An empty table is no error: every masked player
+ * gets the start state.  n == 0 queues nothing. */
+#define RDOOM_SPAWN_TRIES 8u
+#define RDOOM_SPAWN_RISE 0.5f
+typedef struct rdoom_spawn_entry {
+  float a[3], b[3], c[3];
+  float cumulative;
+} rdoom_spawn_entry;
+/* borrowed pointers into a rdoom_world / rdoom_worldset (valid until it is destroyed) */
+typedef struct rdoom_spawn_table {
+  const rdoom_spawn_entry *entries;
+  uint32_t n_entries;
+  float start_pos[3], start_yaw;
+} rdoom_spawn_table;
+typedef struct rdoom_spawn_params {
+  float margin, clearance, max_step;
+  uint32_t flags;
+} rdoom_spawn_params;
+/* The spawn table of the world's level, and of slot `slot` of a set (equal to the single world's of the same level).  Both work on
+ * RDOOM_WORLD_HOST_ONLY handles. */
+rdoom_status rdoom_world_spawn_table(const rdoom_world *world, rdoom_spawn_table *out);
+rdoom_status rdoom_worldset_level_spawn_table(const rdoom_worldset *set, uint32_t slot, rdoom_spawn_table *out);
+rdoom_status rdoom_world_spawn_players(const rdoom_world *world, rdoom_player_state *d_states, uint32_t n,
+                                       const float *d_object_offsets, uint32_t n_objects, const uint8_t *d_mask, uint64_t seed,
+                                       const uint32_t *d_episode, const rdoom_spawn_params *params, uint32_t *d_tries_out,
+                                       void *stream);
+rdoom_status rdoom_worldset_spawn_players(const rdoom_worldset *set, rdoom_player_state *d_states, const uint32_t *d_levels,
+                                          uint32_t n, const float *d_object_offsets, uint32_t n_objects, const uint8_t *d_mask,
+                                          uint64_t seed, const uint32_t *d_episode, const rdoom_spawn_params *params,
+                                          uint32_t *d_tries_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

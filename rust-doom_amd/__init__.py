@@ -78,6 +78,9 @@ MAP_SECTOR = np.dtype([('floor', '<f4'), ('ceiling', '<f4'), ('floor_id', '<u4')
 MAP_EDGE = np.dtype([('a', '<f4', 2), ('d', '<f4', 2)])  # rdoom_map_edge
 SECTOR_NONE, SECTOR_NONE16 = 0xFFFFFFFF, 0xFFFF
 FLOOD_UNREACHED = 0xFFFF  # RDOOM_FLOOD_UNREACHED: flood_maps' distance of a cell no allowed path leads to
+SPAWN_TRIES = 8  # RDOOM_SPAWN_TRIES: the candidates spawn_players draws for a player before it falls back to the level's start
+SPAWN_RISE = 0.5  # RDOOM_SPAWN_RISE: a spawned player's height above the live floor, the start's above the floor at the start marker
+SPAWN_ENTRY = np.dtype([('a', '<f4', 3), ('b', '<f4', 3), ('c', '<f4', 3), ('cumulative', '<f4')])  # rdoom_spawn_entry
 LINE_MAPPED = 0x100  # RDOOM_LINE_MAPPED, Doom's "already on the map": drawn through a seen set whether seen or not
 
 
@@ -167,7 +170,8 @@ API_SYMBOLS = [
     'rdoom_world_reveal_lines', 'rdoom_worldset_reveal_lines', 'rdoom_world_draw_maps_seen', 'rdoom_worldset_draw_maps_seen',
     'rdoom_world_map_sectors', 'rdoom_worldset_level_map_sectors', 'rdoom_world_locate_players', 'rdoom_worldset_locate_players',
     'rdoom_world_draw_sector_maps', 'rdoom_worldset_draw_sector_maps', 'rdoom_batch_resolve_observation',
-    'rdoom_batch_read_observation', 'rdoom_flood_max_cells', 'rdoom_flood_maps']
+    'rdoom_batch_read_observation', 'rdoom_flood_max_cells', 'rdoom_flood_maps',
+    'rdoom_world_spawn_table', 'rdoom_worldset_level_spawn_table', 'rdoom_world_spawn_players', 'rdoom_worldset_spawn_players']
 
 _lib = None
 
@@ -1512,6 +1516,54 @@ def flood_maps(floor, ceiling, seeds=None, max_step=0.24, max_drop=float('inf'),
     return dist_out if count_out is None else (dist_out, count_out)
 
 
+class SpawnTableArrays(ctypes.Structure):
+    """rdoom_spawn_table"""
+    _fields_ = [('entries', ctypes.c_void_p), ('n_entries', ctypes.c_uint32), ('start_pos', ctypes.c_float * 3), ('start_yaw', ctypes.c_float)]
+
+
+class SpawnParams(ctypes.Structure):
+    """rdoom_spawn_params"""
+    _fields_ = [('margin', ctypes.c_float), ('clearance', ctypes.c_float), ('max_step', ctypes.c_float), ('flags', ctypes.c_uint32)]
+
+
+class SpawnTable(collections.namedtuple('SpawnTable', 'entries start_pos start_yaw')):
+    """a copy of a level's spawn table (rdoom_spawn_table): entries, a SPAWN_ENTRY record per floor triangle with an area (its corners
+    a, b, c and the cumulative area up to and including it), in the order of arrays()['triangles']; start_pos (3,) float32 and
+    start_yaw float32, the level's start, which a player without a valid candidate gets"""
+
+
+def _spawn_table(get):
+    """World.spawn_table / WorldSet.spawn_table: a copy of the table get(&rdoom_spawn_table) lends"""
+    a = SpawnTableArrays()
+    _check(get(ctypes.byref(a)))
+    return SpawnTable(BuiltLevel._view(None, a.entries, a.n_entries, SPAWN_ENTRY), np.array(tuple(a.start_pos), np.float32), np.float32(a.start_yaw))
+
+
+def _spawn_players(call, states, levels, seed, mask, episode, offsets, margin, clearance, max_step, flags, tries_out, stream):
+    """World.spawn_players / WorldSet.spawn_players: the checks and the launch; call(states, levels, n, offsets, n_objects, mask, seed,
+    episode, params, tries_out, stream) is the C entry point with its handle bound"""
+    n, n_obj = _player_tensors(states, levels, offsets)
+    seed = int(seed)
+    if not 0 <= seed < 1 << 64:
+        raise ValueError('seed must fit 64 bits without a sign, got %d' % seed)
+    pointers = []
+    for t, size, what in ((mask, 1, 'mask'), (episode, 4, 'episode'), (tries_out, 4, 'tries_out')):
+        if t is None or (isinstance(t, int) and not isinstance(t, bool)):
+            pointers.append(t)  # nothing, or a raw device pointer to n elements
+            continue
+        if not hasattr(t, 'element_size') or t.element_size() != size or t.dtype.is_floating_point:
+            raise ValueError('%s must hold one %d-bit integer per player, or be a device pointer' % (what, 8 * size))
+        pointers.append(_out_tensor(t, n * size, what))
+    if margin is None:
+        margin = float(player_config_default()['radius'])
+    params = SpawnParams(margin, clearance, max_step, int(flags))
+    v = ctypes.c_void_p
+    _check(call(v(states.data_ptr()), v(levels.data_ptr()) if levels is not None else None, n,
+                v(offsets.data_ptr()) if offsets is not None else None, n_obj, v(pointers[0]), ctypes.c_uint64(seed), v(pointers[1]),
+                ctypes.byref(params), v(pointers[2]), v(_stream_handle(stream))))
+    return states
+
+
 class World:
     """game::world::World on the host and the current device (rdoom_world_create): World::sweep_sphere for a batch of queries,
     Player::update for a batch of players."""
@@ -1717,6 +1769,27 @@ class World:
         return _draw_sector_maps(lambda st, lv, *rest: L.rdoom_world_draw_sector_maps(self._h, st, *rest), self.visited_words(), states, None, width,
                                  height, scale, offsets, rotate, top_down, sector_out, floor, ceiling, visited, stream)
 
+    # ---- spawn -------------------------------------------------------------------------------------------------------------
+    def spawn_table(self):
+        """a copy of rdoom_world_spawn_table: the level's SpawnTable of (entries, start_pos, start_yaw)"""
+        return _spawn_table(lambda a: lib().rdoom_world_spawn_table(self._h, a))
+
+    def spawn_players(self, states, seed, mask=None, episode=None, offsets=None, margin=None, clearance=0.56, max_step=0.24,
+                      flags=PLAYER_CLIP, tries_out=None, stream=None):
+        """rdoom_world_spawn_players: a fresh PLAYER_STATE, written in place, for every player whose mask byte is set (mask: None --
+        every player -- or n bytes / bools on the GPU): at rest at a pseudo-random point of the level's floor where a body fits, with
+        a random yaw, SPAWN_RISE above the floor as the level's start is.  The point is a function of (seed, the player's index,
+        episode[p]) alone -- episode: None (0) or a 32-bit integer tensor of n, read only; episode.add_(mask) before the next reset
+        gives other points.  A candidate is a uniform point of the floor triangles (spawn_table()); it is taken when its sector and
+        those of the four points `margin` away along x and z (None: the player config's radius) have `clearance` of headroom in the
+        player's own game (offsets: None or step_game's tensor -- a door the player has not opened is no place to stand) and floors
+        within `max_step` of each other.  After SPAWN_TRIES candidates the player gets the level's start instead.  tries_out: an
+        optional 32-bit integer tensor of n for the winning try, 1 .. SPAWN_TRIES, 0 for the start.  mask, episode and tries_out may
+        be raw device pointers.  Returns states.  One launch, asynchronous on `stream`; it can be captured into a graph."""
+        L = lib()
+        return _spawn_players(lambda st, lv, *rest: L.rdoom_world_spawn_players(self._h, st, *rest), states, None, seed, mask, episode,
+                              offsets, margin, clearance, max_step, flags, tries_out, stream)
+
 
 class WorldSetLevelInfo(ctypes.Structure):
     _fields_ = [('archive_index', ctypes.c_uint32), ('destination', ctypes.c_uint32), ('start_pos', ctypes.c_float * 3),
@@ -1890,3 +1963,17 @@ class WorldSet:
             sector_out = True
         return _draw_sector_maps(lambda st, lv, *rest: L.rdoom_worldset_draw_sector_maps(self._h, st, lv, *rest), self.visited_words(), states, levels, width,
                                  height, scale, offsets, rotate, top_down, sector_out, floor, ceiling, visited, stream)
+
+    # ---- spawn -------------------------------------------------------------------------------------------------------------
+    def spawn_table(self, slot):
+        """World.spawn_table of slot `slot`"""
+        return _spawn_table(lambda a: lib().rdoom_worldset_level_spawn_table(self._h, int(slot), a))
+
+    def spawn_players(self, states, levels, seed, mask=None, episode=None, offsets=None, margin=None, clearance=0.56, max_step=0.24,
+                      flags=PLAYER_CLIP, tries_out=None, stream=None):
+        """rdoom_worldset_spawn_players: World.spawn_players for players spread over the set's levels (levels: game_state's tensor of
+        slots), each on the floor of its own level; a player without a valid candidate gets start_states' record of its slot.  A
+        player whose slot is not in the set keeps its state and has 0 in tries_out."""
+        L = lib()
+        return _spawn_players(lambda st, lv, *rest: L.rdoom_worldset_spawn_players(self._h, st, lv, *rest), states, levels, seed, mask,
+                              episode, offsets, margin, clearance, max_step, flags, tries_out, stream)

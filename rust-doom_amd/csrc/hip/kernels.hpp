@@ -191,4 +191,22 @@ struct FloodArgs {
   float max_step, max_drop, clearance;
 };
 
+// Kernel 13: players reset at seeded random points of their level's floor (spawn.hip; include/rdoom.h "spawn" has the contract).  One
+// lane per player; the sector tables are SectorDevice's, the spawn tables SpawnDevice's (world_shared.hpp).
+struct SpawnArgs {
+  rdoom_player_state *states;
+  const float *offsets;     // n x n_objects x xyz, or null
+  const uint8_t *mask;      // n, or null: every player
+  const uint32_t *episode;  // n, or null: 0
+  uint32_t *tries_out;      // n, or null
+  const float4 *nodes, *edges, *sectors;
+  const uint4 *leaves;
+  const float *cumulative;
+  const float4 *corners;
+  uint32_t n, n_objects;
+  uint32_t key0, key1;  // the seed's low and high words
+  float margin, clearance, max_step;
+  uint32_t flags;
+};
+
 }  // namespace rdoom_dev

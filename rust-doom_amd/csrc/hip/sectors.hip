@@ -6,8 +6,8 @@
 // evaluating the header's expressions gets the same values (tests/sector_restatement.c does).  A node's constant term
 // d.x * o.y - d.y * o.x depends on the node alone and is computed once, at upload, by the same two products and one difference.
 //
-// The sector at a point is one definition, `child_of` (a step of the descent) + `sector_in_leaf` (the void and NaN rules), which
-// both kernels use.  locate_players: one lane per player, `descend` from the root.
+// The sector at a point is one definition, `child_of` (a step of the descent) + `sector_in_leaf` (the void and NaN rules) in
+// world_shared.hpp, which both kernels here and the spawn kernel (spawn.hip) use.  locate_players: one lane per player, `descend` from the root.
 // draw_sector_maps: one 256-thread workgroup per (player, 32 x 32 pixel tile), a wave per 8 rows of it, a thread four pixels of one
 // column.  The contract makes the result a function of the point alone, so a wave walks down from the root TOGETHER for as long
 // as every one of its 256 pixels takes the same child: the node index is then wave-uniform, its record one scalar load, and no
@@ -29,56 +29,18 @@
 
 namespace {
 
-using rdoom_dev::live_height;
+using rdoom_dev::child_of;
+using rdoom_dev::descend;
+using rdoom_dev::live_heights;
+using rdoom_dev::sector_in_leaf;
+using rdoom_dev::SectorLevel;
+using rdoom_dev::SectorTables;
 using rdoom_dev::with_level;
 
 constexpr uint32_t WAVE = 64, THREADS = 256;
 constexpr uint32_t TILE = 32;                       // pixels a side
 constexpr uint32_t PIXELS = TILE * TILE / THREADS;  // per thread: column lane % 32, rows 8 * wave + lane / 32 + 2 k
 constexpr uint32_t WAVE_ROWS = TILE / (THREADS / WAVE), ROW_STEP = WAVE / TILE;
-
-struct SectorTables {  // SectorDevice's arrays
-  const float4 *nodes;
-  const uint4 *leaves;
-  const float4 *edges;
-  const float4 *sectors;
-};
-struct SectorLevel {  // where a level's tables start, and its sectors
-  uint32_t node0, leaf0, sector0, n_sectors;
-};
-
-// the child of a node on q's side, as Child::pack writes it
-__device__ __forceinline__ int32_t child_of(float4 node, float qx, float qz) {
-  const float dist = (qx * node.y - qz * node.x) + node.z;
-  const uint32_t children = __float_as_uint(node.w);
-  return dist >= 0.0f ? (int32_t)(int16_t)(children & 0xFFFFu) : (int32_t)(int16_t)(children >> 16);
-}
-
-// the descent from the root of a level (`nodes`: the level's) to a leaf of it
-__device__ __forceinline__ uint32_t descend(const float4 *nodes, float qx, float qz) {
-  int32_t at = child_of(nodes[0], qx, qz);
-  while (at > 0) at = child_of(nodes[at], qx, qz);
-  return (uint32_t)-at;
-}
-
-// the sector of q in leaf `leaf` (an index into t.leaves): the leaf's, or none when q is void or not a number
-__device__ __forceinline__ uint32_t sector_in_leaf(const SectorTables &t, uint32_t leaf, float qx, float qz) {
-  const uint4 record = t.leaves[leaf];
-  bool inside = qx == qx && qz == qz;
-  for (uint32_t e = 0; e < record.z; e++) {
-    const float4 g = t.edges[record.y + e];
-    const float cross = (qx - g.x) * g.w - (qz - g.y) * g.z;
-    inside = inside && !(cross > 0.0f);
-  }
-  return inside ? record.x : RDOOM_SECTOR_NONE;
-}
-
-// player `off`'s live floor and ceiling of sector s of the level (+inf, -inf for none)
-__device__ __forceinline__ float2 live_heights(const SectorTables &t, const SectorLevel &lv, uint32_t s, const float *off, uint32_t n_objects) {
-  if (s == RDOOM_SECTOR_NONE) return make_float2(__builtin_inff(), -__builtin_inff());
-  const float4 r = t.sectors[lv.sector0 + s];
-  return make_float2(live_height(r.x, __float_as_uint(r.z), off, n_objects), live_height(r.y, __float_as_uint(r.w), off, n_objects));
-}
 
 struct LocateArgs {
   const rdoom_player_state *states;

@@ -921,6 +921,7 @@ struct rdoom_world {
   DevArrays d;
   rdoom::MapDevice map;  // the level's line table, as automap.hip lays it out
   rdoom::SectorDevice sectors;  // its sector table, as sectors.hip lays it out
+  rdoom::SpawnDevice spawn;     // its spawn table, as spawn.hip lays it out
 };
 
 struct rdoom_worldset {
@@ -934,17 +935,18 @@ struct rdoom_worldset {
   uint32_t *d_tri_starts = nullptr;  // each level's triangle base in the concatenation (the ray cast's)
   rdoom::MapDevice map;              // the levels' line tables, one after the other
   rdoom::SectorDevice sectors;       // and their sector tables
+  rdoom::SpawnDevice spawn;          // and their spawn tables
 };
 
 namespace rdoom {
 MapSource map_source(const rdoom_world *w) {
-  return MapSource{&w->map, &w->sectors, (uint32_t)w->host.map_sectors.size(), w->host.game_objects, (uint32_t)w->host.map_lines.size(),
+  return MapSource{&w->map, &w->sectors, &w->spawn, (uint32_t)w->host.map_sectors.size(), w->host.game_objects, (uint32_t)w->host.map_lines.size(),
                    w->on_device, w->device};
 }
 MapSource map_source(const rdoom_worldset *s) {
   size_t most = 0, most_sectors = 0;
   for (const rdoom::game::World &l : s->host.levels) most = std::max(most, l.map_lines.size()), most_sectors = std::max(most_sectors, l.map_sectors.size());
-  return MapSource{&s->map, &s->sectors, (uint32_t)most_sectors, s->host.game_objects, (uint32_t)most, s->on_device, s->device};
+  return MapSource{&s->map, &s->sectors, &s->spawn, (uint32_t)most_sectors, s->host.game_objects, (uint32_t)most, s->on_device, s->device};
 }
 }  // namespace rdoom
 
@@ -984,6 +986,10 @@ void fill_arrays(const rdoom::game::World &h, rdoom_world_arrays &a) {
 void fill_sectors(const rdoom::game::World &h, rdoom_map_sectors &m) {
   m = rdoom_map_sectors{h.map_sectors.data(), h.leaf_sector.data(), h.leaf_edges.data(), h.map_edges.data(), (uint32_t)h.map_sectors.size(),
                         (uint32_t)h.leaf_sector.size(), (uint32_t)h.map_edges.size()};
+}
+
+void fill_spawn(const rdoom::game::World &h, rdoom_spawn_table &t) {
+  t = rdoom_spawn_table{h.spawn.data(), (uint32_t)h.spawn.size(), {h.start_pos[0], h.start_pos[1], h.start_pos[2]}, h.start_yaw};
 }
 
 void fill_triggers(const rdoom::game::World &h, rdoom_world_trigger_arrays &t) {
@@ -1088,6 +1094,7 @@ void rdoom_world_destroy(rdoom_world *w) {
   free_world(w->d);
   rdoom::map_free(w->map);
   rdoom::sector_free(w->sectors);
+  rdoom::spawn_free(w->spawn);
   delete w;
 }
 
@@ -1109,6 +1116,7 @@ rdoom_status rdoom_world_create(const rdoom_wad *wad, uint32_t level_index, uint
     if (rdoom_status st = upload_world(h, w->d)) return st;
     if (rdoom_status st = rdoom::map_upload(h.map_lines, {make_uint2(0u, (uint32_t)h.map_lines.size())}, w->map)) return st;
     if (rdoom_status st = rdoom::sector_upload({&h}, w->sectors)) return st;
+    if (rdoom_status st = rdoom::spawn_upload({&h}, w->spawn)) return st;
     w->on_device = true;
   }
   *out_world = w.release();
@@ -1169,6 +1177,12 @@ rdoom_status rdoom_world_map_sectors(const rdoom_world *w, rdoom_map_sectors *ou
   return RDOOM_OK;
 }
 
+rdoom_status rdoom_world_spawn_table(const rdoom_world *w, rdoom_spawn_table *out) {
+  if (!w || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  fill_spawn(w->host, *out);
+  return RDOOM_OK;
+}
+
 rdoom_status rdoom_world_game_bytes(const rdoom_world *w, uint64_t *bytes_per_player) {
   if (!w || !bytes_per_player) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   *bytes_per_player = (uint64_t)game_view(w).words * sizeof(uint32_t);
@@ -1206,6 +1220,7 @@ void rdoom_worldset_destroy(rdoom_worldset *s) {
   free_world(s->d);
   rdoom::map_free(s->map);
   rdoom::sector_free(s->sectors);
+  rdoom::spawn_free(s->spawn);
   if (s->d_table) (void)hipFree(s->d_table);
   if (s->d_tri_starts) (void)hipFree(s->d_tri_starts);
   delete s;
@@ -1251,6 +1266,7 @@ rdoom_status rdoom_worldset_create(const rdoom_wad *wad, const uint32_t *level_i
     std::vector<const rdoom::game::World *> each;
     for (const rdoom::game::World &l : h.levels) each.push_back(&l);
     if (rdoom_status st = rdoom::sector_upload(each, s->sectors)) return st;
+    if (rdoom_status st = rdoom::spawn_upload(each, s->spawn)) return st;
     s->on_device = true;
   }
   *out_set = s.release();
@@ -1293,6 +1309,13 @@ rdoom_status rdoom_worldset_level_map_sectors(const rdoom_worldset *s, uint32_t 
   if (!s || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   if (slot >= s->host.levels.size()) return rdoom::fail(RDOOM_BAD_ARG, "slot %u of a set of %zu levels", slot, s->host.levels.size());
   fill_sectors(s->host.levels[slot], *out);
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_worldset_level_spawn_table(const rdoom_worldset *s, uint32_t slot, rdoom_spawn_table *out) {
+  if (!s || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (slot >= s->host.levels.size()) return rdoom::fail(RDOOM_BAD_ARG, "slot %u of a set of %zu levels", slot, s->host.levels.size());
+  fill_spawn(s->host.levels[slot], *out);
   return RDOOM_OK;
 }
 

@@ -1,4 +1,4 @@
-// What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip) and the sectors' (sectors.hip) share: the pick of a lane's level,
+// What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip), the sectors' (sectors.hip) and the spawn's (spawn.hip) share: the pick of a lane's level,
 // the checked launch, the device check of a handle, the map's side of a world handle, and what both map units read of a line.
 // One definition each, for player_quat.hpp's reason.
 #pragma once
@@ -76,6 +76,52 @@ __device__ __forceinline__ float live_height(float height, uint32_t object, cons
   return height + ((off && object != 0 && object < n_objects) ? off[(size_t)object * 3 + 1] : 0.0f);
 }
 
+// ---- the sector at a point (include/rdoom.h "sectors"), the one definition the sector kernels (sectors.hip) and the spawn kernel
+// (spawn.hip) share: `child_of` (a step of the descent) + `sector_in_leaf` (the void and NaN rules), in the contract's binary32
+// operations; the units that use them turn contraction off ----
+struct SectorTables {  // SectorDevice's arrays
+  const float4 *nodes;
+  const uint4 *leaves;
+  const float4 *edges;
+  const float4 *sectors;
+};
+struct SectorLevel {  // where a level's tables start, and its sectors
+  uint32_t node0, leaf0, sector0, n_sectors;
+};
+
+// the child of a node on q's side, as Child::pack writes it
+__device__ __forceinline__ int32_t child_of(float4 node, float qx, float qz) {
+  const float dist = (qx * node.y - qz * node.x) + node.z;
+  const uint32_t children = __float_as_uint(node.w);
+  return dist >= 0.0f ? (int32_t)(int16_t)(children & 0xFFFFu) : (int32_t)(int16_t)(children >> 16);
+}
+
+// the descent from the root of a level (`nodes`: the level's) to a leaf of it
+__device__ __forceinline__ uint32_t descend(const float4 *nodes, float qx, float qz) {
+  int32_t at = child_of(nodes[0], qx, qz);
+  while (at > 0) at = child_of(nodes[at], qx, qz);
+  return (uint32_t)-at;
+}
+
+// the sector of q in leaf `leaf` (an index into t.leaves): the leaf's, or none when q is void or not a number
+__device__ __forceinline__ uint32_t sector_in_leaf(const SectorTables &t, uint32_t leaf, float qx, float qz) {
+  const uint4 record = t.leaves[leaf];
+  bool inside = qx == qx && qz == qz;
+  for (uint32_t e = 0; e < record.z; e++) {
+    const float4 g = t.edges[record.y + e];
+    const float cross = (qx - g.x) * g.w - (qz - g.y) * g.z;
+    inside = inside && !(cross > 0.0f);
+  }
+  return inside ? record.x : RDOOM_SECTOR_NONE;
+}
+
+// player `off`'s live floor and ceiling of sector s of the level (+inf, -inf for none)
+__device__ __forceinline__ float2 live_heights(const SectorTables &t, const SectorLevel &lv, uint32_t s, const float *off, uint32_t n_objects) {
+  if (s == RDOOM_SECTOR_NONE) return make_float2(__builtin_inff(), -__builtin_inff());
+  const float4 r = t.sectors[lv.sector0 + s];
+  return make_float2(live_height(r.x, __float_as_uint(r.z), off, n_objects), live_height(r.y, __float_as_uint(r.w), off, n_objects));
+}
+
 }  // namespace rdoom_dev
 
 namespace rdoom::game {
@@ -132,10 +178,26 @@ struct SectorDevice {
 rdoom_status sector_upload(const std::vector<const game::World *> &levels, SectorDevice &out);
 void sector_free(SectorDevice &d);
 
-// what automap.hip, reveal.hip and sectors.hip need of a world or world-set handle (world.hip owns the handles)
+// The device copy of a spawn table (rdoom_spawn_table), private to spawn.hip: a world's, or a world set's levels one after the
+// other.
+struct SpawnDevice {
+  float *cumulative = nullptr;  // an entry's cumulative area
+  float4 *corners = nullptr;    // three per entry: a, b, c as xyz
+  uint4 *levels = nullptr;      // a slot's first entry, its entries, the bound of the search ceil(log2(entries)) + 1, 0
+  float4 *starts = nullptr;     // a slot's start position and yaw
+  uint32_t n_levels = 0;
+  uint4 level0 = {};            // slot 0's two records on the host: a single world's launch passes them by value
+  float4 start0 = {};
+};
+// spawn.hip: the tables of `levels` on the current device; releases what it allocated
+rdoom_status spawn_upload(const std::vector<const game::World *> &levels, SpawnDevice &out);
+void spawn_free(SpawnDevice &d);
+
+// what automap.hip, reveal.hip, sectors.hip and spawn.hip need of a world or world-set handle (world.hip owns the handles)
 struct MapSource {
   const MapDevice *map;
   const SectorDevice *sectors;
+  const SpawnDevice *spawn;
   uint32_t max_sectors;   // the sectors of its table; a set's: of its largest level's (known on host-only handles too)
   uint32_t game_objects;  // the n_objects its game calls need at least
   uint32_t max_lines;     // the lines of its table; a set's: of its largest level's (known on host-only handles too)

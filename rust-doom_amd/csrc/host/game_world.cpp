@@ -202,6 +202,23 @@ World build_world(const LoadedWad &w, size_t level_index) {
     }
     out.leaf_edges[k].count = (uint32_t)out.map_edges.size() - out.leaf_edges[k].first;
   }
+  out.spawn = build_spawn_table(out);
+  return out;
+}
+
+std::vector<rdoom_spawn_entry> build_spawn_table(const World &w) {
+  std::vector<rdoom_spawn_entry> out;
+  double sum = 0.0;
+  for (const WorldTriangle &t : w.triangles) {
+    if (!(w.verts[(size_t)t.normal * 3 + 1] > 0.0f)) continue;  // floors only: walls have y == 0, ceilings y < 0
+    const float *a = &w.verts[(size_t)t.v1 * 3], *b = &w.verts[(size_t)t.v2 * 3], *c = &w.verts[(size_t)t.v3 * 3];
+    const double ux = (double)b[0] - (double)a[0], uz = (double)b[2] - (double)a[2];
+    const double vx = (double)c[0] - (double)a[0], vz = (double)c[2] - (double)a[2];
+    const double area = 0.5 * std::fabs(ux * vz - uz * vx);
+    if (!(area > 0.0)) continue;
+    sum += area;
+    out.push_back(rdoom_spawn_entry{{a[0], a[1], a[2]}, {b[0], b[1], b[2]}, {c[0], c[1], c[2]}, (float)sum});
+  }
   return out;
 }
 

@@ -46,6 +46,8 @@ struct World {
   std::vector<uint32_t> leaf_sector;
   std::vector<rdoom_map_leaf_edges> leaf_edges;
   std::vector<rdoom_map_edge> map_edges;
+  // the level's spawn table (include/rdoom.h "spawn"): an entry per floor triangle with an area, in the order of `triangles`
+  std::vector<rdoom_spawn_entry> spawn;
   float start_pos[3] = {0, 0, 0};  // the player's start, as the renderer's Builder takes it (rdoom_built_start)
   float start_yaw = 0.0f;
 };
@@ -76,6 +78,8 @@ WorldSet build_world_set(const LoadedWad &w, const uint32_t *level_indices, size
 
 // WorldBuilder::new + LevelWalker::walk + WorldBuilder::build.  Throws WadError(RDOOM_BAD_LEVEL) on a level without a BSP.
 World build_world(const LoadedWad &w, size_t level_index);
+// the spawn table of the collision arrays (include/rdoom.h "spawn"): a pure function of triangles and verts
+std::vector<rdoom_spawn_entry> build_spawn_table(const World &w);
 // the archive behind a C handle (csrc/host/wad_api.cpp)
 const LoadedWad *loaded_wad(const rdoom_wad *wad);
 
