@@ -1163,6 +1163,90 @@ rdoom_status rdoom_worldset_spawn_players(const rdoom_worldset *set, rdoom_playe
                                           uint64_t seed, const uint32_t *d_episode, const rdoom_spawn_params *params,
                                           uint32_t *d_tries_out, void *stream);
 
+/* ---- explored area: a fog-of-war occupancy grid per player, kept on the device -------------------------------
+ * A persistent, world-anchored grid per player: a cell is FREE once the player has had it in sight, WALL where sight ended on
+ * something solid, unknown otherwise.  Sight is the seen-lines contract's 2-D fan, sampled at fixed steps; the grid is anchored to
+ * the level, not to the player, so it accumulates as the player moves.  The reference project has no counterpart of this: nothing
+ * here restates it.  Every float below is binary32, every operation is rounded once and none is contracted; divisions are IEEE;
+ * a + b * c means round(a + round(b * c)).
+ * The grid of a level at cell size `cell`, a finite binary32 > 0.  minx, maxx, minz, maxz: the exact minimum and maximum of a[0],
+ * b[0] (x) and of a[1], b[1] (z) over the level's rdoom_map_line records; all four are 0 for a level without lines.
+ *   cx(x) = (int32) floorf(x / cell);   ix0 = cx(minx) - 1;   gw = cx(maxx) + 1 - ix0 + 1;
+ *   iz0 = cx(minz) - 1;   gh = cx(maxz) + 1 - iz0 + 1;   pitch = (gw + 31) / 32;   words = gh * pitch
+ * -- the cells the lines touch and one cell of margin on each side; pitch is the 32-bit words of a grid row, words those of a plane.
+ * Point (x, z) lies in cell (ix, iz) = (cx(x) - ix0, cx(z) - iz0) when x / cell and z / cell are finite and below 2^30 in magnitude
+ * and 0 <= ix < gw, 0 <= iz < gh; otherwise, and whenever x or z is a NaN, it lies in no cell.  Cell (ix, iz) is bit ix % 32 of word
+ * iz * pitch + ix / 32 of a plane.
+ * Limits (RDOOM_BAD_ARG, "a grid over its limits"): a bound whose quotient by cell is not finite and below 2^30 in magnitude; gw or
+ * gh above 8192; words above 2^20.
+ * rdoom_world_area_grid / rdoom_worldset_level_area_grid: the grid of the world's level / of slot `slot`, by these formulas.
+ * rdoom_world_area_words / rdoom_worldset_area_words: `words` of the world's level / the largest `words` among the set's levels (every
+ * level must be within the limits).  All four work on RDOOM_WORLD_HOST_ONLY handles.
+ *
+ * rdoom_world_reveal_area / rdoom_worldset_reveal_area.  d_states, d_levels, d_dirs / n_rays, max_range, d_object_offsets / n_objects:
+ * exactly as rdoom_world_reveal_lines takes them.  n_steps: 1 .. 4096.  d_area: n rows of 2 planes of `stride` uint32 words; plane
+ * 0 (words p * 2 * stride ..) is FREE, plane 1 (words (p * 2 + 1) * stride ..) is WALL, each laid out as above for the grid of the
+ * player's level; stride >= the handle's area words at this cell.
+ * For player p and ray r, vel and T_r are the seen-lines contract's ("Fan", "Ray against line", "Blocking", "Seen" above): the same
+ * expressions giving the same bits.  o = (pos.x, pos.z).
+ *   For k = 0 .. n_steps:  t = (float)k / (float)n_steps;  when t <= T_r, the point (o.x + t * vel.x, o.z + t * vel.z) sets the FREE
+ *   bit of its cell.
+ *   When T_r < 1, the point (o.x + T_r * vel.x, o.z + T_r * vel.z) sets the WALL bit of its cell.
+ * A point in no cell sets nothing.  Bits are only ever set, never cleared; words of a plane beyond the level's `words` and bits of a
+ * grid row beyond gw are never written; the caller zeroes a row to start an episode.  A cell may carry both bits (sight ended in a
+ * cell that another ray crossed): consumers read `wall`, and `free & ~wall`.
+ * d_new_out (n x 2 uint32, may be NULL): d_new_out[2 p] = the FREE bits this call set in row p that were clear before,
+ * d_new_out[2 p + 1] = the WALL bits likewise -- the growth of the explored area in cells.
+ * The result is an OR of a set of bits that the expressions above fix, followed by a population count of the difference: the order in
+ * which rays, steps and cells are visited, which lines are culled before the minimum, and how the work is cut into chunks, windows or
+ * bands are an implementation's free choices and cannot change a bit.
+ * A comparison with a NaN is false and a NaN lies in no cell: a player at a NaN position, or with a NaN yaw, marks nothing and counts
+ * 0.  A level slot >= the set's size is seen on the device only: that player's row is untouched and its counts are 0.
+ * One launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so the call can be
+ * captured into a graph.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): those of rdoom_world_reveal_lines for the
+ * arguments shared with it (a NULL handle, or (n > 0) NULL d_states / d_area / d_dirs / d_levels; n_rays == 0; max_range not finite or
+ * not > 0; d_object_offsets with n_objects smaller than the game's objects; a handle created with RDOOM_WORLD_HOST_ONLY or living
+ * on another device); a cell that is not finite or not > 0; n_steps 0 or above 4096; a grid over its limits; a stride smaller than
+ * the handle's area words.  n == 0 queues nothing.
+ *
+ * rdoom_world_draw_area_maps / rdoom_worldset_draw_area_maps: every player's grid as an egocentric map.  view: width, height and scale
+ * are read, RDOOM_MAP_ROTATE and RDOOM_MAP_TOP_DOWN honoured, any other flag is an error; half_width and marker are not read.  The
+ * pixel's point q is the map contract's ("Pixel to world" above), operation for operation, so an area map registers pixel for pixel
+ * with rdoom_world_draw_maps and rdoom_world_draw_sector_maps of the same view.  d_out (n x height x width bytes): the byte of a
+ * pixel is free_bit | wall_bit << 1 of q's cell in row p of d_area (rows as above) -- RDOOM_AREA_UNKNOWN, RDOOM_AREA_FREE,
+ * RDOOM_AREA_WALL, or 3 for a cell that carries both -- and 0 where q lies in no cell.  A level slot >= the set's size is seen on the
+ * device only: that player's map is all 0.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): those of
+ * rdoom_world_draw_sector_maps that concern what is read here (handle, view, d_states, d_levels, width, height, scale, flags,
+ * host-only, the device); (n > 0) NULL d_area or d_out; n x ceil(width * height / 256) above 2^31 - 1; a bad cell, a grid over its
+ * limits or a stride that is too small, as above.  n == 0 queues nothing. */
+#define RDOOM_AREA_UNKNOWN 0u
+#define RDOOM_AREA_FREE 1u
+#define RDOOM_AREA_WALL 2u
+#define RDOOM_AREA_MAX_SIDE 8192u
+#define RDOOM_AREA_MAX_WORDS 1048576u
+#define RDOOM_AREA_MAX_STEPS 4096u
+typedef struct rdoom_area_grid {
+  int32_t ix0, iz0;
+  uint32_t gw, gh, pitch, words;
+} rdoom_area_grid;
+rdoom_status rdoom_world_area_grid(const rdoom_world *world, float cell, rdoom_area_grid *out);
+rdoom_status rdoom_worldset_level_area_grid(const rdoom_worldset *set, uint32_t slot, float cell, rdoom_area_grid *out);
+rdoom_status rdoom_world_area_words(const rdoom_world *world, float cell, uint32_t *words_out);
+rdoom_status rdoom_worldset_area_words(const rdoom_worldset *set, float cell, uint32_t *words_out);
+rdoom_status rdoom_world_reveal_area(const rdoom_world *world, const rdoom_player_state *d_states, uint32_t n, const float *d_dirs,
+                                     uint32_t n_rays, float max_range, const float *d_object_offsets, uint32_t n_objects, float cell,
+                                     uint32_t n_steps, uint32_t *d_area, uint32_t stride, uint32_t *d_new_out, void *stream);
+rdoom_status rdoom_worldset_reveal_area(const rdoom_worldset *set, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                        uint32_t n, const float *d_dirs, uint32_t n_rays, float max_range,
+                                        const float *d_object_offsets, uint32_t n_objects, float cell, uint32_t n_steps,
+                                        uint32_t *d_area, uint32_t stride, uint32_t *d_new_out, void *stream);
+rdoom_status rdoom_world_draw_area_maps(const rdoom_world *world, const rdoom_player_state *d_states, uint32_t n,
+                                        const rdoom_map_view *view, const uint32_t *d_area, uint32_t stride, float cell,
+                                        uint8_t *d_out, void *stream);
+rdoom_status rdoom_worldset_draw_area_maps(const rdoom_worldset *set, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                           uint32_t n, const rdoom_map_view *view, const uint32_t *d_area, uint32_t stride,
+                                           float cell, uint8_t *d_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,6 +12,7 @@ the `rust_doom_amd` shim at the repository root.)
 """
 import collections
 import ctypes
+import math
 import os
 
 import numpy as np
@@ -82,6 +83,10 @@ SPAWN_TRIES = 8  # RDOOM_SPAWN_TRIES: the candidates spawn_players draws for a p
 SPAWN_RISE = 0.5  # RDOOM_SPAWN_RISE: a spawned player's height above the live floor, the start's above the floor at the start marker
 SPAWN_ENTRY = np.dtype([('a', '<f4', 3), ('b', '<f4', 3), ('c', '<f4', 3), ('cumulative', '<f4')])  # rdoom_spawn_entry
 LINE_MAPPED = 0x100  # RDOOM_LINE_MAPPED, Doom's "already on the map": drawn through a seen set whether seen or not
+AREA_UNKNOWN, AREA_FREE, AREA_WALL = 0, 1, 2  # RDOOM_AREA_*: draw_area_maps' bytes (3: a cell that carries both bits)
+AREA_MAX_STEPS = 4096  # RDOOM_AREA_MAX_STEPS
+# (3, 3) uint8, unknown / free / wall: torch.from_numpy(AREA_COLORS).cuda()[maps.clamp(max=2).long()] is an RGB map (both bits: wall)
+AREA_COLORS = np.array([(0, 0, 0), (72, 72, 88), (252, 0, 0)], np.uint8)
 
 
 def _map_colors():
@@ -171,7 +176,9 @@ API_SYMBOLS = [
     'rdoom_world_map_sectors', 'rdoom_worldset_level_map_sectors', 'rdoom_world_locate_players', 'rdoom_worldset_locate_players',
     'rdoom_world_draw_sector_maps', 'rdoom_worldset_draw_sector_maps', 'rdoom_batch_resolve_observation',
     'rdoom_batch_read_observation', 'rdoom_flood_max_cells', 'rdoom_flood_maps',
-    'rdoom_world_spawn_table', 'rdoom_worldset_level_spawn_table', 'rdoom_world_spawn_players', 'rdoom_worldset_spawn_players']
+    'rdoom_world_spawn_table', 'rdoom_worldset_level_spawn_table', 'rdoom_world_spawn_players', 'rdoom_worldset_spawn_players',
+    'rdoom_world_area_grid', 'rdoom_worldset_level_area_grid', 'rdoom_world_area_words', 'rdoom_worldset_area_words',
+    'rdoom_world_reveal_area', 'rdoom_worldset_reveal_area', 'rdoom_world_draw_area_maps', 'rdoom_worldset_draw_area_maps']
 
 _lib = None
 
@@ -1360,6 +1367,103 @@ def _reveal_lines(call, words, states, levels, fan, max_range, offsets, seen, ne
     return seen
 
 
+class AreaGridStruct(ctypes.Structure):
+    _fields_ = [('ix0', ctypes.c_int32), ('iz0', ctypes.c_int32), ('gw', ctypes.c_uint32), ('gh', ctypes.c_uint32),
+                ('pitch', ctypes.c_uint32), ('words', ctypes.c_uint32)]
+
+
+class AreaGrid(collections.namedtuple('AreaGrid', 'ix0 iz0 gw gh pitch words')):
+    """rdoom_area_grid: the explored-area grid of a level at one cell size.  Cell (ix, iz) covers world x in [(ix0 + ix) * cell,
+    (ix0 + ix + 1) * cell) and z alike; it is bit ix % 32 of word iz * pitch + ix // 32 of a plane of `words` words"""
+
+
+def _area_grid(get):
+    """World.area_grid / WorldSet.area_grid: get(&rdoom_area_grid) as an AreaGrid"""
+    g = AreaGridStruct()
+    _check(get(ctypes.byref(g)))
+    return AreaGrid(g.ix0, g.iz0, g.gw, g.gh, g.pitch, g.words)
+
+
+def _area_words(get):
+    words = ctypes.c_uint32(0)
+    _check(get(ctypes.byref(words)))
+    return words.value
+
+
+def area_steps(max_range, cell):
+    """the n_steps of reveal_area that puts samples half a cell apart along a ray of unit direction: ceil(2 * max_range / cell)"""
+    if not (max_range > 0 and cell > 0):
+        raise ValueError('max_range and cell must be positive')
+    return max(1, int(math.ceil(2.0 * float(max_range) / float(cell))))
+
+
+def unpack_area(rows, grid):
+    """one player's rows of reveal_area's bits (a numpy array or tensor, (2, stride) 32-bit words with stride >= grid.words) as a
+    (2, gh, gw) bool array: [0, iz, ix] = cell (ix, iz) is free, [1, iz, ix] = it is a wall"""
+    if not isinstance(rows, np.ndarray):
+        rows = rows.cpu().numpy()
+    words = np.ascontiguousarray(rows).view(np.uint32)
+    if words.ndim != 2 or words.shape[0] != 2 or words.shape[1] < grid.words:
+        raise ValueError('rows must be (2, stride) words with stride >= %d, got %s' % (grid.words, tuple(words.shape)))
+    planes = words[:, :grid.words].reshape(2, grid.gh, grid.pitch)
+    ix = np.arange(grid.gw)
+    return ((planes[:, :, ix >> 5] >> (ix & 31).astype(np.uint32)) & 1).astype(bool)
+
+
+def _area_rows(area, n, words):
+    """(pointer, stride in words) of a caller's area rows: a contiguous 32-bit (n, 2, stride) GPU tensor with stride >= words"""
+    import torch
+    if not isinstance(area, torch.Tensor) or area.device.type != 'cuda' or not area.is_contiguous() or area.dim() != 3 or \
+            area.element_size() != 4 or area.dtype.is_floating_point or area.shape[0] != n or area.shape[1] != 2 or area.shape[2] < words:
+        raise ValueError('area must be a contiguous 32-bit integer (n, 2, words) tensor on the GPU for %d players with words >= %d' % (n, words))
+    return area.data_ptr(), int(area.shape[2])
+
+
+def _reveal_area(call, words, states, levels, fan, max_range, cell, n_steps, offsets, area, new_out, stream):
+    """World.reveal_area / WorldSet.reveal_area: the checks and the launch; call(states, levels, n, dirs, n_rays, max_range,
+    offsets, n_objects, cell, n_steps, area, stride, new_out, stream) is the C entry point with its handle bound"""
+    import torch
+    if not isinstance(fan, torch.Tensor) or fan.device.type != 'cuda' or not fan.is_contiguous():
+        raise ValueError('fan must be a contiguous tensor on the GPU')
+    n, n_obj = _player_tensors(states, levels, offsets)
+    if fan.dtype != torch.float32 or fan.dim() != 2 or fan.shape[1] != 2 or fan.shape[0] == 0:
+        raise ValueError('fan must be a float32 (n_rays, 2) tensor with n_rays >= 1, got %s %s' % (fan.dtype, tuple(fan.shape)))
+    if n_steps is None:
+        n_steps = area_steps(max_range, cell)
+    if area is None:
+        area = torch.zeros((n, 2, words), dtype=torch.int32, device=states.device)
+    pa, stride = _area_rows(area, n, words)
+    if new_out is not None and (new_out.element_size() != 4 or new_out.dtype.is_floating_point):
+        raise ValueError('new_out must hold 32-bit integers')
+    pn = _out_tensor(new_out, n * 8, 'new_out')
+    v = ctypes.c_void_p
+    _check(call(v(states.data_ptr()), v(levels.data_ptr()) if levels is not None else None, n, v(fan.data_ptr()), int(fan.shape[0]),
+                ctypes.c_float(max_range), v(offsets.data_ptr()) if offsets is not None else None, n_obj, ctypes.c_float(cell), int(n_steps),
+                v(pa), stride, v(pn), v(_stream_handle(stream))))
+    return area
+
+
+def _draw_area_maps(call, words, states, levels, width, height, scale, area, cell, rotate, top_down, out, stream):
+    """World.draw_area_maps / WorldSet.draw_area_maps: the checks and the launch; call(states, levels, n, view, area, stride, cell,
+    out, stream) is the C entry point with its handle bound"""
+    import torch
+    n, _ = _player_tensors(states, levels, None)
+    width, height = int(width), int(height)
+    if width < 1 or height < 1:
+        raise ValueError('a map needs at least 1 x 1 pixels, got %d x %d' % (width, height))
+    pa, stride = _area_rows(area, n, words)
+    if out is None:
+        out = torch.empty((n, height, width), dtype=torch.uint8, device=states.device)
+    elif out.dtype != torch.uint8:
+        raise ValueError('out must be uint8')
+    po = _out_tensor(out, n * height * width, 'out')
+    view = MapView(width, height, scale, 0.0, 0.0, (MAP_ROTATE if rotate else 0) | (MAP_TOP_DOWN if top_down else 0))
+    v = ctypes.c_void_p
+    _check(call(v(states.data_ptr()), v(levels.data_ptr()) if levels is not None else None, n, ctypes.byref(view), v(pa), stride,
+                ctypes.c_float(cell), v(po), v(_stream_handle(stream))))
+    return out
+
+
 class MapSectorArrays(ctypes.Structure):
     _fields_ = [('sectors', ctypes.c_void_p), ('leaf_sector', ctypes.c_void_p), ('leaf_edges', ctypes.c_void_p), ('edges', ctypes.c_void_p),
                 ('n_sectors', ctypes.c_uint32), ('n_leaves', ctypes.c_uint32), ('n_edges', ctypes.c_uint32)]
@@ -1790,6 +1894,37 @@ class World:
         return _spawn_players(lambda st, lv, *rest: L.rdoom_world_spawn_players(self._h, st, *rest), states, None, seed, mask, episode,
                               offsets, margin, clearance, max_step, flags, tries_out, stream)
 
+    # ---- explored area -----------------------------------------------------------------------------------------------------
+    def area_grid(self, cell):
+        """rdoom_world_area_grid: the AreaGrid of the level at cell size `cell` (world units): the cells its lines touch and one of
+        margin on each side"""
+        return _area_grid(lambda g: lib().rdoom_world_area_grid(self._h, ctypes.c_float(cell), g))
+
+    def area_words(self, cell):
+        """the 32-bit words a plane of the explored-area grid takes at that cell size: area_grid(cell).words"""
+        return _area_words(lambda w: lib().rdoom_world_area_words(self._h, ctypes.c_float(cell), w))
+
+    def reveal_area(self, states, fan, max_range, cell, n_steps=None, offsets=None, area=None, new_out=None, stream=None):
+        """rdoom_world_reveal_area: every player's explored area, a world-anchored grid of `cell`-sized cells: reveal_lines' fan
+        (fan, max_range, offsets: as there) sampled at n_steps + 1 points per ray (None: area_steps(max_range, cell), half a cell
+        apart); a cell a ray crossed before it was stopped is FREE, the cell where a blocking line stopped it is WALL.  area: an
+        int32 (n, 2, words >= area_words(cell)) GPU tensor whose bits are OR-ed into, [:, 0] the FREE plane and [:, 1] the WALL plane
+        (unpack_area unpacks a player's); None allocates a zeroed one.  Returns area.  new_out: an optional 32-bit integer (n, 2)
+        tensor that receives how many FREE and WALL bits of each row this call set -- the coverage reward.  Asynchronous on
+        `stream`."""
+        L = lib()
+        return _reveal_area(lambda st, lv, *rest: L.rdoom_world_reveal_area(self._h, st, *rest), self.area_words(cell), states, None, fan,
+                            max_range, cell, n_steps, offsets, area, new_out, stream)
+
+    def draw_area_maps(self, states, width, height, scale, area, cell, rotate=False, top_down=False, out=None, stream=None):
+        """rdoom_world_draw_area_maps: every player's explored area on draw_maps' grid (same width, height, scale, rotate,
+        top_down: the two register pixel for pixel), a uint8 (n, height, width) GPU tensor of AREA_FREE | AREA_WALL bits, AREA_UNKNOWN
+        where nothing was seen and outside the grid.  area, cell: reveal_area's.  out: an optional preallocated tensor.
+        Asynchronous on `stream`."""
+        L = lib()
+        return _draw_area_maps(lambda st, lv, *rest: L.rdoom_world_draw_area_maps(self._h, st, *rest), self.area_words(cell), states, None,
+                               width, height, scale, area, cell, rotate, top_down, out, stream)
+
 
 class WorldSetLevelInfo(ctypes.Structure):
     _fields_ = [('archive_index', ctypes.c_uint32), ('destination', ctypes.c_uint32), ('start_pos', ctypes.c_float * 3),
@@ -1977,3 +2112,27 @@ class WorldSet:
         L = lib()
         return _spawn_players(lambda st, lv, *rest: L.rdoom_worldset_spawn_players(self._h, st, lv, *rest), states, levels, seed, mask,
                               episode, offsets, margin, clearance, max_step, flags, tries_out, stream)
+
+    # ---- explored area -----------------------------------------------------------------------------------------------------
+    def area_grid(self, slot, cell):
+        """rdoom_worldset_level_area_grid: the AreaGrid of slot `slot`, equal to the single world's of that level"""
+        return _area_grid(lambda g: lib().rdoom_worldset_level_area_grid(self._h, int(slot), ctypes.c_float(cell), g))
+
+    def area_words(self, cell):
+        """the 32-bit words a plane of the explored-area grid takes in this set: its largest level's World.area_words(cell)"""
+        return _area_words(lambda w: lib().rdoom_worldset_area_words(self._h, ctypes.c_float(cell), w))
+
+    def reveal_area(self, states, levels, fan, max_range, cell, n_steps=None, offsets=None, area=None, new_out=None, stream=None):
+        """rdoom_worldset_reveal_area: World.reveal_area for players spread over the set's levels (levels: game_state's tensor of
+        slots); a row's planes are laid out for the grid of the player's own level (area_grid(slot, cell)), rows of area_words(cell)
+        words.  A slot outside the set leaves its row untouched and counts 0."""
+        L = lib()
+        return _reveal_area(lambda st, lv, *rest: L.rdoom_worldset_reveal_area(self._h, st, lv, *rest), self.area_words(cell), states, levels,
+                            fan, max_range, cell, n_steps, offsets, area, new_out, stream)
+
+    def draw_area_maps(self, states, levels, width, height, scale, area, cell, rotate=False, top_down=False, out=None, stream=None):
+        """rdoom_worldset_draw_area_maps: World.draw_area_maps for players spread over the set's levels; a slot outside the set
+        gets an all-zero map"""
+        L = lib()
+        return _draw_area_maps(lambda st, lv, *rest: L.rdoom_worldset_draw_area_maps(self._h, st, lv, *rest), self.area_words(cell), states,
+                               levels, width, height, scale, area, cell, rotate, top_down, out, stream)

@@ -245,13 +245,16 @@ rdoom_status map_upload(const std::vector<rdoom_map_line> &lines, const std::vec
   if (rdoom_status s = upload(&out.heights, heights)) return s;
   if (rdoom_status s = upload(&out.ids, ids)) return s;
   if (rdoom_status s = upload(&out.flags, flags)) return s;
+  std::vector<float4> bounds;
+  for (const uint2 &r : levels) bounds.push_back(line_bounds(lines.data() + r.x, r.y));
   if (rdoom_status s = upload(&out.levels, levels)) return s;
+  if (rdoom_status s = upload(&out.bounds, bounds)) return s;
   out.n_lines = (uint32_t)lines.size(), out.n_levels = (uint32_t)levels.size();
   return RDOOM_OK;
 }
 
 void map_free(MapDevice &d) {
-  for (void *p : {(void *)d.seg, (void *)d.heights, (void *)d.ids, (void *)d.flags, (void *)d.levels})
+  for (void *p : {(void *)d.seg, (void *)d.heights, (void *)d.ids, (void *)d.flags, (void *)d.levels, (void *)d.bounds})
     if (p) (void)hipFree(p);
   d = MapDevice{};
 }

@@ -922,6 +922,7 @@ struct rdoom_world {
   rdoom::MapDevice map;  // the level's line table, as automap.hip lays it out
   rdoom::SectorDevice sectors;  // its sector table, as sectors.hip lays it out
   rdoom::SpawnDevice spawn;     // its spawn table, as spawn.hip lays it out
+  float4 bounds = {};           // line_bounds of its line table (area.hip's grid)
 };
 
 struct rdoom_worldset {
@@ -936,17 +937,19 @@ struct rdoom_worldset {
   rdoom::MapDevice map;              // the levels' line tables, one after the other
   rdoom::SectorDevice sectors;       // and their sector tables
   rdoom::SpawnDevice spawn;          // and their spawn tables
+  std::vector<float4> bounds;        // line_bounds of each level's line table (area.hip's grids)
 };
 
 namespace rdoom {
 MapSource map_source(const rdoom_world *w) {
   return MapSource{&w->map, &w->sectors, &w->spawn, (uint32_t)w->host.map_sectors.size(), w->host.game_objects, (uint32_t)w->host.map_lines.size(),
-                   w->on_device, w->device};
+                   &w->bounds, 1u, w->on_device, w->device};
 }
 MapSource map_source(const rdoom_worldset *s) {
   size_t most = 0, most_sectors = 0;
   for (const rdoom::game::World &l : s->host.levels) most = std::max(most, l.map_lines.size()), most_sectors = std::max(most_sectors, l.map_sectors.size());
-  return MapSource{&s->map, &s->sectors, &s->spawn, (uint32_t)most_sectors, s->host.game_objects, (uint32_t)most, s->on_device, s->device};
+  return MapSource{&s->map, &s->sectors, &s->spawn, (uint32_t)most_sectors, s->host.game_objects, (uint32_t)most, s->bounds.data(),
+                   (uint32_t)s->bounds.size(), s->on_device, s->device};
 }
 }  // namespace rdoom
 
@@ -1109,6 +1112,7 @@ rdoom_status rdoom_world_create(const rdoom_wad *wad, uint32_t level_index, uint
       }))
     return st;
   const rdoom::game::World &h = w->host;
+  w->bounds = rdoom::line_bounds(h.map_lines.data(), h.map_lines.size());
   if (h.node_depth > RDOOM_WORLD_MAX_DEPTH)
     return rdoom::fail(RDOOM_BAD_LEVEL, "the level's BSP is %u nodes deep (at most %u)", h.node_depth, RDOOM_WORLD_MAX_DEPTH);
   if (!(flags & RDOOM_WORLD_HOST_ONLY)) {
@@ -1252,6 +1256,7 @@ rdoom_status rdoom_worldset_create(const rdoom_wad *wad, const uint32_t *level_i
     r.start_yaw = l.start_yaw;
     s->table.push_back(r);
     s->words = std::max(s->words, g.words);
+    s->bounds.push_back(rdoom::line_bounds(l.map_lines.data(), l.map_lines.size()));
   }
   if (!(flags & RDOOM_WORLD_HOST_ONLY)) {
     HIP_TRY(hipGetDevice(&s->device));

@@ -1,4 +1,4 @@
-// What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip), the sectors' (sectors.hip) and the spawn's (spawn.hip) share: the pick of a lane's level,
+// What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip), the explored area's (area.hip), the sectors' (sectors.hip) and the spawn's (spawn.hip) share: the pick of a lane's level,
 // the checked launch, the device check of a handle, the map's side of a world handle, and what both map units read of a line.
 // One definition each, for player_quat.hpp's reason.
 #pragma once
@@ -156,8 +156,20 @@ struct MapDevice {
   uint4 *ids = nullptr;       // the objects of those four
   uint32_t *flags = nullptr;  // the linedef's flags; bit 16: the front side is present, bit 17: the back side
   uint2 *levels = nullptr;    // a world set's slots (a world: one entry)
+  float4 *bounds = nullptr;   // a slot's minx, maxx, minz, maxz (line_bounds): what the explored-area grid is derived from (area.hip)
   uint32_t n_lines = 0, n_levels = 0;
 };
+// the exact bounds of a table's end points as the "explored area" contract takes them: minx, maxx, minz, maxz; zeros for no lines
+inline float4 line_bounds(const rdoom_map_line *lines, size_t n) {
+  if (!n) return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  float4 b = make_float4(lines[0].a[0], lines[0].a[0], lines[0].a[1], lines[0].a[1]);
+  for (size_t i = 0; i < n; i++)
+    for (const float *v : {lines[i].a, lines[i].b}) {
+      b.x = v[0] < b.x ? v[0] : b.x, b.y = v[0] > b.y ? v[0] : b.y;
+      b.z = v[1] < b.z ? v[1] : b.z, b.w = v[1] > b.w ? v[1] : b.w;
+    }
+  return b;
+}
 // automap.hip: `lines` with `n_levels` (first, count) ranges on the current device; releases what it allocated
 rdoom_status map_upload(const std::vector<rdoom_map_line> &lines, const std::vector<uint2> &levels, MapDevice &out);
 void map_free(MapDevice &d);
@@ -201,6 +213,8 @@ struct MapSource {
   uint32_t max_sectors;   // the sectors of its table; a set's: of its largest level's (known on host-only handles too)
   uint32_t game_objects;  // the n_objects its game calls need at least
   uint32_t max_lines;     // the lines of its table; a set's: of its largest level's (known on host-only handles too)
+  const float4 *bounds;   // line_bounds of every level, on the host (known on host-only handles too)
+  uint32_t n_levels;      // the levels of the handle: 1 for a world
   bool on_device;
   int device;
 };
