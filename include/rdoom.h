@@ -1247,6 +1247,88 @@ rdoom_status rdoom_worldset_draw_area_maps(const rdoom_worldset *set, const rdoo
                                            uint32_t n, const rdoom_map_view *view, const uint32_t *d_area, uint32_t stride,
                                            float cell, uint8_t *d_out, void *stream);
 
+/* ---- goal distance: walking distance to a goal over the whole level -------------------------------------------
+ * The geodesic distance a navigation task is built on -- shaping reward, success test, shortest-path baseline -- as three pieces: the
+ * level's walkability on its explored-area grid, a flood of grids of any size that can run towards its seed, and the cell a player
+ * is in.  One flood per episode (or per goal) gives a field to_goal[p, iz, ix]; every later tick reads it with one gather at the
+ * player's cell.  The reference project has no counterpart of this: nothing here restates it.  Every float below is binary32, every
+ * operation is rounded once and none is contracted.
+ *
+ * rdoom_world_draw_area_planes / rdoom_worldset_draw_area_planes: the level's planes on its area grid.  n rows; d_levels (the set
+ * form: n uint32 slots); d_object_offsets / n_objects exactly as rdoom_world_draw_sector_maps takes them -- row p is the game whose
+ * doors and lifts count, NULL is all at rest; cell: the explored-area contract's; width, height: the extent of every row's planes,
+ * each at least the gw / gh of the handle's grid at `cell` (for a set: of every level's grid) and at most RDOOM_AREA_MAX_SIDE;
+ * d_area / area_stride: NULL, or the rows of rdoom_world_reveal_area; d_sector_out (uint16), d_floor_out, d_ceiling_out (float):
+ * each n x height x width or NULL, at least one given.
+ * Element (p * height + iz) * width + ix is cell (ix, iz) of the grid of row p's level.  For ix < gw && iz < gh of that level the
+ * sample point is the cell's centre,
+ *   x = ((float)(ix0 + (int32_t)ix) + 0.5f) * cell;   z = ((float)(iz0 + (int32_t)iz) + 0.5f) * cell
+ * s is the sector at (x, z) as the "sectors" contract above defines it, and the three outputs are exactly what
+ * rdoom_world_draw_sector_maps stores for a pixel whose point is that one: s (or RDOOM_SECTOR_NONE16), the live floor and ceiling of
+ * s on row p of the offsets, +inf / -inf for none.  Every element outside the level's own gw x gh is written as none, so a flood
+ * sees closed cells there; a level slot >= the set's size gives a row of none.
+ * With d_area, a cell is written as none in every plane unless its FREE bit is set and its WALL bit is clear in row p (the
+ * free & ~wall the explored-area contract tells consumers to read): the filled level map revealed as the player explores, the
+ * analogue of d_visited in rdoom_world_draw_sector_maps.
+ * This is a point sample per cell, as a map pixel is: a wall thinner than a cell can fall between two centres.  A flood of these
+ * planes models walking on the grid, not the sphere-and-spring physics of rdoom_world_step_players.
+ * One launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so the call can be
+ * captured into a graph.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): a NULL handle; (n > 0) NULL d_levels, or all
+ * three outputs NULL; a cell the explored-area grid calls reject for this handle (not finite or not > 0, a grid over its limits);
+ * width or height smaller than the grid's or above RDOOM_AREA_MAX_SIDE; n x ceil(width * height / 256) above 2^31 - 1;
+ * d_object_offsets with n_objects smaller than the game's objects; d_area with area_stride below the handle's area words at `cell`;
+ * a handle created with RDOOM_WORLD_HOST_ONLY or living on another device.  n == 0 queues nothing.
+ *
+ * rdoom_flood_grids: rdoom_flood_maps for grids of any size, from the seed or towards it.  d_floor, d_ceiling: n x height x width
+ * floats each, row r, column c, a void cell +inf / -inf.
+ * Open.  With f the floor and g the ceiling of a cell, the cell is open when f < +inf && f > -inf && g - f >= clearance.  A NaN makes
+ * every comparison false: that cell is closed.
+ * Moves.  A move from cell a to a 4-neighbour b inside the grid is allowed when both cells are open, f_b - f_a <= max_step,
+ * f_a - f_b <= max_drop, and fminf(g_a, g_b) - fmaxf(f_a, f_b) >= clearance.  max_drop may be +inf.  Moves are directed: a ledge can
+ * be dropped from but not climbed.
+ * Seeds.  d_seeds: n x 2 int32 (column, row) in stored order; NULL: (width / 2, height / 2) for every player -- the cell at, or with
+ * a corner at, the player's point of the map contract.
+ * Distances.  d_dist_out (n x height x width uint32): without RDOOM_FLOOD_TOWARDS in params->flags the smallest number of allowed
+ * moves from row p's seed to the cell; with it the smallest number of allowed moves from the cell to the seed -- the same move
+ * relation, followed backwards from the seed.  0 at the seed; RDOOM_FLOOD_GRID_UNREACHED where there is no path, where the cell is
+ * closed, and everywhere when the seed is closed or outside the grid.  d_count_out (n uint32, may be NULL): the number of cells of
+ * row p with a distance below RDOOM_FLOOD_GRID_UNREACHED.
+ * params: rdoom_flood_params; flags is 0 or RDOOM_FLOOD_TOWARDS, any other bit is an error.
+ * Size.  width * height is at most rdoom_flood_grid_max_cells' *cells_out, a constant of the library: 2^22 (2048 x 2048); each side
+ * is at most RDOOM_AREA_MAX_SIDE.
+ * Property.  For a grid within rdoom_flood_max_cells and flags == 0, rdoom_flood_grids and rdoom_flood_maps give the same distances,
+ * element for element, with 0xFFFF widened to 0xFFFFFFFF.
+ * One launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so the call can be
+ * captured into a graph.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): NULL params; (n > 0) NULL d_floor /
+ * d_ceiling / d_dist_out; a zero width or height; a side above RDOOM_AREA_MAX_SIDE; more cells than rdoom_flood_grid_max_cells; a
+ * flag other than RDOOM_FLOOD_TOWARDS; a NaN or negative max_step, max_drop or clearance; NULL cells_out.  n == 0 queues nothing.
+ *
+ * rdoom_world_area_cells / rdoom_worldset_area_cells: which cell a player is in.  d_cells_out[p] is two int32 (ix, iz): the cell of
+ * (pos.x, pos.z) of d_states[p] in the grid of the player's level at `cell`, by the explored-area contract's "point (x, z) lies in
+ * cell"; (-1, -1) where the point lies in none -- a NaN, outside the grid, a level slot >= the set's size.  The layout is d_seeds',
+ * so the output feeds rdoom_flood_grids directly, and the pair addresses the planes above.  One launch, asynchronous on `stream`;
+ * nothing is allocated and nothing waits, so the call can be captured into a graph.  Errors, all checked before anything is queued
+ * (RDOOM_BAD_ARG): those of rdoom_world_locate_players for the arguments shared with it (a NULL handle; (n > 0) NULL d_states /
+ * d_cells_out / d_levels; a handle created with RDOOM_WORLD_HOST_ONLY or living on another device); a cell the explored-area grid
+ * calls reject.  n == 0 queues nothing. */
+#define RDOOM_FLOOD_GRID_UNREACHED 0xFFFFFFFFu
+#define RDOOM_FLOOD_TOWARDS 1u
+rdoom_status rdoom_world_draw_area_planes(const rdoom_world *world, uint32_t n, const float *d_object_offsets, uint32_t n_objects,
+                                          float cell, uint32_t width, uint32_t height, const uint32_t *d_area, uint32_t area_stride,
+                                          uint16_t *d_sector_out, float *d_floor_out, float *d_ceiling_out, void *stream);
+rdoom_status rdoom_worldset_draw_area_planes(const rdoom_worldset *set, const uint32_t *d_levels, uint32_t n,
+                                             const float *d_object_offsets, uint32_t n_objects, float cell, uint32_t width,
+                                             uint32_t height, const uint32_t *d_area, uint32_t area_stride, uint16_t *d_sector_out,
+                                             float *d_floor_out, float *d_ceiling_out, void *stream);
+rdoom_status rdoom_flood_grid_max_cells(uint32_t *cells_out);
+rdoom_status rdoom_flood_grids(const float *d_floor, const float *d_ceiling, uint32_t n, uint32_t width, uint32_t height,
+                               const int32_t *d_seeds, const rdoom_flood_params *params, uint32_t *d_dist_out, uint32_t *d_count_out,
+                               void *stream);
+rdoom_status rdoom_world_area_cells(const rdoom_world *world, const rdoom_player_state *d_states, uint32_t n, float cell,
+                                    int32_t *d_cells_out, void *stream);
+rdoom_status rdoom_worldset_area_cells(const rdoom_worldset *set, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                       uint32_t n, float cell, int32_t *d_cells_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -79,6 +79,8 @@ MAP_SECTOR = np.dtype([('floor', '<f4'), ('ceiling', '<f4'), ('floor_id', '<u4')
 MAP_EDGE = np.dtype([('a', '<f4', 2), ('d', '<f4', 2)])  # rdoom_map_edge
 SECTOR_NONE, SECTOR_NONE16 = 0xFFFFFFFF, 0xFFFF
 FLOOD_UNREACHED = 0xFFFF  # RDOOM_FLOOD_UNREACHED: flood_maps' distance of a cell no allowed path leads to
+FLOOD_GRID_UNREACHED = 0xFFFFFFFF  # RDOOM_FLOOD_GRID_UNREACHED: flood_grids' distance of such a cell (-1 as int32)
+FLOOD_TOWARDS = 1  # RDOOM_FLOOD_TOWARDS: flood_grids counts the moves from a cell to the seed, not from the seed to the cell
 SPAWN_TRIES = 8  # RDOOM_SPAWN_TRIES: the candidates spawn_players draws for a player before it falls back to the level's start
 SPAWN_RISE = 0.5  # RDOOM_SPAWN_RISE: a spawned player's height above the live floor, the start's above the floor at the start marker
 SPAWN_ENTRY = np.dtype([('a', '<f4', 3), ('b', '<f4', 3), ('c', '<f4', 3), ('cumulative', '<f4')])  # rdoom_spawn_entry
@@ -178,7 +180,9 @@ API_SYMBOLS = [
     'rdoom_batch_read_observation', 'rdoom_flood_max_cells', 'rdoom_flood_maps',
     'rdoom_world_spawn_table', 'rdoom_worldset_level_spawn_table', 'rdoom_world_spawn_players', 'rdoom_worldset_spawn_players',
     'rdoom_world_area_grid', 'rdoom_worldset_level_area_grid', 'rdoom_world_area_words', 'rdoom_worldset_area_words',
-    'rdoom_world_reveal_area', 'rdoom_worldset_reveal_area', 'rdoom_world_draw_area_maps', 'rdoom_worldset_draw_area_maps']
+    'rdoom_world_reveal_area', 'rdoom_worldset_reveal_area', 'rdoom_world_draw_area_maps', 'rdoom_worldset_draw_area_maps',
+    'rdoom_world_draw_area_planes', 'rdoom_worldset_draw_area_planes', 'rdoom_flood_grid_max_cells', 'rdoom_flood_grids',
+    'rdoom_world_area_cells', 'rdoom_worldset_area_cells']
 
 _lib = None
 
@@ -1585,6 +1589,42 @@ def flood_maps(floor, ceiling, seeds=None, max_step=0.24, max_drop=float('inf'),
     32-bit integer tensor or a raw device pointer, returns (distances, counts), counts[p] the number of cells player p reaches.  The defaults are Doom's 24-unit step and 56-unit
     body at this project's 1/100 scale: a model of walking, which nothing ties to the sphere-and-spring physics of World.step.
     One launch, asynchronous on `stream` (None, a torch stream or a raw handle); it can be captured into a graph."""
+    n, height, width = _flood_inputs(floor, ceiling, seeds)
+    dist_out, pd, count_out, pc = _flood_outputs(n, height, width, floor.device, dist_out, count_out, 2)
+    params = FloodParams(max_step, max_drop, clearance, 0)
+    v = ctypes.c_void_p
+    _check(lib().rdoom_flood_maps(v(floor.data_ptr()), v(ceiling.data_ptr()), n, width, height, v(seeds.data_ptr()) if seeds is not None else None,
+                                  ctypes.byref(params), v(pd), v(pc), v(_stream_handle(stream))))
+    return dist_out if count_out is None else (dist_out, count_out)
+
+
+def _flood_outputs(n, height, width, device, dist_out, count_out, dist_bytes):
+    """flood_maps' and flood_grids' outputs, checked: (dist_out, its pointer, count_out or None, its pointer)"""
+    import torch
+    bits = '%d-bit' % (8 * dist_bytes)
+    if dist_out is None:
+        dist_out = torch.empty((n, height, width), dtype=torch.uint16 if dist_bytes == 2 else torch.int32, device=device)
+    if isinstance(dist_out, int) and not isinstance(dist_out, bool):
+        pd = dist_out  # a raw device pointer to n * height * width distances
+    elif not isinstance(dist_out, torch.Tensor) or dist_out.element_size() != dist_bytes or dist_out.dtype.is_floating_point:
+        raise ValueError('dist_out must be a %s integer tensor or a device pointer' % bits)
+    else:
+        pd = _out_tensor(dist_out, n * height * width * dist_bytes, 'dist_out')
+    if count_out is None or count_out is False:
+        count_out = None
+    elif count_out is True:
+        count_out = torch.empty(n, dtype=torch.int32, device=device)
+    if isinstance(count_out, int) and not isinstance(count_out, bool):
+        pc = count_out  # a raw device pointer to n uint32
+    elif count_out is not None and (not isinstance(count_out, torch.Tensor) or count_out.element_size() != 4 or count_out.dtype.is_floating_point):
+        raise ValueError('count_out must be True, a 32-bit integer tensor or a device pointer')
+    else:
+        pc = _out_tensor(count_out, n * 4, 'count_out')
+    return dist_out, pd, count_out, pc
+
+
+def _flood_inputs(floor, ceiling, seeds):
+    """flood_maps' and flood_grids' inputs, checked: (n, height, width)"""
     import torch
     for t, what in ((floor, 'floor'), (ceiling, 'ceiling')):
         if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or not t.is_contiguous() or t.dtype != torch.float32 or t.dim() != 3:
@@ -1595,29 +1635,106 @@ def flood_maps(floor, ceiling, seeds=None, max_step=0.24, max_drop=float('inf'),
     if seeds is not None and (not isinstance(seeds, torch.Tensor) or seeds.device.type != 'cuda' or not seeds.is_contiguous() or
                               seeds.dtype != torch.int32 or tuple(seeds.shape) != (n, 2)):
         raise ValueError('seeds must be a contiguous int32 (%d, 2) tensor of (column, row) on the GPU' % n)
-    if dist_out is None:
-        dist_out = torch.empty((n, height, width), dtype=torch.uint16, device=floor.device)
-    if isinstance(dist_out, int) and not isinstance(dist_out, bool):
-        pd = dist_out  # a raw device pointer to n * height * width uint16
-    elif not isinstance(dist_out, torch.Tensor) or dist_out.element_size() != 2 or dist_out.dtype.is_floating_point:
-        raise ValueError('dist_out must be a 16-bit integer tensor or a device pointer')
-    else:
-        pd = _out_tensor(dist_out, n * height * width * 2, 'dist_out')
-    if count_out is None or count_out is False:
-        count_out = None
-    elif count_out is True:
-        count_out = torch.empty(n, dtype=torch.int32, device=floor.device)
-    if isinstance(count_out, int) and not isinstance(count_out, bool):
-        pc = count_out  # a raw device pointer to n uint32
-    elif count_out is not None and (not isinstance(count_out, torch.Tensor) or count_out.element_size() != 4 or count_out.dtype.is_floating_point):
-        raise ValueError('count_out must be True, a 32-bit integer tensor or a device pointer')
-    else:
-        pc = _out_tensor(count_out, n * 4, 'count_out')
-    params = FloodParams(max_step, max_drop, clearance, 0)
+    return n, height, width
+
+
+def flood_grid_max_cells():
+    """rdoom_flood_grid_max_cells: the most cells (width * height) of a grid flood_grids takes, a constant of the library: 2 ** 22"""
+    cells = ctypes.c_uint32(0)
+    _check(lib().rdoom_flood_grid_max_cells(ctypes.byref(cells)))
+    return cells.value
+
+
+def flood_grids(floor, ceiling, seeds=None, towards=False, max_step=0.24, max_drop=float('inf'), clearance=0.56, dist_out=None, count_out=None,
+                stream=None):
+    """rdoom_flood_grids: flood_maps for grids of any size up to flood_grid_max_cells() cells and AREA_MAX_SIDE a side -- the planes
+    World.draw_area_planes(floor=True, ceiling=True) returns of a whole level -- from the seed or towards it.  floor, ceiling,
+    seeds, max_step, max_drop, clearance: as flood_maps takes them; seeds may be area_cells' output, whose (-1, -1) of a player in no
+    cell gives an all-unreached row.  towards False: the moves from the seed to each cell, as flood_maps counts them; True: the moves
+    from each cell to the seed, the same directed moves followed backwards -- with a goal's cell as the seed, the walking distance
+    to the goal from everywhere, which across a ledge differs from the distance from the goal.  Returns the (n, H, W) int32 tensor of
+    distances, 0 at the seed and FLOOD_GRID_UNREACHED (-1 as int32) where no path leads, where the cell is closed, and everywhere
+    when the seed is closed or outside the grid (dist_out: a 32-bit integer tensor, or a raw device pointer, to write instead of a
+    new one); with count_out True, an (n,) 32-bit integer tensor or a raw device pointer, returns (distances, counts).  For a grid
+    flood_maps takes and towards False the two give the same distances.  One launch, asynchronous on `stream` (None, a torch stream
+    or a raw handle); it can be captured into a graph."""
+    n, height, width = _flood_inputs(floor, ceiling, seeds)
+    dist_out, pd, count_out, pc = _flood_outputs(n, height, width, floor.device, dist_out, count_out, 4)
+    params = FloodParams(max_step, max_drop, clearance, FLOOD_TOWARDS if towards else 0)
     v = ctypes.c_void_p
-    _check(lib().rdoom_flood_maps(v(floor.data_ptr()), v(ceiling.data_ptr()), n, width, height, v(seeds.data_ptr()) if seeds is not None else None,
-                                  ctypes.byref(params), v(pd), v(pc), v(_stream_handle(stream))))
+    _check(lib().rdoom_flood_grids(v(floor.data_ptr()), v(ceiling.data_ptr()), n, width, height, v(seeds.data_ptr()) if seeds is not None else None,
+                                   ctypes.byref(params), v(pd), v(pc), v(_stream_handle(stream))))
     return dist_out if count_out is None else (dist_out, count_out)
+
+
+def _draw_area_planes(call, shape, words, levels, cell, n, offsets, area, sector_out, floor, ceiling, stream):
+    """World.draw_area_planes / WorldSet.draw_area_planes: the checks and the launch; call(levels, n, offsets, n_objects, cell,
+    width, height, area, stride, sector_out, floor_out, ceiling_out, stream) is the C entry point with its handle bound.  Returns
+    the planes asked for, in the order sector, floor, ceiling: one tensor, or a tuple of them"""
+    import torch
+    given = [t for t in (levels, offsets, area, sector_out, floor, ceiling) if isinstance(t, torch.Tensor)]
+    for t, what in ((levels, 'levels'), (offsets, 'offsets')):
+        if t is not None and (not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or not t.is_contiguous()):
+            raise ValueError('%s must be a contiguous tensor on the GPU' % what)
+    if n is None:  # the rows of the first tensor given, else 1
+        n = int(given[0].numel()) if levels is not None else (int(given[0].shape[0]) if given else 1)
+    n = int(n)
+    if levels is not None and (levels.element_size() != 4 or levels.numel() != n):
+        raise ValueError('levels must hold one 32-bit slot per row (%d), got %s %s' % (n, levels.dtype, tuple(levels.shape)))
+    n_obj = 0
+    if offsets is not None:
+        if offsets.dtype != torch.float32 or offsets.dim() != 3 or offsets.shape[0] != n or offsets.shape[2] != 3:
+            raise ValueError('offsets must be a float32 (n, n_objects, 3) tensor for %d rows, got %s %s' % (n, offsets.dtype, tuple(offsets.shape)))
+        n_obj = int(offsets.shape[1])
+    pa, stride = _area_rows(area, n, words) if area is not None else (None, 0)
+    height, width = shape
+    device = given[0].device if given else torch.device('cuda', torch.cuda.current_device())
+    asked = ((sector_out, torch.int16, 'sector_out'), (floor, torch.float32, 'floor'), (ceiling, torch.float32, 'ceiling'))
+    # the caller's tensors first: they set the (padded) extent of every plane, those allocated here too
+    mine = []
+    for want, dtype, what in asked:
+        if want is None or want is False or want is True:
+            continue
+        if not isinstance(want, torch.Tensor) or want.element_size() != (2 if dtype == torch.int16 else 4) or \
+                want.dtype.is_floating_point != (dtype == torch.float32) or want.dim() != 3 or want.shape[0] != n:
+            raise ValueError('%s must be True or a %s (n, height, width) tensor' % (what, '16-bit integer' if dtype == torch.int16 else 'float32'))
+        mine.append(want)
+    if mine:
+        height, width = int(mine[0].shape[1]), int(mine[0].shape[2])
+        if any(tuple(t.shape) != (n, height, width) for t in mine):
+            raise ValueError('the planes differ in shape: %s' % [tuple(t.shape) for t in mine])
+    planes = []
+    for want, dtype, what in asked:
+        if want is None or want is False:
+            planes.append(None)
+            continue
+        if want is True:
+            want = torch.empty((n, height, width), dtype=dtype, device=device)
+        _out_tensor(want, n * height * width * want.element_size(), what)
+        planes.append(want)
+    if all(t is None for t in planes):
+        raise ValueError('no plane asked for: sector_out, floor and ceiling are all off')
+    v = ctypes.c_void_p
+    _check(call(v(levels.data_ptr()) if levels is not None else None, n, v(offsets.data_ptr()) if offsets is not None else None, n_obj,
+                ctypes.c_float(cell), width, height, v(pa), stride, *[v(t.data_ptr()) if t is not None else None for t in planes],
+                v(_stream_handle(stream))))
+    out = tuple(t for t in planes if t is not None)
+    return out[0] if len(out) == 1 else out
+
+
+def _area_cells(call, states, levels, cell, out, stream):
+    """World.area_cells / WorldSet.area_cells: the checks and the launch; call(states, levels, n, cell, out, stream) is the C entry
+    point with its handle bound"""
+    import torch
+    n, _ = _player_tensors(states, levels, None)
+    if out is None:
+        out = torch.empty((n, 2), dtype=torch.int32, device=states.device)
+    elif out.dtype != torch.int32:
+        raise ValueError('out must be int32')
+    po = _out_tensor(out, n * 8, 'out')
+    v = ctypes.c_void_p
+    _check(call(v(states.data_ptr()), v(levels.data_ptr()) if levels is not None else None, n, ctypes.c_float(cell), v(po), v(_stream_handle(stream))))
+    return out
 
 
 class SpawnTableArrays(ctypes.Structure):
@@ -1926,6 +2043,36 @@ class World:
                                width, height, scale, area, cell, rotate, top_down, out, stream)
 
 
+    # ---- goal distance -----------------------------------------------------------------------------------------------------
+    def area_plane_shape(self, cell):
+        """(height, width) of draw_area_planes' planes at that cell size: the (gh, gw) of area_grid(cell)"""
+        g = self.area_grid(cell)
+        return g.gh, g.gw
+
+    def draw_area_planes(self, cell, n=None, offsets=None, area=None, sector_out=None, floor=False, ceiling=False, stream=None):
+        """rdoom_world_draw_area_planes: the level's sector, floor and ceiling on its explored-area grid, n rows of
+        area_plane_shape(cell) cells: element [p, iz, ix] is what draw_sector_maps stores for a pixel at the centre of cell (ix, iz)
+        of area_grid(cell) -- planes anchored to the level, which rd.flood_grids floods whole.  n: the rows (None: those of
+        the first tensor given, else 1); offsets: None or step_game's tensor, row p the game whose doors and lifts count; area: None or reveal_area's rows --
+        only cells the player has seen free (and not as a wall) show, the others are void.  sector_out / floor / ceiling: as
+        draw_sector_maps takes them; a caller's tensor may be larger than area_plane_shape(cell), the padding is void.  With none of
+        the three asked for, the sector plane is drawn.  Returns the planes asked for, in the order sector, floor, ceiling (one
+        tensor, or a tuple).  A point sample per cell: a model of walking on the grid, which nothing ties to World.step.
+        Asynchronous on `stream`; it can be captured into a graph."""
+        L = lib()
+        if sector_out is None and floor is False and ceiling is False:
+            sector_out = True
+        return _draw_area_planes(lambda lv, *rest: L.rdoom_world_draw_area_planes(self._h, *rest), self.area_plane_shape(cell),
+                                 self.area_words(cell), None, cell, n, offsets, area, sector_out, floor, ceiling, stream)
+
+    def area_cells(self, states, cell, out=None, stream=None):
+        """rdoom_world_area_cells: the cell (ix, iz) of area_grid(cell) every player stands in, an int32 (n, 2) tensor, (-1, -1) for
+        a player outside the grid or at a NaN.  The pair indexes draw_area_planes' planes and a flood of them as [p, iz, ix], and
+        the tensor is flood_grids' seeds.  out: an optional preallocated tensor.  Asynchronous on `stream`."""
+        L = lib()
+        return _area_cells(lambda st, lv, *rest: L.rdoom_world_area_cells(self._h, st, *rest), states, None, cell, out, stream)
+
+
 class WorldSetLevelInfo(ctypes.Structure):
     _fields_ = [('archive_index', ctypes.c_uint32), ('destination', ctypes.c_uint32), ('start_pos', ctypes.c_float * 3),
                 ('start_yaw', ctypes.c_float), ('n_triggers', ctypes.c_uint32), ('n_objects', ctypes.c_uint32),
@@ -2136,3 +2283,25 @@ class WorldSet:
         L = lib()
         return _draw_area_maps(lambda st, lv, *rest: L.rdoom_worldset_draw_area_maps(self._h, st, lv, *rest), self.area_words(cell), states,
                                levels, width, height, scale, area, cell, rotate, top_down, out, stream)
+
+    # ---- goal distance -----------------------------------------------------------------------------------------------------
+    def area_plane_shape(self, cell):
+        """(height, width) of draw_area_planes' planes at that cell size: the largest gh and the largest gw of the set's levels"""
+        grids = [self.area_grid(s, cell) for s in range(self.n_levels)]
+        return max(g.gh for g in grids), max(g.gw for g in grids)
+
+    def draw_area_planes(self, levels, cell, n=None, offsets=None, area=None, sector_out=None, floor=False, ceiling=False, stream=None):
+        """rdoom_worldset_draw_area_planes: World.draw_area_planes with row p showing the level of slot levels[p] on that level's own
+        grid (area_grid(slot, cell)), every row area_plane_shape(cell) cells; outside the level's grid, and for a slot outside the
+        set, the planes are void"""
+        L = lib()
+        if sector_out is None and floor is False and ceiling is False:
+            sector_out = True
+        return _draw_area_planes(lambda lv, *rest: L.rdoom_worldset_draw_area_planes(self._h, lv, *rest), self.area_plane_shape(cell),
+                                 self.area_words(cell), levels, cell, n, offsets, area, sector_out, floor, ceiling, stream)
+
+    def area_cells(self, states, levels, cell, out=None, stream=None):
+        """rdoom_worldset_area_cells: World.area_cells for players spread over the set's levels, each in the grid of its own level;
+        (-1, -1) for a slot outside the set"""
+        L = lib()
+        return _area_cells(lambda st, lv, *rest: L.rdoom_worldset_area_cells(self._h, st, lv, *rest), states, levels, cell, out, stream)

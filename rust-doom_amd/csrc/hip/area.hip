@@ -40,36 +40,13 @@ constexpr uint32_t WAVE = 64, THREADS = 256, WAVES = THREADS / WAVE;
 constexpr float CULL_MARGIN = 9.765625e-4f;  // reveal.hip's
 constexpr uint32_t WINDOW_WORDS = 4096;      // the LDS window, both planes: 16 KiB of the unit's 25
 constexpr uint32_t CHUNK = 32;               // the steps of a sampling item
-constexpr float CELL_LIMIT = 1073741824.0f;  // 2^30
 
-// ---- the grid of a level (the contract's formulas; host and device) ----
-struct Grid {
-  int32_t ix0, iz0;
-  uint32_t gw, gh, pitch;
-};
-// cx(x), and whether x / cell is finite and below 2^30 in magnitude
-__host__ __device__ __forceinline__ bool cell_of(float x, float cell, int32_t &c) {
-  const float q = x / cell;
-  c = (int32_t)__builtin_floorf(q);
-  return __builtin_fabsf(q) < CELL_LIMIT;
-}
-// false: a bound outside the limits (the host refuses such a grid before anything is queued, so a kernel never meets one)
-__host__ __device__ __forceinline__ bool grid_of(float4 b, float cell, Grid &g) {
-  int32_t x0, x1, z0, z1;
-  const bool ok = cell_of(b.x, cell, x0) & cell_of(b.y, cell, x1) & cell_of(b.z, cell, z0) & cell_of(b.w, cell, z1);
-  g.ix0 = x0 - 1, g.iz0 = z0 - 1;
-  g.gw = (uint32_t)(x1 + 1 - g.ix0 + 1), g.gh = (uint32_t)(z1 + 1 - g.iz0 + 1);
-  g.pitch = (g.gw + 31u) / 32u;
-  return ok;
-}
-// the cell of point (x, z) in grid g: false when it lies in none.  The differences are taken modulo 2^32: a true difference is
-// within -2^31 .. 2^31, so a negative or overflowing one is far above gw
-__device__ __forceinline__ bool point_cell(const Grid &g, float cell, float x, float z, uint32_t &ix, uint32_t &iz) {
-  int32_t cx, cz;
-  const bool ok = cell_of(x, cell, cx) & cell_of(z, cell, cz);
-  ix = (uint32_t)cx - (uint32_t)g.ix0, iz = (uint32_t)cz - (uint32_t)g.iz0;
-  return ok && ix < g.gw && iz < g.gh;
-}
+// ---- the grid of a level (the contract's formulas; host and device): world_shared.hpp's, which goal.hip reads too ----
+using rdoom_dev::cell_of;
+using rdoom_dev::CELL_LIMIT;
+using rdoom_dev::Grid;
+using rdoom_dev::grid_of;
+using rdoom_dev::point_cell;
 
 struct AreaArgs {
   const rdoom_player_state *states;

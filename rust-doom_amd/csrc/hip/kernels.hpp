@@ -209,4 +209,36 @@ struct SpawnArgs {
   uint32_t flags;
 };
 
+// Kernels 14 to 16: walking distance over a whole level (goal.hip; include/rdoom.h "goal distance" has the contract).
+// 14: a level's sector, floor and ceiling planes on its explored-area grid, one thread per cell.
+struct AreaPlaneArgs {
+  const float *offsets;   // n x n_objects x xyz, or null
+  const uint32_t *area;   // n x 2 x stride words (reveal_area's rows), or null: every cell shows
+  uint16_t *sector_out;   // each n x height x width, or null
+  float *floor_out, *ceiling_out;
+  const float4 *nodes, *edges, *sectors;  // SectorDevice's arrays
+  const uint4 *leaves;
+  uint32_t n_objects, stride, width, height, blocks;  // blocks: workgroups per row of planes
+  float cell;
+};
+// 15: the cell of the explored-area grid every player stands in, one lane per player.
+struct AreaCellArgs {
+  const rdoom_player_state *states;
+  int32_t *cells_out;  // n x (ix, iz)
+  uint32_t n;
+  float cell;
+};
+// 16: grids of any size flooded from a seed or towards it.  One workgroup per grid; the distances live in dist_out, the four
+// move bits of a cell in the top four bits of its word while the kernel runs.
+struct FloodGridArgs {
+  const float *floor, *ceiling;  // n x height x width each
+  const int32_t *seeds;          // n x (column, row), or null: (width / 2, height / 2)
+  uint32_t *dist_out;            // n x height x width
+  uint32_t *count_out;           // n, or null
+  uint32_t width, height, cells; // cells = width * height <= rdoom_flood_grid_max_cells
+  uint32_t seg;                  // cells of a row or column one thread sweeps at a time
+  uint32_t towards;              // RDOOM_FLOOD_TOWARDS: the move relation is followed backwards
+  float max_step, max_drop, clearance;
+};
+
 }  // namespace rdoom_dev

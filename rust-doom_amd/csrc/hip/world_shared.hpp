@@ -1,4 +1,4 @@
-// What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip), the explored area's (area.hip), the sectors' (sectors.hip) and the spawn's (spawn.hip) share: the pick of a lane's level,
+// What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip), the explored area's (area.hip), the sectors' (sectors.hip), the spawn's (spawn.hip) and the goal distance's (goal.hip) share: the pick of a lane's level,
 // the checked launch, the device check of a handle, the map's side of a world handle, and what both map units read of a line.
 // One definition each, for player_quat.hpp's reason.
 #pragma once
@@ -120,6 +120,38 @@ __device__ __forceinline__ float2 live_heights(const SectorTables &t, const Sect
   if (s == RDOOM_SECTOR_NONE) return make_float2(__builtin_inff(), -__builtin_inff());
   const float4 r = t.sectors[lv.sector0 + s];
   return make_float2(live_height(r.x, __float_as_uint(r.z), off, n_objects), live_height(r.y, __float_as_uint(r.w), off, n_objects));
+}
+
+constexpr float CELL_LIMIT = 1073741824.0f;  // 2^30
+
+// ---- the explored-area grid of a level (include/rdoom.h "explored area": the contract's formulas; host and device), the one
+// definition the explored area's kernels (area.hip) and the goal unit's (goal.hip) share ----
+struct Grid {
+  int32_t ix0, iz0;
+  uint32_t gw, gh, pitch;
+};
+// cx(x), and whether x / cell is finite and below 2^30 in magnitude
+__host__ __device__ __forceinline__ bool cell_of(float x, float cell, int32_t &c) {
+  const float q = x / cell;
+  c = (int32_t)__builtin_floorf(q);
+  return __builtin_fabsf(q) < CELL_LIMIT;
+}
+// false: a bound outside the limits (the host refuses such a grid before anything is queued, so a kernel never meets one)
+__host__ __device__ __forceinline__ bool grid_of(float4 b, float cell, Grid &g) {
+  int32_t x0, x1, z0, z1;
+  const bool ok = cell_of(b.x, cell, x0) & cell_of(b.y, cell, x1) & cell_of(b.z, cell, z0) & cell_of(b.w, cell, z1);
+  g.ix0 = x0 - 1, g.iz0 = z0 - 1;
+  g.gw = (uint32_t)(x1 + 1 - g.ix0 + 1), g.gh = (uint32_t)(z1 + 1 - g.iz0 + 1);
+  g.pitch = (g.gw + 31u) / 32u;
+  return ok;
+}
+// the cell of point (x, z) in grid g: false when it lies in none.  The differences are taken modulo 2^32: a true difference is
+// within -2^31 .. 2^31, so a negative or overflowing one is far above gw
+__device__ __forceinline__ bool point_cell(const Grid &g, float cell, float x, float z, uint32_t &ix, uint32_t &iz) {
+  int32_t cx, cz;
+  const bool ok = cell_of(x, cell, cx) & cell_of(z, cell, cz);
+  ix = (uint32_t)cx - (uint32_t)g.ix0, iz = (uint32_t)cz - (uint32_t)g.iz0;
+  return ok && ix < g.gw && iz < g.gh;
 }
 
 }  // namespace rdoom_dev
