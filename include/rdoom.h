@@ -1329,6 +1329,70 @@ rdoom_status rdoom_world_area_cells(const rdoom_world *world, const rdoom_player
 rdoom_status rdoom_worldset_area_cells(const rdoom_worldset *set, const rdoom_player_state *d_states, const uint32_t *d_levels,
                                        uint32_t n, float cell, int32_t *d_cells_out, void *stream);
 
+/* ---- waypoints and frontiers: a flood's distance field followed on the device -----------------------------------
+ * What turns the fields of the two sections above into somewhere to walk: the walk down a field from a start -- the next waypoint
+ * on a shortest path to a goal, or the way to a cell from the player -- and the frontier of a player's explored area with the cell
+ * of it the field says is nearest.  Neither can be had from the distances alone, because moves are directed: a 4-neighbour whose
+ * distance is one less is not necessarily a cell one may step into.  The reference project has no counterpart of this: nothing
+ * here restates it.  Every float below is binary32, every operation is rounded once and none is contracted.
+ *
+ * rdoom_flood_descend: walk a field downhill.  A pure function of its arrays: no handle.  d_floor, d_ceiling: the planes
+ * rdoom_flood_grids took, n x height x width floats each; d_dist: the n x height x width uint32 that call wrote with the same
+ * `params` (flags 0 or RDOOM_FLOOD_TOWARDS, as there); D(c) is row p's word of cell c.  d_starts: n x 2 int32 (column, row), the
+ * layout of d_seeds and of rdoom_world_area_cells' output.
+ * The walk of row p.  Let a be the start.  If a is outside the grid or D(a) is RDOOM_FLOOD_GRID_UNREACHED, d_cells_out[p] =
+ * (-1, -1), d_moves_out[p] = 0 and nothing is walked.  Otherwise m = 0, and while D(a) > stop_dist and m < max_moves: among the
+ * 4-neighbours b of a inside the grid, taken in the order (column - 1, column + 1, row - 1, row + 1), the first with
+ * D(b) == D(a) - 1 whose connecting move is allowed by "Open" and "Moves" of the goal-distance contract above -- with
+ * RDOOM_FLOOD_TOWARDS the move from a to b, without it the move from b to a, because that field counts moves from the seed --
+ * becomes a, and m += 1; if no neighbour qualifies the walk stops, which only happens when the field was not flooded from these
+ * planes with these params.  At the end d_cells_out[p] = a (n x 2 int32, column then row) and d_moves_out[p] = m (n uint32).
+ * Path.  d_path_out may be NULL; otherwise it is n x path_len x 2 int32: entry k of row p is the cell after move k + 1 for
+ * k < min(m, path_len) and (-1, -1) for every later entry; every entry is written.
+ * Uses.  With RDOOM_FLOOD_TOWARDS, max_moves = K and stop_dist = 0: the waypoint K moves ahead on a shortest path to the goal, or
+ * the goal itself if it is nearer.  On a forward field, started at a frontier cell with max_moves = 0xFFFFFFFF and stop_dist = K:
+ * the cell K moves from the player on a shortest path to that frontier.  The walk is a shortest path of the field's move relation;
+ * among several, the one the neighbour order picks.
+ * One launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so the call can be
+ * captured into a graph.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): those of rdoom_flood_grids for the
+ * arguments shared with it (NULL params; (n > 0) NULL d_floor / d_ceiling; a zero width or height; a side above
+ * RDOOM_AREA_MAX_SIDE; more cells than rdoom_flood_grid_max_cells; a flag other than RDOOM_FLOOD_TOWARDS; a NaN or negative
+ * max_step, max_drop or clearance); (n > 0) NULL d_dist / d_starts / d_cells_out / d_moves_out; d_path_out with path_len 0 or above
+ * 2^22 (a walk is shorter than that: a distance is below the number of cells).  n == 0 queues nothing.
+ *
+ * rdoom_world_area_frontiers / rdoom_worldset_area_frontiers: the frontier of each player's explored area.  n rows; d_levels (the
+ * set form: n uint32 slots); cell: the explored-area contract's; d_area / area_stride: the rows of rdoom_world_reveal_area;
+ * width, height: the extent of every row of d_dist and d_mask_out, as rdoom_world_draw_area_planes and rdoom_flood_grids shape
+ * them -- each at least the gw / gh of the handle's grid at `cell` (for a set: of every level's) and at most RDOOM_AREA_MAX_SIDE;
+ * d_dist: n x height x width uint32, a field of rdoom_flood_grids (usually forwards from the players' cells, over the planes drawn
+ * through d_area); D(ix, iz) is word (p * height + iz) * width + ix.
+ * Frontier cell.  Cell (ix, iz) of row p is a frontier cell when ix < gw and iz < gh of the row's level, D(ix, iz) is not
+ * RDOOM_FLOOD_GRID_UNREACHED, and at least one of its 4-neighbours inside that gw x gh has both its FREE bit and its WALL bit clear
+ * in row p.  Bits of a grid row beyond gw, and cells beyond the grid, are not neighbours.
+ * d_cell_out (n x 2 int32, ix then iz): the frontier cell with the smallest D, ties to the smallest iz, then the smallest ix;
+ *   (-1, -1) when there is none.  The layout is d_starts', so the output feeds rdoom_flood_descend directly.
+ * d_dist_out (n uint32, may be NULL): that cell's D, or RDOOM_FLOOD_GRID_UNREACHED when there is none.
+ * d_count_out (n uint32, may be NULL): the number of frontier cells of row p.
+ * d_mask_out (n x height x width bytes, may be NULL): 1 on frontier cells and 0 elsewhere, every byte written.
+ * A level slot >= the set's size is seen on the device only: (-1, -1), RDOOM_FLOOD_GRID_UNREACHED, 0 and a mask of zeros.
+ * One launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so the call can be
+ * captured into a graph.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): those of rdoom_world_draw_area_planes for
+ * the arguments shared with it (a NULL handle; (n > 0) NULL d_levels; a cell the explored-area grid calls reject; width or height
+ * smaller than the grid's or above RDOOM_AREA_MAX_SIDE; area_stride below the handle's area words at `cell`; a handle created with
+ * RDOOM_WORLD_HOST_ONLY or living on another device); (n > 0) NULL d_area / d_dist / d_cell_out; n above 2^31 - 1.  n == 0 queues
+ * nothing. */
+rdoom_status rdoom_flood_descend(const float *d_floor, const float *d_ceiling, const uint32_t *d_dist, uint32_t n, uint32_t width,
+                                 uint32_t height, const int32_t *d_starts, const rdoom_flood_params *params, uint32_t max_moves,
+                                 uint32_t stop_dist, int32_t *d_cells_out, uint32_t *d_moves_out, int32_t *d_path_out,
+                                 uint32_t path_len, void *stream);
+rdoom_status rdoom_world_area_frontiers(const rdoom_world *world, uint32_t n, float cell, uint32_t width, uint32_t height,
+                                        const uint32_t *d_area, uint32_t area_stride, const uint32_t *d_dist, int32_t *d_cell_out,
+                                        uint32_t *d_dist_out, uint32_t *d_count_out, uint8_t *d_mask_out, void *stream);
+rdoom_status rdoom_worldset_area_frontiers(const rdoom_worldset *set, const uint32_t *d_levels, uint32_t n, float cell,
+                                           uint32_t width, uint32_t height, const uint32_t *d_area, uint32_t area_stride,
+                                           const uint32_t *d_dist, int32_t *d_cell_out, uint32_t *d_dist_out, uint32_t *d_count_out,
+                                           uint8_t *d_mask_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

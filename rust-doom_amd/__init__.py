@@ -182,7 +182,8 @@ API_SYMBOLS = [
     'rdoom_world_area_grid', 'rdoom_worldset_level_area_grid', 'rdoom_world_area_words', 'rdoom_worldset_area_words',
     'rdoom_world_reveal_area', 'rdoom_worldset_reveal_area', 'rdoom_world_draw_area_maps', 'rdoom_worldset_draw_area_maps',
     'rdoom_world_draw_area_planes', 'rdoom_worldset_draw_area_planes', 'rdoom_flood_grid_max_cells', 'rdoom_flood_grids',
-    'rdoom_world_area_cells', 'rdoom_worldset_area_cells']
+    'rdoom_world_area_cells', 'rdoom_worldset_area_cells', 'rdoom_flood_descend', 'rdoom_world_area_frontiers',
+    'rdoom_worldset_area_frontiers']
 
 _lib = None
 
@@ -1667,6 +1668,91 @@ def flood_grids(floor, ceiling, seeds=None, towards=False, max_step=0.24, max_dr
     return dist_out if count_out is None else (dist_out, count_out)
 
 
+def _int32_out(t, shape, device, what):
+    """an int32 output of `shape`: None allocates, a 32-bit integer tensor of that many elements or a raw device pointer is used as
+    given.  Returns (tensor or the pointer, pointer)"""
+    import torch
+    if t is None or t is True:
+        t = torch.empty(shape, dtype=torch.int32, device=device)
+    if isinstance(t, int) and not isinstance(t, bool):
+        return t, t
+    if not isinstance(t, torch.Tensor) or t.element_size() != 4 or t.dtype.is_floating_point:
+        raise ValueError('%s must be a 32-bit integer tensor or a device pointer' % what)
+    return t, _out_tensor(t, int(np.prod(shape)) * 4, what)
+
+
+def descend_grids(floor, ceiling, dist, starts, towards=False, max_moves=None, stop_dist=0, max_step=0.24, max_drop=float('inf'), clearance=0.56,
+                  cells_out=None, moves_out=None, path_out=None, stream=None):
+    """rdoom_flood_descend: walk flood_grids' field downhill.  floor, ceiling: the planes that flood took; dist: the (n, H, W)
+    distances it returned with the same towards, max_step, max_drop and clearance; starts: an int32 (n, 2) tensor of (column, row),
+    area_cells' or area_frontiers' layout.  From its start every row steps to the first 4-neighbour (left, right, up, down) whose
+    distance is one less and which the field's directed moves connect -- a ledge is dropped from and not climbed, which the
+    distances alone do not say -- until the distance is stop_dist or max_moves (None: no limit) moves are made.  Returns (cells,
+    moves): the int32 (n, 2) cell reached, (-1, -1) for a start outside the grid or on an unreached cell, and the int32 (n,) moves
+    made.  With towards=True and max_moves=K the cell is the waypoint K moves ahead on a shortest path to the goal (the goal itself
+    if nearer); on a forward field, from a frontier cell with stop_dist=K, it is the cell K moves from the player on the way
+    there.  path_out: an int (the length to allocate) or a 32-bit integer (n, length, 2) tensor: entry k is the cell after move
+    k + 1, (-1, -1) past the walk's end; then (cells, moves, path) is returned.  cells_out, moves_out: tensors or raw device
+    pointers to write instead of new ones.  One launch, asynchronous on `stream` (None, a torch stream or a raw handle); it can be
+    captured into a graph."""
+    import torch
+    n, height, width = _flood_inputs(floor, ceiling, None)
+    if not isinstance(starts, torch.Tensor) or starts.device.type != 'cuda' or not starts.is_contiguous() or starts.dtype != torch.int32 or \
+            tuple(starts.shape) != (n, 2):
+        raise ValueError('starts must be a contiguous int32 (%d, 2) tensor of (column, row) on the GPU' % n)
+    if not isinstance(dist, torch.Tensor) or dist.device.type != 'cuda' or not dist.is_contiguous() or dist.element_size() != 4 or \
+            dist.dtype.is_floating_point or tuple(dist.shape) != (n, height, width):
+        raise ValueError('dist must be a contiguous 32-bit integer (%d, %d, %d) tensor on the GPU' % (n, height, width))
+    cells_out, pc = _int32_out(cells_out, (n, 2), floor.device, 'cells_out')
+    moves_out, pm = _int32_out(moves_out, (n,), floor.device, 'moves_out')
+    pp, path_len = None, 0
+    if path_out is not None:
+        if isinstance(path_out, int) and not isinstance(path_out, bool):
+            path_out = torch.empty((n, path_out, 2), dtype=torch.int32, device=floor.device)
+        if not isinstance(path_out, torch.Tensor) or path_out.dim() != 3 or path_out.shape[0] != n or path_out.shape[2] != 2:
+            raise ValueError('path_out must be a length or a 32-bit integer (%d, length, 2) tensor' % n)
+        path_len = int(path_out.shape[1])
+        path_out, pp = _int32_out(path_out, (n, path_len, 2), floor.device, 'path_out')
+    params = FloodParams(max_step, max_drop, clearance, FLOOD_TOWARDS if towards else 0)
+    v = ctypes.c_void_p
+    _check(lib().rdoom_flood_descend(v(floor.data_ptr()), v(ceiling.data_ptr()), v(dist.data_ptr()), n, width, height, v(starts.data_ptr()),
+                                     ctypes.byref(params), ctypes.c_uint32(0xFFFFFFFF if max_moves is None else int(max_moves)),
+                                     ctypes.c_uint32(int(stop_dist)), v(pc), v(pm), v(pp), path_len, v(_stream_handle(stream))))
+    return (cells_out, moves_out) if path_out is None else (cells_out, moves_out, path_out)
+
+
+def _area_frontiers(call, words, levels, area, dist, cell, cell_out, dist_out, count_out, mask_out, stream):
+    """World.area_frontiers / WorldSet.area_frontiers: the checks and the launch; call(levels, n, cell, width, height, area, stride,
+    dist, cell_out, dist_out, count_out, mask_out, stream) is the C entry point with its handle bound.  Returns cell_out, or a tuple
+    of it and the optional outputs asked for, in the order dist, count, mask"""
+    import torch
+    if not isinstance(dist, torch.Tensor) or dist.device.type != 'cuda' or not dist.is_contiguous() or dist.element_size() != 4 or \
+            dist.dtype.is_floating_point or dist.dim() != 3:
+        raise ValueError('dist must be a contiguous 32-bit integer (n, height, width) tensor on the GPU')
+    n, height, width = (int(x) for x in dist.shape)
+    if levels is not None and (not isinstance(levels, torch.Tensor) or levels.device.type != 'cuda' or not levels.is_contiguous() or
+                               levels.element_size() != 4 or levels.numel() != n):
+        raise ValueError('levels must hold one 32-bit slot per row (%d) in a contiguous tensor on the GPU' % n)
+    pa, stride = _area_rows(area, n, words)
+    cell_out, pc = _int32_out(cell_out, (n, 2), dist.device, 'cell_out')
+    optional = []
+    for want, what in ((dist_out, 'dist_out'), (count_out, 'count_out')):
+        optional.append((None, None) if want is None or want is False else _int32_out(want, (n,), dist.device, what))
+    if mask_out is None or mask_out is False:
+        optional.append((None, None))
+    else:
+        if mask_out is True:
+            mask_out = torch.empty((n, height, width), dtype=torch.uint8, device=dist.device)
+        elif not isinstance(mask_out, torch.Tensor) or mask_out.element_size() != 1:
+            raise ValueError('mask_out must be True or a one-byte (n, height, width) tensor')
+        optional.append((mask_out, _out_tensor(mask_out, n * height * width, 'mask_out')))
+    v = ctypes.c_void_p
+    _check(call(v(levels.data_ptr()) if levels is not None else None, n, ctypes.c_float(cell), width, height, v(pa), stride, v(dist.data_ptr()),
+                v(pc), *[v(ptr) for _, ptr in optional], v(_stream_handle(stream))))
+    out = (cell_out,) + tuple(t for t, _ in optional if t is not None)
+    return out[0] if len(out) == 1 else out
+
+
 def _draw_area_planes(call, shape, words, levels, cell, n, offsets, area, sector_out, floor, ceiling, stream):
     """World.draw_area_planes / WorldSet.draw_area_planes: the checks and the launch; call(levels, n, offsets, n_objects, cell,
     width, height, area, stride, sector_out, floor_out, ceiling_out, stream) is the C entry point with its handle bound.  Returns
@@ -2072,6 +2158,21 @@ class World:
         L = lib()
         return _area_cells(lambda st, lv, *rest: L.rdoom_world_area_cells(self._h, st, *rest), states, None, cell, out, stream)
 
+    # ---- waypoints and frontiers -------------------------------------------------------------------------------------------
+    def area_frontiers(self, area, dist, cell, cell_out=None, dist_out=None, count_out=None, mask_out=None, stream=None):
+        """rdoom_world_area_frontiers: the frontier of every player's explored area -- the cells `dist` reaches that have a
+        4-neighbour, inside the level's grid, the player has seen neither free nor as a wall -- and the nearest of them.  area:
+        reveal_area's rows; dist: the (n, height, width) distances of rd.flood_grids, usually from the players' cells over
+        draw_area_planes(area=area); it may be larger than area_plane_shape(cell).  Returns the int32 (n, 2) tensor of the frontier
+        cell (ix, iz) with the smallest distance (ties: the smallest iz, then ix), (-1, -1) for a row without one: descend_grids'
+        starts.  dist_out, count_out, mask_out: True allocates, a tensor (dist_out, count_out: or a raw device pointer) is used
+        as given -- that cell's distance (FLOOD_GRID_UNREACHED for none), the number of frontier cells, and a uint8 (n, height,
+        width) mask of them; those asked for are returned after the cells, in that order.  One launch, asynchronous on `stream`; it
+        can be captured into a graph."""
+        L = lib()
+        return _area_frontiers(lambda lv, *rest: L.rdoom_world_area_frontiers(self._h, *rest), self.area_words(cell), None, area, dist, cell,
+                               cell_out, dist_out, count_out, mask_out, stream)
+
 
 class WorldSetLevelInfo(ctypes.Structure):
     _fields_ = [('archive_index', ctypes.c_uint32), ('destination', ctypes.c_uint32), ('start_pos', ctypes.c_float * 3),
@@ -2305,3 +2406,11 @@ class WorldSet:
         (-1, -1) for a slot outside the set"""
         L = lib()
         return _area_cells(lambda st, lv, *rest: L.rdoom_worldset_area_cells(self._h, st, lv, *rest), states, levels, cell, out, stream)
+
+    # ---- waypoints and frontiers -------------------------------------------------------------------------------------------
+    def area_frontiers(self, levels, area, dist, cell, cell_out=None, dist_out=None, count_out=None, mask_out=None, stream=None):
+        """rdoom_worldset_area_frontiers: World.area_frontiers with row p on the grid of slot levels[p]; a slot outside the set has
+        no frontier: (-1, -1), FLOOD_GRID_UNREACHED, 0 and a mask of zeros"""
+        L = lib()
+        return _area_frontiers(lambda lv, *rest: L.rdoom_worldset_area_frontiers(self._h, lv, *rest), self.area_words(cell), levels, area, dist,
+                               cell, cell_out, dist_out, count_out, mask_out, stream)

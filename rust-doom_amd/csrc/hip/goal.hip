@@ -43,16 +43,19 @@
 namespace {
 
 using rdoom_dev::AreaCellArgs;
+using rdoom_dev::allowed;
 using rdoom_dev::AreaPlaneArgs;
 using rdoom_dev::descend;
 using rdoom_dev::FloodGridArgs;
 using rdoom_dev::Grid;
+using rdoom_dev::is_open;
 using rdoom_dev::grid_of;
 using rdoom_dev::live_heights;
 using rdoom_dev::point_cell;
 using rdoom_dev::sector_in_leaf;
 using rdoom_dev::SectorLevel;
 using rdoom_dev::SectorTables;
+using rdoom_dev::WalkLimits;
 
 constexpr uint32_t WAVE = 64;
 
@@ -149,16 +152,6 @@ static_assert(MAX_CELLS < PENDING && MAX_CELLS <= RDOOM_AREA_MAX_SIDE * RDOOM_AR
 __device__ __forceinline__ uint32_t word_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 __device__ __forceinline__ void word_store(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
 
-__device__ __forceinline__ bool is_open(float f, float g, float clearance) {
-  return f < __builtin_inff() && f > -__builtin_inff() && g - f >= clearance;
-}
-
-// the move from a to b
-__device__ __forceinline__ bool allowed(float fa, float ga, float fb, float gb, const FloodGridArgs &a) {
-  return is_open(fa, ga, a.clearance) && is_open(fb, gb, a.clearance) && fb - fa <= a.max_step && fa - fb <= a.max_drop &&
-         fminf(ga, gb) - fmaxf(fa, fb) >= a.clearance;
-}
-
 // a batch of a run walked in one direction: words w[0 .. m) of cells at, at + step, ..., the distance of the cell before them in
 // `carry`
 template <uint32_t BIT>
@@ -224,13 +217,14 @@ __global__ __launch_bounds__(THREADS) void flood_grids_kernel(FloodGridArgs a) {
   // staging: the four move bits of every cell, the seed's 0.  Forwards a bit says the neighbour's move INTO the cell is allowed,
   // towards the seed that the cell's move into the neighbour is
   const bool towards = a.towards != 0;  // (a kernel argument: uniform)
+  const WalkLimits lim{a.max_step, a.max_drop, a.clearance};
   for (uint32_t i = tid; i < cells; i += THREADS) {
     const uint32_t r = i / W, c = i - r * W;
     const float f = floor[i], g = ceiling[i];
-    const bool open = is_open(f, g, a.clearance);
+    const bool open = is_open(f, g, lim.clearance);
     uint32_t m = 0;
     if (open) {
-      auto move = [&](uint32_t other) { return towards ? allowed(f, g, floor[other], ceiling[other], a) : allowed(floor[other], ceiling[other], f, g, a); };
+      auto move = [&](uint32_t other) { return towards ? allowed(f, g, floor[other], ceiling[other], lim) : allowed(floor[other], ceiling[other], f, g, lim); };
       if (c > 0 && move(i - 1)) m |= FROM_LEFT;
       if (c + 1 < W && move(i + 1)) m |= FROM_RIGHT;
       if (r > 0 && move(i - W)) m |= FROM_ABOVE;
@@ -284,27 +278,13 @@ __global__ __launch_bounds__(THREADS) void flood_grids_kernel(FloodGridArgs a) {
 }
 
 // ---- the host's side ----
-bool bad_limit(float v) { return !(v >= 0.0f); }  // a NaN or negative
-
-// the largest gw, gh and words of the handle's levels at `cell`, by the explored-area grid calls: their errors are this unit's
-rdoom_status handle_grid(const rdoom_world *w, const rdoom_worldset *set, uint32_t n_levels, float cell, rdoom_area_grid &most) {
-  most = rdoom_area_grid{};
-  for (uint32_t slot = 0; slot < n_levels; slot++) {
-    rdoom_area_grid g;
-    if (rdoom_status s = w ? rdoom_world_area_grid(w, cell, &g) : rdoom_worldset_level_area_grid(set, slot, cell, &g)) return s;
-    most.gw = g.gw > most.gw ? g.gw : most.gw, most.gh = g.gh > most.gh ? g.gh : most.gh;
-    most.words = g.words > most.words ? g.words : most.words;
-  }
-  return RDOOM_OK;
-}
-
 // the arguments of a draw, checked, as the kernel takes them.  noun: "world" or "world set"
 rdoom_status plane_args(const rdoom::MapSource &src, const rdoom_world *w, const rdoom_worldset *set, const char *noun, uint32_t n,
                         const float *d_offsets, uint32_t n_objects, float cell, uint32_t width, uint32_t height, const uint32_t *d_area,
                         uint32_t stride, uint16_t *d_sector_out, float *d_floor_out, float *d_ceiling_out, AreaPlaneArgs &a) {
   if (n && !d_sector_out && !d_floor_out && !d_ceiling_out) return rdoom::fail(RDOOM_BAD_ARG, "no output plane: sector, floor and ceiling are all null");
   rdoom_area_grid most;
-  if (rdoom_status s = handle_grid(w, set, src.n_levels, cell, most)) return s;
+  if (rdoom_status s = rdoom::handle_grid(w, set, src.n_levels, cell, most)) return s;
   if (width < most.gw || height < most.gh || width > RDOOM_AREA_MAX_SIDE || height > RDOOM_AREA_MAX_SIDE)
     return rdoom::fail(RDOOM_BAD_ARG, "planes of %u x %u cells: the %s's grid at cell %g takes %u x %u, a side is at most %u", width, height, noun,
                        (double)cell, most.gw, most.gh, RDOOM_AREA_MAX_SIDE);
@@ -326,13 +306,32 @@ rdoom_status cell_args(const rdoom::MapSource &src, const rdoom_world *w, const 
                        uint32_t n, float cell, int32_t *d_cells_out, AreaCellArgs &a) {
   if (n && (!d_states || !d_cells_out)) return rdoom::fail(RDOOM_BAD_ARG, "null states or cell output with n = %u", n);
   rdoom_area_grid most;
-  if (rdoom_status s = handle_grid(w, set, src.n_levels, cell, most)) return s;
+  if (rdoom_status s = rdoom::handle_grid(w, set, src.n_levels, cell, most)) return s;
   if (n > 0x7FFFFFFFu) return rdoom::fail(RDOOM_BAD_ARG, "%u players: too many for one launch", n);
   a = AreaCellArgs{d_states, d_cells_out, n, cell};
   return RDOOM_OK;
 }
 
 }  // namespace
+
+// what rdoom_flood_grids and rdoom_flood_descend (path.hip) check of the arguments they share
+rdoom_status rdoom::check_flood_grids(const rdoom_flood_params *params, uint32_t n, bool pointers, const char *missing, uint32_t width,
+                                      uint32_t height) {
+  const auto bad_limit = [](float v) { return !(v >= 0.0f); };  // a NaN or negative
+  if (!params) return rdoom::fail(RDOOM_BAD_ARG, "null params");
+  if (n && !pointers) return rdoom::fail(RDOOM_BAD_ARG, "null %s with n = %u", missing, n);
+  if (!width || !height) return rdoom::fail(RDOOM_BAD_ARG, "a grid of %u x %u cells (at least 1 a side)", width, height);
+  if (width > RDOOM_AREA_MAX_SIDE || height > RDOOM_AREA_MAX_SIDE)
+    return rdoom::fail(RDOOM_BAD_ARG, "a grid of %u x %u cells: a side is at most %u", width, height, RDOOM_AREA_MAX_SIDE);
+  if ((uint64_t)width * height > MAX_CELLS)
+    return rdoom::fail(RDOOM_BAD_ARG, "a grid of %u x %u cells: too many (at most %u)", width, height, MAX_CELLS);
+  if (params->flags & ~RDOOM_FLOOD_TOWARDS) return rdoom::fail(RDOOM_BAD_ARG, "flood flags 0x%x: 0 or RDOOM_FLOOD_TOWARDS", params->flags);
+  if (bad_limit(params->max_step)) return rdoom::fail(RDOOM_BAD_ARG, "max_step %g is a NaN or negative", (double)params->max_step);
+  if (bad_limit(params->max_drop)) return rdoom::fail(RDOOM_BAD_ARG, "max_drop %g is a NaN or negative", (double)params->max_drop);
+  if (bad_limit(params->clearance)) return rdoom::fail(RDOOM_BAD_ARG, "clearance %g is a NaN or negative", (double)params->clearance);
+  if (n > 0x7FFFFFFFu) return rdoom::fail(RDOOM_BAD_ARG, "%u grids: too many for one launch", n);
+  return RDOOM_OK;
+}
 
 extern "C" {
 
@@ -400,18 +399,7 @@ rdoom_status rdoom_flood_grid_max_cells(uint32_t *cells_out) {
 
 rdoom_status rdoom_flood_grids(const float *d_floor, const float *d_ceiling, uint32_t n, uint32_t width, uint32_t height, const int32_t *d_seeds,
                                const rdoom_flood_params *params, uint32_t *d_dist_out, uint32_t *d_count_out, void *stream) {
-  if (!params) return rdoom::fail(RDOOM_BAD_ARG, "null params");
-  if (n && (!d_floor || !d_ceiling || !d_dist_out)) return rdoom::fail(RDOOM_BAD_ARG, "null floor, ceiling or distance output with n = %u", n);
-  if (!width || !height) return rdoom::fail(RDOOM_BAD_ARG, "a grid of %u x %u cells (at least 1 a side)", width, height);
-  if (width > RDOOM_AREA_MAX_SIDE || height > RDOOM_AREA_MAX_SIDE)
-    return rdoom::fail(RDOOM_BAD_ARG, "a grid of %u x %u cells: a side is at most %u", width, height, RDOOM_AREA_MAX_SIDE);
-  if ((uint64_t)width * height > MAX_CELLS)
-    return rdoom::fail(RDOOM_BAD_ARG, "a grid of %u x %u cells: too many (at most %u)", width, height, MAX_CELLS);
-  if (params->flags & ~RDOOM_FLOOD_TOWARDS) return rdoom::fail(RDOOM_BAD_ARG, "flood flags 0x%x: 0 or RDOOM_FLOOD_TOWARDS", params->flags);
-  if (bad_limit(params->max_step)) return rdoom::fail(RDOOM_BAD_ARG, "max_step %g is a NaN or negative", (double)params->max_step);
-  if (bad_limit(params->max_drop)) return rdoom::fail(RDOOM_BAD_ARG, "max_drop %g is a NaN or negative", (double)params->max_drop);
-  if (bad_limit(params->clearance)) return rdoom::fail(RDOOM_BAD_ARG, "clearance %g is a NaN or negative", (double)params->clearance);
-  if (n > 0x7FFFFFFFu) return rdoom::fail(RDOOM_BAD_ARG, "%u grids: too many for one launch", n);
+  if (rdoom_status s = rdoom::check_flood_grids(params, n, d_floor && d_ceiling && d_dist_out, "floor, ceiling or distance output", width, height)) return s;
   if (!n) return RDOOM_OK;
   const uint32_t cells = width * height;
   // the shortest runs that give every thread at most one run of a phase, where the grid's shape allows that

@@ -241,4 +241,30 @@ struct FloodGridArgs {
   float max_step, max_drop, clearance;
 };
 
+// Kernels 17 and 18: waypoints and frontiers (path.hip; include/rdoom.h "waypoints and frontiers" has the contract).
+// 17: a flood's field walked downhill from a start, one wavefront per row; lanes 0 .. 3 test one neighbour each.
+struct DescendArgs {
+  const float *floor, *ceiling;  // n x height x width each: the planes the field was flooded from
+  const uint32_t *dist;          // n x height x width: rdoom_flood_grids' distances
+  const int32_t *starts;         // n x (column, row)
+  int32_t *cells_out;            // n x (column, row)
+  uint32_t *moves_out;           // n
+  int32_t *path_out;             // n x path_len x (column, row), or null
+  uint32_t n, width, height, path_len;
+  uint32_t max_moves, stop_dist;
+  float max_step, max_drop, clearance;
+};
+// 18: the frontier of every player's explored area, one workgroup per row; a thread takes 32 cells, a word of the bit planes, at a
+// time.
+struct FrontierArgs {
+  const uint32_t *area;  // n x 2 x stride words (reveal_area's rows)
+  const uint32_t *dist;  // n x height x width: rdoom_flood_grids' distances
+  int32_t *cell_out;     // n x (ix, iz)
+  uint32_t *dist_out;    // n, or null
+  uint32_t *count_out;   // n, or null
+  uint8_t *mask_out;     // n x height x width, or null
+  uint32_t stride, width, height;
+  float cell;
+};
+
 }  // namespace rdoom_dev

@@ -1,4 +1,4 @@
-// What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip), the explored area's (area.hip), the sectors' (sectors.hip), the spawn's (spawn.hip) and the goal distance's (goal.hip) share: the pick of a lane's level,
+// What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip), the explored area's (area.hip), the sectors' (sectors.hip), the spawn's (spawn.hip), the goal distance's (goal.hip) and the path unit's (path.hip) share: the pick of a lane's level,
 // the checked launch, the device check of a handle, the map's side of a world handle, and what both map units read of a line.
 // One definition each, for player_quat.hpp's reason.
 #pragma once
@@ -125,7 +125,7 @@ __device__ __forceinline__ float2 live_heights(const SectorTables &t, const Sect
 constexpr float CELL_LIMIT = 1073741824.0f;  // 2^30
 
 // ---- the explored-area grid of a level (include/rdoom.h "explored area": the contract's formulas; host and device), the one
-// definition the explored area's kernels (area.hip) and the goal unit's (goal.hip) share ----
+// definition the explored area's kernels (area.hip), the goal unit's (goal.hip) and the path unit's (path.hip) share ----
 struct Grid {
   int32_t ix0, iz0;
   uint32_t gw, gh, pitch;
@@ -152,6 +152,20 @@ __device__ __forceinline__ bool point_cell(const Grid &g, float cell, float x, f
   const bool ok = cell_of(x, cell, cx) & cell_of(z, cell, cz);
   ix = (uint32_t)cx - (uint32_t)g.ix0, iz = (uint32_t)cz - (uint32_t)g.iz0;
   return ok && ix < g.gw && iz < g.gh;
+}
+
+// ---- walking on a grid of floor and ceiling planes (include/rdoom.h "goal distance": "Open", "Moves"), the one definition the
+// flood of grids (goal.hip) and the walk down its field (path.hip) share; the units that use them turn contraction off ----
+struct WalkLimits {
+  float max_step, max_drop, clearance;
+};
+__device__ __forceinline__ bool is_open(float f, float g, float clearance) {
+  return f < __builtin_inff() && f > -__builtin_inff() && g - f >= clearance;
+}
+// the move from a to b
+__device__ __forceinline__ bool allowed(float fa, float ga, float fb, float gb, const WalkLimits &l) {
+  return is_open(fa, ga, l.clearance) && is_open(fb, gb, l.clearance) && fb - fa <= l.max_step && fa - fb <= l.max_drop &&
+         fminf(ga, gb) - fmaxf(fa, fb) >= l.clearance;
 }
 
 }  // namespace rdoom_dev
@@ -263,5 +277,22 @@ inline rdoom_status check_seen_stride(const MapSource &src, const char *noun, ui
                        src.max_lines);
   return RDOOM_OK;
 }
+
+// the largest gw, gh and words of the handle's levels at `cell` (w, or set with its n_levels), by the explored-area grid calls: their
+// errors are the caller's
+inline rdoom_status handle_grid(const rdoom_world *w, const rdoom_worldset *set, uint32_t n_levels, float cell, rdoom_area_grid &most) {
+  most = rdoom_area_grid{};
+  for (uint32_t slot = 0; slot < n_levels; slot++) {
+    rdoom_area_grid g;
+    if (rdoom_status s = w ? rdoom_world_area_grid(w, cell, &g) : rdoom_worldset_level_area_grid(set, slot, cell, &g)) return s;
+    most.gw = g.gw > most.gw ? g.gw : most.gw, most.gh = g.gh > most.gh ? g.gh : most.gh;
+    most.words = g.words > most.words ? g.words : most.words;
+  }
+  return RDOOM_OK;
+}
+// goal.hip: what rdoom_flood_grids and rdoom_flood_descend check of the arguments they share -- params, the grid's size, n; and
+// `pointers`, whether the caller's required pointers are there (`missing` names them)
+rdoom_status check_flood_grids(const rdoom_flood_params *params, uint32_t n, bool pointers, const char *missing, uint32_t width,
+                               uint32_t height);
 
 }  // namespace rdoom
