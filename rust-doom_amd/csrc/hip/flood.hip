@@ -1,20 +1,13 @@
-// Every player's sector map flooded from a seed cell: the walking distance to every cell (include/rdoom.h "flood", DESIGN section
-// 20): rdoom_flood_maps and rdoom_flood_max_cells.  It reads the floor and ceiling planes rdoom_world_draw_sector_maps writes and
-// nothing else: no world handle, no table.
+// Both distance floods: every player's sector map flooded from a seed cell (include/rdoom.h "flood", DESIGN section 20:
+// rdoom_flood_maps, rdoom_flood_max_cells) and grids of any size flooded from a seed or towards it (include/rdoom.h "goal
+// distance", DESIGN section 23: rdoom_flood_grids, rdoom_flood_grid_max_cells, rdoom::check_flood_grids).  They read floor and
+// ceiling planes -- rdoom_world_draw_sector_maps' or rdoom_world_draw_area_planes' -- and nothing else: no world handle, no table.
 //
-// Arithmetic: binary32, the contract's comparisons in the contract's order; the build passes -ffp-contract=off.
+// Arithmetic: binary32, the contract's comparisons in the contract's order; the build passes -ffp-contract=off.  The open and move
+// comparisons are world_shared.hpp's, the ones path.hip walks with.
 //
-// One 1024-thread workgroup per player.  Staged once from global memory into dynamic LDS: per cell a byte of four bits -- the cell
-// may be entered from its left, right, upper, lower neighbour -- and a 16-bit distance, 3 bytes a cell.  Then passes entirely in
-// LDS until one changes nothing.  A pass is two phases with a barrier between them: in the row phase a thread owns a run of `seg`
-// cells of a row and carries a distance along it left to right and back right to left; in the column phase it owns a run of a
-// column, top to bottom and back.  In a phase only a run's owner writes its cells; what it reads of a neighbouring run (the one
-// cell before and the one after, aligned 16-bit words) may be mid-pass -- values only fall and every value ever stored is the length
-// of a real path, so any schedule ends at the same fixed point, the shortest distances.
-// Termination: the loop condition is one LDS word every thread reads between two barriers, so it is workgroup-uniform, every
-// thread reaches every barrier, and the pass count has the hard bound cells + 1 -- a pass relaxes every move at least once (a
-// Bellman-Ford round), a distance is below the number of cells, so pass number `cells` at the latest changes nothing.
-// No global atomics, no scratch; a wave stores runs of 64 consecutive cells.
+// One skeleton, `flood`, over a store: where a cell's distance and its four move bits live.  flood_maps_kernel keeps them in LDS
+// (LdsStore), flood_grids_kernel in the output itself (GlobalStore).  One 1024-thread workgroup per grid.
 #include <hip/hip_runtime.h>
 
 #include "../common.hpp"
@@ -25,64 +18,168 @@
 
 namespace {
 
+using rdoom_dev::allowed;
 using rdoom_dev::FloodArgs;
+using rdoom_dev::FloodGridArgs;
+using rdoom_dev::FloodPlanes;
+using rdoom_dev::is_open;
+using rdoom_dev::WalkLimits;
 
 constexpr uint32_t WAVE = 64, THREADS = 1024;
-constexpr uint32_t FROM_LEFT = 1, FROM_RIGHT = 2, FROM_ABOVE = 4, FROM_BELOW = 8;  // above: the stored row before
-constexpr uint32_t UNREACHED = RDOOM_FLOOD_UNREACHED;
-// The LDS of a launch that raises no attribute of the function is 64 KiB, static and dynamic together, and two such workgroups
-// fit a CU's 160 KiB.  255 x 85 cells: 43 352 bytes of distances (rounded up to a word) + 21 675 of move bits + STATIC_LDS.
-constexpr uint32_t MAX_CELLS = 21675;
-constexpr uint32_t STATIC_LDS = (2 + THREADS / WAVE) * sizeof(uint32_t);
+constexpr uint32_t STATIC_LDS = (2 + THREADS / WAVE) * sizeof(uint32_t);  // the skeleton's: two flags and a count per wave
 constexpr uint32_t MAX_SEG = 64;
 
-constexpr uint32_t dist_bytes(uint32_t cells) { return (cells * 2u + 3u) & ~3u; }
-static_assert(dist_bytes(MAX_CELLS) + MAX_CELLS + STATIC_LDS <= 64 * 1024, "flood: the LDS of the largest grid");
-static_assert(MAX_CELLS >= 19200 && MAX_CELLS < UNREACHED, "flood: the contract's limits");
+// ---- the LDS store: per cell a 16-bit distance and a byte of move bits in dynamic LDS, 3 bytes a cell, plain loads and stores;
+// what an owner reads of a neighbouring run are aligned 16-bit words.  No global atomics, no scratch; the write-out copies the
+// distances to global memory, a wave 64 consecutive cells at a time ----
+struct LdsStore {
+  static constexpr uint32_t FROM_LEFT = 1, FROM_RIGHT = 2, FROM_ABOVE = 4, FROM_BELOW = 8;  // above: the stored row before
+  static constexpr uint32_t UNREACHED = RDOOM_FLOOD_UNREACHED;
+  // The LDS of a launch that raises no attribute of the function is 64 KiB, static and dynamic together, and two such workgroups
+  // fit a CU's 160 KiB.  255 x 85 cells: 43 352 bytes of distances (rounded up to a word) + 21 675 of move bits + STATIC_LDS.
+  static constexpr uint32_t MAX_CELLS = 21675;
+  static constexpr uint32_t dist_bytes(uint32_t cells) { return (cells * 2u + 3u) & ~3u; }
 
-__device__ __forceinline__ bool is_open(float f, float g, float clearance) {
-  return f < __builtin_inff() && f > -__builtin_inff() && g - f >= clearance;
-}
+  uint16_t *dist;
+  uint8_t *moves;
+  uint16_t *out;
 
-// the move from a to b, b known to be open
-__device__ __forceinline__ bool enters(float fa, float ga, float fb, float gb, const FloodArgs &a) {
-  return is_open(fa, ga, a.clearance) && fb - fa <= a.max_step && fa - fb <= a.max_drop && fminf(ga, gb) - fmaxf(fa, fb) >= a.clearance;
-}
-
-// One run: cells base + k * stride, k < len, forwards with the distance of the cell before the run (if there is one) carried in
-// through the FWD bits, then backwards from the cell after it through the BWD bits.  True when a distance fell.
-template <uint32_t FWD, uint32_t BWD>
-__device__ __forceinline__ bool sweep(uint16_t *dist, const uint8_t *moves, uint32_t base, uint32_t stride, uint32_t len, bool before,
-                                      bool after) {
-  bool fell = false;
-  uint32_t carry = before ? dist[base - stride] : UNREACHED;
-  for (uint32_t k = 0, at = base; k < len; k++, at += stride) {
-    uint32_t d = dist[at];
-    if ((moves[at] & FWD) && carry + 1u < d) dist[at] = (uint16_t)(d = carry + 1u), fell = true;
-    carry = d;
+  __device__ __forceinline__ void stage(uint32_t i, uint32_t m, bool seeded) {
+    moves[i] = (uint8_t)m;
+    dist[i] = (uint16_t)(seeded ? 0u : UNREACHED);
   }
-  const uint32_t last = base + (len - 1u) * stride;
-  carry = after ? dist[last + stride] : UNREACHED;
-  for (uint32_t k = 0, at = last; k < len; k++, at -= stride) {
-    uint32_t d = dist[at];
-    if ((moves[at] & BWD) && carry + 1u < d) dist[at] = (uint16_t)(d = carry + 1u), fell = true;
-    carry = d;
-  }
-  return fell;
-}
 
-__global__ __launch_bounds__(THREADS) void flood_maps_kernel(FloodArgs a) {
-  extern __shared__ __attribute__((aligned(16))) uint16_t flood_lds[];
+  template <uint32_t FWD, uint32_t BWD>
+  __device__ __forceinline__ bool sweep(uint32_t base, uint32_t stride, uint32_t len, bool before, bool after) {
+    bool fell = false;
+    uint32_t carry = before ? dist[base - stride] : UNREACHED;
+    for (uint32_t k = 0, at = base; k < len; k++, at += stride) {
+      uint32_t d = dist[at];
+      if ((moves[at] & FWD) && carry + 1u < d) dist[at] = (uint16_t)(d = carry + 1u), fell = true;
+      carry = d;
+    }
+    const uint32_t last = base + (len - 1u) * stride;
+    carry = after ? dist[last + stride] : UNREACHED;
+    for (uint32_t k = 0, at = last; k < len; k++, at -= stride) {
+      uint32_t d = dist[at];
+      if ((moves[at] & BWD) && carry + 1u < d) dist[at] = (uint16_t)(d = carry + 1u), fell = true;
+      carry = d;
+    }
+    return fell;
+  }
+
+  __device__ __forceinline__ bool finish(uint32_t i) {
+    const uint32_t d = dist[i];
+    out[i] = (uint16_t)d;
+    return d != UNREACHED;
+  }
+};
+static_assert(LdsStore::dist_bytes(LdsStore::MAX_CELLS) + LdsStore::MAX_CELLS + STATIC_LDS <= 64 * 1024, "flood: the LDS of the largest grid");
+static_assert(LdsStore::MAX_CELLS >= 19200 && LdsStore::MAX_CELLS < LdsStore::UNREACHED, "flood: the contract's limits");
+
+// ---- the global store: always in global memory, so a grid of any size takes the same code.  A cell's word of d_dist_out holds its
+// distance in the low 28 bits (PENDING: not reached so far) and, while the kernel runs, its move bits in the top four; the
+// write-out stores the clean distances in place, a thread the words it staged.  A word is read and written whole by relaxed
+// workgroup-scope atomic accesses, so it is never torn.
+// Visibility: the rule relied on is the AMDGPU memory model's for workgroup scope outside threadgroup-split mode.  The waves of a
+// workgroup run on one CU and share its vector L1, which takes that CU's vector memory accesses in the order they were issued and
+// which every store writes through; so a workgroup-scope release or acquire of global memory needs no cache maintenance and no wait
+// on the vector-memory counter, and the compiler emits none: __syncthreads() is that fence pair around s_barrier and comes out as
+// a bare s_barrier (with a wait for LDS only).  A word stored by a wave before the barrier was issued to the L1 before any load a
+// wave issues after it, so that load reads it.  The relaxed workgroup-scope atomics (sc0 loads and stores) keep every access to a
+// cell's word on that path -- the vector L1, never the scalar cache, never a register copy carried across a barrier.  No other
+// workgroup touches the grid, and nothing waits for one: no grid-wide barrier, no spin on global memory, no global
+// read-modify-write ----
+struct GlobalStore {
+  static constexpr uint32_t DIST_BITS = 28, DIST_MASK = (1u << DIST_BITS) - 1u;
+  static constexpr uint32_t PENDING = DIST_MASK;  // a cell not reached so far, while the kernel runs
+  static constexpr uint32_t FROM_LEFT = 1u << DIST_BITS, FROM_RIGHT = 2u << DIST_BITS, FROM_ABOVE = 4u << DIST_BITS, FROM_BELOW = 8u << DIST_BITS;
+  static constexpr uint32_t MAX_CELLS = 1u << 22;
+  static constexpr uint32_t BATCH = 8;  // the words of a run loaded side by side before they are walked
+
+  uint32_t *dist;
+
+  static __device__ __forceinline__ uint32_t word_load(const uint32_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+  static __device__ __forceinline__ void word_store(uint32_t *p, uint32_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+  __device__ __forceinline__ void stage(uint32_t i, uint32_t m, bool seeded) { word_store(dist + i, m | (seeded ? 0u : PENDING)); }
+
+  // a batch of a run walked in one direction: words w[0 .. m) of cells at, at + step, ..., the distance of the cell before them in
+  // `carry`
+  template <uint32_t BIT>
+  __device__ __forceinline__ bool walk(const uint32_t (&w)[BATCH], uint32_t m, uint32_t at, int32_t step, uint32_t &carry) {
+    bool fell = false;
+#pragma unroll
+    for (uint32_t j = 0; j < BATCH; j++) {
+      if (j < m) {
+        uint32_t d = w[j] & DIST_MASK;
+        if ((w[j] & BIT) && carry + 1u < d) {
+          d = carry + 1u;
+          word_store(dist + (at + (int32_t)j * step), (w[j] & ~DIST_MASK) | d);
+          fell = true;
+        }
+        carry = d;
+      }
+    }
+    return fell;
+  }
+
+  template <uint32_t FWD, uint32_t BWD>
+  __device__ __forceinline__ bool sweep(uint32_t base, uint32_t stride, uint32_t len, bool before, bool after) {
+    bool fell = false;
+    uint32_t carry = before ? word_load(dist + (base - stride)) & DIST_MASK : PENDING;
+    for (uint32_t k0 = 0; k0 < len; k0 += BATCH) {
+      const uint32_t m = min(BATCH, len - k0), at = base + k0 * stride;
+      uint32_t w[BATCH];
+#pragma unroll
+      for (uint32_t j = 0; j < BATCH; j++) w[j] = j < m ? word_load(dist + (at + j * stride)) : 0u;
+      fell |= walk<FWD>(w, m, at, (int32_t)stride, carry);
+    }
+    const uint32_t last = base + (len - 1u) * stride;
+    carry = after ? word_load(dist + (last + stride)) & DIST_MASK : PENDING;
+    for (uint32_t k0 = 0; k0 < len; k0 += BATCH) {
+      const uint32_t m = min(BATCH, len - k0), at = last - k0 * stride;
+      uint32_t w[BATCH];
+#pragma unroll
+      for (uint32_t j = 0; j < BATCH; j++) w[j] = j < m ? word_load(dist + (at - j * stride)) : 0u;
+      fell |= walk<BWD>(w, m, at, -(int32_t)stride, carry);
+    }
+    return fell;
+  }
+
+  __device__ __forceinline__ bool finish(uint32_t i) {
+    const uint32_t d = word_load(dist + i) & DIST_MASK;
+    word_store(dist + i, d == PENDING ? RDOOM_FLOOD_GRID_UNREACHED : d);
+    return d != PENDING;
+  }
+};
+static_assert(GlobalStore::MAX_CELLS < GlobalStore::PENDING && GlobalStore::MAX_CELLS <= RDOOM_AREA_MAX_SIDE * RDOOM_AREA_MAX_SIDE,
+              "flood_grids: a distance fits its 28 bits");
+
+// ---- the skeleton: grid blockIdx.x of `a` flooded in store `s`.  The four move bits of every cell -- the cell may be entered from
+// its left, right, upper, lower neighbour; `towards`: it may be LEFT for that neighbour, the same relation followed backwards --
+// are computed once from the floats and staged with the seed's 0.  Then passes until one changes nothing.  A pass is two phases
+// with a barrier between them: in the row phase a thread owns runs of `seg` cells of a row and carries a distance along each left
+// to right and back right to left (Store::sweep: cells base + k * stride, k < len, forwards with the distance of the cell before
+// the run, if there is one, carried in through the FWD bits, then backwards from the cell after it through the BWD bits; true when
+// a distance fell); in the column phase it owns runs of a column, top to bottom and back.  In a phase only a run's owner writes its
+// cells; what it reads of a neighbouring run (the one cell before and the one after, never torn) may be mid-pass -- values only
+// fall and every value ever stored is the length of a real path, so any schedule ends at the same fixed point, the shortest
+// distances.
+// Termination: the loop condition is one LDS word (two, used alternately) every thread reads between two barriers, so it is
+// workgroup-uniform, every thread reaches every barrier, and the `for` has the hard bound cells + 1 -- a pass relaxes every move
+// at least once (a Bellman-Ford round), a distance is below the number of cells, so pass number `cells` at the latest changes
+// nothing.  A closed or outside seed leaves every cell unreached: the first pass changes nothing and is the last.
+// Last the write-out (Store::finish: a cell's final distance, and whether it was reached) and the count of reached cells ----
+template <class Store>
+__device__ __forceinline__ void flood(Store s, const FloodPlanes &a, bool towards) {  // (towards: uniform)
   __shared__ uint32_t changed[2];
   __shared__ uint32_t wave_count[THREADS / WAVE];
   static_assert(sizeof changed + sizeof wave_count == STATIC_LDS, "flood: STATIC_LDS");
-  uint16_t *dist = flood_lds;
-  uint8_t *moves = (uint8_t *)flood_lds + dist_bytes(a.cells);
 
   const uint32_t tid = threadIdx.x, p = blockIdx.x;
   const uint32_t W = a.width, H = a.height, cells = a.cells;
-  const size_t map = (size_t)p * cells;
-  const float *floor = a.floor + map, *ceiling = a.ceiling + map;
+  const float *floor = a.floor + (size_t)p * cells, *ceiling = a.ceiling + (size_t)p * cells;
 
   uint32_t seed = 0xFFFFFFFFu;  // outside the grid: no cell
   {
@@ -91,20 +188,22 @@ __global__ __launch_bounds__(THREADS) void flood_maps_kernel(FloodArgs a) {
     if ((uint32_t)sc < W && (uint32_t)sr < H) seed = (uint32_t)sr * W + (uint32_t)sc;
   }
 
-  // staging: the four move bits of every cell, the seed's 0
+  // staging.  Forwards a bit says the neighbour's move INTO the cell is allowed, towards the seed that the cell's move into the
+  // neighbour is
+  const WalkLimits lim{a.max_step, a.max_drop, a.clearance};
   for (uint32_t i = tid; i < cells; i += THREADS) {
     const uint32_t r = i / W, c = i - r * W;
     const float f = floor[i], g = ceiling[i];
-    const bool open = is_open(f, g, a.clearance);
+    const bool open = is_open(f, g, lim.clearance);
     uint32_t m = 0;
     if (open) {
-      if (c > 0 && enters(floor[i - 1], ceiling[i - 1], f, g, a)) m |= FROM_LEFT;
-      if (c + 1 < W && enters(floor[i + 1], ceiling[i + 1], f, g, a)) m |= FROM_RIGHT;
-      if (r > 0 && enters(floor[i - W], ceiling[i - W], f, g, a)) m |= FROM_ABOVE;
-      if (r + 1 < H && enters(floor[i + W], ceiling[i + W], f, g, a)) m |= FROM_BELOW;
+      auto move = [&](uint32_t other) { return towards ? allowed(f, g, floor[other], ceiling[other], lim) : allowed(floor[other], ceiling[other], f, g, lim); };
+      if (c > 0 && move(i - 1)) m |= Store::FROM_LEFT;
+      if (c + 1 < W && move(i + 1)) m |= Store::FROM_RIGHT;
+      if (r > 0 && move(i - W)) m |= Store::FROM_ABOVE;
+      if (r + 1 < H && move(i + W)) m |= Store::FROM_BELOW;
     }
-    moves[i] = (uint8_t)m;
-    dist[i] = (uint16_t)((open && i == seed) ? 0u : UNREACHED);
+    s.stage(i, m, open && i == seed);
   }
   if (tid == 0) changed[0] = 0, changed[1] = 0;
   __syncthreads();
@@ -118,28 +217,23 @@ __global__ __launch_bounds__(THREADS) void flood_maps_kernel(FloodArgs a) {
     for (uint32_t run = tid; run < row_runs; run += THREADS) {
       const uint32_t r = run / runs_per_row, c0 = (run - r * runs_per_row) * seg;
       const uint32_t len = min(seg, W - c0);
-      fell |= sweep<FROM_LEFT, FROM_RIGHT>(dist, moves, r * W + c0, 1u, len, c0 > 0, c0 + len < W);
+      fell |= s.template sweep<Store::FROM_LEFT, Store::FROM_RIGHT>(r * W + c0, 1u, len, c0 > 0, c0 + len < W);
     }
     __syncthreads();
     if (tid == 0) changed[(pass + 1u) & 1u] = 0;  // the next pass's: last read before the barrier above
     for (uint32_t run = tid; run < column_runs; run += THREADS) {  // consecutive lanes: consecutive columns
       const uint32_t k = run / W, c = run - k * W, r0 = k * seg;
       const uint32_t len = min(seg, H - r0);
-      fell |= sweep<FROM_ABOVE, FROM_BELOW>(dist, moves, r0 * W + c, W, len, r0 > 0, r0 + len < H);
+      fell |= s.template sweep<Store::FROM_ABOVE, Store::FROM_BELOW>(r0 * W + c, W, len, r0 > 0, r0 + len < H);
     }
     if (fell) *flag = 1;
     __syncthreads();
     if (*flag == 0) break;  // one word, read by every thread after the barrier: uniform
   }
 
-  // out: a wave stores 64 consecutive cells at a time; the count by shuffles, then across the waves through LDS
-  uint16_t *out = a.dist_out + map;
+  // out; the count by shuffles, then across the waves through LDS
   uint32_t reached = 0;
-  for (uint32_t i = tid; i < cells; i += THREADS) {
-    const uint32_t d = dist[i];
-    out[i] = (uint16_t)d;
-    reached += d != UNREACHED;
-  }
+  for (uint32_t i = tid; i < cells; i += THREADS) reached += s.finish(i);
   if (a.count_out) {  // (a kernel argument: uniform)
     for (uint32_t step = WAVE / 2; step; step >>= 1) reached += __shfl_down(reached, step, WAVE);
     if ((tid & (WAVE - 1)) == 0) wave_count[tid / WAVE] = reached;
@@ -152,17 +246,70 @@ __global__ __launch_bounds__(THREADS) void flood_maps_kernel(FloodArgs a) {
   }
 }
 
-bool bad_limit(float v) { return !(v >= 0.0f); }  // a NaN or negative
+__global__ __launch_bounds__(THREADS) void flood_maps_kernel(FloodArgs a) {
+  extern __shared__ __attribute__((aligned(16))) uint16_t flood_lds[];
+  flood(LdsStore{flood_lds, (uint8_t *)flood_lds + LdsStore::dist_bytes(a.planes.cells), a.dist_out + (size_t)blockIdx.x * a.planes.cells}, a.planes,
+        false);
+}
+
+__global__ __launch_bounds__(THREADS) void flood_grids_kernel(FloodGridArgs a) {
+  flood(GlobalStore{a.dist_out + (size_t)blockIdx.x * a.planes.cells}, a.planes, a.towards != 0);
+}
+
+// ---- the host's side ----
+rdoom_status check_limits(const rdoom_flood_params *params) {
+  const auto bad = [](float v) { return !(v >= 0.0f); };  // a NaN or negative
+  if (bad(params->max_step)) return rdoom::fail(RDOOM_BAD_ARG, "max_step %g is a NaN or negative", (double)params->max_step);
+  if (bad(params->max_drop)) return rdoom::fail(RDOOM_BAD_ARG, "max_drop %g is a NaN or negative", (double)params->max_drop);
+  if (bad(params->clearance)) return rdoom::fail(RDOOM_BAD_ARG, "clearance %g is a NaN or negative", (double)params->clearance);
+  return RDOOM_OK;
+}
+
+// the cells of a row or column one thread sweeps at a time: the shortest runs that give every thread at most one run of a phase,
+// where the grid's shape allows that
+uint32_t run_length(uint32_t width, uint32_t height) {
+  uint32_t seg = 2;
+  while (seg < MAX_SEG && ((uint64_t)height * ((width + seg - 1) / seg) > THREADS || (uint64_t)width * ((height + seg - 1) / seg) > THREADS)) seg++;
+  return seg;
+}
+
+FloodPlanes flood_planes(const float *d_floor, const float *d_ceiling, const int32_t *d_seeds, uint32_t *d_count_out, uint32_t width,
+                         uint32_t height, const rdoom_flood_params *params) {
+  return FloodPlanes{d_floor, d_ceiling, d_seeds, d_count_out, width, height, width * height, run_length(width, height),
+                     params->max_step, params->max_drop, params->clearance};
+}
 
 }  // namespace
 
 static_assert(sizeof(rdoom_flood_params) == 16, "ABI sizes");
 
+// what rdoom_flood_grids and rdoom_flood_descend (path.hip) check of the arguments they share
+rdoom_status rdoom::check_flood_grids(const rdoom_flood_params *params, uint32_t n, bool pointers, const char *missing, uint32_t width,
+                                      uint32_t height) {
+  if (!params) return rdoom::fail(RDOOM_BAD_ARG, "null params");
+  if (n && !pointers) return rdoom::fail(RDOOM_BAD_ARG, "null %s with n = %u", missing, n);
+  if (!width || !height) return rdoom::fail(RDOOM_BAD_ARG, "a grid of %u x %u cells (at least 1 a side)", width, height);
+  if (width > RDOOM_AREA_MAX_SIDE || height > RDOOM_AREA_MAX_SIDE)
+    return rdoom::fail(RDOOM_BAD_ARG, "a grid of %u x %u cells: a side is at most %u", width, height, RDOOM_AREA_MAX_SIDE);
+  if ((uint64_t)width * height > GlobalStore::MAX_CELLS)
+    return rdoom::fail(RDOOM_BAD_ARG, "a grid of %u x %u cells: too many (at most %u)", width, height, GlobalStore::MAX_CELLS);
+  if (params->flags & ~RDOOM_FLOOD_TOWARDS) return rdoom::fail(RDOOM_BAD_ARG, "flood flags 0x%x: 0 or RDOOM_FLOOD_TOWARDS", params->flags);
+  if (rdoom_status s = check_limits(params)) return s;
+  if (n > 0x7FFFFFFFu) return rdoom::fail(RDOOM_BAD_ARG, "%u grids: too many for one launch", n);
+  return RDOOM_OK;
+}
+
 extern "C" {
 
 rdoom_status rdoom_flood_max_cells(uint32_t *cells_out) {
   if (!cells_out) return rdoom::fail(RDOOM_BAD_ARG, "null cells_out");
-  *cells_out = MAX_CELLS;
+  *cells_out = LdsStore::MAX_CELLS;
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_flood_grid_max_cells(uint32_t *cells_out) {
+  if (!cells_out) return rdoom::fail(RDOOM_BAD_ARG, "null cells_out");
+  *cells_out = GlobalStore::MAX_CELLS;
   return RDOOM_OK;
 }
 
@@ -171,21 +318,23 @@ rdoom_status rdoom_flood_maps(const float *d_floor, const float *d_ceiling, uint
   if (!params) return rdoom::fail(RDOOM_BAD_ARG, "null params");
   if (n && (!d_floor || !d_ceiling || !d_dist_out)) return rdoom::fail(RDOOM_BAD_ARG, "null floor, ceiling or distance output with n = %u", n);
   if (!width || !height) return rdoom::fail(RDOOM_BAD_ARG, "a map of %u x %u cells (at least 1 a side)", width, height);
-  if ((uint64_t)width * height > MAX_CELLS)
-    return rdoom::fail(RDOOM_BAD_ARG, "a map of %u x %u cells: too many for one workgroup's LDS (at most %u)", width, height, MAX_CELLS);
+  if ((uint64_t)width * height > LdsStore::MAX_CELLS)
+    return rdoom::fail(RDOOM_BAD_ARG, "a map of %u x %u cells: too many for one workgroup's LDS (at most %u)", width, height, LdsStore::MAX_CELLS);
   if (params->flags) return rdoom::fail(RDOOM_BAD_ARG, "flood flags 0x%x: must be 0", params->flags);
-  if (bad_limit(params->max_step)) return rdoom::fail(RDOOM_BAD_ARG, "max_step %g is a NaN or negative", (double)params->max_step);
-  if (bad_limit(params->max_drop)) return rdoom::fail(RDOOM_BAD_ARG, "max_drop %g is a NaN or negative", (double)params->max_drop);
-  if (bad_limit(params->clearance)) return rdoom::fail(RDOOM_BAD_ARG, "clearance %g is a NaN or negative", (double)params->clearance);
+  if (rdoom_status s = check_limits(params)) return s;
   if (n > 0x7FFFFFFFu) return rdoom::fail(RDOOM_BAD_ARG, "%u maps: too many for one launch", n);
   if (!n) return RDOOM_OK;
-  const uint32_t cells = width * height;
-  // the shortest runs that give every thread at most one run of a phase, where the grid's shape allows that
-  uint32_t seg = 2;
-  while (seg < MAX_SEG && (height * ((width + seg - 1) / seg) > THREADS || width * ((height + seg - 1) / seg) > THREADS)) seg++;
-  const FloodArgs a{d_floor, d_ceiling, d_seeds, d_dist_out, d_count_out, width, height, cells, seg, params->max_step, params->max_drop,
-                    params->clearance};
-  return rdoom::launch_checked(flood_maps_kernel, dim3(n), dim3(THREADS), dist_bytes(cells) + cells, stream, a);
+  const FloodArgs a{flood_planes(d_floor, d_ceiling, d_seeds, d_count_out, width, height, params), d_dist_out};
+  return rdoom::launch_checked(flood_maps_kernel, dim3(n), dim3(THREADS), LdsStore::dist_bytes(a.planes.cells) + a.planes.cells, stream, a);
+}
+
+rdoom_status rdoom_flood_grids(const float *d_floor, const float *d_ceiling, uint32_t n, uint32_t width, uint32_t height, const int32_t *d_seeds,
+                               const rdoom_flood_params *params, uint32_t *d_dist_out, uint32_t *d_count_out, void *stream) {
+  if (rdoom_status s = rdoom::check_flood_grids(params, n, d_floor && d_ceiling && d_dist_out, "floor, ceiling or distance output", width, height)) return s;
+  if (!n) return RDOOM_OK;
+  const FloodGridArgs a{flood_planes(d_floor, d_ceiling, d_seeds, d_count_out, width, height, params), d_dist_out,
+                        params->flags & RDOOM_FLOOD_TOWARDS};
+  return rdoom::launch_checked(flood_grids_kernel, dim3(n), dim3(THREADS), 0, stream, a);
 }
 
 }  // extern "C"

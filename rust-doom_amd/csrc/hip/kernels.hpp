@@ -179,16 +179,28 @@ struct LightTableArgs {
 };
 rdoom_status launch_light_tables(hipStream_t st, const LightTableArgs &args);
 
-// Kernel 12: every player's sector map flooded from its seed (flood.hip; include/rdoom.h "flood" has the contract).  One workgroup
-// per player; dynamic LDS: a 16-bit distance and a byte of move bits per cell.
-struct FloodArgs {
-  const float *floor, *ceiling;  // n x height x width each, as rdoom_world_draw_sector_maps stores them
+// Kernels 12 and 16: the two distance floods (flood.hip; include/rdoom.h "flood" and "goal distance" have the contracts).  One
+// workgroup per grid.  What both take:
+struct FloodPlanes {
+  const float *floor, *ceiling;  // n x height x width each, as rdoom_world_draw_sector_maps or rdoom_world_draw_area_planes stores them
   const int32_t *seeds;          // n x (column, row), or null: (width / 2, height / 2)
-  uint16_t *dist_out;            // n x height x width
   uint32_t *count_out;           // n, or null
-  uint32_t width, height, cells; // cells = width * height <= rdoom_flood_max_cells
-  uint32_t seg;                  // cells of a row or column one thread sweeps in a phase
+  uint32_t width, height, cells; // cells = width * height
+  uint32_t seg;                  // cells of a row or column one thread sweeps at a time
   float max_step, max_drop, clearance;
+};
+// 12: every player's sector map flooded from its seed; cells <= rdoom_flood_max_cells.  Dynamic LDS: a 16-bit distance and a byte
+// of move bits per cell.
+struct FloodArgs {
+  FloodPlanes planes;
+  uint16_t *dist_out;  // n x height x width
+};
+// 16: grids of any size flooded from a seed or towards it; cells <= rdoom_flood_grid_max_cells.  The distances live in dist_out,
+// the four move bits of a cell in the top four bits of its word while the kernel runs.
+struct FloodGridArgs {
+  FloodPlanes planes;
+  uint32_t *dist_out;  // n x height x width
+  uint32_t towards;    // RDOOM_FLOOD_TOWARDS: the move relation is followed backwards
 };
 
 // Kernel 13: players reset at seeded random points of their level's floor (spawn.hip; include/rdoom.h "spawn" has the contract).  One
@@ -209,7 +221,8 @@ struct SpawnArgs {
   uint32_t flags;
 };
 
-// Kernels 14 to 16: walking distance over a whole level (goal.hip; include/rdoom.h "goal distance" has the contract).
+// Kernels 14 and 15: the planes and cells of the walking distance over a whole level (goal.hip; include/rdoom.h "goal distance" has
+// the contract; its flood is kernel 16 above).
 // 14: a level's sector, floor and ceiling planes on its explored-area grid, one thread per cell.
 struct AreaPlaneArgs {
   const float *offsets;   // n x n_objects x xyz, or null
@@ -227,18 +240,6 @@ struct AreaCellArgs {
   int32_t *cells_out;  // n x (ix, iz)
   uint32_t n;
   float cell;
-};
-// 16: grids of any size flooded from a seed or towards it.  One workgroup per grid; the distances live in dist_out, the four
-// move bits of a cell in the top four bits of its word while the kernel runs.
-struct FloodGridArgs {
-  const float *floor, *ceiling;  // n x height x width each
-  const int32_t *seeds;          // n x (column, row), or null: (width / 2, height / 2)
-  uint32_t *dist_out;            // n x height x width
-  uint32_t *count_out;           // n, or null
-  uint32_t width, height, cells; // cells = width * height <= rdoom_flood_grid_max_cells
-  uint32_t seg;                  // cells of a row or column one thread sweeps at a time
-  uint32_t towards;              // RDOOM_FLOOD_TOWARDS: the move relation is followed backwards
-  float max_step, max_drop, clearance;
 };
 
 // Kernels 17 and 18: waypoints and frontiers (path.hip; include/rdoom.h "waypoints and frontiers" has the contract).

@@ -3,7 +3,7 @@
 // (rdoom_world_area_frontiers, rdoom_worldset_area_frontiers).
 //
 // Arithmetic: binary32, the contract's operations in the contract's order; the build passes -ffp-contract=off.  The grid formulas
-// and the open and move comparisons are world_shared.hpp's, the ones goal.hip floods with.
+// and the open and move comparisons are world_shared.hpp's, the ones flood.hip floods with.
 //
 // flood_descend: one wavefront per row, four rows to a 256-thread workgroup.  Lanes 0 .. 3 each test one neighbour of the current
 // cell, in the contract's order: its distance, the two cells' floors and ceilings, the comparisons.  A ballot's lowest set bit is

@@ -1,4 +1,4 @@
-// What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip), the explored area's (area.hip), the sectors' (sectors.hip), the spawn's (spawn.hip), the goal distance's (goal.hip) and the path unit's (path.hip) share: the pick of a lane's level,
+// What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip), the explored area's (area.hip), the sectors' (sectors.hip), the spawn's (spawn.hip), the floods' (flood.hip), the goal distance's (goal.hip) and the path unit's (path.hip) share: the pick of a lane's level,
 // the checked launch, the device check of a handle, the map's side of a world handle, and what both map units read of a line.
 // One definition each, for player_quat.hpp's reason.
 #pragma once
@@ -155,7 +155,7 @@ __device__ __forceinline__ bool point_cell(const Grid &g, float cell, float x, f
 }
 
 // ---- walking on a grid of floor and ceiling planes (include/rdoom.h "goal distance": "Open", "Moves"), the one definition the
-// flood of grids (goal.hip) and the walk down its field (path.hip) share; the units that use them turn contraction off ----
+// two floods (flood.hip) and the walk down their field (path.hip) share; the units that use them turn contraction off ----
 struct WalkLimits {
   float max_step, max_drop, clearance;
 };
@@ -290,7 +290,7 @@ inline rdoom_status handle_grid(const rdoom_world *w, const rdoom_worldset *set,
   }
   return RDOOM_OK;
 }
-// goal.hip: what rdoom_flood_grids and rdoom_flood_descend check of the arguments they share -- params, the grid's size, n; and
+// flood.hip: what rdoom_flood_grids and rdoom_flood_descend check of the arguments they share -- params, the grid's size, n; and
 // `pointers`, whether the caller's required pointers are there (`missing` names them)
 rdoom_status check_flood_grids(const rdoom_flood_params *params, uint32_t n, bool pointers, const char *missing, uint32_t width,
                                uint32_t height);

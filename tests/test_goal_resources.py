@@ -1,7 +1,7 @@
-"""The goal unit's kernels (rust-doom_amd/csrc/hip/goal.hip) as shipped: the flood of grids, the two plane kernels and the two cell
-kernels are in the library, use no scratch memory, spill no register and leave room for four waves per SIMD; the flood keeps its
-workgroup of 1024 threads and its LDS to the two flags and the waves' counts -- its distances and move bits live in global memory,
-whatever the grid's size."""
+"""The goal distance's kernels as shipped: the flood of grids (rust-doom_amd/csrc/hip/flood.hip), the two plane kernels and the two
+cell kernels (goal.hip) are in the library, use no scratch memory, spill no register and leave room for four waves per SIMD; the
+flood keeps its workgroup of 1024 threads and its LDS to the two flags and the waves' counts -- its distances and move bits live in
+global memory, whatever the grid's size."""
 import importlib.util
 import os
 import shutil

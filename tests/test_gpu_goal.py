@@ -1,9 +1,10 @@
-"""The goal distance on the GPU (goal.hip: flood_grids_kernel, the two plane kernels, the two cell kernels) against tests/goal_ref.py,
-every element of every output, bit for bit.  The flood on hand-made grids in both directions, fifteen rows a launch, on the longest
-single runs, against flood_maps where that takes the grid and on shapes it cannot take; the planes of E1M2 and E1M1 against sector_at
-at the cell centres, at rest and with offsets, padded, in a set, and through explored-area rows; planes, cells and a TOWARDS flood of
-the whole of E1M1 end to end; a door of E1M4 open in one row only; area_cells against the grid's arithmetic and as seeds; streams,
-the caller's tensors, raw pointers and a captured graph, in a child process."""
+"""The goal distance on the GPU (flood.hip: flood_grids_kernel; goal.hip: the two plane kernels, the two cell kernels) against
+tests/goal_ref.py, every element of every output, bit for bit.  The flood on hand-made grids in both directions, fifteen rows a
+launch, on the longest single runs, against flood_maps where that takes the grid -- once on a grid whose rows and columns are both
+ragged runs -- and on shapes it cannot take; the planes of E1M2 and E1M1 against sector_at at the cell centres, at rest and with
+offsets, padded, in a set, and through explored-area rows; planes, cells and a TOWARDS flood of the whole of E1M1 end to end; a door
+of E1M4 open in one row only; area_cells against the grid's arithmetic and as seeds; streams, the caller's tensors, raw pointers and
+a captured graph, in a child process."""
 import functools
 import os
 import subprocess
@@ -125,8 +126,8 @@ def test_the_sides_and_the_longest_single_runs():
 
 
 def _run_length(w, h):
-    """the cells of a row or column one thread sweeps at a time, as rdoom_flood_grids chooses them for a w x h grid (goal.hip): the
-    shortest run from 2 to 64 that gives each of the 1024 threads at most one run of a phase, else 64"""
+    """the cells of a row or column one thread sweeps at a time, as flood.hip's run_length chooses them for a w x h grid of either
+    flood: the shortest run from 2 to 64 that gives each of the 1024 threads at most one run of a phase, else 64"""
     seg = 2
     while seg < 64 and (h * -(-w // seg) > 1024 or w * -(-h // seg) > 1024):
         seg += 1
@@ -186,6 +187,37 @@ def test_grids_that_take_many_passes_and_shapes_flood_maps_cannot_take(name):
     _same(_run(floor, ceiling, seeds, towards=towards), want, name)
     if cells <= limit and not towards:
         _same(_run(floor, ceiling, seeds), _maps(floor, ceiling, seeds), (name, 'flood_maps'))
+
+
+@functools.lru_cache(maxsize=None)
+def _ragged_grid():
+    """257 x 83, the 257 x 131 recipe at a size flood_maps takes: (floor, ceiling, seeds, goal_ref forwards, goal_ref towards,
+    flood_ref widened with its counts): computed once, left unchanged"""
+    rng = np.random.default_rng(11)
+    f = np.where(rng.random((3, 83, 257)) < 0.15, 0.3, 0.0).astype(F)
+    g = np.where(rng.random((3, 83, 257)) < 0.1, 0.2, 1.5).astype(F)
+    seeds = np.array([(128, 41), (0, 0), (256, 82)], np.int32)
+    f[np.arange(3), seeds[:, 1], seeds[:, 0]], g[np.arange(3), seeds[:, 1], seeds[:, 0]] = 0.0, 1.5
+    search = goal_ref.widen(np.stack([flood_ref.flood(f[p], g[p], tuple(int(v) for v in seeds[p])) for p in range(3)]))
+    search = (search, (search != U).reshape(3, -1).sum(1).astype(np.uint32))
+    return f, g, seeds, goal_ref.flood_grids(f, g, seeds), goal_ref.flood_grids(f, g, seeds, True), search
+
+
+def test_both_floods_on_a_grid_whose_rows_and_columns_are_ragged_runs():
+    """one skeleton, two stores (flood.hip): both kernels on the same 257 x 83 planes, where neither side is whole runs"""
+    rd.set_device(0)
+    floor, ceiling, seeds, fwd, back, search = _ragged_grid()
+    seg = _run_length(257, 83)
+    assert floor[0].size <= rd.flood_max_cells() and seg == 28 and 257 % seg == 5 and 83 % seg == 27
+    for want in (fwd, back):
+        assert want[1][0] > 16000 and want[1][1] < 10 and want[1][2] > 16000 and (want[0] == U).any()
+    assert not np.array_equal(fwd[0], back[0])  # the directions differ
+    _same(search, fwd, 'the two references')
+    _same(_run(floor, ceiling, seeds), fwd, 'flood_grids')
+    _same(_run(floor, ceiling, seeds, towards=True), back, 'flood_grids towards')
+    maps = _maps(floor, ceiling, seeds)
+    _same(maps, search, 'flood_maps')
+    _same(maps, _run(floor, ceiling, seeds), 'flood_maps and flood_grids')
 
 
 # ---- the planes ------------------------------------------------------------------------------------------------------------------------

@@ -22,10 +22,12 @@ for p in (ROOT, os.path.join(ROOT, 'tests'), os.path.join(ROOT, 'tools')):
 VIEWS = ((160, 120, 0.12), (77, 53, 0.30))
 
 
-def torch_flood(floor, ceiling, max_step=0.24, max_drop=float('inf'), clearance=0.56):
-    """(distances (n, H, W) int32 with 0xFFFF for unreached, iterations): the flood from the cell (W // 2, H // 2) in plain torch"""
+def torch_flood(floor, ceiling, seeds=None, unreached=0xFFFF, max_step=0.24, max_drop=float('inf'), clearance=0.56):
+    """(distances (n, H, W) int32 with `unreached` for unreached, iterations): the flood in plain torch, from seeds (n, 2) of
+    (column, row) -- a negative pair seeds nothing -- or from the cell (W // 2, H // 2)"""
     import torch
     n, h, w = floor.shape
+    far = 0x7FFFFFF0
     is_open = torch.isfinite(floor) & ((ceiling - floor) >= clearance)
 
     def enters(a, b):  # the move from the cells of slice a into those of slice b
@@ -36,8 +38,13 @@ def torch_flood(floor, ceiling, max_step=0.24, max_drop=float('inf'), clearance=
     ways = [((every, every, lo), (every, every, hi)), ((every, every, hi), (every, every, lo)),
             ((every, lo, every), (every, hi, every)), ((every, hi, every), (every, lo, every))]
     ways = [(a, b, enters(a, b)) for a, b in ways]
-    dist = torch.full((n, h, w), 0xFFFF, dtype=torch.int32, device=floor.device)
-    dist[:, h // 2, w // 2] = torch.where(is_open[:, h // 2, w // 2], 0, 0xFFFF).to(torch.int32)
+    dist = torch.full((n, h, w), far, dtype=torch.int32, device=floor.device)
+    if seeds is None:
+        seeds = torch.tensor([[w // 2, h // 2]], dtype=torch.int32, device=floor.device).expand(n, 2)
+    rows = torch.arange(n, device=floor.device)
+    valid = (seeds >= 0).all(1)
+    r, c = seeds[:, 1].clamp(0, h - 1).long(), seeds[:, 0].clamp(0, w - 1).long()
+    dist[rows, r, c] = torch.where(valid & is_open[rows, r, c], 0, far).to(torch.int32)
     iterations = 0
     while True:
         new = dist.clone()
@@ -45,7 +52,7 @@ def torch_flood(floor, ceiling, max_step=0.24, max_drop=float('inf'), clearance=
             new[b] = torch.where(ok, torch.minimum(new[b], dist[a] + 1), new[b])
         iterations += 1
         if torch.equal(new, dist):
-            return dist, iterations
+            return torch.where(dist == far, unreached, dist), iterations
         dist = new
 
 

@@ -25,37 +25,6 @@ CONFIGS = (('E1M1', 0.25, 1.0), ('E1M1', 0.125, 0.25), ('big', 0.125, 1.0 / 32))
 MAX_STEP = 0.32  # the synthetic levels join most of their sectors by steps of 0.32
 
 
-def torch_flood(floor, ceiling, seeds, max_step=MAX_STEP, max_drop=float('inf'), clearance=0.56):
-    """(distances (n, H, W) int32 with -1 for unreached, iterations): tools/flood_cost.py's flood in plain torch, from seeds (n, 2)"""
-    import torch
-    n, h, w = floor.shape
-    far = 0x7FFFFFF0
-    is_open = torch.isfinite(floor) & ((ceiling - floor) >= clearance)
-
-    def enters(a, b):  # the move from the cells of slice a into those of slice b
-        fa, fb, ga, gb = floor[a], floor[b], ceiling[a], ceiling[b]
-        return is_open[a] & is_open[b] & ((fb - fa) <= max_step) & ((fa - fb) <= max_drop) & \
-            ((torch.minimum(ga, gb) - torch.maximum(fa, fb)) >= clearance)
-    lo, hi, every = slice(None, -1), slice(1, None), slice(None)
-    ways = [((every, every, lo), (every, every, hi)), ((every, every, hi), (every, every, lo)),
-            ((every, lo, every), (every, hi, every)), ((every, hi, every), (every, lo, every))]
-    ways = [(a, b, enters(a, b)) for a, b in ways]
-    dist = torch.full((n, h, w), far, dtype=torch.int32, device=floor.device)
-    rows = torch.arange(n, device=floor.device)
-    valid = (seeds >= 0).all(1)
-    r, c = seeds[:, 1].clamp(0, h - 1).long(), seeds[:, 0].clamp(0, w - 1).long()
-    dist[rows, r, c] = torch.where(valid & is_open[rows, r, c], 0, far).to(torch.int32)
-    iterations = 0
-    while True:
-        new = dist.clone()
-        for a, b, ok in ways:
-            new[b] = torch.where(ok, torch.minimum(new[b], dist[a] + 1), new[b])
-        iterations += 1
-        if torch.equal(new, dist):
-            return torch.where(dist == far, -1, dist), iterations
-        dist = new
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--rows', type=int, default=1024)
@@ -71,6 +40,7 @@ def main():
     import rays_ref
     import rust_doom_amd as rd
     from automap_cost import _event_ms
+    from flood_cost import torch_flood
     from util import META_PATH, ensure_big_wad, ensure_wad
     rd.set_device(0)
     stream = torch.cuda.Stream()
@@ -106,12 +76,12 @@ def main():
             maps = rd.flood_maps(floor, ceiling, cells, max_step=MAX_STEP).to(torch.int32)
             if not torch.equal(torch.where(maps == rd.FLOOD_UNREACHED, -1, maps), dist):
                 raise SystemExit('%s at %g: flood_grids and flood_maps differ' % (level, cell))
-            want, iterations = torch_flood(floor, ceiling, cells)
+            want, iterations = torch_flood(floor, ceiling, cells, unreached=-1, max_step=MAX_STEP)
             if not torch.equal(want, dist):
                 raise SystemExit('%s at %g: the torch flood and the kernel differ in %d cells' % (level, cell, int((want != dist).sum())))
             d16 = torch.empty((n, height, width), dtype=torch.uint16, device='cuda')
             maps_ms = _event_ms(lambda: rd.flood_maps(floor, ceiling, cells, max_step=MAX_STEP, dist_out=d16, stream=stream), stream, a.warmup, a.steps)
-            torch_ms = _event_ms(lambda: torch_flood(floor, ceiling, cells), torch.cuda.current_stream(), 1, a.torch_steps)
+            torch_ms = _event_ms(lambda: torch_flood(floor, ceiling, cells, unreached=-1, max_step=MAX_STEP), torch.cuda.current_stream(), 1, a.torch_steps)
             r.update(flood_maps_ms=maps_ms[0], torch_flood_ms=torch_ms[0], torch_iterations=iterations)
         draw_ms = _event_ms(draw, stream, a.warmup, a.steps)
         flood_ms = _event_ms(flood, stream, a.warmup, a.steps)
