@@ -48,6 +48,9 @@ constexpr uint32_t FRAG_WAVES = 4;  // waves per workgroup (they share the LDS c
 constexpr int FRAG_OCC = 6;         // waves per SIMD the register allocation must allow: at most 80 VGPRs
 typedef uint32_t TexelWord __attribute__((aligned(2)));
 constexpr int FRAG_WLIST = 160;  // per-wave list of unfinished quads: at most 15 carried over + 64 x 2 new
+// A list entry is a quad index (< 2^24, launch_fragment); LIST_NO_ENTRY marks a quad whose quadrant has no table entry (or a
+// render that reads no table): its pixels are in the visibility words, and shade_listed does not ask the table first.
+constexpr uint32_t LIST_NO_ENTRY = 1u << 31, LIST_QUAD_MASK = (1u << 24) - 1u;
 
 __device__ __forceinline__ uint32_t shade_sky(const LevelSlice &lv, const uint16_t *__restrict__ sky_texels, const uint8_t *cmap, float px, float py,
                                               int width, int height, float vr0, float vr1) {
@@ -160,14 +163,18 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
     if (j < count) {
       const DeviceLevelView &lv = fc->lv;  // (read here, on the rare path, not held in registers through the hot loop)
       const uint32_t div_m = fc->div_m, div_sh = fc->div_sh;
-      const uint32_t qi = mylist[first + j];
+      const uint32_t le = mylist[first + j], qi = le & LIST_QUAD_MASK;
       const uint32_t row = fast_div(qi, div_m, div_sh), qx = qi - row * quads_per_row;
       // the record of my pixel: from the quadrant table where it has an entry (the rasteriser then wrote no visibility
-      // words for that quadrant), else the pixel's visibility word
-      uint32_t id = NONE;
-      if (qtab_mode != 0u)
-        id = qtab_record(qtab[((size_t)pose * n_tiles + ((row >> 6) * tiles_x + (qx >> 4))) * 4u + ((row >> 5) & 1u) * 2u + ((qx >> 3) & 1u)]);
-      if (id == NONE) id = VIS16 ? (uint32_t)pvis16[(size_t)qi * 4u + k] : pvis32[(size_t)qi * 4u + k];
+      // words for that quadrant), else the pixel's visibility word.  The list entry says which (the block that listed the quad
+      // had looked the entry up): ONE load per pixel instead of the table entry and then, where it is NONE, the word -- and in
+      // a call that holds both kinds the two loads are issued before either is waited for.
+      const bool from_vis = (le & LIST_NO_ENTRY) != 0u;
+      uint32_t ent = NONE, word = NONE_ID;
+      if (!from_vis)
+        ent = qtab[((size_t)pose * n_tiles + ((row >> 6) * tiles_x + (qx >> 4))) * 4u + ((row >> 5) & 1u) * 2u + ((qx >> 3) & 1u)];
+      if (from_vis) word = VIS16 ? (uint32_t)pvis16[(size_t)qi * 4u + k] : pvis32[(size_t)qi * 4u + k];
+      const uint32_t id = from_vis ? word : (ent == NONE ? NONE_ID : (ent & ENTRY_REC_MASK));  // (listed without LIST_NO_ENTRY: there is an entry)
       uint32_t c = 0;
       const uint32_t pix = (row * quads_per_row + qx) * 4u + k;
       if (id != NONE_ID) {
@@ -248,6 +255,7 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
       }
     }
     tq = (uint32_t)__builtin_amdgcn_readfirstlane((int)tq);
+    const uint32_t list_tag = ((tq == NONE) & (tl == NONE)) ? LIST_NO_ENTRY : 0u;  // for shade_listed: my quadrant has no entry (or no table is read)
     const bool table_one = (tq != NONE) & (debug_leak_mod == 0u);
     uint32_t id0;
     bool uniform;
@@ -482,7 +490,7 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
       if (!done) {
         const uint32_t at = wn + (uint32_t)NQ * (uint32_t)__popcll(sm & ((1ull << lane) - 1ull));
 #pragma unroll
-        for (int q = 0; q < NQ; q++) mylist[at + (uint32_t)q] = q0 + (uint32_t)q;
+        for (int q = 0; q < NQ; q++) mylist[at + (uint32_t)q] = (q0 + (uint32_t)q) | list_tag;
       }
       wn += (uint32_t)NQ * (uint32_t)__popcll(sm);
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
