@@ -1393,6 +1393,53 @@ rdoom_status rdoom_worldset_area_frontiers(const rdoom_worldset *set, const uint
                                            const uint32_t *d_dist, int32_t *d_cell_out, uint32_t *d_dist_out, uint32_t *d_count_out,
                                            uint8_t *d_mask_out, void *stream);
 
+/* ---- wall distance: how far the nearest wall is from every cell, and planes that keep a body's radius away from it
+ * The floods above treat the walker as a point: a cell is open when its own centre has floor and headroom.  This is the one
+ * primitive that gives the walker a radius: the exact squared distance, in cells, from every cell to the nearest cell that is not
+ * open, up to a radius R, and the same planes with every cell too near such a cell made void.  The inflated planes go through
+ * rdoom_flood_maps, rdoom_flood_grids, rdoom_flood_descend and the frontier calls as they are; the distances are an observation
+ * channel, a wall-proximity penalty or a spawn margin.  The reference project has no counterpart of this: nothing here restates it.
+ *
+ * rdoom_wall_distance.  A pure function of its arrays: no handle.  d_floor, d_ceiling: n x height x width floats each, row r,
+ * column c, a void cell +inf / -inf -- the planes of rdoom_world_draw_sector_maps or rdoom_world_draw_area_planes.
+ * A cell is open by "Open" of the goal-distance contract above with params->clearance: f finite && g - f >= clearance, a NaN closes it.
+ * Blocking cells of row p.  The cells of that row's grid that are not open.  Without RDOOM_WALL_EDGE_OPEN every cell position
+ * outside width x height is blocking as well -- what the floods assume, and what rdoom_world_draw_area_planes stores outside a
+ * level's grid.  With the flag only cells inside the grid block: the reading for rdoom_world_draw_sector_maps' window, whose edge
+ * is unknown and not a wall.
+ * D2.  D2(c, r) = min over blocking (c', r') of (c - c')^2 + (r - r')^2, in integers; nothing is rounded.
+ * d_dist2_out (n x height x width uint16, may be NULL): D2 where D2 <= R * R with R = params->radius, RDOOM_WALL_FAR elsewhere.  A
+ *   closed cell holds 0.  Every value up to R * R is exact; nothing beyond R * R is reported, so the corners of the square window
+ *   the kernel looks at never leak.
+ * d_floor_out, d_ceiling_out (n x height x width floats each; both NULL or both given): where D2 > params->close_d2 the input's
+ *   32-bit word unchanged, a NaN's payload and the sign of a zero included; where D2 <= close_d2, +inf and -inf, the void cell of
+ *   the planes' own contract.  close_d2 == 0 touches closed cells only.  At least one of the three outputs is given.
+ * Model.  A body of radius r on a grid of cell size `cell` must not stand where a blocked centre lies within r of its own centre:
+ * D2 <= (r / cell)^2, so close_d2 = floor((r / cell)^2) and R is the smallest integer with R * R >= close_d2.  This is a point
+ * sample per cell like the rest of the grid: a wall thinner than a cell can still fall between two centres.  Ledges are not
+ * inflated: blocking is a property of a cell alone, not of the floor one stands on, so a step too high to climb between two open
+ * cells stays the business of the floods' move rule and is not this field's.
+ * Size.  Each side is at most RDOOM_AREA_MAX_SIDE; width * height is at most rdoom_flood_grid_max_cells' *cells_out.
+ * One launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so the call can be
+ * captured into a graph.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): NULL params; (n > 0) NULL d_floor /
+ * d_ceiling; all three outputs NULL, or one of the two planes without the other; a zero width or height; a side above
+ * RDOOM_AREA_MAX_SIDE; more cells than rdoom_flood_grid_max_cells; a radius of 0 or above RDOOM_WALL_MAX_RADIUS; close_d2 above
+ * radius * radius; a flag other than RDOOM_WALL_EDGE_OPEN; a NaN or negative clearance; n x the 64 x 32 tiles of a grid above
+ * 2^24 - 1; an output plane whose bytes overlap an input plane's -- the kernel reads neighbours, so there is no in-place form.
+ * n == 0 queues nothing. */
+#define RDOOM_WALL_FAR 0xFFFFu
+#define RDOOM_WALL_MAX_RADIUS 32u
+#define RDOOM_WALL_EDGE_OPEN 1u
+typedef struct rdoom_wall_params {
+  float clearance;   /* "Open" above, rdoom_flood_maps' word for word */
+  uint32_t radius;   /* R, in cells: 1 .. RDOOM_WALL_MAX_RADIUS */
+  uint32_t close_d2; /* cells with D2 <= close_d2 are void in the output planes; at most R * R */
+  uint32_t flags;    /* 0 or RDOOM_WALL_EDGE_OPEN */
+} rdoom_wall_params;
+rdoom_status rdoom_wall_distance(const float *d_floor, const float *d_ceiling, uint32_t n, uint32_t width, uint32_t height,
+                                 const rdoom_wall_params *params, uint16_t *d_dist2_out, float *d_floor_out, float *d_ceiling_out,
+                                 void *stream);
+
 #ifdef __cplusplus
 }
 #endif

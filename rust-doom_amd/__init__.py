@@ -81,6 +81,10 @@ SECTOR_NONE, SECTOR_NONE16 = 0xFFFFFFFF, 0xFFFF
 FLOOD_UNREACHED = 0xFFFF  # RDOOM_FLOOD_UNREACHED: flood_maps' distance of a cell no allowed path leads to
 FLOOD_GRID_UNREACHED = 0xFFFFFFFF  # RDOOM_FLOOD_GRID_UNREACHED: flood_grids' distance of such a cell (-1 as int32)
 FLOOD_TOWARDS = 1  # RDOOM_FLOOD_TOWARDS: flood_grids counts the moves from a cell to the seed, not from the seed to the cell
+WALL_FAR = 0xFFFF  # RDOOM_WALL_FAR: wall_distances' value of a cell with no blocking cell within the radius
+WALL_MAX_RADIUS = 32  # RDOOM_WALL_MAX_RADIUS: the largest radius, in cells, of wall_distances and inflate_grids
+WALL_EDGE_OPEN = 1  # RDOOM_WALL_EDGE_OPEN: cells outside the grid do not block
+WALL_TILE = (64, 32)  # the cells (across, down) of the tile one workgroup of the wall-distance kernel takes (kernels.hpp)
 SPAWN_TRIES = 8  # RDOOM_SPAWN_TRIES: the candidates spawn_players draws for a player before it falls back to the level's start
 SPAWN_RISE = 0.5  # RDOOM_SPAWN_RISE: a spawned player's height above the live floor, the start's above the floor at the start marker
 SPAWN_ENTRY = np.dtype([('a', '<f4', 3), ('b', '<f4', 3), ('c', '<f4', 3), ('cumulative', '<f4')])  # rdoom_spawn_entry
@@ -183,7 +187,7 @@ API_SYMBOLS = [
     'rdoom_world_reveal_area', 'rdoom_worldset_reveal_area', 'rdoom_world_draw_area_maps', 'rdoom_worldset_draw_area_maps',
     'rdoom_world_draw_area_planes', 'rdoom_worldset_draw_area_planes', 'rdoom_flood_grid_max_cells', 'rdoom_flood_grids',
     'rdoom_world_area_cells', 'rdoom_worldset_area_cells', 'rdoom_flood_descend', 'rdoom_world_area_frontiers',
-    'rdoom_worldset_area_frontiers']
+    'rdoom_worldset_area_frontiers', 'rdoom_wall_distance']
 
 _lib = None
 
@@ -1719,6 +1723,80 @@ def descend_grids(floor, ceiling, dist, starts, towards=False, max_moves=None, s
                                      ctypes.byref(params), ctypes.c_uint32(0xFFFFFFFF if max_moves is None else int(max_moves)),
                                      ctypes.c_uint32(int(stop_dist)), v(pc), v(pm), v(pp), path_len, v(_stream_handle(stream))))
     return (cells_out, moves_out) if path_out is None else (cells_out, moves_out, path_out)
+
+
+class WallParams(ctypes.Structure):
+    """rdoom_wall_params"""
+    _fields_ = [('clearance', ctypes.c_float), ('radius', ctypes.c_uint32), ('close_d2', ctypes.c_uint32), ('flags', ctypes.c_uint32)]
+
+
+def wall_close_d2(radius, cell):
+    """the close_d2 of a body of `radius` on a grid of `cell`: a blocked centre within radius of a cell's centre is D2 <= (radius / cell) ** 2"""
+    return int(math.floor((float(radius) / float(cell)) ** 2))
+
+
+def _wall_radius(close_d2):
+    """the smallest R >= 1 with R * R >= close_d2; ValueError above WALL_MAX_RADIUS"""
+    r = max(1, math.isqrt(close_d2 - 1) + 1) if close_d2 > 0 else 1
+    if r > WALL_MAX_RADIUS:
+        raise ValueError('close_d2 %d needs a radius of %d cells: at most %d (a coarser cell, or a smaller body)' % (close_d2, r, WALL_MAX_RADIUS))
+    return r
+
+
+def _plane_out(t, like, what):
+    """an output plane shaped like `like`: None allocates, a float32 tensor of that many bytes or a raw device pointer is used as
+    given.  Returns (tensor or the pointer, pointer)"""
+    import torch
+    if t is None:
+        t = torch.empty_like(like)
+    if isinstance(t, int) and not isinstance(t, bool):
+        return t, t
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise ValueError('%s must be a float32 tensor or a device pointer' % what)
+    return t, _out_tensor(t, like.numel() * 4, what)
+
+
+def _wall_distance(floor, ceiling, radius, close_d2, clearance, edge_open, pd, pf, pc, stream):
+    n, height, width = (int(x) for x in floor.shape)
+    params = WallParams(clearance, radius, close_d2, WALL_EDGE_OPEN if edge_open else 0)
+    v = ctypes.c_void_p
+    _check(lib().rdoom_wall_distance(v(floor.data_ptr()), v(ceiling.data_ptr()), n, width, height, ctypes.byref(params), v(pd), v(pf), v(pc),
+                                     v(_stream_handle(stream))))
+
+
+def wall_distances(floor, ceiling, radius_cells, clearance=0.56, edge_open=False, dist2_out=None, stream=None):
+    """rdoom_wall_distance, the distances alone: how far the nearest wall is from every cell.  floor, ceiling: the float32 (n, H, W)
+    GPU tensors flood_maps or flood_grids take; a cell blocks when it is not open (floor finite and ceiling - floor >= clearance),
+    and so does every position outside the grid unless edge_open -- True for draw_sector_maps' window, whose edge is unknown and
+    not a wall.  Returns the (n, H, W) uint16 tensor of D2, the squared distance in cells to the nearest blocking cell: exact where
+    D2 <= radius_cells ** 2 (1 .. WALL_MAX_RADIUS), 0 on a closed cell, WALL_FAR beyond (dist2_out: a 16-bit integer tensor, or a
+    raw device pointer, to write instead of a new one).  One launch, asynchronous on `stream` (None, a torch stream or a raw handle);
+    it can be captured into a graph."""
+    n, height, width = _flood_inputs(floor, ceiling, None)
+    dist2_out, pd, _, _ = _flood_outputs(n, height, width, floor.device, dist2_out, None, 2)
+    _wall_distance(floor, ceiling, int(radius_cells), 0, clearance, edge_open, pd, None, None, stream)
+    return dist2_out
+
+
+def inflate_grids(floor, ceiling, radius, cell, clearance=0.56, edge_open=False, floor_out=None, ceiling_out=None, dist2_out=None, stream=None):
+    """rdoom_wall_distance, the planes: floor and ceiling with every cell a body of `radius` cannot stand in made void (+inf / -inf)
+    -- the cells with a blocking cell's centre within `radius` of their own, D2 <= wall_close_d2(radius, cell) -- and every other
+    word as it was.  radius and cell are in the level's units (World.step's body: 0.19).  The result goes through flood_maps,
+    flood_grids, descend_grids and area_frontiers as it is.  Returns (floor, ceiling), new tensors or floor_out / ceiling_out (float32
+    tensors or raw device pointers, not the inputs: there is no in-place form); with dist2_out True, a 16-bit integer tensor or a raw
+    device pointer, (floor, ceiling, dist2) with wall_distances' D2 up to the launch's radius, the smallest R with R * R >= close_d2.
+    ValueError when that R is above WALL_MAX_RADIUS.  A radius below the cell's size (0.19 at cell 0.25) gives close_d2 0: only
+    closed cells are touched.  One launch, asynchronous on `stream`; it can be captured into a graph."""
+    n, height, width = _flood_inputs(floor, ceiling, None)
+    close_d2 = wall_close_d2(radius, cell)
+    r = _wall_radius(close_d2)
+    floor_out, pf = _plane_out(floor_out, floor, 'floor_out')
+    ceiling_out, pc = _plane_out(ceiling_out, ceiling, 'ceiling_out')
+    pd = None
+    if dist2_out is not None and dist2_out is not False:
+        dist2_out, pd, _, _ = _flood_outputs(n, height, width, floor.device, None if dist2_out is True else dist2_out, None, 2)
+    _wall_distance(floor, ceiling, r, close_d2, clearance, edge_open, pd, pf, pc, stream)
+    return (floor_out, ceiling_out) if pd is None else (floor_out, ceiling_out, dist2_out)
 
 
 def _area_frontiers(call, words, levels, area, dist, cell, cell_out, dist_out, count_out, mask_out, stream):

@@ -268,4 +268,19 @@ struct FrontierArgs {
   float cell;
 };
 
+// Kernel 19: the squared distance to the nearest blocking cell, capped at a radius, and the planes with the cells near a wall made
+// void (walls.hip; include/rdoom.h "wall distance" has the contract).  One workgroup per WALL_TILE_X x WALL_TILE_Y tile of one row's
+// grid; static LDS for the tile and a halo of the largest radius.
+constexpr uint32_t WALL_TILE_X = 64, WALL_TILE_Y = 32;
+struct WallArgs {
+  const float *floor, *ceiling;       // n x height x width each
+  uint16_t *dist2_out;                // n x height x width, or null
+  float *floor_out, *ceiling_out;     // n x height x width each, or both null
+  uint32_t width, height;
+  uint32_t tiles_x, tiles;            // tiles across a grid, tiles of a grid
+  uint32_t radius, close_d2;          // R in cells; D2 <= close_d2 is void in the output planes
+  uint32_t edge_open;                 // RDOOM_WALL_EDGE_OPEN: cells outside the grid do not block
+  float clearance;
+};
+
 }  // namespace rdoom_dev

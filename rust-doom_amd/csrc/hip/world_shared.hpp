@@ -155,7 +155,8 @@ __device__ __forceinline__ bool point_cell(const Grid &g, float cell, float x, f
 }
 
 // ---- walking on a grid of floor and ceiling planes (include/rdoom.h "goal distance": "Open", "Moves"), the one definition the
-// two floods (flood.hip) and the walk down their field (path.hip) share; the units that use them turn contraction off ----
+// two floods (flood.hip), the walk down their field (path.hip) and the wall distance (walls.hip, is_open alone) share; the units
+// that use them turn contraction off ----
 struct WalkLimits {
   float max_step, max_drop, clearance;
 };
