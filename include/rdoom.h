@@ -355,6 +355,18 @@ rdoom_status rdoom_batch_read_primitive_ids(rdoom_batch *batch, uint32_t first, 
  * [7] packed-vs-scalar mismatches.  [0], [1], [3], [7] must be 0. */
 rdoom_status rdoom_selftest_fastmath(uint64_t out_counts[8]);
 
+/* On-device evaluation of the project's sine and cosine (rust-doom_amd/csrc/hip/sincos_rd.hpp, the one every world-side kernel
+ * takes its yaw's from) for ALL 2^32 binary32 arguments, for a bit-for-bit comparison with a host restatement
+ * (tests/sincos_sweep.c, tests/test_gpu_sincos.py).  A binade is b = bits >> 23, sign and exponent together: 512 of them, 2^23
+ * arguments each.  out_sums[b] is the sum modulo 2^64, over the binade's arguments, of term(bits of x, bits of s, bits of c)
+ * with (s, c) = sincos(x), a NaN result replaced by the one pattern 0x7FC00000, and, in uint64_t arithmetic,
+ *   term(x, s, c):  h = x * 0x9E3779B97F4A7C15;  h ^= (s << 32) | c;  h ^= h >> 32;  h *= 0xD6E8FEB86659FD93;  h ^= h >> 32;
+ *                   h *= 0xD6E8FEB86659FD93;  h ^= h >> 32;  return h
+ * device_raw, if not NULL: device memory on the current device, aligned to 8 bytes, for 2^24 floats (64 MiB), which receives the
+ * results of binade raw_binade (< 512) as they are, NaNs included: (s, c) of the argument (raw_binade << 23) | m at floats 2m and
+ * 2m + 1.  Runs on the null stream and returns when the results are there; allocates 4 KiB of device memory for the call. */
+rdoom_status rdoom_selftest_sincos(uint64_t out_sums[512], uint32_t raw_binade, float *device_raw);
+
 /* Test hooks (no reference counterpart; the library never reads the environment).  Each option selects a differently
  * shaped but EQUIVALENT path through the kernels -- the image must not change -- so that the rarely taken ones can be
  * forced (tests/test_gpu_debug_paths.py).  Process-wide; read when a batch is created ("vis32", "entry_cap") or
@@ -489,7 +501,13 @@ rdoom_status rdoom_pose_from_player(const float pos[3], float yaw, float pitch, 
  * by WorldBuilder from the same level walk as the renderer's Builder (game/src/level.rs:378-382).  Here a rdoom_world holds
  * that volume on the host and the current device; N players step K ticks in ONE launch.
  * Arithmetic: binary32, no contraction, IEEE division and sqrt; the sine / cosine of yaw and pitch come from a project-owned
- * binary32 sincos (csrc/hip/world.hip), not the device libm, so a step is reproducible bit for bit on any IEEE host. */
+ * binary32 sincos (csrc/hip/sincos_rd.hpp), not the device libm, so a step is reproducible bit for bit on any IEEE host that
+ * takes the sincos's quadrant as the device's float-to-int conversion does (saturating; tests/sincos_restatement.h).
+ * The sincos's domain (rdoom_selftest_sincos; tests/test_sincos_host.py, tests/test_gpu_sincos.py): its bits are reproducible
+ * for every finite argument; its results are within 2 of the project's ulp measure for |x| < 512 (measured over every such
+ * argument: 1.562); from there the error grows -- 2.95 below 1024, 5.68 below 2048, 12.3 below 4096, 25.2 below 8192, the
+ * record is tests/golden/sincos_error.json -- and beyond 8192 no accuracy is promised.  The step computes yaw -= look.x and
+ * never wraps it: a caller that lets yaw grow stays inside this statement, with the accuracy of the yaw it has reached. */
 typedef struct rdoom_world rdoom_world;
 typedef struct rdoom_world_node {      /* world.rs:139-143 Node: partition Line2f + Child::pack'ed children (world.rs:152-163): */
   float origin[2], displace[2], length; /* > 0 a node index, <= 0 minus a chunk index; never linked = 0 = Leaf(0), as the reference */
@@ -518,7 +536,9 @@ typedef struct rdoom_world_arrays {
  * Orientation is (yaw, pitch), as rdoom_pose_from_player takes it.  flags: RDOOM_PLAYER_FLY / RDOOM_PLAYER_CLIP are the
  * caller's (the reference's defaults: fly off, clip on, player.rs:347-353); RDOOM_PLAYER_DIVERGED is set by a step in which
  * the collision loop ran 100 sweeps without settling -- the reference's error!("Failed to compute collisions.")
- * (player.rs:162-165) -- and is never cleared by the library. */
+ * (player.rs:162-165) -- and is never cleared by the library.
+ * yaw is not wrapped, by the step or by anything else: every kernel takes its sine and cosine as they are, reproducible for every
+ * finite yaw, within 2 of the ulp measure for |yaw| < 512 and degrading beyond (the domain statement above, at the step). */
 #define RDOOM_PLAYER_FLY 1u
 #define RDOOM_PLAYER_CLIP 2u
 #define RDOOM_PLAYER_DIVERGED 0x100u

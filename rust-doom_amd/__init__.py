@@ -187,7 +187,7 @@ API_SYMBOLS = [
     'rdoom_world_reveal_area', 'rdoom_worldset_reveal_area', 'rdoom_world_draw_area_maps', 'rdoom_worldset_draw_area_maps',
     'rdoom_world_draw_area_planes', 'rdoom_worldset_draw_area_planes', 'rdoom_flood_grid_max_cells', 'rdoom_flood_grids',
     'rdoom_world_area_cells', 'rdoom_worldset_area_cells', 'rdoom_flood_descend', 'rdoom_world_area_frontiers',
-    'rdoom_worldset_area_frontiers', 'rdoom_wall_distance']
+    'rdoom_worldset_area_frontiers', 'rdoom_wall_distance', 'rdoom_selftest_sincos']
 
 _lib = None
 
@@ -263,6 +263,25 @@ def selftest_fastmath():
     keys = ('rcp_mismatches', 'div09_mismatches', 'inputs_swept', 'mod_violations', 'mod_samples', 'mod_certified',
             'mod_floor_differs', 'packed_mismatches')
     return dict(zip(keys, [int(x) for x in out]))
+
+
+def selftest_sincos(raw_binade=None, raw_out=None):
+    """rdoom_selftest_sincos: the device's sincos over all 2^32 binary32 arguments.  Returns the 512 per-binade sums (uint64; a
+    binade is bits >> 23; include/rdoom.h states the sum).  With raw_binade and raw_out -- a contiguous float32 torch tensor of
+    2^24 elements on the current device, or a device pointer -- binade raw_binade's (s, c) pairs are written there as well."""
+    sums = np.zeros(512, np.uint64)
+    if (raw_binade is None) != (raw_out is None):
+        raise ValueError('raw_binade and raw_out go together')
+    ptr = None
+    if raw_out is not None:
+        if hasattr(raw_out, 'data_ptr'):
+            if not (raw_out.is_cuda and raw_out.is_contiguous() and raw_out.element_size() == 4 and raw_out.numel() >= 1 << 24):
+                raise ValueError('raw_out must be a contiguous device tensor of at least 2^24 float32')
+            ptr = ctypes.c_void_p(raw_out.data_ptr())
+        else:
+            ptr = ctypes.c_void_p(int(raw_out))
+    _check(lib().rdoom_selftest_sincos(sums.ctypes.data_as(ctypes.c_void_p), int(raw_binade or 0), ptr))
+    return sums
 
 
 def wad_name(value):

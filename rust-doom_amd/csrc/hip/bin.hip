@@ -157,7 +157,8 @@ __global__ __launch_bounds__(BIN_THREADS, BIN_OCC) void bin_kernel(const TriRec 
           }
         }
         nt = (tx1 >= tx0 && ty1 >= ty0) ? (uint32_t)((tx1 - tx0 + 1) * (ty1 - ty0 + 1)) : 0u;
-        trange[tid] = (uint32_t)tx0 | ((uint32_t)ty0 << 8) | ((uint32_t)(tx1 - tx0 + 1) << 16);  // tiles per side <= 128
+        // tiles per side <= 256: tx0, ty0 <= 255 fill their 8 bits, the count has 16
+        trange[tid] = (uint32_t)tx0 | ((uint32_t)ty0 << 8) | ((uint32_t)(tx1 - tx0 + 1) << 16);
       }
       const uint32_t incl = block_scan<BIN_THREADS>(nt, scan_tmp);  // inclusive prefix of nt over the workgroup
       pref[tid] = incl - nt;                                        // exclusive; entries past cn repeat the total
@@ -195,8 +196,10 @@ __global__ __launch_bounds__(BIN_THREADS, BIN_OCC) void bin_kernel(const TriRec 
             const int x0 = (int)(bb.x & 0xFFFFu), y0 = (int)(bb.x >> 16), x1 = (int)(bb.y & 0xFFFFu), y1 = (int)(bb.y >> 16);
             const uint32_t tr = trange[lo[u]];
             const int tx0 = (int)(tr & 0xFFu), ty0 = (int)((tr >> 8) & 0xFFu), ntx = (int)(tr >> 16);
-            // t / ntx for t < 8192, ntx <= 128: (t + 0.5) / ntx lies at least 1 / 256 away from an integer and v_rcp_f32's error
-            // (one ulp) moves the product by less than 8192.5 * 2^-22 < 1 / 256: exact without the IEEE division's dozen instructions
+            // t / ntx for t < 8192, ntx <= 256: q = (t + 0.5) / ntx lies at least 1 / (2 ntx) >= 1 / 512 away from an integer, and
+            // v_rcp_f32's error (one ulp) and the product's rounding (half an ulp) move it by less than q * 2^-22 <=
+            // 8192.5 * 2^-22 / ntx, 250 times less than 1 / (2 ntx) for every ntx: exact without the IEEE division's dozen
+            // instructions (selftest sweep 4 tries every pair)
             const int ty = (int)(((float)t + 0.5f) * __builtin_amdgcn_rcpf((float)ntx)), tx = (int)t - ty * ntx;
             const uint4 c0 = coef[lo[u]][0], c1 = coef[lo[u]][1], c2 = coef[lo[u]][2];
             // (no whole-tile test first: a quadrant's corner values ask for no less than the tile's, so the mask is zero wherever

@@ -6,14 +6,19 @@
 //            mod_cert(x, r, y) must imply floor(x * RN(1/y)) == floor(x / y)
 //   sweep 3  v_pk_fma_f32 / v_pk_mul_f32 / v_pk_add_f32 == scalar fmaf / * / + on pseudo-random operands
 //   sweep 4  the binning kernel's pair -> tile row: (int)((t + 0.5f) * v_rcp_f32(ntx)) == t / ntx for every t < 8192,
-//            1 <= ntx <= 128 (bin.hip; mismatches are added to sweep 3's count)
+//            1 <= ntx <= 256 (bin.hip: a frame is at most 16384 pixels = 256 tiles wide; mismatches are added to sweep 3's count)
 // Takes a few seconds on an MI355X; used by tests/test_gpu_fastmath.py.
+//
+// rdoom_selftest_sincos: sincos_rd (sincos_rd.hpp) evaluated for every one of the 2^32 binary32 arguments, summed per binade
+// (include/rdoom.h states the sum), and one binade's raw results on request.  The host side of the comparison is
+// tests/sincos_sweep.c; used by tests/test_gpu_sincos.py.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "../common.hpp"
 #include "fastmath.hpp"
+#include "sincos_rd.hpp"
 
 #pragma clang fp contract(off)
 
@@ -116,7 +121,7 @@ __global__ void sweep_packed(unsigned long long *out) {  // out[7] mismatches
 }
 
 __global__ void sweep_tile_index(unsigned long long *out) {  // out[7] += mismatches
-  const uint32_t ntx = blockIdx.x + 1u;  // 1..128
+  const uint32_t ntx = blockIdx.x + 1u;  // 1..256
   unsigned long long n = 0;
   for (uint32_t t = threadIdx.x; t < 8192u; t += blockDim.x) {
     const int ty = (int)(((float)t + 0.5f) * __builtin_amdgcn_rcpf((float)ntx));
@@ -125,7 +130,63 @@ __global__ void sweep_tile_index(unsigned long long *out) {  // out[7] += mismat
   if (n) atomicAdd(&out[7], n);
 }
 
+constexpr uint32_t kBinades = 512u, kBinadeSize = 1u << 23, kSincosBlocksPerBinade = 64u, kSincosThreads = 256u;
+
+__device__ __forceinline__ uint32_t canonical_bits(float f) { return f != f ? 0x7FC00000u : __float_as_uint(f); }
+
+// the term of include/rdoom.h's sum
+__device__ __forceinline__ uint64_t sincos_term(uint32_t x, uint32_t s, uint32_t c) {
+  uint64_t h = (uint64_t)x * 0x9E3779B97F4A7C15ull;
+  h ^= ((uint64_t)s << 32) | c;
+  h ^= h >> 32;
+  h *= 0xD6E8FEB86659FD93ull;
+  h ^= h >> 32;
+  h *= 0xD6E8FEB86659FD93ull;
+  h ^= h >> 32;
+  return h;
+}
+
+// grid: kBinades * kSincosBlocksPerBinade blocks of kSincosThreads; a block takes every kSincosBlocksPerBinade-th run of
+// kSincosThreads mantissas of its binade.  raw (or null): 2 * kBinadeSize floats, the (s, c) pairs of binade raw_binade by mantissa.
+__global__ void __launch_bounds__(kSincosThreads) sweep_sincos(unsigned long long *sums, uint32_t raw_binade, float2 *raw) {
+  const uint32_t binade = blockIdx.x / kSincosBlocksPerBinade, part = blockIdx.x % kSincosBlocksPerBinade;
+  const bool keep = raw != nullptr && binade == raw_binade;
+  uint64_t sum = 0;
+  for (uint32_t m = part * kSincosThreads + threadIdx.x; m < kBinadeSize; m += kSincosBlocksPerBinade * kSincosThreads) {
+    const uint32_t bits = (binade << 23) | m;
+    float s, c;
+    rdoom_dev::sincos_rd(__uint_as_float(bits), s, c);
+    if (keep) raw[m] = float2{s, c};  // m < kBinadeSize: inside the caller's 2 * kBinadeSize floats
+    sum += sincos_term(bits, canonical_bits(s), canonical_bits(c));
+  }
+  __shared__ unsigned long long block_sum;
+  if (threadIdx.x == 0) block_sum = 0;
+  __syncthreads();
+  atomicAdd(&block_sum, (unsigned long long)sum);
+  __syncthreads();
+  if (threadIdx.x == 0) atomicAdd(&sums[binade], block_sum);  // binade < kBinades by the grid's size
+}
+
 }  // namespace
+
+extern "C" rdoom_status rdoom_selftest_sincos(uint64_t out_sums[512], uint32_t raw_binade, float *device_raw) {
+  if (!out_sums) return rdoom::fail(RDOOM_BAD_ARG, "out_sums is null");
+  if (device_raw && raw_binade >= kBinades) return rdoom::fail(RDOOM_BAD_ARG, "raw_binade %u is not below 512", raw_binade);
+  if (device_raw && ((uintptr_t)device_raw & 7u)) return rdoom::fail(RDOOM_BAD_ARG, "device_raw is not aligned to 8 bytes");
+  unsigned long long *d = nullptr;
+  hipError_t e = hipMalloc((void **)&d, kBinades * sizeof(unsigned long long));
+  if (e == hipSuccess) e = hipMemset(d, 0, kBinades * sizeof(unsigned long long));
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(sweep_sincos, dim3(kBinades * kSincosBlocksPerBinade), dim3(kSincosThreads), 0, nullptr, d, raw_binade,
+                       (float2 *)device_raw);
+    e = hipGetLastError();
+  }
+  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the sums are copied as they are");
+  if (e == hipSuccess) e = hipMemcpy(out_sums, d, kBinades * sizeof(uint64_t), hipMemcpyDeviceToHost);
+  if (d) (void)hipFree(d);
+  if (e != hipSuccess) return rdoom::fail(RDOOM_HIP_ERROR, "sincos selftest failed: %s", hipGetErrorString(e));
+  return RDOOM_OK;
+}
 
 extern "C" rdoom_status rdoom_selftest_fastmath(uint64_t out_counts[8]) {
   if (!out_counts) return rdoom::fail(RDOOM_BAD_ARG, "out_counts is null");
@@ -136,7 +197,7 @@ extern "C" rdoom_status rdoom_selftest_fastmath(uint64_t out_counts[8]) {
     hipLaunchKernelGGL(sweep_div, dim3(4096), dim3(256), 0, nullptr, d);
     hipLaunchKernelGGL(sweep_mod, dim3(4096), dim3(256), 0, nullptr, d);
     hipLaunchKernelGGL(sweep_packed, dim3(1024), dim3(256), 0, nullptr, d);
-    hipLaunchKernelGGL(sweep_tile_index, dim3(128), dim3(256), 0, nullptr, d);
+    hipLaunchKernelGGL(sweep_tile_index, dim3(256), dim3(256), 0, nullptr, d);
     e = hipGetLastError();
   }
   unsigned long long h[8] = {};

@@ -33,7 +33,7 @@ def lib():
     global _lib
     with _lock:
         if _lib is None:
-            L = restatement_lib(SRC)
+            L = restatement_lib(SRC, [os.path.join(HERE, 'sincos_restatement.h')])
             v, u, f = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_float
             L.ar_grid.restype = ctypes.c_int
             L.ar_grid.argtypes = [v, u, f, v]
@@ -143,15 +143,21 @@ def popcount(words):
 
 
 def sincos(x):
-    """the project's sincos in numpy float32, operation for operation (csrc/hip/sincos_rd.hpp, as the restatements write it out)"""
-    x = F(x)
-    k = np.floor(x * F(0.636619772) + F(0.5))
-    r = ((x - k * F(1.5703125)) - k * F(4.837512969970703125e-4)) - k * F(7.54978995489188216e-8)
-    z = r * r
-    ps = ((F(-1.9515295891e-4) * z + F(8.3321608736e-3)) * z - F(1.6666654611e-1)) * z * r + r
-    pc = ((F(2.443315711809948e-5) * z - F(1.388731625493765e-3)) * z + F(4.166664568298827e-2)) * z * z - F(0.5) * z + F(1.0)
-    q = int(k) & 3
-    return [(ps, pc), (pc, -ps), (-ps, -pc), (-pc, ps)][q]
+    """the project's sincos in numpy float32, operation for operation (csrc/hip/sincos_rd.hpp, as tests/sincos_restatement.h writes
+    it out), of a scalar or an array: (s, c).  The quadrant is taken as gfx950's conversion gives it -- saturated at INT_MIN and
+    INT_MAX, 0 for a NaN -- so every bit pattern has a result."""
+    x = np.asarray(x, F)
+    with np.errstate(all='ignore'):  # (inf and NaN go through like any argument)
+        k = np.floor(x * F(0.636619772) + F(0.5))
+        r = ((x - k * F(1.5703125)) - k * F(4.837512969970703125e-4)) - k * F(7.54978995489188216e-8)
+        z = r * r
+        ps = ((F(-1.9515295891e-4) * z + F(8.3321608736e-3)) * z - F(1.6666654611e-1)) * z * r + r
+        pc = ((F(2.443315711809948e-5) * z - F(1.388731625493765e-3)) * z + F(4.166664568298827e-2)) * z * z - F(0.5) * z + F(1.0)
+        in_range = np.abs(k) < F(2147483648.0)  # (false for a NaN)
+        q = np.where(in_range, np.where(in_range, k, F(0.0)).astype(np.int64) & 3, np.where(k >= F(2147483648.0), 3, 0))
+        s = np.select([q == 0, q == 1, q == 2], [ps, pc, -ps], -pc)
+        c = np.select([q == 0, q == 1, q == 2], [pc, -ps, -pc], ps)
+    return (F(s), F(c)) if x.ndim == 0 else (s, c)
 
 
 def bands(g, cell, states, fan, max_range):

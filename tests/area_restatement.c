@@ -3,8 +3,8 @@
  * its nearest blocking hit -- nothing is culled -- and then every one of its n_steps + 1 samples is taken in turn, into planes of one
  * byte per cell of the whole grid, which are packed into the caller's words at the end: no window, no bands, no chunks.  It reads
  * the HOST line table (rdoom_map_line records as rdoom_world_map_lines lends them) and derives the grid from it with its own
- * formulas.  The sine and cosine of the yaw are written out here on their own (the project's sincos: Cody-Waite reduction by pi/2
- * in three parts, the Cephes sinf / cosf polynomials).
+ * formulas.  The sine and cosine of the yaw are the restatements' one definition of the project's sincos
+ * (tests/sincos_restatement.h).
  * Built by the tests like the other restatements (tests/area_ref.py): gcc -O2 -ffp-contract=off -fno-fast-math. */
 #include <math.h>
 #include <stddef.h>
@@ -12,21 +12,11 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "sincos_restatement.h"
 typedef struct { uint32_t present; float floor, ceiling; uint32_t floor_id, ceiling_id; } ar_side;
 typedef struct { uint32_t linedef; float a[2], b[2]; uint32_t flags, special; ar_side front, back; } ar_line;
 typedef struct { float pos[3], vel[3], yaw, pitch, last_height_diff; uint32_t flags; } ar_state;
 typedef struct { int32_t ix0, iz0; uint32_t gw, gh, pitch, words; } ar_grid_t;
-
-static void ar_sincos(float x, float *sn, float *cs) {
-  float k = floorf(x * 0.636619772f + 0.5f);
-  float r = ((x - k * 1.5703125f) - k * 4.837512969970703125e-4f) - k * 7.54978995489188216e-8f;
-  float z = r * r;
-  float ps = ((-1.9515295891e-4f * z + 8.3321608736e-3f) * z - 1.6666654611e-1f) * z * r + r;
-  float pc = ((2.443315711809948e-5f * z - 1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z * z - 0.5f * z + 1.0f;
-  int q = (int)k & 3;
-  *sn = q == 0 ? ps : (q == 1 ? pc : (q == 2 ? -ps : -pc));
-  *cs = q == 0 ? pc : (q == 1 ? -ps : (q == 2 ? -pc : ps));
-}
 
 static float ar_live(float height, uint32_t object, const float *off, uint32_t n_objects) {
   float by = 0.0f;
@@ -122,7 +112,7 @@ void ar_reveal(const ar_line *lines, uint32_t n_lines, const uint32_t *ranges, c
     if (wall_witness)
       for (size_t k = 0; k < cells; k++) wall_witness[(size_t)p * witness_stride + k] = 0xFFFFFFFFu;
     float sn, cs;
-    ar_sincos(st[p].yaw, &sn, &cs);
+    sincos_restated(st[p].yaw, &sn, &cs);
     float ox = st[p].pos[0], oz = st[p].pos[2];
     for (uint32_t r = 0; r < n_rays; r++) {
       float right = dirs[2 * r], forward = dirs[2 * r + 1];
@@ -184,7 +174,7 @@ void ar_draw(const ar_line *lines, uint32_t n_lines, const uint32_t *ranges, con
     ar_grid_t g;
     if (!ar_grid(mine, n_mine, cell, &g)) continue;
     float sn, cs;
-    ar_sincos(st[p].yaw, &sn, &cs);
+    sincos_restated(st[p].yaw, &sn, &cs);
     float px = st[p].pos[0], pz = st[p].pos[2];
     float hw = (float)width * 0.5f, hh = (float)height * 0.5f;
     const uint32_t *free_row = area + (size_t)p * 2 * stride, *wall_row = free_row + stride;

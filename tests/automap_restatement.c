@@ -1,8 +1,8 @@
 /* Test-side restatement of the top-down map (include/rdoom.h "top-down maps"; the product's is
  * rust-doom_amd/csrc/hip/automap.hip), in binary32, sharing no code with the product and none of its shape: every line of the
  * level is tried against every pixel, nothing is culled, nothing is chunked.  It reads the HOST line table (rdoom_map_line records
- * as rdoom_world_map_lines lends them), not the kernel's arrays.  The sine and cosine of the yaw are written out here on their own
- * (the project's sincos: Cody-Waite reduction by pi/2 in three parts, the Cephes sinf / cosf polynomials).
+ * as rdoom_world_map_lines lends them), not the kernel's arrays.  The sine and cosine of the yaw are the restatements' one definition of
+ * the project's sincos (tests/sincos_restatement.h).
  * Built by the tests like the other restatements (tests/automap_ref.py): gcc -O2 -ffp-contract=off -fno-fast-math. */
 #include <math.h>
 #include <stddef.h>
@@ -10,6 +10,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "sincos_restatement.h"
 typedef struct { uint32_t present; float floor, ceiling; uint32_t floor_id, ceiling_id; } am_side;
 typedef struct { uint32_t linedef; float a[2], b[2]; uint32_t flags, special; am_side front, back; } am_line;
 typedef struct { float pos[3], vel[3], yaw, pitch, last_height_diff; uint32_t flags; } am_state;
@@ -17,20 +18,6 @@ typedef struct { uint32_t width, height; float scale, half_width, marker; uint32
 
 enum { AM_ROTATE = 1, AM_SHOW_FLAT = 2, AM_SHOW_HIDDEN = 4, AM_TOP_DOWN = 8 };
 enum { AM_NONE = 0, AM_FLAT = 1, AM_CEILING_STEP = 2, AM_FLOOR_STEP = 3, AM_CLOSED = 4, AM_ONE_SIDED = 5, AM_PLAYER = 8 };
-
-static void am_sincos(float x, float *sn, float *cs) {
-  float turns = floorf(x * 0.636619772f + 0.5f);
-  float rem = ((x - turns * 1.5703125f) - turns * 4.837512969970703125e-4f) - turns * 7.54978995489188216e-8f;
-  float sq = rem * rem;
-  float sine = ((-1.9515295891e-4f * sq + 8.3321608736e-3f) * sq - 1.6666654611e-1f) * sq * rem + rem;
-  float cosine = ((2.443315711809948e-5f * sq - 1.388731625493765e-3f) * sq + 4.166664568298827e-2f) * sq * sq - 0.5f * sq + 1.0f;
-  switch ((int)turns & 3) {
-    case 0: *sn = sine, *cs = cosine; break;
-    case 1: *sn = cosine, *cs = -sine; break;
-    case 2: *sn = -sine, *cs = -cosine; break;
-    default: *sn = -cosine, *cs = sine; break;
-  }
-}
 
 /* the contract's dist2 in its two halves: what depends on the segment a -> b alone (ok: it has a length), and the squared
  * distance of (qx, qz) from it */
@@ -121,7 +108,7 @@ void am_draw(const am_line *lines, uint32_t n_lines, const uint32_t *ranges, con
       cls[drawn++] = (uint8_t)c;
     }
     float sn, cs;
-    am_sincos(st[p].yaw, &sn, &cs);
+    sincos_restated(st[p].yaw, &sn, &cs);
     float mark = v->marker * v->scale;
     am_seg tip = am_segment(st[p].pos[0], st[p].pos[2], st[p].pos[0] + (-sn) * (2.0f * mark), st[p].pos[2] + (-cs) * (2.0f * mark));
     for (uint32_t row = 0; row < v->height; row++) {
@@ -151,7 +138,7 @@ void am_draw(const am_line *lines, uint32_t n_lines, const uint32_t *ranges, con
 /* the world points of a player's pixels, for the test of the axes: out 2 floats (x, z) per pixel, rows as in the map */
 void am_points(const am_view *v, const am_state *st, float *out) {
   float sn, cs;
-  am_sincos(st->yaw, &sn, &cs);
+  sincos_restated(st->yaw, &sn, &cs);
   for (uint32_t row = 0; row < v->height; row++)
     for (uint32_t i = 0; i < v->width; i++) {
       uint32_t j = (v->flags & AM_TOP_DOWN) ? v->height - 1 - row : row;

@@ -19,7 +19,7 @@ def lib():
     global _lib
     with _lock:
         if _lib is None:
-            L = restatement_lib(SRC, [os.path.join(HERE, 'world_restatement.c')])
+            L = restatement_lib(SRC, [os.path.join(HERE, 'world_restatement.c'), os.path.join(HERE, 'sincos_restatement.h')])
             L.fr_cameras.restype = None
             L.fr_cameras.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint32,
                                      ctypes.c_void_p, ctypes.c_void_p]

@@ -27,7 +27,7 @@ def lib():
     global _lib
     with _lock:
         if _lib is None:
-            L = restatement_lib(SRC, [world_ref.SRC])
+            L = restatement_lib(SRC, [world_ref.SRC, os.path.join(HERE, 'sincos_restatement.h')])
             L.rs_game_step.restype = None
             L.rs_game_step.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_uint32] + [ctypes.c_void_p] * 4 + [ctypes.c_uint32] * 4 + \
                 [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 4

@@ -33,10 +33,14 @@ def main():
     fb, prim = batch.read_framebuffer(), batch.read_primitive_ids()
     ro = raster.RasterOracle(lv)
     bad = 0
+    corner = w * h  # the fewest pixels of geometry any pose shows in the frame's last tile (last tile column and last tile row)
+    x0, y0 = (w - 1) // 64 * 64, (h - 1) // 64 * 64
     for i in range(n):
         ofb, oprim = ro.render(poses[i]['modelview'], poses[i]['projection'], 0.4, lights, w, h, want_prim=True)
         bad += int((ofb != fb[i]).sum()) + int((oprim != prim[i]).sum()) + int((ofb != fb_plain[i]).sum())
+        corner = min(corner, int((oprim[y0:, x0:] != 0xFFFFFFFF).sum()))
     print('RESULT bad=%d fixups=%d' % (bad, t['fixup_pixels']))
+    print('COVER last_tile=%d' % corner)
     return 0 if bad == 0 else 1
 
 

@@ -23,7 +23,7 @@ def lib():
     global _lib
     with _lock:
         if _lib is None:
-            L = restatement_lib(SRC, [world_ref.SRC])
+            L = restatement_lib(SRC, [world_ref.SRC, os.path.join(HERE, 'sincos_restatement.h')])
             v, u = ctypes.c_void_p, ctypes.c_uint32
             L.ry_cast.restype = None
             L.ry_cast.argtypes = [v, v, u, u, u, v, u, ctypes.c_float, v, u, v, v, v, v, v, v]

@@ -28,7 +28,7 @@ def lib():
     global _lib
     with _lock:
         if _lib is None:
-            L = restatement_lib(SRC)
+            L = restatement_lib(SRC, [os.path.join(HERE, 'sincos_restatement.h')])
             v, u = ctypes.c_void_p, ctypes.c_uint32
             L.rv_reveal.restype = None
             L.rv_reveal.argtypes = [v, u, v, v, u, v, u, u, u, v, u, ctypes.c_float, v, u, v, u, v, v, v, v, v, v, u]

@@ -2,30 +2,20 @@
  * binary32, sharing no code with the product and none of its shape: for every player, every ray meets every line of the level,
  * twice -- once for the nearest blocking hit, once for the lines seen up to it -- nothing is culled, staged or skipped, and bits
  * already set are tested like any other.  It reads the HOST line table (rdoom_map_line records as rdoom_world_map_lines lends
- * them).  The sine and cosine of the yaw are written out here on their own (the project's sincos: Cody-Waite reduction by pi/2 in
- * three parts, the Cephes sinf / cosf polynomials).
+ * them).  The sine and cosine of the yaw are the restatements' one definition of the project's sincos
+ * (tests/sincos_restatement.h).
  * Built by the tests like the other restatements (tests/reveal_ref.py): gcc -O2 -ffp-contract=off -fno-fast-math. */
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "sincos_restatement.h"
 typedef struct { uint32_t present; float floor, ceiling; uint32_t floor_id, ceiling_id; } rv_side;
 typedef struct { uint32_t linedef; float a[2], b[2]; uint32_t flags, special; rv_side front, back; } rv_line;
 typedef struct { float pos[3], vel[3], yaw, pitch, last_height_diff; uint32_t flags; } rv_state;
 
 enum { RV_STOP_RANGE = 0, RV_STOP_ONE_SIDED = 1, RV_STOP_TWO_SIDED = 2 };
-
-static void rv_sincos(float x, float *sn, float *cs) {
-  float k = floorf(x * 0.636619772f + 0.5f);
-  float r = ((x - k * 1.5703125f) - k * 4.837512969970703125e-4f) - k * 7.54978995489188216e-8f;
-  float z = r * r;
-  float ps = ((-1.9515295891e-4f * z + 8.3321608736e-3f) * z - 1.6666654611e-1f) * z * r + r;
-  float pc = ((2.443315711809948e-5f * z - 1.388731625493765e-3f) * z + 4.166664568298827e-2f) * z * z - 0.5f * z + 1.0f;
-  int q = (int)k & 3;
-  *sn = q == 0 ? ps : (q == 1 ? pc : (q == 2 ? -ps : -pc));
-  *cs = q == 0 ? pc : (q == 1 ? -ps : (q == 2 ? -pc : ps));
-}
 
 static float rv_live(float height, uint32_t object, const float *off, uint32_t n_objects) {
   float by = 0.0f;
@@ -78,7 +68,7 @@ void rv_reveal(const rv_line *lines, uint32_t n_lines, const uint32_t *ranges, c
     if (witness_ray)
       for (uint32_t l = 0; l < n_mine; l++) witness_ray[(size_t)p * witness_stride + l] = 0xFFFFFFFFu;
     float sn, cs;
-    rv_sincos(st[p].yaw, &sn, &cs);
+    sincos_restated(st[p].yaw, &sn, &cs);
     float ox = st[p].pos[0], oz = st[p].pos[2];
     for (uint32_t r = 0; r < n_rays; r++) {
       float right = dirs[2 * r], forward = dirs[2 * r + 1];

@@ -32,7 +32,7 @@ def lib():
     global _lib
     with _lock:
         if _lib is None:
-            L = restatement_lib(SRC)
+            L = restatement_lib(SRC, [os.path.join(HERE, 'sincos_restatement.h')])
             v, u = ctypes.c_void_p, ctypes.c_uint32
             L.sr_points.restype = None
             L.sr_points.argtypes = [v, v, u, v]

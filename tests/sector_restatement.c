@@ -2,12 +2,13 @@
  * binary32, sharing no code with the product and none of its shape: every point goes down from the root on its own, node by node,
  * through the HOST arrays as the library lends them (rdoom_world_node records of rdoom_world_host_arrays, the tables of
  * rdoom_world_map_sectors) -- no packed children, no precomputed constant, no wave, no tile.  The pixel's point is the map
- * contract's, written out as tests/automap_restatement.c writes it, with the same sincos of its own.
+ * contract's, written out as tests/automap_restatement.c writes it, with the restatements' sincos (tests/sincos_restatement.h).
  * Built by the tests like the other restatements (tests/sector_ref.py): gcc -O2 -ffp-contract=off -fno-fast-math. */
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
 
+#include "sincos_restatement.h"
 #define SR_NONE 0xFFFFFFFFu
 #define SR_NONE16 0xFFFFu
 
@@ -27,20 +28,6 @@ typedef struct { float pos[3], vel[3], yaw, pitch, last_height_diff; uint32_t fl
 typedef struct { uint32_t width, height; float scale, half_width, marker; uint32_t flags; } sr_view;
 
 enum { SR_ROTATE = 1, SR_TOP_DOWN = 8 };
-
-static void sr_sincos(float x, float *sn, float *cs) {
-  float turns = floorf(x * 0.636619772f + 0.5f);
-  float rem = ((x - turns * 1.5703125f) - turns * 4.837512969970703125e-4f) - turns * 7.54978995489188216e-8f;
-  float sq = rem * rem;
-  float sine = ((-1.9515295891e-4f * sq + 8.3321608736e-3f) * sq - 1.6666654611e-1f) * sq * rem + rem;
-  float cosine = ((2.443315711809948e-5f * sq - 1.388731625493765e-3f) * sq + 4.166664568298827e-2f) * sq * sq - 0.5f * sq + 1.0f;
-  switch ((int)turns & 3) {
-    case 0: *sn = sine, *cs = cosine; break;
-    case 1: *sn = cosine, *cs = -sine; break;
-    case 2: *sn = -sine, *cs = -cosine; break;
-    default: *sn = -cosine, *cs = sine; break;
-  }
-}
 
 /* the sector at (qx, qz): the descent from the root, the void rule, the NaN rule */
 static uint32_t sr_sector_at(const sr_level *lv, float qx, float qz) {
@@ -133,7 +120,7 @@ void sr_draw(const sr_level *levels, uint32_t n_slots, const uint32_t *level_of,
     const sr_level *lv = sr_level_of(levels, n_slots, level_of, p);
     const float *off = offsets ? offsets + (size_t)p * n_objects * 3 : NULL;
     float sn, cs;
-    sr_sincos(st[p].yaw, &sn, &cs);
+    sincos_restated(st[p].yaw, &sn, &cs);
     for (uint32_t row = 0; row < v->height; row++) {
       uint32_t j = (v->flags & SR_TOP_DOWN) ? v->height - 1 - row : row;
       for (uint32_t i = 0; i < v->width; i++) {

@@ -40,6 +40,15 @@ def run_child(hooks, args=('0', '320', '200', '6')):
     return int(m.group(1)), int(m.group(2))
 
 
+def run_child_covering(args):
+    """run_child without hooks, for the frames that are about tile coordinates: (bad, pixels of geometry -- oracle primitive ids
+    that are not the void's -- which the pose shows in the frame's last tile, that of the last tile column and last tile row)"""
+    p = subprocess.run([sys.executable, os.path.join(HERE, 'gpu_child_case.py'), *args], cwd=HERE, capture_output=True, text=True, timeout=600)
+    m, c = re.search(r'RESULT bad=(\d+) fixups=(\d+)', p.stdout), re.search(r'COVER last_tile=(\d+)', p.stdout)
+    assert m and c, p.stdout + p.stderr
+    return int(m.group(1)), int(c.group(1))
+
+
 def test_forced_alpha_leak_fixups_do_not_change_the_image():
     bad, fixups = run_child({'leak_mod': 97})
     assert bad == 0
@@ -183,6 +192,27 @@ def test_frames_around_the_split_lists_tile_limit(size):
     them, a 6K frame (5 184 tiles) falls back to whole-tile lists and the rasteriser's instantiation without them"""
     bad, _ = run_child({}, ('0', str(size[0]), str(size[1]), '1'))
     assert bad == 0, size
+
+
+@pytest.mark.parametrize('level', ['0', '1'])
+@pytest.mark.parametrize('size', [(8256, 40), (16384, 64), (16322, 130), (64, 16384), (40, 8256)])
+def test_frames_up_to_256_tiles_a_side(size, level):
+    """the smallest frames that reach the tile coordinates above 128 (the binning kernel's pair -> tile row by reciprocal, the top
+    bit of its 8-bit tile fields): 129 tiles across (the first column index with that bit set), 256 x 1, 256 x 3 with a padded pitch
+    and a partial last column and row, and the same counts down a column.  E1M1's spawn view (level 0) fills every one of these
+    frames, and that is asserted: geometry is binned and rasterised in the last tile column and row.  E1M2 (level 1), the small
+    level, fills the tall frames and 16322 x 130 as well; seen across 8256 x 40 and 16384 x 64 its right end is the void, which then
+    has to come out clear after the other poses' render: tiles above column 128 that no triangle of the checked pose reaches."""
+    bad, covered = run_child_covering((level, str(size[0]), str(size[1]), '1'))
+    assert bad == 0, (size, level)
+    assert covered > 0 or (level == '1' and size in ((8256, 40), (16384, 64))), (size, level)
+
+
+def test_frame_above_the_binning_kernels_tile_limit():
+    """16384 x 2049 = 256 x 33 = 8448 tiles, the smallest frame above MAX_TILES = 8192: binning is skipped and every pose takes
+    the sorted-list rasteriser, with no hook; the pose shows geometry in the last tile, (255, 32)"""
+    bad, covered = run_child_covering(('1', '16384', '2049', '1'))
+    assert bad == 0 and covered > 0
 
 
 def test_child_case_plain():

@@ -78,7 +78,7 @@ def test_golden_poses_equal_the_oracle_composition(oracle_levels, index):
 
 
 @gpu
-@pytest.mark.parametrize('size', [(321, 200, 4), (1000, 520, 2), (1920, 1080, 2)])
+@pytest.mark.parametrize('size', [(321, 200, 4), (1000, 520, 2), (1920, 1080, 2), (16384, 40, 1)])
 def test_sweep_poses_at_odd_and_full_sizes(wad_path, oracle_levels, size):
     """321 x 200: padded row pitch, u16 rows that start on odd halfwords; 1000 x 520: an 8-pixel tail per row; 1920 x 1080: the
     bench size.  Each with a view from outside the level: geometry and the void in one frame."""

@@ -103,7 +103,7 @@ def outside_pose(lv, w, h, time):
     raise AssertionError('no view from outside the level shows both geometry and the void')
 
 
-@pytest.mark.parametrize('size', [(321, 200, 4), (1000, 520, 2), (1920, 1080, 2)])
+@pytest.mark.parametrize('size', [(321, 200, 4), (1000, 520, 2), (1920, 1080, 2), (16384, 40, 1)])
 def test_sweep_poses_at_odd_and_full_sizes(wad_path, oracle_levels, size):
     """321 x 200: padded row pitch (324), byte stores of RGB8 rows; 1000 x 520: a 8-pixel tail per row; 1920 x 1080: the bench size
     (poses of the seeded sweep bench.py times)"""

@@ -26,21 +26,22 @@ _restatements = {}
 _restatements_lock = threading.Lock()
 
 
-def restatement_lib(src, deps=()):
+def restatement_lib(src, deps=(), flags=(), tag=''):
     """tests/<name>.c, one of the C restatements, as a ctypes library (loaded once): compiled with gcc -O2 -ffp-contract=off
     -fno-fast-math into tests/_build/ when that is missing or older than `src` or one of `deps` (the sources it includes), or into a
-    temporary directory when the checkout is read-only"""
+    temporary directory when the checkout is read-only.  flags: further compiler flags, for a library of its own named by `tag`"""
     here = os.path.dirname(os.path.abspath(src))
-    name = os.path.splitext(os.path.basename(src))[0]
+    name = os.path.splitext(os.path.basename(src))[0] + tag
 
     def compile_to(out):
         os.makedirs(os.path.dirname(out), exist_ok=True)
         tmp = '%s.%d.tmp' % (out, os.getpid())
-        subprocess.check_call(['gcc', '-shared', '-fPIC', '-O2', '-ffp-contract=off', '-fno-fast-math', '-I', here, '-o', tmp, src, '-lm'])
+        subprocess.check_call(['gcc', '-shared', '-fPIC', '-O2', '-ffp-contract=off', '-fno-fast-math', *flags, '-I', here, '-o', tmp, src, '-lm'])
         os.replace(tmp, out)
 
     with _restatements_lock:
-        if src not in _restatements:
+        key = (src, tag)
+        if key not in _restatements:
             out = os.path.join(here, '_build', 'lib%s.so' % name)
             if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(d) for d in [src, *deps]):
                 try:
@@ -48,8 +49,8 @@ def restatement_lib(src, deps=()):
                 except OSError:  # a read-only checkout
                     out = os.path.join(tempfile.mkdtemp(prefix=name + '_'), 'lib%s.so' % name)
                     compile_to(out)
-            _restatements[src] = ctypes.CDLL(out)
-        return _restatements[src]
+            _restatements[key] = ctypes.CDLL(out)
+        return _restatements[key]
 
 
 def perspective(fovy_deg, aspect, near, far):

@@ -25,7 +25,7 @@ def lib():
     global _lib
     with _lock:
         if _lib is None:
-            L = restatement_lib(SRC)
+            L = restatement_lib(SRC, [os.path.join(HERE, 'sincos_restatement.h')])
             L.wb_new.restype = ctypes.c_void_p
             for name in ('wb_free', 'wb_leaf_end', 'wb_node_end', 'wb_build', 'wb_counts', 'wb_copy', 'rs_sweep', 'rs_step'):
                 getattr(L, name).restype = None

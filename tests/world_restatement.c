@@ -8,6 +8,8 @@
 #include <stdlib.h>
 #include <string.h>
 
+#include "sincos_restatement.h"
+
 typedef struct { float ox, oy, dx, dy, len; int32_t pos, neg; } node_t;  /* Node + packed children */
 typedef struct { uint32_t start, end; } chunk_t;
 typedef struct { uint32_t a, b, c, n; } tri_t;
@@ -332,25 +334,7 @@ void rs_sweep(const world_t *w, const float *spheres, const float *vels, uint32_
 }
 
 /* ---- sin / cos: Cody-Waite by pi/2 in three parts, then Cephes' sinf / cosf polynomials on [-pi/4, pi/4] ---------------- */
-void rs_sincos(float x, float *s, float *c) {
-  float j = floorf(x * 0.636619772f + 0.5f);
-  float r = x - j * 1.5703125f;
-  r = r - j * 4.837512969970703125e-4f;
-  r = r - j * 7.54978995489188216e-8f;
-  float z = r * r;
-  float sp = -1.9515295891e-4f * z + 8.3321608736e-3f;
-  sp = sp * z - 1.6666654611e-1f;
-  sp = sp * z * r + r;
-  float cp = 2.443315711809948e-5f * z - 1.388731625493765e-3f;
-  cp = cp * z + 4.166664568298827e-2f;
-  cp = cp * z * z - 0.5f * z + 1.0f;
-  switch ((int)j & 3) {
-    case 0: *s = sp, *c = cp; break;
-    case 1: *s = cp, *c = -sp; break;
-    case 2: *s = -sp, *c = -cp; break;
-    default: *s = -cp, *c = sp; break;
-  }
-}
+void rs_sincos(float x, float *s, float *c) { sincos_restated(x, s, c); }
 
 /* ---- Player::update ------------------------------------------------------------------------------------------------------- */
 typedef struct { float pos[3], vel[3], yaw, pitch, lhd; uint32_t flags; } pstate;
