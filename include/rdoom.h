@@ -18,6 +18,20 @@
  *     rdoom_batch_resolve_rgb / rdoom_batch_read_rgb turn them into the colours the reference's window shows: PLAYPAL 0 of
  *     the pose's level where a primitive was drawn, the GL clear colour RDOOM_CLEAR_R/G/B where none was.
  *   - a rdoom_level is immutable after create (shareable); a rdoom_batch is single-owner.
+ *
+ * Caller memory: alignment and extent
+ *   What the library asks of a device pointer, and what it does with the memory behind it (tests/test_gpu_caller_memory_*.py hold
+ *   it to this, with every pointer at the least alignment allowed here and guard bands around every array).  A device pointer
+ *   needs the alignment of its element and no more: 1 for bytes (frames, maps, masks, light tables given to a render), 2 for
+ *   16-bit planes and distances, 4 for float, int32_t and uint32_t data (times, offsets, fans, directions, seeds, counts, `seen`,
+ *   `area` and `visited` words, level slots, depth and primitive planes).  A record needs the alignment of its widest member:
+ *   4 for rdoom_player_state, rdoom_player_input and rdoom_pose.  The exceptions, each stated at its entry point and refused with
+ *   RDOOM_BAD_ARG where less is given: a game state (rdoom_world_game_bytes) needs 16 bytes, the light tables
+ *   rdoom_lightset_tables writes need 4, and rdoom_selftest_sincos' device_raw needs 8.  Rows and records are tight unless a
+ *   stride is an argument, so an array of records is aligned as its first record is and no better (pose 1 of an array of
+ *   136-byte rdoom_pose is 8 bytes off a 16-byte boundary).  The library writes the stated extent of every output -- the frames
+ *   [first, first + count) of a resolve, n players, n rows -- and not one byte outside it, in front or behind, and it writes to
+ *   no input; a record an entry point leaves alone (a player a mask excludes) keeps every byte.
  */
 #ifndef RDOOM_H
 #define RDOOM_H

@@ -51,7 +51,7 @@ using rdoom_dev::point_cell;
 struct AreaArgs {
   const rdoom_player_state *states;
   const float *offsets;  // n x n_objects x xyz, or null
-  const float2 *dirs;    // n_rays x (right, forward)
+  const float *dirs;     // n_rays x (right, forward): a caller's floats, dword aligned and no more
   uint32_t *area;        // n x 2 x stride words
   uint32_t *new_out;     // n x 2, or null
   const float4 *seg;
@@ -144,8 +144,8 @@ __device__ __forceinline__ void reveal_area_player(const AreaArgs &a, uint32_t p
     // the pass's rays, the longest of them (no hit lies farther from the player) and their largest components (no sample does)
     float len2 = 0.0f, ax = 0.0f, az = 0.0f;
     if (tid < nr) {
-      const float2 d = a.dirs[ray0 + tid];
-      const float dir_x = c * d.x + fx * d.y, dir_z = fx * d.x + fz * d.y;
+      const float dr = a.dirs[2 * (size_t)(ray0 + tid)], df = a.dirs[2 * (size_t)(ray0 + tid) + 1];
+      const float dir_x = c * dr + fx * df, dir_z = fx * dr + fz * df;
       const float vx = dir_x * a.max_range, vz = dir_z * a.max_range;
       rays[tid] = make_float4(vx, vz, 1.0f, 0.0f);
       len2 = vx * vx + vz * vz, ax = __builtin_fabsf(vx), az = __builtin_fabsf(vz);
@@ -411,7 +411,7 @@ rdoom_status reveal_args(const rdoom::MapSource &src, const char *noun, const rd
     return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the %s's %u objects", n_objects, noun, src.game_objects);
   if (n > 0x7FFFFFFFu) return rdoom::fail(RDOOM_BAD_ARG, "%u players: too many for one launch", n);
   const rdoom::MapDevice &d = *src.map;
-  a = AreaArgs{d_states, d_offsets, (const float2 *)d_dirs, d_area, d_new_out, d.seg, d.heights, d.ids, d.flags, n_objects, n_rays, stride, n_steps,
+  a = AreaArgs{d_states, d_offsets, d_dirs, d_area, d_new_out, d.seg, d.heights, d.ids, d.flags, n_objects, n_rays, stride, n_steps,
                max_range, cell};
   return RDOOM_OK;
 }

@@ -46,7 +46,7 @@ struct LocateArgs {
   const rdoom_player_state *states;
   const float *offsets;  // n x n_objects x xyz, or null
   uint32_t *sector_out;
-  float2 *heights_out;  // or null
+  float *heights_out;   // n x (floor, ceiling), or null: a caller's floats, dword aligned and no more
   uint32_t *visited;    // n rows of stride words, or null
   uint32_t *new_out;    // or null
   SectorTables t;
@@ -61,7 +61,10 @@ __device__ __forceinline__ void locate(const LocateArgs &a, uint32_t p, const Se
     s = sector_in_leaf(a.t, lv.leaf0 + descend(a.t.nodes + lv.node0, qx, qz), qx, qz);
   }
   a.sector_out[p] = s;
-  if (a.heights_out) a.heights_out[p] = live_heights(a.t, lv, s, a.offsets ? a.offsets + (size_t)p * a.n_objects * 3 : nullptr, a.n_objects);
+  if (a.heights_out) {
+    const float2 h = live_heights(a.t, lv, s, a.offsets ? a.offsets + (size_t)p * a.n_objects * 3 : nullptr, a.n_objects);
+    a.heights_out[2 * (size_t)p] = h.x, a.heights_out[2 * (size_t)p + 1] = h.y;
+  }
   uint32_t fresh = 0;
   if (a.visited && s < lv.n_sectors) {  // the row is this lane's alone
     uint32_t *word = a.visited + (size_t)p * a.stride + (s >> 5);
@@ -214,7 +217,7 @@ rdoom_status locate_args(const rdoom::MapSource &src, const char *noun, const rd
                          uint32_t *d_new_out, LocateArgs &a) {
   if (n && (!d_states || !d_sector_out)) return rdoom::fail(RDOOM_BAD_ARG, "null states or sector output with n = %u", n);
   if (rdoom_status s = check_rows(src, noun, d_offsets, n_objects, d_visited, stride)) return s;
-  a = LocateArgs{d_states, d_offsets, d_sector_out, (float2 *)d_heights_out, d_visited, d_new_out, tables(*src.sectors), n, n_objects, stride};
+  a = LocateArgs{d_states, d_offsets, d_sector_out, d_heights_out, d_visited, d_new_out, tables(*src.sectors), n, n_objects, stride};
   return RDOOM_OK;
 }
 
