@@ -565,7 +565,11 @@ typedef struct rdoom_player_input {
   float movement[2], look[2];
   uint32_t jump; /* != 0: held */
 } rdoom_player_input;
-/* player.rs:56-92 Config, the physics half */
+/* player.rs:56-92 Config, the physics half.  The domain the tests hold the steps to (tests/step_cases.py, every field moved by
+ * a quarter or more from its default, one at a time and all at once): every field finite; radius, height and spring_const_p > 0;
+ * the others >= 0.  Values outside it are not checked by the library: a step takes them as they are and computes what the
+ * reference's arithmetic gives.  (friction < move_force lets a walker start at all; a feet sphere at rest above the floor needs
+ * height > 17 / spring_const_p, and a head sphere above it 0.2 + height - 17 / spring_const_p > radius.) */
 typedef struct rdoom_player_config {
   float move_force, spring_const_p, spring_const_d, radius, height, air_drag, ground_drag, friction;
 } rdoom_player_config;
@@ -589,10 +593,14 @@ rdoom_status rdoom_world_sweep(const rdoom_world *world, const float *d_spheres,
 /* n_ticks ticks of Player::update (player.rs:359-408: force() with the feet probe and move_force, then clip() or noclip(),
  * then velocity += force * dt) for n_players players in one launch, asynchronous on `stream`.  d_states (device) is read and
  * written in place; d_inputs (device): n_ticks x n_players, entry [t * n_players + p] is player p's input at tick t.
- * cfg: NULL = rdoom_player_config_default.  dt: the tick (0 = 1/60, engine Tick's timestep).  d_object_offsets: as for
- * rdoom_world_sweep, per player (constant over the ticks).  The look update is yaw -= look.x,
- * pitch = clamp(pitch - look.y, +-(pi/2 - 1e-2)) -- in exact arithmetic the reference's quaternion composition
- * (player.rs:194-205).  Triggers, teleports and level changes are not simulated. */
+ * cfg: NULL = rdoom_player_config_default.  dt: the tick (0 or -0.0 = 1/60, engine Tick's timestep); a negative, infinite or
+ * NaN dt is RDOOM_BAD_ARG and queues nothing.  The tests cover cfg in the domain stated at rdoom_player_config and dt in
+ * [1/120, 1/30] or 0; values outside are not checked by the library.  (The spring of player.rs:302-305 makes the height's excess
+ * over the rest height a recurrence with the characteristic polynomial z^3 - 2 z^2 + (1 + p dt^2 + d dt) z - d dt, p and d
+ * the spring constants: where its largest root passes 1 -- the default config at dt = 1/30 -- a standing player's height no
+ * longer settles, in the reference as here.)  d_object_offsets: as for rdoom_world_sweep, per player (constant over the
+ * ticks).  The look update is yaw -= look.x, pitch = clamp(pitch - look.y, +-(pi/2 - 1e-2)) -- in exact arithmetic the
+ * reference's quaternion composition (player.rs:194-205).  Triggers, teleports and level changes are not simulated. */
 rdoom_status rdoom_world_step_players(const rdoom_world *world, rdoom_player_state *d_states, const rdoom_player_input *d_inputs,
                                       uint32_t n_players, uint32_t n_ticks, const rdoom_player_config *cfg, float dt,
                                       const float *d_object_offsets, uint32_t n_objects, void *stream);
@@ -662,7 +670,8 @@ rdoom_status rdoom_world_game_bytes(const rdoom_world *world, uint64_t *bytes_pe
 rdoom_status rdoom_world_game_reset(const rdoom_world *world, void *d_game, float *d_object_offsets, uint32_t n_objects, uint32_t n,
                                     const uint8_t *d_mask, void *stream);
 /* n_ticks game ticks (see above) for n_players players in one launch, asynchronous on `stream`; every pointer is device memory.
- * d_states, d_inputs, cfg, dt: as for rdoom_world_step_players.  d_actions: NULL (no action) or n_ticks x n_players bytes,
+ * d_states, d_inputs, cfg, dt: as for rdoom_world_step_players, the tested domain of cfg and dt and the refused dt included;
+ * dt is the tick of the physics and of the move effects alike.  d_actions: NULL (no action) or n_ticks x n_players bytes,
  * entry [t * n_players + p] = RDOOM_ACTION_NONE / PUSH / SHOOT of player p at tick t (any other value is no action).
  * d_game: n_players games (rdoom_world_game_bytes), read and written.  d_object_offsets: n_players x n_objects x xyz,
  * n_objects >= rdoom_world_trigger_arrays.n_objects; the step reads every entry (the collision sweeps) and writes only the y
@@ -715,7 +724,8 @@ rdoom_status rdoom_worldset_game_bytes(const rdoom_worldset *set, uint64_t *byte
  * Asynchronous on `stream`. */
 rdoom_status rdoom_worldset_game_reset(const rdoom_worldset *set, void *d_game, float *d_object_offsets, uint32_t n_objects,
                                        const uint32_t *d_levels, uint32_t n, const uint8_t *d_mask, void *stream);
-/* n_ticks game ticks for n_players players in one launch, asynchronous on `stream`; arguments as rdoom_world_step_game's, with
+/* n_ticks game ticks for n_players players in one launch, asynchronous on `stream`; arguments as rdoom_world_step_game's (cfg and
+ * dt: the domain the tests cover and the dt refused are rdoom_world_step_players'), with
  * d_game (rdoom_worldset_game_bytes per player) and n_objects >= rdoom_worldset_info's.  d_levels: n_players uint32 of device
  * memory, read and written: each player's slot, changed by the level change above.  A player whose slot is >= the set's size is
  * left untouched (state, game, offsets and slot).  K launches of one tick equal one launch of K ticks.  Captured into a graph,

@@ -10,6 +10,7 @@ import pytest
 import game_ref
 import rust_doom_amd as rd
 import world_ref
+from step_cases import floor_y as _floor_y, front as _front, game_script as _script, seed_players as _seed  # (moved there)
 from test_game_host import ORDER_A, ORDER_B, ordering_run, ordering_variant, patched_variant
 from util import META_PATH, ROOT, ensure_wad, render_checked
 
@@ -26,58 +27,6 @@ def patched(tmp_path_factory):
 def _u32(a):
     a = np.ascontiguousarray(a)
     return a.view(np.uint32).reshape(len(a), -1)
-
-
-def _front(trig, dist):
-    """a point `dist` in front of each trigger line's midpoint (the side its right sidedef faces; behind it for dist < 0) and the
-    yaw that looks at the line"""
-    mid = trig['origin'] + trig['displace'] * (trig['length'][:, None] * F(0.5))
-    normal = np.stack([-trig['displace'][:, 1], trig['displace'][:, 0]], 1)  # the right side in world coordinates
-    p = mid + normal * F(dist)
-    face = -normal * F(np.sign(dist))  # towards the line; forward = (-sin yaw, -cos yaw) in (x, z)
-    return p, np.arctan2(-face[:, 0], -face[:, 1]).astype(F)
-
-
-def _floor_y(ref, xz, top=10.0):
-    """the floor under each (x, z): a sweep down from just below the sector's ceiling is not known, so from several heights"""
-    n = len(xz)
-    best = np.full(n, np.nan, F)
-    for y0 in (-2.0, -1.0, 0.0, 1.0, 2.0, 3.0):
-        sph = np.zeros((n, 4), F)
-        sph[:, 0], sph[:, 1], sph[:, 2], sph[:, 3] = xz[:, 0], y0, xz[:, 1], 0.2
-        vel = np.zeros((n, 3), F)
-        vel[:, 1] = -3.0
-        hit = ref.sweep(sph, vel)
-        y = F(y0) - F(3.0) * hit[:, 0]
-        ok = np.isfinite(hit[:, 0]) & (hit[:, 2] > 0.5) & np.isnan(best)
-        best[ok] = y[ok]
-    return best
-
-
-def _seed(ref, trig, n, seed, dist=0.45):
-    """n players on the floor in front of random trigger lines, facing them"""
-    rng = np.random.default_rng(seed)
-    pick = rng.integers(0, len(trig), n)
-    p, yaw = _front(trig[pick], dist)
-    y = _floor_y(ref, p)
-    ok = np.isfinite(y)
-    pos = np.stack([p[:, 0], np.where(ok, y + F(0.25), F(0)), p[:, 1]], 1).astype(F)
-    st = rd.player_states(pos, yaw + rng.normal(scale=0.1, size=n).astype(F))
-    return st[ok], pick[ok]
-
-
-def _script(n, ticks, seed, push=0.05, shoot=0.02):
-    rng = np.random.default_rng(seed)
-    inp = np.zeros((ticks, n), rd.PLAYER_INPUT)
-    fwd = rng.random((ticks, n)) < 0.6
-    inp['movement'][..., 1] = np.where(fwd, -1.0, rng.uniform(-1, 1, (ticks, n))).astype(F)
-    inp['movement'][..., 0] = np.where(fwd, 0.0, rng.uniform(-1, 1, (ticks, n))).astype(F)
-    inp['look'][..., 0] = rng.normal(scale=0.01, size=(ticks, n)).astype(F)
-    inp['look'][..., 1] = rng.normal(scale=0.005, size=(ticks, n)).astype(F)
-    inp['jump'] = rng.random((ticks, n)) < 0.01
-    r = rng.random((ticks, n))
-    act = np.where(r < push, rd.ACTION_PUSH, np.where(r < push + shoot, rd.ACTION_SHOOT, rd.ACTION_NONE)).astype(np.uint8)
-    return inp, act
 
 
 def _setup(wad_path, meta_path, n, seed):

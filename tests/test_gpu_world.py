@@ -9,6 +9,7 @@ import pytest
 
 import rust_doom_amd as rd
 import world_ref
+from step_cases import players as _players, script as _script  # (moved there; the same bytes)
 from util import META_PATH, ROOT, ensure_big_wad, ensure_wad, render_checked
 
 torch = pytest.importorskip('torch')
@@ -110,36 +111,6 @@ def test_sweep_matches_the_restatement(path, index):
     # device tensors in, device tensor out (asynchronous path)
     t = world.sweep(torch.from_numpy(sph).cuda(), torch.from_numpy(vel).cuda())
     assert np.array_equal(_u32(t.cpu().numpy()), _u32(ref.sweep(sph, vel)))
-
-
-def _script(n, ticks, seed):
-    """scripted inputs, player p runs script p % 6: walk forward (into whatever wall is ahead), strafe, jump while walking,
-    look up while walking, stand still, turn and walk with random look"""
-    rng = np.random.default_rng(seed)
-    inp = np.zeros((ticks, n), rd.PLAYER_INPUT)
-    s = np.arange(n) % 6
-    t = np.arange(ticks)[:, None]
-    inp['movement'][:, :, 1] = np.where((s == 0) | (s == 2) | (s == 3) | (s == 5), -1.0, 0.0)
-    inp['movement'][:, :, 0] = np.where(s == 1, 1.0, np.where(s == 0, (t > 150) * 1.0, 0.0))  # into the wall, then strafe along it
-    inp['jump'] = np.where((s == 2) & (t % 40 < 5), 1, 0)
-    inp['look'][:, :, 1] = np.where(s == 3, -0.015, 0.0)  # Up (player.rs:30-36: step 0.015 per tick)
-    inp['look'][:, :, 0] = np.where(s == 5, rng.normal(scale=0.02, size=(ticks, n)), 0.0).astype(np.float32)
-    inp['movement'][:, :, 1] = np.where(s == 4, 0.0, inp['movement'][:, :, 1])
-    return inp
-
-
-def _players(built, n, seed):
-    """start pose and floor centroids; every 7th player flies, every 5th does not clip"""
-    rng = np.random.default_rng(seed)
-    pos, yaw = built.start()
-    cent = built.floor_centroids()
-    p = np.concatenate([pos[None], cent[rng.integers(0, len(cent), n - 1)] + np.array([0, 0.3, 0], np.float32)])
-    yaws = rng.uniform(-np.pi, np.pi, n).astype(np.float32)
-    yaws[0] = yaw
-    flags = np.full(n, rd.PLAYER_CLIP, np.uint32)
-    flags[np.arange(n) % 7 == 3] |= rd.PLAYER_FLY
-    flags[np.arange(n) % 5 == 4] &= ~np.uint32(rd.PLAYER_CLIP)
-    return rd.player_states(p, yaws, flags=flags)
 
 
 @pytest.mark.parametrize('index', [0, 4])

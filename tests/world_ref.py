@@ -155,7 +155,8 @@ class RefWorld:
         return out
 
     def step(self, states, inputs, config=None, dt=1.0 / 60.0, offsets=None, threads=16):
-        """a stepped copy of `states` (rd.PLAYER_STATE); inputs (n_ticks, n) rd.PLAYER_INPUT"""
+        """a stepped copy of `states` (rd.PLAYER_STATE); inputs (n_ticks, n) rd.PLAYER_INPUT; dt 0 means 1/60 (include/rdoom.h)"""
+        dt = float(np.float32(1.0) / np.float32(60.0)) if dt == 0 else dt
         states = np.array(states, rd.PLAYER_STATE).reshape(-1)
         n = len(states)
         inputs = np.ascontiguousarray(inputs, rd.PLAYER_INPUT).reshape(-1, n)

@@ -122,7 +122,7 @@ class RefWorldSet:
         g.counts[p] = len(g.trig)
         g.act[p], g.aflags[p], g.offsets[p] = 0, 0, 0
 
-    def step(self, states, inputs, actions=None, threads=16):
+    def step(self, states, inputs, actions=None, config=None, dt=1.0 / 60.0, threads=16):
         """n_ticks ticks, one at a time: (states, inputs (n_ticks, n), actions (n_ticks, n) or None) -> the stepped states"""
         states = np.array(states, rd.PLAYER_STATE).reshape(-1)
         n = len(states)
@@ -149,7 +149,7 @@ class RefWorldSet:
                 before = states[sel].copy()
                 before['flags'] &= ~np.uint32(rd.PLAYER_EXITED)
                 act = None if actions is None else np.asarray(actions, np.uint8).reshape(-1, n)[t:t + 1, sel]
-                after = sub.step(before, inputs[t:t + 1, sel], act, threads=threads)
+                after = sub.step(before, inputs[t:t + 1, sel], act, config=config, dt=dt, threads=threads)
                 fired = (after['flags'] & rd.PLAYER_EXITED) != 0
                 after['flags'] |= states[sel]['flags']
                 states[sel] = after
