@@ -173,6 +173,10 @@ typedef struct rdoom_path_stats {
   uint64_t tile_entries;          /* sum of the tile lists' lengths (one per triangle and tile) */
   uint64_t quadrants;             /* 32 x 32 quadrants that lie (partly) inside the frame */
   uint64_t described_quadrants;   /* of those: all pixels show one record -- no visibility words stored or read */
+  /* the fragment kernel's own census, counted only in a render under rdoom_debug_set("frag_count", 1) (zero otherwise): */
+  uint64_t half_runs;             /* 8-pixel runs an edge crosses whose uniform quad was shaded with the run's neighbours (one quad listed) */
+  uint64_t half_fallbacks;        /* such runs that failed a guard of the packed body, or show sky / a decoration: both quads listed */
+  uint64_t listed_quads;          /* 4-pixel quads shaded by the general per-pixel body */
 } rdoom_path_stats;
 
 const char *rdoom_last_error(void);
@@ -385,7 +389,7 @@ rdoom_status rdoom_selftest_sincos(uint64_t out_sums[512], uint32_t raw_binade, 
  * shaped but EQUIVALENT path through the kernels -- the image must not change -- so that the rarely taken ones can be
  * forced (tests/test_gpu_debug_paths.py).  Process-wide; read when a batch is created ("vis32", "entry_cap") or
  * rendered (the rest).  Names: no_bins, entry_cap, vis32, leak_mod, frag_nq, frag_bw, frag_chunk, bin_threads,
- * no_cover, no_pair, no_settle, settle_max, raster_stats, no_qtab, keep_vis, qpath, no_split (rust-doom_amd/csrc/common.hpp:
+ * no_cover, no_pair, no_settle, settle_max, raster_stats, no_qtab, keep_vis, qpath, no_split, no_half_runs, frag_count (rust-doom_amd/csrc/common.hpp:
  * DebugOptions); "reset" restores the defaults. */
 rdoom_status rdoom_debug_set(const char *name, int32_t value);
 

@@ -28,6 +28,8 @@ struct DebugOptions {
   int no_settle = 0;     // no settle_kernel: the rasteriser's waves find the one-triangle quadrants themselves, as before round 5
   int settle_max = 0;    // longest tile list settle_kernel examines (0 = default, raster.hip SETTLE_MAX)
   int no_split = 0;      // no per-quadrant lists for tiles with more than 64 entries: the rasteriser re-gathers such a tile's whole list for every quadrant
+  int no_half_runs = 0;  // the fragment kernel lists both quads of a run an edge crosses (no half lanes: fragment.hip), as before round 8
+  int frag_count = 0;    // the fragment kernel counts half lanes and listed quads (rdoom_batch_path_stats: half_runs, half_fallbacks, listed_quads)
   int raster_stats = 0;  // census of the rasteriser's paths on stderr (instrumented instantiation: slower)
 };
 DebugOptions debug_options();  // a snapshot taken under the lock rdoom_debug_set writes under (one host thread per GPU may render while a test thread sets hooks)

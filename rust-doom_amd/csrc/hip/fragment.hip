@@ -40,6 +40,17 @@ namespace {
 // decor, rw outside the verified range, an uncertified mod, a transparent texel) is appended, quad by quad,
 // to a per-wave LDS list and shaded afterwards by the general per-pixel body, lane per pixel -- same
 // results, one code path for everything unusual.
+// Half lanes (two quads per lane): an edge almost always crosses only ONE of a run's two quads (95.5 % of the mixed runs of the
+// E1M1 sweep have a quad that shows one record).  Such a lane does not list both quads: it takes the record of its uniform quad
+// (quad 0 when both are uniform, a 4|4 split), rides the per-lane packed body its neighbours run anyway over all 8 positions of
+// the run -- the four outside its quad are computed and dropped; their texel offsets are masked into the texture's window like
+// those of a lane outside the frame -- stores that quad alone (4 bytes) and lists only the other one.  The body's guards stay
+// run-wide: 1/w is linear along the run, so both ends inside the verified range put every position inside it, the two ends'
+// COLORMAP rows bracket every position's, and the mod guard is taken over the whole run; where the extrapolated half trips a guard
+// (1/w leaves the range next to the eye plane, an uncertified mod, a transparent texel), or the uniform quad shows sky, a
+// decoration or a record without SHADE_FAST, the lane lists both quads as before.  A uniform quad of background is stored as 0.
+// Only lanes that read visibility words are half lanes (no table entry, no leak_mod); a half lane is not `uniform` and never
+// counts towards a wave-uniform record.  The general body runs for 38 % fewer quads of the 1080p sweep (tools/half_runs_census.py).
 // =================================================================================================
 // Launch shape, measured with the quadrant table in place (profiles/r03_ab.txt, run 9): 2 or 4 waves per workgroup alike, 8 slower;
 // a register budget for 4-6 waves per SIMD alike, 7 slower; 16 or 32 wave blocks per wave alike, 4, 8 and 64 slower.
@@ -47,7 +58,11 @@ constexpr int FRAG_CHUNK = 16;
 constexpr uint32_t FRAG_WAVES = 4;  // waves per workgroup (they share the LDS copy of COLORMAP)
 constexpr int FRAG_OCC = 6;         // waves per SIMD the register allocation must allow: at most 80 VGPRs
 typedef uint32_t TexelWord __attribute__((aligned(2)));
-constexpr int FRAG_WLIST = 160;  // per-wave list of unfinished quads: at most 15 carried over + 64 x 2 new
+constexpr int FRAG_WLIST = 160;  // per-wave list of unfinished quads: at most 15 carried over + 64 x 2 new (a half lane adds one, not two)
+// The kernel argument qtab_mode carries two test hooks above the mode proper (no scalar register is spare for another argument):
+// FRAG_NO_HALF = no half lanes (a mixed run lists both quads, as before round 8); FRAG_COUNT = the waves count half lanes and
+// listed quads into the words behind FragConst (rdoom_batch_path_stats).
+constexpr uint32_t FRAG_MODE_MASK = 3u, FRAG_NO_HALF = 4u, FRAG_COUNT = 8u;
 // A list entry is a quad index (< 2^24, launch_fragment); LIST_NO_ENTRY marks a quad whose quadrant has no table entry (or a
 // render that reads no table): its pixels are in the visibility words, and shade_listed does not ask the table first.
 constexpr uint32_t LIST_NO_ENTRY = 1u << 31, LIST_QUAD_MASK = (1u << 24) - 1u;
@@ -113,6 +128,7 @@ struct FragConst {
   uint2 *fix_list;
   const float *ndc_tab;
   uint32_t fix_cap, div_m, div_sh, pad;
+  uint32_t *counts;  // FRAG_COUNT: [0] half lanes that finished their uniform quad, [1] half lanes that fell back, [2] listed quads
 };
 
 template <int NQ, bool VIS16>  // NQ: adjacent quads per lane (1 or 2; the frame width is a multiple of 4 NQ);
@@ -132,6 +148,8 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
   constexpr int NP = 2 * NQ, NPX = 4 * NQ;  // float2 pairs and pixels per lane
   __shared__ uint8_t cmap[32 * 256];
   __shared__ uint32_t wlist[FRAG_WAVES][FRAG_WLIST];
+  __shared__ uint32_t wcount[FRAG_WAVES][4];  // FRAG_COUNT only
+  if (threadIdx.x < FRAG_WAVES * 4u) wcount[threadIdx.x >> 2][threadIdx.x & 3u] = 0u;
   {
     const uint4 *src = reinterpret_cast<const uint4 *>(colormap);
     uint4 *dst = reinterpret_cast<uint4 *>(cmap);
@@ -154,6 +172,7 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
   uint32_t *pfb = reinterpret_cast<uint32_t *>(fb) + (size_t)pose * quads_per_pose;
   const uint32_t lane = threadIdx.x & 63u;
   uint32_t *mylist = wlist[threadIdx.x >> 6];
+  uint32_t *mycount = wcount[threadIdx.x >> 6];
   uint32_t wn = 0;  // wave-uniform: quads waiting in mylist
   const PoseConst &pc = poses[pose];
   // general body: 16 listed quads at a time, lane per pixel.  The list is private to the wave (LDS operations of
@@ -234,13 +253,13 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
     // its own quadrant's entry (tl), and only lanes without one load visibility words.
     uint32_t tq = NONE;
     uint32_t tl = NONE;  // per lane: the entry of the quadrant my pixels lie in, when the block spans two that differ
-    if (qtab_mode != 0u) {
+    if ((qtab_mode & FRAG_MODE_MASK) != 0u) {
       const uint32_t bx0 = (wbx << bw_log2) * (uint32_t)NPX, by0 = wby << (6u - bw_log2);
       const uint32_t *e = qtab + ((size_t)pose * n_tiles + ((by0 >> 6) * tiles_x + (bx0 >> 6))) * 4u + ((by0 >> 5) & 1u) * 2u;
       // A quadrant fragment_quadrant_kernel has shaded carries QTAB_HANDLED: a block that lies in handled quadrants only is
       // done (wave-uniform: the entries arrive by scalar loads).  A block with one handled half shades that half again from
       // the entry like any other described quadrant -- same record, same operations, same bytes.
-      if (qtab_mode == 1u) {
+      if ((qtab_mode & FRAG_MODE_MASK) == 1u) {
         const uint32_t one = e[(bx0 >> 5) & 1u];
         if (qtab_handled(one)) continue;
         tq = one;
@@ -251,7 +270,9 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
         const uint32_t left = qtab_record(two.x), right = qtab_record(two.y);
         const bool same = left == right || right_out;
         tq = same ? left : NONE;
-        tl = same ? NONE : (((lane_col * (uint32_t)NPX) & 32u) ? right : left);
+        uint32_t lc = lane_col;
+        asm volatile("" : "+v"(lc));  // (compared here: hoisted out of the loop, "my lane is in the right quadrant" is a lane mask that spills)
+        tl = same ? NONE : (((lc * (uint32_t)NPX) & 32u) ? right : left);
       }
     }
     tq = (uint32_t)__builtin_amdgcn_readfirstlane((int)tq);
@@ -259,6 +280,15 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
     const bool table_one = (tq != NONE) & (debug_leak_mod == 0u);
     uint32_t id0;
     bool uniform;
+    // Half lanes (NQ = 2): a lane whose 8 words differ but whose quad 0 or quad 1 shows ONE record rides the per-lane packed body
+    // with that record over all 8 positions, stores that quad alone and lists only the other one.  Only where the lane read
+    // visibility words (no table entry, no leak_mod); not `uniform`, so it never counts towards wave_one.
+    // hs, one VGPR (a lane mask each would spill scalar registers across the body): bit 0 = half lane, bit 1 = its uniform quad is
+    // quad 1 (quad 0 is chosen when both are uniform, a 4|4 split)
+    uint32_t hs = 0u;
+    uint32_t no_half = (qtab_mode & FRAG_NO_HALF) | debug_leak_mod;
+    asm volatile("" : "+s"(no_half));  // (evaluated here, two scalar operations: hoisted out of the loop it is a lane mask that spills)
+    const bool half_ok = (NQ == 2) & (no_half == 0u);
     if (table_one) {
       id0 = tq;
       uniform = true;
@@ -269,8 +299,11 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
     } else if (VIS16) {
       if (NQ == 2) {
         const uint4 v = *reinterpret_cast<const uint4 *>(pvis_bytes + q0l * 8u);
-        id0 = v.x & 0xFFFFu;
-        uniform = (((v.x ^ __builtin_amdgcn_alignbit(v.x, v.x, 16)) | (v.x ^ v.y)) | ((v.y ^ v.z) | (v.z ^ v.w))) == 0u;
+        const uint32_t d0 = (v.x ^ __builtin_amdgcn_alignbit(v.x, v.x, 16)) | (v.x ^ v.y);
+        const uint32_t d1 = (v.z ^ __builtin_amdgcn_alignbit(v.z, v.z, 16)) | (v.z ^ v.w);
+        uniform = ((d0 | d1) | (v.y ^ v.z)) == 0u;
+        hs = (half_ok & valid & !uniform & ((d0 == 0u) | (d1 == 0u))) ? (d0 != 0u ? 3u : 1u) : 0u;
+        id0 = ((hs & 2u) ? v.z : v.x) & 0xFFFFu;
       } else {
         const uint2 v = *reinterpret_cast<const uint2 *>(pvis_bytes + q0l * 8u);
         id0 = v.x & 0xFFFFu;
@@ -279,20 +312,24 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
     } else {
       const uint4 v = *reinterpret_cast<const uint4 *>(pvis_bytes + q0l * 16u);
       id0 = v.x;
-      uint32_t diff = (v.x ^ v.y) | (v.y ^ v.z) | (v.z ^ v.w);
+      const uint32_t d0 = (v.x ^ v.y) | (v.y ^ v.z) | (v.z ^ v.w);
+      uniform = d0 == 0u;
       if (NQ == 2) {
         const uint4 w = *reinterpret_cast<const uint4 *>(pvis_bytes + (q0l + 1u) * 16u);
-        diff |= (w.x ^ id0) | (w.x ^ w.y) | (w.y ^ w.z) | (w.z ^ w.w);
+        const uint32_t d1 = (w.x ^ w.y) | (w.y ^ w.z) | (w.z ^ w.w);
+        uniform = ((d0 | d1) | (w.x ^ v.x)) == 0u;
+        hs = (half_ok & valid & !uniform & ((d0 == 0u) | (d1 == 0u))) ? (d0 != 0u ? 3u : 1u) : 0u;
+        id0 = (hs & 2u) ? w.x : v.x;
       }
-      uniform = diff == 0u;
     }
     id0 = valid ? id0 : NONE_ID;
     uniform |= !valid;
+    asm volatile("" : "+v"(hs));
     bool done = false;
     uint32_t out[NQ];
 #pragma unroll
     for (int q = 0; q < NQ; q++) out[q] = 0;
-    if (uniform & (id0 == NONE_ID)) done = true;  // background (or past the end: nothing is stored)
+    if ((uniform | (hs != 0u)) & (id0 == NONE_ID)) done = true;  // background (or past the end: nothing is stored; a half lane: its quad stays 0)
     // The packed body for a run that lies in ONE flat / wall triangle with SHADE_FAST.  ONE = the whole wave holds the
     // same record (77 % of the waves of the 1080p E1M1 sweep): its words then arrive by scalar loads and are SGPR
     // operands of the packed instructions -- no per-lane record loads, no register pairs to build for the splats.
@@ -438,7 +475,7 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
         took_one = true;
       }
     }
-    if (!took_one & uniform & (id0 != NONE_ID) & (debug_leak_mod == 0u)) {
+    if (!took_one & (uniform | (hs != 0u)) & (id0 != NONE_ID) & (debug_leak_mod == 0u)) {
       const uint4 *rp = reinterpret_cast<const uint4 *>(&prec[id0].s);
       const uint4 r0 = rp[0], r1 = rp[1], r2 = rp[2], r3 = rp[3];
       const uint32_t flags = r3.z;
@@ -446,7 +483,7 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
       asm volatile("" ::"v"(r0.x), "v"(r1.x), "v"(r2.x));
       if (flags & SHADE_FAST) {
         fast_run(std::false_type{}, r0, r1, r2, r3);
-      } else if ((flags & 3u) == RDOOM_KIND_SKY) {
+      } else if (((flags & 3u) == RDOOM_KIND_SKY) & (hs == 0u)) {  // (a half lane takes the packed body or nothing: it then lists both quads)
         // a run of sky (sky.frag:12-26): the colour depends on the pixel and the pose only.  ndc_tab holds
         // p / (size / 2) - 1 for every column and row of the frame (computed once per batch with the same two
         // operations), the record carries v_r.y and 4 v_r.x / 3.14159265358; the row part is evaluated once per run.
@@ -479,6 +516,11 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
         done = true;
       }
     }
+    // A half lane whose body passed its (run-wide) guards has finished its uniform quad and lists the other one: hf keeps hs for it
+    // and is 0 for every other lane (a half lane that failed lists both quads like any unfinished lane).  A half lane always lists,
+    // so its store and its bookkeeping sit in the listing branch below: a block without unfinished lanes pays two instructions.
+    const uint32_t hf = (NQ == 2 && done) ? hs : 0u;
+    done &= hf == 0u;
     if (done & valid) {
       if (NQ == 2)
         *reinterpret_cast<uint2 *>(pfb_bytes + q0 * 4u) = make_uint2(out[0], out[NQ - 1]);
@@ -486,13 +528,24 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
         *reinterpret_cast<uint32_t *>(pfb_bytes + q0 * 4u) = out[0];
     }
     const unsigned long long sm = __ballot(!done);
-    if (sm) {  // ordered append of this wave's unfinished quads, then shade full groups of 16
+    if (sm) {  // ordered append of this wave's unfinished quads (NQ per lane, one for a half lane), then shade full groups of 16
+      const bool hfin = hf != 0u;
+      if (NQ == 2 && hfin) *reinterpret_cast<uint32_t *>(pfb_bytes + (q0 + (hf >> 1)) * 4u) = (hf & 2u) ? out[NQ - 1] : out[0];
+      const unsigned long long hm = NQ == 2 ? __ballot(hfin) : 0ull;
       if (!done) {
-        const uint32_t at = wn + (uint32_t)NQ * (uint32_t)__popcll(sm & ((1ull << lane) - 1ull));
-#pragma unroll
-        for (int q = 0; q < NQ; q++) mylist[at + (uint32_t)q] = (q0 + (uint32_t)q) | list_tag;
+        const unsigned long long below = (1ull << lane) - 1ull;
+        const uint32_t at = wn + (uint32_t)NQ * (uint32_t)__popcll(sm & below) - (uint32_t)__popcll(hm & below);
+        mylist[at] = (q0 + (hf == 1u ? 1u : 0u)) | list_tag;  // (hf == 1: quad 0 is finished, quad 1 is listed)
+        if (NQ == 2 && !hfin) mylist[at + 1u] = (q0 + 1u) | list_tag;
       }
-      wn += (uint32_t)NQ * (uint32_t)__popcll(sm);
+      const uint32_t listed = (uint32_t)NQ * (uint32_t)__popcll(sm) - (uint32_t)__popcll(hm);
+      wn += listed;
+      if (qtab_mode & FRAG_COUNT) {  // (test hook; LDS operations of one wave execute in order)
+        const uint32_t fell = (uint32_t)__popcll(__ballot(hs != 0u)) - (uint32_t)__popcll(hm);
+        // (every lane writes the same sums: no lane mask to keep)
+        const uint32_t c0 = mycount[0] + (uint32_t)__popcll(hm), c1 = mycount[1] + fell, c2 = mycount[2] + listed;
+        mycount[0] = c0, mycount[1] = c1, mycount[2] = c2;
+      }
       __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
       while (wn >= 16u) {
         wn -= 16u;
@@ -502,6 +555,7 @@ __global__ __launch_bounds__(64 * FRAG_WAVES) __attribute__((amdgpu_waves_per_eu
   }
   __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
   if (wn) shade_listed(0u, wn);
+  if ((qtab_mode & FRAG_COUNT) && lane < 3u && mycount[lane]) atomicAdd(fc->counts + lane, mycount[lane]);
 }
 
 // =================================================================================================
@@ -850,7 +904,8 @@ __global__ __launch_bounds__(256) void fixup_kernel(DeviceLevelView lv, const Tr
 
 }  // namespace
 
-size_t fragment_const_bytes() { return sizeof(FragConst); }
+size_t fragment_const_bytes() { return sizeof(FragConst) + 4u * sizeof(uint32_t); }  // + the words FRAG_COUNT counts into
+size_t fragment_counts_offset() { return sizeof(FragConst); }
 
 FragmentPlan plan_fragment(int width, int pitch, int height, bool have_qtab) {
   const rdoom::DebugOptions dbg = rdoom::debug_options();  // test hooks: equivalent paths, same image
@@ -865,6 +920,8 @@ FragmentPlan plan_fragment(int width, int pitch, int height, bool have_qtab) {
   const int bw_auto = (p.nq == 2 && (size_t)pitch * (size_t)height >= (size_t)1280 * 720) ? 2 : 3;
   p.bwl = (uint32_t)std::min(6, dbg.frag_bw >= 0 ? dbg.frag_bw : bw_auto);
   p.chunk = dbg.frag_chunk > 0 ? (uint32_t)dbg.frag_chunk : (uint32_t)FRAG_CHUNK;
+  p.no_half_runs = dbg.no_half_runs != 0;
+  p.count = dbg.frag_count != 0;
   // the quadrant table serves blocks that lie inside one 32 x 32 quadrant, or inside two side by side
   const uint32_t bw = 1u << p.bwl, bh = 64u >> p.bwl, block_px = bw * 4u * (uint32_t)p.nq;
   p.qtab_mode = (!have_qtab || dbg.no_qtab || bh > 32u) ? 0u : (block_px == 32u ? 1u : (block_px == 64u ? 2u : 0u));
@@ -916,13 +973,16 @@ rdoom_status launch_fragment(hipStream_t st, uint32_t n_poses, const DeviceLevel
   if (fgrid > 0x7FFFFFFFull) return rdoom::fail(RDOOM_BAD_ARG, "batch too large for one launch");
   auto frag = nq == 2 ? (vis16 ? fragment_kernel<2, true> : fragment_kernel<2, false>)
                       : (vis16 ? fragment_kernel<1, true> : fragment_kernel<1, false>);
-  const uint32_t qtab_mode = qtab ? plan.qtab_mode : 0u;
+  const uint32_t qtab_mode = (qtab ? plan.qtab_mode : 0u) | (plan.no_half_runs ? FRAG_NO_HALF : 0u) | (plan.count ? FRAG_COUNT : 0u);
+  uint32_t *frag_counts = reinterpret_cast<uint32_t *>(static_cast<char *>(d_frag_const) + sizeof(FragConst));
   if (!*frag_const_ready) {  // constant for the life of the batch: written once
     FragConst h{};
     h.lv = lv, h.fix_count = fix_count, h.fix_list = fix_list, h.ndc_tab = ndc_tab, h.fix_cap = fix_cap, h.div_m = div_m, h.div_sh = div_sh;
+    h.counts = frag_counts;
     HIP_TRY(hipMemcpy(d_frag_const, &h, sizeof h, hipMemcpyHostToDevice));
     *frag_const_ready = true;
   }
+  if (plan.count) HIP_TRY(hipMemsetAsync(frag_counts, 0, 4u * sizeof(uint32_t), st));
   if (qtab && plan.quadrant_path) {  // described quadrants first: whole quadrants, one record each (marks them QTAB_HANDLED)
     const uint32_t n_tiles = (uint32_t)(tiles_x * tiles_y), groups = (n_tiles + 4u * QUAD_TILES_PER_WAVE - 1u) / (4u * QUAD_TILES_PER_WAVE);
     const uint64_t qgrid = (uint64_t)((n + 7) / 8) * 8ull * groups;

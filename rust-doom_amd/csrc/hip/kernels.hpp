@@ -50,6 +50,8 @@ struct FragmentPlan {
   bool skip_described_vis;
   // fragment_quadrant_kernel shades the described quadrants whose record qualifies before fragment_kernel runs
   bool quadrant_path;
+  // test hooks carried in the kernel's qtab_mode argument: no half lanes (a mixed run lists both quads); count half lanes and listed quads
+  bool no_half_runs, count;
 };
 FragmentPlan plan_fragment(int width, int pitch, int height, bool have_qtab);
 // Kernels 3 + 4: fragment kernel -> palette indices, then the alpha-leak fixup (fragment.hip)
@@ -62,6 +64,7 @@ rdoom_status launch_fragment(hipStream_t st, uint32_t n_poses, const DeviceLevel
                              uint2 *fix_list, uint32_t fix_cap, uint32_t *qtab, void *d_frag_const,
                              bool *frag_const_ready, const FragmentPlan &plan);  // d_frag_const: fragment_const_bytes() of device memory owned by the batch
 size_t fragment_const_bytes();
+size_t fragment_counts_offset();  // in d_frag_const: three words the fragment kernel counts into under the hook frag_count (FragmentPlan::count)
 
 // Kernels 5 + 6: frames [first, first + count) of the last render -> RGB8 / RGBA8, then the pixels of the fixup list (resolve.hip)
 struct ResolveArgs {

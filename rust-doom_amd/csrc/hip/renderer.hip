@@ -93,6 +93,7 @@ struct rdoom_batch {
   float *d_ndc = nullptr;  // (ix + 0.5) / (width / 2) - 1 for every column, then (iy + 0.5) / (height / 2) - 1 for every row
   // the last render's FragmentPlan::skip_described_vis: a described quadrant's visibility words are another render's (resolve reads the table)
   bool last_skip_vis = false;
+  bool last_frag_count = false;  // the last render's FragmentPlan::count: the fragment kernel counted its half lanes and listed quads
   uint8_t *d_rgb = nullptr;  // rdoom_batch_read_rgb's staging (allocated on first use, at most RGB_STAGING_BYTES or one frame)
   size_t rgb_bytes = 0;
   // the last render was rdoom_batch_render_players: its levels are on the device only (the pinned staging is an older render's)
@@ -617,6 +618,7 @@ static rdoom_status queue_pipeline(rdoom_batch *b, uint32_t n, uint32_t kinds_ma
   // one reading of the debug hooks for both kernels: who writes and who reads visibility words must not change in between
   const FragmentPlan plan = plan_fragment(W, PITCH, H, b->d_qtab != nullptr);
   b->last_skip_vis = plan.skip_described_vis;
+  b->last_frag_count = plan.count;
   // (the rasteriser's frame is PITCH pixels wide: the padding columns of a width that is not a multiple of 4 are pixels no
   // bounding box reaches -- they stay uncovered, and the quadrants they lie in simply never count as covered)
   if (rdoom_status rs = launch_raster(st, n, lv->view, b->d_recs, b->d_counts, b->cap, PITCH, H, tiles_x, tiles_y,
@@ -924,6 +926,11 @@ rdoom_status rdoom_batch_path_stats(rdoom_batch *b, rdoom_path_stats *out) {
       }
     }
     out->tiles = (uint64_t)n * T;
+    if (b->last_frag_count) {  // (rendered under the hook frag_count; zero otherwise)
+      uint32_t fc[3];
+      HIP_TRY(read_back(b, fc, static_cast<const char *>(b->d_frag_const) + fragment_counts_offset(), sizeof fc));
+      out->half_runs = fc[0], out->half_fallbacks = fc[1], out->listed_quads = fc[2];
+    }
   } catch (const std::bad_alloc &) {
     return rdoom::fail(RDOOM_OOM, "out of host memory");
   }

@@ -97,7 +97,7 @@ other = os.path.join(src, 'bench_other.jsonl')
 lines = [json.loads(x) for x in open(other)] if os.path.exists(other) else []
 if lines:
     shutil.copy(other, os.path.join(dst, 'r%02d_bench_other.jsonl' % rnd))
-md = ['# Round %d measurements (one MI355X; generated by tools/profile_collect.py from gpurun_out/%s)' % (rnd, tag), '',
+md = ['# Round %d measurements (one MI355X; generated by tools/profile_collect.py from the profile run %s)' % (rnd, tag), '',
       '## rocprofv3 --kernel-trace --stats of `python bench.py --streams 1` (E1M1, 1024 poses, 1920x1080: one launch per kernel and step,',
       'nothing overlapping -- the per-kernel accounting the bench line\'s `kernels_ms` / `roofline` must agree with)', '',
       '| kernel | calls | average (us) | share |', '|---|---|---|---|']

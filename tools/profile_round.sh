@@ -41,10 +41,10 @@ wc -l $OUT/bench_other.jsonl
 # 4. issue-slot / occupancy counters of the hot kernels on the final device sources
 bash tools/pmc_frag.sh $TAG/issue > $OUT/issue.log 2>&1
 find $OUT/issue -name '*counter_collection.csv' | wc -l
-# 5. A/B lines of the round's hooks on the same box (equivalent paths, same images): settle_kernel off / other list limits
+# 5. A/B lines of the round's hooks on the same box (equivalent paths, same images): no half lanes in the fragment kernel
 : > $OUT/bench_hooks.jsonl
-for ARGS in "--debug no_settle=1" "--debug settle_max=16" "--debug settle_max=64" "--width 3840 --height 2160 --poses 256 --debug no_settle=1" \
-            "--big --debug no_settle=1" "--width 320 --height 200 --poses 8192 --debug no_settle=1" "--levels 0-8 --debug no_settle=1"; do
+for ARGS in "--debug no_half_runs=1" "--width 3840 --height 2160 --poses 256 --debug no_half_runs=1" \
+            "--big --debug no_half_runs=1" "--width 320 --height 200 --poses 8192 --debug no_half_runs=1" "--levels 0-8 --debug no_half_runs=1"; do
   python bench.py $ARGS --steps 10 --warmup 2 --cpu-sample 0 --other off 2>/dev/null | grep '^{' | tail -1 >> $OUT/bench_hooks.jsonl
 done
 wc -l $OUT/bench_hooks.jsonl
