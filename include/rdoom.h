@@ -1488,6 +1488,63 @@ rdoom_status rdoom_wall_distance(const float *d_floor, const float *d_ceiling, u
                                  const rdoom_wall_params *params, uint16_t *d_dist2_out, float *d_floor_out, float *d_ceiling_out,
                                  void *stream);
 
+/* ---- octile distance: grid floods over the eight neighbours, and their descent ------------------------------------
+ * rdoom_flood_grids counts moves to 4-neighbours, so moves * cell is a Manhattan-style length that overstates a diagonal walk by up
+ * to 41 %.  These two calls add the diagonal move: with integer costs 5 and 7 the free-space error against the Euclidean length is
+ * between -1 % and +8 %, and the field stays exact integer arithmetic.  rdoom_flood_grids and rdoom_flood_descend are unchanged.
+ * The reference project has no counterpart of this: nothing here restates it.
+ *
+ * rdoom_flood_grids_octile.  A pure function of its arrays: no handle.  d_floor, d_ceiling, n, width, height, d_seeds, d_count_out
+ * and the limits max_step, max_drop and clearance of `params` are rdoom_flood_grids': the planes, which cells are open, which moves
+ * to a 4-neighbour -- the axial moves -- are allowed and where the seed lies are defined by the goal-distance contract above and
+ * by nothing here.
+ * Diagonal moves.  Let a and d be cells inside the grid with d = (column +- 1, row +- 1) of a, and s1, s2 the two cells that are
+ * 4-neighbours of both.  The diagonal move from a to d is allowed exactly when all four axial moves a -> s1, s1 -> d, a -> s2 and
+ * s2 -> d are allowed; nothing else is compared.  So a diagonal never passes the corner of a closed cell, a ledge or a door, and it
+ * is a pure function of the axial move bits of d, s1 and s2.  With RDOOM_FLOOD_TOWARDS the same rule applies to the reversed
+ * relation.
+ * Costs.  An axial move costs params->axial_cost, a diagonal move params->diagonal_cost, with
+ * 1 <= axial_cost <= diagonal_cost <= 2 * axial_cost and (uint64_t)axial_cost * width * height <= 0x00FFFFFF: a cheapest path is
+ * never dearer than an axial-only one of fewer than width * height moves, so a distance fits 24 bits.
+ * Octile distances.  d_dist_out (n x height x width uint32): without RDOOM_FLOOD_TOWARDS in params->flags the smallest total cost
+ * of a sequence of allowed moves from row p's seed to the cell; with it the smallest total cost from the cell to the seed.  The
+ * seed holds 0; RDOOM_FLOOD_GRID_UNREACHED where there is no path, where the cell is closed, and everywhere when the seed is closed
+ * or outside the grid.  d_count_out is as in rdoom_flood_grids.  dist * cell / axial_cost is the length in world units.
+ * Properties, with D4 what rdoom_flood_grids gives for the same planes, seeds, limits and direction and D8 this call's distances:
+ *   1. a cell is reached exactly when rdoom_flood_grids reaches it;
+ *   2. with diagonal_cost == 2 * axial_cost, D8 == axial_cost * D4 on every reached cell;
+ *   3. otherwise D8 <= axial_cost * D4;
+ *   4. D8 >= axial_cost * (max(|dc|, |dr|) - min(|dc|, |dr|)) + diagonal_cost * min(|dc|, |dr|) for the cell at the offset
+ *      (dc, dr) from the seed.
+ *
+ * rdoom_flood_descend_octile: rdoom_flood_descend's walk down an octile field.  d_dist: the words rdoom_flood_grids_octile wrote
+ * with the same `params`.  The start, d_cells_out, d_moves_out, d_path_out and the unreached or outside start behave as in
+ * rdoom_flood_descend.  While D(a) > stop_dist and m < max_moves: among the 8-neighbours b of a inside the grid, taken in the
+ * order (column - 1, column + 1, row - 1, row + 1), then the (column, row) offsets (-1, -1), (+1, -1), (-1, +1), (+1, +1), the first
+ * with D(b) + cost == D(a) -- cost the axial or the diagonal one of that move, the sum taken in integers, so an unreached b never
+ * qualifies -- whose connecting move is allowed, with RDOOM_FLOOD_TOWARDS the move from a to b, without it the move from b to a, a
+ * diagonal's by the rule above, becomes a, and m += 1; if no neighbour qualifies the walk stops.  stop_dist is in cost units;
+ * max_moves and d_moves_out count moves.
+ *
+ * Frontiers.  rdoom_world_area_frontiers and rdoom_worldset_area_frontiers take an octile field as d_dist as they are: they then
+ * pick the frontier cell nearest by octile cost, and d_dist_out is that cost.
+ * Both calls are one launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so
+ * they can be captured into a graph.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): those of rdoom_flood_grids
+ * and rdoom_flood_descend for the arguments shared with them; an axial_cost of 0; a diagonal_cost below axial_cost or above
+ * 2 * axial_cost; axial_cost * width * height above 0x00FFFFFF.  n == 0 queues nothing. */
+typedef struct rdoom_flood_octile_params {
+  float max_step, max_drop, clearance;   /* rdoom_flood_params' */
+  uint32_t flags;                        /* 0 or RDOOM_FLOOD_TOWARDS */
+  uint32_t axial_cost, diagonal_cost;    /* cost units of a move to a 4-neighbour / to a diagonal neighbour */
+} rdoom_flood_octile_params;             /* 24 bytes */
+rdoom_status rdoom_flood_grids_octile(const float *d_floor, const float *d_ceiling, uint32_t n, uint32_t width, uint32_t height,
+                                      const int32_t *d_seeds, const rdoom_flood_octile_params *params, uint32_t *d_dist_out,
+                                      uint32_t *d_count_out, void *stream);
+rdoom_status rdoom_flood_descend_octile(const float *d_floor, const float *d_ceiling, const uint32_t *d_dist, uint32_t n, uint32_t width,
+                                        uint32_t height, const int32_t *d_starts, const rdoom_flood_octile_params *params,
+                                        uint32_t max_moves, uint32_t stop_dist, int32_t *d_cells_out, uint32_t *d_moves_out,
+                                        int32_t *d_path_out, uint32_t path_len, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

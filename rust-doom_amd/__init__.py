@@ -188,7 +188,8 @@ API_SYMBOLS = [
     'rdoom_world_reveal_area', 'rdoom_worldset_reveal_area', 'rdoom_world_draw_area_maps', 'rdoom_worldset_draw_area_maps',
     'rdoom_world_draw_area_planes', 'rdoom_worldset_draw_area_planes', 'rdoom_flood_grid_max_cells', 'rdoom_flood_grids',
     'rdoom_world_area_cells', 'rdoom_worldset_area_cells', 'rdoom_flood_descend', 'rdoom_world_area_frontiers',
-    'rdoom_worldset_area_frontiers', 'rdoom_wall_distance', 'rdoom_selftest_sincos']
+    'rdoom_worldset_area_frontiers', 'rdoom_wall_distance', 'rdoom_selftest_sincos', 'rdoom_flood_grids_octile',
+    'rdoom_flood_descend_octile']
 
 _lib = None
 
@@ -1705,20 +1706,9 @@ def _int32_out(t, shape, device, what):
     return t, _out_tensor(t, int(np.prod(shape)) * 4, what)
 
 
-def descend_grids(floor, ceiling, dist, starts, towards=False, max_moves=None, stop_dist=0, max_step=0.24, max_drop=float('inf'), clearance=0.56,
-                  cells_out=None, moves_out=None, path_out=None, stream=None):
-    """rdoom_flood_descend: walk flood_grids' field downhill.  floor, ceiling: the planes that flood took; dist: the (n, H, W)
-    distances it returned with the same towards, max_step, max_drop and clearance; starts: an int32 (n, 2) tensor of (column, row),
-    area_cells' or area_frontiers' layout.  From its start every row steps to the first 4-neighbour (left, right, up, down) whose
-    distance is one less and which the field's directed moves connect -- a ledge is dropped from and not climbed, which the
-    distances alone do not say -- until the distance is stop_dist or max_moves (None: no limit) moves are made.  Returns (cells,
-    moves): the int32 (n, 2) cell reached, (-1, -1) for a start outside the grid or on an unreached cell, and the int32 (n,) moves
-    made.  With towards=True and max_moves=K the cell is the waypoint K moves ahead on a shortest path to the goal (the goal itself
-    if nearer); on a forward field, from a frontier cell with stop_dist=K, it is the cell K moves from the player on the way
-    there.  path_out: an int (the length to allocate) or a 32-bit integer (n, length, 2) tensor: entry k is the cell after move
-    k + 1, (-1, -1) past the walk's end; then (cells, moves, path) is returned.  cells_out, moves_out: tensors or raw device
-    pointers to write instead of new ones.  One launch, asynchronous on `stream` (None, a torch stream or a raw handle); it can be
-    captured into a graph."""
+def _descend(entry, params, floor, ceiling, dist, starts, max_moves, stop_dist, cells_out, moves_out, path_out, stream):
+    """descend_grids' and descend_grids_octile's arguments, checked, and the call of `entry` (rdoom_flood_descend's signature) with
+    `params`; what they return"""
     import torch
     n, height, width = _flood_inputs(floor, ceiling, None)
     if not isinstance(starts, torch.Tensor) or starts.device.type != 'cuda' or not starts.is_contiguous() or starts.dtype != torch.int32 or \
@@ -1737,12 +1727,69 @@ def descend_grids(floor, ceiling, dist, starts, towards=False, max_moves=None, s
             raise ValueError('path_out must be a length or a 32-bit integer (%d, length, 2) tensor' % n)
         path_len = int(path_out.shape[1])
         path_out, pp = _int32_out(path_out, (n, path_len, 2), floor.device, 'path_out')
-    params = FloodParams(max_step, max_drop, clearance, FLOOD_TOWARDS if towards else 0)
     v = ctypes.c_void_p
-    _check(lib().rdoom_flood_descend(v(floor.data_ptr()), v(ceiling.data_ptr()), v(dist.data_ptr()), n, width, height, v(starts.data_ptr()),
-                                     ctypes.byref(params), ctypes.c_uint32(0xFFFFFFFF if max_moves is None else int(max_moves)),
-                                     ctypes.c_uint32(int(stop_dist)), v(pc), v(pm), v(pp), path_len, v(_stream_handle(stream))))
+    _check(entry(v(floor.data_ptr()), v(ceiling.data_ptr()), v(dist.data_ptr()), n, width, height, v(starts.data_ptr()), ctypes.byref(params),
+                 ctypes.c_uint32(0xFFFFFFFF if max_moves is None else int(max_moves)), ctypes.c_uint32(int(stop_dist)), v(pc), v(pm), v(pp),
+                 path_len, v(_stream_handle(stream))))
     return (cells_out, moves_out) if path_out is None else (cells_out, moves_out, path_out)
+
+
+def descend_grids(floor, ceiling, dist, starts, towards=False, max_moves=None, stop_dist=0, max_step=0.24, max_drop=float('inf'), clearance=0.56,
+                  cells_out=None, moves_out=None, path_out=None, stream=None):
+    """rdoom_flood_descend: walk flood_grids' field downhill.  floor, ceiling: the planes that flood took; dist: the (n, H, W)
+    distances it returned with the same towards, max_step, max_drop and clearance; starts: an int32 (n, 2) tensor of (column, row),
+    area_cells' or area_frontiers' layout.  From its start every row steps to the first 4-neighbour (left, right, up, down) whose
+    distance is one less and which the field's directed moves connect -- a ledge is dropped from and not climbed, which the
+    distances alone do not say -- until the distance is stop_dist or max_moves (None: no limit) moves are made.  Returns (cells,
+    moves): the int32 (n, 2) cell reached, (-1, -1) for a start outside the grid or on an unreached cell, and the int32 (n,) moves
+    made.  With towards=True and max_moves=K the cell is the waypoint K moves ahead on a shortest path to the goal (the goal itself
+    if nearer); on a forward field, from a frontier cell with stop_dist=K, it is the cell K moves from the player on the way
+    there.  path_out: an int (the length to allocate) or a 32-bit integer (n, length, 2) tensor: entry k is the cell after move
+    k + 1, (-1, -1) past the walk's end; then (cells, moves, path) is returned.  cells_out, moves_out: tensors or raw device
+    pointers to write instead of new ones.  One launch, asynchronous on `stream` (None, a torch stream or a raw handle); it can be
+    captured into a graph."""
+    params = FloodParams(max_step, max_drop, clearance, FLOOD_TOWARDS if towards else 0)
+    return _descend(lib().rdoom_flood_descend, params, floor, ceiling, dist, starts, max_moves, stop_dist, cells_out, moves_out, path_out, stream)
+
+
+class FloodOctileParams(ctypes.Structure):
+    """rdoom_flood_octile_params"""
+    _fields_ = [('max_step', ctypes.c_float), ('max_drop', ctypes.c_float), ('clearance', ctypes.c_float), ('flags', ctypes.c_uint32),
+                ('axial_cost', ctypes.c_uint32), ('diagonal_cost', ctypes.c_uint32)]
+
+
+def flood_grids_octile(floor, ceiling, seeds=None, towards=False, axial_cost=5, diagonal_cost=7, max_step=0.24, max_drop=float('inf'),
+                       clearance=0.56, dist_out=None, count_out=None, stream=None):
+    """rdoom_flood_grids_octile: flood_grids over moves to the eight neighbours.  floor, ceiling, seeds, towards, max_step, max_drop,
+    clearance, dist_out, count_out: as flood_grids takes them.  A move to a 4-neighbour costs axial_cost; a diagonal move costs
+    diagonal_cost and is allowed exactly when the four axial moves round both sides of it are, so it never cuts the corner of a
+    closed cell, a ledge or a door.  1 <= axial_cost <= diagonal_cost <= 2 * axial_cost, and axial_cost * H * W is at most
+    0xFFFFFF.  Returns the (n, H, W) int32 tensor of smallest total costs, 0 at the seed and FLOOD_GRID_UNREACHED (-1 as int32)
+    exactly where flood_grids has it (with count_out: (costs, counts)); cost * cell / axial_cost is the length in world units,
+    with the default (5, 7) within -1 % and +8 % of the straight line in free space.  With diagonal_cost == 2 * axial_cost the
+    result is axial_cost * flood_grids'.  One launch, asynchronous on `stream` (None, a torch stream or a raw handle); it can be
+    captured into a graph."""
+    n, height, width = _flood_inputs(floor, ceiling, seeds)
+    dist_out, pd, count_out, pc = _flood_outputs(n, height, width, floor.device, dist_out, count_out, 4)
+    params = FloodOctileParams(max_step, max_drop, clearance, FLOOD_TOWARDS if towards else 0, int(axial_cost), int(diagonal_cost))
+    v = ctypes.c_void_p
+    _check(lib().rdoom_flood_grids_octile(v(floor.data_ptr()), v(ceiling.data_ptr()), n, width, height,
+                                          v(seeds.data_ptr()) if seeds is not None else None, ctypes.byref(params), v(pd), v(pc),
+                                          v(_stream_handle(stream))))
+    return dist_out if count_out is None else (dist_out, count_out)
+
+
+def descend_grids_octile(floor, ceiling, dist, starts, towards=False, axial_cost=5, diagonal_cost=7, max_moves=None, stop_dist=0, max_step=0.24,
+                         max_drop=float('inf'), clearance=0.56, cells_out=None, moves_out=None, path_out=None, stream=None):
+    """rdoom_flood_descend_octile: descend_grids down flood_grids_octile's field.  dist: the costs that call returned with the same
+    towards, costs and limits.  Every row steps to the first of its eight neighbours -- left, right, up, down, then the (column,
+    row) offsets (-1, -1), (+1, -1), (-1, +1), (+1, +1) -- whose cost plus the move's equals the cell's and which the field's
+    directed moves connect, until the cost is at most stop_dist (in cost units) or max_moves (None: no limit) moves are made.
+    starts, cells_out, moves_out, path_out, the return value and a start outside the grid or on an unreached cell: as
+    descend_grids has them; moves count moves, not cost.  One launch, asynchronous on `stream`; it can be captured into a graph."""
+    params = FloodOctileParams(max_step, max_drop, clearance, FLOOD_TOWARDS if towards else 0, int(axial_cost), int(diagonal_cost))
+    return _descend(lib().rdoom_flood_descend_octile, params, floor, ceiling, dist, starts, max_moves, stop_dist, cells_out, moves_out, path_out,
+                    stream)
 
 
 class WallParams(ctypes.Structure):

@@ -265,23 +265,23 @@ rdoom_status check_limits(const rdoom_flood_params *params) {
   return RDOOM_OK;
 }
 
-// the cells of a row or column one thread sweeps at a time: the shortest runs that give every thread at most one run of a phase,
-// where the grid's shape allows that
-uint32_t run_length(uint32_t width, uint32_t height) {
-  uint32_t seg = 2;
-  while (seg < MAX_SEG && ((uint64_t)height * ((width + seg - 1) / seg) > THREADS || (uint64_t)width * ((height + seg - 1) / seg) > THREADS)) seg++;
-  return seg;
-}
-
 FloodPlanes flood_planes(const float *d_floor, const float *d_ceiling, const int32_t *d_seeds, uint32_t *d_count_out, uint32_t width,
                          uint32_t height, const rdoom_flood_params *params) {
-  return FloodPlanes{d_floor, d_ceiling, d_seeds, d_count_out, width, height, width * height, run_length(width, height),
+  return FloodPlanes{d_floor, d_ceiling, d_seeds, d_count_out, width, height, width * height, rdoom::flood_run_length(width, height),
                      params->max_step, params->max_drop, params->clearance};
 }
 
 }  // namespace
 
 static_assert(sizeof(rdoom_flood_params) == 16, "ABI sizes");
+
+// the cells of a row or column one thread sweeps at a time: the shortest runs that give every thread at most one run of a phase,
+// where the grid's shape allows that
+uint32_t rdoom::flood_run_length(uint32_t width, uint32_t height) {
+  uint32_t seg = 2;
+  while (seg < MAX_SEG && ((uint64_t)height * ((width + seg - 1) / seg) > THREADS || (uint64_t)width * ((height + seg - 1) / seg) > THREADS)) seg++;
+  return seg;
+}
 
 // what rdoom_flood_grids and rdoom_flood_descend (path.hip) check of the arguments they share
 rdoom_status rdoom::check_flood_grids(const rdoom_flood_params *params, uint32_t n, bool pointers, const char *missing, uint32_t width,

@@ -286,4 +286,32 @@ struct WallArgs {
   float clearance;
 };
 
+// Kernels 20 and 21: the octile walking distance (octile.hip; include/rdoom.h "octile distance" has the contract).
+// 20: grids flooded over moves to the eight neighbours, one workgroup per grid.  The distances live in dist_out, the eight move
+// bits of a cell in the top byte of its word while the kernel runs.
+struct FloodOctileArgs {
+  const float *floor, *ceiling;  // n x height x width each
+  const int32_t *seeds;          // n x (column, row), or null: (width / 2, height / 2)
+  uint32_t *count_out;           // n, or null
+  uint32_t *dist_out;            // n x height x width
+  uint32_t width, height;
+  uint32_t seg;                  // cells of a row, column or diagonal one thread sweeps at a time
+  uint32_t towards;              // RDOOM_FLOOD_TOWARDS: the move relation is followed backwards
+  uint32_t axial_cost, diagonal_cost;
+  float max_step, max_drop, clearance;
+};
+// 21: an octile field walked downhill from a start, one wavefront per row; lanes 0 .. 7 test one neighbour each.
+struct DescendOctileArgs {
+  const float *floor, *ceiling;  // n x height x width each: the planes the field was flooded from
+  const uint32_t *dist;          // n x height x width: rdoom_flood_grids_octile's distances
+  const int32_t *starts;         // n x (column, row)
+  int32_t *cells_out;            // n x (column, row)
+  uint32_t *moves_out;           // n
+  int32_t *path_out;             // n x path_len x (column, row), or null
+  uint32_t n, width, height, path_len;
+  uint32_t max_moves, stop_dist;
+  uint32_t axial_cost, diagonal_cost;
+  float max_step, max_drop, clearance;
+};
+
 }  // namespace rdoom_dev

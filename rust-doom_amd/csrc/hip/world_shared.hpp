@@ -295,5 +295,7 @@ inline rdoom_status handle_grid(const rdoom_world *w, const rdoom_worldset *set,
 // `pointers`, whether the caller's required pointers are there (`missing` names them)
 rdoom_status check_flood_grids(const rdoom_flood_params *params, uint32_t n, bool pointers, const char *missing, uint32_t width,
                                uint32_t height);
+// flood.hip: the cells of a row or column (octile.hip: or diagonal) one thread of a grid's flood sweeps at a time
+uint32_t flood_run_length(uint32_t width, uint32_t height);
 
 }  // namespace rdoom
