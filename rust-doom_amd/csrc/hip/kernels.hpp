@@ -182,14 +182,14 @@ struct LightTableArgs {
 };
 rdoom_status launch_light_tables(hipStream_t st, const LightTableArgs &args);
 
-// Kernels 12 and 16: the two distance floods (flood.hip; include/rdoom.h "flood" and "goal distance" have the contracts).  One
-// workgroup per grid.  What both take:
+// Kernels 12, 16 and 20: the three distance floods (flood.hip; include/rdoom.h "flood", "goal distance" and "octile distance" have
+// the contracts).  One workgroup per grid.  What all take:
 struct FloodPlanes {
   const float *floor, *ceiling;  // n x height x width each, as rdoom_world_draw_sector_maps or rdoom_world_draw_area_planes stores them
   const int32_t *seeds;          // n x (column, row), or null: (width / 2, height / 2)
   uint32_t *count_out;           // n, or null
   uint32_t width, height, cells; // cells = width * height
-  uint32_t seg;                  // cells of a row or column one thread sweeps at a time
+  uint32_t seg;                  // cells of a row, column or diagonal one thread sweeps at a time
   float max_step, max_drop, clearance;
 };
 // 12: every player's sector map flooded from its seed; cells <= rdoom_flood_max_cells.  Dynamic LDS: a 16-bit distance and a byte
@@ -204,6 +204,11 @@ struct FloodGridArgs {
   FloodPlanes planes;
   uint32_t *dist_out;  // n x height x width
   uint32_t towards;    // RDOOM_FLOOD_TOWARDS: the move relation is followed backwards
+};
+// 20: such grids flooded over moves to the eight neighbours.  The eight move bits of a cell live in the top byte of its word while
+// the kernel runs.
+struct FloodOctileArgs : FloodGridArgs {
+  uint32_t axial_cost, diagonal_cost;
 };
 
 // Kernel 13: players reset at seeded random points of their level's floor (spawn.hip; include/rdoom.h "spawn" has the contract).  One
@@ -245,7 +250,8 @@ struct AreaCellArgs {
   float cell;
 };
 
-// Kernels 17 and 18: waypoints and frontiers (path.hip; include/rdoom.h "waypoints and frontiers" has the contract).
+// Kernels 17, 18 and 21: waypoints and frontiers (path.hip; include/rdoom.h "waypoints and frontiers" and "octile distance" have the
+// contracts).
 // 17: a flood's field walked downhill from a start, one wavefront per row; lanes 0 .. 3 test one neighbour each.
 struct DescendArgs {
   const float *floor, *ceiling;  // n x height x width each: the planes the field was flooded from
@@ -257,6 +263,10 @@ struct DescendArgs {
   uint32_t n, width, height, path_len;
   uint32_t max_moves, stop_dist;
   float max_step, max_drop, clearance;
+};
+// 21: an octile field (rdoom_flood_grids_octile's distances) walked the same way; lanes 0 .. 7 test one neighbour each.
+struct DescendOctileArgs : DescendArgs {
+  uint32_t axial_cost, diagonal_cost;
 };
 // 18: the frontier of every player's explored area, one workgroup per row; a thread takes 32 cells, a word of the bit planes, at a
 // time.
@@ -284,34 +294,6 @@ struct WallArgs {
   uint32_t radius, close_d2;          // R in cells; D2 <= close_d2 is void in the output planes
   uint32_t edge_open;                 // RDOOM_WALL_EDGE_OPEN: cells outside the grid do not block
   float clearance;
-};
-
-// Kernels 20 and 21: the octile walking distance (octile.hip; include/rdoom.h "octile distance" has the contract).
-// 20: grids flooded over moves to the eight neighbours, one workgroup per grid.  The distances live in dist_out, the eight move
-// bits of a cell in the top byte of its word while the kernel runs.
-struct FloodOctileArgs {
-  const float *floor, *ceiling;  // n x height x width each
-  const int32_t *seeds;          // n x (column, row), or null: (width / 2, height / 2)
-  uint32_t *count_out;           // n, or null
-  uint32_t *dist_out;            // n x height x width
-  uint32_t width, height;
-  uint32_t seg;                  // cells of a row, column or diagonal one thread sweeps at a time
-  uint32_t towards;              // RDOOM_FLOOD_TOWARDS: the move relation is followed backwards
-  uint32_t axial_cost, diagonal_cost;
-  float max_step, max_drop, clearance;
-};
-// 21: an octile field walked downhill from a start, one wavefront per row; lanes 0 .. 7 test one neighbour each.
-struct DescendOctileArgs {
-  const float *floor, *ceiling;  // n x height x width each: the planes the field was flooded from
-  const uint32_t *dist;          // n x height x width: rdoom_flood_grids_octile's distances
-  const int32_t *starts;         // n x (column, row)
-  int32_t *cells_out;            // n x (column, row)
-  uint32_t *moves_out;           // n
-  int32_t *path_out;             // n x path_len x (column, row), or null
-  uint32_t n, width, height, path_len;
-  uint32_t max_moves, stop_dist;
-  uint32_t axial_cost, diagonal_cost;
-  float max_step, max_drop, clearance;
 };
 
 }  // namespace rdoom_dev

@@ -1,16 +1,19 @@
 // Waypoints and frontiers (include/rdoom.h "waypoints and frontiers"): a flood's distance field walked downhill
-// from a start (rdoom_flood_descend), and the frontier of every player's explored area with its nearest cell
+// from a start (rdoom_flood_descend; down an octile field, include/rdoom.h "octile distance" and DESIGN section 26,
+// rdoom_flood_descend_octile), and the frontier of every player's explored area with its nearest cell
 // (rdoom_world_area_frontiers, rdoom_worldset_area_frontiers).
 //
 // Arithmetic: binary32, the contract's operations in the contract's order; the build passes -ffp-contract=off.  The grid formulas
-// and the open and move comparisons are world_shared.hpp's, the ones flood.hip floods with.
+// and the open and move comparisons are world_shared.hpp's, the ones flood.hip floods with.  Costs and distances are integers.
 //
-// flood_descend: one wavefront per row, four rows to a 256-thread workgroup.  Lanes 0 .. 3 each test one neighbour of the current
-// cell, in the contract's order: its distance, the two cells' floors and ceilings, the comparisons.  A ballot's lowest set bit is
-// the contract's first qualifying neighbour, one scalar for the whole wave, so the walk's state -- the cell, its distance, the
-// moves made -- is wave-uniform.
+// flood_descend: one wavefront per row, four rows to a 256-thread workgroup.  Lanes 0 .. 3 (octile: 0 .. 7) each test one
+// neighbour of the current cell, in the contract's order: its distance, the two cells' floors and ceilings, the comparisons -- for
+// a diagonal the four axial moves through the two cells between them.  A ballot's lowest set bit is the contract's first
+// qualifying neighbour, one scalar for the whole wave, so the walk's state -- the cell, its distance, the moves made -- is
+// wave-uniform.
 // Termination: the loop's bound is computed before the loop as min(max_moves, D(start) - stop_dist); every iteration makes one
-// move to a cell whose distance is one less, or breaks.  No barrier, no LDS, no atomic; nothing waits on anything.
+// move to a cell whose distance is one less (octile: at least one less, a cost is at least 1), or breaks.  No barrier, no LDS, no
+// atomic; nothing waits on anything.
 //
 // area_frontiers: one 1024-thread workgroup per row.  A thread takes a 32-cell word of the bit planes at a time: the cells with an
 // unknown neighbour come from the FREE and WALL words of the row above, the row itself and the row below, the shifts carrying in
@@ -30,6 +33,7 @@ namespace {
 
 using rdoom_dev::allowed;
 using rdoom_dev::DescendArgs;
+using rdoom_dev::DescendOctileArgs;
 using rdoom_dev::FrontierArgs;
 using rdoom_dev::Grid;
 using rdoom_dev::grid_of;
@@ -42,8 +46,20 @@ constexpr uint32_t UNREACHED = RDOOM_FLOOD_GRID_UNREACHED;
 constexpr uint32_t DESCEND_THREADS = 256, DESCEND_ROWS = DESCEND_THREADS / WAVE;
 constexpr uint32_t MAX_PATH = 1u << 22;
 
-template <bool TOWARDS>
-__device__ __forceinline__ void descend_row(const DescendArgs &a) {
+// neighbour k's offset, in the contract's order: 0 .. 3 are (column - 1, column + 1, row - 1, row + 1), and with OCTILE 4 .. 7 the
+// offsets (-1, -1), (+1, -1), (-1, +1), (+1, +1)
+template <bool OCTILE>
+__device__ __forceinline__ int32_t column_step(uint32_t k) {
+  return OCTILE && k >= 4 ? ((k & 1u) ? 1 : -1) : (k == 0 ? -1 : (k == 1 ? 1 : 0));
+}
+template <bool OCTILE>
+__device__ __forceinline__ int32_t row_step(uint32_t k) {
+  return OCTILE && k >= 4 ? ((k & 2u) ? 1 : -1) : (k == 2 ? -1 : (k == 3 ? 1 : 0));
+}
+
+// the wave's row walked.  Without OCTILE a move costs 1 and `axial` is the literal; stop_dist is in cost units
+template <bool TOWARDS, bool OCTILE>
+__device__ __forceinline__ void descend_row(const DescendArgs &a, uint32_t axial, uint32_t diagonal) {
   const uint32_t lane = threadIdx.x & (WAVE - 1);
   const uint32_t p = blockIdx.x * DESCEND_ROWS + threadIdx.x / WAVE;  // the wave's row
   if (p >= a.n) return;
@@ -60,23 +76,35 @@ __device__ __forceinline__ void descend_row(const DescendArgs &a) {
   uint32_t m = 0;
   if (d == UNREACHED) col = -1, row = -1;
   else {
-    // the neighbour this lane tests: lanes 0 .. 3 are (column - 1, column + 1, row - 1, row + 1)
-    const int32_t dc = lane == 0 ? -1 : (lane == 1 ? 1 : 0), dr = lane == 2 ? -1 : (lane == 3 ? 1 : 0);
+    const int32_t dc = column_step<OCTILE>(lane), dr = row_step<OCTILE>(lane);  // the neighbour this lane tests
+    const uint32_t cost = OCTILE && lane >= 4 ? diagonal : axial;               // and what the move to it costs
     const uint32_t bound = d > a.stop_dist ? min(a.max_moves, d - a.stop_dist) : 0u;
-    for (; m < bound; m++) {
+    for (; m < bound && (!OCTILE || d > a.stop_dist); m++) {  // (a move that costs 1: the bound says it all)
       bool ok = false;
       const uint32_t bc = (uint32_t)(col + dc), br = (uint32_t)(row + dr);  // (outside: far above W, H)
-      if (lane < 4 && bc < W && br < H) {
+      if (lane < (OCTILE ? 8u : 4u) && bc < W && br < H) {
         const uint32_t at = (uint32_t)row * W + (uint32_t)col, b = br * W + bc;
         const uint32_t db = dist[b];
-        const float fa = floor[at], ga = ceiling[at], fb = floor[b], gb = ceiling[b];
-        ok = db == d - 1u && (TOWARDS ? allowed(fa, ga, fb, gb, lim) : allowed(fb, gb, fa, ga, lim));
+        if constexpr (!OCTILE) {  // (its own expression, not the one below with a cost of 1: that one compiles to more)
+          const float fa = floor[at], ga = ceiling[at], fb = floor[b], gb = ceiling[b];
+          ok = db == d - 1u && (TOWARDS ? allowed(fa, ga, fb, gb, lim) : allowed(fb, gb, fa, ga, lim));
+        } else if (db <= d && d - db == cost) {  // D(b) + cost == D(a), in integers: an unreached b is above every D(a) walked from
+          // the move of the field's relation between cells x and y, y the one nearer the seed
+          auto move = [&](uint32_t x, uint32_t y) {
+            return TOWARDS ? allowed(floor[x], ceiling[x], floor[y], ceiling[y], lim) : allowed(floor[y], ceiling[y], floor[x], ceiling[x], lim);
+          };
+          if (lane < 4) ok = move(at, b);
+          else {
+            const uint32_t s1 = (uint32_t)row * W + bc, s2 = br * W + (uint32_t)col;  // inside the grid with a and b
+            ok = move(at, s1) && move(s1, b) && move(at, s2) && move(s2, b);
+          }
+        }
       }
       const uint64_t qualify = __builtin_amdgcn_ballot_w64(ok);
       if (qualify == 0) break;  // (only on a field that was not flooded from these planes)
       const uint32_t k = (uint32_t)__builtin_ctzll(qualify);
-      col += k == 0 ? -1 : (k == 1 ? 1 : 0), row += k == 2 ? -1 : (k == 3 ? 1 : 0);
-      d -= 1u;
+      col += column_step<OCTILE>(k), row += row_step<OCTILE>(k);
+      d -= OCTILE && k >= 4 ? diagonal : axial;
       if (path && lane == 0 && m < a.path_len) path[2 * (size_t)m] = col, path[2 * (size_t)m + 1] = row;
     }
   }
@@ -88,8 +116,14 @@ __device__ __forceinline__ void descend_row(const DescendArgs &a) {
     for (size_t k = 2 * (size_t)min(m, a.path_len) + lane; k < 2 * (size_t)a.path_len; k += WAVE) path[k] = -1;  // a lane a word
 }
 
-__global__ __launch_bounds__(DESCEND_THREADS) void flood_descend_kernel(DescendArgs a) { descend_row<false>(a); }
-__global__ __launch_bounds__(DESCEND_THREADS) void flood_descend_towards_kernel(DescendArgs a) { descend_row<true>(a); }
+__global__ __launch_bounds__(DESCEND_THREADS) void flood_descend_kernel(DescendArgs a) { descend_row<false, false>(a, 1u, 1u); }
+__global__ __launch_bounds__(DESCEND_THREADS) void flood_descend_towards_kernel(DescendArgs a) { descend_row<true, false>(a, 1u, 1u); }
+__global__ __launch_bounds__(DESCEND_THREADS) void flood_descend_octile_kernel(DescendOctileArgs a) {
+  descend_row<false, true>(a, a.axial_cost, a.diagonal_cost);
+}
+__global__ __launch_bounds__(DESCEND_THREADS) void flood_descend_octile_towards_kernel(DescendOctileArgs a) {
+  descend_row<true, true>(a, a.axial_cost, a.diagonal_cost);
+}
 
 // ---- the frontier of an explored area ----
 constexpr uint32_t THREADS = 1024;
@@ -206,6 +240,17 @@ __global__ __launch_bounds__(THREADS) void worldset_area_frontiers_kernel(Fronti
 }
 
 // ---- the host's side ----
+// what both walks check of the path, and the arguments they share as the kernels take them
+rdoom_status descend_args(const float *d_floor, const float *d_ceiling, const uint32_t *d_dist, uint32_t n, uint32_t width, uint32_t height,
+                          const int32_t *d_starts, float max_step, float max_drop, float clearance, uint32_t max_moves, uint32_t stop_dist,
+                          int32_t *d_cells_out, uint32_t *d_moves_out, int32_t *d_path_out, uint32_t path_len, DescendArgs &a) {
+  if (d_path_out && (path_len == 0 || path_len > MAX_PATH))
+    return rdoom::fail(RDOOM_BAD_ARG, "a path of %u entries: 1 to %u", path_len, MAX_PATH);
+  a = DescendArgs{d_floor, d_ceiling, d_dist, d_starts, d_cells_out, d_moves_out, d_path_out, n, width, height, d_path_out ? path_len : 0u,
+                  max_moves, stop_dist, max_step, max_drop, clearance};
+  return RDOOM_OK;
+}
+
 // the arguments of a frontier call, checked, as the kernel takes them.  noun: "world" or "world set"
 rdoom_status frontier_args(const rdoom::MapSource &src, const rdoom_world *w, const rdoom_worldset *set, const char *noun, uint32_t n, float cell,
                            uint32_t width, uint32_t height, const uint32_t *d_area, uint32_t stride, const uint32_t *d_dist, int32_t *d_cell_out,
@@ -235,14 +280,32 @@ rdoom_status rdoom_flood_descend(const float *d_floor, const float *d_ceiling, c
   if (rdoom_status s = rdoom::check_flood_grids(params, n, d_floor && d_ceiling && d_dist && d_starts && d_cells_out && d_moves_out,
                                                 "floor, ceiling, distances, starts, cell output or move output", width, height))
     return s;
-  if (d_path_out && (path_len == 0 || path_len > MAX_PATH))
-    return rdoom::fail(RDOOM_BAD_ARG, "a path of %u entries: 1 to %u", path_len, MAX_PATH);
+  DescendArgs a;
+  if (rdoom_status s = descend_args(d_floor, d_ceiling, d_dist, n, width, height, d_starts, params->max_step, params->max_drop, params->clearance,
+                                    max_moves, stop_dist, d_cells_out, d_moves_out, d_path_out, path_len, a))
+    return s;
   if (!n) return RDOOM_OK;
-  const DescendArgs a{d_floor, d_ceiling, d_dist, d_starts, d_cells_out, d_moves_out, d_path_out, n, width, height, d_path_out ? path_len : 0u,
-                      max_moves, stop_dist, params->max_step, params->max_drop, params->clearance};
   const dim3 blocks((n + DESCEND_ROWS - 1) / DESCEND_ROWS);
   if (params->flags & RDOOM_FLOOD_TOWARDS) return rdoom::launch_checked(flood_descend_towards_kernel, blocks, dim3(DESCEND_THREADS), 0, stream, a);
   return rdoom::launch_checked(flood_descend_kernel, blocks, dim3(DESCEND_THREADS), 0, stream, a);
+}
+
+rdoom_status rdoom_flood_descend_octile(const float *d_floor, const float *d_ceiling, const uint32_t *d_dist, uint32_t n, uint32_t width,
+                                        uint32_t height, const int32_t *d_starts, const rdoom_flood_octile_params *params,
+                                        uint32_t max_moves, uint32_t stop_dist, int32_t *d_cells_out, uint32_t *d_moves_out,
+                                        int32_t *d_path_out, uint32_t path_len, void *stream) {
+  if (rdoom_status s = rdoom::check_flood_octile(params, n, d_floor && d_ceiling && d_dist && d_starts && d_cells_out && d_moves_out,
+                                                 "floor, ceiling, distances, starts, cell output or move output", width, height))
+    return s;
+  DescendOctileArgs a{{}, params->axial_cost, params->diagonal_cost};
+  if (rdoom_status s = descend_args(d_floor, d_ceiling, d_dist, n, width, height, d_starts, params->max_step, params->max_drop, params->clearance,
+                                    max_moves, stop_dist, d_cells_out, d_moves_out, d_path_out, path_len, a))
+    return s;
+  if (!n) return RDOOM_OK;
+  const dim3 blocks((n + DESCEND_ROWS - 1) / DESCEND_ROWS);
+  if (params->flags & RDOOM_FLOOD_TOWARDS)
+    return rdoom::launch_checked(flood_descend_octile_towards_kernel, blocks, dim3(DESCEND_THREADS), 0, stream, a);
+  return rdoom::launch_checked(flood_descend_octile_kernel, blocks, dim3(DESCEND_THREADS), 0, stream, a);
 }
 
 rdoom_status rdoom_world_area_frontiers(const rdoom_world *w, uint32_t n, float cell, uint32_t width, uint32_t height, const uint32_t *d_area,

@@ -155,7 +155,7 @@ __device__ __forceinline__ bool point_cell(const Grid &g, float cell, float x, f
 }
 
 // ---- walking on a grid of floor and ceiling planes (include/rdoom.h "goal distance": "Open", "Moves"), the one definition the
-// two floods (flood.hip), the walk down their field (path.hip) and the wall distance (walls.hip, is_open alone) share; the units
+// floods (flood.hip), the walk down their field (path.hip) and the wall distance (walls.hip, is_open alone) share; the units
 // that use them turn contraction off ----
 struct WalkLimits {
   float max_step, max_drop, clearance;
@@ -295,7 +295,10 @@ inline rdoom_status handle_grid(const rdoom_world *w, const rdoom_worldset *set,
 // `pointers`, whether the caller's required pointers are there (`missing` names them)
 rdoom_status check_flood_grids(const rdoom_flood_params *params, uint32_t n, bool pointers, const char *missing, uint32_t width,
                                uint32_t height);
-// flood.hip: the cells of a row or column (octile.hip: or diagonal) one thread of a grid's flood sweeps at a time
+// flood.hip: what rdoom_flood_grids_octile and rdoom_flood_descend_octile check: the same, then the two costs
+rdoom_status check_flood_octile(const rdoom_flood_octile_params *params, uint32_t n, bool pointers, const char *missing, uint32_t width,
+                                uint32_t height);
+// flood.hip: the cells of a row, column or diagonal one thread of a grid's flood sweeps at a time
 uint32_t flood_run_length(uint32_t width, uint32_t height);
 
 }  // namespace rdoom

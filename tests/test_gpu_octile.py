@@ -1,4 +1,4 @@
-"""The octile distance on the GPU (octile.hip: flood_octile_kernel and the two flood_descend_octile kernels) against
+"""The octile distance on the GPU (flood.hip: flood_octile_kernel; path.hip: the two flood_descend_octile kernels) against
 tests/octile_ref.py, every element of every output, bit for bit.  The grids written out by hand; every 7 x 5 hand grid from each of
 its 35 seeds in both directions, fifteen rows a launch, with four pairs of costs; costs (5, 10) against five times flood_grids on the
 grids that take many passes; 1 x 1, and the longest single runs from either end; random rooms whose rows, columns and diagonals are

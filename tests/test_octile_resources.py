@@ -1,4 +1,4 @@
-"""The octile distance's kernels as shipped (rust-doom_amd/csrc/hip/octile.hip): the flood and the two descents are in the library,
+"""The octile distance's kernels as shipped (rust-doom_amd/csrc/hip/flood.hip, path.hip): the flood and the two descents are in the library,
 use no scratch memory, spill no register and leave room for four waves per SIMD; the flood keeps a workgroup of 1024 threads and
 its LDS to the two flags and the waves' counts -- its distances and move bits live in global memory, whatever the grid's size.  The
 kernels of the 4-neighbour calls are still there beside them."""
