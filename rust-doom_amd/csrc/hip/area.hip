@@ -6,8 +6,8 @@
 // grid formulas are one host-and-device function: the host checks the limits with it, the kernels index with it.
 //
 // reveal_area: one 256-thread workgroup per player, the fan taken 256 rays at a time.  A pass over that many rays:
-// Sight limits.  T_r of every ray, reveal.hip's phase 1 restated here (the same cull, list and minimum, so the same bits): that unit's
-// kernels stay as they are.
+// Sight limits.  T_r of every ray: sight.hpp's sight_limits, the one pass this unit and reveal.hip share, over this kernel's LDS
+// arrays.
 // Window.  The samples of the pass fall into a window of the grid that is known before any is taken: the word-aligned columns and the
 // rows between the cells of pos -+ the largest |vel| component of the pass, clipped to the grid (axis_window: exact, no margin is
 // needed).  The two bit planes of the window live in LDS, WINDOW_WORDS words for both; a window with more rows than that holds is
@@ -24,22 +24,20 @@
 #include "../common.hpp"
 #include "kernels.hpp"
 #include "player_quat.hpp"
+#include "sight.hpp"
 #include "world_shared.hpp"
 
 #pragma clang fp contract(off)
 
 namespace {
 
-using rdoom_dev::BOTH_SIDES;
-using rdoom_dev::dist2;
-using rdoom_dev::live_height;
 using rdoom_dev::sincos_rd;
-using rdoom_dev::with_level;
+using rdoom_dev::wave_max;
+using rdoom_dev::wave_sum;
 
-constexpr uint32_t WAVE = 64, THREADS = 256, WAVES = THREADS / WAVE;
-constexpr float CULL_MARGIN = 9.765625e-4f;  // reveal.hip's
-constexpr uint32_t WINDOW_WORDS = 4096;      // the LDS window, both planes: 16 KiB of the unit's 25
-constexpr uint32_t CHUNK = 32;               // the steps of a sampling item
+constexpr uint32_t WAVE = 64, THREADS = rdoom_dev::SIGHT_THREADS, WAVES = THREADS / WAVE;
+constexpr uint32_t WINDOW_WORDS = 4096;  // the LDS window, both planes: 16 KiB of the unit's 25
+constexpr uint32_t CHUNK = 32;           // the steps of a sampling item
 
 // ---- the grid of a level (the contract's formulas; host and device): world_shared.hpp's, which goal.hip reads too ----
 using rdoom_dev::cell_of;
@@ -54,34 +52,10 @@ struct AreaArgs {
   const float *dirs;     // n_rays x (right, forward): a caller's floats, dword aligned and no more
   uint32_t *area;        // n x 2 x stride words
   uint32_t *new_out;     // n x 2, or null
-  const float4 *seg;
-  const float4 *heights;
-  const uint4 *ids;
-  const uint32_t *flags;
+  rdoom_dev::LineTable lines;
   uint32_t n_objects, n_rays, stride, n_steps;
   float max_range, cell;
 };
-
-// the contract's ray against line, as reveal.hip has it
-__device__ __forceinline__ bool ray_hits(float wx, float wz, float dx, float dz, float vx, float vz, float &t) {
-  const float den = vx * dz - vz * dx;
-  t = (wx * dz - wz * dx) / den;
-  const float u = (wx * vz - wz * vx) / den;
-  return den != 0.0f && u >= 0.0f && u <= 1.0f && t >= 0.0f && t <= 1.0f;
-}
-
-// what a thread reads of a line for player position (px, pz), as reveal.hip has it: conservative, so it cannot change a minimum
-struct Near {
-  float wx, wz, dx, dz;
-  bool ok;
-};
-__device__ __forceinline__ Near near_line(const float4 e, float px, float pz, float reach, float player_size) {
-  const float dx = e.z - e.x, dz = e.w - e.y;
-  const float len2 = dx * dx + dz * dz;
-  const float size = player_size + ((__builtin_fabsf(e.x) + __builtin_fabsf(e.y)) + (__builtin_fabsf(e.z) + __builtin_fabsf(e.w)));
-  const float limit = reach + size * CULL_MARGIN;
-  return Near{e.x - px, e.y - pz, dx, dz, len2 > 0.0f && dist2(px, pz, e.x, e.y, dx, dz, 1.0f / len2) <= limit * limit};
-}
 
 // The cells [lo, hi] of the grid axis (first cell c0, n cells) that a sample o + t * vel can fall into when |vel| <= reach on this
 // axis: t * vel is within -+reach (|t| <= 1, reach is a binary32 and rounding is monotone), so the sum is within round(o - reach) and
@@ -102,17 +76,6 @@ __device__ __forceinline__ bool axis_window(float o, float reach, float cell, in
 // kept in a vector register, which costs nothing there and saves a scalar spill
 __device__ __forceinline__ float in_vgpr(float v) {
   asm("" : "+v"(v));
-  return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (uint32_t o = WAVE / 2; o; o >>= 1) v = __builtin_fmaxf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
-#pragma unroll
-  for (uint32_t o = WAVE / 2; o; o >>= 1) v += __shfl_xor(v, o);
   return v;
 }
 
@@ -158,60 +121,8 @@ __device__ __forceinline__ void reveal_area_player(const AreaArgs &a, uint32_t p
     const float reach_z = __builtin_fmaxf(__builtin_fmaxf(wave_reach[2][0], wave_reach[2][1]), __builtin_fmaxf(wave_reach[2][2], wave_reach[2][3]));
     const float player_size = (__builtin_fabsf(px) + __builtin_fabsf(pz)) + reach;
 
-    // ---- sight limits: thread (slice, ray) folds entries slice, slice + slices, ... of the list into its ray's minimum
-    const uint32_t slices = THREADS / nr, ray = tid % nr, slice = tid / nr;
-    const float4 mine = rays[ray];
-    float nearest = 1.0f;
-    for (uint32_t base = 0; base < n_lines; base += THREADS) {
-      const uint32_t l = base + tid;
-      bool keep = false;
-      Near e{};
-      if (l < n_lines) {
-        e = near_line(a.seg[first + l], px, pz, reach, player_size);
-        keep = e.ok;
-        if (keep && (a.flags[first + l] & BOTH_SIDES) == BOTH_SIDES) {  // two-sided: it blocks when its opening is empty
-          const float4 h = a.heights[first + l];
-          const uint4 o = a.ids[first + l];
-          const float ff = live_height(h.x, o.x, off, a.n_objects), fc = live_height(h.y, o.y, off, a.n_objects);
-          const float bf = live_height(h.z, o.z, off, a.n_objects), bc = live_height(h.w, o.w, off, a.n_objects);
-          const float lo = ff > bf ? ff : bf, hi = fc < bc ? fc : bc;
-          keep = !(hi > lo);
-        }
-      }
-      const uint64_t kept = __builtin_amdgcn_ballot_w64(keep);
-      const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(kept >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)kept, 0u));
-      if (lane == 0) wave_count[0][wave] = (uint32_t)__builtin_popcountll(kept);
-      __syncthreads();
-      uint32_t at = 0, total = 0;
-#pragma unroll
-      for (uint32_t w = 0; w < WAVES; w++) {
-        const uint32_t n = wave_count[0][w];
-        at += w < wave ? n : 0u;
-        total += n;
-      }
-      if (keep) list[at + before] = make_float4(e.wx, e.wz, e.dx, e.dz);  // at + before < total <= THREADS
-      __syncthreads();
-      if (total) {
-        if (slice < slices)
-          for (uint32_t k = slice; k < total; k += slices) {
-            const float4 b = list[k];
-            float t;
-            if (ray_hits(b.x, b.y, b.z, b.w, mine.x, mine.y, t)) nearest = t < nearest ? t : nearest;
-          }
-        __syncthreads();  // before the next lines overwrite the list
-      }
-    }
-    part[tid] = nearest;
-    __syncthreads();
-    if (tid < nr) {
-      float t = part[tid];
-      for (uint32_t k = 1; k < slices; k++) {
-        const float other = part[k * nr + tid];
-        t = other < t ? other : t;
-      }
-      rays[tid].z = t;
-    }
-    __syncthreads();
+    // ---- sight limits: T_r into rays[r].z
+    rdoom_dev::sight_limits(a.lines, off, a.n_objects, first, n_lines, px, pz, reach, player_size, nr, list, rays, part, wave_count[0]);
 
     // ---- the window of the pass: columns c_lo .. c_hi as whole words, rows r_lo .. r_hi, in bands of band_rows
     uint32_t c_lo = 0, c_hi = 0, r_lo = 0, r_hi = 0;
@@ -402,30 +313,22 @@ rdoom_status reveal_args(const rdoom::MapSource &src, const char *noun, const rd
                          uint32_t n_rays, float max_range, const float *d_offsets, uint32_t n_objects, float cell, uint32_t n_steps,
                          uint32_t *d_area, uint32_t stride, uint32_t *d_new_out, AreaArgs &a) {
   if (n && (!d_states || !d_area || !d_dirs)) return rdoom::fail(RDOOM_BAD_ARG, "null states, area rows or directions with n = %u", n);
-  if (!n_rays) return rdoom::fail(RDOOM_BAD_ARG, "n_rays is 0");
-  if (!(max_range > 0.0f) || max_range == __builtin_inff())
-    return rdoom::fail(RDOOM_BAD_ARG, "max_range %g is not a finite positive number", (double)max_range);
+  if (rdoom_status s = rdoom::check_fan(n_rays, max_range)) return s;
   if (!n_steps || n_steps > RDOOM_AREA_MAX_STEPS) return rdoom::fail(RDOOM_BAD_ARG, "n_steps %u (1 .. %u)", n_steps, RDOOM_AREA_MAX_STEPS);
   if (rdoom_status s = check_area_rows(src, noun, cell, stride)) return s;
-  if (d_offsets && n_objects < src.game_objects)
-    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the %s's %u objects", n_objects, noun, src.game_objects);
+  if (rdoom_status s = rdoom::check_offsets(d_offsets, n_objects, src.game_objects, noun)) return s;
   if (n > 0x7FFFFFFFu) return rdoom::fail(RDOOM_BAD_ARG, "%u players: too many for one launch", n);
   const rdoom::MapDevice &d = *src.map;
-  a = AreaArgs{d_states, d_offsets, d_dirs, d_area, d_new_out, d.seg, d.heights, d.ids, d.flags, n_objects, n_rays, stride, n_steps,
+  a = AreaArgs{d_states, d_offsets, d_dirs, d_area, d_new_out, {d.seg, d.heights, d.ids, d.flags}, n_objects, n_rays, stride, n_steps,
                max_range, cell};
   return RDOOM_OK;
 }
-
-constexpr uint32_t MAX_SIDE = 16384;  // of a map, as automap.hip has it
 
 rdoom_status map_args(const rdoom::MapSource &src, const char *noun, const rdoom_player_state *d_states, uint32_t n, const rdoom_map_view *view,
                       const uint32_t *d_area, uint32_t stride, float cell, uint8_t *d_out, AreaMapArgs &a) {
   if (!view) return rdoom::fail(RDOOM_BAD_ARG, "null view");
   if (n && (!d_states || !d_area || !d_out)) return rdoom::fail(RDOOM_BAD_ARG, "null states, area rows or output with n = %u", n);
-  if (!view->width || !view->height || view->width > MAX_SIDE || view->height > MAX_SIDE)
-    return rdoom::fail(RDOOM_BAD_ARG, "a map of %u x %u pixels (1 .. %u a side)", view->width, view->height, MAX_SIDE);
-  if (!(view->scale > 0.0f) || view->scale == __builtin_inff())
-    return rdoom::fail(RDOOM_BAD_ARG, "scale %g is not a finite positive number", (double)view->scale);
+  if (rdoom_status s = rdoom::check_view(view)) return s;
   if (view->flags & ~(RDOOM_MAP_ROTATE | RDOOM_MAP_TOP_DOWN)) return rdoom::fail(RDOOM_BAD_ARG, "map flags 0x%x: an area map takes ROTATE and TOP_DOWN", view->flags);
   if (rdoom_status s = check_area_rows(src, noun, cell, stride)) return s;
   const uint32_t blocks = (view->width * view->height + THREADS - 1) / THREADS;

@@ -8,9 +8,10 @@
 //
 // Shape: one 256-thread workgroup per (player, 32 x 32 pixel tile).  The threads stride over the level's lines, 256 at a time,
 // and keep those that can touch the tile -- a distance test against the tile's centre, conservative under rounding (cull_margin)
-// -- in a list in LDS, appended with a wave ballot and a prefix over the four waves; a kept line's class is computed then, once,
-// from the player's object offsets.  Each thread then folds its four pixels over the list: the pixel value is a maximum, so the
-// order of the list and where it is cut do not matter, and a list that would outgrow LDS is folded and emptied in between.
+// -- in a list in LDS, appended with a wave ballot and a prefix over the four waves (world_shared.hpp's append, which the sight
+// pass of reveal.hip and area.hip calls too); a kept line's class is computed then, once, from the player's object offsets.
+// Each thread then folds its four pixels over the list: the pixel value is a maximum, so the order of the list and where it is
+// cut do not matter, and a list that would outgrow LDS is folded and emptied in between.
 // A wave holds two rows of 32 pixels: its byte stores are two runs of 32 consecutive bytes.
 #include <hip/hip_runtime.h>
 
@@ -119,23 +120,12 @@ __device__ __forceinline__ void draw_tile(const MapArgs &a, uint32_t p, uint32_t
         keep = cls != RDOOM_MAP_FLAT || show_flat;
       }
     }
-    // append the kept lines: a ballot and a prefix within the wave, the waves' counts through LDS
-    const uint64_t kept = __builtin_amdgcn_ballot_w64(keep);
-    const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(kept >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)kept, 0u));
-    if (lane == 0) wave_kept[wave] = (uint32_t)__builtin_popcountll(kept);
-    __syncthreads();
-    uint32_t at = count, total = 0;
-#pragma unroll
-    for (uint32_t w = 0; w < WAVES; w++) {
-      const uint32_t n = wave_kept[w];
-      at += w < wave ? n : 0u;
-      total += n;
+    const rdoom_dev::Appended kept = rdoom_dev::append<WAVES>(keep, lane, wave, wave_kept, count);
+    if (keep) {  // count <= LIST_CAP - THREADS here, so kept.slot < LIST_CAP
+      list_seg[kept.slot] = make_float4(g.ax, g.az, g.dx, g.dz);
+      list_aux[kept.slot] = make_float2(g.inv, __uint_as_float(cls));
     }
-    if (keep) {  // count <= LIST_CAP - THREADS here, so at + before < LIST_CAP
-      list_seg[at + before] = make_float4(g.ax, g.az, g.dx, g.dz);
-      list_aux[at + before] = make_float2(g.inv, __uint_as_float(cls));
-    }
-    count += total;
+    count += kept.total;
     const bool fold = count > LIST_CAP - THREADS || base + THREADS >= n_lines;  // the next 256 might not fit, or there are none
     __syncthreads();
     if (fold) {
@@ -188,14 +178,6 @@ __global__ __launch_bounds__(THREADS) void worldset_draw_maps_kernel(MapArgs a, 
   draw_tile(a, p, blockIdx.x % a.tiles, first, n_lines, lv >= n_levels);
 }
 
-template <class T>
-rdoom_status upload(T **dst, const std::vector<T> &src) {
-  HIP_TRY(hipMalloc((void **)dst, src.empty() ? 16 : src.size() * sizeof(T)));  // (no lines: a valid, unread pointer)
-  if (!src.empty()) HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  return RDOOM_OK;
-}
-
-constexpr uint32_t MAX_SIDE = 16384;
 constexpr uint32_t KNOWN_FLAGS = RDOOM_MAP_ROTATE | RDOOM_MAP_SHOW_FLAT | RDOOM_MAP_SHOW_HIDDEN | RDOOM_MAP_TOP_DOWN;
 
 // the arguments of a draw, checked, as the kernel takes them.  noun: "world" or "world set"
@@ -204,17 +186,14 @@ rdoom_status map_args(const rdoom::MapSource &src, const char *noun, const rdoom
                       uint8_t *d_out, MapArgs &a) {
   if (!view) return rdoom::fail(RDOOM_BAD_ARG, "null view");
   if (n && (!d_states || !d_out)) return rdoom::fail(RDOOM_BAD_ARG, "null states or output with n = %u", n);
-  if (!view->width || !view->height || view->width > MAX_SIDE || view->height > MAX_SIDE)
-    return rdoom::fail(RDOOM_BAD_ARG, "a map of %u x %u pixels (1 .. %u a side)", view->width, view->height, MAX_SIDE);
+  if (rdoom_status s = rdoom::check_view(view)) return s;
   const float inf = __builtin_inff();
-  if (!(view->scale > 0.0f) || view->scale == inf) return rdoom::fail(RDOOM_BAD_ARG, "scale %g is not a finite positive number", (double)view->scale);
   if (!(view->half_width > 0.0f) || view->half_width == inf)
     return rdoom::fail(RDOOM_BAD_ARG, "half_width %g is not a finite positive number", (double)view->half_width);
   if (!(view->marker >= 0.0f) || view->marker == inf)
     return rdoom::fail(RDOOM_BAD_ARG, "marker %g is not a finite non-negative number", (double)view->marker);
   if (view->flags & ~KNOWN_FLAGS) return rdoom::fail(RDOOM_BAD_ARG, "unknown map flags 0x%x", view->flags);
-  if (d_offsets && n_objects < src.game_objects)
-    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the %s's %u objects", n_objects, noun, src.game_objects);
+  if (rdoom_status s = rdoom::check_offsets(d_offsets, n_objects, src.game_objects, noun)) return s;
   if (d_seen)
     if (rdoom_status s = rdoom::check_seen_stride(src, noun, stride)) return s;
   const uint32_t tiles_x = (view->width + TILE - 1) / TILE, tiles_y = (view->height + TILE - 1) / TILE;
@@ -254,8 +233,7 @@ rdoom_status map_upload(const std::vector<rdoom_map_line> &lines, const std::vec
 }
 
 void map_free(MapDevice &d) {
-  for (void *p : {(void *)d.seg, (void *)d.heights, (void *)d.ids, (void *)d.flags, (void *)d.levels, (void *)d.bounds})
-    if (p) (void)hipFree(p);
+  free_all({d.seg, d.heights, d.ids, d.flags, d.levels, d.bounds});
   d = MapDevice{};
 }
 

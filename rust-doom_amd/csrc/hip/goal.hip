@@ -123,8 +123,7 @@ rdoom_status plane_args(const rdoom::MapSource &src, const rdoom_world *w, const
   const uint32_t blocks = (width * height + PLANE_THREADS - 1) / PLANE_THREADS;
   if ((uint64_t)n * blocks > 0x7FFFFFFFull)
     return rdoom::fail(RDOOM_BAD_ARG, "%u rows of %u x %u cells: too many for one launch", n, width, height);
-  if (d_offsets && n_objects < src.game_objects)
-    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the %s's %u objects", n_objects, noun, src.game_objects);
+  if (rdoom_status s = rdoom::check_offsets(d_offsets, n_objects, src.game_objects, noun)) return s;
   if (d_area && stride < most.words)
     return rdoom::fail(RDOOM_BAD_ARG, "a stride of %u words is smaller than the %u a plane of the %s's grid takes at cell %g", stride, most.words,
                        noun, (double)cell);

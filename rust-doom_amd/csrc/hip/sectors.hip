@@ -190,22 +190,12 @@ __global__ __launch_bounds__(THREADS) void worldset_draw_sector_maps_kernel(Sect
   draw_tile(a, p, blockIdx.x % a.tiles, lv, slot < n_levels);
 }
 
-template <class T>
-rdoom_status upload(T **dst, const std::vector<T> &src) {
-  HIP_TRY(hipMalloc((void **)dst, src.empty() ? 16 : src.size() * sizeof(T)));  // (no edges: a valid, unread pointer)
-  if (!src.empty()) HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  return RDOOM_OK;
-}
-
 SectorTables tables(const rdoom::SectorDevice &d) { return SectorTables{d.nodes, d.leaves, d.edges, d.sectors}; }
-
-constexpr uint32_t MAX_SIDE = 16384;
 
 // what both calls check of the game's offsets and of the rows of visited bits.  noun: "world" or "world set"
 rdoom_status check_rows(const rdoom::MapSource &src, const char *noun, const float *d_offsets, uint32_t n_objects, const uint32_t *d_visited,
                         uint32_t stride) {
-  if (d_offsets && n_objects < src.game_objects)
-    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the %s's %u objects", n_objects, noun, src.game_objects);
+  if (rdoom_status s = rdoom::check_offsets(d_offsets, n_objects, src.game_objects, noun)) return s;
   if (d_visited && stride < rdoom::visited_words(src))
     return rdoom::fail(RDOOM_BAD_ARG, "a stride of %u words is smaller than the %u a row of the %s's %u sectors takes", stride,
                        rdoom::visited_words(src), noun, src.max_sectors);
@@ -228,10 +218,7 @@ rdoom_status map_args(const rdoom::MapSource &src, const char *noun, const rdoom
   if (!view) return rdoom::fail(RDOOM_BAD_ARG, "null view");
   if (n && !d_states) return rdoom::fail(RDOOM_BAD_ARG, "null states with n = %u", n);
   if (n && !d_sector_out && !d_floor_out && !d_ceiling_out) return rdoom::fail(RDOOM_BAD_ARG, "no output plane: sector, floor and ceiling are all null");
-  if (!view->width || !view->height || view->width > MAX_SIDE || view->height > MAX_SIDE)
-    return rdoom::fail(RDOOM_BAD_ARG, "a map of %u x %u pixels (1 .. %u a side)", view->width, view->height, MAX_SIDE);
-  if (!(view->scale > 0.0f) || view->scale == __builtin_inff())
-    return rdoom::fail(RDOOM_BAD_ARG, "scale %g is not a finite positive number", (double)view->scale);
+  if (rdoom_status s = rdoom::check_view(view)) return s;
   if (view->flags & ~(RDOOM_MAP_ROTATE | RDOOM_MAP_TOP_DOWN)) return rdoom::fail(RDOOM_BAD_ARG, "map flags 0x%x: a sector map takes ROTATE and TOP_DOWN", view->flags);
   if (rdoom_status s = check_rows(src, noun, d_offsets, n_objects, d_visited, stride)) return s;
   const uint32_t tiles_x = (view->width + TILE - 1) / TILE, tiles_y = (view->height + TILE - 1) / TILE;
@@ -291,8 +278,7 @@ rdoom_status sector_upload(const std::vector<const game::World *> &levels, Secto
 }
 
 void sector_free(SectorDevice &d) {
-  for (void *p : {(void *)d.nodes, (void *)d.leaves, (void *)d.edges, (void *)d.sectors, (void *)d.levels})
-    if (p) (void)hipFree(p);
+  free_all({d.nodes, d.leaves, d.edges, d.sectors, d.levels});
   d = SectorDevice{};
 }
 

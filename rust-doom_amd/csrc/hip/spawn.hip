@@ -142,13 +142,6 @@ __global__ __launch_bounds__(WAVE) void worldset_spawn_players_kernel(SpawnArgs 
   });
 }
 
-template <class T>
-rdoom_status upload(T **dst, const std::vector<T> &src) {
-  HIP_TRY(hipMalloc((void **)dst, src.empty() ? 16 : src.size() * sizeof(T)));  // (an empty table: a valid, unread pointer)
-  if (!src.empty()) HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  return RDOOM_OK;
-}
-
 // ceil(log2(n)) + 1: the most steps the contract's search takes over n entries
 uint32_t search_steps(uint32_t n) {
   uint32_t steps = 1;
@@ -170,8 +163,7 @@ rdoom_status spawn_args(const rdoom::MapSource &src, const char *noun, rdoom_pla
   if (!(params->margin >= 0.0f)) return rdoom::fail(RDOOM_BAD_ARG, "margin %g is negative or not a number", (double)params->margin);
   if (!(params->clearance >= 0.0f)) return rdoom::fail(RDOOM_BAD_ARG, "clearance %g is negative or not a number", (double)params->clearance);
   if (!(params->max_step >= 0.0f)) return rdoom::fail(RDOOM_BAD_ARG, "max_step %g is negative or not a number", (double)params->max_step);
-  if (d_offsets && n_objects < src.game_objects)
-    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the %s's %u objects", n_objects, noun, src.game_objects);
+  if (rdoom_status s = rdoom::check_offsets(d_offsets, n_objects, src.game_objects, noun)) return s;
   const rdoom::SectorDevice &sd = *src.sectors;
   const rdoom::SpawnDevice &pd = *src.spawn;
   a = SpawnArgs{d_states, d_offsets, d_mask, d_episode, d_tries_out, sd.nodes, sd.edges, sd.sectors, sd.leaves, pd.cumulative, pd.corners,
@@ -207,8 +199,7 @@ rdoom_status spawn_upload(const std::vector<const game::World *> &levels, SpawnD
 }
 
 void spawn_free(SpawnDevice &d) {
-  for (void *p : {(void *)d.cumulative, (void *)d.corners, (void *)d.levels, (void *)d.starts})
-    if (p) (void)hipFree(p);
+  free_all({d.cumulative, d.corners, d.levels, d.starts});
   d = SpawnDevice{};
 }
 

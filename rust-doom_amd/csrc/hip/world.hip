@@ -909,8 +909,7 @@ rdoom_status upload_world(const rdoom::game::World &h, DevArrays &d) {
   return RDOOM_OK;
 }
 void free_world(DevArrays &d) {
-  for (void *p : {(void *)d.nodes, (void *)d.chunks, (void *)d.tris, (void *)d.verts, (void *)d.dynamics, (void *)d.triggers, (void *)d.effects})
-    if (p) (void)hipFree(p);
+  rdoom::free_all({d.nodes, d.chunks, d.tris, d.verts, d.dynamics, d.triggers, d.effects});
 }
 }  // namespace
 
@@ -1038,15 +1037,11 @@ rdoom_status check_game(bool set, uint32_t game_objects, const void *d_game, con
   if (!d_game || !d_offsets || (set && !d_levels))
     return rdoom::fail(RDOOM_BAD_ARG, "%s", set ? "null game state, object offsets or levels" : "null game state or object offsets");
   if ((uintptr_t)d_game % 16) return rdoom::fail(RDOOM_BAD_ARG, "the game state is not 16-byte aligned");
-  if (n_objects < game_objects)
-    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the %s's %u objects", n_objects, set ? "set" : "game", game_objects);
-  return RDOOM_OK;
+  return rdoom::check_offsets(d_offsets, n_objects, game_objects, set ? "set" : "game");
 }
 
 rdoom_status check_offsets(const rdoom_world *w, const float *offsets, uint32_t n_objects) {
-  if (offsets && n_objects < w->host.n_objects)
-    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the world's %u objects", n_objects, w->host.n_objects);
-  return RDOOM_OK;
+  return rdoom::check_offsets(offsets, n_objects, w->host.n_objects, "world");
 }
 
 // the arguments every step checks: states and inputs, and dt; resolves dt (0: 1/60) and the config (cfg null: the default) into c
@@ -1077,13 +1072,10 @@ GameLevel game_level(const GameView &g, void *d_game, float *d_offsets, const ui
 rdoom_status ray_args(const rdoom_player_state *d_states, uint32_t n, const float *d_dirs, uint32_t n_rays, float max_range,
                       const float *d_offsets, uint32_t n_objects, uint32_t world_objects, const char *noun, float *d_frac, uint32_t *d_hit,
                       float *d_origin, float *d_vel, RayArgs &a) {
-  if (n_rays == 0) return rdoom::fail(RDOOM_BAD_ARG, "n_rays is 0");
-  if (!(max_range > 0.0f) || max_range == __builtin_inff())
-    return rdoom::fail(RDOOM_BAD_ARG, "max_range %g is not a finite positive number", (double)max_range);
+  if (rdoom_status s = rdoom::check_fan(n_rays, max_range)) return s;
   if (!d_dirs) return rdoom::fail(RDOOM_BAD_ARG, "null ray directions");
   if (n && (!d_states || !d_frac)) return rdoom::fail(RDOOM_BAD_ARG, "null states or fraction output with n = %u", n);
-  if (d_offsets && n_objects < world_objects)
-    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the %s's %u objects", n_objects, noun, world_objects);
+  if (rdoom_status s = rdoom::check_offsets(d_offsets, n_objects, world_objects, noun)) return s;
   if ((uint64_t)n * n_rays > 0xFFFFFFFFull - WAVE) return rdoom::fail(RDOOM_BAD_ARG, "%u players x %u rays: too many for one launch", n, n_rays);
   a = RayArgs{d_states, d_dirs, d_offsets, d_frac, d_hit, d_origin, d_vel, n_rays, n_objects, n * n_rays, max_range};
   return RDOOM_OK;

@@ -1,9 +1,12 @@
 // What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip), the explored area's (area.hip), the sectors' (sectors.hip), the spawn's (spawn.hip), the floods' (flood.hip), the goal distance's (goal.hip) and the path unit's (path.hip) share: the pick of a lane's level,
-// the checked launch, the device check of a handle, the map's side of a world handle, and what both map units read of a line.
+// a wave's maximum and sum and the append into a list in LDS, what the map units read of a line, the checked launch, the device
+// check of a handle, the upload and release of a table, the checks of a fan, of a row of offsets and of a map view, and the map's
+// side of a world handle.  (The sight pass of reveal.hip and area.hip is sight.hpp's.)
 // One definition each, for player_quat.hpp's reason.
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <initializer_list>
 #include <vector>
 
 #include "../common.hpp"
@@ -19,6 +22,41 @@ __device__ __forceinline__ void with_level(uint32_t lv, Use use) {
   const uint32_t u = __builtin_amdgcn_readfirstlane(lv);
   if (__builtin_amdgcn_ballot_w64(lv != u) == 0) use(u);
   else use(lv);
+}
+
+// ---- a workgroup of 64-lane waves: a wave's maximum and sum, and the append of its threads' keepers to a list in LDS ----
+constexpr uint32_t WAVE_LANES = 64;
+__device__ __forceinline__ float wave_max(float v) {
+#pragma unroll
+  for (uint32_t o = WAVE_LANES / 2; o; o >>= 1) v = __builtin_fmaxf(v, __shfl_xor(v, o));
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_sum(uint32_t v) {
+#pragma unroll
+  for (uint32_t o = WAVE_LANES / 2; o; o >>= 1) v += __shfl_xor(v, o);
+  return v;
+}
+// Where a thread that keeps its item puts it in a list that holds `start` entries, and the keepers of the whole workgroup: a ballot
+// and a prefix within the wave, the waves' counts through LDS (`counts`: WAVES words).  Items stay in thread order.  Every thread of
+// the workgroup calls it, with its lane and its wave: there is one barrier inside, and the caller's own follows its stores.  A
+// count is the same in every lane, and is read as the scalar it is: through a pointer the compiler no longer sees that by itself
+struct Appended {
+  uint32_t slot, total;
+};
+template <uint32_t WAVES>
+__device__ __forceinline__ Appended append(bool keep, uint32_t lane, uint32_t wave, uint32_t *counts, uint32_t start) {
+  const uint64_t kept = __builtin_amdgcn_ballot_w64(keep);
+  const uint32_t before = __builtin_amdgcn_mbcnt_hi((uint32_t)(kept >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)kept, 0u));
+  if (lane == 0) counts[wave] = (uint32_t)__builtin_popcountll(kept);
+  __syncthreads();
+  uint32_t at = start, total = 0;
+#pragma unroll
+  for (uint32_t w = 0; w < WAVES; w++) {
+    const uint32_t n = __builtin_amdgcn_readfirstlane(counts[w]);
+    at += w < wave ? n : 0u;
+    total += n;
+  }
+  return Appended{at + before, total};
 }
 
 // ---- a line of the table as the map contracts read it (include/rdoom.h "top-down maps", "seen lines") ----
@@ -192,6 +230,41 @@ rdoom_status check_device(const Handle *h, const char *noun) {
   int cur = -1;
   HIP_TRY(hipGetDevice(&cur));
   if (cur != h->device) return rdoom::fail(RDOOM_BAD_ARG, "%s lives on device %d, the current device is %d", noun, h->device, cur);
+  return RDOOM_OK;
+}
+
+// a table on the current device (an empty one: a valid, unread pointer), and the release of a handle's tables
+template <class T>
+rdoom_status upload(T **dst, const std::vector<T> &src) {
+  HIP_TRY(hipMalloc((void **)dst, src.empty() ? 16 : src.size() * sizeof(T)));
+  if (!src.empty()) HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+  return RDOOM_OK;
+}
+inline void free_all(std::initializer_list<void *> pointers) {
+  for (void *p : pointers)
+    if (p) (void)hipFree(p);
+}
+
+// what every call that takes a fan of rays checks of it
+inline rdoom_status check_fan(uint32_t n_rays, float max_range) {
+  if (!n_rays) return rdoom::fail(RDOOM_BAD_ARG, "n_rays is 0");
+  if (!(max_range > 0.0f) || max_range == __builtin_inff())
+    return rdoom::fail(RDOOM_BAD_ARG, "max_range %g is not a finite positive number", (double)max_range);
+  return RDOOM_OK;
+}
+// a caller's rows of object offsets (null: none) against the `needed` objects of the noun: "world", "world set", "game", "set"
+inline rdoom_status check_offsets(const float *d_offsets, uint32_t n_objects, uint32_t needed, const char *noun) {
+  if (d_offsets && n_objects < needed)
+    return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is smaller than the %s's %u objects", n_objects, noun, needed);
+  return RDOOM_OK;
+}
+// the size and the scale of a drawn map (automap.hip, sectors.hip, area.hip)
+constexpr uint32_t MAX_SIDE = 16384;
+inline rdoom_status check_view(const rdoom_map_view *view) {
+  if (!view->width || !view->height || view->width > MAX_SIDE || view->height > MAX_SIDE)
+    return rdoom::fail(RDOOM_BAD_ARG, "a map of %u x %u pixels (1 .. %u a side)", view->width, view->height, MAX_SIDE);
+  if (!(view->scale > 0.0f) || view->scale == __builtin_inff())
+    return rdoom::fail(RDOOM_BAD_ARG, "scale %g is not a finite positive number", (double)view->scale);
   return RDOOM_OK;
 }
 

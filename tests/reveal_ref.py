@@ -22,6 +22,13 @@ _lock = threading.Lock()
 
 # the fans of the GPU comparison: (rays, fov, range)
 FANS = [(64, 1.6, 12.0), (200, 2 * np.pi, 40.0), (1, 0.0, 12.0)]
+# the fan that takes the sight pass (sight.hpp) twice: a pass of 256 rays, then one of 3 rays that point backwards -- 85 slices of the
+# list and a thread without one -- for 16 players of E1M1, whose 713 lines fill the list in three chunks
+TAIL_PLAYERS, TAIL_RANGE = 16, 12.0
+
+
+def tail_fan():
+    return np.concatenate([rd.map_fan(256, 1.6), -rd.map_fan(3, 1.0)])
 
 
 def lib():

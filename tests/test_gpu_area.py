@@ -108,6 +108,27 @@ def test_rows_and_counts_match_the_restatement(level):
             _same(new, want['new'], (level, k, moved, 'new'))
 
 
+def test_a_second_pass_of_three_rays_that_look_backwards():
+    """259 rays: the pass loop runs twice, and the second pass's sight limits come from 85 slices and a thread without one"""
+    d = inputs('E1M1')
+    n, fan, rng, cell = reveal_ref.TAIL_PLAYERS, reveal_ref.tail_fan(), reveal_ref.TAIL_RANGE, 0.25
+    assert len(d['lines']) == 713 and fan.shape == (259, 2) and fan.dtype == F
+    st = rays_ref.players(wad().build_level(d['index']), LEVELS['E1M1'][1], count=n)
+    off = reveal_ref.random_offsets(np.random.RandomState(LEVELS['E1M1'][1]), n, d['offsets'].shape[1])
+    rd.set_device(0)
+    world = wad().build_world(d['index'])
+    for o_np in (None, off):
+        want = area_ref.reveal(d['lines'], st, fan, rng, cell, offsets=o_np, detail=True)
+        head = area_ref.reveal(d['lines'], st, fan[:256], rng, cell, offsets=o_np)
+        # on the restatement's own result: the tail pass marks cells of its own for every player, and every ray of it ends on a wall
+        assert (want['area'] != head['area']).any((1, 2)).all() and (want['limit'][:, 256:] < 1).all()
+        new = torch.full((n, 2), 77, dtype=torch.int32, device='cuda')
+        area = world.reveal_area(_dev(st), torch.from_numpy(fan).cuda(), rng, cell, offsets=None if o_np is None else torch.from_numpy(o_np).cuda(),
+                                 new_out=new)
+        _same(area, want['area'], ('tail', o_np is not None))
+        _same(new, want['new'], ('tail', o_np is not None, 'new'))
+
+
 def test_rows_accumulate_and_the_counts_are_what_is_new():
     rd.set_device(0)
     d = inputs('E1M1')

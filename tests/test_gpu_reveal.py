@@ -98,6 +98,29 @@ def test_rows_and_counts_match_the_restatement(level):
             _same(new, want['new'], (level, k, moved, 'new'))
 
 
+def test_a_second_pass_of_three_rays_that_look_backwards():
+    """259 rays: the pass loop runs twice, and the second pass has 85 slices and a thread without one"""
+    d = inputs('E1M1')
+    n, fan, rng = reveal_ref.TAIL_PLAYERS, reveal_ref.tail_fan(), reveal_ref.TAIL_RANGE
+    assert len(d['lines']) == 713 and fan.shape == (259, 2) and fan.dtype == F
+    st = rays_ref.players(d['wad'].build_level(d['index']), LEVELS['E1M1'][2], count=n)
+    off = reveal_ref.random_offsets(np.random.RandomState(LEVELS['E1M1'][2]), n, d['offsets'].shape[1])
+    rd.set_device(0)
+    world = d['wad'].build_world(d['index'])
+    for o_np in (None, off):
+        want = reveal_ref.reveal(d['lines'], st, fan, rng, o_np, detail=True)
+        head = reveal_ref.reveal(d['lines'], st, fan[:256], rng, o_np)
+        # on the restatement's own result: the tail pass sees lines of its own for every player, and every ray of it ends on a wall
+        tail_only = (want['witness_ray'] >= 256) & (want['witness_ray'] != reveal_ref.NO_WITNESS)
+        assert tail_only.any(1).all(), tail_only.sum(1)
+        assert (want['seen'] != head['seen']).any(1).all() and (want['limit'][:, 256:] < 1).all()
+        new = torch.full((n,), 77, dtype=torch.int32, device='cuda')
+        seen = world.reveal_lines(_dev(st), torch.from_numpy(fan).cuda(), rng, offsets=None if o_np is None else torch.from_numpy(o_np).cuda(),
+                                  new_out=new)
+        _same(seen, want['seen'], ('tail', o_np is not None))
+        _same(new, want['new'], ('tail', o_np is not None, 'new'))
+
+
 def test_rows_accumulate_and_the_count_is_what_is_new():
     rd.set_device(0)
     d = inputs('E1M8')
