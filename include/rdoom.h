@@ -177,6 +177,11 @@ typedef struct rdoom_path_stats {
   uint64_t half_runs;             /* 8-pixel runs an edge crosses whose uniform quad was shaded with the run's neighbours (one quad listed) */
   uint64_t half_fallbacks;        /* such runs that failed a guard of the packed body, or show sky / a decoration: both quads listed */
   uint64_t listed_quads;          /* 4-pixel quads shaded by the general per-pixel body */
+  /* the rasteriser's census of its fast masked body, counted only in a render under rdoom_debug_set("raster_stats", 1) (zero otherwise): */
+  uint64_t masked_fast_bodies;    /* sixteen-pixel bodies that alpha-tested a masked-interior record's winners (per wave) */
+  uint64_t masked_fast_pixels;    /* winners alpha-tested by those bodies */
+  uint64_t masked_fast_replays;   /* lanes of those bodies that replayed their block through the general rule (tie, 1/w range, certificate) */
+  uint64_t masked_general_bodies; /* general bodies that ran on a masked-interior record */
 } rdoom_path_stats;
 
 const char *rdoom_last_error(void);
@@ -389,8 +394,8 @@ rdoom_status rdoom_selftest_sincos(uint64_t out_sums[512], uint32_t raw_binade, 
  * shaped but EQUIVALENT path through the kernels -- the image must not change -- so that the rarely taken ones can be
  * forced (tests/test_gpu_debug_paths.py).  Process-wide; read when a batch is created ("vis32", "entry_cap") or
  * rendered (the rest).  Names: no_bins, entry_cap, vis32, leak_mod, frag_nq, frag_bw, frag_chunk, bin_threads,
- * no_cover, no_pair, no_settle, settle_max, raster_stats, no_qtab, keep_vis, qpath, no_split, no_half_runs, frag_count (rust-doom_amd/csrc/common.hpp:
- * DebugOptions); "reset" restores the defaults. */
+ * no_cover, no_pair, no_settle, settle_max, raster_stats, no_qtab, keep_vis, qpath, no_split, no_half_runs, frag_count, no_masked_fast
+ * (rust-doom_amd/csrc/common.hpp: DebugOptions); "reset" restores the defaults. */
 rdoom_status rdoom_debug_set(const char *name, int32_t value);
 
 /* ---- loader + builder: the `wad` crate and `game::level` static-geometry builder ----------- */

@@ -146,7 +146,9 @@ class Timings(ctypes.Structure):
 class PathStats(ctypes.Structure):
     _fields_ = [('poses', ctypes.c_uint32), ('bins_overflowed_poses', ctypes.c_uint32), ('tiles', ctypes.c_uint64), ('split_tiles', ctypes.c_uint64),
                 ('tile_entries', ctypes.c_uint64), ('quadrants', ctypes.c_uint64), ('described_quadrants', ctypes.c_uint64),
-                ('half_runs', ctypes.c_uint64), ('half_fallbacks', ctypes.c_uint64), ('listed_quads', ctypes.c_uint64)]
+                ('half_runs', ctypes.c_uint64), ('half_fallbacks', ctypes.c_uint64), ('listed_quads', ctypes.c_uint64),
+                ('masked_fast_bodies', ctypes.c_uint64), ('masked_fast_pixels', ctypes.c_uint64), ('masked_fast_replays', ctypes.c_uint64),
+                ('masked_general_bodies', ctypes.c_uint64)]
 
 
 class HostTimings(ctypes.Structure):

@@ -30,7 +30,8 @@ struct DebugOptions {
   int no_split = 0;      // no per-quadrant lists for tiles with more than 64 entries: the rasteriser re-gathers such a tile's whole list for every quadrant
   int no_half_runs = 0;  // the fragment kernel lists both quads of a run an edge crosses (no half lanes: fragment.hip), as before round 8
   int frag_count = 0;    // the fragment kernel counts half lanes and listed quads (rdoom_batch_path_stats: half_runs, half_fallbacks, listed_quads)
-  int raster_stats = 0;  // census of the rasteriser's paths on stderr (instrumented instantiation: slower)
+  int raster_stats = 0;  // census of the rasteriser's paths on stderr (instrumented instantiation: slower; rdoom_batch_path_stats: masked_fast_*)
+  int no_masked_fast = 0;  // masked-interior records take the rasteriser's general rule in every lane (no fast masked body: raster.hip), as before round 9
 };
 DebugOptions debug_options();  // a snapshot taken under the lock rdoom_debug_set writes under (one host thread per GPU may render while a test thread sets hooks)
 inline rdoom_status fail(rdoom_status code, const char *fmt, ...) {

@@ -19,6 +19,18 @@
 namespace rdoom_dev {
 namespace {
 
+// counters of the STATS instantiation (launch_raster prints them): [0..19] as before; [20] general bodies on masked-interior
+// records, [21] rows of those that ran the alpha part, [22] pixels alpha-tested there, [23] pixels fetched; [24] fast bodies
+// whose block straddles the bbox in some lane; the fast masked body: [25] bodies, [26] lanes, [27] winners alpha-tested,
+// [28] lanes replayed through the general rule (tie, 1/w range, certificate), [29] winners that survived the alpha test
+constexpr int RASTER_NSTAT = 30;
+// sum over the active lanes of a small per-lane count (STATS only)
+__device__ __forceinline__ unsigned long long wave_sum_small(uint32_t v) {
+  unsigned long long s = 0;
+  for (uint32_t b = 0; b < 8u; b++) s += (unsigned long long)__popcll(__ballot(((v >> b) & 1u) != 0u)) << b;
+  return s;
+}
+
 // =================================================================================================
 // Rasteriser, per-entry part.  Rejection is hierarchical and exact: fmaf is monotone in each argument, so the
 // extreme of a *computed* edge function, depth plane or 1/w plane over a pixel rectangle sits at a corner --
@@ -35,7 +47,7 @@ __device__ __forceinline__ void raster_entry(const DeviceLevelView &lv, const Tr
                                              int x1, int y1, uint32_t flags, uint32_t ridx, int bx, int by, float pxlo,
                                              float pxhi, float pylo, float pyhi, uint32_t (&best_d)[16],
                                              uint32_t (&best_r)[16], uint32_t &lane_far, ShadeFetch fetch_shade,
-                                             unsigned long long (&st)[20]) {
+                                             const bool masked_fast, unsigned long long (&st)[RASTER_NSTAT]) {
     // lane-level exact rejection over my 4x4 block.  Early-z first (most rejected triangles are simply hidden):
     // nearest depth of the plane over the block against the farthest depth I still hold
     const float zn = fmaf(za, pos(za) ? pxlo : pxhi, fmaf(zb, pos(zb) ? pylo : pyhi, zc));
@@ -71,6 +83,7 @@ __device__ __forceinline__ void raster_entry(const DeviceLevelView &lv, const Tr
     // need guarantees the block overlaps the bbox, so the column and row ranges below are non-empty.
     uint32_t outside = 0u;
     if (__any(fast & !((bx >= x0) & (bx + 3 <= x1) & (by >= y0) & (by + 3 <= y1)))) {
+      if (STATS) st[24]++;
       const int clo = max(x0 - bx, 0), chi = min(x1 - bx, 3), rlo = max(y0 - by, 0), rhi = min(y1 - by, 3);
       const uint32_t cm = ((2u << chi) - 1u) & ~((1u << clo) - 1u);                // columns inside, 4 bits
       const uint32_t rows = ((16u << (4 * rhi)) - 1u) & ~((1u << (4 * rlo)) - 1u);  // all pixels of the rows inside
@@ -108,15 +121,136 @@ __device__ __forceinline__ void raster_entry(const DeviceLevelView &lv, const Tr
         }
       }
     }
+    // The fast masked body: a texture with holes in its rectangle (RASTER_MASKED_INTERIOR: a grate, a decor sprite) needs ONE
+    // thing more than an opaque one -- the alpha test R6 on the pixels that would win, before the depth write.  Geometry, depth,
+    // the `outside` mask, the borrow as the depth test and the folded tie detector are those of the fast body, but a row's wins
+    // go into a bit mask; the row's texel coordinates are formed with the exact short forms of fastmath.hpp and its four fetches
+    // are in flight during its geometry, a transparent texel clears its pixel's win bit, and what remains is committed.  (Row by
+    // row: sixteen offsets, texels or depths held across the block do not fit the registers -- 27 to 217 of them spilled,
+    // profiles/r09_ab.txt.  A row commits before a later row may detect a tie, as the fast body does: each committed pixel lies
+    // strictly inside, strictly nearer and is certified, so the replay through the general rule finds it held by this record.)
+    // Exactness: 1/w is monotone over the block (corner argument), so both corner values inside [2^-100, 2^100] put every
+    // pixel's 1/w where exact_rcp equals the division; a power-of-two tile size divides by an exponent subtraction (as
+    // texel_coords does); an integer size in [1, 4096] takes floor(t * RN(1/size)), certified by mod_cert with ONE guard per
+    // block and axis: |t| = |n * w| <= max |n at the corners| * RN(1 / smallest 1/w) (the numerator plane is monotone in x and y
+    // too, rounding is monotone), so the block's guard is at least every pixel's own and the block's smallest and largest
+    // remainder inside [guard, size - guard] imply mod_cert() for each pixel.  A lane whose 1/w leaves the range, whose
+    // certificate fails or that detects a tie replays its block through the general rule (a failed row commits nothing), like a tie of
+    // the fast body; a record whose sizes are neither (never seen from the WAD path) takes the general rule as before.
+    bool fastm = false;
+    if (masked_fast && (flags & RASTER_MASKED_INTERIOR) != 0u) {  // (uniform)
+      // (one unsigned compare per corner: the bit patterns of [2^-100, 2^100] are the integers [0x0D800000, 0x71800000];
+      // negative numbers and NaNs land above the interval)
+      const uint32_t off_n = __float_as_uint(rwn) - 0x0D800000u, off_f = __float_as_uint(rwf) - 0x0D800000u;
+      fastm = need & (zn >= 0.0f) & (zf <= 1.0f) & (max(off_n, off_f) <= 0x71800000u - 0x0D800000u);
+      uint32_t c_win = 0u, c_left = 0u;  // STATS: this lane's winners before and after the alpha test
+      if (__any(fastm)) {
+        const ShadeRec sh = fetch_shade();
+        const bool p2x = (sh.flags & SHADE_POW2_X) != 0u, p2y = (sh.flags & SHADE_POW2_Y) != 0u;
+        // an integer in [1, 4096], tested on the bits (scalar arithmetic on a uniform value: a float compare against 4096 kept
+        // the literal in a vector register for the whole walk): exponent 0..12, no fraction bits, and 2^12 itself
+        auto integer_size = [](float s) {
+          const uint32_t u = __float_as_uint(s), e = (u >> 23) - 127u;
+          return e <= 12u && (u << (9u + e)) == 0u && (e < 12u || (u & 0x7FFFFFu) == 0u);
+        };
+        if (!((p2x || integer_size(sh.size_x)) && (p2y || integer_size(sh.size_y)))) fastm = false;
+        if (STATS && __any(fastm)) st[25]++, st[26] += (unsigned long long)__popcll(__ballot(fastm));
+        if (fastm) {
+          uint32_t outm = 0u;  // (as `outside` above)
+          if (!((bx >= x0) & (bx + 3 <= x1) & (by >= y0) & (by + 3 <= y1))) {
+            const int clo = max(x0 - bx, 0), chi = min(x1 - bx, 3), rlo = max(y0 - by, 0), rhi = min(y1 - by, 3);
+            const uint32_t cm = ((2u << chi) - 1u) & ~((1u << clo) - 1u);
+            const uint32_t rows = ((16u << (4 * rhi)) - 1u) & ~((1u << (4 * rlo)) - 1u);
+            outm = ~((cm * 0x1111u) & rows);  // (bits 0..15 are read)
+          }
+          // (uniform values: kept in scalar registers)
+          auto uniform = [](float v) { return __uint_as_float((uint32_t)__builtin_amdgcn_readfirstlane((int)__float_as_uint(v))); };
+          const float inv_x = p2x ? __uint_as_float(0x7F000000u - __float_as_uint(sh.size_x)) : uniform(exact_rcp(sh.size_x));
+          const float inv_y = p2y ? __uint_as_float(0x7F000000u - __float_as_uint(sh.size_y)) : uniform(exact_rcp(sh.size_y));
+          // the block's guards (zero for a power-of-two axis, whose quotient is exact); a bound of 2^23 or more fails every row
+          float gx = 0.0f, gy = 0.0f;
+          if (!(p2x && p2y)) {  // (uniform) an integer size that is no power of two
+            const float w_hi = exact_rcp(rwn);
+            auto corner_max = [&](const float (&p)[3]) {
+              const float l = fmaf(p[1], pylo, p[2]), h = fmaf(p[1], pyhi, p[2]);
+              return fmaxf(fmaxf(fabsf(fmaf(p[0], pxlo, l)), fabsf(fmaf(p[0], pxhi, l))), fmaxf(fabsf(fmaf(p[0], pxlo, h)), fabsf(fmaf(p[0], pxhi, h))));
+            };
+            const float bu = corner_max(sh.up) * w_hi, bv = corner_max(sh.vp) * w_hi;
+            gx = p2x ? 0.0f : ((bu < 0x1p23f) ? fmaxf(bu, sh.size_x) * 0x1p-20f : sh.size_x);  // (guard = size: no remainder passes)
+            gy = p2y ? 0.0f : ((bv < 0x1p23f) ? fmaxf(bv, sh.size_y) * 0x1p-20f : sh.size_y);
+          }
+#pragma unroll
+          for (int ry = 0; ry < 4; ry++) {
+            const float py = pylo + (float)ry;
+            const float t0 = fmaf(e0b, py, e0c), t1 = fmaf(e1b, py, e1c), t2 = fmaf(e2b, py, e2c);
+            const float tz = fmaf(zb, py, zc);
+            const float tw = fmaf(wb, py, wc), tu = fmaf(sh.up[1], py, sh.up[2]), tv = fmaf(sh.vp[1], py, sh.vp[2]);
+            // R6 first: F1, F2 (texel_coords with the short forms), the offsets of F3 and the row's four fetches, which are then
+            // in flight during the row's geometry.  A pixel that will not win computes coordinates nobody reads: its offset stays
+            // inside the texel store (texel_offset masks it)
+            uint32_t toff[4], tx[4];
+            float rus[4], rvs[4];
+#pragma unroll
+            for (int rx = 0; rx < 4; rx++) {
+              const float px = pxlo + (float)rx;
+              const float w = exact_rcp(fmaf(wa, px, tw));
+              const float u = fmaf(sh.up[0], px, tu) * w, v = fmaf(sh.vp[0], px, tv) * w;
+              const float ru = u - sh.size_x * floorf(u * inv_x), rv = v - sh.size_y * floorf(v * inv_y);
+              rus[rx] = ru, rvs[rx] = rv;
+              toff[rx] = texel_offset(sh.flags, sh.tex, (int)floorf(ru + sh.atlas_u), (int)floorf(rv + sh.atlas_v));
+            }
+#pragma unroll
+            for (int rx = 0; rx < 4; rx++) tx[rx] = lv.texels[toff[rx]];
+            // the row's smallest and largest remainder against the guards (three-operand min / max; no remainder is a NaN where
+            // it matters: a bound below 2^23 keeps t finite, and with a larger one the guard is the size, which nothing passes)
+            const bool cert = (fminf(fminf(rus[0], rus[1]), fminf(rus[2], rus[3])) >= gx) & (fmaxf(fmaxf(rus[0], rus[1]), fmaxf(rus[2], rus[3])) <= sh.size_x - gx) &
+                              (fminf(fminf(rvs[0], rvs[1]), fminf(rvs[2], rvs[3])) >= gy) & (fmaxf(fmaxf(rvs[0], rvs[1]), fmaxf(rvs[2], rvs[3])) <= sh.size_y - gy);
+            uint32_t winm = 0u, d24s[4];  // bit rx: the pixel lies inside, nearer than what it holds
+#pragma unroll
+            for (int rx = 0; rx < 4; rx++) {
+              const int k = ry * 4 + rx;
+              const float px = pxlo + (float)rx;
+              const float em = fminf(fminf(fmaf(e0a, px, t0), fmaf(e1a, px, t1)), fmaf(e2a, px, t2));
+              const uint32_t d24 = __float2uint_rz(fmaf(fmaf(za, px, tz), 16777215.0f, 0.5f));
+              const uint32_t d24m = d24 | (uint32_t)__builtin_amdgcn_sbfe((int)outm, k, 1);  // all ones when outside
+              uint32_t diff;
+              const bool nearer = __builtin_usub_overflow(d24m, best_d[k], &diff);
+              const int ei = (int)__float_as_uint(em);
+              const bool inside = ei > 0;
+              tiez = min(tiez, inside ? diff : ((uint32_t)ei << 1));
+              winm |= (inside & nearer) ? (1u << rx) : 0u;
+              d24s[rx] = d24;
+            }
+            if (STATS) c_win += (uint32_t)__popc(winm);
+#pragma unroll
+            for (int rx = 0; rx < 4; rx++) winm &= (tx[rx] & 0x8000u) ? ~(1u << rx) : ~0u;
+            // a row whose certificate fails commits nothing and has the block replayed (a power-of-two axis: guard 0, always true
+            // for the remainders of [0, size] -- and were one not, the general rule decides)
+            if (!cert) winm = 0u, tiez = 0u;
+            if (STATS) c_left += (uint32_t)__popc(winm);
+            updated |= winm != 0u;
+#pragma unroll
+            for (int rx = 0; rx < 4; rx++) {
+              const bool win = ((winm >> rx) & 1u) != 0u;
+              best_d[ry * 4 + rx] = win ? d24s[rx] : best_d[ry * 4 + rx];
+              best_r[ry * 4 + rx] = win ? ridx : best_r[ry * 4 + rx];
+            }
+            __builtin_amdgcn_sched_barrier(0);  // (rows interleaved by the scheduler do not fit the registers)
+          }
+        }
+        if (STATS) st[27] += wave_sum_small(c_win), st[29] += wave_sum_small(c_left), st[28] += (unsigned long long)__popcll(__ballot(fastm & (tiez == 0u)));
+      }
+    }
     const bool redo = tiez == 0u;
-    if (__any(need & (!fast | redo))) {
+    if (__any(need & (!(fast | fastm) | redo))) {
       if (STATS) {
-        st[6]++, st[7] += (unsigned long long)__popcll(__ballot(need & (!fast | redo)));
+        st[6]++, st[7] += (unsigned long long)__popcll(__ballot(need & (!(fast | fastm) | redo)));
         // why: [12] masked texture, [13] tie replay
-        st[12] += (unsigned long long)__popcll(__ballot(need & ((flags & RASTER_MASKED_INTERIOR) != 0u)));
+        st[12] += (unsigned long long)__popcll(__ballot(need & (!fastm | redo) & ((flags & RASTER_MASKED_INTERIOR) != 0u)));
         st[13] += (unsigned long long)__popcll(__ballot(need & fast & redo));
       }
-      if (need & (!fast | redo)) {
+      uint32_t c_rows = 0u, c_test = 0u, c_fetch = 0u;  // STATS: this lane's alpha rows (bit per row), pixels tested, pixels fetched
+      if (need & (!(fast | fastm) | redo)) {
         // The general rule R1..R6, a row of four pixels at a time and branch-free but for two rare cases (a depth tie
         // that the primitive order must settle; texels to look at): compare results go straight into bit masks.
         const uint32_t prim = flags & 0xFFFFFFu;
@@ -158,6 +292,7 @@ __device__ __forceinline__ void raster_entry(const DeviceLevelView &lv, const Tr
               }
           }
           if (masked && passm != 0u) {  // R6: alpha test before the depth write; the row's texel fetches in flight together
+            if (STATS && interior) c_rows |= 1u << ry, c_test += (uint32_t)__popc(passm);
             const float tu = fmaf(sh.up[1], py, sh.up[2]), tv = fmaf(sh.vp[1], py, sh.vp[2]);
             uint32_t toff[4], fetchm = 0u;
 #pragma unroll
@@ -172,6 +307,7 @@ __device__ __forceinline__ void raster_entry(const DeviceLevelView &lv, const Tr
               fetchm |= must_fetch ? (1u << rx) : 0u;
             }
             fetchm &= passm;
+            if (STATS && interior) c_fetch += (uint32_t)__popc(fetchm);
             if (fetchm != 0u) {
               uint32_t tx[4];
 #pragma unroll
@@ -193,6 +329,11 @@ __device__ __forceinline__ void raster_entry(const DeviceLevelView &lv, const Tr
               }
           }
         }
+      }
+      if (STATS && (flags & RASTER_MASKED_INTERIOR) != 0u) {  // (the branch above has rejoined: every lane of the wave counts)
+        st[20]++;
+        for (uint32_t ry = 0; ry < 4u; ry++) st[21] += __any(((c_rows >> ry) & 1u) != 0u) ? 1ull : 0ull;
+        st[22] += wave_sum_small(c_test), st[23] += wave_sum_small(c_fetch);
       }
     }
     if (updated) {
@@ -355,7 +496,7 @@ __global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_ker
                                                              uint32_t *__restrict__ prim_out, uint32_t no_cover,
                                                              uint32_t *__restrict__ qtab, uint32_t settled,
                                                              unsigned long long *__restrict__ stats) {
-  unsigned long long st[20] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+  unsigned long long st[RASTER_NSTAT] = {};
   __shared__ uint32_t wq[RASTER_WAVES][64];
   __shared__ uint4 wrec[RASTER_WAVES][64][4];  // per wave: 15 words of each of the 64 gathered raster records
   // per entry: a sign-blind hash of each edge's three coefficients (a shared edge has exactly negated coefficients in the two
@@ -502,7 +643,7 @@ __global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_ker
           auto edge_hash = [&](uint32_t a, uint32_t b, uint32_t c) {
             return mag(a) ^ __builtin_amdgcn_alignbit(mag(b), mag(b), 21) ^ __builtin_amdgcn_alignbit(mag(c), mag(c), 11);
           };
-          whash[wave][lane] = make_uint4(edge_hash(c0.x, c0.y, c0.z), edge_hash(c0.w, c1.x, c1.y), edge_hash(c1.z, c1.w, c2.x), no_cover ? 0u : covx);  // (bit 1 alone: test hook "no_pair")
+          whash[wave][lane] = make_uint4(edge_hash(c0.x, c0.y, c0.z), edge_hash(c0.w, c1.x, c1.y), edge_hash(c1.z, c1.w, c2.x), (no_cover & 3u) ? 0u : covx);  // (bit 1 alone: test hook "no_pair"; bit 2: "no_masked_fast", raster_entry)
         }
         dnq0 = dn[0], dnq1 = dn[1], dnq2 = dn[2], dnq3 = dn[3];
         myrq = myrec | (myqb << 24);
@@ -553,7 +694,7 @@ __global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_ker
           }
         }
         if (STATS && lane == 0)
-          for (int k = 0; k < 20; k++) atomicAdd(&stats[k], st[k]);
+          for (int k = 0; k < RASTER_NSTAT; k++) atomicAdd(&stats[k], st[k]);
         return;
       }
     }
@@ -811,7 +952,7 @@ __global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_ker
         const int x0 = (int)(bb0 & 0xFFFFu), y0 = (int)(bb0 >> 16), x1 = (int)(bb1 & 0xFFFFu), y1 = (int)(bb1 >> 16);
         raster_entry<STATS>(lv, prec, uf(r0.x), uf(r0.y), uf(r0.z), uf(r0.w), uf(r1.x), uf(r1.y), uf(r1.z), uf(r1.w),
                                  uf(r3.x), za, zb, zc, uf(r2.x), uf(r2.y), uf(r2.z), x0, y0, x1, y1, flags, ridx, bx, by, pxlo,
-                                 pxhi, pylo, pyhi, best_d, best_r, lane_far, [&]() -> ShadeRec { return prec[ridx].s; }, st);
+                                 pxhi, pylo, pyhi, best_d, best_r, lane_far, [&]() -> ShadeRec { return prec[ridx].s; }, (no_cover & 4u) == 0u, st);
         refresh();
       }
     }
@@ -875,7 +1016,7 @@ __global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_ker
     }
   }
   if (STATS && lane == 0)
-    for (int k = 0; k < 20; k++) atomicAdd(&stats[k], st[k]);
+    for (int k = 0; k < RASTER_NSTAT; k++) atomicAdd(&stats[k], st[k]);
 }
 
 }  // namespace
@@ -884,7 +1025,8 @@ rdoom_status launch_raster(hipStream_t st, uint32_t n_poses, const DeviceLevelVi
                            const uint32_t *counts, uint32_t cap, int width, int height, int tiles_x,
                            int tiles_y, const uint2 *tile_hdr, const uint32_t *entries, uint32_t entry_cap,
                            const uint32_t *overflow, uint32_t *vis, bool vis16, uint32_t *prim_out, uint32_t *qtab,
-                           bool skip_described_vis, bool split_lists, bool bins_launched) {
+                           bool skip_described_vis, bool split_lists, bool bins_launched, uint64_t (&masked_census)[4]) {
+  masked_census[0] = masked_census[1] = masked_census[2] = masked_census[3] = 0u;
   const uint32_t n = n_poses;
   const uint32_t groups = (n + 7u) / 8u;  // pose groups of eight: one pose per XCD
   if (groups > 65535u || tiles_y > 65535 || (uint64_t)tiles_x * 8ull > 0x7FFFFFFFull)
@@ -892,8 +1034,8 @@ rdoom_status launch_raster(hipStream_t st, uint32_t n_poses, const DeviceLevelVi
   const rdoom::DebugOptions &dbg = rdoom::debug_options();
   unsigned long long *d_stats = nullptr;
   if (dbg.raster_stats) {
-    HIP_TRY(hipMalloc((void **)&d_stats, 20 * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(d_stats, 0, 20 * sizeof(unsigned long long), st));
+    HIP_TRY(hipMalloc((void **)&d_stats, RASTER_NSTAT * sizeof(unsigned long long)));
+    HIP_TRY(hipMemsetAsync(d_stats, 0, RASTER_NSTAT * sizeof(unsigned long long), st));
   }
   const bool skip = skip_described_vis && qtab != nullptr;  // (without a table every visibility word is needed)
   auto pick = [&](auto stats, auto skipvis, auto splt) {
@@ -917,12 +1059,13 @@ rdoom_status launch_raster(hipStream_t st, uint32_t n_poses, const DeviceLevelVi
   }
   const dim3 rgrid((uint32_t)tiles_x * 8u, groups, (uint32_t)tiles_y);  // tile rows the slowest dimension (raster_wave_kernel)
   hipLaunchKernelGGL(rk, rgrid, dim3(64 * RASTER_WAVES), 0, st, lv, recs, counts, cap, n, width, height, tiles_x,
-                     tiles_y, tile_hdr, entries, entry_cap, overflow, vis, prim_out, (dbg.no_cover ? 1u : 0u) | (dbg.no_pair ? 2u : 0u),
+                     tiles_y, tile_hdr, entries, entry_cap, overflow, vis, prim_out, (dbg.no_cover ? 1u : 0u) | (dbg.no_pair ? 2u : 0u) | (dbg.no_masked_fast ? 4u : 0u),
                      qtab, settle ? 1u : 0u, d_stats);
   if (d_stats) {
-    unsigned long long h[20];
+    unsigned long long h[RASTER_NSTAT];
     HIP_TRY(hipMemcpy(h, d_stats, sizeof h, hipMemcpyDeviceToHost));
     (void)hipFree(d_stats);
+    masked_census[0] = h[25], masked_census[1] = h[27], masked_census[2] = h[28], masked_census[3] = h[20];
     {  // census of the tile lists' lengths (a tile with more than 64 entries gets a list per quadrant: bin.hip)
       const size_t nt = (size_t)n * (size_t)(tiles_x * tiles_y);
       std::vector<uint2> hdrs(nt);
@@ -955,6 +1098,10 @@ rdoom_status launch_raster(hipStream_t st, uint32_t n_poses, const DeviceLevelVi
     fprintf(stderr, "[rdoom stats] sixteen-pixel bodies: %llu in %llu passes that ran any (%.2f per such pass, %.1f lanes each); the most ONE lane needed, summed over those passes: %llu (%.2f per pass) -- "
             "what a body with a per-lane choice of entry would run; all needs / 64: %.2f per pass\n",
             h[2], h[18], h[18] ? (double)h[2] / h[18] : 0.0, h[2] ? (double)h[3] / h[2] : 0.0, h[17], h[18] ? (double)h[17] / h[18] : 0.0, h[18] ? (double)h[3] / 64.0 / h[18] : 0.0);
+    fprintf(stderr, "[rdoom stats] masked-interior records: general bodies %llu (%.4f per pass), rows that ran the alpha part %llu (%.2f per body), pixels alpha-tested %llu, "
+            "fetched %llu | fast bodies %llu, of which some lane's block straddles the bbox %llu (%.3f) | fast masked bodies %llu (lanes %llu), winners alpha-tested %llu, "
+            "survived %llu, lanes replayed %llu\n",
+            h[20], h[20] / waves, h[21], h[20] ? (double)h[21] / h[20] : 0.0, h[22], h[23], h[4], h[24], h[4] ? (double)h[24] / h[4] : 0.0, h[25], h[26], h[27], h[29], h[28]);
   }
   return RDOOM_OK;
 }

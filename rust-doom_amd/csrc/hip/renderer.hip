@@ -93,6 +93,7 @@ struct rdoom_batch {
   float *d_ndc = nullptr;  // (ix + 0.5) / (width / 2) - 1 for every column, then (iy + 0.5) / (height / 2) - 1 for every row
   // the last render's FragmentPlan::skip_described_vis: a described quadrant's visibility words are another render's (resolve reads the table)
   bool last_skip_vis = false;
+  uint64_t last_masked_census[4] = {0, 0, 0, 0};  // the last render's census of the rasteriser's masked bodies (hook raster_stats; else zeros)
   bool last_frag_count = false;  // the last render's FragmentPlan::count: the fragment kernel counted its half lanes and listed quads
   uint8_t *d_rgb = nullptr;  // rdoom_batch_read_rgb's staging (allocated on first use, at most RGB_STAGING_BYTES or one frame)
   size_t rgb_bytes = 0;
@@ -623,7 +624,7 @@ static rdoom_status queue_pipeline(rdoom_batch *b, uint32_t n, uint32_t kinds_ma
   // bounding box reaches -- they stay uncovered, and the quadrants they lie in simply never count as covered)
   if (rdoom_status rs = launch_raster(st, n, lv->view, b->d_recs, b->d_counts, b->cap, PITCH, H, tiles_x, tiles_y,
                                       b->d_tile_hdr, b->d_entries, b->entry_cap, b->d_overflow, b->d_vis, b->vis16, prim_out, b->d_qtab,
-                                      plan.skip_described_vis, split_lists, bins))
+                                      plan.skip_described_vis, split_lists, bins, b->last_masked_census))
     return rs;
   if (marks) HIP_TRY(hipEventRecord(ev[2], st));
   if (rdoom_status rs = launch_fragment(st, n, lv->view, b->d_recs, b->d_counts, b->cap, b->d_poses, W, PITCH, H, tiles_x,
@@ -926,6 +927,8 @@ rdoom_status rdoom_batch_path_stats(rdoom_batch *b, rdoom_path_stats *out) {
       }
     }
     out->tiles = (uint64_t)n * T;
+    out->masked_fast_bodies = b->last_masked_census[0], out->masked_fast_pixels = b->last_masked_census[1];
+    out->masked_fast_replays = b->last_masked_census[2], out->masked_general_bodies = b->last_masked_census[3];
     if (b->last_frag_count) {  // (rendered under the hook frag_count; zero otherwise)
       uint32_t fc[3];
       HIP_TRY(read_back(b, fc, static_cast<const char *>(b->d_frag_const) + fragment_counts_offset(), sizeof fc));
