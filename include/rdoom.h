@@ -1550,6 +1550,69 @@ rdoom_status rdoom_flood_descend_octile(const float *d_floor, const float *d_cei
                                         uint32_t max_moves, uint32_t stop_dist, int32_t *d_cells_out, uint32_t *d_moves_out,
                                         int32_t *d_path_out, uint32_t path_len, void *stream);
 
+/* ---- straight walks: the line-of-walk test and string-pulled paths -------------------------------------------------
+ * "Can I walk straight from here to there?" -- asked of a goal, a waypoint, a frontier cell or another player's cell under the open
+ * and move rules the floods use -- and the heading that makes of a descent's staircase of 4- or 8-neighbour moves: the farthest
+ * cell of the path that can be walked to in a straight line.  Both rest on one primitive, the chain of grid moves that the straight
+ * segment between two cell centres makes, defined in exact integers.  No existing call changes.  The reference project has no
+ * counterpart of this: nothing here restates it.
+ *
+ * The line chain.  Cells are (column, row).  For a = (ca, ra) and b = (cb, rb) inside the grid: dx = |cb - ca|, dy = |rb - ra|, and
+ * sx, sy are the signs of cb - ca and rb - ra.  The segment between the two centres crosses dx column boundaries and dy row
+ * boundaries; column crossing i (0 <= i < dx) is at parameter (2i + 1) / (2 dx), row crossing j (0 <= j < dy) at
+ * (2j + 1) / (2 dy).  The chain starts at a with i = j = 0 and runs while i < dx or j < dy:
+ *   if j == dy, or i < dx and (2i + 1) * dy < (2j + 1) * dx: a column move to (c + sx, r), then i += 1;
+ *   else if i == dx, or (2i + 1) * dy > (2j + 1) * dx: a row move to (c, r + sy), then j += 1;
+ *   else the segment passes exactly through a cell corner: a diagonal move to (c + sx, r + sy), then i += 1 and j += 1.
+ * Every product is an integer below 2^28.  Nothing is rounded.  The chain ends at b.
+ * Allowed.  A column or row move from x to y is allowed by "Open" and "Moves" of the goal-distance contract above, with max_step,
+ * max_drop and clearance.  A diagonal move is allowed by the octile contract's rule: all four axial moves round both sides must be
+ * allowed.  So a line never cuts the corner of a closed cell, a ledge or a door.
+ * Direction.  Without the reversed flag, each move of the chain is tested in the chain's direction, x to y.  With the flag, each
+ * move is tested y to x, and a diagonal's four axial moves are reversed likewise: the walk from b back to a over the same cells.
+ * Result of a line.  The line is clear when a and b are inside the grid, a is open, and every move of the chain is allowed.  A
+ * zero-move line (a == b) is clear exactly when a is open.  `stop` is the last cell reached from a: b when clear, else the cell the
+ * first refused move starts from -- a itself when a is closed.  `stop` is (-1, -1) when a or b is outside the grid.
+ * Property.  The chain from b to a is the chain from a to b, reversed.
+ *
+ * rdoom_grid_walk_lines.  A pure function of its arrays: no handle.  d_floor, d_ceiling, n, width, height: rdoom_flood_grids' planes.
+ * d_from: n x 2 int32, in the layout of d_seeds and of rdoom_world_area_cells' output; d_to: n x n_to x 2 int32.  Line (p, k) runs
+ * from d_from[p] to d_to[p][k] on row p's planes.  params: rdoom_flood_params' limits; flags is 0 or RDOOM_LINE_REVERSED, any other
+ * bit is an error.  d_clear_out: n x n_to bytes, 1 for clear and 0 otherwise, every byte written.  d_stop_out: n x n_to x 2 int32
+ * (column, row), may be NULL.
+ * One launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so the call can be
+ * captured into a graph.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): those of rdoom_flood_grids for the
+ * arguments shared with it; (n > 0) NULL d_from / d_to / d_clear_out; n_to == 0; n * n_to above 2^31 - 1.  n == 0 queues nothing.
+ *
+ * rdoom_path_straighten.  d_starts: n x 2 int32.  d_path: n x path_len x 2 int32, what rdoom_flood_descend or
+ * rdoom_flood_descend_octile wrote, or any list of cells.  params->flags is the descent's: with RDOOM_FLOOD_TOWARDS the lines are
+ * tested in the listed direction; without it they are tested reversed, because a forward field's path is listed from the far end
+ * back to the player.
+ * Row p.  m is the index of the first entry of the row that is not a cell inside the grid, or path_len if there is none.  If the
+ * start is outside the grid: count 0 and length 0.  Otherwise a = start, i = 0, count = 0, length = +0.0f, and while i < m and
+ * count < corner_len: K = min(max_look, m - i); k* is the largest k in [0, K) whose line from a to path[i + k] is clear -- if
+ * there is none the loop ends; the corner is path[i + k*], stored as entry `count`;
+ * length += sqrtf((float)(dc * dc + dr * dr)) with dc and dr the offsets from a to the corner -- the integer converted once, the
+ * square root IEEE, one rounded add, no contraction; then a = corner, i += k* + 1, count += 1.
+ * Outputs.  d_corners_out: n x corner_len x 2 int32; every later entry is (-1, -1), and every entry is written.
+ * d_count_out[p] = count (n uint32).  d_length_out (n floats, may be NULL): the length in cells; length * cell is world units.
+ * Entry 0 is the any-angle waypoint.
+ * Limits.  1 <= max_look <= RDOOM_STRAIGHTEN_MAX_LOOK; 1 <= path_len <= 2^22; 1 <= corner_len <= 2^22.  i strictly grows, so the
+ * loop ends.
+ * One launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so the call can be
+ * captured into a graph.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): those of rdoom_flood_grids for the
+ * arguments shared with it; (n > 0) NULL d_starts / d_path / d_corners_out / d_count_out; a max_look, path_len or corner_len
+ * outside its limits.  n == 0 queues nothing. */
+#define RDOOM_LINE_REVERSED 1u
+#define RDOOM_STRAIGHTEN_MAX_LOOK 1024u
+rdoom_status rdoom_grid_walk_lines(const float *d_floor, const float *d_ceiling, uint32_t n, uint32_t width, uint32_t height,
+                                   const int32_t *d_from, const int32_t *d_to, uint32_t n_to, const rdoom_flood_params *params,
+                                   uint8_t *d_clear_out, int32_t *d_stop_out, void *stream);
+rdoom_status rdoom_path_straighten(const float *d_floor, const float *d_ceiling, uint32_t n, uint32_t width, uint32_t height,
+                                   const int32_t *d_starts, const int32_t *d_path, uint32_t path_len, const rdoom_flood_params *params,
+                                   uint32_t max_look, int32_t *d_corners_out, uint32_t corner_len, uint32_t *d_count_out,
+                                   float *d_length_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -81,6 +81,8 @@ SECTOR_NONE, SECTOR_NONE16 = 0xFFFFFFFF, 0xFFFF
 FLOOD_UNREACHED = 0xFFFF  # RDOOM_FLOOD_UNREACHED: flood_maps' distance of a cell no allowed path leads to
 FLOOD_GRID_UNREACHED = 0xFFFFFFFF  # RDOOM_FLOOD_GRID_UNREACHED: flood_grids' distance of such a cell (-1 as int32)
 FLOOD_TOWARDS = 1  # RDOOM_FLOOD_TOWARDS: flood_grids counts the moves from a cell to the seed, not from the seed to the cell
+LINE_REVERSED = 1  # RDOOM_LINE_REVERSED: walk_lines tests every move of a line from its far cell back to its near one
+STRAIGHTEN_MAX_LOOK = 1024  # RDOOM_STRAIGHTEN_MAX_LOOK: the most cells of a path straighten_paths looks ahead from a corner
 WALL_FAR = 0xFFFF  # RDOOM_WALL_FAR: wall_distances' value of a cell with no blocking cell within the radius
 WALL_MAX_RADIUS = 32  # RDOOM_WALL_MAX_RADIUS: the largest radius, in cells, of wall_distances and inflate_grids
 WALL_EDGE_OPEN = 1  # RDOOM_WALL_EDGE_OPEN: cells outside the grid do not block
@@ -191,7 +193,7 @@ API_SYMBOLS = [
     'rdoom_world_draw_area_planes', 'rdoom_worldset_draw_area_planes', 'rdoom_flood_grid_max_cells', 'rdoom_flood_grids',
     'rdoom_world_area_cells', 'rdoom_worldset_area_cells', 'rdoom_flood_descend', 'rdoom_world_area_frontiers',
     'rdoom_worldset_area_frontiers', 'rdoom_wall_distance', 'rdoom_selftest_sincos', 'rdoom_flood_grids_octile',
-    'rdoom_flood_descend_octile']
+    'rdoom_flood_descend_octile', 'rdoom_grid_walk_lines', 'rdoom_path_straighten']
 
 _lib = None
 
@@ -1792,6 +1794,99 @@ def descend_grids_octile(floor, ceiling, dist, starts, towards=False, axial_cost
     params = FloodOctileParams(max_step, max_drop, clearance, FLOOD_TOWARDS if towards else 0, int(axial_cost), int(diagonal_cost))
     return _descend(lib().rdoom_flood_descend_octile, params, floor, ceiling, dist, starts, max_moves, stop_dist, cells_out, moves_out, path_out,
                     stream)
+
+
+def _cells_in(t, shape, what):
+    """an int32 input of (column, row) cells of `shape` on the GPU, checked"""
+    import torch
+    if not isinstance(t, torch.Tensor) or t.device.type != 'cuda' or not t.is_contiguous() or t.dtype != torch.int32 or tuple(t.shape) != shape:
+        raise ValueError('%s must be a contiguous int32 %s tensor of (column, row) on the GPU' % (what, shape))
+
+
+def walk_lines(floor, ceiling, starts, targets, reversed=False, max_step=0.24, max_drop=float('inf'), clearance=0.56, clear_out=None,
+               stop_out=None, stream=None):
+    """rdoom_grid_walk_lines: can each target be walked to in a straight line?  floor, ceiling: the (n, H, W) planes flood_grids
+    takes; starts: an int32 (n, 2) tensor of (column, row), area_cells' layout; targets: an int32 (n, q, 2) tensor.  Line (p, k)
+    is the chain of grid moves the segment from the centre of starts[p] to the centre of targets[p, k] makes -- a column or row
+    move at every boundary it crosses, a diagonal move where it passes exactly through a cell corner -- and it is clear when both
+    cells are inside the grid, the start is open and every move is allowed by flood_grids' rules with max_step, max_drop and
+    clearance, a diagonal by flood_grids_octile's: no corner of a closed cell, a ledge or a door is cut.  reversed: every move is
+    tested from its far cell back to its near one, the walk from the target to the start over the same cells.  Returns the (n, q)
+    uint8 tensor, 1 for clear (clear_out: a one-byte tensor or a raw device pointer to write instead); with stop_out True, a 32-bit
+    integer (n, q, 2) tensor or a raw device pointer, returns (clear, stop): the last cell reached from the start -- the target
+    when clear, else the cell the first refused move starts from, (-1, -1) when either end is outside the grid.  One launch,
+    asynchronous on `stream` (None, a torch stream or a raw handle); it can be captured into a graph."""
+    import torch
+    n, height, width = _flood_inputs(floor, ceiling, None)
+    _cells_in(starts, (n, 2), 'starts')
+    if not isinstance(targets, torch.Tensor) or targets.dim() != 3:
+        raise ValueError('targets must be a contiguous int32 (%d, q, 2) tensor of (column, row) on the GPU' % n)
+    q = int(targets.shape[1])
+    _cells_in(targets, (n, q, 2), 'targets')
+    if clear_out is None:
+        clear_out = torch.empty((n, q), dtype=torch.uint8, device=floor.device)
+    if isinstance(clear_out, int) and not isinstance(clear_out, bool):
+        pc = clear_out  # a raw device pointer to n * q bytes
+    elif not isinstance(clear_out, torch.Tensor) or clear_out.element_size() != 1:
+        raise ValueError('clear_out must be a one-byte tensor or a device pointer')
+    else:
+        pc = _out_tensor(clear_out, n * q, 'clear_out')
+    ps = None
+    if stop_out is not None and stop_out is not False:
+        stop_out, ps = _int32_out(stop_out, (n, q, 2), floor.device, 'stop_out')
+    else:
+        stop_out = None
+    params = FloodParams(max_step, max_drop, clearance, LINE_REVERSED if reversed else 0)
+    v = ctypes.c_void_p
+    _check(lib().rdoom_grid_walk_lines(v(floor.data_ptr()), v(ceiling.data_ptr()), n, width, height, v(starts.data_ptr()), v(targets.data_ptr()),
+                                       q, ctypes.byref(params), v(pc), v(ps), v(_stream_handle(stream))))
+    return clear_out if stop_out is None else (clear_out, stop_out)
+
+
+def straighten_paths(floor, ceiling, starts, path, towards=False, max_look=64, corners=8, max_step=0.24, max_drop=float('inf'), clearance=0.56,
+                     count_out=None, length_out=None, stream=None):
+    """rdoom_path_straighten: pull a descent's staircase straight.  floor, ceiling, starts: as descend_grids took them; path: the
+    int32 (n, length, 2) path it or descend_grids_octile wrote, or any list of cells ended by (-1, -1); towards, max_step, max_drop,
+    clearance: the descent's -- with towards the lines are walked in the listed direction, without it from the listed cell back,
+    because a forward field's path is listed from the far end to the player.  From its start every row takes as its next corner
+    the farthest of the next max_look (at most STRAIGHTEN_MAX_LOOK) cells of the path that walk_lines calls clear from the last
+    corner, and goes on behind it, until the path ends, no cell ahead is clear or `corners` are found.  corners: an int (the
+    number to allocate) or a 32-bit integer (n, number, 2) tensor.  Returns (corners, count): the int32 corners, (-1, -1) past the
+    last, and the int32 (n,) number found -- corners[:, 0] is the any-angle waypoint, the cell to head for; with length_out True, a
+    float32 (n,) tensor or a raw device pointer, returns (corners, count, length): the summed Euclidean length of the straight
+    walks in cells, times the cell size in world units.  count_out: a tensor or a raw device pointer to write instead of a new
+    one.  One launch, asynchronous on `stream` (None, a torch stream or a raw handle); it can be captured into a graph."""
+    import torch
+    n, height, width = _flood_inputs(floor, ceiling, None)
+    _cells_in(starts, (n, 2), 'starts')
+    if not isinstance(path, torch.Tensor) or path.dim() != 3:
+        raise ValueError('path must be a contiguous int32 (%d, length, 2) tensor of (column, row) on the GPU' % n)
+    path_len = int(path.shape[1])
+    _cells_in(path, (n, path_len, 2), 'path')
+    if isinstance(corners, int) and not isinstance(corners, bool):
+        corners = torch.empty((n, corners, 2), dtype=torch.int32, device=floor.device)
+    if not isinstance(corners, torch.Tensor) or corners.dim() != 3 or corners.shape[0] != n or corners.shape[2] != 2:
+        raise ValueError('corners must be a number or a 32-bit integer (%d, number, 2) tensor' % n)
+    corner_len = int(corners.shape[1])
+    corners, pk = _int32_out(corners, (n, corner_len, 2), floor.device, 'corners')
+    count_out, pc = _int32_out(count_out, (n,), floor.device, 'count_out')
+    pl = None
+    if length_out is None or length_out is False:
+        length_out = None
+    elif isinstance(length_out, int) and not isinstance(length_out, bool):
+        pl = length_out  # a raw device pointer to n floats
+    else:
+        if length_out is True:
+            length_out = torch.empty(n, dtype=torch.float32, device=floor.device)
+        if not isinstance(length_out, torch.Tensor) or length_out.dtype != torch.float32:
+            raise ValueError('length_out must be True, a float32 tensor or a device pointer')
+        pl = _out_tensor(length_out, n * 4, 'length_out')
+    params = FloodParams(max_step, max_drop, clearance, FLOOD_TOWARDS if towards else 0)
+    v = ctypes.c_void_p
+    _check(lib().rdoom_path_straighten(v(floor.data_ptr()), v(ceiling.data_ptr()), n, width, height, v(starts.data_ptr()), v(path.data_ptr()),
+                                       path_len, ctypes.byref(params), ctypes.c_uint32(int(max_look)), v(pk), corner_len, v(pc), v(pl),
+                                       v(_stream_handle(stream))))
+    return (corners, count_out) if length_out is None else (corners, count_out, length_out)
 
 
 class WallParams(ctypes.Structure):

@@ -390,6 +390,28 @@ rdoom_status rdoom::check_flood_octile(const rdoom_flood_octile_params *params, 
   return RDOOM_OK;
 }
 
+// what rdoom_grid_walk_lines (line.hip) checks: the arguments above (RDOOM_LINE_REVERSED is the one flag bit), then the targets
+rdoom_status rdoom::check_walk_lines(const rdoom_flood_params *params, uint32_t n, bool pointers, uint32_t width, uint32_t height, uint32_t n_to) {
+  static_assert(RDOOM_LINE_REVERSED == RDOOM_FLOOD_TOWARDS, "check_flood_grids admits the one flag bit");
+  if (rdoom_status s = rdoom::check_flood_grids(params, n, pointers, "floor, ceiling, starts, targets or clear output", width, height)) return s;
+  if (!n_to) return rdoom::fail(RDOOM_BAD_ARG, "n_to is 0: at least one target a row");
+  if ((uint64_t)n * n_to > 0x7FFFFFFFu) return rdoom::fail(RDOOM_BAD_ARG, "%u rows of %u targets: too many lines for one launch", n, n_to);
+  return RDOOM_OK;
+}
+
+// what rdoom_path_straighten (line.hip) checks: the arguments above, then the look-ahead and the two lengths
+rdoom_status rdoom::check_path_straighten(const rdoom_flood_params *params, uint32_t n, bool pointers, uint32_t width, uint32_t height,
+                                          uint32_t path_len, uint32_t max_look, uint32_t corner_len) {
+  constexpr uint32_t MAX_LEN = 1u << 22;
+  if (rdoom_status s = rdoom::check_flood_grids(params, n, pointers, "floor, ceiling, starts, path, corner output or count output", width, height))
+    return s;
+  if (!max_look || max_look > RDOOM_STRAIGHTEN_MAX_LOOK)
+    return rdoom::fail(RDOOM_BAD_ARG, "a max_look of %u: 1 to %u", max_look, RDOOM_STRAIGHTEN_MAX_LOOK);
+  if (!path_len || path_len > MAX_LEN) return rdoom::fail(RDOOM_BAD_ARG, "a path of %u entries: 1 to %u", path_len, MAX_LEN);
+  if (!corner_len || corner_len > MAX_LEN) return rdoom::fail(RDOOM_BAD_ARG, "a corner_len of %u entries: 1 to %u", corner_len, MAX_LEN);
+  return RDOOM_OK;
+}
+
 extern "C" {
 
 rdoom_status rdoom_flood_max_cells(uint32_t *cells_out) {

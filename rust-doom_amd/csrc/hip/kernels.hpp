@@ -297,4 +297,29 @@ struct WallArgs {
   float clearance;
 };
 
+// Kernels 22 and 23: straight walks on the grid (line.hip; include/rdoom.h "straight walks" has the contract).
+// 22: the chain of grid moves of the segment between two cell centres tested, one wavefront per line; a lane takes one crossing of
+// the longer axis and the crossing of the shorter one before it.
+struct WalkLinesArgs {
+  const float *floor, *ceiling;  // n x height x width each: rdoom_flood_grids' planes
+  const int32_t *from;           // n x (column, row)
+  const int32_t *to;             // n x n_to x (column, row)
+  uint8_t *clear_out;            // n x n_to
+  int32_t *stop_out;             // n x n_to x (column, row), or null
+  uint32_t lines, n_to;          // lines = n * n_to
+  uint32_t width, height;
+  float max_step, max_drop, clearance;
+};
+// 23: a listed path pulled straight, one wavefront per row; a lane walks the line to one candidate cell of the path.
+struct StraightenArgs {
+  const float *floor, *ceiling;  // n x height x width each
+  const int32_t *starts;         // n x (column, row)
+  const int32_t *path;           // n x path_len x (column, row)
+  int32_t *corners_out;          // n x corner_len x (column, row)
+  uint32_t *count_out;           // n
+  float *length_out;             // n, or null
+  uint32_t n, width, height, path_len, max_look, corner_len;
+  float max_step, max_drop, clearance;
+};
+
 }  // namespace rdoom_dev

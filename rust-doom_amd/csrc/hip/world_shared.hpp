@@ -371,6 +371,11 @@ rdoom_status check_flood_grids(const rdoom_flood_params *params, uint32_t n, boo
 // flood.hip: what rdoom_flood_grids_octile and rdoom_flood_descend_octile check: the same, then the two costs
 rdoom_status check_flood_octile(const rdoom_flood_octile_params *params, uint32_t n, bool pointers, const char *missing, uint32_t width,
                                 uint32_t height);
+// flood.hip: what rdoom_grid_walk_lines (line.hip) checks: the arguments shared with rdoom_flood_grids, then the targets a row
+rdoom_status check_walk_lines(const rdoom_flood_params *params, uint32_t n, bool pointers, uint32_t width, uint32_t height, uint32_t n_to);
+// flood.hip: what rdoom_path_straighten (line.hip) checks: the same, then the look-ahead and the two lengths
+rdoom_status check_path_straighten(const rdoom_flood_params *params, uint32_t n, bool pointers, uint32_t width, uint32_t height,
+                                   uint32_t path_len, uint32_t max_look, uint32_t corner_len);
 // flood.hip: the cells of a row, column or diagonal one thread of a grid's flood sweeps at a time
 uint32_t flood_run_length(uint32_t width, uint32_t height);
 
