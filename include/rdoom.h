@@ -24,8 +24,8 @@
  *   it to this, with every pointer at the least alignment allowed here and guard bands around every array).  A device pointer
  *   needs the alignment of its element and no more: 1 for bytes (frames, maps, masks, light tables given to a render), 2 for
  *   16-bit planes and distances, 4 for float, int32_t and uint32_t data (times, offsets, fans, directions, seeds, counts, `seen`,
- *   `area` and `visited` words, level slots, depth and primitive planes).  A record needs the alignment of its widest member:
- *   4 for rdoom_player_state, rdoom_player_input and rdoom_pose.  The exceptions, each stated at its entry point and refused with
+ *   `area`, `visited` and thing-bit words, level slots, depth and primitive planes).  A record needs the alignment of its widest member:
+ *   4 for rdoom_player_state, rdoom_player_input, rdoom_pose and rdoom_thing_nearest.  The exceptions, each stated at its entry point and refused with
  *   RDOOM_BAD_ARG where less is given: a game state (rdoom_world_game_bytes) needs 16 bytes, the light tables
  *   rdoom_lightset_tables writes need 4, and rdoom_selftest_sincos' device_raw needs 8.  Rows and records are tight unless a
  *   stride is an argument, so an array of records is aligned as its first record is and no better (pose 1 of an array of
@@ -1612,6 +1612,124 @@ rdoom_status rdoom_path_straighten(const float *d_floor, const float *d_ceiling,
                                    const int32_t *d_starts, const int32_t *d_path, uint32_t path_len, const rdoom_flood_params *params,
                                    uint32_t max_look, int32_t *d_corners_out, uint32_t corner_len, uint32_t *d_count_out,
                                    float *d_length_out, void *stream);
+
+/* ---- things: what each player sees, touches and collects of a level's things -----------------------------------
+ * The thing table.  One 32-byte record per THINGS entry, in lump order, for the entries LevelWalker::things sends down its decor
+ * branch (wad/src/visitor.rs:1010-1026): sector_at finds a sector for the entry, and its type is none of the marker types 1, 2, 3,
+ * 4, 11, 14.  An entry has its record whether or not the metadata knows its type and whether or not its sprite lump exists: an item
+ * is somewhere even when it cannot be drawn.
+ *   x, z: from_wad_coords of the entry, the low[0] and low[2] of the rdoom_decor of the same thing.
+ *   base: from_wad_height of its sector's floor; of its ceiling when the metadata says hanging.
+ *   radius: (float)metadata radius / 100.0f; 0 without metadata.
+ *   object_id: the sector's floor_id (hanging: ceiling_id) as rdoom_map_sector carries it; 0: nothing moves it.
+ *   sector: its index in rdoom_world_map_sectors' table.
+ *   thing_type, flags, angle: WadThing's fields, verbatim (the angle's 16 bits as they stand in the lump).
+ *   category: in the low byte the array of [things] the metadata read the type from, in the order they are merged (first match),
+ *   RDOOM_THING_UNKNOWN without metadata; RDOOM_THING_HANGING or-ed in when the metadata says hanging.
+ * The live height of a thing in player p's game is base + off(object_id), off() the map contract's on row p of d_object_offsets: a
+ * candle on a lift rides it. */
+#define RDOOM_THING_DECORATION 0u
+#define RDOOM_THING_WEAPON 1u
+#define RDOOM_THING_POWERUP 2u
+#define RDOOM_THING_ARTIFACT 3u
+#define RDOOM_THING_AMMO 4u
+#define RDOOM_THING_KEY 5u
+#define RDOOM_THING_MONSTER 6u
+#define RDOOM_THING_UNKNOWN 7u
+#define RDOOM_THING_HANGING 0x100u
+typedef struct rdoom_thing {
+  float x, z;
+  float base;
+  float radius;
+  uint32_t object_id;
+  uint32_t sector;
+  uint16_t thing_type, flags;
+  uint16_t category;
+  uint16_t angle;
+} rdoom_thing;
+/* borrowed pointers into a rdoom_world / rdoom_worldset (valid until it is destroyed) */
+typedef struct rdoom_map_things {
+  const rdoom_thing *things;
+  uint32_t n_things;
+} rdoom_map_things;
+/* The thing table of the world's level, and of slot `slot` of a set (equal to the single world's of the same level).  Both work on
+ * RDOOM_WORLD_HOST_ONLY handles. */
+rdoom_status rdoom_world_map_things(const rdoom_world *world, rdoom_map_things *out);
+rdoom_status rdoom_worldset_level_map_things(const rdoom_worldset *set, uint32_t slot, rdoom_map_things *out);
+
+/* A rdoom_thingset holds the thing tables of n_levels levels on the current device: things[l] points at counts[l] records, a
+ * level's own table or any other -- a consumer may scatter items of its own per run.  A level may hold 0 things (things[l] may
+ * then be NULL).  rdoom_thingset_info: the levels, *out_words = max(1, ceil(largest count / 32)), the stride every row of thing
+ * bits needs at least, and the largest object_id of any record.  Every out pointer of it may be NULL.
+ * Errors of create (RDOOM_BAD_ARG): n_levels == 0; NULL things, counts or out; a NULL table with a non-zero count; a count above
+ * 2^20; a category whose low byte is above 7, or with bits other than RDOOM_THING_HANGING above it; an x, z, base or radius that
+ * is not finite; a negative radius. */
+typedef struct rdoom_thingset rdoom_thingset;
+rdoom_status rdoom_thingset_create(const rdoom_thing *const *things, const uint32_t *counts, uint32_t n_levels, rdoom_thingset **out);
+void rdoom_thingset_destroy(rdoom_thingset *set);
+rdoom_status rdoom_thingset_info(const rdoom_thingset *set, uint32_t *out_n_levels, uint32_t *out_words, uint32_t *out_max_object_id);
+
+/* Sensing: which things each of n players sees and touches, the nearest visible thing of every category, and what it collects, in
+ * one launch.  params: max_range finite and > 0; cos_half_fov finite, <= -1 means no field-of-view test; touch_radius finite and
+ * >= 0, the body's (0.19 is the player step's); touch_below and touch_above >= 0, +inf allowed: the vertical window; collect_mask:
+ * bit c set means a touched thing of category c is collected; flags: 0.
+ * Every float below is binary32, every operation is rounded once and none is contracted; divisions and the square root are IEEE;
+ * a * b + c * d means round(round(a * b) + round(c * d)).
+ * Player p, in level L with T things (a world: its one level; a set: slot d_levels[p], level L of `things`).  (s, c) = the
+ * project's sincos of the player's yaw (csrc/hip/sincos_rd.hpp); r = (c, -s) and f = (-s, -c) are the map contract's right and
+ * forward; o = (pos.x, pos.z).
+ * Thing i < T is examined when its bit -- bit i % 32 of word p * stride + i / 32 -- is clear in d_collected as it stood when the
+ * call began (a NULL d_collected: nothing is collected).  For an examined thing:
+ *   dx = x - pos.x;  dz = z - pos.z;  d2 = dx * dx + dz * dz;  y = base + off(object_id);  dy = pos.y - y,
+ * off() the map contract's on row p of d_object_offsets.
+ * Touched: d2 <= tr * tr with tr = touch_radius + radius, and dy >= -touch_below, and dy <= touch_above.
+ * In range: d2 <= max_range * max_range.
+ * In the field of view: cos_half_fov <= -1, or dx * f.x + dz * f.z >= cos_half_fov * sqrtf(d2).
+ * Visible: in range, in the field of view, and T_r == 1, T_r the seen-lines contract's for the ray o + t * vel with vel = (dx, dz):
+ * its "Ray against line" and "Blocking" word for word, over the line table of the player's level.  So a shut door hides a thing in
+ * the game of the player who has not opened it, and only there; and a thing exactly on a blocking line is visible, because a hit at
+ * t == 1 leaves T_r at 1.
+ * A comparison with a NaN is false: a player at a NaN position sees and touches nothing.  A thing that is not examined is neither
+ * visible nor touched, and cannot be nearest.
+ * Outputs; every one may be NULL, but not all five.  Bit rows are rows of `stride` uint32 words, stride >= the set's words.
+ *   d_visible_out, d_touched_out: words [0, ceil(T / 32)) of row p are written whole, bit i % 32 of word i / 32 set for a visible /
+ *   touched thing i and the bits at and above T zero.  No word beyond them is written.
+ *   d_collected: the bits of the touched things whose category bit (1 << the category's low byte) is in collect_mask are OR-ed in,
+ *   after everything above was evaluated: a thing collected by this call is still reported by this call and is gone in the next.
+ *   Bits are never cleared; words beyond ceil(T / 32) are never written; the caller zeroes a row to start an episode.
+ *   d_new_out[p * 8 + c] (n x 8 uint32): how many things of category c this call collected for p.  All eight are written.
+ *   d_nearest_out[p * 8 + c] (n x 8 rdoom_thing_nearest): the visible thing of category c with the smallest d2, the lowest index
+ *   among equals: index, d2, right = dx * r.x + dz * r.z, forward = dx * f.x + dz * f.z.  Where there is none: {-1, +inf, 0, 0}.
+ * A level slot >= the set's size is seen on the device only: that player's bit rows are untouched, its nearest records are "none"
+ * and its counts are 0.
+ * One launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so the call can be
+ * captured into a graph.  Errors, all checked before anything is queued (RDOOM_BAD_ARG): a NULL handle, thing set or params, or
+ * (n > 0) NULL d_states / d_levels; all five outputs NULL; a stride smaller than the set's words while d_collected, d_visible_out
+ * or d_touched_out is given; a thing set whose levels are not as many as the handle's (a world: not 1) or that lives on another
+ * device; n_objects smaller than the game's objects (as for rdoom_world_draw_maps), or not above the set's largest object_id, while
+ * d_object_offsets is given; params outside the domains above; flags not 0; a handle created with RDOOM_WORLD_HOST_ONLY or living
+ * on another device.  n == 0 queues nothing. */
+typedef struct rdoom_thing_sense {
+  float max_range;
+  float cos_half_fov;
+  float touch_radius;
+  float touch_below, touch_above;
+  uint32_t collect_mask;
+  uint32_t flags;
+} rdoom_thing_sense;
+typedef struct rdoom_thing_nearest {
+  int32_t index;
+  float d2, right, forward;
+} rdoom_thing_nearest;
+rdoom_status rdoom_world_sense_things(const rdoom_world *world, const rdoom_thingset *things, const rdoom_player_state *d_states,
+                                      uint32_t n, const float *d_object_offsets, uint32_t n_objects, const rdoom_thing_sense *params,
+                                      uint32_t *d_collected, uint32_t *d_visible_out, uint32_t *d_touched_out, uint32_t stride,
+                                      rdoom_thing_nearest *d_nearest_out, uint32_t *d_new_out, void *stream);
+rdoom_status rdoom_worldset_sense_things(const rdoom_worldset *set, const rdoom_thingset *things, const rdoom_player_state *d_states,
+                                         const uint32_t *d_levels, uint32_t n, const float *d_object_offsets, uint32_t n_objects,
+                                         const rdoom_thing_sense *params, uint32_t *d_collected, uint32_t *d_visible_out,
+                                         uint32_t *d_touched_out, uint32_t stride, rdoom_thing_nearest *d_nearest_out,
+                                         uint32_t *d_new_out, void *stream);
 
 #ifdef __cplusplus
 }

@@ -90,6 +90,15 @@ WALL_TILE = (64, 32)  # the cells (across, down) of the tile one workgroup of th
 SPAWN_TRIES = 8  # RDOOM_SPAWN_TRIES: the candidates spawn_players draws for a player before it falls back to the level's start
 SPAWN_RISE = 0.5  # RDOOM_SPAWN_RISE: a spawned player's height above the live floor, the start's above the floor at the start marker
 SPAWN_ENTRY = np.dtype([('a', '<f4', 3), ('b', '<f4', 3), ('c', '<f4', 3), ('cumulative', '<f4')])  # rdoom_spawn_entry
+# rdoom_thing: one thing of a level's thing table (World.map_things, DeviceThings), its categories (the low byte of `category`), and
+# rdoom_thing_nearest: sense_things' record of the nearest visible thing of a category
+THING = np.dtype([('x', '<f4'), ('z', '<f4'), ('base', '<f4'), ('radius', '<f4'), ('object_id', '<u4'), ('sector', '<u4'),
+                  ('thing_type', '<u2'), ('flags', '<u2'), ('category', '<u2'), ('angle', '<u2')])
+THING_NEAREST = np.dtype([('index', '<i4'), ('d2', '<f4'), ('right', '<f4'), ('forward', '<f4')])
+assert THING.itemsize == 32 and THING_NEAREST.itemsize == 16
+THING_DECORATION, THING_WEAPON, THING_POWERUP, THING_ARTIFACT, THING_AMMO, THING_KEY, THING_MONSTER, THING_UNKNOWN = range(8)
+THING_HANGING = 0x100  # RDOOM_THING_HANGING, above the category's low byte
+THING_CATEGORIES = 8
 LINE_MAPPED = 0x100  # RDOOM_LINE_MAPPED, Doom's "already on the map": drawn through a seen set whether seen or not
 AREA_UNKNOWN, AREA_FREE, AREA_WALL = 0, 1, 2  # RDOOM_AREA_*: draw_area_maps' bytes (3: a cell that carries both bits)
 AREA_MAX_STEPS = 4096  # RDOOM_AREA_MAX_STEPS
@@ -193,7 +202,9 @@ API_SYMBOLS = [
     'rdoom_world_draw_area_planes', 'rdoom_worldset_draw_area_planes', 'rdoom_flood_grid_max_cells', 'rdoom_flood_grids',
     'rdoom_world_area_cells', 'rdoom_worldset_area_cells', 'rdoom_flood_descend', 'rdoom_world_area_frontiers',
     'rdoom_worldset_area_frontiers', 'rdoom_wall_distance', 'rdoom_selftest_sincos', 'rdoom_flood_grids_octile',
-    'rdoom_flood_descend_octile', 'rdoom_grid_walk_lines', 'rdoom_path_straighten']
+    'rdoom_flood_descend_octile', 'rdoom_grid_walk_lines', 'rdoom_path_straighten',
+    'rdoom_world_map_things', 'rdoom_worldset_level_map_things', 'rdoom_thingset_create', 'rdoom_thingset_destroy', 'rdoom_thingset_info',
+    'rdoom_world_sense_things', 'rdoom_worldset_sense_things']
 
 _lib = None
 
@@ -210,7 +221,8 @@ def lib():
         for name in API_SYMBOLS:
             fn = getattr(L, name)  # AttributeError if a declared symbol is not exported
             if name not in ('rdoom_last_error', 'rdoom_level_destroy', 'rdoom_batch_destroy', 'rdoom_wad_close',
-                            'rdoom_built_destroy', 'rdoom_world_destroy', 'rdoom_worldset_destroy', 'rdoom_lightset_destroy'):
+                            'rdoom_built_destroy', 'rdoom_world_destroy', 'rdoom_worldset_destroy', 'rdoom_lightset_destroy',
+                            'rdoom_thingset_destroy'):
                 fn.restype = ctypes.c_int32
             elif name != 'rdoom_last_error':
                 fn.restype = None
@@ -1401,6 +1413,149 @@ def _reveal_lines(call, words, states, levels, fan, max_range, offsets, seen, ne
     return seen
 
 
+class MapThings(ctypes.Structure):
+    _fields_ = [('things', ctypes.c_void_p), ('n_things', ctypes.c_uint32)]
+
+
+class ThingSense(ctypes.Structure):
+    """rdoom_thing_sense"""
+    _fields_ = [('max_range', ctypes.c_float), ('cos_half_fov', ctypes.c_float), ('touch_radius', ctypes.c_float),
+                ('touch_below', ctypes.c_float), ('touch_above', ctypes.c_float), ('collect_mask', ctypes.c_uint32),
+                ('flags', ctypes.c_uint32)]
+
+
+def _map_things(get):
+    """World.map_things / WorldSet.map_things: a copy of the table get(&rdoom_map_things) lends"""
+    a = MapThings()
+    _check(get(ctypes.byref(a)))
+    return BuiltLevel._view(None, a.things, a.n_things, THING)
+
+
+class DeviceThings:
+    """The thing tables of one or more levels resident on the device (rdoom_thingset_create): slot l holds tables[l], an array of
+    THING records -- a level's own (World.map_things()) or any other, so that a consumer can scatter items of its own per run.
+    A single array is a set of one level.  World.sense_things / WorldSet.sense_things sense them."""
+
+    def __init__(self, tables):
+        if isinstance(tables, np.ndarray):
+            tables = [tables]
+        arrays = [np.ascontiguousarray(t, THING).reshape(-1) for t in tables]
+        self.n_levels, self.counts = len(arrays), [len(a) for a in arrays]
+        ptrs = (ctypes.c_void_p * max(1, len(arrays)))(*[_ptr(a) for a in arrays])
+        counts = (ctypes.c_uint32 * max(1, len(arrays)))(*self.counts)
+        self._h = ctypes.c_void_p()
+        _check(lib().rdoom_thingset_create(ptrs, counts, len(arrays), ctypes.byref(self._h)))
+
+    def close(self):
+        if self._h:
+            lib().rdoom_thingset_destroy(self._h)
+            self._h = ctypes.c_void_p()
+
+    def __del__(self):
+        _close_quietly(self)
+
+    def info(self):
+        """rdoom_thingset_info: (levels, words, largest object_id)"""
+        n, w, o = ctypes.c_uint32(0), ctypes.c_uint32(0), ctypes.c_uint32(0)
+        _check(lib().rdoom_thingset_info(self._h, ctypes.byref(n), ctypes.byref(w), ctypes.byref(o)))
+        return n.value, w.value, o.value
+
+    def words(self):
+        """the 32-bit words a row of thing bits takes at least: max(1, ceil(largest table / 32))"""
+        return self.info()[1]
+
+
+def unpack_things(row, n):
+    """a row of sense_things' bits (a numpy array or tensor of 32-bit words) as a bool array of n: [i] = thing i's bit is set"""
+    return unpack_seen(row, n)
+
+
+ThingsSensed = collections.namedtuple('ThingsSensed', 'collected visible touched nearest new')
+
+
+def _pointer(t, nbytes, what):
+    """the device pointer of an optional argument: None, a raw device pointer (an int, taken as it is), or a contiguous GPU tensor
+    of at least nbytes"""
+    if t is None or isinstance(t, (int, np.integer)):
+        return int(t) if t else None
+    if t.device.type != 'cuda' or not t.is_contiguous() or t.numel() * t.element_size() < nbytes:
+        raise ValueError('%s must be a contiguous GPU tensor of at least %d bytes' % (what, nbytes))
+    return t.data_ptr()
+
+
+def _sense_things(call, states, levels, things, max_range, fov, touch_radius, touch_below, touch_above, collect, offsets, collected,
+                  visible_out, touched_out, nearest_out, new_out, stream, n, n_objects, stride):
+    """World.sense_things / WorldSet.sense_things: the checks and the launch; call(states, levels, n, offsets, n_objects, params,
+    collected, visible, touched, stride, nearest, new, stream) is the C entry point with its handle and the thing set bound"""
+    if not isinstance(things, DeviceThings):
+        raise ValueError('things must be a DeviceThings')
+    raw = isinstance(states, (int, np.integer))
+    if raw:
+        if n is None:
+            raise ValueError('n is needed with raw pointers')
+        n = int(n)
+    else:
+        n = _n_players(states)
+    words = things.words()
+    rows = (collected, visible_out, touched_out)
+    if all(o is None for o in rows + (nearest_out, new_out)):
+        import torch
+        visible_out = torch.empty((n, words), dtype=torch.int32, device=states.device)
+        touched_out = torch.empty((n, words), dtype=torch.int32, device=states.device)
+        nearest_out = torch.empty((n, THING_CATEGORIES, 4), dtype=torch.float32, device=states.device)
+        new_out = torch.empty((n, THING_CATEGORIES), dtype=torch.int32, device=states.device)
+        rows = (collected, visible_out, touched_out)
+    if stride is None:
+        strides = {int(r.shape[-1]) for r in rows if r is not None and not isinstance(r, (int, np.integer))}
+        if len(strides) > 1:
+            raise ValueError('collected, visible_out and touched_out must have rows of one length, got %s' % sorted(strides))
+        stride = strides.pop() if strides else words
+    stride = int(stride)
+    for r, what in zip(rows, ('collected', 'visible_out', 'touched_out')):
+        if r is not None and not isinstance(r, (int, np.integer)) and (r.element_size() != 4 or r.dtype.is_floating_point or r.dim() != 2
+                                                                       or r.shape[0] != n):
+            raise ValueError('%s must be a 32-bit integer (n, words) tensor for %d players' % (what, n))
+    n_obj = 0
+    if offsets is not None:
+        if isinstance(offsets, (int, np.integer)):
+            if n_objects is None:
+                raise ValueError('n_objects is needed with a raw offsets pointer')
+            n_obj = int(n_objects)
+        else:
+            if offsets.dim() != 3 or offsets.shape[0] != n or offsets.shape[2] != 3 or offsets.element_size() != 4:
+                raise ValueError('offsets must be a float32 (n, n_objects, 3) tensor for %d players, got %s' % (n, tuple(offsets.shape)))
+            n_obj = int(offsets.shape[1])
+    mask = 0
+    for c in ((collect,) if isinstance(collect, (int, np.integer)) else collect):
+        if not 0 <= int(c) < THING_CATEGORIES:
+            raise ValueError('collect names categories 0 .. 7, not %r' % (c,))
+        mask |= 1 << int(c)
+    params = ThingSense(max_range, -1.0 if fov is None else math.cos(0.5 * float(fov)), touch_radius, touch_below, touch_above, mask, 0)
+    v = ctypes.c_void_p
+    _check(call(v(_pointer(states, n * PLAYER_STATE.itemsize, 'states')), v(_pointer(levels, n * 4, 'levels')), n,
+                v(_pointer(offsets, n * n_obj * 12, 'offsets')), n_obj, ctypes.byref(params),
+                v(_pointer(collected, n * stride * 4, 'collected')), v(_pointer(visible_out, n * stride * 4, 'visible_out')),
+                v(_pointer(touched_out, n * stride * 4, 'touched_out')), stride,
+                v(_pointer(nearest_out, n * THING_CATEGORIES * 16, 'nearest_out')), v(_pointer(new_out, n * THING_CATEGORIES * 4, 'new_out')),
+                v(_stream_handle(stream))))
+    return ThingsSensed(collected, visible_out, touched_out, nearest_out, new_out)
+
+
+_SENSE_DOC = """marks the things of `things` (a DeviceThings) every player sees and touches, finds the nearest visible
+        thing of each category and collects what the player walks over, in one launch.  states: the tensor a step leaves; offsets:
+        None or step_game's tensor, so that a shut door hides a thing until that player opens it and a candle on a lift rides it.
+        max_range: how far a player sees; fov: None (all round) or the full opening angle in radians; touch_radius: the body's;
+        touch_below / touch_above: how far the thing's base may lie above / below the player's position to be touched; collect: the
+        categories (THING_*) whose touched things are collected.  collected: an int32 (n, words >= things.words()) tensor -- a
+        collected thing is neither seen nor touched any more; its bits are OR-ed into after the call's evaluation and never
+        cleared, so zero a row to start an episode.  visible_out / touched_out: int32 (n, words) tensors, bit i % 32 of word i // 32
+        of row p for thing i (unpack_things unpacks a row); nearest_out: n x 8 THING_NEAREST records (any tensor of n * 128 bytes,
+        for instance float32 (n, 8, 4): index as bits, d2, right, forward); new_out: int32 (n, 8), what this call collected per
+        category.  With every output None, visible, touched, nearest and new are allocated.  Every tensor may instead be a raw
+        device pointer (an int; then n, and with offsets n_objects, and stride must be given).  Returns a ThingsSensed of the five.
+        Asynchronous on `stream`."""
+
+
 class AreaGridStruct(ctypes.Structure):
     _fields_ = [('ix0', ctypes.c_int32), ('iz0', ctypes.c_int32), ('gw', ctypes.c_uint32), ('gh', ctypes.c_uint32),
                 ('pitch', ctypes.c_uint32), ('words', ctypes.c_uint32)]
@@ -2280,6 +2435,21 @@ class World:
         return _reveal_lines(lambda st, lv, *rest: L.rdoom_world_reveal_lines(self._h, st, *rest), self.seen_words(), states, None, fan,
                              max_range, offsets, seen, new_out, stream)
 
+    # ---- things ------------------------------------------------------------------------------------------------------------
+    def map_things(self):
+        """a copy of rdoom_world_map_things: the level's thing table, a THING record per THINGS entry that is no marker and stands in
+        a sector, in lump order (position, base height and the object that moves it, radius, sector, type, flags, category, angle)"""
+        return _map_things(lambda a: lib().rdoom_world_map_things(self._h, a))
+
+    def sense_things(self, states, things, max_range, fov=None, touch_radius=0.19, touch_below=math.inf, touch_above=math.inf, collect=(),
+                     offsets=None, collected=None, visible_out=None, touched_out=None, nearest_out=None, new_out=None, stream=None,
+                     n=None, n_objects=None, stride=None):
+        L = lib()
+        return _sense_things(lambda st, lv, *rest: L.rdoom_world_sense_things(self._h, things._h, st, *rest), states, None, things,
+                             max_range, fov, touch_radius, touch_below, touch_above, collect, offsets, collected, visible_out, touched_out,
+                             nearest_out, new_out, stream, n, n_objects, stride)
+    sense_things.__doc__ = 'rdoom_world_sense_things: ' + _SENSE_DOC
+
     # ---- sectors -----------------------------------------------------------------------------------------------------------
     def map_sectors(self):
         """a copy of rdoom_world_map_sectors: the level's sector table, a MapSectors of (sectors, leaf_sector, leaf_edges, edges)"""
@@ -2556,6 +2726,20 @@ class WorldSet:
                              levels, fan, max_range, offsets, seen, new_out, stream)
 
     # ---- sectors -----------------------------------------------------------------------------------------------------------
+    def map_things(self, slot):
+        """a copy of rdoom_worldset_level_map_things: the thing table of the level in `slot`, as World.map_things gives it"""
+        return _map_things(lambda a: lib().rdoom_worldset_level_map_things(self._h, int(slot), a))
+
+    def sense_things(self, states, levels, things, max_range, fov=None, touch_radius=0.19, touch_below=math.inf, touch_above=math.inf,
+                     collect=(), offsets=None, collected=None, visible_out=None, touched_out=None, nearest_out=None, new_out=None,
+                     stream=None, n=None, n_objects=None, stride=None):
+        L = lib()
+        return _sense_things(lambda *rest: L.rdoom_worldset_sense_things(self._h, things._h, *rest), states, levels, things, max_range, fov,
+                             touch_radius, touch_below, touch_above, collect, offsets, collected, visible_out, touched_out, nearest_out,
+                             new_out, stream, n, n_objects, stride)
+    sense_things.__doc__ = 'rdoom_worldset_sense_things (levels: a GPU tensor of one 32-bit slot per player; slot l of `things` is the ' \
+                           'level in slot l): ' + _SENSE_DOC
+
     def map_sectors(self, slot):
         """a copy of rdoom_worldset_level_map_sectors: the level's sector table, a MapSectors of (sectors, leaf_sector, leaf_edges, edges)"""
         return _map_sectors(lambda a: lib().rdoom_worldset_level_map_sectors(self._h, int(slot), a))

@@ -322,4 +322,21 @@ struct StraightenArgs {
   float max_step, max_drop, clearance;
 };
 
+// Kernel 24: what each player sees, touches and collects of its level's things (things.hip; include/rdoom.h "things" has the
+// contract).  One 256-thread workgroup per player; a thread takes one thing of a pass of 256, and the pass's candidates for sight
+// go through sight.hpp's sight_limits as rays.
+struct ThingSenseArgs {
+  const rdoom_player_state *states;
+  const float *offsets;          // n x n_objects x xyz, or null
+  const rdoom_thing *things;     // the set's records, level after level
+  uint32_t *collected;           // n x stride words, or null: read as they stand, then OR-ed into
+  uint32_t *visible_out;         // n x stride words, or null
+  uint32_t *touched_out;         // n x stride words, or null
+  rdoom_thing_nearest *nearest_out;  // n x 8 records, or null
+  uint32_t *new_out;             // n x 8, or null
+  uint32_t n_objects, stride;
+  float max_range, cos_half_fov, touch_radius, touch_below, touch_above;
+  uint32_t collect_mask;
+};
+
 }  // namespace rdoom_dev

@@ -1173,6 +1173,12 @@ rdoom_status rdoom_world_map_sectors(const rdoom_world *w, rdoom_map_sectors *ou
   return RDOOM_OK;
 }
 
+rdoom_status rdoom_world_map_things(const rdoom_world *w, rdoom_map_things *out) {
+  if (!w || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  *out = rdoom_map_things{w->host.things.data(), (uint32_t)w->host.things.size()};
+  return RDOOM_OK;
+}
+
 rdoom_status rdoom_world_spawn_table(const rdoom_world *w, rdoom_spawn_table *out) {
   if (!w || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   fill_spawn(w->host, *out);
@@ -1306,6 +1312,14 @@ rdoom_status rdoom_worldset_level_map_sectors(const rdoom_worldset *s, uint32_t 
   if (!s || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   if (slot >= s->host.levels.size()) return rdoom::fail(RDOOM_BAD_ARG, "slot %u of a set of %zu levels", slot, s->host.levels.size());
   fill_sectors(s->host.levels[slot], *out);
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_worldset_level_map_things(const rdoom_worldset *s, uint32_t slot, rdoom_map_things *out) {
+  if (!s || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (slot >= s->host.levels.size()) return rdoom::fail(RDOOM_BAD_ARG, "slot %u of a set of %zu levels", slot, s->host.levels.size());
+  const std::vector<rdoom_thing> &things = s->host.levels[slot].things;
+  *out = rdoom_map_things{things.data(), (uint32_t)things.size()};
   return RDOOM_OK;
 }
 

@@ -130,12 +130,15 @@ World build_world(const LoadedWad &w, size_t level_index) {
   const LevelAnalysis analysis(level, archive.metadata());
   WorldBuilder b;
   std::vector<uint32_t> leaf_subsectors;  // per chunk, in walk order
+  std::vector<rdoom_thing> things;        // the thing table, in lump order
   {
     LevelWalker walker(level, analysis, w.textures, archive.metadata(), b);
     walker.record_leaf_subsectors = &leaf_subsectors;
+    walker.record_things = &things;
     walker.walk();
   }
   World out = b.build();
+  out.things = std::move(things);
   out.game_objects = (uint32_t)std::max<size_t>(1, analysis.num_objects());
   for (const Trigger &t : analysis.triggers()) {
     rdoom_trigger r{};

@@ -46,6 +46,8 @@ struct World {
   std::vector<uint32_t> leaf_sector;
   std::vector<rdoom_map_leaf_edges> leaf_edges;
   std::vector<rdoom_map_edge> map_edges;
+  // the level's thing table (include/rdoom.h "things"): a record per THINGS entry the walk sends down its decor branch, in lump order
+  std::vector<rdoom_thing> things;
   // the level's spawn table (include/rdoom.h "spawn"): an entry per floor triangle with an area, in the order of `triangles`
   std::vector<rdoom_spawn_entry> spawn;
   float start_pos[3] = {0, 0, 0};  // the player's start, as the renderer's Builder takes it (rdoom_built_start)

@@ -161,6 +161,7 @@ struct ThingMetadata {
   std::string sequence;
   bool hanging;
   uint32_t radius;
+  uint16_t category;  // the array of [things] it was read from, in the order they are merged: RDOOM_THING_DECORATION .. RDOOM_THING_MONSTER
 };
 struct WadMetadata {
   std::vector<SkyMetadata> sky;
@@ -529,6 +530,9 @@ class LevelWalker {  // visitor.rs:499-1138
   // wall_quad() / sky_quad() by the device's results.
   std::vector<SegInput> *record_segs = nullptr;
   const std::vector<SegGeometry> *precomputed_segs = nullptr;
+  // Records one rdoom_thing (include/rdoom.h "things") per THINGS entry that things() sends down its decor branch, in lump order,
+  // whether or not the metadata knows the type or the sprite exists.
+  std::vector<rdoom_thing> *record_things = nullptr;
 
  private:
   const Level &level_;

@@ -384,6 +384,7 @@ WadMetadata WadMetadata::from_text(const std::string &text) {
   m.animated_flats = names2(need(anim, "flats", TomlValue::Array));
   m.animated_walls = names2(need(anim, "walls", TomlValue::Array));
   const TomlValue &things = need(root, "things", TomlValue::Table);
+  uint16_t category = 0;  // RDOOM_THING_DECORATION .. RDOOM_THING_MONSTER, in this order
   for (const char *cat : {"decorations", "weapons", "powerups", "artifacts", "ammo", "keys", "monsters"}) {
     for (const TomlValue &t : need(things, cat, TomlValue::Array).arr) {
       ThingMetadata tm;
@@ -392,8 +393,10 @@ WadMetadata WadMetadata::from_text(const std::string &text) {
       tm.sequence = need(t, "sequence", TomlValue::Str).s;
       tm.hanging = need(t, "hanging", TomlValue::Bool).b;
       tm.radius = (uint32_t)need(t, "radius", TomlValue::Int).i;
+      tm.category = category;
       m.things.push_back(std::move(tm));
     }
+    category++;
   }
   if (const TomlValue *lds = root.find("linedef")) {
     if (lds->type != TomlValue::Array) meta_fail("`linedef` must be an array of tables");

@@ -683,6 +683,20 @@ void LevelWalker::things() {  // visitor.rs:1010-1026
 
 void LevelWalker::decor(const WadThing &thing, Pnt2f pos, const WadSector *sector) {  // visitor.rs:1062-1137
   const ThingMetadata *meta = meta_.find_thing(thing.thing_type);
+  if (record_things) {  // the thing table's record: an item is somewhere even when it cannot be drawn
+    const DynamicSectorInfo *dyn = analysis_.dynamic(level_.sector_id(sector));
+    const bool hanging = meta && meta->hanging;
+    rdoom_thing r{};
+    r.x = pos.x, r.z = pos.y;
+    r.base = from_wad_height(hanging ? sector->ceiling_height : sector->floor_height);
+    r.radius = meta ? (float)meta->radius / 100.0f : 0.0f;
+    r.object_id = dyn ? (hanging ? dyn->ceiling_id.v : dyn->floor_id.v) : 0u;
+    r.sector = level_.sector_id(sector);
+    r.thing_type = thing.thing_type, r.flags = thing.flags;
+    r.category = (uint16_t)((meta ? meta->category : RDOOM_THING_UNKNOWN) | (hanging ? RDOOM_THING_HANGING : 0u));
+    r.angle = (uint16_t)thing.angle;
+    record_things->push_back(r);
+  }
   if (!meta) return;
   WadName sprite0 = meta->sprite;
   if (!meta->sequence.empty()) (void)sprite0.push((uint8_t)meta->sequence[0]);
