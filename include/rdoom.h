@@ -17,7 +17,7 @@
  *   - framebuffers are 8-bit palette indices, row 0 = bottom row (glReadPixels order), background 0.
  *     rdoom_batch_resolve_rgb / rdoom_batch_read_rgb turn them into the colours the reference's window shows: PLAYPAL 0 of
  *     the pose's level where a primitive was drawn, the GL clear colour RDOOM_CLEAR_R/G/B where none was.
- *   - a rdoom_level is immutable after create (shareable); a rdoom_batch is single-owner.
+ *   - a rdoom_level is immutable after create (shareable), but for rdoom_level_set_decor_things; a rdoom_batch is single-owner.
  *
  * Caller memory: alignment and extent
  *   What the library asks of a device pointer, and what it does with the memory behind it (tests/test_gpu_caller_memory_*.py hold
@@ -502,6 +502,11 @@ rdoom_status rdoom_built_light_infos(const rdoom_built *built, const rdoom_light
 rdoom_status rdoom_built_start(const rdoom_built *built, float out_pos[3], float *out_yaw);
 /* bounds of the sub-sector floor polygons, for pose generators: n polygons, centroid xz + floor y */
 rdoom_status rdoom_built_floor_centroids(const rdoom_built *built, const float **out_xyz, uint32_t *out_n);
+/* Which thing every decor quad is: *out_n == n_decor_verts / 4 entries, entry q for the quad of decor vertices 4q .. 4q + 3: the
+ * thing's index in the level's thing table (rdoom_world_map_things of the same level; "things" below).  Strictly increasing: the
+ * build visits the things in table order and a thing emits at most one quad (none without metadata or sprite).  Borrowed, valid
+ * until rdoom_built_destroy.  Feeds rdoom_level_set_decor_things.  No reference counterpart. */
+rdoom_status rdoom_built_decor_things(const rdoom_built *built, const uint32_t **out, uint32_t *out_n);
 
 /* Camera of the reference: view = inverse(T(eye) * Ry(yaw) * Rx(pitch)),
  * projection = perspective(65 deg, (w/h)*1.2, 0.01, 100) (game/src/player.rs:84-89, 325-345;
@@ -1730,6 +1735,33 @@ rdoom_status rdoom_worldset_sense_things(const rdoom_worldset *set, const rdoom_
                                          const rdoom_thing_sense *params, uint32_t *d_collected, uint32_t *d_visible_out,
                                          uint32_t *d_touched_out, uint32_t stride, rdoom_thing_nearest *d_nearest_out,
                                          uint32_t *d_new_out, void *stream);
+
+/* ---- hidden things: a collected thing leaves its player's frames ------------------------------------------------------------
+ * The reference draws every decoration of a level in every frame (game/src/level.rs:764-793 builds them once; nothing is ever
+ * picked up).  Here a batch may take one row of thing bits per pose -- rdoom_world_sense_things' d_collected as it stands -- and
+ * the cull kernel drops the decor triangles of the things whose bit is set, for that pose only.  Every later stage reads only
+ * what survives the cull, so the frames, the depth, label and primitive planes and the observations all lose the thing, and the
+ * primitive ids of everything else stay what they are.
+ *
+ * rdoom_level_set_decor_things attaches, to level `slot` of the handle (0 for rdoom_level_create), the thing of every decor quad:
+ * thing_of_quad[q] for the quad of decor vertices 4q .. 4q + 3 of that level's descriptor, n_quads == n_decor_verts / 4
+ * (rdoom_built_decor_things' array for a built level).  An entry of RDOOM_NO_THING means "never hidden".  Several quads may name
+ * one thing.  Synchronous; called before any batch on the level renders with hidden rows; calling again replaces the slot's table.
+ * This is the one change a rdoom_level admits after create.  The handle keeps 4 bytes per triangle of the set on the device from
+ * the first call on.  Errors (RDOOM_BAD_ARG): a NULL level, or a NULL thing_of_quad with n_quads > 0; a slot outside the set;
+ * n_quads != n_decor_verts / 4; a decor triangle of the slot whose three indices do not lie in one quad. */
+#define RDOOM_NO_THING 0xFFFFFFFFu
+rdoom_status rdoom_level_set_decor_things(rdoom_level *level, uint32_t slot, const uint32_t *thing_of_quad, uint32_t n_quads);
+/* Rows for every following render of the batch, by any of rdoom_batch_render, _timed, _profiled, _objects, _levels, _players and
+ * _players_clocked: d_hidden is a borrowed device pointer, 4-byte aligned, to rows of `stride` uint32 words, laid out as
+ * d_collected above; row p belongs to pose or player p.  A decor triangle of thing i of pose p's level is not drawn for pose p
+ * when bit i % 32 of word p * stride + i / 32 is set.  A triangle whose thing is RDOOM_NO_THING or >= 32 * stride is drawn, and a
+ * bit no decor quad of the pose's level maps to has no effect.  The rows are read on the render's stream when the render runs
+ * (words [0, stride) of rows [0, n_poses), never written): a sense call queued before the render on the same stream is seen
+ * without a host wait.  d_hidden == NULL switches it off (stride is ignored).  The call itself queues nothing.
+ * Errors (RDOOM_BAD_ARG): a NULL batch; with a non-NULL d_hidden: stride == 0, a pointer that is not 4-byte aligned, or a level of
+ * the batch's handle that has decor triangles and no attached table. */
+rdoom_status rdoom_batch_set_hidden_things(rdoom_batch *batch, const uint32_t *d_hidden, uint32_t stride);
 
 #ifdef __cplusplus
 }

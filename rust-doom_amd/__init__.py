@@ -204,7 +204,8 @@ API_SYMBOLS = [
     'rdoom_worldset_area_frontiers', 'rdoom_wall_distance', 'rdoom_selftest_sincos', 'rdoom_flood_grids_octile',
     'rdoom_flood_descend_octile', 'rdoom_grid_walk_lines', 'rdoom_path_straighten',
     'rdoom_world_map_things', 'rdoom_worldset_level_map_things', 'rdoom_thingset_create', 'rdoom_thingset_destroy', 'rdoom_thingset_info',
-    'rdoom_world_sense_things', 'rdoom_worldset_sense_things']
+    'rdoom_world_sense_things', 'rdoom_worldset_sense_things',
+    'rdoom_built_decor_things', 'rdoom_level_set_decor_things', 'rdoom_batch_set_hidden_things']
 
 _lib = None
 
@@ -580,9 +581,27 @@ class BuiltLevel:
         _check(lib().rdoom_built_floor_centroids(self._h, ctypes.byref(p), ctypes.byref(n)))
         return self._view(p.value, n.value * 3, np.float32).reshape(-1, 3)
 
+    def decor_things(self):
+        """rdoom_built_decor_things: per decor quad q (decor vertices 4q .. 4q + 3), the index of its thing in the level's thing
+        table (World.map_things of the same level); uint32, strictly increasing"""
+        p = ctypes.c_void_p()
+        n = ctypes.c_uint32()
+        _check(lib().rdoom_built_decor_things(self._h, ctypes.byref(p), ctypes.byref(n)))
+        return self._view(p.value, n.value, np.uint32)
+
+
+NO_THING = 0xFFFFFFFF  # RDOOM_NO_THING: a decor quad that no row of hidden things hides
+
+
+def _set_decor_things(level, slot, table):
+    table = np.ascontiguousarray(table, np.uint32).reshape(-1)
+    _check(lib().rdoom_level_set_decor_things(level._h, int(slot), _ptr(table), len(table)))
+
 
 class DeviceLevel:
-    """Level arrays resident in HBM (replaces the GL vertex/index buffers and textures)."""
+    """Level arrays resident in HBM (replaces the GL vertex/index buffers and textures).  A BuiltLevel's decor_things() are
+    attached at once, so that a Batch on it can hide things per pose (Batch.set_hidden_things); any other source attaches its
+    own table with set_decor_things."""
 
     def __init__(self, source):
         if isinstance(source, BuiltLevel):
@@ -593,6 +612,13 @@ class DeviceLevel:
             desc, self._keep = make_desc(source)
         self._h = ctypes.c_void_p()
         _check(lib().rdoom_level_create(ctypes.byref(desc), ctypes.byref(self._h)))
+        if isinstance(source, BuiltLevel):
+            self.set_decor_things(source.decor_things())
+
+    def set_decor_things(self, table):
+        """rdoom_level_set_decor_things: table[q] is the thing-table index of decor quad q (decor vertices 4q .. 4q + 3), or
+        NO_THING for a quad that is never hidden; one entry per quad.  Synchronous; replaces an earlier table."""
+        _set_decor_things(self, 0, table)
 
     def num_objects(self):
         n = ctypes.c_uint32()
@@ -614,6 +640,7 @@ class DeviceLevelSet(DeviceLevel):
 
     def __init__(self, sources):
         descs, self._keep = [], []
+        sources = list(sources)
         for source in sources:
             if isinstance(source, BuiltLevel):
                 desc, keep = source.desc, source
@@ -626,6 +653,13 @@ class DeviceLevelSet(DeviceLevel):
         arr = (ctypes.POINTER(LevelDesc) * len(descs))(*[ctypes.pointer(d) for d in descs])
         self._h = ctypes.c_void_p()
         _check(lib().rdoom_levelset_create(arr, len(descs), ctypes.byref(self._h)))
+        for slot, source in enumerate(sources):
+            if isinstance(source, BuiltLevel):
+                self.set_decor_things(slot, source.decor_things())
+
+    def set_decor_things(self, slot, table):
+        """rdoom_level_set_decor_things for level `slot` of the set (DeviceLevel.set_decor_things has the table)"""
+        _set_decor_things(self, slot, table)
 
     def num_levels(self):
         n = ctypes.c_uint32()
@@ -687,6 +721,7 @@ class Batch:
         self._h = ctypes.c_void_p()
         _check(lib().rdoom_batch_create(level._h, self.width, self.height, self.max_poses, ctypes.byref(self._h)))
         self.last_n = 0
+        self._hidden = None
 
     def close(self):
         if self._h:
@@ -722,7 +757,7 @@ class Batch:
     def render_profiled(self, poses, lights, kinds=ALL_KINDS, stream=None, level_of_pose=None):
         """rdoom_batch_render_profiled: asynchronous, the per-kernel events stay pending (at most 64 renders)"""
         poses, lights, stride = self._prep(poses, lights)
-        self.last_n = len(poses)
+        self.last_n = self._rows_for(len(poses))
         if level_of_pose is not None:
             return self._render_levels(poses, lights, stride, kinds, stream, level_of_pose, None, True)
         _check(lib().rdoom_batch_render_profiled(self._h, poses.ctypes.data_as(ctypes.c_void_p), lights.ctypes.data_as(ctypes.c_void_p),
@@ -741,7 +776,7 @@ class Batch:
         object_modelviews: optional (n_poses, n_objects, 16) u_modelview per object -> rdoom_batch_render_objects.
         level_of_pose: (n_poses,) level index of every pose, for a batch on a DeviceLevelSet -> rdoom_batch_render_levels."""
         poses, lights, stride = self._prep(poses, lights)
-        self.last_n = len(poses)
+        self.last_n = self._rows_for(len(poses))
         if level_of_pose is not None:
             assert not timed, 'timed renders of a level set: use render_profiled + collect_timings'
             return self._render_levels(poses, lights, stride, kinds, stream, level_of_pose, object_modelviews, False)
@@ -813,7 +848,7 @@ class Batch:
                 raise ValueError('levels must hold one 32-bit slot per player (%d)' % n)
         po, pm = _out_tensor(poses_out, n * POSE.itemsize, 'poses_out'), _out_tensor(modelviews_out, n * n_obj * 64, 'modelviews_out')
         pv, po_ = dev(levels, 'levels'), dev(offsets, 'offsets')
-        self.last_n = n
+        self.last_n = self._rows_for(n)
         if times is None:
             _check(lib().rdoom_batch_render_players(self._h, ctypes.c_void_p(ps), ctypes.c_void_p(pv), ctypes.c_void_p(po_), n_obj,
                                                     ctypes.c_void_p(pl), stride, ctypes.c_float(time), n, int(kinds),
@@ -827,6 +862,40 @@ class Batch:
         if any(uploaded for _, uploaded in keep):
             import torch
             torch.cuda.synchronize()
+
+    def _rows_for(self, n):
+        """n, once the tensor given to set_hidden_things is known to hold a row for each of a render's n poses"""
+        rows = self._hidden
+        if rows is not None and not isinstance(rows, (int, np.integer)) and int(rows.shape[0]) < n:
+            raise ValueError('the hidden-things tensor has %d rows, the render %d poses' % (int(rows.shape[0]), n))
+        return n
+
+    def set_hidden_things(self, rows, stride=None):
+        """rdoom_batch_set_hidden_things: every following render of this batch leaves out, for pose or player p, the decor
+        triangles of the things whose bit is set in row p of `rows` -- sense_things' `collected` tensor as it stands: a 32-bit
+        integer (n, words) GPU tensor, read on the render's stream when the render runs, so a sense_things queued before the
+        render on that stream is seen without a wait.  Or a raw device pointer (an int) with `stride`, the words of a row.  The
+        batch keeps a reference to the tensor.  None switches it off.  The level needs its decor things attached
+        (DeviceLevel.set_decor_things; a BuiltLevel's are)."""
+        if rows is None:
+            _check(lib().rdoom_batch_set_hidden_things(self._h, None, 0))
+            self._hidden = None
+            return
+        if isinstance(rows, (int, np.integer)):
+            if stride is None:
+                raise ValueError('stride is needed with a raw pointer')
+            ptr = int(rows)
+        else:
+            if rows.device.type != 'cuda' or not rows.is_contiguous() or rows.element_size() != 4 or rows.dtype.is_floating_point \
+                    or rows.dim() != 2:
+                raise ValueError('rows must be a contiguous 32-bit integer (n, words) tensor on the GPU')
+            if stride is None:
+                stride = int(rows.shape[1])
+            elif int(stride) != int(rows.shape[1]):
+                raise ValueError('stride %d, but the rows are %d words long' % (int(stride), int(rows.shape[1])))
+            ptr = rows.data_ptr()
+        _check(lib().rdoom_batch_set_hidden_things(self._h, ctypes.c_void_p(ptr), int(stride)))
+        self._hidden = rows
 
     def finish(self):
         """rdoom_batch_finish: wait for the last render and raise if the device found a problem"""

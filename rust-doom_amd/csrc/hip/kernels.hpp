@@ -23,7 +23,10 @@ constexpr uint32_t LONG_LIST = 64, TILE_SPLIT = 0x80000000u;
 rdoom_status launch_setup(hipStream_t st, uint32_t n_poses, const DeviceLevelView &lv, const PoseConst *poses,
                           const ObjectConst *objects, uint32_t n_objects, int width, int height, uint32_t kinds_mask,
                           TriRec *recs, uint32_t *visible, uint32_t *counts, uint32_t *ghist, uint32_t cap,
-                          uint32_t *mismatch_flag);  // set when the set-up kernel rejects a triangle the cull kernel kept
+                          uint32_t *mismatch_flag,  // set when the set-up kernel rejects a triangle the cull kernel kept
+                          // rows of thing bits, hidden_stride words per pose, or null (rdoom_batch_set_hidden_things): the cull
+                          // kernel drops the decor triangles of the things set in a pose's row (lv.tri_thing names them)
+                          const uint32_t *hidden, uint32_t hidden_stride);
 size_t setup_histogram_bytes(uint32_t max_poses);  // scratch of the counting sort (per pose: one counter per depth bucket)
 // Kernel 1b: per-tile triangle lists (bin.hip).  *launched = false: the frame has too many tiles for the kernel's LDS counters --
 // nothing was launched and the caller must flag every pose as "bins incomplete".  A launch that FAILS is an error.

@@ -142,6 +142,10 @@ struct DeviceLevelView {
   uint32_t n_slices;
   uint32_t max_clusters;     // the largest slice's cluster / triangle count: grid sizes and per-pose record strides
   uint32_t max_ntri;
+  // per triangle of `tris`: the thing (index in its level's thing table) a decor triangle belongs to, NONE for every other triangle
+  // and for a decor quad that is never hidden.  Null until rdoom_level_set_decor_things is first called; read by the cull kernel
+  // only, and only in a render with hidden rows.
+  const uint32_t *tri_thing;
 };
 
 __device__ __forceinline__ float plane3(const float *p, float px, float py) {

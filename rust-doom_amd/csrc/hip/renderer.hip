@@ -37,6 +37,14 @@ struct rdoom_level {
   // as an argument of their own, so no struct another kernel takes by value carries it)
   uint32_t *d_palettes = nullptr;
   std::vector<uint8_t> has_palette;  // the level's desc had a playpal (else its poses cannot be resolved to RGB)
+  // Hidden things (rdoom_level_set_decor_things): per level, its descriptor's decor vertex count and, per triangle, the decor
+  // quad its three indices lie in (idx / 4) -- NONE for a triangle of another kind, QUAD_SPANS for a decor triangle whose indices
+  // lie in two quads.  d_tri_thing: one word per triangle of the set (view.tri_thing), allocated by the first attach.
+  static constexpr uint32_t QUAD_SPANS = 0xFFFFFFFEu;
+  std::vector<uint32_t> n_decor_verts;
+  std::vector<std::vector<uint32_t>> tri_quad;
+  std::vector<uint8_t> has_decor, things_attached;
+  uint32_t *d_tri_thing = nullptr;
 };
 
 struct rdoom_batch {
@@ -99,6 +107,9 @@ struct rdoom_batch {
   size_t rgb_bytes = 0;
   // the last render was rdoom_batch_render_players: its levels are on the device only (the pinned staging is an older render's)
   bool last_levels_on_device = false;
+  // rdoom_batch_set_hidden_things: the caller's rows of thing bits (borrowed), read by the cull kernel of every render; null: none
+  const uint32_t *d_hidden = nullptr;
+  uint32_t hidden_stride = 0;
 };
 
 // Every entry point that touches a batch's memory or waits for its work first makes the level's device current: a host
@@ -152,7 +163,8 @@ rdoom_status rdoom_set_device(int32_t device) {
 
 void rdoom_level_destroy(rdoom_level *level) {
   if (!level) return;
-  for (void *p : {level->d_clusters, level->d_tris, level->d_texels, level->d_sky, level->d_cmap, level->d_slices, (void *)level->d_palettes})
+  for (void *p : {level->d_clusters, level->d_tris, level->d_texels, level->d_sky, level->d_cmap, level->d_slices, (void *)level->d_palettes,
+                  (void *)level->d_tri_thing})
     if (p) (void)hipFree(p);
   delete level;
 }
@@ -167,6 +179,8 @@ struct HostLevel {
   std::vector<uint16_t> sky;
   LevelSlice dims{};                 // the atlas / sky sizes (bases and ranges are filled in when the set is assembled)
   uint32_t n_objects = 1;
+  std::vector<uint32_t> tri_quad;    // per triangle: rdoom_level::tri_quad's entry
+  uint32_t n_decor_verts = 0;
 };
 }  // namespace
 
@@ -246,6 +260,7 @@ static rdoom_status flatten_level(const rdoom_level_desc *d, HostLevel &out) {
       LevelTri lt;
       std::memset(&lt, 0, sizeof lt);
       lt.packed = 1u | (dr.kind << 16);
+      uint32_t quad = NONE;  // of a decor triangle: the quad its indices lie in
       if (dr.kind == RDOOM_KIND_FLAT || dr.kind == RDOOM_KIND_WALL) {
         if ((uint64_t)dr.first_index + dr.index_count > d->n_static_indices)
           return rdoom::fail(RDOOM_BAD_ARG, "draw %u: static index range out of bounds", di);
@@ -291,6 +306,7 @@ static rdoom_status flatten_level(const rdoom_level_desc *d, HostLevel &out) {
         for (int i = 0; i < 3; i++) {
           const uint32_t idx = d->decor_indices[dr.first_index + 3 * t + i];
           if (idx >= d->n_decor_verts) return rdoom::fail(RDOOM_BAD_ARG, "draw %u: decor vertex out of bounds", di);
+          quad = i == 0 || quad == idx / 4u ? idx / 4u : rdoom_level::QUAD_SPANS;
           vv[i] = &d->decor_verts[idx];
           std::memcpy(&lt.pos[3 * i], vv[i]->a_pos, 12);
           lt.uv[2 * i] = vv[i]->a_tile_uv[0];
@@ -310,10 +326,12 @@ static rdoom_status flatten_level(const rdoom_level_desc *d, HostLevel &out) {
       }
       lt.packed |= dr.object_id << 20;
       tris.push_back(lt);
+      out.tri_quad.push_back(quad);
     }
   }
   if (tris.size() >= (1u << 24)) return rdoom::fail(RDOOM_BAD_LEVEL, "too many triangles (%zu)", tris.size());
   out.n_objects = n_objects;
+  out.n_decor_verts = d->n_decor_verts;
   // clusters for the set-up kernel's coarse cull: runs of at most CLUSTER_TRIS consecutive triangles of one object
   std::vector<Cluster> &clusters = out.clusters;
   for (size_t t = 0; t < tris.size();) {
@@ -394,6 +412,10 @@ static rdoom_status levelset_create_impl(const rdoom_level_desc *const *descs, u
     lv->ntri = std::max(lv->ntri, sl.ntri);
     lv->n_objects = std::max(lv->n_objects, h.n_objects);
     max_clusters = std::max(max_clusters, sl.n_clusters);
+    lv->n_decor_verts.push_back(h.n_decor_verts);
+    lv->has_decor.push_back(std::any_of(h.tri_quad.begin(), h.tri_quad.end(), [](uint32_t q) { return q != NONE; }) ? 1 : 0);
+    lv->things_attached.push_back(0);
+    lv->tri_quad.push_back(std::move(h.tri_quad));
     h = HostLevel{};  // (released: a set of many levels would otherwise hold every atlas twice)
   }
   // a record addresses the store with (base >> 10) in 16 bits (ShadeRec::flags), a cluster index fits 32 bits
@@ -602,7 +624,7 @@ static rdoom_status queue_pipeline(rdoom_batch *b, uint32_t n, uint32_t kinds_ma
   if (lv->ntri)
     if (rdoom_status rs = launch_setup(st, n, lv->view, b->d_poses, objects ? (const ObjectConst *)b->d_objects : nullptr,
                                        lv->n_objects, W, H, kinds_mask, b->d_recs, b->d_visible, b->d_counts,
-                                       b->d_ghist, b->cap, b->d_fix_count + 2))
+                                       b->d_ghist, b->cap, b->d_fix_count + 2, b->d_hidden, b->hidden_stride))
       return rs;
   const int tiles_x = (W + TILE_W - 1) / TILE_W, tiles_y = (H + TILE_H - 1) / TILE_H;
   bool split_lists = false;  // long tile lists stored per quadrant this render (binning kernel and rasteriser must agree)
@@ -885,6 +907,65 @@ rdoom_status rdoom_level_num_levels(const rdoom_level *level, uint32_t *out) {
 rdoom_status rdoom_level_num_objects(const rdoom_level *level, uint32_t *out) {
   if (!level || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   *out = level->n_objects;
+  return RDOOM_OK;
+}
+
+static rdoom_status set_decor_things_impl(rdoom_level *lv, uint32_t slot, const uint32_t *thing_of_quad, uint32_t n_quads) {
+  if (!lv || (!thing_of_quad && n_quads)) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (slot >= lv->view.n_slices) return rdoom::fail(RDOOM_BAD_ARG, "slot %u of a set of %u levels", slot, lv->view.n_slices);
+  if (n_quads != lv->n_decor_verts[slot] / 4u)
+    return rdoom::fail(RDOOM_BAD_ARG, "n_quads %u, but level %u has %u decor vertices: %u quads", n_quads, slot, lv->n_decor_verts[slot],
+                       lv->n_decor_verts[slot] / 4u);
+  const std::vector<uint32_t> &tri_quad = lv->tri_quad[slot];
+  std::vector<uint32_t> table(tri_quad.size(), NONE);
+  for (size_t t = 0; t < tri_quad.size(); t++) {
+    const uint32_t q = tri_quad[t];
+    if (q == NONE) continue;
+    // (a vertex count that is no multiple of 4 leaves a last, partial quad the table has no entry for)
+    if (q == rdoom_level::QUAD_SPANS || q >= n_quads)
+      return rdoom::fail(RDOOM_BAD_ARG, "level %u: the indices of decor triangle %zu do not lie in one quad of four vertices", slot, t);
+    table[t] = thing_of_quad[q];
+  }
+  const size_t total = (size_t)lv->slices.back().first_tri + lv->slices.back().ntri;  // triangles of the set
+  HIP_TRY(hipSetDevice(lv->device));
+  if (!lv->d_tri_thing && total) {
+    uint32_t *p = nullptr;
+    HIP_TRY(hipMalloc((void **)&p, sizeof(uint32_t) * total));
+    const hipError_t e = hipMemset(p, 0xFF, sizeof(uint32_t) * total);  // levels without a table: nothing is ever hidden
+    if (e != hipSuccess) {
+      (void)hipFree(p);
+      HIP_TRY(e);
+    }
+    lv->d_tri_thing = p;
+    lv->view.tri_thing = p;
+  }
+  if (!table.empty())
+    HIP_TRY(hipMemcpy(lv->d_tri_thing + lv->slices[slot].first_tri, table.data(), sizeof(uint32_t) * table.size(), hipMemcpyHostToDevice));
+  lv->things_attached[slot] = 1;
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_level_set_decor_things(rdoom_level *level, uint32_t slot, const uint32_t *thing_of_quad, uint32_t n_quads) {
+  try {
+    return set_decor_things_impl(level, slot, thing_of_quad, n_quads);
+  } catch (const std::bad_alloc &) {
+    return rdoom::fail(RDOOM_OOM, "out of host memory");
+  }
+}
+
+rdoom_status rdoom_batch_set_hidden_things(rdoom_batch *b, const uint32_t *d_hidden, uint32_t stride) {
+  if (!b) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (!d_hidden) {
+    b->d_hidden = nullptr, b->hidden_stride = 0;
+    return RDOOM_OK;
+  }
+  if (stride == 0) return rdoom::fail(RDOOM_BAD_ARG, "stride is 0");
+  if ((uintptr_t)d_hidden % 4u) return rdoom::fail(RDOOM_BAD_ARG, "d_hidden is not 4-byte aligned");
+  const rdoom_level *lv = b->level;
+  for (uint32_t k = 0; k < lv->view.n_slices; k++)
+    if (lv->has_decor[k] && !lv->things_attached[k])
+      return rdoom::fail(RDOOM_BAD_ARG, "level %u has decor triangles but no thing table (rdoom_level_set_decor_things)", k);
+  b->d_hidden = d_hidden, b->hidden_stride = stride;
   return RDOOM_OK;
 }
 

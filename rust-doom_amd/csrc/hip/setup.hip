@@ -24,7 +24,8 @@ namespace {
 //   cull_kernel       a few workgroups per pose, each with a share of the level's clusters (runs of <= 32 triangles with a
 //                     bounding box): coarse cull of whole clusters, then the cheap half of the set-up (transform, S1, S4,
 //                     S6) for four triangles per thread; the visible triangles are listed and their log-depth buckets
-//                     (exponent + top mantissa bits of the nearest vertex's w) counted;
+//                     (exponent + top mantissa bits of the nearest vertex's w) counted; with hidden rows, the decor triangles
+//                     of the things hidden from the pose are dropped here, so no later stage ever sees them;
 //   sort_scan_kernel  exclusive scan of each pose's bucket histogram;
 //   setup_kernel      one lane per VISIBLE triangle does the full set-up -- all lanes busy, where a single pass would run
 //                     the whole set-up for every wave that holds one visible triangle -- and stores the record at its
@@ -237,11 +238,16 @@ __device__ __forceinline__ uint32_t depth_bucket(float wmin) {
 // No register budget for the set-up kernels: the set-up kernel held to 96 / 80 VGPRs spills 2 / 29 registers and is slower
 // (profiles/r04_ab.txt, item 10)
 constexpr int CULL_OCC = 1, SETUP_OCC = 1;
+// HIDDEN (rdoom_batch_set_hidden_things): the pose has a row of `hidden_stride` words of thing bits at `hidden`,
+// and a decor triangle whose thing (lv.tri_thing) has its bit set there is skipped before its set-up.  Without rows the
+// instantiation is the kernel as it was: the two arguments are not read.
+template <bool HIDDEN>
 __global__ __launch_bounds__(256, CULL_OCC) void cull_kernel(DeviceLevelView lv, const PoseConst *__restrict__ poses,
                                                    const ObjectConst *__restrict__ objects, uint32_t n_objects,
                                                    int width, int height, uint32_t kinds_mask,
                                                    uint32_t *__restrict__ visible, uint32_t *__restrict__ counts,
-                                                   uint32_t *__restrict__ ghist, uint32_t cap, uint32_t groups) {
+                                                   uint32_t *__restrict__ ghist, uint32_t cap, uint32_t groups,
+                                                   const uint32_t *__restrict__ hidden, uint32_t hidden_stride) {
   __shared__ uint32_t hist[SORT_BUCKETS];   // this workgroup's share of the pose's depth-bucket histogram
   __shared__ uint16_t clist[CLUSTER_LIST];  // my clusters that survived the coarse cull, ascending
   __shared__ uint32_t wsum[4];
@@ -325,10 +331,18 @@ __global__ __launch_bounds__(256, CULL_OCC) void cull_kernel(DeviceLevelView lv,
         uint4 *dst = reinterpret_cast<uint4 *>(&tri);
 #pragma unroll
         for (uint32_t k = 0; k < 6u; k++) dst[k] = stage[half * 192u + in * 6u + k];
+        bool shown = true;
+        if (HIDDEN && ((tri.packed >> 16) & 3u) == RDOOM_KIND_DECOR) {
+          // tri_of[j] lies in the pose's slice (in < count of one of its clusters): inside the table, one word per triangle of the
+          // set; pose < n_poses rows; word < hidden_stride
+          const uint32_t thing = lv.tri_thing[tri_of[j]], word = thing >> 5;
+          if (thing != NONE && word < hidden_stride)
+            shown = ((hidden[(size_t)pose * hidden_stride + word] >> (thing & 31u)) & 1u) == 0u;
+        }
         RasterRec rr;
         ShadeRec sr;
-        float wkey;
-        if (setup_triangle(ls, pc, objs, tri_of[j], tri, width, height, kinds_mask, rr, sr, wkey)) vis4 |= 1u << j;
+        float wkey = 0.0f;
+        if (shown && setup_triangle(ls, pc, objs, tri_of[j], tri, width, height, kinds_mask, rr, sr, wkey)) vis4 |= 1u << j;
         bucket_of[j] = depth_bucket(wkey);
       }
     }
@@ -498,14 +512,19 @@ __global__ __launch_bounds__(256, SETUP_OCC) void setup_kernel(DeviceLevelView l
 rdoom_status launch_setup(hipStream_t st, uint32_t n_poses, const DeviceLevelView &lv, const PoseConst *poses,
                           const ObjectConst *objects, uint32_t n_objects, int width, int height, uint32_t kinds_mask,
                           TriRec *recs, uint32_t *visible, uint32_t *counts, uint32_t *ghist, uint32_t cap,
-                          uint32_t *mismatch_flag) {
+                          uint32_t *mismatch_flag, const uint32_t *hidden, uint32_t hidden_stride) {
   // (counts and ghist arrive zeroed: the caller clears them together with its other per-render words in one fill)
   // several workgroups per pose on large levels (each takes a share of the clusters): one would walk them serially
   // (of a set of levels: by the largest; a smaller level's workgroups take shorter shares)
   const uint32_t groups = std::min<uint32_t>(std::max<uint32_t>(lv.max_clusters / 96u, 1u), 16u);
   (void)hipGetLastError();  // (a stale error of an earlier, unrelated call must not be blamed on these launches)
-  hipLaunchKernelGGL(cull_kernel, dim3(n_poses * groups), dim3(256), 0, st, lv, poses, objects, n_objects, width, height,
-                     kinds_mask, visible, counts, ghist, cap, groups);
+  // (rows without a table: no level of the handle has a decor triangle, rdoom_batch_set_hidden_things checked -- nothing to hide)
+  if (hidden && lv.tri_thing)
+    hipLaunchKernelGGL(cull_kernel<true>, dim3(n_poses * groups), dim3(256), 0, st, lv, poses, objects, n_objects, width, height,
+                       kinds_mask, visible, counts, ghist, cap, groups, hidden, hidden_stride);
+  else
+    hipLaunchKernelGGL(cull_kernel<false>, dim3(n_poses * groups), dim3(256), 0, st, lv, poses, objects, n_objects, width, height,
+                       kinds_mask, visible, counts, ghist, cap, groups, (const uint32_t *)nullptr, 0u);
   hipLaunchKernelGGL(sort_scan_kernel, dim3(n_poses), dim3(256), 0, st, ghist);
   const uint32_t place_groups = std::min<uint32_t>((cap + 1023u) / 1024u, 16u);  // about a fifth of a level is visible: one or two chunks of 256 records each
   hipLaunchKernelGGL(setup_kernel, dim3(n_poses * place_groups), dim3(256), 0, st, lv, poses, objects, n_objects, width, height,

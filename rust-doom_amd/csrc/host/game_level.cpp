@@ -170,6 +170,7 @@ void Builder::visit_decor(const Decor &d) {  // level.rs:764-793
   vertex(d.high, d.half_width, b->size[0], 0.0f);
   vertex(d.high, -d.half_width, 0.0f, 0.0f);
   any_quad(decor_vertices.size(), object_indices[d.object_id.v].decor);
+  decor_things.push_back(d.thing_index);  // quad q = vertices 4q .. 4q + 3
 }
 
 // ---- level assembly -------------------------------------------------------------------------------------
@@ -277,6 +278,7 @@ std::unique_ptr<BuiltLevel> build_level(const LoadedWad &w, size_t level_index, 
   out->static_vertices = std::move(builder.static_vertices);
   out->sky_vertices = std::move(builder.sky_vertices);
   out->decor_vertices = std::move(builder.decor_vertices);
+  out->decor_things = std::move(builder.decor_things);
   // draw order: per object id ascending: flats, walls, decor, sky (game/src/level.rs:443-496)
   for (auto &kv : builder.object_indices) {
     const Indices &ind = kv.second;

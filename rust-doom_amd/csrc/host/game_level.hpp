@@ -49,6 +49,7 @@ class Builder : public wad::LevelVisitor {  // game/src/level.rs:307-327, 648-79
   std::vector<rdoom_static_vertex> static_vertices;
   std::vector<float> sky_vertices;  // xyz triples
   std::vector<rdoom_sprite_vertex> decor_vertices;
+  std::vector<uint32_t> decor_things;  // per emitted decor quad (vertices 4q .. 4q + 3): wad::Decor::thing_index
   std::map<uint32_t, Indices> object_indices;  // VecMap<Indices>: ascending object id
   rdoom_counters counters{};
   rdoom_host_timings timings{};  // level_lumps_ms, atlases_ms, analysis_ms, walk_ms of this build
@@ -72,6 +73,7 @@ struct BuiltLevel {
   std::vector<uint32_t> sky_indices;
   std::vector<rdoom_sprite_vertex> decor_vertices;
   std::vector<uint32_t> decor_indices;
+  std::vector<uint32_t> decor_things;  // decor_vertices.size() / 4 entries: the thing-table index of every decor quad
   std::vector<rdoom_draw> draws;
   wad::OpaqueImage flat_atlas;
   wad::TransparentImage wall_atlas, decor_atlas, sky_texture;

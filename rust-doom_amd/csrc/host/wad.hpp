@@ -368,6 +368,9 @@ struct Decor {  // visitor.rs:56-63
   float half_width;
   const LightInfo *light_info;
   WadName tex_name;
+  // (not the reference's) the ordinal of this thing among the THINGS entries LevelWalker::things sends down its decor branch: its
+  // index in the level's thing table (include/rdoom.h "things"), counted whether or not a table is recorded
+  uint32_t thing_index = 0;
 };
 enum class Branch { Positive, Negative };
 enum class MarkerKind { StartPos, TeleportStart, TeleportEnd };
@@ -545,6 +548,7 @@ class LevelWalker {  // visitor.rs:499-1138
   std::vector<Pnt2f> subsector_points_;
   std::vector<Line2f> subsector_seg_lines_;
   std::map<uint16_t, LightInfo> light_cache_;
+  uint32_t decor_things_ = 0;  // entries things() has sent down its decor branch so far: Decor::thing_index of the next one
 
   SectorInfo sector_info(const WadSector *s) const;
   const LightInfo *light_info(const WadSector *s);

@@ -286,6 +286,13 @@ rdoom_status rdoom_built_desc(const rdoom_built *built, rdoom_level_desc *d) {
   return RDOOM_OK;
 }
 
+rdoom_status rdoom_built_decor_things(const rdoom_built *built, const uint32_t **out, uint32_t *out_n) {
+  if (!built || !out || !out_n) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  *out = built->b->decor_things.data();
+  *out_n = (uint32_t)built->b->decor_things.size();
+  return RDOOM_OK;
+}
+
 rdoom_status rdoom_built_counters(const rdoom_built *built, rdoom_counters *out) {
   if (!built || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   *out = built->b->counters;

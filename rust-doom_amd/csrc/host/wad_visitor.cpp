@@ -657,6 +657,7 @@ const WadSector *LevelWalker::sector_at(Pnt2f pos) const {  // visitor.rs:1028-1
 }
 
 void LevelWalker::things() {  // visitor.rs:1010-1026
+  decor_things_ = 0;
   for (const WadThing &thing : level_.things) {
     const Pnt2f pos = from_wad_coords(thing.x, thing.y);
     const float yaw_deg = std::round((float)thing.angle / 45.0f) * 45.0f;  // f32::round: half away from zero
@@ -683,6 +684,7 @@ void LevelWalker::things() {  // visitor.rs:1010-1026
 
 void LevelWalker::decor(const WadThing &thing, Pnt2f pos, const WadSector *sector) {  // visitor.rs:1062-1137
   const ThingMetadata *meta = meta_.find_thing(thing.thing_type);
+  const uint32_t thing_index = decor_things_++;  // == record_things->size() here, when a table is recorded
   if (record_things) {  // the thing table's record: an item is somewhere even when it cannot be drawn
     const DynamicSectorInfo *dyn = analysis_.dynamic(level_.sector_id(sector));
     const bool hanging = meta && meta->hanging;
@@ -726,6 +728,7 @@ void LevelWalker::decor(const WadThing &thing, Pnt2f pos, const WadSector *secto
   d.half_width = sx * 0.5f;
   d.light_info = light_info(sector);
   d.tex_name = name;
+  d.thing_index = thing_index;
   visitor_.visit_decor(d);
 }
 
