@@ -2,6 +2,8 @@
 #pragma once
 #include <cstdarg>
 #include <cstdio>
+#include <new>
+#include <stdexcept>
 #include <string>
 
 #include "rdoom.h"
@@ -42,5 +44,27 @@ inline rdoom_status fail(rdoom_status code, const char *fmt, ...) {
   va_end(ap);
   last_error_ref() = buf;
   return code;
+}
+
+namespace wad {
+struct WadError : std::runtime_error {
+  rdoom_status code;
+  WadError(rdoom_status c, const std::string &m) : std::runtime_error(m), code(c) {}
+};
+}  // namespace wad
+
+// The one place exceptions become a status: nothing unwinds across the C ABI.  Every entry point that builds a std container or
+// calls the loader runs its body, a callable that returns the status, through this.
+template <class F>
+rdoom_status guarded(F &&f) {
+  try {
+    return f();
+  } catch (const wad::WadError &e) {
+    return fail(e.code, "%s", e.what());
+  } catch (const std::bad_alloc &) {
+    return fail(RDOOM_OOM, "out of host memory");
+  } catch (const std::exception &e) {
+    return fail(RDOOM_BAD_LEVEL, "%s", e.what());
+  }
 }
 }  // namespace rdoom

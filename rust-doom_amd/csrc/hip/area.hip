@@ -319,7 +319,7 @@ rdoom_status reveal_args(const rdoom::MapSource &src, const char *noun, const rd
   if (rdoom_status s = rdoom::check_offsets(d_offsets, n_objects, src.game_objects, noun)) return s;
   if (n > 0x7FFFFFFFu) return rdoom::fail(RDOOM_BAD_ARG, "%u players: too many for one launch", n);
   const rdoom::MapDevice &d = *src.map;
-  a = AreaArgs{d_states, d_offsets, d_dirs, d_area, d_new_out, {d.seg, d.heights, d.ids, d.flags}, n_objects, n_rays, stride, n_steps,
+  a = AreaArgs{d_states, d_offsets, d_dirs, d_area, d_new_out, {d.seg.get(), d.heights.get(), d.ids.get(), d.flags.get()}, n_objects, n_rays, stride, n_steps,
                max_range, cell};
   return RDOOM_OK;
 }
@@ -395,8 +395,8 @@ rdoom_status rdoom_worldset_reveal_area(const rdoom_worldset *set, const rdoom_p
     return s;
   if (rdoom_status s = rdoom::check_device(&src, "the world set")) return s;
   if (!n) return RDOOM_OK;
-  return rdoom::launch_checked(worldset_reveal_area_kernel, dim3(n), dim3(THREADS), 0, stream, a, (const uint2 *)src.map->levels,
-                               (const float4 *)src.map->bounds, d_levels, src.map->n_levels);
+  return rdoom::launch_checked(worldset_reveal_area_kernel, dim3(n), dim3(THREADS), 0, stream, a, (const uint2 *)src.map->levels.get(),
+                               (const float4 *)src.map->bounds.get(), d_levels, src.map->n_levels);
 }
 
 rdoom_status rdoom_world_draw_area_maps(const rdoom_world *w, const rdoom_player_state *d_states, uint32_t n, const rdoom_map_view *view,
@@ -420,7 +420,7 @@ rdoom_status rdoom_worldset_draw_area_maps(const rdoom_worldset *set, const rdoo
   if (rdoom_status s = map_args(src, "world set", d_states, n, view, d_area, stride, cell, d_out, a)) return s;
   if (rdoom_status s = rdoom::check_device(&src, "the world set")) return s;
   if (!n) return RDOOM_OK;
-  return rdoom::launch_checked(worldset_draw_area_maps_kernel, dim3(n * a.blocks), dim3(THREADS), 0, stream, a, (const float4 *)src.map->bounds,
+  return rdoom::launch_checked(worldset_draw_area_maps_kernel, dim3(n * a.blocks), dim3(THREADS), 0, stream, a, (const float4 *)src.map->bounds.get(),
                                d_levels, src.map->n_levels);
 }
 

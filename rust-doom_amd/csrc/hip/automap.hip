@@ -201,7 +201,7 @@ rdoom_status map_args(const rdoom::MapSource &src, const char *noun, const rdoom
     return rdoom::fail(RDOOM_BAD_ARG, "%u maps of %u x %u tiles: too many for one launch", n, tiles_x, tiles_y);
   const float rad = view->half_width * view->scale;
   const rdoom::MapDevice &d = *src.map;
-  a = MapArgs{d_states, d_offsets, d_out, d_seen, stride, d.seg, d.heights, d.ids, d.flags, n_objects, view->width, view->height, tiles_x,
+  a = MapArgs{d_states, d_offsets, d_out, d_seen, stride, d.seg.get(), d.heights.get(), d.ids.get(), d.flags.get(), n_objects, view->width, view->height, tiles_x,
               tiles_x * tiles_y, view->scale, rad, rad * rad, view->marker, view->flags};
   return RDOOM_OK;
 }
@@ -220,21 +220,16 @@ rdoom_status map_upload(const std::vector<rdoom_map_line> &lines, const std::vec
     ids.push_back(make_uint4(l.front.floor_id, l.front.ceiling_id, l.back.floor_id, l.back.ceiling_id));
     flags.push_back((l.flags & 0xFFFFu) | (l.front.present ? SIDE_FRONT : 0u) | (l.back.present ? SIDE_BACK : 0u));
   }
-  if (rdoom_status s = upload(&out.seg, seg)) return s;
-  if (rdoom_status s = upload(&out.heights, heights)) return s;
-  if (rdoom_status s = upload(&out.ids, ids)) return s;
-  if (rdoom_status s = upload(&out.flags, flags)) return s;
+  if (rdoom_status s = out.seg.upload(seg, EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = out.heights.upload(heights, EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = out.ids.upload(ids, EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = out.flags.upload(flags, EMPTY_TABLE_BYTES)) return s;
   std::vector<float4> bounds;
   for (const uint2 &r : levels) bounds.push_back(line_bounds(lines.data() + r.x, r.y));
-  if (rdoom_status s = upload(&out.levels, levels)) return s;
-  if (rdoom_status s = upload(&out.bounds, bounds)) return s;
+  if (rdoom_status s = out.levels.upload(levels, EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = out.bounds.upload(bounds, EMPTY_TABLE_BYTES)) return s;
   out.n_lines = (uint32_t)lines.size(), out.n_levels = (uint32_t)levels.size();
   return RDOOM_OK;
-}
-
-void map_free(MapDevice &d) {
-  free_all({d.seg, d.heights, d.ids, d.flags, d.levels, d.bounds});
-  d = MapDevice{};
 }
 
 }  // namespace rdoom
@@ -265,7 +260,7 @@ rdoom_status rdoom_worldset_draw_maps_seen(const rdoom_worldset *set, const rdoo
   if (rdoom_status s = map_args(src, "world set", d_states, n, d_object_offsets, n_objects, view, d_seen, stride, d_out, a)) return s;
   if (rdoom_status s = rdoom::check_device(&src, "the world set")) return s;
   if (!n) return RDOOM_OK;
-  return rdoom::launch_checked(worldset_draw_maps_kernel, dim3(n * a.tiles), dim3(THREADS), 0, stream, a, (const uint2 *)src.map->levels,
+  return rdoom::launch_checked(worldset_draw_maps_kernel, dim3(n * a.tiles), dim3(THREADS), 0, stream, a, (const uint2 *)src.map->levels.get(),
                                d_levels, src.map->n_levels);
 }
 

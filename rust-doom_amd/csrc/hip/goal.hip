@@ -128,7 +128,7 @@ rdoom_status plane_args(const rdoom::MapSource &src, const rdoom_world *w, const
     return rdoom::fail(RDOOM_BAD_ARG, "a stride of %u words is smaller than the %u a plane of the %s's grid takes at cell %g", stride, most.words,
                        noun, (double)cell);
   const rdoom::SectorDevice &d = *src.sectors;
-  a = AreaPlaneArgs{d_offsets, d_area, d_sector_out, d_floor_out, d_ceiling_out, d.nodes, d.edges, d.sectors, d.leaves, n_objects, stride,
+  a = AreaPlaneArgs{d_offsets, d_area, d_sector_out, d_floor_out, d_ceiling_out, d.nodes.get(), d.edges.get(), d.sectors.get(), d.leaves.get(), n_objects, stride,
                     width, height, blocks, cell};
   return RDOOM_OK;
 }
@@ -176,7 +176,7 @@ rdoom_status rdoom_worldset_draw_area_planes(const rdoom_worldset *set, const ui
   if (rdoom_status s = rdoom::check_device(&src, "the world set")) return s;
   if (!n) return RDOOM_OK;
   return rdoom::launch_checked(worldset_draw_area_planes_kernel, dim3(n * a.blocks), dim3(PLANE_THREADS), 0, stream, a,
-                               (const float4 *)src.map->bounds, (const uint4 *)src.sectors->levels, d_levels, src.n_levels);
+                               (const float4 *)src.map->bounds.get(), (const uint4 *)src.sectors->levels.get(), d_levels, src.n_levels);
 }
 
 rdoom_status rdoom_world_area_cells(const rdoom_world *w, const rdoom_player_state *d_states, uint32_t n, float cell, int32_t *d_cells_out,
@@ -200,7 +200,7 @@ rdoom_status rdoom_worldset_area_cells(const rdoom_worldset *set, const rdoom_pl
   if (rdoom_status s = rdoom::check_device(&src, "the world set")) return s;
   if (!n) return RDOOM_OK;
   return rdoom::launch_checked(worldset_area_cells_kernel, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), 0, stream, a,
-                               (const float4 *)src.map->bounds, d_levels, src.n_levels);
+                               (const float4 *)src.map->bounds.get(), d_levels, src.n_levels);
 }
 
 }  // extern "C"

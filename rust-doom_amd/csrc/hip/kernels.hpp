@@ -1,15 +1,8 @@
 // Launchers of the renderer's kernels, one translation unit per kernel (setup.hip, bin.hip, raster.hip,
 // fragment.hip); renderer.hip (the C ABI) strings them together on the caller's stream.
 #pragma once
+#include "device_memory.hpp"  // HIP_TRY
 #include "records.hpp"
-
-#define HIP_TRY(expr)                                                                                     \
-  do {                                                                                                    \
-    hipError_t _e = (expr);                                                                               \
-    if (_e != hipSuccess)                                                                                 \
-      return rdoom::fail(_e == hipErrorOutOfMemory ? RDOOM_OOM : RDOOM_HIP_ERROR, "%s failed: %s", #expr, \
-                         hipGetErrorString(_e));                                                          \
-  } while (0)
 
 namespace rdoom_dev {
 

@@ -14,6 +14,7 @@
 // loading.  Only Random entries pay the binary64 sine.
 #include <hip/hip_runtime.h>
 
+#include <memory>
 #include <vector>
 
 #include "kernels.hpp"
@@ -21,8 +22,9 @@
 #pragma clang fp contract(off)
 
 struct rdoom_lightset {
-  rdoom_dev::LightSetView view{};
-  void *d_infos = nullptr, *d_ranges = nullptr;
+  rdoom_dev::LightSetView view{};  // its pointers are views of the two arrays below
+  rdoom::DeviceArray<rdoom_light_info> d_infos;
+  rdoom::DeviceArray<uint2> d_ranges;
 };
 
 namespace rdoom_dev {
@@ -101,45 +103,37 @@ rdoom_status rdoom_lightset_create(const rdoom_light_info *const *infos, const u
   if (!out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   *out = nullptr;
   if (!infos || !counts || n_levels == 0) return rdoom::fail(RDOOM_BAD_ARG, "a light set needs at least one level's info list");
-  std::vector<rdoom_light_info> all;
-  std::vector<uint2> ranges;
-  for (uint32_t l = 0; l < n_levels; l++) {
-    if (counts[l] > 255u) return rdoom::fail(RDOOM_BAD_ARG, "level %u has %u light infos (at most 255)", l, counts[l]);
-    if (counts[l] && !infos[l]) return rdoom::fail(RDOOM_BAD_ARG, "level %u: %u light infos at a null pointer", l, counts[l]);
-    ranges.push_back(make_uint2((uint32_t)all.size(), counts[l]));
-    for (uint32_t i = 0; i < counts[l]; i++) {
-      const rdoom_light_info &info = infos[l][i];
-      if (info.has_effect && (info.effect_kind < 0 || info.effect_kind > 2))
-        return rdoom::fail(RDOOM_BAD_ARG, "level %u, light %u: effect_kind %d is not 0 (Glow), 1 (Random) or 2 (Alternate)", l, i,
-                           info.effect_kind);
-      all.push_back(info);
+  return rdoom::guarded([&]() -> rdoom_status {
+    std::vector<rdoom_light_info> all;
+    std::vector<uint2> ranges;
+    for (uint32_t l = 0; l < n_levels; l++) {
+      if (counts[l] > 255u) return rdoom::fail(RDOOM_BAD_ARG, "level %u has %u light infos (at most 255)", l, counts[l]);
+      if (counts[l] && !infos[l]) return rdoom::fail(RDOOM_BAD_ARG, "level %u: %u light infos at a null pointer", l, counts[l]);
+      ranges.push_back(make_uint2((uint32_t)all.size(), counts[l]));
+      for (uint32_t i = 0; i < counts[l]; i++) {
+        const rdoom_light_info &info = infos[l][i];
+        if (info.has_effect && (info.effect_kind < 0 || info.effect_kind > 2))
+          return rdoom::fail(RDOOM_BAD_ARG, "level %u, light %u: effect_kind %d is not 0 (Glow), 1 (Random) or 2 (Alternate)", l, i,
+                             info.effect_kind);
+        all.push_back(info);
+      }
     }
-  }
-  rdoom_lightset *set = new (std::nothrow) rdoom_lightset();
-  if (!set) return rdoom::fail(RDOOM_OOM, "out of host memory");
-  hipError_t e = hipGetDevice(&set->view.device);
-  // (never a zero-byte allocation: a set whose levels all have no light keeps one unused info)
-  if (e == hipSuccess) e = hipMalloc(&set->d_infos, sizeof(rdoom_light_info) * (all.size() + 1u));
-  if (e == hipSuccess) e = hipMalloc(&set->d_ranges, sizeof(uint2) * ranges.size());
-  if (e == hipSuccess && !all.empty()) e = hipMemcpy(set->d_infos, all.data(), sizeof(rdoom_light_info) * all.size(), hipMemcpyHostToDevice);
-  if (e == hipSuccess) e = hipMemcpy(set->d_ranges, ranges.data(), sizeof(uint2) * ranges.size(), hipMemcpyHostToDevice);
-  if (e != hipSuccess) {
-    rdoom_lightset_destroy(set);
-    return rdoom::fail(e == hipErrorOutOfMemory ? RDOOM_OOM : RDOOM_HIP_ERROR, "light set upload failed: %s", hipGetErrorString(e));
-  }
-  set->view.infos = static_cast<const rdoom_light_info *>(set->d_infos);
-  set->view.ranges = static_cast<const uint2 *>(set->d_ranges);
-  set->view.n_levels = n_levels;
-  *out = set;
-  return RDOOM_OK;
+    auto set = std::make_unique<rdoom_lightset>();
+    HIP_TRY(hipGetDevice(&set->view.device));
+    // (never a zero-byte allocation: a set whose levels all have no light keeps one unused info)
+    if (rdoom_status s = set->d_infos.alloc(all.size() + 1u)) return s;
+    if (rdoom_status s = set->d_ranges.alloc(ranges.size())) return s;
+    if (!all.empty()) HIP_TRY(hipMemcpy(set->d_infos.get(), all.data(), sizeof(rdoom_light_info) * all.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(set->d_ranges.get(), ranges.data(), sizeof(uint2) * ranges.size(), hipMemcpyHostToDevice));
+    set->view.infos = set->d_infos.get();
+    set->view.ranges = set->d_ranges.get();
+    set->view.n_levels = n_levels;
+    *out = set.release();
+    return RDOOM_OK;
+  });
 }
 
-void rdoom_lightset_destroy(rdoom_lightset *set) {
-  if (!set) return;
-  (void)hipFree(set->d_infos);
-  (void)hipFree(set->d_ranges);
-  delete set;
-}
+void rdoom_lightset_destroy(rdoom_lightset *set) { delete set; }
 
 rdoom_status rdoom_lightset_tables(const rdoom_lightset *set, const uint32_t *d_levels, const float *d_times, uint32_t n,
                                    uint8_t *d_out, void *stream) {

@@ -335,7 +335,7 @@ rdoom_status rdoom_worldset_area_frontiers(const rdoom_worldset *set, const uint
     return s;
   if (rdoom_status s = rdoom::check_device(&src, "the world set")) return s;
   if (!n) return RDOOM_OK;
-  return rdoom::launch_checked(worldset_area_frontiers_kernel, dim3(n), dim3(THREADS), 0, stream, a, (const float4 *)src.map->bounds, d_levels,
+  return rdoom::launch_checked(worldset_area_frontiers_kernel, dim3(n), dim3(THREADS), 0, stream, a, (const float4 *)src.map->bounds.get(), d_levels,
                                src.n_levels);
 }
 

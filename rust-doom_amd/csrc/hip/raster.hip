@@ -1032,10 +1032,10 @@ rdoom_status launch_raster(hipStream_t st, uint32_t n_poses, const DeviceLevelVi
   if (groups > 65535u || tiles_y > 65535 || (uint64_t)tiles_x * 8ull > 0x7FFFFFFFull)
     return rdoom::fail(RDOOM_BAD_ARG, "batch too large for one launch");
   const rdoom::DebugOptions &dbg = rdoom::debug_options();
-  unsigned long long *d_stats = nullptr;
+  rdoom::DeviceArray<unsigned long long> d_stats;  // (released on every way out, after the synchronous copy that reads it)
   if (dbg.raster_stats) {
-    HIP_TRY(hipMalloc((void **)&d_stats, RASTER_NSTAT * sizeof(unsigned long long)));
-    HIP_TRY(hipMemsetAsync(d_stats, 0, RASTER_NSTAT * sizeof(unsigned long long), st));
+    if (rdoom_status s = d_stats.alloc(RASTER_NSTAT)) return s;
+    HIP_TRY(hipMemsetAsync(d_stats.get(), 0, RASTER_NSTAT * sizeof(unsigned long long), st));
   }
   const bool skip = skip_described_vis && qtab != nullptr;  // (without a table every visibility word is needed)
   auto pick = [&](auto stats, auto skipvis, auto splt) {
@@ -1060,11 +1060,10 @@ rdoom_status launch_raster(hipStream_t st, uint32_t n_poses, const DeviceLevelVi
   const dim3 rgrid((uint32_t)tiles_x * 8u, groups, (uint32_t)tiles_y);  // tile rows the slowest dimension (raster_wave_kernel)
   hipLaunchKernelGGL(rk, rgrid, dim3(64 * RASTER_WAVES), 0, st, lv, recs, counts, cap, n, width, height, tiles_x,
                      tiles_y, tile_hdr, entries, entry_cap, overflow, vis, prim_out, (dbg.no_cover ? 1u : 0u) | (dbg.no_pair ? 2u : 0u) | (dbg.no_masked_fast ? 4u : 0u),
-                     qtab, settle ? 1u : 0u, d_stats);
+                     qtab, settle ? 1u : 0u, d_stats.get());
   if (d_stats) {
     unsigned long long h[RASTER_NSTAT];
-    HIP_TRY(hipMemcpy(h, d_stats, sizeof h, hipMemcpyDeviceToHost));
-    (void)hipFree(d_stats);
+    HIP_TRY(hipMemcpy(h, d_stats.get(), sizeof h, hipMemcpyDeviceToHost));
     masked_census[0] = h[25], masked_census[1] = h[27], masked_census[2] = h[28], masked_census[3] = h[20];
     {  // census of the tile lists' lengths (a tile with more than 64 entries gets a list per quadrant: bin.hip)
       const size_t nt = (size_t)n * (size_t)(tiles_x * tiles_y);

@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <tuple>
 #include <vector>
 
@@ -19,6 +20,8 @@
 #pragma clang fp contract(off)
 
 using namespace rdoom_dev;
+using rdoom::DeviceArray;
+using rdoom::PinnedArray;
 
 namespace {
 bool is_pow2(uint32_t x) { return x != 0 && (x & (x - 1)) == 0; }
@@ -27,15 +30,18 @@ bool is_pow2(uint32_t x) { return x != 0 && (x & (x - 1)) == 0; }
 // A resident SET of levels (rdoom_levelset_create); rdoom_level_create makes a set of one.
 struct rdoom_level {
   int device = 0;
-  DeviceLevelView view{};
-  void *d_clusters = nullptr;
-  void *d_tris = nullptr, *d_texels = nullptr, *d_sky = nullptr, *d_cmap = nullptr, *d_slices = nullptr;
+  DeviceLevelView view{};  // its pointers are views of the arrays below
+  DeviceArray<LevelTri> d_tris;
+  DeviceArray<Cluster> d_clusters;
+  DeviceArray<uint16_t> d_texels, d_sky;
+  DeviceArray<uint8_t> d_cmap;
+  DeviceArray<LevelSlice> d_slices;
   std::vector<LevelSlice> slices;      // host copy of the slice table
   uint32_t ntri = 0;        // the LARGEST level's triangle count: a pose's records and visible list have this stride
   uint32_t n_objects = 1;   // 1 + the largest object id any level of the set draws
   // PLAYPAL 0 of every level, 256 words R | G << 8 | B << 16 | 0xFF << 24 per level: read by the resolve kernels only (they take it
   // as an argument of their own, so no struct another kernel takes by value carries it)
-  uint32_t *d_palettes = nullptr;
+  DeviceArray<uint32_t> d_palettes;
   std::vector<uint8_t> has_palette;  // the level's desc had a playpal (else its poses cannot be resolved to RGB)
   // Hidden things (rdoom_level_set_decor_things): per level, its descriptor's decor vertex count and, per triangle, the decor
   // quad its three indices lie in (idx / 4) -- NONE for a triangle of another kind, QUAD_SPANS for a decor triangle whose indices
@@ -44,72 +50,85 @@ struct rdoom_level {
   std::vector<uint32_t> n_decor_verts;
   std::vector<std::vector<uint32_t>> tri_quad;
   std::vector<uint8_t> has_decor, things_attached;
-  uint32_t *d_tri_thing = nullptr;
+  DeviceArray<uint32_t> d_tri_thing;
 };
 
+// The members that own something are declared in the reverse of the order they must be released in -- pinned staging, the copy
+// stream, the events, the device buffers -- so that the destructor frees the device buffers FIRST: a batch destroyed while its last
+// render is still in flight relies on that first release waiting for the device, before an event or the staging a queued copy reads
+// goes away.  The raw pointers are views or borrowed, each says of what.
 struct rdoom_batch {
-  const rdoom_level *level = nullptr;
+  const rdoom_level *level = nullptr;  // borrowed: the caller keeps the level alive for as long as the batch
   uint32_t width = 0, height = 0, max_poses = 0, cap = 0, last_n = 0;
   // Row pitch, in pixels, of the visibility words, primitive ids and framebuffers: the width itself when it is a multiple of 4
   // (every size the kernels were written for), else the next multiple of 8 -- the reference takes any --resolution WxH
   // (src/main.rs:41).  The frame's geometry (viewport, bounding boxes, sky ndc) uses `width`; the padding columns are never
   // covered (S6 clamps every bounding box to the frame) and never read back.
   uint32_t pitch = 0;
-  PoseConst *d_poses = nullptr;
-  TriRec *d_recs = nullptr;   // max_poses x cap records in near-to-far order (setup -> bin, raster, fragment)
-  uint32_t *d_visible = nullptr;  // max_poses x cap: the visible triangles of each pose (cull kernel -> set-up kernel)
-  uint2 *d_tile_hdr = nullptr;     // per (pose, tile): (first entry, entry count)
-  uint32_t *d_entries = nullptr;   // per pose: entry_cap tile-list entries (record index | quadrant mask << 28)
-  uint2 *d_hits = nullptr;         // per pose: entry_cap (entry, tile) pairs: the binning kernel's count pass -> its fill pass
-  uint32_t *d_overflow = nullptr;  // per pose: 1 = bins incomplete, rasteriser scans the sorted list
   uint32_t entry_cap = 0, n_tiles = 0;
-  // The words every render starts from zero -- d_fix_count (4), d_counts (max_poses), d_ghist (2048 per pose) -- are ONE
-  // allocation, d_zeroed, cleared by one hipMemsetAsync: four separate fills per render were four more packets between the
-  // kernels of a stream (the 1/8 share of config 4 queues 9 x 13 packets per step for a few hundred microseconds of work each).
-  uint32_t *d_zeroed = nullptr;
-  uint32_t *d_fix_count = nullptr;  // [0] = queued pixels, [1] = error flag (fixup list overflow), [2] = error flag (the set-up kernel
-                                    // disagreed with the cull kernel about a triangle: the counting sort's buckets would not add up),
-                                    // [3] = rdoom_batch_render_players' level error word (level_error)
-  uint2 *d_fix_list = nullptr;
   uint32_t fix_cap = 1u << 20;
-  uint32_t *d_counts = nullptr, *d_vis = nullptr, *d_prim = nullptr;
-  void *d_frag_const = nullptr;  // the fragment kernel's rarely read constants (fragment.hip: FragConst), written on first use
   bool frag_const_ready = false;
-  uint32_t *d_qtab = nullptr;  // per (pose, tile, quadrant): the record every pixel of the quadrant shows, or NONE (rasteriser -> fragment kernel)
-  uint32_t *d_ghist = nullptr;  // counting sort of the set-up: per pose, one counter per depth bucket
-  uint8_t *d_fb = nullptr;
-  // Pinned staging for the per-pose constants, TWO deep: a render waits for the H2D copy of the render before the previous
-  // one, not for the previous one's -- with one buffer the host could not queue a render before the stream had reached the last
-  // render's copy, and a host thread that feeds several batches on several streams stalled on each in turn (the 1/8 share of
-  // BASELINE config 4, nine levels x small batches, ran SLOWER on two streams than on one).
-  static constexpr uint32_t STAGES = 2;
-  PoseConst *h_poses[STAGES] = {nullptr, nullptr};
-  ObjectConst *d_objects = nullptr, *h_objects[STAGES] = {nullptr, nullptr};  // max_poses x n_objects, allocated on first use
   uint32_t stage = 0;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-  static constexpr uint32_t RING = 64;  // renders whose per-kernel events may be pending (rdoom_batch_render_profiled)
-  hipEvent_t ring[RING][4] = {};
   uint32_t ring_n = 0, ring_poses = 0;
-  hipEvent_t ev_copy[STAGES] = {nullptr, nullptr};  // H2D of h_poses[i] finished: that staging buffer may be rewritten
-  // The end of the last render on ITS stream, and a stream of the batch's own for read-backs: rdoom_batch_finish and the
-  // rdoom_batch_read_* wait for this batch's work only, never for the device -- another host thread's render on another
-  // stream (SURVEY 8(b): one host thread per GPU or stream) does not delay them.
-  hipEvent_t ev_done = nullptr;
-  hipStream_t copy_stream = nullptr;
   bool want_prim = false;
   bool vis16 = false;  // record indices fit 16 bits: visibility words are u16
-  float *d_ndc = nullptr;  // (ix + 0.5) / (width / 2) - 1 for every column, then (iy + 0.5) / (height / 2) - 1 for every row
   // the last render's FragmentPlan::skip_described_vis: a described quadrant's visibility words are another render's (resolve reads the table)
   bool last_skip_vis = false;
   uint64_t last_masked_census[4] = {0, 0, 0, 0};  // the last render's census of the rasteriser's masked bodies (hook raster_stats; else zeros)
   bool last_frag_count = false;  // the last render's FragmentPlan::count: the fragment kernel counted its half lanes and listed quads
-  uint8_t *d_rgb = nullptr;  // rdoom_batch_read_rgb's staging (allocated on first use, at most RGB_STAGING_BYTES or one frame)
-  size_t rgb_bytes = 0;
+  size_t rgb_bytes = 0;          // of d_rgb
   // the last render was rdoom_batch_render_players: its levels are on the device only (the pinned staging is an older render's)
   bool last_levels_on_device = false;
   // rdoom_batch_set_hidden_things: the caller's rows of thing bits (borrowed), read by the cull kernel of every render; null: none
   const uint32_t *d_hidden = nullptr;
   uint32_t hidden_stride = 0;
+
+  // ---- released last: pinned host memory ----
+  // Pinned staging for the per-pose constants, TWO deep: a render waits for the H2D copy of the render before the previous
+  // one, not for the previous one's -- with one buffer the host could not queue a render before the stream had reached the last
+  // render's copy, and a host thread that feeds several batches on several streams stalled on each in turn (the 1/8 share of
+  // BASELINE config 4, nine levels x small batches, ran SLOWER on two streams than on one).
+  static constexpr uint32_t STAGES = 2;
+  PinnedArray<ObjectConst> h_objects[STAGES];  // max_poses x n_objects, allocated on first use
+  PinnedArray<PoseConst> h_poses[STAGES];
+  // ---- then the copy stream ----
+  // The end of the last render on ITS stream (ev_done), and a stream of the batch's own for read-backs: rdoom_batch_finish and the
+  // rdoom_batch_read_* wait for this batch's work only, never for the device -- another host thread's render on another
+  // stream (SURVEY 8(b): one host thread per GPU or stream) does not delay them.
+  rdoom::Stream copy_stream;
+  // ---- then the events ----
+  rdoom::Event ev_done;
+  rdoom::Event ev_copy[STAGES];  // H2D of h_poses[i] finished: that staging buffer may be rewritten
+  static constexpr uint32_t RING = 64;  // renders whose per-kernel events may be pending (rdoom_batch_render_profiled)
+  rdoom::Event ring[RING][4];           // created on first use
+  rdoom::Event ev[4];
+  // ---- released first: device memory ----
+  DeviceArray<PoseConst> d_poses;
+  DeviceArray<TriRec> d_recs;        // max_poses x cap records in near-to-far order (setup -> bin, raster, fragment)
+  DeviceArray<uint32_t> d_visible;   // max_poses x cap: the visible triangles of each pose (cull kernel -> set-up kernel)
+  DeviceArray<uint2> d_tile_hdr;     // per (pose, tile): (first entry, entry count)
+  DeviceArray<uint32_t> d_entries;   // per pose: entry_cap tile-list entries (record index | quadrant mask << 28)
+  DeviceArray<uint2> d_hits;         // per pose: entry_cap (entry, tile) pairs: the binning kernel's count pass -> its fill pass
+  DeviceArray<uint32_t> d_overflow;  // per pose: 1 = bins incomplete, rasteriser scans the sorted list
+  // The words every render starts from zero -- d_fix_count (4), d_counts (max_poses), d_ghist (2048 per pose) -- are ONE
+  // allocation, d_zeroed, cleared by one hipMemsetAsync: four separate fills per render were four more packets between the
+  // kernels of a stream (the 1/8 share of config 4 queues 9 x 13 packets per step for a few hundred microseconds of work each).
+  DeviceArray<uint32_t> d_zeroed;
+  // views into d_zeroed:
+  uint32_t *d_fix_count = nullptr;  // [0] = queued pixels, [1] = error flag (fixup list overflow), [2] = error flag (the set-up kernel
+                                    // disagreed with the cull kernel about a triangle: the counting sort's buckets would not add up),
+                                    // [3] = rdoom_batch_render_players' level error word (level_error)
+  uint32_t *d_counts = nullptr;
+  uint32_t *d_ghist = nullptr;  // counting sort of the set-up: per pose, one counter per depth bucket
+  DeviceArray<uint2> d_fix_list;
+  DeviceArray<uint32_t> d_vis;       // (u16 words when vis16)
+  DeviceArray<uint8_t> d_fb;
+  DeviceArray<uint8_t> d_frag_const;  // the fragment kernel's rarely read constants (fragment.hip: FragConst), written on first use
+  DeviceArray<uint32_t> d_qtab;  // per (pose, tile, quadrant): the record every pixel of the quadrant shows, or NONE (rasteriser -> fragment kernel)
+  DeviceArray<float> d_ndc;  // (ix + 0.5) / (width / 2) - 1 for every column, then (iy + 0.5) / (height / 2) - 1 for every row
+  DeviceArray<uint32_t> d_prim;        // allocated by rdoom_batch_enable_primitive_ids
+  DeviceArray<ObjectConst> d_objects;  // max_poses x n_objects, allocated on first use
+  DeviceArray<uint8_t> d_rgb;  // rdoom_batch_read_rgb's staging (allocated on first use, at most RGB_STAGING_BYTES or one frame)
 };
 
 // Every entry point that touches a batch's memory or waits for its work first makes the level's device current: a host
@@ -120,14 +139,14 @@ static hipError_t bind_device(const rdoom_batch *b) { return hipSetDevice(b->lev
 // Device -> host over the batch's own stream, after the batch's last render (and nothing else) has finished.  rows > 1: a
 // strided source (pitch_bytes between rows), tightly packed at the destination.
 static hipError_t read_back(const rdoom_batch *b, void *dst, const void *src, size_t row_bytes, size_t rows = 1, size_t pitch_bytes = 0) {
-  hipError_t e = hipStreamWaitEvent(b->copy_stream, b->ev_done, 0);  // (an event never recorded counts as complete)
+  hipError_t e = hipStreamWaitEvent(b->copy_stream.get(), b->ev_done.get(), 0);  // (an event never recorded counts as complete)
   if (e != hipSuccess) return e;
   if (rows <= 1 || pitch_bytes == row_bytes)
-    e = hipMemcpyAsync(dst, src, row_bytes * (rows ? rows : 1), hipMemcpyDeviceToHost, b->copy_stream);
+    e = hipMemcpyAsync(dst, src, row_bytes * (rows ? rows : 1), hipMemcpyDeviceToHost, b->copy_stream.get());
   else
-    e = hipMemcpy2DAsync(dst, row_bytes, src, pitch_bytes, row_bytes, rows, hipMemcpyDeviceToHost, b->copy_stream);
+    e = hipMemcpy2DAsync(dst, row_bytes, src, pitch_bytes, row_bytes, rows, hipMemcpyDeviceToHost, b->copy_stream.get());
   if (e != hipSuccess) return e;
-  return hipStreamSynchronize(b->copy_stream);
+  return hipStreamSynchronize(b->copy_stream.get());
 }
 
 // fix[3] is rdoom_batch_render_players' error word: ~p for the first pose p whose level lay outside the set (0: none)
@@ -161,13 +180,7 @@ rdoom_status rdoom_set_device(int32_t device) {
   return RDOOM_OK;
 }
 
-void rdoom_level_destroy(rdoom_level *level) {
-  if (!level) return;
-  for (void *p : {level->d_clusters, level->d_tris, level->d_texels, level->d_sky, level->d_cmap, level->d_slices, (void *)level->d_palettes,
-                  (void *)level->d_tri_thing})
-    if (p) (void)hipFree(p);
-  delete level;
-}
+void rdoom_level_destroy(rdoom_level *level) { delete level; }
 
 // One level of a set, flattened on the host: what rdoom_levelset_create concatenates and uploads.
 namespace {
@@ -188,13 +201,7 @@ static rdoom_status flatten_level(const rdoom_level_desc *d, HostLevel &out);
 static rdoom_status levelset_create_impl(const rdoom_level_desc *const *descs, uint32_t n_levels, rdoom_level **out_level);
 
 rdoom_status rdoom_levelset_create(const rdoom_level_desc *const *descs, uint32_t n_levels, rdoom_level **out_level) {
-  try {  // std::vector / std::map below may throw: nothing unwinds across the C ABI
-    return levelset_create_impl(descs, n_levels, out_level);
-  } catch (const std::bad_alloc &) {
-    return rdoom::fail(RDOOM_OOM, "out of host memory");
-  } catch (const std::exception &e) {
-    return rdoom::fail(RDOOM_BAD_LEVEL, "%s", e.what());
-  }
+  return rdoom::guarded([&] { return levelset_create_impl(descs, n_levels, out_level); });  // (std::vector / std::map may throw)
 }
 
 rdoom_status rdoom_level_create(const rdoom_level_desc *d, rdoom_level **out_level) {
@@ -385,7 +392,7 @@ static rdoom_status levelset_create_impl(const rdoom_level_desc *const *descs, u
     if (k && std::memcmp(descs[k]->colormap, descs[0]->colormap, 32 * 256) != 0)
       return rdoom::fail(RDOOM_BAD_ARG, "level %u: its COLORMAP differs from level 0's (the levels of a set share one)", k);
   }
-  rdoom_level *lv = new rdoom_level;
+  auto lv = std::make_unique<rdoom_level>();
   (void)hipGetDevice(&lv->device);
   // the set's arrays: triangles, clusters, texels, skies, level after level
   std::vector<LevelTri> tris;
@@ -395,6 +402,11 @@ static rdoom_status levelset_create_impl(const rdoom_level_desc *const *descs, u
   uint32_t max_clusters = 0;
   for (uint32_t k = 0; k < n_levels; k++) {
     HostLevel &h = host[k];
+    // a record addresses the store with (base >> 10) in 16 bits (ShadeRec::flags), a cluster index fits 32 bits: checked on the
+    // running totals, before a base below is narrowed to 32 bits and before the set's copy grows by this level
+    if (texels.size() + h.texels.size() >= ((size_t)1 << 26))
+      return rdoom::fail(RDOOM_BAD_LEVEL, "atlases too large (%zu texels in the set; at most 2^26)", texels.size() + h.texels.size());
+    if (tris.size() + h.tris.size() >= ((size_t)1 << 31)) return rdoom::fail(RDOOM_BAD_LEVEL, "too many triangles in the set");
     LevelSlice &sl = lv->slices[k];
     sl = h.dims;
     sl.first_tri = (uint32_t)tris.size(), sl.ntri = (uint32_t)h.tris.size();
@@ -418,95 +430,44 @@ static rdoom_status levelset_create_impl(const rdoom_level_desc *const *descs, u
     lv->tri_quad.push_back(std::move(h.tri_quad));
     h = HostLevel{};  // (released: a set of many levels would otherwise hold every atlas twice)
   }
-  // a record addresses the store with (base >> 10) in 16 bits (ShadeRec::flags), a cluster index fits 32 bits
-  if (texels.size() >= ((size_t)1 << 26)) {
-    const size_t n = texels.size();
-    rdoom_level_destroy(lv);
-    return rdoom::fail(RDOOM_BAD_LEVEL, "atlases too large (%zu texels in the set; at most 2^26)", n);
-  }
-  if (tris.size() >= ((size_t)1 << 31)) {
-    rdoom_level_destroy(lv);
-    return rdoom::fail(RDOOM_BAD_LEVEL, "too many triangles in the set");
-  }
   texels.push_back(0);  // never empty; the fragment kernel's 32-bit load at the last texel's 2-byte-aligned address reads one past it
   texels.push_back(0);
-  auto upload = [&](void **dst, const void *src, size_t bytes) -> hipError_t {
-    if (bytes == 0 || !src) {
-      *dst = nullptr;
-      return hipSuccess;
-    }
-    hipError_t e = hipMalloc(dst, bytes);
-    if (e != hipSuccess) return e;
-    return hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-  };
-  hipError_t e = upload(&lv->d_tris, tris.data(), tris.size() * sizeof(LevelTri));
-  if (e == hipSuccess) e = upload(&lv->d_clusters, clusters.data(), clusters.size() * sizeof(Cluster));
-  if (e == hipSuccess) e = upload(&lv->d_texels, texels.data(), texels.size() * 2);
-  if (e == hipSuccess) e = upload(&lv->d_sky, sky.data(), sky.size() * 2);
-  if (e == hipSuccess) e = upload(&lv->d_cmap, descs[0]->colormap, 32 * 256);
-  if (e == hipSuccess) e = upload(&lv->d_slices, lv->slices.data(), lv->slices.size() * sizeof(LevelSlice));
-  {  // PLAYPAL 0 of each level (no rule that they match: a level without one is created as before and cannot be resolved)
-    std::vector<uint32_t> pal((size_t)n_levels * 256u, 0u);
-    lv->has_palette.assign(n_levels, 0);
-    for (uint32_t k = 0; k < n_levels; k++) {
-      const uint8_t *pp = descs[k]->playpal;
-      if (!pp) continue;
-      lv->has_palette[k] = 1;
-      for (uint32_t i = 0; i < 256u; i++)
-        pal[(size_t)k * 256u + i] = (uint32_t)pp[3 * i] | ((uint32_t)pp[3 * i + 1] << 8) | ((uint32_t)pp[3 * i + 2] << 16) | 0xFF000000u;
-    }
-    if (e == hipSuccess) e = upload((void **)&lv->d_palettes, pal.data(), pal.size() * sizeof(uint32_t));
+  // PLAYPAL 0 of each level (no rule that they match: a level without one is created as before and cannot be resolved)
+  std::vector<uint32_t> pal((size_t)n_levels * 256u, 0u);
+  lv->has_palette.assign(n_levels, 0);
+  for (uint32_t k = 0; k < n_levels; k++) {
+    const uint8_t *pp = descs[k]->playpal;
+    if (!pp) continue;
+    lv->has_palette[k] = 1;
+    for (uint32_t i = 0; i < 256u; i++)
+      pal[(size_t)k * 256u + i] = (uint32_t)pp[3 * i] | ((uint32_t)pp[3 * i + 1] << 8) | ((uint32_t)pp[3 * i + 2] << 16) | 0xFF000000u;
   }
-  if (e != hipSuccess) {
-    rdoom_level_destroy(lv);
-    return rdoom::fail(e == hipErrorOutOfMemory ? RDOOM_OOM : RDOOM_HIP_ERROR, "level upload failed: %s",
-                       hipGetErrorString(e));
-  }
-  lv->view.tris = (const LevelTri *)lv->d_tris;
-  lv->view.clusters = (const Cluster *)lv->d_clusters;
-  lv->view.texels = (const uint16_t *)lv->d_texels;
-  lv->view.sky_texels = (const uint16_t *)lv->d_sky;
-  lv->view.colormap = (const uint8_t *)lv->d_cmap;
-  lv->view.slices = (const LevelSlice *)lv->d_slices;
+  // (an empty array stays a null pointer: a set without a sky has no sky texels)
+  if (rdoom_status rs = lv->d_tris.upload(tris)) return rs;
+  if (rdoom_status rs = lv->d_clusters.upload(clusters)) return rs;
+  if (rdoom_status rs = lv->d_texels.upload(texels)) return rs;
+  if (rdoom_status rs = lv->d_sky.upload(sky)) return rs;
+  if (rdoom_status rs = lv->d_cmap.upload(descs[0]->colormap, 32 * 256)) return rs;
+  if (rdoom_status rs = lv->d_slices.upload(lv->slices)) return rs;
+  if (rdoom_status rs = lv->d_palettes.upload(pal)) return rs;
+  lv->view.tris = lv->d_tris.get();
+  lv->view.clusters = lv->d_clusters.get();
+  lv->view.texels = lv->d_texels.get();
+  lv->view.sky_texels = lv->d_sky.get();
+  lv->view.colormap = lv->d_cmap.get();
+  lv->view.slices = lv->d_slices.get();
   lv->view.n_slices = n_levels;
   lv->view.max_clusters = max_clusters;
   lv->view.max_ntri = lv->ntri;
-  *out_level = lv;
+  *out_level = lv.release();
   return RDOOM_OK;
 }
 
-void rdoom_batch_destroy(rdoom_batch *b) {
-  if (!b) return;
-  for (void *p : {(void *)b->d_poses, (void *)b->d_recs, (void *)b->d_visible, (void *)b->d_tile_hdr, (void *)b->d_entries, (void *)b->d_hits,
-                  (void *)b->d_overflow, (void *)b->d_zeroed, (void *)b->d_fix_list, (void *)b->d_vis,
-                  (void *)b->d_prim, (void *)b->d_fb, (void *)b->d_qtab, b->d_frag_const, (void *)b->d_rgb})
-    if (p) (void)hipFree(p);
-  for (auto &e : b->ev)
-    if (e) (void)hipEventDestroy(e);
-  for (auto &slot : b->ring)
-    for (auto &e : slot)
-      if (e) (void)hipEventDestroy(e);
-  for (auto &e : b->ev_copy)
-    if (e) (void)hipEventDestroy(e);
-  if (b->ev_done) (void)hipEventDestroy(b->ev_done);
-  if (b->copy_stream) (void)hipStreamDestroy(b->copy_stream);
-  for (auto &h : b->h_poses)
-    if (h) (void)hipHostFree(h);
-  for (auto &h : b->h_objects)
-    if (h) (void)hipHostFree(h);
-  if (b->d_ndc) (void)hipFree(b->d_ndc);
-  if (b->d_objects) (void)hipFree(b->d_objects);
-  delete b;
-}
+void rdoom_batch_destroy(rdoom_batch *b) { delete b; }
 
-rdoom_status rdoom_batch_create(const rdoom_level *level, uint32_t width, uint32_t height, uint32_t max_poses,
-                                rdoom_batch **out_batch) {
-  if (!level || !out_batch) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
-  *out_batch = nullptr;
-  if (width == 0 || height == 0 || max_poses == 0 || width > 16384 || height > 16384)
-    return rdoom::fail(RDOOM_BAD_ARG, "bad frame size %ux%u (1..16384 on a side) or max_poses %u", width, height, max_poses);
+static rdoom_status batch_create_impl(const rdoom_level *level, uint32_t width, uint32_t height, uint32_t max_poses, rdoom_batch **out_batch) {
   HIP_TRY(hipSetDevice(level->device));  // the batch lives on the level's device, whatever the caller's current one is
-  rdoom_batch *b = new rdoom_batch;
+  auto b = std::make_unique<rdoom_batch>();
   b->level = level;
   b->width = width;
   b->height = height;
@@ -516,9 +477,9 @@ rdoom_status rdoom_batch_create(const rdoom_level *level, uint32_t width, uint32
   const rdoom::DebugOptions &dbg = rdoom::debug_options();
   b->vis16 = b->cap < 0xFFFFu && !dbg.vis32;
   const size_t npx = (size_t)b->pitch * height * max_poses;
-  hipError_t e = hipMalloc((void **)&b->d_poses, sizeof(PoseConst) * max_poses);
-  if (e == hipSuccess) e = hipMalloc((void **)&b->d_recs, sizeof(TriRec) * (size_t)b->cap * max_poses);
-  if (e == hipSuccess) e = hipMalloc((void **)&b->d_visible, sizeof(uint32_t) * (size_t)b->cap * max_poses);
+  if (rdoom_status rs = b->d_poses.alloc(max_poses)) return rs;
+  if (rdoom_status rs = b->d_recs.alloc((size_t)b->cap * max_poses)) return rs;
+  if (rdoom_status rs = b->d_visible.alloc((size_t)b->cap * max_poses)) return rs;
   b->n_tiles = ((width + TILE_W - 1) / TILE_W) * ((height + TILE_H - 1) / TILE_H);
   // tile-list entries per pose; beyond it the pose is rasterised from its sorted list (slow: every tile scans every visible
   // triangle).  A long tile's list is stored per quadrant (bin.hip), an entry once per quadrant it touches, so the array is
@@ -532,45 +493,48 @@ rdoom_status rdoom_batch_create(const rdoom_level *level, uint32_t width, uint32
                                               (uint64_t)b->cap * b->n_tiles * 4u + 8u * (uint64_t)b->n_tiles);
   b->entry_cap = (b->entry_cap + 3u) & ~3u;
   if (dbg.entry_cap > 0) b->entry_cap = (uint32_t)dbg.entry_cap;  // tests: force that fallback
-  if (e == hipSuccess) e = hipMalloc((void **)&b->d_tile_hdr, sizeof(uint2) * (size_t)b->n_tiles * max_poses);
-  if (e == hipSuccess) e = hipMalloc((void **)&b->d_entries, sizeof(uint32_t) * (size_t)b->entry_cap * max_poses);
-  if (e == hipSuccess) e = hipMalloc((void **)&b->d_hits, sizeof(uint2) * (size_t)b->entry_cap * max_poses);
-  if (e == hipSuccess) e = hipMalloc((void **)&b->d_overflow, sizeof(uint32_t) * max_poses);
+  if (rdoom_status rs = b->d_tile_hdr.alloc((size_t)b->n_tiles * max_poses)) return rs;
+  if (rdoom_status rs = b->d_entries.alloc((size_t)b->entry_cap * max_poses)) return rs;
+  if (rdoom_status rs = b->d_hits.alloc((size_t)b->entry_cap * max_poses)) return rs;
+  if (rdoom_status rs = b->d_overflow.alloc(max_poses)) return rs;
   const size_t counts_words = ((size_t)max_poses + 3u) & ~(size_t)3u;
-  if (e == hipSuccess) e = hipMalloc((void **)&b->d_zeroed, sizeof(uint32_t) * (4u + counts_words) + setup_histogram_bytes(max_poses));
-  if (e == hipSuccess) b->d_fix_count = b->d_zeroed, b->d_counts = b->d_zeroed + 4, b->d_ghist = b->d_zeroed + 4 + counts_words;
-  if (e == hipSuccess) e = hipMalloc((void **)&b->d_fix_list, sizeof(uint2) * (size_t)b->fix_cap);
-  if (e == hipSuccess) e = hipMalloc((void **)&b->d_vis, (b->vis16 ? sizeof(uint16_t) : sizeof(uint32_t)) * npx);
-  if (e == hipSuccess) e = hipMalloc((void **)&b->d_fb, npx);
-  if (e == hipSuccess) e = hipMalloc(&b->d_frag_const, fragment_const_bytes());
-  if (e == hipSuccess) e = hipMalloc((void **)&b->d_qtab, sizeof(uint32_t) * 4u * (size_t)b->n_tiles * max_poses);
+  if (rdoom_status rs = b->d_zeroed.alloc_bytes(sizeof(uint32_t) * (4u + counts_words) + setup_histogram_bytes(max_poses))) return rs;
+  b->d_fix_count = b->d_zeroed.get(), b->d_counts = b->d_fix_count + 4, b->d_ghist = b->d_counts + counts_words;
+  if (rdoom_status rs = b->d_fix_list.alloc(b->fix_cap)) return rs;
+  if (rdoom_status rs = b->d_vis.alloc_bytes((b->vis16 ? sizeof(uint16_t) : sizeof(uint32_t)) * npx)) return rs;
+  if (rdoom_status rs = b->d_fb.alloc(npx)) return rs;
+  if (rdoom_status rs = b->d_frag_const.alloc(fragment_const_bytes())) return rs;
+  if (rdoom_status rs = b->d_qtab.alloc(4u * (size_t)b->n_tiles * max_poses)) return rs;
   // (the rasteriser never writes the entries of quadrants that lie outside the frame: NONE from the start, so that the
   // table is self-consistent for every reader)
-  if (e == hipSuccess) e = hipMemset(b->d_qtab, 0xFF, sizeof(uint32_t) * 4u * (size_t)b->n_tiles * max_poses);
-  if (e == hipSuccess) {  // sky.frag:13's ndc per column / row, same two operations as the per-pixel form
+  HIP_TRY(hipMemset(b->d_qtab.get(), 0xFF, sizeof(uint32_t) * 4u * (size_t)b->n_tiles * max_poses));
+  {  // sky.frag:13's ndc per column / row, same two operations as the per-pixel form
     // (a run of sky that ends in the padding columns of a padded row pitch reads up to 7 values past the columns: row values, or
     // the zeros the table is extended by -- colours of pixels nobody reads)
     std::vector<float> ndc(std::max(width + height, b->pitch), 0.0f);
     for (uint32_t i = 0; i < width; i++) ndc[i] = ((float)i + 0.5f) / (0.5f * (float)width) - 1.0f;
     for (uint32_t i = 0; i < height; i++) ndc[width + i] = ((float)i + 0.5f) / (0.5f * (float)height) - 1.0f;
-    e = hipMalloc((void **)&b->d_ndc, sizeof(float) * ndc.size());
-    if (e == hipSuccess) e = hipMemcpy(b->d_ndc, ndc.data(), sizeof(float) * ndc.size(), hipMemcpyHostToDevice);
+    if (rdoom_status rs = b->d_ndc.upload(ndc)) return rs;
   }
-  for (auto &ev : b->ev)
-    if (e == hipSuccess) e = hipEventCreate(&ev);
-  for (auto &ev : b->ev_copy)
-    if (e == hipSuccess) e = hipEventCreate(&ev);
-  if (e == hipSuccess) e = hipEventCreate(&b->ev_done);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&b->copy_stream, hipStreamNonBlocking);
-  for (auto &h : b->h_poses)
-    if (e == hipSuccess) e = hipHostMalloc((void **)&h, sizeof(PoseConst) * max_poses, hipHostMallocDefault);
-  if (e != hipSuccess) {
-    rdoom_batch_destroy(b);
-    return rdoom::fail(e == hipErrorOutOfMemory ? RDOOM_OOM : RDOOM_HIP_ERROR, "batch allocation failed: %s",
-                       hipGetErrorString(e));
-  }
-  *out_batch = b;
+  for (rdoom::Event &ev : b->ev)
+    if (rdoom_status rs = ev.create()) return rs;
+  for (rdoom::Event &ev : b->ev_copy)
+    if (rdoom_status rs = ev.create()) return rs;
+  if (rdoom_status rs = b->ev_done.create()) return rs;
+  if (rdoom_status rs = b->copy_stream.create(hipStreamNonBlocking)) return rs;
+  for (PinnedArray<PoseConst> &h : b->h_poses)
+    if (rdoom_status rs = h.alloc(max_poses)) return rs;
+  *out_batch = b.release();
   return RDOOM_OK;
+}
+
+rdoom_status rdoom_batch_create(const rdoom_level *level, uint32_t width, uint32_t height, uint32_t max_poses,
+                                rdoom_batch **out_batch) {
+  if (!level || !out_batch) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  *out_batch = nullptr;
+  if (width == 0 || height == 0 || max_poses == 0 || width > 16384 || height > 16384)
+    return rdoom::fail(RDOOM_BAD_ARG, "bad frame size %ux%u (1..16384 on a side) or max_poses %u", width, height, max_poses);
+  return rdoom::guarded([&] { return batch_create_impl(level, width, height, max_poses, out_batch); });
 }
 
 static void mat_mul_v1(const float *P, const float *M, float *pm) {  // V1: PM = P * M, plain multiply/add, left to right
@@ -589,19 +553,19 @@ struct DoneGuard {
   hipStream_t st;
   bool armed = false;
   ~DoneGuard() {
-    if (armed) (void)hipEventRecord(b->ev_done, st);
+    if (armed) (void)hipEventRecord(b->ev_done.get(), st);
   }
 };
 }  // namespace
 
 // The four marks of a render: the batch's own, or a slot of the ring when nobody waits (RDOOM_RENDER_PROFILED)
-static rdoom_status render_marks(rdoom_batch *b, bool profiled, hipEvent_t **out) {
-  hipEvent_t *ev = b->ev;
+static rdoom_status render_marks(rdoom_batch *b, bool profiled, rdoom::Event **out) {
+  rdoom::Event *ev = b->ev;
   if (profiled) {
     if (b->ring_n == rdoom_batch::RING) return rdoom::fail(RDOOM_BAD_ARG, "%u profiled renders pending: collect the timings first", b->ring_n);
     ev = b->ring[b->ring_n];
     for (int k = 0; k < 4; k++)
-      if (!ev[k]) HIP_TRY(hipEventCreate(&ev[k]));
+      if (rdoom_status rs = ev[k].create()) return rs;
   }
   *out = ev;
   return RDOOM_OK;
@@ -614,61 +578,61 @@ static rdoom_status render_marks(rdoom_batch *b, bool profiled, hipEvent_t **out
 extern "C++" {  // (a template, inside the C ABI's extern "C" block)
 template <class Constants>
 static rdoom_status queue_pipeline(rdoom_batch *b, uint32_t n, uint32_t kinds_mask, hipStream_t st, rdoom_timings *tm,
-                                   bool objects, bool profiled, hipEvent_t *ev, DoneGuard &done, Constants &&constants) {
+                                   bool objects, bool profiled, rdoom::Event *ev, DoneGuard &done, Constants &&constants) {
   const rdoom_level *lv = b->level;
   const bool marks = tm || profiled;
   const int W = (int)b->width, H = (int)b->height, PITCH = (int)b->pitch;
   // fix_count[0..3], the poses' visible-triangle counts and depth-bucket histograms (of the first n poses): one fill
-  HIP_TRY(hipMemsetAsync(b->d_zeroed, 0, (size_t)((const char *)b->d_ghist - (const char *)b->d_zeroed) + setup_histogram_bytes(n), st));
+  HIP_TRY(hipMemsetAsync(b->d_zeroed.get(), 0, (size_t)((const char *)b->d_ghist - (const char *)b->d_zeroed.get()) + setup_histogram_bytes(n), st));
   if (rdoom_status rs = constants()) return rs;
   if (lv->ntri)
-    if (rdoom_status rs = launch_setup(st, n, lv->view, b->d_poses, objects ? (const ObjectConst *)b->d_objects : nullptr,
-                                       lv->n_objects, W, H, kinds_mask, b->d_recs, b->d_visible, b->d_counts,
+    if (rdoom_status rs = launch_setup(st, n, lv->view, b->d_poses.get(), objects ? (const ObjectConst *)b->d_objects.get() : nullptr,
+                                       lv->n_objects, W, H, kinds_mask, b->d_recs.get(), b->d_visible.get(), b->d_counts,
                                        b->d_ghist, b->cap, b->d_fix_count + 2, b->d_hidden, b->hidden_stride))
       return rs;
   const int tiles_x = (W + TILE_W - 1) / TILE_W, tiles_y = (H + TILE_H - 1) / TILE_H;
   bool split_lists = false;  // long tile lists stored per quadrant this render (binning kernel and rasteriser must agree)
   bool bins = false;
   if (lv->ntri && !rdoom::debug_options().no_bins)
-    if (rdoom_status rs = launch_bin(st, n, b->d_recs, b->d_counts, b->cap, tiles_x, tiles_y, b->d_tile_hdr, b->d_entries,
-                                     b->entry_cap, b->d_hits, b->d_overflow, !rdoom::debug_options().no_split, &bins, &split_lists))
+    if (rdoom_status rs = launch_bin(st, n, b->d_recs.get(), b->d_counts, b->cap, tiles_x, tiles_y, b->d_tile_hdr.get(), b->d_entries.get(),
+                                     b->entry_cap, b->d_hits.get(), b->d_overflow.get(), !rdoom::debug_options().no_split, &bins, &split_lists))
       return rs;
   if (!bins) {
-    HIP_TRY(hipMemsetAsync(b->d_overflow, 0xFF, sizeof(uint32_t) * n, st));
+    HIP_TRY(hipMemsetAsync(b->d_overflow.get(), 0xFF, sizeof(uint32_t) * n, st));
   }
-  if (marks) HIP_TRY(hipEventRecord(ev[1], st));
-  uint32_t *prim_out = b->want_prim ? b->d_prim : nullptr;
+  if (marks) HIP_TRY(hipEventRecord(ev[1].get(), st));
+  uint32_t *prim_out = b->want_prim ? b->d_prim.get() : nullptr;
   // one reading of the debug hooks for both kernels: who writes and who reads visibility words must not change in between
-  const FragmentPlan plan = plan_fragment(W, PITCH, H, b->d_qtab != nullptr);
+  const FragmentPlan plan = plan_fragment(W, PITCH, H, (bool)b->d_qtab);
   b->last_skip_vis = plan.skip_described_vis;
   b->last_frag_count = plan.count;
   // (the rasteriser's frame is PITCH pixels wide: the padding columns of a width that is not a multiple of 4 are pixels no
   // bounding box reaches -- they stay uncovered, and the quadrants they lie in simply never count as covered)
-  if (rdoom_status rs = launch_raster(st, n, lv->view, b->d_recs, b->d_counts, b->cap, PITCH, H, tiles_x, tiles_y,
-                                      b->d_tile_hdr, b->d_entries, b->entry_cap, b->d_overflow, b->d_vis, b->vis16, prim_out, b->d_qtab,
+  if (rdoom_status rs = launch_raster(st, n, lv->view, b->d_recs.get(), b->d_counts, b->cap, PITCH, H, tiles_x, tiles_y,
+                                      b->d_tile_hdr.get(), b->d_entries.get(), b->entry_cap, b->d_overflow.get(), b->d_vis.get(), b->vis16, prim_out, b->d_qtab.get(),
                                       plan.skip_described_vis, split_lists, bins, b->last_masked_census))
     return rs;
-  if (marks) HIP_TRY(hipEventRecord(ev[2], st));
-  if (rdoom_status rs = launch_fragment(st, n, lv->view, b->d_recs, b->d_counts, b->cap, b->d_poses, W, PITCH, H, tiles_x,
-                                        tiles_y, b->d_tile_hdr, b->d_entries, b->entry_cap, b->d_overflow, b->d_vis, b->vis16,
-                                        prim_out, b->d_ndc, b->d_fb, b->d_fix_count, b->d_fix_list, b->fix_cap, b->d_qtab, b->d_frag_const,
+  if (marks) HIP_TRY(hipEventRecord(ev[2].get(), st));
+  if (rdoom_status rs = launch_fragment(st, n, lv->view, b->d_recs.get(), b->d_counts, b->cap, b->d_poses.get(), W, PITCH, H, tiles_x,
+                                        tiles_y, b->d_tile_hdr.get(), b->d_entries.get(), b->entry_cap, b->d_overflow.get(), b->d_vis.get(), b->vis16,
+                                        prim_out, b->d_ndc.get(), b->d_fb.get(), b->d_fix_count, b->d_fix_list.get(), b->fix_cap, b->d_qtab.get(), b->d_frag_const.get(),
                                         &b->frag_const_ready, plan))
     return rs;
   HIP_TRY(hipGetLastError());
   done.armed = false;
-  HIP_TRY(hipEventRecord(b->ev_done, st));
+  HIP_TRY(hipEventRecord(b->ev_done.get(), st));
   if (profiled) {
-    HIP_TRY(hipEventRecord(ev[3], st));
+    HIP_TRY(hipEventRecord(ev[3].get(), st));
     b->ring_n++;
     b->ring_poses += n;
   }
   if (tm) {
-    HIP_TRY(hipEventRecord(b->ev[3], st));
-    HIP_TRY(hipEventSynchronize(b->ev[3]));
-    HIP_TRY(hipEventElapsedTime(&tm->setup_ms, b->ev[0], b->ev[1]));
-    HIP_TRY(hipEventElapsedTime(&tm->raster_ms, b->ev[1], b->ev[2]));
-    HIP_TRY(hipEventElapsedTime(&tm->fragment_ms, b->ev[2], b->ev[3]));
-    HIP_TRY(hipEventElapsedTime(&tm->total_ms, b->ev[0], b->ev[3]));
+    HIP_TRY(hipEventRecord(b->ev[3].get(), st));
+    HIP_TRY(hipEventSynchronize(b->ev[3].get()));
+    HIP_TRY(hipEventElapsedTime(&tm->setup_ms, b->ev[0].get(), b->ev[1].get()));
+    HIP_TRY(hipEventElapsedTime(&tm->raster_ms, b->ev[1].get(), b->ev[2].get()));
+    HIP_TRY(hipEventElapsedTime(&tm->fragment_ms, b->ev[2].get(), b->ev[3].get()));
+    HIP_TRY(hipEventElapsedTime(&tm->total_ms, b->ev[0].get(), b->ev[3].get()));
     tm->pixels = (uint64_t)n * W * H;
     std::vector<uint32_t> counts(n);
     HIP_TRY(read_back(b, counts.data(), b->d_counts, sizeof(uint32_t) * n));
@@ -699,14 +663,14 @@ static rdoom_status render_impl(rdoom_batch *b, const rdoom_pose *poses, const u
     return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u but the level draws objects 0..%u", n_objects, lv->n_objects - 1);
   const uint32_t sg = b->stage;  // this render's staging buffers: the H2D copy that last read them is two renders back
   b->stage = (sg + 1u) % rdoom_batch::STAGES;
-  HIP_TRY(hipEventSynchronize(b->ev_copy[sg]));
-  PoseConst *h_poses = b->h_poses[sg];
+  HIP_TRY(hipEventSynchronize(b->ev_copy[sg].get()));
+  PoseConst *h_poses = b->h_poses[sg].get();
   if (object_modelviews) {
     const size_t count = (size_t)b->max_poses * lv->n_objects;
-    if (!b->d_objects) HIP_TRY(hipMalloc((void **)&b->d_objects, sizeof(ObjectConst) * count));
-    for (auto &h : b->h_objects)
-      if (!h) HIP_TRY(hipHostMalloc((void **)&h, sizeof(ObjectConst) * count, hipHostMallocDefault));
-    ObjectConst *h_objects = b->h_objects[sg];
+    if (rdoom_status rs = b->d_objects.alloc(count)) return rs;  // (on the batch's first render with objects)
+    for (PinnedArray<ObjectConst> &h : b->h_objects)
+      if (rdoom_status rs = h.alloc(count)) return rs;
+    ObjectConst *h_objects = b->h_objects[sg].get();
     for (uint32_t p = 0; p < n; p++)
       for (uint32_t o = 0; o < lv->n_objects; o++) {
         ObjectConst &oc = h_objects[(size_t)p * lv->n_objects + o];
@@ -734,17 +698,17 @@ static rdoom_status render_impl(rdoom_batch *b, const rdoom_pose *poses, const u
   }
   b->last_n = n;
   b->last_levels_on_device = false;
-  hipEvent_t *ev = nullptr;
+  rdoom::Event *ev = nullptr;
   if (rdoom_status rs = render_marks(b, profiled, &ev)) return rs;
   const bool marks = tm || profiled;
-  if (marks) HIP_TRY(hipEventRecord(ev[0], st));
+  if (marks) HIP_TRY(hipEventRecord(ev[0].get(), st));
   DoneGuard done{b, st};
   done.armed = true;  // from here on work of this render may be queued: whatever happens, ev_done is recorded after it
-  HIP_TRY(hipMemcpyAsync(b->d_poses, h_poses, sizeof(PoseConst) * n, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(b->d_poses.get(), h_poses, sizeof(PoseConst) * n, hipMemcpyHostToDevice, st));
   if (object_modelviews)
-    HIP_TRY(hipMemcpyAsync(b->d_objects, b->h_objects[sg], sizeof(ObjectConst) * (size_t)n * lv->n_objects,
+    HIP_TRY(hipMemcpyAsync(b->d_objects.get(), b->h_objects[sg].get(), sizeof(ObjectConst) * (size_t)n * lv->n_objects,
                            hipMemcpyHostToDevice, st));
-  HIP_TRY(hipEventRecord(b->ev_copy[sg], st));
+  HIP_TRY(hipEventRecord(b->ev_copy[sg].get(), st));
   return queue_pipeline(b, n, kinds_mask, st, tm, object_modelviews != nullptr, profiled, ev, done, [] { return RDOOM_OK; });
 }
 
@@ -773,13 +737,13 @@ rdoom_status rdoom_batch_collect_timings(rdoom_batch *b, rdoom_timings *out, uin
   HIP_TRY(bind_device(b));
   // profiled renders may have been queued on several streams (bench.py --streams): nothing orders an earlier slot's
   // events against the last one's, so every slot's closing event is waited for
-  for (uint32_t i = 0; i < b->ring_n; i++) HIP_TRY(hipEventSynchronize(b->ring[i][3]));
+  for (uint32_t i = 0; i < b->ring_n; i++) HIP_TRY(hipEventSynchronize(b->ring[i][3].get()));
   for (uint32_t i = 0; i < b->ring_n; i++) {
     float a = 0, r = 0, f = 0, t = 0;
-    HIP_TRY(hipEventElapsedTime(&a, b->ring[i][0], b->ring[i][1]));
-    HIP_TRY(hipEventElapsedTime(&r, b->ring[i][1], b->ring[i][2]));
-    HIP_TRY(hipEventElapsedTime(&f, b->ring[i][2], b->ring[i][3]));
-    HIP_TRY(hipEventElapsedTime(&t, b->ring[i][0], b->ring[i][3]));
+    HIP_TRY(hipEventElapsedTime(&a, b->ring[i][0].get(), b->ring[i][1].get()));
+    HIP_TRY(hipEventElapsedTime(&r, b->ring[i][1].get(), b->ring[i][2].get()));
+    HIP_TRY(hipEventElapsedTime(&f, b->ring[i][2].get(), b->ring[i][3].get()));
+    HIP_TRY(hipEventElapsedTime(&t, b->ring[i][0].get(), b->ring[i][3].get()));
     out->setup_ms += a, out->raster_ms += r, out->fragment_ms += f, out->total_ms += t;
   }
   out->pixels = (uint64_t)b->ring_poses * b->width * b->height;
@@ -846,22 +810,22 @@ static rdoom_status render_players_impl(rdoom_batch *b, const rdoom_player_state
   PlayerFrameArgs a{};
   if (rdoom_status rs = player_projection(b->width, b->height, a.proj, &a.zk)) return rs;
   HIP_TRY(hipSetDevice(lv->device));
-  if (d_object_offsets && !b->d_objects)  // (the one allocation of this path: on the batch's first render with objects)
-    HIP_TRY(hipMalloc((void **)&b->d_objects, sizeof(ObjectConst) * (size_t)b->max_poses * lv->n_objects));
+  if (d_object_offsets)  // (the one allocation of this path: on the batch's first render with objects)
+    if (rdoom_status rs = b->d_objects.alloc((size_t)b->max_poses * lv->n_objects)) return rs;
   const hipStream_t st = (hipStream_t)stream;
   a.states = d_states, a.n = n_players, a.time = time;
   a.offsets = d_object_offsets, a.lanes = d_object_offsets ? n_objects : 1u;
   a.levels = d_levels, a.n_slices = lv->view.n_slices, a.error_word = b->d_fix_count + 3;
   a.lights = d_lights, a.lights_stride = lights_stride, a.times = clock ? clock->d_times : nullptr;
-  a.pose_consts = b->d_poses;
-  a.object_consts = d_object_offsets ? b->d_objects : nullptr, a.n_render_objects = d_object_offsets ? lv->n_objects : 0u;
+  a.pose_consts = b->d_poses.get();
+  a.object_consts = d_object_offsets ? b->d_objects.get() : nullptr, a.n_render_objects = d_object_offsets ? lv->n_objects : 0u;
   a.poses_out = d_poses_out, a.modelviews_out = d_object_modelviews_out;
   // the pinned staging is not touched (no wait on ev_copy); the levels of this render live on the device only
   b->last_n = n_players;
   b->last_levels_on_device = true;
-  hipEvent_t *ev = nullptr;
+  rdoom::Event *ev = nullptr;
   if (rdoom_status rs = render_marks(b, profiled, &ev)) return rs;
-  if (profiled) HIP_TRY(hipEventRecord(ev[0], st));
+  if (profiled) HIP_TRY(hipEventRecord(ev[0].get(), st));
   DoneGuard done{b, st};
   done.armed = true;
   if (!clock)
@@ -870,7 +834,7 @@ static rdoom_status render_players_impl(rdoom_batch *b, const rdoom_player_state
   // every pose's table goes straight into its PoseConst; a level outside the set shows level 0's, as its geometry
   LightTableArgs lt{};
   lt.set = *clock->lights, lt.levels = d_levels, lt.times = clock->d_times, lt.n = n_players;
-  lt.out = reinterpret_cast<uint8_t *>(b->d_poses) + offsetof(PoseConst, lights), lt.stride = (uint32_t)sizeof(PoseConst), lt.fallback = 0u;
+  lt.out = reinterpret_cast<uint8_t *>(b->d_poses.get()) + offsetof(PoseConst, lights), lt.stride = (uint32_t)sizeof(PoseConst), lt.fallback = 0u;
   return queue_pipeline(b, n_players, kinds_mask, st, nullptr, d_object_offsets != nullptr, profiled, ev, done, [&] {
     if (rdoom_status rs = launch_player_frames(st, a)) return rs;
     return launch_light_tables(st, lt);
@@ -929,28 +893,20 @@ static rdoom_status set_decor_things_impl(rdoom_level *lv, uint32_t slot, const 
   const size_t total = (size_t)lv->slices.back().first_tri + lv->slices.back().ntri;  // triangles of the set
   HIP_TRY(hipSetDevice(lv->device));
   if (!lv->d_tri_thing && total) {
-    uint32_t *p = nullptr;
-    HIP_TRY(hipMalloc((void **)&p, sizeof(uint32_t) * total));
-    const hipError_t e = hipMemset(p, 0xFF, sizeof(uint32_t) * total);  // levels without a table: nothing is ever hidden
-    if (e != hipSuccess) {
-      (void)hipFree(p);
-      HIP_TRY(e);
-    }
-    lv->d_tri_thing = p;
-    lv->view.tri_thing = p;
+    DeviceArray<uint32_t> words;  // (the level's only once they are filled)
+    if (rdoom_status rs = words.alloc(total)) return rs;
+    HIP_TRY(hipMemset(words.get(), 0xFF, sizeof(uint32_t) * total));  // levels without a table: nothing is ever hidden
+    lv->d_tri_thing = std::move(words);
+    lv->view.tri_thing = lv->d_tri_thing.get();
   }
   if (!table.empty())
-    HIP_TRY(hipMemcpy(lv->d_tri_thing + lv->slices[slot].first_tri, table.data(), sizeof(uint32_t) * table.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(lv->d_tri_thing.get() + lv->slices[slot].first_tri, table.data(), sizeof(uint32_t) * table.size(), hipMemcpyHostToDevice));
   lv->things_attached[slot] = 1;
   return RDOOM_OK;
 }
 
 rdoom_status rdoom_level_set_decor_things(rdoom_level *level, uint32_t slot, const uint32_t *thing_of_quad, uint32_t n_quads) {
-  try {
-    return set_decor_things_impl(level, slot, thing_of_quad, n_quads);
-  } catch (const std::bad_alloc &) {
-    return rdoom::fail(RDOOM_OOM, "out of host memory");
-  }
+  return rdoom::guarded([&] { return set_decor_things_impl(level, slot, thing_of_quad, n_quads); });
 }
 
 rdoom_status rdoom_batch_set_hidden_things(rdoom_batch *b, const uint32_t *d_hidden, uint32_t stride) {
@@ -983,12 +939,12 @@ rdoom_status rdoom_batch_path_stats(rdoom_batch *b, rdoom_path_stats *out) {
   const uint32_t n = b->last_n, T = b->n_tiles;
   out->poses = n;
   if (n == 0) return RDOOM_OK;
-  try {
+  return rdoom::guarded([&]() -> rdoom_status {
     std::vector<uint32_t> over(n), qtab((size_t)n * T * 4u);
     std::vector<uint2> hdr((size_t)n * T);
-    HIP_TRY(read_back(b, over.data(), b->d_overflow, sizeof(uint32_t) * n));
-    HIP_TRY(read_back(b, hdr.data(), b->d_tile_hdr, sizeof(uint2) * hdr.size()));
-    HIP_TRY(read_back(b, qtab.data(), b->d_qtab, sizeof(uint32_t) * qtab.size()));
+    HIP_TRY(read_back(b, over.data(), b->d_overflow.get(), sizeof(uint32_t) * n));
+    HIP_TRY(read_back(b, hdr.data(), b->d_tile_hdr.get(), sizeof(uint2) * hdr.size()));
+    HIP_TRY(read_back(b, qtab.data(), b->d_qtab.get(), sizeof(uint32_t) * qtab.size()));
     const uint32_t tiles_x = (b->width + TILE_W - 1) / TILE_W;
     for (uint32_t p = 0; p < n; p++) {
       const bool binned = over[p] == 0u;
@@ -1012,18 +968,16 @@ rdoom_status rdoom_batch_path_stats(rdoom_batch *b, rdoom_path_stats *out) {
     out->masked_fast_replays = b->last_masked_census[2], out->masked_general_bodies = b->last_masked_census[3];
     if (b->last_frag_count) {  // (rendered under the hook frag_count; zero otherwise)
       uint32_t fc[3];
-      HIP_TRY(read_back(b, fc, static_cast<const char *>(b->d_frag_const) + fragment_counts_offset(), sizeof fc));
+      HIP_TRY(read_back(b, fc, b->d_frag_const.get() + fragment_counts_offset(), sizeof fc));
       out->half_runs = fc[0], out->half_fallbacks = fc[1], out->listed_quads = fc[2];
     }
-  } catch (const std::bad_alloc &) {
-    return rdoom::fail(RDOOM_OOM, "out of host memory");
-  }
-  return RDOOM_OK;
+    return RDOOM_OK;
+  });
 }
 
 rdoom_status rdoom_batch_framebuffer_device(const rdoom_batch *batch, uint8_t **out_device_ptr) {
   if (!batch || !out_device_ptr) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
-  *out_device_ptr = batch->d_fb;
+  *out_device_ptr = batch->d_fb.get();
   return RDOOM_OK;
 }
 
@@ -1039,17 +993,14 @@ rdoom_status rdoom_batch_read_framebuffer(rdoom_batch *b, uint32_t first, uint32
   const size_t frame = (size_t)b->pitch * b->height;
   HIP_TRY(bind_device(b));
   if (rdoom_status fs = device_flags(b)) return fs;
-  if (count) HIP_TRY(read_back(b, host_out, b->d_fb + frame * first, b->width, (size_t)b->height * count, b->pitch));
+  if (count) HIP_TRY(read_back(b, host_out, b->d_fb.get() + frame * first, b->width, (size_t)b->height * count, b->pitch));
   return RDOOM_OK;
 }
 
 rdoom_status rdoom_batch_enable_primitive_ids(rdoom_batch *b) {
   if (!b) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   HIP_TRY(bind_device(b));  // the ids live next to the batch's other scratch, on the level's device
-  if (!b->d_prim) {
-    const size_t npx = (size_t)b->pitch * b->height * b->max_poses;
-    HIP_TRY(hipMalloc((void **)&b->d_prim, sizeof(uint32_t) * npx));
-  }
+  if (rdoom_status rs = b->d_prim.alloc((size_t)b->pitch * b->height * b->max_poses)) return rs;  // (once)
   b->want_prim = true;
   b->last_n = 0;  // nothing captured yet: render first
   return RDOOM_OK;
@@ -1066,7 +1017,7 @@ rdoom_status rdoom_batch_read_primitive_ids(rdoom_batch *b, uint32_t first, uint
   HIP_TRY(read_back(b, &level_word, b->d_fix_count + 3, sizeof level_word));
   if (rdoom_status rs = level_error(b, level_word)) return rs;
   if (count)
-    HIP_TRY(read_back(b, host_out, b->d_prim + frame * first, sizeof(uint32_t) * b->width, (size_t)b->height * count, sizeof(uint32_t) * b->pitch));
+    HIP_TRY(read_back(b, host_out, b->d_prim.get() + frame * first, sizeof(uint32_t) * b->width, (size_t)b->height * count, sizeof(uint32_t) * b->pitch));
   return RDOOM_OK;
 }
 
@@ -1083,7 +1034,7 @@ static rdoom_status playpal_check(const rdoom_batch *b, uint32_t first, uint32_t
       return rdoom::fail(RDOOM_BAD_ARG, "level %u of the set was created without a playpal, and the last render's levels are on the device",
                          (uint32_t)(std::find(lv->has_palette.begin(), lv->has_palette.end(), 0) - lv->has_palette.begin()));
     // the levels of the last render's poses: its pinned staging (the next render writes the other one)
-    const PoseConst *pc = b->h_poses[(b->stage + rdoom_batch::STAGES - 1u) % rdoom_batch::STAGES];
+    const PoseConst *pc = b->h_poses[(b->stage + rdoom_batch::STAGES - 1u) % rdoom_batch::STAGES].get();
     for (uint32_t p = first; p < first + count; p++)
       if (!lv->has_palette[pc[p].level]) return rdoom::fail(RDOOM_BAD_ARG, "pose %u: its level %u was created without a playpal", p, pc[p].level);
   }
@@ -1121,9 +1072,8 @@ static rdoom_status device_out_check(const rdoom_batch *b, const void *device_ou
 // the batch's bounded staging buffer of the synchronous read functions: at least `bytes` of device memory
 static rdoom_status staging(rdoom_batch *b, size_t bytes) {
   if (b->rgb_bytes < bytes) {
-    if (b->d_rgb) HIP_TRY(hipFree(b->d_rgb));
-    b->d_rgb = nullptr, b->rgb_bytes = 0;
-    HIP_TRY(hipMalloc((void **)&b->d_rgb, bytes));
+    b->d_rgb.reset(), b->rgb_bytes = 0;
+    if (rdoom_status rs = b->d_rgb.alloc(bytes)) return rs;
     b->rgb_bytes = bytes;
   }
   return RDOOM_OK;
@@ -1131,14 +1081,14 @@ static rdoom_status staging(rdoom_batch *b, size_t bytes) {
 
 // queues the two resolve kernels on st behind the last render; ev_done then marks their end (finish / read_* wait for it)
 static rdoom_status resolve_impl(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint8_t *out, hipStream_t st) {
-  HIP_TRY(hipStreamWaitEvent(st, b->ev_done, 0));
+  HIP_TRY(hipStreamWaitEvent(st, b->ev_done.get(), 0));
   ResolveArgs a{};
-  a.fb = b->d_fb, a.vis = b->d_vis, a.vis16 = b->vis16, a.qtab = b->d_qtab, a.use_qtab = b->last_skip_vis, a.poses = b->d_poses;
-  a.palettes = b->level->d_palettes, a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list, a.fix_cap = b->fix_cap;
+  a.fb = b->d_fb.get(), a.vis = b->d_vis.get(), a.vis16 = b->vis16, a.qtab = b->d_qtab.get(), a.use_qtab = b->last_skip_vis, a.poses = b->d_poses.get();
+  a.palettes = b->level->d_palettes.get(), a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list.get(), a.fix_cap = b->fix_cap;
   a.first = first, a.count = count, a.width = (int)b->width, a.pitch = (int)b->pitch, a.height = (int)b->height;
   a.bpp = format & 0xFFu, a.top_down = (format & RDOOM_RGB_TOP_DOWN) != 0u, a.out = out;
   const rdoom_status rs = launch_resolve(st, a);
-  HIP_TRY(hipEventRecord(b->ev_done, st));  // (also after a failed launch: nothing waits for a render that is not the last)
+  HIP_TRY(hipEventRecord(b->ev_done.get(), st));  // (also after a failed launch: nothing waits for a render that is not the last)
   return rs;
 }
 
@@ -1159,9 +1109,9 @@ rdoom_status rdoom_batch_read_rgb(rdoom_batch *b, uint32_t first, uint32_t count
   if (rdoom_status rs = staging(b, chunk * frame)) return rs;
   for (uint32_t f = first; f < first + count; f += chunk) {
     const uint32_t n = std::min(chunk, first + count - f);
-    if (rdoom_status rs = resolve_impl(b, f, n, format, b->d_rgb, b->copy_stream)) return rs;
-    HIP_TRY(hipMemcpyAsync(host_out + (size_t)(f - first) * frame, b->d_rgb, n * frame, hipMemcpyDeviceToHost, b->copy_stream));
-    HIP_TRY(hipStreamSynchronize(b->copy_stream));
+    if (rdoom_status rs = resolve_impl(b, f, n, format, b->d_rgb.get(), b->copy_stream.get())) return rs;
+    HIP_TRY(hipMemcpyAsync(host_out + (size_t)(f - first) * frame, b->d_rgb.get(), n * frame, hipMemcpyDeviceToHost, b->copy_stream.get()));
+    HIP_TRY(hipStreamSynchronize(b->copy_stream.get()));
   }
   return RDOOM_OK;
 }
@@ -1182,15 +1132,15 @@ static rdoom_status plane_args(const rdoom_batch *b, uint32_t first, uint32_t co
 
 // queues the two plane kernels on st behind the last render; ev_done then marks their end, as resolve_impl
 static rdoom_status plane_impl(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t plane, void *out, hipStream_t st) {
-  HIP_TRY(hipStreamWaitEvent(st, b->ev_done, 0));
+  HIP_TRY(hipStreamWaitEvent(st, b->ev_done.get(), 0));
   PlaneArgs a{};
-  a.vis = b->d_vis, a.vis16 = b->vis16, a.qtab = b->d_qtab, a.use_qtab = b->last_skip_vis, a.poses = b->d_poses;
-  a.recs = b->d_recs, a.cap = b->cap, a.tris = b->level->view.tris, a.slices = b->level->view.slices;
-  a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list, a.fix_cap = b->fix_cap;
+  a.vis = b->d_vis.get(), a.vis16 = b->vis16, a.qtab = b->d_qtab.get(), a.use_qtab = b->last_skip_vis, a.poses = b->d_poses.get();
+  a.recs = b->d_recs.get(), a.cap = b->cap, a.tris = b->level->view.tris, a.slices = b->level->view.slices;
+  a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list.get(), a.fix_cap = b->fix_cap;
   a.first = first, a.count = count, a.width = (int)b->width, a.pitch = (int)b->pitch, a.height = (int)b->height;
   a.plane = plane & 0xFFu, a.top_down = (plane & RDOOM_RGB_TOP_DOWN) != 0u, a.out = out;
   const rdoom_status rs = launch_plane(st, a);
-  HIP_TRY(hipEventRecord(b->ev_done, st));
+  HIP_TRY(hipEventRecord(b->ev_done.get(), st));
   return rs;
 }
 
@@ -1211,9 +1161,9 @@ rdoom_status rdoom_batch_read_plane(rdoom_batch *b, uint32_t first, uint32_t cou
   if (rdoom_status rs = staging(b, chunk * frame)) return rs;
   for (uint32_t f = first; f < first + count; f += chunk) {
     const uint32_t n = std::min(chunk, first + count - f);
-    if (rdoom_status rs = plane_impl(b, f, n, plane, b->d_rgb, b->copy_stream)) return rs;
-    HIP_TRY(hipMemcpyAsync((uint8_t *)host_out + (size_t)(f - first) * frame, b->d_rgb, n * frame, hipMemcpyDeviceToHost, b->copy_stream));
-    HIP_TRY(hipStreamSynchronize(b->copy_stream));
+    if (rdoom_status rs = plane_impl(b, f, n, plane, b->d_rgb.get(), b->copy_stream.get())) return rs;
+    HIP_TRY(hipMemcpyAsync((uint8_t *)host_out + (size_t)(f - first) * frame, b->d_rgb.get(), n * frame, hipMemcpyDeviceToHost, b->copy_stream.get()));
+    HIP_TRY(hipStreamSynchronize(b->copy_stream.get()));
   }
   return RDOOM_OK;
 }
@@ -1244,15 +1194,15 @@ static size_t observation_frame_bytes(const rdoom_batch *b, uint32_t format, uin
 // queues the two observation kernels on st behind the last render; ev_done then marks their end, as resolve_impl
 static rdoom_status observation_impl(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint32_t fx, uint32_t fy, void *out,
                                      hipStream_t st) {
-  HIP_TRY(hipStreamWaitEvent(st, b->ev_done, 0));
+  HIP_TRY(hipStreamWaitEvent(st, b->ev_done.get(), 0));
   ObserveArgs a{};
-  a.fb = b->d_fb, a.vis = b->d_vis, a.vis16 = b->vis16, a.qtab = b->d_qtab, a.use_qtab = b->last_skip_vis, a.poses = b->d_poses;
-  a.palettes = b->level->d_palettes, a.recs = b->d_recs, a.cap = b->cap;
-  a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list, a.fix_cap = b->fix_cap;
+  a.fb = b->d_fb.get(), a.vis = b->d_vis.get(), a.vis16 = b->vis16, a.qtab = b->d_qtab.get(), a.use_qtab = b->last_skip_vis, a.poses = b->d_poses.get();
+  a.palettes = b->level->d_palettes.get(), a.recs = b->d_recs.get(), a.cap = b->cap;
+  a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list.get(), a.fix_cap = b->fix_cap;
   a.first = first, a.count = count, a.width = (int)b->width, a.pitch = (int)b->pitch, a.height = (int)b->height;
   a.format = format & 0xFFu, a.fx = fx, a.fy = fy, a.top_down = (format & RDOOM_RGB_TOP_DOWN) != 0u, a.out = out;
   const rdoom_status rs = launch_observe(st, a);
-  HIP_TRY(hipEventRecord(b->ev_done, st));
+  HIP_TRY(hipEventRecord(b->ev_done.get(), st));
   return rs;
 }
 
@@ -1275,9 +1225,9 @@ rdoom_status rdoom_batch_read_observation(rdoom_batch *b, uint32_t first, uint32
   if (rdoom_status rs = staging(b, chunk * frame)) return rs;
   for (uint32_t f = first; f < first + count; f += chunk) {
     const uint32_t n = std::min(chunk, first + count - f);
-    if (rdoom_status rs = observation_impl(b, f, n, format, fx, fy, b->d_rgb, b->copy_stream)) return rs;
-    HIP_TRY(hipMemcpyAsync((uint8_t *)host_out + (size_t)(f - first) * frame, b->d_rgb, n * frame, hipMemcpyDeviceToHost, b->copy_stream));
-    HIP_TRY(hipStreamSynchronize(b->copy_stream));
+    if (rdoom_status rs = observation_impl(b, f, n, format, fx, fy, b->d_rgb.get(), b->copy_stream.get())) return rs;
+    HIP_TRY(hipMemcpyAsync((uint8_t *)host_out + (size_t)(f - first) * frame, b->d_rgb.get(), n * frame, hipMemcpyDeviceToHost, b->copy_stream.get()));
+    HIP_TRY(hipStreamSynchronize(b->copy_stream.get()));
   }
   return RDOOM_OK;
 }

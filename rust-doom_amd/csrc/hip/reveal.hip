@@ -141,7 +141,7 @@ rdoom_status reveal_args(const rdoom::MapSource &src, const char *noun, const rd
   if (rdoom_status s = rdoom::check_offsets(d_offsets, n_objects, src.game_objects, noun)) return s;
   if (n > 0x7FFFFFFFu) return rdoom::fail(RDOOM_BAD_ARG, "%u players: too many for one launch", n);
   const rdoom::MapDevice &d = *src.map;
-  a = RevealArgs{d_states, d_offsets, d_dirs, d_seen, d_new_out, {d.seg, d.heights, d.ids, d.flags}, n_objects, n_rays, stride, max_range};
+  a = RevealArgs{d_states, d_offsets, d_dirs, d_seen, d_new_out, {d.seg.get(), d.heights.get(), d.ids.get(), d.flags.get()}, n_objects, n_rays, stride, max_range};
   return RDOOM_OK;
 }
 
@@ -173,7 +173,7 @@ rdoom_status rdoom_worldset_reveal_lines(const rdoom_worldset *set, const rdoom_
     return s;
   if (rdoom_status s = rdoom::check_device(&src, "the world set")) return s;
   if (!n) return RDOOM_OK;
-  return rdoom::launch_checked(worldset_reveal_lines_kernel, dim3(n), dim3(THREADS), 0, stream, a, (const uint2 *)src.map->levels, d_levels,
+  return rdoom::launch_checked(worldset_reveal_lines_kernel, dim3(n), dim3(THREADS), 0, stream, a, (const uint2 *)src.map->levels.get(), d_levels,
                                src.map->n_levels);
 }
 

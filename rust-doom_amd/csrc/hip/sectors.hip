@@ -190,7 +190,7 @@ __global__ __launch_bounds__(THREADS) void worldset_draw_sector_maps_kernel(Sect
   draw_tile(a, p, blockIdx.x % a.tiles, lv, slot < n_levels);
 }
 
-SectorTables tables(const rdoom::SectorDevice &d) { return SectorTables{d.nodes, d.leaves, d.edges, d.sectors}; }
+SectorTables tables(const rdoom::SectorDevice &d) { return SectorTables{d.nodes.get(), d.leaves.get(), d.edges.get(), d.sectors.get()}; }
 
 // what both calls check of the game's offsets and of the rows of visited bits.  noun: "world" or "world set"
 rdoom_status check_rows(const rdoom::MapSource &src, const char *noun, const float *d_offsets, uint32_t n_objects, const uint32_t *d_visited,
@@ -268,18 +268,13 @@ rdoom_status sector_upload(const std::vector<const game::World *> &levels, Secto
       sectors.push_back(make_float4(s.floor, s.ceiling, floor_id, ceiling_id));
     }
   }
-  if (rdoom_status s = upload(&out.nodes, nodes)) return s;
-  if (rdoom_status s = upload(&out.leaves, leaves)) return s;
-  if (rdoom_status s = upload(&out.edges, edges)) return s;
-  if (rdoom_status s = upload(&out.sectors, sectors)) return s;
-  if (rdoom_status s = upload(&out.levels, slots)) return s;
+  if (rdoom_status s = out.nodes.upload(nodes, EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = out.leaves.upload(leaves, EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = out.edges.upload(edges, EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = out.sectors.upload(sectors, EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = out.levels.upload(slots, EMPTY_TABLE_BYTES)) return s;
   out.n_levels = (uint32_t)slots.size();
   return RDOOM_OK;
-}
-
-void sector_free(SectorDevice &d) {
-  free_all({d.nodes, d.leaves, d.edges, d.sectors, d.levels});
-  d = SectorDevice{};
 }
 
 }  // namespace rdoom
@@ -313,7 +308,7 @@ rdoom_status rdoom_worldset_locate_players(const rdoom_worldset *set, const rdoo
   if (rdoom_status s = rdoom::check_device(&src, "the world set")) return s;
   if (!n) return RDOOM_OK;
   return rdoom::launch_checked(worldset_locate_players_kernel, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), 0, stream, a,
-                               (const uint4 *)src.sectors->levels, d_levels, src.sectors->n_levels);
+                               (const uint4 *)src.sectors->levels.get(), d_levels, src.sectors->n_levels);
 }
 
 rdoom_status rdoom_world_draw_sector_maps(const rdoom_world *w, const rdoom_player_state *d_states, uint32_t n, const float *d_object_offsets,
@@ -342,7 +337,7 @@ rdoom_status rdoom_worldset_draw_sector_maps(const rdoom_worldset *set, const rd
   if (rdoom_status s = rdoom::check_device(&src, "the world set")) return s;
   if (!n) return RDOOM_OK;
   return rdoom::launch_checked(worldset_draw_sector_maps_kernel, dim3(n * a.tiles), dim3(THREADS), 0, stream, a,
-                               (const uint4 *)src.sectors->levels, d_levels, src.sectors->n_levels);
+                               (const uint4 *)src.sectors->levels.get(), d_levels, src.sectors->n_levels);
 }
 
 }  // extern "C"

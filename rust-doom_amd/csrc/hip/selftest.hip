@@ -17,6 +17,7 @@
 #include <cstdint>
 
 #include "../common.hpp"
+#include "device_memory.hpp"
 #include "fastmath.hpp"
 #include "sincos_rd.hpp"
 
@@ -173,37 +174,29 @@ extern "C" rdoom_status rdoom_selftest_sincos(uint64_t out_sums[512], uint32_t r
   if (!out_sums) return rdoom::fail(RDOOM_BAD_ARG, "out_sums is null");
   if (device_raw && raw_binade >= kBinades) return rdoom::fail(RDOOM_BAD_ARG, "raw_binade %u is not below 512", raw_binade);
   if (device_raw && ((uintptr_t)device_raw & 7u)) return rdoom::fail(RDOOM_BAD_ARG, "device_raw is not aligned to 8 bytes");
-  unsigned long long *d = nullptr;
-  hipError_t e = hipMalloc((void **)&d, kBinades * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemset(d, 0, kBinades * sizeof(unsigned long long));
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(sweep_sincos, dim3(kBinades * kSincosBlocksPerBinade), dim3(kSincosThreads), 0, nullptr, d, raw_binade,
-                       (float2 *)device_raw);
-    e = hipGetLastError();
-  }
+  rdoom::DeviceArray<unsigned long long> d;
+  if (rdoom_status s = d.alloc(kBinades)) return s;
+  HIP_TRY(hipMemset(d.get(), 0, kBinades * sizeof(unsigned long long)));
+  hipLaunchKernelGGL(sweep_sincos, dim3(kBinades * kSincosBlocksPerBinade), dim3(kSincosThreads), 0, nullptr, d.get(), raw_binade,
+                     (float2 *)device_raw);
+  HIP_TRY(hipGetLastError());
   static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "the sums are copied as they are");
-  if (e == hipSuccess) e = hipMemcpy(out_sums, d, kBinades * sizeof(uint64_t), hipMemcpyDeviceToHost);
-  if (d) (void)hipFree(d);
-  if (e != hipSuccess) return rdoom::fail(RDOOM_HIP_ERROR, "sincos selftest failed: %s", hipGetErrorString(e));
+  HIP_TRY(hipMemcpy(out_sums, d.get(), kBinades * sizeof(uint64_t), hipMemcpyDeviceToHost));
   return RDOOM_OK;
 }
 
 extern "C" rdoom_status rdoom_selftest_fastmath(uint64_t out_counts[8]) {
   if (!out_counts) return rdoom::fail(RDOOM_BAD_ARG, "out_counts is null");
-  unsigned long long *d = nullptr;
-  hipError_t e = hipMalloc((void **)&d, 8 * sizeof(unsigned long long));
-  if (e == hipSuccess) e = hipMemset(d, 0, 8 * sizeof(unsigned long long));
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(sweep_div, dim3(4096), dim3(256), 0, nullptr, d);
-    hipLaunchKernelGGL(sweep_mod, dim3(4096), dim3(256), 0, nullptr, d);
-    hipLaunchKernelGGL(sweep_packed, dim3(1024), dim3(256), 0, nullptr, d);
-    hipLaunchKernelGGL(sweep_tile_index, dim3(256), dim3(256), 0, nullptr, d);
-    e = hipGetLastError();
-  }
+  rdoom::DeviceArray<unsigned long long> d;
+  if (rdoom_status s = d.alloc(8)) return s;
+  HIP_TRY(hipMemset(d.get(), 0, 8 * sizeof(unsigned long long)));
+  hipLaunchKernelGGL(sweep_div, dim3(4096), dim3(256), 0, nullptr, d.get());
+  hipLaunchKernelGGL(sweep_mod, dim3(4096), dim3(256), 0, nullptr, d.get());
+  hipLaunchKernelGGL(sweep_packed, dim3(1024), dim3(256), 0, nullptr, d.get());
+  hipLaunchKernelGGL(sweep_tile_index, dim3(256), dim3(256), 0, nullptr, d.get());
+  HIP_TRY(hipGetLastError());
   unsigned long long h[8] = {};
-  if (e == hipSuccess) e = hipMemcpy(h, d, sizeof h, hipMemcpyDeviceToHost);
-  if (d) (void)hipFree(d);
-  if (e != hipSuccess) return rdoom::fail(RDOOM_HIP_ERROR, "selftest failed: %s", hipGetErrorString(e));
+  HIP_TRY(hipMemcpy(h, d.get(), sizeof h, hipMemcpyDeviceToHost));
   for (int i = 0; i < 8; i++) out_counts[i] = h[i];
   return RDOOM_OK;
 }

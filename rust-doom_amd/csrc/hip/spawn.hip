@@ -166,7 +166,8 @@ rdoom_status spawn_args(const rdoom::MapSource &src, const char *noun, rdoom_pla
   if (rdoom_status s = rdoom::check_offsets(d_offsets, n_objects, src.game_objects, noun)) return s;
   const rdoom::SectorDevice &sd = *src.sectors;
   const rdoom::SpawnDevice &pd = *src.spawn;
-  a = SpawnArgs{d_states, d_offsets, d_mask, d_episode, d_tries_out, sd.nodes, sd.edges, sd.sectors, sd.leaves, pd.cumulative, pd.corners,
+  a = SpawnArgs{d_states, d_offsets, d_mask, d_episode, d_tries_out, sd.nodes.get(), sd.edges.get(), sd.sectors.get(), sd.leaves.get(), pd.cumulative.get(),
+                pd.corners.get(),
                 n, n_objects, (uint32_t)(seed & 0xFFFFFFFFull), (uint32_t)(seed >> 32), params->margin, params->clearance, params->max_step,
                 params->flags};
   return RDOOM_OK;
@@ -189,18 +190,13 @@ rdoom_status spawn_upload(const std::vector<const game::World *> &levels, SpawnD
       for (const float *v : {e.a, e.b, e.c}) corners.push_back(make_float4(v[0], v[1], v[2], 0.0f));
     }
   }
-  if (rdoom_status s = upload(&out.cumulative, cumulative)) return s;
-  if (rdoom_status s = upload(&out.corners, corners)) return s;
-  if (rdoom_status s = upload(&out.levels, slots)) return s;
-  if (rdoom_status s = upload(&out.starts, starts)) return s;
+  if (rdoom_status s = out.cumulative.upload(cumulative, EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = out.corners.upload(corners, EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = out.levels.upload(slots, EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = out.starts.upload(starts, EMPTY_TABLE_BYTES)) return s;
   out.n_levels = (uint32_t)slots.size();
   if (!slots.empty()) out.level0 = slots[0], out.start0 = starts[0];
   return RDOOM_OK;
-}
-
-void spawn_free(SpawnDevice &d) {
-  free_all({d.cumulative, d.corners, d.levels, d.starts});
-  d = SpawnDevice{};
 }
 
 }  // namespace rdoom
@@ -234,7 +230,7 @@ rdoom_status rdoom_worldset_spawn_players(const rdoom_worldset *set, rdoom_playe
   if (rdoom_status s = rdoom::check_device(&src, "the world set")) return s;
   if (!n) return RDOOM_OK;
   return rdoom::launch_checked(worldset_spawn_players_kernel, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), 0, stream, a,
-                               (const uint4 *)src.sectors->levels, (const uint4 *)src.spawn->levels, (const float4 *)src.spawn->starts, d_levels,
+                               (const uint4 *)src.sectors->levels.get(), (const uint4 *)src.spawn->levels.get(), (const float4 *)src.spawn->starts.get(), d_levels,
                                src.spawn->n_levels);
 }
 

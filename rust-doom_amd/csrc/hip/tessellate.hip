@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../host/game_level.hpp"
+#include "device_memory.hpp"
 
 #pragma clang fp contract(off)
 
@@ -299,18 +300,13 @@ __global__ __launch_bounds__(64) void seg_quads_kernel(const SegInput *__restric
   outputs[i] = g;
 }
 
-struct DevBuf {
-  void *p = nullptr;
-  ~DevBuf() {
-    if (p) (void)hipFree(p);
-  }
-  hipError_t alloc_copy(const void *src, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    hipError_t e = hipMalloc(&p, bytes);
-    if (e == hipSuccess && src) e = hipMemcpy(p, src, bytes, hipMemcpyHostToDevice);
-    return e;
-  }
-};
+// a failed runtime call of the host code below, as the loader reports its errors (the boundary of the C ABI turns it into a status)
+void check(hipError_t e, const char *what) {
+  if (e != hipSuccess) throw rdoom::wad::WadError(RDOOM_HIP_ERROR, std::string(what) + hipGetErrorString(e));
+}
+void check(rdoom_status s, const char *what) {
+  if (s != RDOOM_OK) throw rdoom::wad::WadError(RDOOM_HIP_ERROR, what + rdoom::last_error_ref());
+}
 
 }  // namespace
 
@@ -346,26 +342,27 @@ std::vector<std::vector<wad::Pnt2f>> tessellate_on_device(const wad::Level &leve
   }
   std::vector<std::vector<wad::Pnt2f>> polygons(level.subsectors.size());
   if (descs.empty()) return polygons;
-  DevBuf d_desc, d_lines, d_points, d_out, d_n, d_over;
-  hipError_t e = d_desc.alloc_copy(descs.data(), descs.size() * sizeof(LeafDesc));
-  if (e == hipSuccess) e = d_lines.alloc_copy(lines.data(), lines.size() * sizeof(float4));
-  if (e == hipSuccess) e = d_points.alloc_copy(points.data(), points.size() * sizeof(float2));
-  if (e == hipSuccess) e = d_out.alloc_copy(nullptr, descs.size() * MAX_POINTS * sizeof(float2));
-  if (e == hipSuccess) e = d_n.alloc_copy(nullptr, descs.size() * sizeof(uint32_t));
+  rdoom::DeviceArray<LeafDesc> d_desc;
+  rdoom::DeviceArray<float4> d_lines;
+  rdoom::DeviceArray<float2> d_points, d_out;
+  rdoom::DeviceArray<uint32_t> d_n, d_over;
+  const char *what = "tessellate: ";
+  check(d_desc.upload(descs), what);
+  check(d_lines.upload(lines, rdoom::EMPTY_TABLE_BYTES), what);
+  check(d_points.upload(points, rdoom::EMPTY_TABLE_BYTES), what);
+  check(d_out.alloc(descs.size() * MAX_POINTS), what);
+  check(d_n.alloc(descs.size()), what);
   const uint32_t zero = 0;
-  if (e == hipSuccess) e = d_over.alloc_copy(&zero, sizeof zero);
-  if (e != hipSuccess) throw WadError(RDOOM_HIP_ERROR, std::string("tessellate: ") + hipGetErrorString(e));
-  hipLaunchKernelGGL(subsector_polygon_kernel, dim3((uint32_t)descs.size()), dim3(64), 0, 0,
-                     (const LeafDesc *)d_desc.p, (const float4 *)d_lines.p, (const float2 *)d_points.p,
-                     (float2 *)d_out.p, (uint32_t *)d_n.p, (uint32_t *)d_over.p);
+  check(d_over.upload(&zero, 1), what);
+  hipLaunchKernelGGL(subsector_polygon_kernel, dim3((uint32_t)descs.size()), dim3(64), 0, 0, (const LeafDesc *)d_desc.get(),
+                     (const float4 *)d_lines.get(), (const float2 *)d_points.get(), d_out.get(), d_n.get(), d_over.get());
   std::vector<uint32_t> counts(descs.size());
   std::vector<float2> out(descs.size() * MAX_POINTS);
   uint32_t over = 0;
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(counts.data(), d_n.p, counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(out.data(), d_out.p, out.size() * sizeof(float2), hipMemcpyDeviceToHost);
-  if (e == hipSuccess) e = hipMemcpy(&over, d_over.p, sizeof over, hipMemcpyDeviceToHost);
-  if (e != hipSuccess) throw WadError(RDOOM_HIP_ERROR, std::string("tessellate: ") + hipGetErrorString(e));
+  check(hipGetLastError(), what);
+  check(hipMemcpy(counts.data(), d_n.get(), counts.size() * sizeof(uint32_t), hipMemcpyDeviceToHost), what);
+  check(hipMemcpy(out.data(), d_out.get(), out.size() * sizeof(float2), hipMemcpyDeviceToHost), what);
+  check(hipMemcpy(&over, d_over.get(), sizeof over, hipMemcpyDeviceToHost), what);
   if (over) throw WadError(RDOOM_BAD_LEVEL, "tessellate: sub-sector with more than 512 candidate points");
   for (size_t i = 0; i < leaves.size(); i++) {
     auto &poly = polygons[leaves[i].subsector];
@@ -377,19 +374,17 @@ std::vector<std::vector<wad::Pnt2f>> tessellate_on_device(const wad::Level &leve
 
 // SEG -> wall quads on the device: one lane per recorded seg (see seg_quads_kernel)
 std::vector<wad::SegGeometry> tessellate_segs_on_device(const std::vector<wad::SegInput> &inputs) {
-  using wad::WadError;
   std::vector<wad::SegGeometry> out(inputs.size());
   if (inputs.empty()) return out;
-  DevBuf d_in, d_out;
-  hipError_t e = d_in.alloc_copy(inputs.data(), inputs.size() * sizeof(wad::SegInput));
-  if (e == hipSuccess) e = d_out.alloc_copy(nullptr, out.size() * sizeof(wad::SegGeometry));
-  if (e != hipSuccess) throw WadError(RDOOM_HIP_ERROR, std::string("tessellate segs: ") + hipGetErrorString(e));
+  rdoom::DeviceArray<wad::SegInput> d_in;
+  rdoom::DeviceArray<wad::SegGeometry> d_out;
+  const char *what = "tessellate segs: ";
+  check(d_in.upload(inputs), what);
+  check(d_out.alloc(out.size()), what);
   const uint32_t n = (uint32_t)inputs.size();
-  hipLaunchKernelGGL(seg_quads_kernel, dim3((n + 63u) / 64u), dim3(64), 0, 0, (const wad::SegInput *)d_in.p,
-                     (wad::SegGeometry *)d_out.p, n);
-  e = hipGetLastError();
-  if (e == hipSuccess) e = hipMemcpy(out.data(), d_out.p, out.size() * sizeof(wad::SegGeometry), hipMemcpyDeviceToHost);
-  if (e != hipSuccess) throw WadError(RDOOM_HIP_ERROR, std::string("tessellate segs: ") + hipGetErrorString(e));
+  hipLaunchKernelGGL(seg_quads_kernel, dim3((n + 63u) / 64u), dim3(64), 0, 0, (const wad::SegInput *)d_in.get(), d_out.get(), n);
+  check(hipGetLastError(), what);
+  check(hipMemcpy(out.data(), d_out.get(), out.size() * sizeof(wad::SegGeometry), hipMemcpyDeviceToHost), what);
   return out;
 }
 

@@ -22,7 +22,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <new>
+#include <memory>
 #include <vector>
 
 #include "../common.hpp"
@@ -34,9 +34,9 @@
 #pragma clang fp contract(off)
 
 struct rdoom_thingset {
-  rdoom_thing *d_things = nullptr;  // the levels' records, one level after the other
-  uint2 *d_levels = nullptr;        // a slot's (first record, number of records)
-  uint2 level0 = {};                // slot 0's, on the host: a single world's launch passes it by value
+  rdoom::DeviceArray<rdoom_thing> d_things;  // the levels' records, one level after the other
+  rdoom::DeviceArray<uint2> d_levels;        // a slot's (first record, number of records)
+  uint2 level0 = {};                         // slot 0's, on the host: a single world's launch passes it by value
   uint32_t n_levels = 0, words = 1, max_object_id = 0;
   int device = -1;
 };
@@ -249,13 +249,13 @@ rdoom_status sense_args(const rdoom::MapSource &src, const char *noun, const cha
   if (rdoom_status s = rdoom::check_offsets(d_offsets, n_objects, src.game_objects, noun)) return s;
   if (d_offsets && n_objects <= things->max_object_id)
     return rdoom::fail(RDOOM_BAD_ARG, "n_objects %u is not above the thing set's largest object_id %u", n_objects, things->max_object_id);
-  a = ThingSenseArgs{d_states,      d_offsets, things->d_things, d_collected,       d_visible_out,        d_touched_out,
+  a = ThingSenseArgs{d_states,      d_offsets, things->d_things.get(), d_collected,      d_visible_out,        d_touched_out,
                      d_nearest_out, d_new_out, n_objects,        stride,            params->max_range,    params->cos_half_fov,
                      params->touch_radius, params->touch_below, params->touch_above, params->collect_mask};
   return RDOOM_OK;
 }
 
-LineTable line_table(const rdoom::MapDevice &d) { return LineTable{d.seg, d.heights, d.ids, d.flags}; }
+LineTable line_table(const rdoom::MapDevice &d) { return LineTable{d.seg.get(), d.heights.get(), d.ids.get(), d.flags.get()}; }
 
 }  // namespace
 
@@ -265,47 +265,38 @@ rdoom_status rdoom_thingset_create(const rdoom_thing *const *things, const uint3
   if (!out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   *out = nullptr;
   if (!things || !counts || n_levels == 0) return rdoom::fail(RDOOM_BAD_ARG, "a thing set needs at least one level's table");
-  std::vector<rdoom_thing> all;
-  std::vector<uint2> levels;
-  uint32_t most = 0, max_object_id = 0;
-  for (uint32_t l = 0; l < n_levels; l++) {
-    if (counts[l] > MAX_THINGS) return rdoom::fail(RDOOM_BAD_ARG, "level %u has %u things (at most %u)", l, counts[l], MAX_THINGS);
-    if (counts[l] && !things[l]) return rdoom::fail(RDOOM_BAD_ARG, "level %u: %u things at a null pointer", l, counts[l]);
-    levels.push_back(make_uint2((uint32_t)all.size(), counts[l]));
-    most = counts[l] > most ? counts[l] : most;
-    for (uint32_t i = 0; i < counts[l]; i++) {
-      const rdoom_thing &t = things[l][i];
-      if ((t.category & 0xFFu) > RDOOM_THING_UNKNOWN || (t.category & ~(0xFFu | RDOOM_THING_HANGING)))
-        return rdoom::fail(RDOOM_BAD_ARG, "level %u, thing %u: category %#x", l, i, t.category);
-      if (!is_finite(t.x) || !is_finite(t.z) || !is_finite(t.base) || !is_finite(t.radius) || t.radius < 0.0f)
-        return rdoom::fail(RDOOM_BAD_ARG, "level %u, thing %u: x, z, base and radius must be finite and the radius >= 0", l, i);
-      max_object_id = t.object_id > max_object_id ? t.object_id : max_object_id;
-      all.push_back(t);
+  return rdoom::guarded([&]() -> rdoom_status {
+    std::vector<rdoom_thing> all;
+    std::vector<uint2> levels;
+    uint32_t most = 0, max_object_id = 0;
+    for (uint32_t l = 0; l < n_levels; l++) {
+      if (counts[l] > MAX_THINGS) return rdoom::fail(RDOOM_BAD_ARG, "level %u has %u things (at most %u)", l, counts[l], MAX_THINGS);
+      if (counts[l] && !things[l]) return rdoom::fail(RDOOM_BAD_ARG, "level %u: %u things at a null pointer", l, counts[l]);
+      levels.push_back(make_uint2((uint32_t)all.size(), counts[l]));
+      most = counts[l] > most ? counts[l] : most;
+      for (uint32_t i = 0; i < counts[l]; i++) {
+        const rdoom_thing &t = things[l][i];
+        if ((t.category & 0xFFu) > RDOOM_THING_UNKNOWN || (t.category & ~(0xFFu | RDOOM_THING_HANGING)))
+          return rdoom::fail(RDOOM_BAD_ARG, "level %u, thing %u: category %#x", l, i, t.category);
+        if (!is_finite(t.x) || !is_finite(t.z) || !is_finite(t.base) || !is_finite(t.radius) || t.radius < 0.0f)
+          return rdoom::fail(RDOOM_BAD_ARG, "level %u, thing %u: x, z, base and radius must be finite and the radius >= 0", l, i);
+        max_object_id = t.object_id > max_object_id ? t.object_id : max_object_id;
+        all.push_back(t);
+      }
     }
-  }
-  if (all.size() > 0x7FFFFFFFu) return rdoom::fail(RDOOM_BAD_ARG, "%zu things in all: too many for one set", all.size());
-  rdoom_thingset *set = new (std::nothrow) rdoom_thingset();
-  if (!set) return rdoom::fail(RDOOM_OOM, "out of host memory");
-  const rdoom_status s = [&]() -> rdoom_status {
+    if (all.size() > 0x7FFFFFFFu) return rdoom::fail(RDOOM_BAD_ARG, "%zu things in all: too many for one set", all.size());
+    auto set = std::make_unique<rdoom_thingset>();
     HIP_TRY(hipGetDevice(&set->device));
-    if (rdoom_status u = rdoom::upload(&set->d_things, all)) return u;
-    return rdoom::upload(&set->d_levels, levels);
-  }();
-  if (s != RDOOM_OK) {
-    rdoom_thingset_destroy(set);
-    return s;
-  }
-  set->level0 = levels[0], set->n_levels = n_levels, set->max_object_id = max_object_id;
-  set->words = most ? (most + 31u) / 32u : 1u;
-  *out = set;
-  return RDOOM_OK;
+    if (rdoom_status s = set->d_things.upload(all, rdoom::EMPTY_TABLE_BYTES)) return s;
+    if (rdoom_status s = set->d_levels.upload(levels, rdoom::EMPTY_TABLE_BYTES)) return s;
+    set->level0 = levels[0], set->n_levels = n_levels, set->max_object_id = max_object_id;
+    set->words = most ? (most + 31u) / 32u : 1u;
+    *out = set.release();
+    return RDOOM_OK;
+  });
 }
 
-void rdoom_thingset_destroy(rdoom_thingset *set) {
-  if (!set) return;
-  rdoom::free_all({set->d_things, set->d_levels});
-  delete set;
-}
+void rdoom_thingset_destroy(rdoom_thingset *set) { delete set; }
 
 rdoom_status rdoom_thingset_info(const rdoom_thingset *set, uint32_t *out_n_levels, uint32_t *out_words, uint32_t *out_max_object_id) {
   if (!set) return rdoom::fail(RDOOM_BAD_ARG, "null thing set");
@@ -343,7 +334,7 @@ rdoom_status rdoom_worldset_sense_things(const rdoom_worldset *set, const rdoom_
     return s;
   if (!n) return RDOOM_OK;
   return rdoom::launch_checked(worldset_sense_things_kernel, dim3(n), dim3(THREADS), 0, stream, a, line_table(*src.map),
-                               (const uint2 *)src.map->levels, (const uint2 *)things->d_levels, d_levels, src.map->n_levels);
+                               (const uint2 *)src.map->levels.get(), (const uint2 *)things->d_levels.get(), d_levels, src.map->n_levels);
 }
 
 }  // extern "C"

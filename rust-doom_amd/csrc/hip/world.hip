@@ -862,24 +862,22 @@ static_assert(sizeof(rdoom_world_node) == sizeof(rdoom::game::WorldNode) && size
               "the C ABI records are the host builder's");
 static_assert(sizeof(rdoom_player_state) == 40 && sizeof(rdoom_player_input) == 20 && sizeof(rdoom_player_config) == 32, "ABI sizes");
 
+static_assert(sizeof(rdoom::game::WorldChunk) == sizeof(uint2) && sizeof(rdoom::game::WorldTriangle) == sizeof(uint4),
+              "the kernels read the host builder's chunks and triangles as they are");
+
 namespace {
-template <class T>
-rdoom_status upload(T **dst, const void *src, size_t bytes) {
-  if (!bytes) bytes = 16;  // (a level without dynamic chunks: a valid, unread pointer)
-  HIP_TRY(hipMalloc((void **)dst, bytes));
-  if (src) HIP_TRY(hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice));
-  return RDOOM_OK;
-}
+using rdoom::DeviceArray;
+using rdoom::EMPTY_TABLE_BYTES;  // (a level without dynamic chunks: a valid, unread pointer)
 
 // the device arrays of a host World (rdoom_world_create; a world set's concatenation)
 struct DevArrays {
-  DevNode *nodes = nullptr;
-  uint2 *chunks = nullptr;
-  uint4 *tris = nullptr;
-  float *verts = nullptr;
-  DevDynamic *dynamics = nullptr;
-  DevTrigger *triggers = nullptr;
-  DevEffect *effects = nullptr;
+  DeviceArray<DevNode> nodes;
+  DeviceArray<uint2> chunks;
+  DeviceArray<uint4> tris;
+  DeviceArray<float> verts;
+  DeviceArray<DevDynamic> dynamics;
+  DeviceArray<DevTrigger> triggers;
+  DeviceArray<DevEffect> effects;
 };
 rdoom_status upload_world(const rdoom::game::World &h, DevArrays &d) {
   std::vector<DevNode> nodes(h.nodes.size());
@@ -889,11 +887,11 @@ rdoom_status upload_world(const rdoom::game::World &h, DevArrays &d) {
   }
   std::vector<DevDynamic> dyn(h.dynamics.size());
   for (size_t i = 0; i < dyn.size(); i++) dyn[i] = DevDynamic{h.dynamics[i].object_id, h.dynamics[i].tri_start, h.dynamics[i].tri_end, 0};
-  if (rdoom_status s = upload(&d.nodes, nodes.data(), nodes.size() * sizeof(DevNode))) return s;
-  if (rdoom_status s = upload(&d.chunks, h.chunks.data(), h.chunks.size() * sizeof(uint2))) return s;
-  if (rdoom_status s = upload(&d.tris, h.triangles.data(), h.triangles.size() * sizeof(uint4))) return s;
-  if (rdoom_status s = upload(&d.verts, h.verts.data(), h.verts.size() * sizeof(float))) return s;
-  if (rdoom_status s = upload(&d.dynamics, dyn.data(), dyn.size() * sizeof(DevDynamic))) return s;
+  if (rdoom_status s = d.nodes.upload(nodes, EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = d.chunks.upload(reinterpret_cast<const uint2 *>(h.chunks.data()), h.chunks.size(), EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = d.tris.upload(reinterpret_cast<const uint4 *>(h.triangles.data()), h.triangles.size(), EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = d.verts.upload(h.verts, EMPTY_TABLE_BYTES)) return s;
+  if (rdoom_status s = d.dynamics.upload(dyn, EMPTY_TABLE_BYTES)) return s;
   std::vector<DevTrigger> trig(h.triggers.size());
   for (size_t i = 0; i < trig.size(); i++) {
     const rdoom_trigger &t = h.triggers[i];
@@ -904,12 +902,8 @@ rdoom_status upload_world(const rdoom::game::World &h, DevArrays &d) {
     const rdoom_move_effect &e = h.effects[i];
     eff[i] = DevEffect{e.object_id, e.has_second, e.first_height_offset, e.second_height_offset, e.wait, e.speed, {0.0f, 0.0f}};
   }
-  if (rdoom_status s = upload(&d.triggers, trig.data(), trig.size() * sizeof(DevTrigger))) return s;
-  if (rdoom_status s = upload(&d.effects, eff.data(), eff.size() * sizeof(DevEffect))) return s;
-  return RDOOM_OK;
-}
-void free_world(DevArrays &d) {
-  rdoom::free_all({d.nodes, d.chunks, d.tris, d.verts, d.dynamics, d.triggers, d.effects});
+  if (rdoom_status s = d.triggers.upload(trig, EMPTY_TABLE_BYTES)) return s;
+  return d.effects.upload(eff, EMPTY_TABLE_BYTES);
 }
 }  // namespace
 
@@ -931,8 +925,8 @@ struct rdoom_worldset {
   bool on_device = false;
   int device = -1;
   DevArrays d;
-  DevSetLevel *d_table = nullptr;
-  uint32_t *d_tri_starts = nullptr;  // each level's triangle base in the concatenation (the ray cast's)
+  DeviceArray<DevSetLevel> d_table;
+  DeviceArray<uint32_t> d_tri_starts;  // each level's triangle base in the concatenation (the ray cast's)
   rdoom::MapDevice map;              // the levels' line tables, one after the other
   rdoom::SectorDevice sectors;       // and their sector tables
   rdoom::SpawnDevice spawn;          // and their spawn tables
@@ -953,21 +947,6 @@ MapSource map_source(const rdoom_worldset *s) {
 }  // namespace rdoom
 
 namespace {
-// the host build of rdoom_world_create / rdoom_worldset_create: what it throws becomes a status (nothing unwinds across the C ABI)
-template <class Build>
-rdoom_status build_host(Build &&build) {
-  try {
-    build();
-  } catch (const rdoom::wad::WadError &e) {
-    return rdoom::fail(e.code, "%s", e.what());
-  } catch (const std::bad_alloc &) {
-    return rdoom::fail(RDOOM_OOM, "out of host memory");
-  } catch (const std::exception &e) {
-    return rdoom::fail(RDOOM_BAD_LEVEL, "%s", e.what());
-  }
-  return RDOOM_OK;
-}
-
 void fill_arrays(const rdoom::game::World &h, rdoom_world_arrays &a) {
   std::memset(&a, 0, sizeof a);
   a.nodes = reinterpret_cast<const rdoom_world_node *>(h.nodes.data());
@@ -1004,7 +983,7 @@ void fill_triggers(const rdoom::game::World &h, rdoom_world_trigger_arrays &t) {
 }
 
 WorldView view(const DevArrays &d, uint32_t n_dynamics, uint32_t node_depth) {
-  return WorldView{d.nodes, d.chunks, d.tris, d.verts, d.dynamics, n_dynamics, node_depth + 1};
+  return WorldView{d.nodes.get(), d.chunks.get(), d.tris.get(), d.verts.get(), d.dynamics.get(), n_dynamics, node_depth + 1};
 }
 
 // kernel(v, args...) with one lane per query, player or ray: one wave per workgroup, each lane's node stack in LDS
@@ -1027,7 +1006,7 @@ GameView game_layout(const rdoom::game::World &h) {  // the layout include/rdoom
 
 GameView game_view(const rdoom_world *w) {
   GameView g = game_layout(w->host);
-  g.triggers = w->d.triggers, g.effects = w->d.effects;
+  g.triggers = w->d.triggers.get(), g.effects = w->d.effects.get();
   return g;
 }
 
@@ -1084,39 +1063,30 @@ rdoom_status ray_args(const rdoom_player_state *d_states, uint32_t n, const floa
 
 extern "C" {
 
-void rdoom_world_destroy(rdoom_world *w) {
-  if (!w) return;
-  free_world(w->d);
-  rdoom::map_free(w->map);
-  rdoom::sector_free(w->sectors);
-  rdoom::spawn_free(w->spawn);
-  delete w;
-}
+void rdoom_world_destroy(rdoom_world *w) { delete w; }
 
 rdoom_status rdoom_world_create(const rdoom_wad *wad, uint32_t level_index, uint32_t flags, rdoom_world **out_world) {
   if (!wad || !out_world) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   if (flags & ~RDOOM_WORLD_HOST_ONLY) return rdoom::fail(RDOOM_BAD_ARG, "unknown flags 0x%x", flags);
   *out_world = nullptr;
-  std::unique_ptr<rdoom_world, void (*)(rdoom_world *)> w(nullptr, rdoom_world_destroy);
-  if (rdoom_status st = build_host([&] {
-        w.reset(new rdoom_world);
-        w->host = rdoom::game::build_world(*rdoom::game::loaded_wad(wad), level_index);
-      }))
-    return st;
-  const rdoom::game::World &h = w->host;
-  w->bounds = rdoom::line_bounds(h.map_lines.data(), h.map_lines.size());
-  if (h.node_depth > RDOOM_WORLD_MAX_DEPTH)
-    return rdoom::fail(RDOOM_BAD_LEVEL, "the level's BSP is %u nodes deep (at most %u)", h.node_depth, RDOOM_WORLD_MAX_DEPTH);
-  if (!(flags & RDOOM_WORLD_HOST_ONLY)) {
-    HIP_TRY(hipGetDevice(&w->device));
-    if (rdoom_status st = upload_world(h, w->d)) return st;
-    if (rdoom_status st = rdoom::map_upload(h.map_lines, {make_uint2(0u, (uint32_t)h.map_lines.size())}, w->map)) return st;
-    if (rdoom_status st = rdoom::sector_upload({&h}, w->sectors)) return st;
-    if (rdoom_status st = rdoom::spawn_upload({&h}, w->spawn)) return st;
-    w->on_device = true;
-  }
-  *out_world = w.release();
-  return RDOOM_OK;
+  return rdoom::guarded([&]() -> rdoom_status {  // (the host build and the uploads' tables are std containers)
+    auto w = std::make_unique<rdoom_world>();
+    w->host = rdoom::game::build_world(*rdoom::game::loaded_wad(wad), level_index);
+    const rdoom::game::World &h = w->host;
+    w->bounds = rdoom::line_bounds(h.map_lines.data(), h.map_lines.size());
+    if (h.node_depth > RDOOM_WORLD_MAX_DEPTH)
+      return rdoom::fail(RDOOM_BAD_LEVEL, "the level's BSP is %u nodes deep (at most %u)", h.node_depth, RDOOM_WORLD_MAX_DEPTH);
+    if (!(flags & RDOOM_WORLD_HOST_ONLY)) {
+      HIP_TRY(hipGetDevice(&w->device));
+      if (rdoom_status st = upload_world(h, w->d)) return st;
+      if (rdoom_status st = rdoom::map_upload(h.map_lines, {make_uint2(0u, (uint32_t)h.map_lines.size())}, w->map)) return st;
+      if (rdoom_status st = rdoom::sector_upload({&h}, w->sectors)) return st;
+      if (rdoom_status st = rdoom::spawn_upload({&h}, w->spawn)) return st;
+      w->on_device = true;
+    }
+    *out_world = w.release();
+    return RDOOM_OK;
+  });
 }
 
 rdoom_status rdoom_world_host_arrays(const rdoom_world *w, rdoom_world_arrays *out) {
@@ -1217,63 +1187,52 @@ rdoom_status rdoom_world_step_game(const rdoom_world *w, rdoom_player_state *d_s
                       level.g.triggers, level.g.effects, d_states, d_inputs, n_ticks, c);
 }
 
-void rdoom_worldset_destroy(rdoom_worldset *s) {
-  if (!s) return;
-  free_world(s->d);
-  rdoom::map_free(s->map);
-  rdoom::sector_free(s->sectors);
-  rdoom::spawn_free(s->spawn);
-  if (s->d_table) (void)hipFree(s->d_table);
-  if (s->d_tri_starts) (void)hipFree(s->d_tri_starts);
-  delete s;
-}
+void rdoom_worldset_destroy(rdoom_worldset *s) { delete s; }
 
 rdoom_status rdoom_worldset_create(const rdoom_wad *wad, const uint32_t *level_indices, uint32_t n_levels, uint32_t flags,
                                    rdoom_worldset **out_set) {
   if (!wad || !out_set || (n_levels && !level_indices)) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   if (flags & ~RDOOM_WORLD_HOST_ONLY) return rdoom::fail(RDOOM_BAD_ARG, "unknown flags 0x%x", flags);
   *out_set = nullptr;
-  std::unique_ptr<rdoom_worldset, void (*)(rdoom_worldset *)> s(nullptr, rdoom_worldset_destroy);
-  if (rdoom_status st = build_host([&] {
-        s.reset(new rdoom_worldset);
-        s->host = rdoom::game::build_world_set(*rdoom::game::loaded_wad(wad), level_indices, n_levels);
-      }))
-    return st;
-  const rdoom::game::WorldSet &h = s->host;
-  if (h.node_depth > RDOOM_WORLD_MAX_DEPTH)
-    return rdoom::fail(RDOOM_BAD_LEVEL, "a level's BSP is %u nodes deep (at most %u)", h.node_depth, RDOOM_WORLD_MAX_DEPTH);
-  for (size_t i = 0; i < h.levels.size(); i++) {
-    const rdoom::game::World &l = h.levels[i];
-    const rdoom::game::WorldSetLevel &t = h.table[i];
-    const GameView g = game_layout(l);
-    DevSetLevel r{};
-    r.root = t.node_base, r.dyn_start = t.dynamic_base, r.n_dynamics = (uint32_t)l.dynamics.size(), r.destination = t.destination;
-    r.trig_start = t.trigger_base, r.n_triggers = g.n_triggers, r.n_objects = g.n_objects, r.words = g.words;
-    r.live = g.live, r.fired = g.fired, r.active = g.active, r.second = g.second, r.order = g.order, r.effect = g.effect;
-    std::memcpy(r.start, l.start_pos, sizeof r.start);
-    r.start_yaw = l.start_yaw;
-    s->table.push_back(r);
-    s->words = std::max(s->words, g.words);
-    s->bounds.push_back(rdoom::line_bounds(l.map_lines.data(), l.map_lines.size()));
-  }
-  if (!(flags & RDOOM_WORLD_HOST_ONLY)) {
-    HIP_TRY(hipGetDevice(&s->device));
-    if (rdoom_status st = upload_world(h.all, s->d)) return st;
-    if (rdoom_status st = upload(&s->d_table, s->table.data(), s->table.size() * sizeof(DevSetLevel))) return st;
-    std::vector<uint32_t> tri_starts;
-    for (const rdoom::game::WorldSetLevel &t : h.table) tri_starts.push_back(t.triangle_base);
-    if (rdoom_status st = upload(&s->d_tri_starts, tri_starts.data(), tri_starts.size() * sizeof(uint32_t))) return st;
-    std::vector<uint2> map_ranges;
-    for (size_t i = 0; i < h.levels.size(); i++) map_ranges.push_back(make_uint2(h.table[i].map_base, (uint32_t)h.levels[i].map_lines.size()));
-    if (rdoom_status st = rdoom::map_upload(h.all.map_lines, map_ranges, s->map)) return st;
-    std::vector<const rdoom::game::World *> each;
-    for (const rdoom::game::World &l : h.levels) each.push_back(&l);
-    if (rdoom_status st = rdoom::sector_upload(each, s->sectors)) return st;
-    if (rdoom_status st = rdoom::spawn_upload(each, s->spawn)) return st;
-    s->on_device = true;
-  }
-  *out_set = s.release();
-  return RDOOM_OK;
+  return rdoom::guarded([&]() -> rdoom_status {
+    auto s = std::make_unique<rdoom_worldset>();
+    s->host = rdoom::game::build_world_set(*rdoom::game::loaded_wad(wad), level_indices, n_levels);
+    const rdoom::game::WorldSet &h = s->host;
+    if (h.node_depth > RDOOM_WORLD_MAX_DEPTH)
+      return rdoom::fail(RDOOM_BAD_LEVEL, "a level's BSP is %u nodes deep (at most %u)", h.node_depth, RDOOM_WORLD_MAX_DEPTH);
+    for (size_t i = 0; i < h.levels.size(); i++) {
+      const rdoom::game::World &l = h.levels[i];
+      const rdoom::game::WorldSetLevel &t = h.table[i];
+      const GameView g = game_layout(l);
+      DevSetLevel r{};
+      r.root = t.node_base, r.dyn_start = t.dynamic_base, r.n_dynamics = (uint32_t)l.dynamics.size(), r.destination = t.destination;
+      r.trig_start = t.trigger_base, r.n_triggers = g.n_triggers, r.n_objects = g.n_objects, r.words = g.words;
+      r.live = g.live, r.fired = g.fired, r.active = g.active, r.second = g.second, r.order = g.order, r.effect = g.effect;
+      std::memcpy(r.start, l.start_pos, sizeof r.start);
+      r.start_yaw = l.start_yaw;
+      s->table.push_back(r);
+      s->words = std::max(s->words, g.words);
+      s->bounds.push_back(rdoom::line_bounds(l.map_lines.data(), l.map_lines.size()));
+    }
+    if (!(flags & RDOOM_WORLD_HOST_ONLY)) {
+      HIP_TRY(hipGetDevice(&s->device));
+      if (rdoom_status st = upload_world(h.all, s->d)) return st;
+      if (rdoom_status st = s->d_table.upload(s->table, EMPTY_TABLE_BYTES)) return st;
+      std::vector<uint32_t> tri_starts;
+      for (const rdoom::game::WorldSetLevel &t : h.table) tri_starts.push_back(t.triangle_base);
+      if (rdoom_status st = s->d_tri_starts.upload(tri_starts, EMPTY_TABLE_BYTES)) return st;
+      std::vector<uint2> map_ranges;
+      for (size_t i = 0; i < h.levels.size(); i++) map_ranges.push_back(make_uint2(h.table[i].map_base, (uint32_t)h.levels[i].map_lines.size()));
+      if (rdoom_status st = rdoom::map_upload(h.all.map_lines, map_ranges, s->map)) return st;
+      std::vector<const rdoom::game::World *> each;
+      for (const rdoom::game::World &l : h.levels) each.push_back(&l);
+      if (rdoom_status st = rdoom::sector_upload(each, s->sectors)) return st;
+      if (rdoom_status st = rdoom::spawn_upload(each, s->spawn)) return st;
+      s->on_device = true;
+    }
+    *out_set = s.release();
+    return RDOOM_OK;
+  });
 }
 
 rdoom_status rdoom_worldset_info(const rdoom_worldset *s, uint32_t *out_n_levels, uint32_t *out_n_objects) {
@@ -1342,7 +1301,7 @@ rdoom_status rdoom_worldset_game_reset(const rdoom_worldset *s, void *d_game, fl
   if (rdoom_status st = check_game(true, s->host.game_objects, d_game, d_object_offsets, n_objects, d_levels)) return st;
   if (rdoom_status st = check_device(s, "the world set")) return st;
   if (!n) return RDOOM_OK;
-  hipLaunchKernelGGL(worldset_game_reset_kernel, dim3(n), dim3(WAVE), 0, (hipStream_t)stream, s->d_table, (uint32_t)s->table.size(),
+  hipLaunchKernelGGL(worldset_game_reset_kernel, dim3(n), dim3(WAVE), 0, (hipStream_t)stream, s->d_table.get(), (uint32_t)s->table.size(),
                      s->words, (uint32_t *)d_game, d_object_offsets, n_objects, d_levels, d_mask);
   HIP_TRY(hipGetLastError());
   return RDOOM_OK;
@@ -1359,12 +1318,12 @@ rdoom_status rdoom_worldset_step_game(const rdoom_worldset *s, rdoom_player_stat
   if (rdoom_status st = check_device(s, "the world set")) return st;
   if (!n_players || !n_ticks) return RDOOM_OK;
   SetGame set{};
-  set.gl = game_level(GameView{s->d.triggers, s->d.effects, 0, s->host.game_objects, 0, 0, 0, 0, 0, 0, s->words}, d_game,
+  set.gl = game_level(GameView{s->d.triggers.get(), s->d.effects.get(), 0, s->host.game_objects, 0, 0, 0, 0, 0, 0, s->words}, d_game,
                       d_object_offsets, d_actions, n_players, n_objects, dt);
   set.level_of = d_levels;
   set.n_levels = (uint32_t)s->table.size();
-  return launch_lanes(worldset_game_step_kernel, n_players, view(s->d, 0u, s->host.node_depth), stream, set, s->d.triggers, s->d.effects,
-                      s->d_table, d_states, d_inputs, n_ticks, c);
+  return launch_lanes(worldset_game_step_kernel, n_players, view(s->d, 0u, s->host.node_depth), stream, set, s->d.triggers.get(), s->d.effects.get(),
+                      s->d_table.get(), d_states, d_inputs, n_ticks, c);
 }
 
 rdoom_status rdoom_world_cast_rays(const rdoom_world *w, const rdoom_player_state *d_states, uint32_t n, const float *d_dirs,
@@ -1392,8 +1351,8 @@ rdoom_status rdoom_worldset_cast_rays(const rdoom_worldset *s, const rdoom_playe
     return st;
   if (rdoom_status st = check_device(s, "the world set")) return st;
   if (!n) return RDOOM_OK;
-  return launch_lanes(worldset_cast_rays_kernel, a.total, view(s->d, 0u, s->host.node_depth), stream, a, s->d_table, s->d_tri_starts, d_levels,
-                      (uint32_t)s->table.size());
+  return launch_lanes(worldset_cast_rays_kernel, a.total, view(s->d, 0u, s->host.node_depth), stream, a, s->d_table.get(),
+                      s->d_tri_starts.get(), d_levels, (uint32_t)s->table.size());
 }
 
 }  // extern "C"

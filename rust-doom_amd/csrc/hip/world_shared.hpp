@@ -1,12 +1,11 @@
 // What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip), the explored area's (area.hip), the sectors' (sectors.hip), the spawn's (spawn.hip), the floods' (flood.hip), the goal distance's (goal.hip) and the path unit's (path.hip) share: the pick of a lane's level,
 // a wave's maximum and sum and the append into a list in LDS, what the map units read of a line, the checked launch, the device
-// check of a handle, the upload and release of a table, the checks of a fan, of a row of offsets and of a map view, and the map's
-// side of a world handle.  (The sight pass of reveal.hip and area.hip is sight.hpp's.)
+// check of a handle, the checks of a fan, of a row of offsets and of a map view, and the map's side of a world handle (its
+// tables own their device memory: device_memory.hpp).  (The sight pass of reveal.hip and area.hip is sight.hpp's.)
 // One definition each, for player_quat.hpp's reason.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <initializer_list>
 #include <vector>
 
 #include "../common.hpp"
@@ -233,18 +232,6 @@ rdoom_status check_device(const Handle *h, const char *noun) {
   return RDOOM_OK;
 }
 
-// a table on the current device (an empty one: a valid, unread pointer), and the release of a handle's tables
-template <class T>
-rdoom_status upload(T **dst, const std::vector<T> &src) {
-  HIP_TRY(hipMalloc((void **)dst, src.empty() ? 16 : src.size() * sizeof(T)));
-  if (!src.empty()) HIP_TRY(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
-  return RDOOM_OK;
-}
-inline void free_all(std::initializer_list<void *> pointers) {
-  for (void *p : pointers)
-    if (p) (void)hipFree(p);
-}
-
 // what every call that takes a fan of rays checks of it
 inline rdoom_status check_fan(uint32_t n_rays, float max_range) {
   if (!n_rays) return rdoom::fail(RDOOM_BAD_ARG, "n_rays is 0");
@@ -271,12 +258,12 @@ inline rdoom_status check_view(const rdoom_map_view *view) {
 // The device copy of a line table (rdoom_map_line), a structure of arrays private to automap.hip and reveal.hip: a world's, or a world set's
 // levels one after the other with `levels[slot]` = (first line, number of lines).
 struct MapDevice {
-  float4 *seg = nullptr;      // a.x, a.z, b.x, b.z
-  float4 *heights = nullptr;  // front floor, front ceiling, back floor, back ceiling
-  uint4 *ids = nullptr;       // the objects of those four
-  uint32_t *flags = nullptr;  // the linedef's flags; bit 16: the front side is present, bit 17: the back side
-  uint2 *levels = nullptr;    // a world set's slots (a world: one entry)
-  float4 *bounds = nullptr;   // a slot's minx, maxx, minz, maxz (line_bounds): what the explored-area grid is derived from (area.hip)
+  DeviceArray<float4> seg;      // a.x, a.z, b.x, b.z
+  DeviceArray<float4> heights;  // front floor, front ceiling, back floor, back ceiling
+  DeviceArray<uint4> ids;       // the objects of those four
+  DeviceArray<uint32_t> flags;  // the linedef's flags; bit 16: the front side is present, bit 17: the back side
+  DeviceArray<uint2> levels;    // a world set's slots (a world: one entry)
+  DeviceArray<float4> bounds;   // a slot's minx, maxx, minz, maxz (line_bounds): what the explored-area grid is derived from (area.hip)
   uint32_t n_lines = 0, n_levels = 0;
 };
 // the exact bounds of a table's end points as the "explored area" contract takes them: minx, maxx, minz, maxz; zeros for no lines
@@ -290,40 +277,37 @@ inline float4 line_bounds(const rdoom_map_line *lines, size_t n) {
     }
   return b;
 }
-// automap.hip: `lines` with `n_levels` (first, count) ranges on the current device; releases what it allocated
+// automap.hip: `lines` with `n_levels` (first, count) ranges on the current device
 rdoom_status map_upload(const std::vector<rdoom_map_line> &lines, const std::vector<uint2> &levels, MapDevice &out);
-void map_free(MapDevice &d);
 
 // The device copy of a sector table (rdoom_map_sectors) and of the BSP that leads to it, a structure of arrays private to
 // sectors.hip: a world's, or a world set's levels one after the other, every index inside a level the level's own.
 struct SectorDevice {
-  float4 *nodes = nullptr;    // d.x, d.y, c = d.x * o.y - d.y * o.x, and as bits the children: positive in the low 16, negative in the
-                              // high 16, each an int16 as Child::pack writes it (> 0 a node, <= 0 minus a leaf)
-  uint4 *leaves = nullptr;    // the leaf's sector or RDOOM_SECTOR_NONE, its first solid edge (in `edges`), their number, 0
-  float4 *edges = nullptr;    // a.x, a.z, d.x, d.z
-  float4 *sectors = nullptr;  // floor, ceiling, and as bits floor_id, ceiling_id
-  uint4 *levels = nullptr;    // a slot's first node, first leaf, first sector, number of sectors
+  DeviceArray<float4> nodes;    // d.x, d.y, c = d.x * o.y - d.y * o.x, and as bits the children: positive in the low 16, negative in
+                                // the high 16, each an int16 as Child::pack writes it (> 0 a node, <= 0 minus a leaf)
+  DeviceArray<uint4> leaves;    // the leaf's sector or RDOOM_SECTOR_NONE, its first solid edge (in `edges`), their number, 0
+  DeviceArray<float4> edges;    // a.x, a.z, d.x, d.z
+  DeviceArray<float4> sectors;  // floor, ceiling, and as bits floor_id, ceiling_id
+  DeviceArray<uint4> levels;    // a slot's first node, first leaf, first sector, number of sectors
   uint32_t n_levels = 0;
 };
 // sectors.hip: the tables of `levels` on the current device (RDOOM_BAD_LEVEL: a level with more nodes or leaves than 16 bits
-// address); releases what it allocated
+// address)
 rdoom_status sector_upload(const std::vector<const game::World *> &levels, SectorDevice &out);
-void sector_free(SectorDevice &d);
 
 // The device copy of a spawn table (rdoom_spawn_table), private to spawn.hip: a world's, or a world set's levels one after the
 // other.
 struct SpawnDevice {
-  float *cumulative = nullptr;  // an entry's cumulative area
-  float4 *corners = nullptr;    // three per entry: a, b, c as xyz
-  uint4 *levels = nullptr;      // a slot's first entry, its entries, the bound of the search ceil(log2(entries)) + 1, 0
-  float4 *starts = nullptr;     // a slot's start position and yaw
+  DeviceArray<float> cumulative;  // an entry's cumulative area
+  DeviceArray<float4> corners;    // three per entry: a, b, c as xyz
+  DeviceArray<uint4> levels;      // a slot's first entry, its entries, the bound of the search ceil(log2(entries)) + 1, 0
+  DeviceArray<float4> starts;     // a slot's start position and yaw
   uint32_t n_levels = 0;
   uint4 level0 = {};            // slot 0's two records on the host: a single world's launch passes them by value
   float4 start0 = {};
 };
-// spawn.hip: the tables of `levels` on the current device; releases what it allocated
+// spawn.hip: the tables of `levels` on the current device
 rdoom_status spawn_upload(const std::vector<const game::World *> &levels, SpawnDevice &out);
-void spawn_free(SpawnDevice &d);
 
 // what automap.hip, reveal.hip, sectors.hip and spawn.hip need of a world or world-set handle (world.hip owns the handles)
 struct MapSource {

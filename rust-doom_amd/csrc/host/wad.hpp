@@ -27,11 +27,6 @@
 
 namespace rdoom::wad {
 
-struct WadError : std::runtime_error {
-  rdoom_status code;
-  WadError(rdoom_status c, const std::string &m) : std::runtime_error(m), code(c) {}
-};
-
 // ---- name.rs -------------------------------------------------------------------------------------
 struct WadName {
   std::array<uint8_t, 8> b{};

@@ -142,18 +142,7 @@ void keep_light_infos(rdoom_built &b) {
   for (const rdoom::wad::LightInfo &info : b.b->lights.infos()) b.light_infos.push_back(plain_light(info));
 }
 
-template <class F>
-rdoom_status guarded(F f) {
-  try {
-    return f();
-  } catch (const rdoom::wad::WadError &e) {
-    return rdoom::fail(e.code, "%s", e.what());
-  } catch (const std::bad_alloc &) {
-    return rdoom::fail(RDOOM_OOM, "out of host memory");
-  } catch (const std::exception &e) {
-    return rdoom::fail(RDOOM_BAD_LEVEL, "%s", e.what());
-  }
-}
+using rdoom::guarded;  // common.hpp
 }  // namespace
 
 extern "C" {

@@ -385,6 +385,56 @@ def test_clean_iwad_under_the_sanitizers(driver, wad_path, oracle_levels):
     assert kind == 'level' and ('LEVEL %d 0 ' % LEVEL) in p.stdout and digest in p.stdout
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# The handles' failure paths (tests/sanitize/handle_errors.cpp): the WHOLE library, HIP units included, under the sanitizers in a
+# stand-alone program that sees no device, so that every create fails at its first call of the runtime.
+HIPCC = os.environ.get('HIPCC', '/opt/rocm/bin/hipcc')
+HANDLE_BUILD = os.path.join(HERE, '_build', 'handle_errors')
+SANITIZE = '-fsanitize=address,undefined'
+
+
+def _build_handle_errors():
+    csrc = os.path.join(ROOT, 'rust-doom_amd', 'csrc')
+    hip = sorted(glob.glob(os.path.join(csrc, 'hip', '*.hip')))
+    cpp = sorted(glob.glob(os.path.join(csrc, 'host', '*.cpp'))) + [os.path.join(HERE, 'sanitize', 'handle_errors.cpp')]
+    headers = glob.glob(os.path.join(csrc, '**', '*.hpp'), recursive=True) + [os.path.join(ROOT, 'include', 'rdoom.h')]
+    common = ['-O1', '-g', '-std=c++17', '-ffp-contract=off', '-fno-fast-math', '-I' + os.path.join(ROOT, 'include')]
+    os.makedirs(HANDLE_BUILD, exist_ok=True)
+
+    def stale(target, deps):
+        return not os.path.exists(target) or any(os.path.getmtime(d) > os.path.getmtime(target) for d in deps)
+
+    def cc(src):  # (objects are kept by mtime, as rust-doom_amd/build.py keeps the library's)
+        obj = os.path.join(HANDLE_BUILD, os.path.basename(src) + '.o')
+        if stale(obj, [src] + headers):
+            unit = ['--offload-arch=gfx950', '-x', 'hip', '-Xarch_host', SANITIZE] if src.endswith('.hip') else ['-x', 'c++', SANITIZE]
+            subprocess.check_call([HIPCC] + unit + common + ['-c', src, '-o', obj])
+        return obj
+
+    import fcntl
+    with open(os.path.join(HANDLE_BUILD, '.lock'), 'w') as lock:  # (pytest-xdist: one worker builds)
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        with ThreadPoolExecutor(min(len(hip + cpp), os.cpu_count() or 1, 16)) as ex:
+            objs = list(ex.map(cc, hip + cpp))
+        out = os.path.join(HANDLE_BUILD, 'handle_errors')
+        if stale(out, objs):
+            subprocess.check_call([HIPCC, '--offload-arch=gfx950', SANITIZE] + objs + ['-o', out])
+        return out
+
+
+@pytest.mark.skipif(not os.path.exists(HIPCC), reason='needs hipcc')
+def test_handle_failure_paths_under_the_sanitizers(wad_path):
+    """every create of a device handle with no device in sight: RDOOM_HIP_ERROR, a null handle, nothing leaked, no report; host-only
+    worlds are whole and refuse device calls; every destroy takes NULL"""
+    exe = _build_handle_errors()
+    env = dict(os.environ, HIP_VISIBLE_DEVICES='-1', ASAN_OPTIONS='detect_leaks=1', UBSAN_OPTIONS='print_stacktrace=1')
+    p = subprocess.run([exe, wad_path, META_PATH], capture_output=True, text=True, timeout=300, env=env)
+    assert p.returncode == 0 and 'Sanitizer' not in p.stderr and 'runtime error' not in p.stderr, (p.stdout[-2000:], p.stderr[-3000:])
+    if p.stdout.startswith('SKIP'):
+        pytest.skip('a device is visible to the sanitized program, which then creates nothing')
+    assert p.stdout.strip().endswith('OK'), p.stdout[-2000:]
+
+
 @pytest.mark.parametrize('name', [m[0] for m in MUTATIONS])
 def test_malformed_iwad(driver, wad_path, tmp_path, name):
     w = WadFile(wad_path)
