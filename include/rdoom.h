@@ -1763,6 +1763,59 @@ rdoom_status rdoom_level_set_decor_things(rdoom_level *level, uint32_t slot, con
  * the batch's handle that has decor triangles and no attached table. */
 rdoom_status rdoom_batch_set_hidden_things(rdoom_batch *batch, const uint32_t *d_hidden, uint32_t stride);
 
+/* ---- thing maps: each player's thing marks on the automap grid ----------------------------------------------
+ * The things of a rdoom_thingset drawn as discs on the pixels of rdoom_world_draw_maps, per player and in the player's own game:
+ * a thing the player has collected is gone from its map and only from its map, and optionally only the things the player has
+ * already seen are drawn.  The call needs no world handle: the thing set knows its levels, the player state gives the position and
+ * the yaw, and things do not move in xz.  The reference has no automap and no counterpart.
+ * n players' maps in one launch, asynchronous on `stream` (a hipStream_t, may be NULL); every pointer but `things`, `view` and
+ * `marks` is device memory, nothing is allocated, nothing is copied to the host and nothing waits, so the call can be captured into
+ * a graph.
+ * Every float below is binary32, every operation is rounded once and none is contracted; a * b + c * d means
+ * round(round(a * b) + round(c * d)).
+ * Pixel to world.  The map contract's ("top-down maps"), word for word: the byte at row `row`, column i of map p is pixel (i, j)
+ * with j = row, or j = height - 1 - row with RDOOM_MAP_TOP_DOWN; hw = (float)width * 0.5f, hh = (float)height * 0.5f;
+ *   u = (((float)i + 0.5f) - hw) * scale;  v = (((float)j + 0.5f) - hh) * scale;
+ * without RDOOM_MAP_ROTATE q = (pos.x - v, pos.z - u); with it, (s, c) = the project's sincos of yaw (csrc/hip/sincos_rd.hpp):
+ * q.x = (pos.x + c * u) + (-s) * v;  q.z = (pos.z + (-s) * u) + (-c) * v.  Of `view` the call reads width, height, scale and those
+ * two flags; half_width, marker, RDOOM_MAP_SHOW_FLAT and RDOOM_MAP_SHOW_HIDDEN are not read, so the view of a draw_maps call can
+ * be passed as it is.
+ * Which things are drawn.  Player p is in level L = d_levels[p] of the set (a NULL d_levels: every player in slot 0), which has T
+ * things.  Thing i < T is drawn when codes[category & 0xFF] != 0, and its bit is clear in row p of d_hidden (a NULL d_hidden hides
+ * nothing; it is rdoom_world_sense_things' d_collected as it stands), and its bit is set in row p of d_known (a NULL d_known: every
+ * thing is known; a caller keeps it by OR-ing sense_things' d_visible_out into it).  Bit i is bit i % 32 of word
+ * p * stride + i / 32, as in "things"; only words [0, ceil(T / 32)) of a row are read, and none is written.
+ * Coverage.  For a drawn thing: rp = min_radius * scale; r = radius > rp ? radius : rp; r2 = r * r.  The thing covers q when
+ *   ex = q.x - x;  ez = q.z - z;  ex * ex + ez * ez <= r2.
+ * A radius so large that r * r overflows to +inf covers every pixel whose q is a number.
+ * Pixel value.  Each covering thing has the key (code << 20) | (0xFFFFF - i), code = codes[category & 0xFF]; T <= 2^20, so the
+ * key's low 20 bits hold 0xFFFFF - i.  The pixel takes the largest key: the larger code wins, and among equal codes the lower
+ * index.  d_out gets the key's code, d_index_out its i.  Where nothing covers, d_out is 0 and d_index_out is -1.  The value is a
+ * maximum, so it does not depend on the order in which things are visited, on a thing being visited twice or on where a list of
+ * things is cut -- the reason "top-down maps" gives for its own rule.
+ * Outputs.  d_out: n x height x width bytes; d_index_out: n x height x width int32; map p at element p * height * width, row-major.
+ * Either may be NULL, but not both.  Without RDOOM_THING_MARKS_OVER every byte of d_out is written; with it only the covered bytes
+ * are, and every other byte is left as it was: a call after rdoom_world_draw_maps on the same buffer overlays the marks on the line
+ * map (the default codes lie above every RDOOM_MAP_* class).  d_index_out is always written whole.
+ * A comparison with a NaN is false: a player at a NaN position gets no mark.  A level slot >= the set's levels is seen on the
+ * device only: that player gets no mark.
+ * Errors, all RDOOM_BAD_ARG and all checked before anything is queued, in this order.  What needs no set: a NULL view or marks;
+ * (n > 0) a NULL d_states; both outputs NULL; width or height 0 or above 16384; scale not finite or not > 0; view flags other than
+ * the four RDOOM_MAP_* flags; min_radius not finite or < 0; marks->flags other than RDOOM_THING_MARKS_OVER; n x the view's 32 x 32
+ * pixel tiles above 2^31 - 1.  Then: a NULL set; a set that lives on another device than the current one; a NULL d_levels while the
+ * set has more than one level; a stride smaller than the set's words while d_hidden or d_known is given.  n == 0 queues nothing. */
+#define RDOOM_MAP_THING 16u            /* default code of category c: RDOOM_MAP_THING + c, clear of the RDOOM_MAP_* line classes */
+#define RDOOM_THING_MARKS_OVER 1u      /* d_out is written only where a mark covers; every other byte is left as it was */
+typedef struct rdoom_thing_marks {
+  float min_radius;                    /* pixels; finite, >= 0: a mark is never drawn smaller than this */
+  uint8_t codes[8];                    /* the byte of a thing of category c; 0: that category is not drawn */
+  uint32_t flags;                      /* RDOOM_THING_MARKS_OVER or 0 */
+} rdoom_thing_marks;
+rdoom_status rdoom_thingset_draw_maps(const rdoom_thingset *things, const rdoom_player_state *d_states, const uint32_t *d_levels,
+                                      uint32_t n, const rdoom_map_view *view, const rdoom_thing_marks *marks,
+                                      const uint32_t *d_hidden, const uint32_t *d_known, uint32_t stride,
+                                      uint8_t *d_out, int32_t *d_index_out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

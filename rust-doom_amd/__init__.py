@@ -118,6 +118,31 @@ def _map_colors():
 
 
 MAP_COLORS = _map_colors()  # (256, 3) uint8: torch.from_numpy(MAP_COLORS).cuda()[maps.long()] is an RGB map
+# rdoom_thingset_draw_maps (DeviceThings.draw_maps): the default code of a thing of category c is MAP_THING + c, above every MAP_*
+# line class; THING_MARKS_OVER: only the covered bytes are written; THING_MARKS: rdoom_thing_marks as a numpy record
+MAP_THING = 16
+THING_MARKS_OVER = 1
+THING_MARKS = np.dtype([('min_radius', '<f4'), ('codes', 'u1', 8), ('flags', '<u4')])
+assert THING_MARKS.itemsize == 16
+
+
+def _thing_map_colors():
+    t = np.zeros((MAP_THING + THING_CATEGORIES, 3), np.uint8)
+    t[:MAP_THING] = MAP_COLORS[:MAP_THING]
+    t[MAP_THING + THING_DECORATION] = (120, 120, 140)  # grey-blue: scenery
+    t[MAP_THING + THING_WEAPON] = (255, 128, 0)        # orange
+    t[MAP_THING + THING_POWERUP] = (0, 255, 0)         # green
+    t[MAP_THING + THING_ARTIFACT] = (200, 0, 255)      # violet
+    t[MAP_THING + THING_AMMO] = (255, 220, 120)        # sand
+    t[MAP_THING + THING_KEY] = (64, 128, 255)          # blue
+    t[MAP_THING + THING_MONSTER] = (255, 0, 128)       # pink
+    t[MAP_THING + THING_UNKNOWN] = (160, 160, 160)     # grey
+    return t
+
+
+# (24, 3) uint8: MAP_COLORS' first 16 rows, then one colour per thing category, so that
+# torch.from_numpy(THING_MAP_COLORS).cuda()[maps.long()] colours a line map with the default thing marks overlaid
+THING_MAP_COLORS = _thing_map_colors()
 # rdoom_light_info (wad/src/light.rs:8-25 LightInfo): what BuiltLevel.light_infos returns and DeviceLights takes
 LIGHT_INFO = np.dtype([('level', '<f4'), ('has_effect', '<i4'), ('effect_kind', '<i4'), ('alt_level', '<f4'), ('speed', '<f4'),
                        ('duration', '<f4'), ('sync', '<f4')])
@@ -205,7 +230,7 @@ API_SYMBOLS = [
     'rdoom_flood_descend_octile', 'rdoom_grid_walk_lines', 'rdoom_path_straighten',
     'rdoom_world_map_things', 'rdoom_worldset_level_map_things', 'rdoom_thingset_create', 'rdoom_thingset_destroy', 'rdoom_thingset_info',
     'rdoom_world_sense_things', 'rdoom_worldset_sense_things',
-    'rdoom_built_decor_things', 'rdoom_level_set_decor_things', 'rdoom_batch_set_hidden_things']
+    'rdoom_built_decor_things', 'rdoom_level_set_decor_things', 'rdoom_batch_set_hidden_things', 'rdoom_thingset_draw_maps']
 
 _lib = None
 
@@ -1493,6 +1518,11 @@ class ThingSense(ctypes.Structure):
                 ('flags', ctypes.c_uint32)]
 
 
+class ThingMarks(ctypes.Structure):
+    """rdoom_thing_marks (THING_MARKS is the same record for numpy)"""
+    _fields_ = [('min_radius', ctypes.c_float), ('codes', ctypes.c_uint8 * 8), ('flags', ctypes.c_uint32)]
+
+
 def _map_things(get):
     """World.map_things / WorldSet.map_things: a copy of the table get(&rdoom_map_things) lends"""
     a = MapThings()
@@ -1532,6 +1562,84 @@ class DeviceThings:
     def words(self):
         """the 32-bit words a row of thing bits takes at least: max(1, ceil(largest table / 32))"""
         return self.info()[1]
+
+    def draw_maps(self, states, width, height, scale, levels=None, min_radius=2.0, codes=None, hidden=None, known=None, rotate=False,
+                  top_down=False, over=False, out=None, index_out=None, stream=None, n=None, stride=None):
+        """rdoom_thingset_draw_maps: every player's thing marks on the pixels of World.draw_maps(states, width, height, scale,
+        rotate=, top_down=), one launch.  A thing is a disc of its own radius, at least min_radius pixels; its byte is
+        codes[category] (a sequence of eight, 0: that category is not drawn; None: MAP_THING + category), and where discs overlap the
+        larger code wins, the lower index among equal codes.  levels: None (every player in slot 0; a set of one level) or one
+        32-bit slot per player.  hidden: None or sense_things' `collected` (n, words) tensor as it stands: player p's map leaves
+        out the things whose bit is set in row p.  known: None (every thing) or such a tensor of the things a player may see on
+        its map, for instance `known |= visible` after every sense_things.  out: a uint8 (n, height, width) tensor, allocated when
+        None, or False for no byte plane; over: only the covered bytes of `out` are written, so that a call on the tensor draw_maps
+        filled overlays the marks on the lines (THING_MAP_COLORS colours the result).  index_out: None / False, True (allocated) or
+        an int32 (n, height, width) tensor: the index of the thing at each pixel, -1 where there is none; always written whole.
+        Every tensor may instead be a raw device pointer (an int; then n, and with hidden or known stride, must be given).  Returns
+        what was asked for: out, index_out, or (out, index_out).  Asynchronous on `stream`; nothing is copied to the host."""
+        raw = isinstance(states, (int, np.integer))
+        if raw:
+            if n is None:
+                raise ValueError('n is needed with raw pointers')
+            n = int(n)
+        else:
+            n = _n_players(states)
+        width, height = int(width), int(height)
+        if width < 1 or height < 1:
+            raise ValueError('a map needs at least 1 x 1 pixels, got %d x %d' % (width, height))
+        if codes is None:
+            codes = [MAP_THING + c for c in range(THING_CATEGORIES)]
+        codes = [int(c) for c in codes]
+        if len(codes) != THING_CATEGORIES or not all(0 <= c <= 255 for c in codes):
+            raise ValueError('codes must be eight bytes, one per category, got %r' % (codes,))
+        for r, what in ((hidden, 'hidden'), (known, 'known')):
+            if r is None or isinstance(r, (int, np.integer)):
+                if r is not None and stride is None:
+                    raise ValueError('stride is needed with a raw %s pointer' % what)
+                continue
+            if r.element_size() != 4 or r.dtype.is_floating_point or r.dim() != 2:
+                raise ValueError('%s must be a 32-bit integer (n, words) tensor' % what)
+            if int(r.shape[0]) < n:
+                raise ValueError('the %s tensor has %d rows, the call %d players' % (what, int(r.shape[0]), n))
+            if stride is not None and int(stride) != int(r.shape[1]):
+                raise ValueError('stride %d, but the %s rows are %d words long' % (int(stride), what, int(r.shape[1])))
+            stride = int(r.shape[1])
+        stride = 0 if stride is None else int(stride)
+        if levels is not None and not isinstance(levels, (int, np.integer)) and (levels.element_size() != 4 or levels.numel() != n):
+            raise ValueError('levels must hold one 32-bit slot per player (%d), got %s %s' % (n, levels.dtype, tuple(levels.shape)))
+        wants_index = index_out is not None and index_out is not False
+        if out is False:
+            out = None
+        elif out is None:
+            if over:
+                raise ValueError('over=True writes only the covered bytes: it needs the tensor to draw over as out')
+            if raw:
+                raise ValueError('out is needed with raw pointers')
+            import torch
+            out = torch.empty((n, height, width), dtype=torch.uint8, device=states.device)
+        elif not isinstance(out, (int, np.integer)) and out.element_size() != 1:
+            raise ValueError('out must hold bytes')
+        if index_out is True:
+            if raw:
+                raise ValueError('index_out must be a tensor or a pointer with raw pointers')
+            import torch
+            index_out = torch.empty((n, height, width), dtype=torch.int32, device=states.device)
+        elif not wants_index:
+            index_out = None
+        elif not isinstance(index_out, (int, np.integer)) and (index_out.element_size() != 4 or index_out.dtype.is_floating_point):
+            raise ValueError('index_out must hold 32-bit integers')
+        view = MapView(width, height, scale, 0.0, 0.0, (MAP_ROTATE if rotate else 0) | (MAP_TOP_DOWN if top_down else 0))
+        marks = ThingMarks(min_radius, (ctypes.c_uint8 * 8)(*codes), THING_MARKS_OVER if over else 0)
+        v = ctypes.c_void_p
+        pixels = n * height * width
+        _check(lib().rdoom_thingset_draw_maps(self._h, v(_pointer(states, n * PLAYER_STATE.itemsize, 'states')),
+                                              v(_pointer(levels, n * 4, 'levels')), n, ctypes.byref(view), ctypes.byref(marks),
+                                              v(_pointer(hidden, n * stride * 4, 'hidden')), v(_pointer(known, n * stride * 4, 'known')),
+                                              stride, v(_pointer(out, pixels, 'out')), v(_pointer(index_out, pixels * 4, 'index_out')),
+                                              v(_stream_handle(stream))))
+        if out is None:
+            return index_out
+        return (out, index_out) if index_out is not None else out
 
 
 def unpack_things(row, n):
@@ -2519,6 +2627,13 @@ class World:
                              nearest_out, new_out, stream, n, n_objects, stride)
     sense_things.__doc__ = 'rdoom_world_sense_things: ' + _SENSE_DOC
 
+    def draw_thing_maps(self, states, things, width, height, scale, **kw):
+        """things.draw_maps(states, width, height, scale, ...): the marks of `things` (a DeviceThings of this level) on the pixels
+        of draw_maps with the same width, height, scale, rotate and top_down"""
+        if not isinstance(things, DeviceThings):
+            raise ValueError('things must be a DeviceThings')
+        return things.draw_maps(states, width, height, scale, **kw)
+
     # ---- sectors -----------------------------------------------------------------------------------------------------------
     def map_sectors(self):
         """a copy of rdoom_world_map_sectors: the level's sector table, a MapSectors of (sectors, leaf_sector, leaf_edges, edges)"""
@@ -2808,6 +2923,13 @@ class WorldSet:
                              new_out, stream, n, n_objects, stride)
     sense_things.__doc__ = 'rdoom_worldset_sense_things (levels: a GPU tensor of one 32-bit slot per player; slot l of `things` is the ' \
                            'level in slot l): ' + _SENSE_DOC
+
+    def draw_thing_maps(self, states, levels, things, width, height, scale, **kw):
+        """things.draw_maps(states, width, height, scale, levels=levels, ...): the marks of `things` (slot l of it is the level in
+        slot l) on the pixels of draw_maps with the same width, height, scale, rotate and top_down"""
+        if not isinstance(things, DeviceThings):
+            raise ValueError('things must be a DeviceThings')
+        return things.draw_maps(states, width, height, scale, levels=levels, **kw)
 
     def map_sectors(self, slot):
         """a copy of rdoom_worldset_level_map_sectors: the level's sector table, a MapSectors of (sectors, leaf_sector, leaf_edges, edges)"""

@@ -29,17 +29,10 @@
 #include "kernels.hpp"
 #include "player_quat.hpp"
 #include "sight.hpp"
+#include "thingset.hpp"
 #include "world_shared.hpp"
 
 #pragma clang fp contract(off)
-
-struct rdoom_thingset {
-  rdoom::DeviceArray<rdoom_thing> d_things;  // the levels' records, one level after the other
-  rdoom::DeviceArray<uint2> d_levels;        // a slot's (first record, number of records)
-  uint2 level0 = {};                         // slot 0's, on the host: a single world's launch passes it by value
-  uint32_t n_levels = 0, words = 1, max_object_id = 0;
-  int device = -1;
-};
 
 namespace {
 
