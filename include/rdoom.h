@@ -1816,6 +1816,21 @@ rdoom_status rdoom_thingset_draw_maps(const rdoom_thingset *things, const rdoom_
                                       const uint32_t *d_hidden, const uint32_t *d_known, uint32_t stride,
                                       uint8_t *d_out, int32_t *d_index_out, void *stream);
 
+/* ---- solid things: which things of a level are obstacles ----------------------------------------------------
+ * The reference has no thing collision at all (its player walks through every barrel), so nothing here restates it: this header is
+ * the authority, as it is for the explored area and for the things.
+ * The metadata may give a [[things.*]] entry the optional boolean `obstacle` (absent: false).  The two calls below lend the level's
+ * obstacle bits (borrowed pointers, valid until the handle is destroyed), in the layout every row of thing bits has: bit i % 32 of
+ * word i / 32 is set when the metadata entry that gave thing i of rdoom_world_map_things its category -- the first match in merge
+ * order -- says obstacle = true; a thing without metadata has a clear bit.  *out_n_words = max(1, ceil(T / 32)) for the level's T
+ * things, and the bits at and above T are zero.  rdoom_thing stays as it is: solidity travels in bit rows.  Both work on
+ * RDOOM_WORLD_HOST_ONLY handles.  Errors (RDOOM_BAD_ARG): a NULL argument; a slot outside the set.
+ * Nothing on the device reads these bits yet: the player step does not see things (DESIGN section 31 has the contract of the step
+ * that will, and why it is not here). */
+rdoom_status rdoom_world_thing_obstacles(const rdoom_world *world, const uint32_t **out_words, uint32_t *out_n_words);
+rdoom_status rdoom_worldset_level_thing_obstacles(const rdoom_worldset *set, uint32_t slot, const uint32_t **out_words,
+                                                  uint32_t *out_n_words);
+
 #ifdef __cplusplus
 }
 #endif

@@ -230,7 +230,8 @@ API_SYMBOLS = [
     'rdoom_flood_descend_octile', 'rdoom_grid_walk_lines', 'rdoom_path_straighten',
     'rdoom_world_map_things', 'rdoom_worldset_level_map_things', 'rdoom_thingset_create', 'rdoom_thingset_destroy', 'rdoom_thingset_info',
     'rdoom_world_sense_things', 'rdoom_worldset_sense_things',
-    'rdoom_built_decor_things', 'rdoom_level_set_decor_things', 'rdoom_batch_set_hidden_things', 'rdoom_thingset_draw_maps']
+    'rdoom_built_decor_things', 'rdoom_level_set_decor_things', 'rdoom_batch_set_hidden_things', 'rdoom_thingset_draw_maps',
+    'rdoom_world_thing_obstacles', 'rdoom_worldset_level_thing_obstacles']
 
 _lib = None
 
@@ -1647,6 +1648,32 @@ def unpack_things(row, n):
     return unpack_seen(row, n)
 
 
+def pack_things(bools, words=None):
+    """the inverse of unpack_things: a bool array of n things as a row of `words` 32-bit words (None: max(1, ceil(n / 32))), bit
+    i % 32 of word i // 32 for thing i, an int32 array.  A list of arrays gives a (levels, words) array, one row a level: for
+    instance pack_things([ws.thing_obstacles(s) for s in range(ws.n_levels)]), the obstacle bits of a set"""
+    if isinstance(bools, (list, tuple)) and len(bools) and not np.isscalar(bools[0]):
+        rows = [np.asarray(b, bool).reshape(-1) for b in bools]
+        if words is None:
+            words = max(1, max((len(r) + 31) // 32 for r in rows))
+        return np.stack([pack_things(r, words) for r in rows])
+    bits = np.asarray(bools, bool).reshape(-1)
+    need = max(1, (len(bits) + 31) // 32)
+    words = need if words is None else int(words)
+    if words < need:
+        raise ValueError('%d words hold fewer than %d things' % (words, len(bits)))
+    padded = np.zeros(words * 32, np.uint8)
+    padded[:len(bits)] = bits
+    return np.packbits(padded.reshape(words, 32), axis=1, bitorder='little').view('<u4').reshape(words).astype(np.uint32).view(np.int32)
+
+
+def _thing_obstacles(get, n_things):
+    """World.thing_obstacles / WorldSet.thing_obstacles: the bits get(&words, &n_words) lends, as a bool array of n_things"""
+    p, n = ctypes.POINTER(ctypes.c_uint32)(), ctypes.c_uint32(0)
+    _check(get(ctypes.byref(p), ctypes.byref(n)))
+    return unpack_things(np.ctypeslib.as_array(p, shape=(n.value,)).copy(), n_things)
+
+
 ThingsSensed = collections.namedtuple('ThingsSensed', 'collected visible touched nearest new')
 
 
@@ -2618,6 +2645,11 @@ class World:
         a sector, in lump order (position, base height and the object that moves it, radius, sector, type, flags, category, angle)"""
         return _map_things(lambda a: lib().rdoom_world_map_things(self._h, a))
 
+    def thing_obstacles(self):
+        """rdoom_world_thing_obstacles: a bool per thing of map_things(), true where the metadata entry of its type says
+        obstacle = true (pack_things packs them into a row of bits)"""
+        return _thing_obstacles(lambda *out: lib().rdoom_world_thing_obstacles(self._h, *out), len(self.map_things()))
+
     def sense_things(self, states, things, max_range, fov=None, touch_radius=0.19, touch_below=math.inf, touch_above=math.inf, collect=(),
                      offsets=None, collected=None, visible_out=None, touched_out=None, nearest_out=None, new_out=None, stream=None,
                      n=None, n_objects=None, stride=None):
@@ -2870,6 +2902,10 @@ class WorldSet:
                                               ctypes.c_void_p(levels.data_ptr()), a.n, int(a.n_ticks), a.cfg_ptr(), ctypes.c_float(dt),
                                               ctypes.c_void_p(_stream_handle(stream))))
         return a.result()
+
+    def thing_obstacles(self, slot):
+        """rdoom_worldset_level_thing_obstacles: World.thing_obstacles of the level in `slot`"""
+        return _thing_obstacles(lambda *out: lib().rdoom_worldset_level_thing_obstacles(self._h, int(slot), *out), len(self.map_things(slot)))
 
     def cast_rays(self, states, levels, dirs, max_range, offsets=None, frac_out=None, hit_out=None, origin_out=None, vel_out=None,
                   stream=None):

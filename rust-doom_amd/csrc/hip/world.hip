@@ -1149,6 +1149,13 @@ rdoom_status rdoom_world_map_things(const rdoom_world *w, rdoom_map_things *out)
   return RDOOM_OK;
 }
 
+rdoom_status rdoom_world_thing_obstacles(const rdoom_world *w, const uint32_t **out_words, uint32_t *out_n_words) {
+  if (!w || !out_words || !out_n_words) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  *out_words = w->host.thing_obstacles.data();
+  *out_n_words = (uint32_t)w->host.thing_obstacles.size();
+  return RDOOM_OK;
+}
+
 rdoom_status rdoom_world_spawn_table(const rdoom_world *w, rdoom_spawn_table *out) {
   if (!w || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
   fill_spawn(w->host, *out);
@@ -1279,6 +1286,15 @@ rdoom_status rdoom_worldset_level_map_things(const rdoom_worldset *s, uint32_t s
   if (slot >= s->host.levels.size()) return rdoom::fail(RDOOM_BAD_ARG, "slot %u of a set of %zu levels", slot, s->host.levels.size());
   const std::vector<rdoom_thing> &things = s->host.levels[slot].things;
   *out = rdoom_map_things{things.data(), (uint32_t)things.size()};
+  return RDOOM_OK;
+}
+
+rdoom_status rdoom_worldset_level_thing_obstacles(const rdoom_worldset *s, uint32_t slot, const uint32_t **out_words, uint32_t *out_n_words) {
+  if (!s || !out_words || !out_n_words) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (slot >= s->host.levels.size()) return rdoom::fail(RDOOM_BAD_ARG, "slot %u of a set of %zu levels", slot, s->host.levels.size());
+  const std::vector<uint32_t> &words = s->host.levels[slot].thing_obstacles;
+  *out_words = words.data();
+  *out_n_words = (uint32_t)words.size();
   return RDOOM_OK;
 }
 

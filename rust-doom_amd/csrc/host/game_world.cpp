@@ -139,6 +139,11 @@ World build_world(const LoadedWad &w, size_t level_index) {
   }
   World out = b.build();
   out.things = std::move(things);
+  out.thing_obstacles.assign(std::max<size_t>(1, (out.things.size() + 31) / 32), 0u);
+  for (size_t i = 0; i < out.things.size(); i++) {  // the entry that gave the record its category: the first match
+    const ThingMetadata *m = archive.metadata().find_thing(out.things[i].thing_type);
+    if (m && m->obstacle) out.thing_obstacles[i / 32] |= 1u << (i % 32);
+  }
   out.game_objects = (uint32_t)std::max<size_t>(1, analysis.num_objects());
   for (const Trigger &t : analysis.triggers()) {
     rdoom_trigger r{};

@@ -48,6 +48,8 @@ struct World {
   std::vector<rdoom_map_edge> map_edges;
   // the level's thing table (include/rdoom.h "things"): a record per THINGS entry the walk sends down its decor branch, in lump order
   std::vector<rdoom_thing> things;
+  // which of them are solid (include/rdoom.h "solid things"): max(1, ceil(things / 32)) words, bit i % 32 of word i / 32 for thing i
+  std::vector<uint32_t> thing_obstacles;
   // the level's spawn table (include/rdoom.h "spawn"): an entry per floor triangle with an area, in the order of `triangles`
   std::vector<rdoom_spawn_entry> spawn;
   float start_pos[3] = {0, 0, 0};  // the player's start, as the renderer's Builder takes it (rdoom_built_start)

@@ -157,6 +157,7 @@ struct ThingMetadata {
   bool hanging;
   uint32_t radius;
   uint16_t category;  // the array of [things] it was read from, in the order they are merged: RDOOM_THING_DECORATION .. RDOOM_THING_MONSTER
+  bool obstacle = false;  // (not the reference's) the optional key `obstacle`: the thing blocks the player step (include/rdoom.h "solid things")
 };
 struct WadMetadata {
   std::vector<SkyMetadata> sky;

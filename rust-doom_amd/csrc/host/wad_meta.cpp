@@ -394,6 +394,7 @@ WadMetadata WadMetadata::from_text(const std::string &text) {
       tm.hanging = need(t, "hanging", TomlValue::Bool).b;
       tm.radius = (uint32_t)need(t, "radius", TomlValue::Int).i;
       tm.category = category;
+      if (const TomlValue *v = t.find("obstacle")) tm.obstacle = v->type == TomlValue::Bool && v->b;  // optional; absent: false
       m.things.push_back(std::move(tm));
     }
     category++;
