@@ -182,6 +182,10 @@ typedef struct rdoom_path_stats {
   uint64_t masked_fast_pixels;    /* winners alpha-tested by those bodies */
   uint64_t masked_fast_replays;   /* lanes of those bodies that replayed their block through the general rule (tie, 1/w range, certificate) */
   uint64_t masked_general_bodies; /* general bodies that ran on a masked-interior record */
+  /* shared-edge pairs (two triangles that cover a quadrant but for the edge they share), counted under "raster_stats" likewise;
+   * "raster_stats" = 2 counts the default routing (settle_kernel runs), 1 sends every quadrant to the rasteriser's waves: */
+  uint64_t settled_pairs;         /* quadrants settle_kernel proved a pair for: expanded by the tile's wave before its gather */
+  uint64_t raster_pairs;          /* quadrants the tile's wave paired itself, after its gather (the two-entry shortcut) */
 } rdoom_path_stats;
 
 const char *rdoom_last_error(void);
@@ -394,7 +398,7 @@ rdoom_status rdoom_selftest_sincos(uint64_t out_sums[512], uint32_t raw_binade, 
  * shaped but EQUIVALENT path through the kernels -- the image must not change -- so that the rarely taken ones can be
  * forced (tests/test_gpu_debug_paths.py).  Process-wide; read when a batch is created ("vis32", "entry_cap") or
  * rendered (the rest).  Names: no_bins, entry_cap, vis32, leak_mod, frag_nq, frag_bw, frag_chunk, bin_threads,
- * no_cover, no_pair, no_settle, settle_max, raster_stats, no_qtab, keep_vis, qpath, no_split, no_half_runs, frag_count, no_masked_fast
+ * no_cover, no_pair, no_settle, no_settle_pairs, settle_max, raster_stats, no_qtab, keep_vis, qpath, no_split, no_half_runs, frag_count, no_masked_fast
  * (rust-doom_amd/csrc/common.hpp: DebugOptions); "reset" restores the defaults. */
 rdoom_status rdoom_debug_set(const char *name, int32_t value);
 

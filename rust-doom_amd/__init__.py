@@ -184,7 +184,7 @@ class PathStats(ctypes.Structure):
                 ('tile_entries', ctypes.c_uint64), ('quadrants', ctypes.c_uint64), ('described_quadrants', ctypes.c_uint64),
                 ('half_runs', ctypes.c_uint64), ('half_fallbacks', ctypes.c_uint64), ('listed_quads', ctypes.c_uint64),
                 ('masked_fast_bodies', ctypes.c_uint64), ('masked_fast_pixels', ctypes.c_uint64), ('masked_fast_replays', ctypes.c_uint64),
-                ('masked_general_bodies', ctypes.c_uint64)]
+                ('masked_general_bodies', ctypes.c_uint64), ('settled_pairs', ctypes.c_uint64), ('raster_pairs', ctypes.c_uint64)]
 
 
 class HostTimings(ctypes.Structure):

@@ -27,12 +27,14 @@ struct DebugOptions {
   int qpath = 0;         // the whole-quadrant fragment kernel runs first (off by default: measured slower)
   int keep_vis = 0;      // the rasteriser writes the visibility words of every quadrant, also of those the table describes
   int no_pair = 0;       // no two-entry shortcut in the rasteriser (a quadrant shared by two triangles along a common edge takes the general pass)
+  int no_settle_pairs = 0;  // settle_kernel proves no shared-edge pairs (QTAB_PAIR): the rasteriser's waves find them after their gather, as before round 10
   int no_settle = 0;     // no settle_kernel: the rasteriser's waves find the one-triangle quadrants themselves, as before round 5
   int settle_max = 0;    // longest tile list settle_kernel examines (0 = default, raster.hip SETTLE_MAX)
   int no_split = 0;      // no per-quadrant lists for tiles with more than 64 entries: the rasteriser re-gathers such a tile's whole list for every quadrant
   int no_half_runs = 0;  // the fragment kernel lists both quads of a run an edge crosses (no half lanes: fragment.hip), as before round 8
   int frag_count = 0;    // the fragment kernel counts half lanes and listed quads (rdoom_batch_path_stats: half_runs, half_fallbacks, listed_quads)
-  int raster_stats = 0;  // census of the rasteriser's paths on stderr (instrumented instantiation: slower; rdoom_batch_path_stats: masked_fast_*)
+  int raster_stats = 0;  // census of the rasteriser's paths on stderr (instrumented instantiation: slower; rdoom_batch_path_stats: masked_fast_*, *_pairs);
+                         // 1: without settle_kernel (every quadrant is the rasteriser's: the census of everything), 2: with it (the default routing)
   int no_masked_fast = 0;  // masked-interior records take the rasteriser's general rule in every lane (no fast masked body: raster.hip), as before round 9
 };
 DebugOptions debug_options();  // a snapshot taken under the lock rdoom_debug_set writes under (one host thread per GPU may render while a test thread sets hooks)

@@ -11,6 +11,7 @@ constexpr uint32_t MAX_TILES = 8192;     // tiles per frame the binning kernel k
 // tile header word y carries TILE_SPLIT, word x points at (first entry, count) x 4 in the pose's entry array
 // (LONG_LIST 32 / 64 / 128: 64 gives the fastest rasteriser at 1080p, at 320 x 200 and on the large level, profiles/r04_ab.txt, item 7)
 constexpr uint32_t LONG_LIST = 64, TILE_SPLIT = 0x80000000u;
+constexpr int RASTER_CENSUS = 6;  // counters launch_raster hands back under the hook raster_stats
 
 // Kernel 1: vertex stage, triangle setup, near-to-far record order (setup.hip)
 rdoom_status launch_setup(hipStream_t st, uint32_t n_poses, const DeviceLevelView &lv, const PoseConst *poses,
@@ -33,10 +34,13 @@ rdoom_status launch_raster(hipStream_t st, uint32_t n_poses, const DeviceLevelVi
                            int tiles_y, const uint2 *tile_hdr, const uint32_t *entries, uint32_t entry_cap,
                            const uint32_t *overflow, uint32_t *vis, bool vis16, uint32_t *prim_out,
                            uint32_t *qtab,  // qtab (optional): per (pose, tile, quadrant) the record all its pixels show, or NONE
+                           uint2 *qpair,    // beside the table: settle_kernel's pair descriptors, as many (internal to the two kernels)
                            bool skip_described_vis,  // no visibility words for quadrants the table describes (FragmentPlan)
                            bool split_lists,  // the binning kernel stored long lists per quadrant (launch_bin's answer for this render)
                            bool bins_launched,  // the binning kernel ran (its overflow flags are this render's): settle_kernel may read the lists
-                           uint64_t (&masked_census)[4]);  // under the hook raster_stats: fast masked bodies, their winners, replayed lanes, general masked bodies (else zeros)
+                           // under the hook raster_stats (else zeros): fast masked bodies, their winners, replayed lanes, general masked
+                           // bodies; pairs settle_kernel proved and the tile's wave expanded, pairs the wave found itself
+                           uint64_t (&census)[RASTER_CENSUS]);
 // How the fragment kernel will walk a frame of this size, decided ONCE per render from the debug hooks (rasteriser and
 // fragment kernel must agree on who reads the quadrant table): quads per lane, log2(units per block row), blocks per
 // workgroup wave, the test hook leak_mod, and qtab_mode (0: table unused; 1 / 2: a wave block lies in one / two quadrants).

@@ -22,8 +22,11 @@ namespace {
 // counters of the STATS instantiation (launch_raster prints them): [0..19] as before; [20] general bodies on masked-interior
 // records, [21] rows of those that ran the alpha part, [22] pixels alpha-tested there, [23] pixels fetched; [24] fast bodies
 // whose block straddles the bbox in some lane; the fast masked body: [25] bodies, [26] lanes, [27] winners alpha-tested,
-// [28] lanes replayed through the general rule (tie, 1/w range, certificate), [29] winners that survived the alpha test
-constexpr int RASTER_NSTAT = 30;
+// [28] lanes replayed through the general rule (tie, 1/w range, certificate), [29] winners that survived the alpha test;
+// [30] pairs settle_kernel had proven, expanded by the tile's wave; the census of what settle_kernel could take over: [31] two-entry
+// shortcuts taken in tiles whose list it examines, [32] of those, in tiles whose other quadrants inside the frame all took the
+// one-entry or the two-entry shortcut (or came settled): tiles that need no gather once it proves the pairs
+constexpr int RASTER_NSTAT = 33;
 // sum over the active lanes of a small per-lane count (STATS only)
 __device__ __forceinline__ unsigned long long wave_sum_small(uint32_t v) {
   unsigned long long s = 0;
@@ -397,12 +400,25 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {  // (the same red
 // reading the tile's four entries: nothing to do -> it ends after one scalar load; else it passes only the TODO quadrants.
 // (Instantiations that store visibility words or primitive ids for described quadrants -- tests -- ignore this and do everything.)
 // Poses whose bins overflowed are left alone: the rasteriser scans their sorted lists as before.
+//
+// Pairs.  One population of the quadrants left over is as cheap to decide here: the rasteriser's two-entry shortcut along a shared
+// edge (the diagonal of a wall quad, a spoke of a floor fan: 7 % of the passes of a 1080p sweep), which the tile's wave finds only
+// after its gather.  The lane keeps the second-nearest entry B too and the nearest depth among all the others; where the nearest
+// entry A does not cover, it applies the shortcut's conditions to (A, B), with the same corner arguments and the same strictness:
+// each covers the quadrant but for one edge, those two edges have exactly negated coefficients and complementary tie flags, the
+// shared edge function is finite at the corners, everything else lies strictly behind the farther of their farthest depths.  A
+// proven pair gets QTAB_PAIR and a descriptor in qpair[pose][tile][quadrant] -- x: A's record | shared edge of A << 24 | A's tie
+// flag << 26, y: B's record --, from which the tile's wave writes the quadrant's visibility words BEFORE it decides whether to
+// gather (pair_pixels, the shortcut's own expression).  Whatever is not proven stays QTAB_TODO, which is always correct.  The
+// descriptors are read only under the marker, so the array is never cleared.
 // =================================================================================================
 constexpr uint32_t QTAB_TODO = 0xFFFFFFFEu;  // (not NONE, not a record index: the rasteriser replaces every one before anybody else reads the table)
+constexpr uint32_t QTAB_PAIR = 0xFFFFFFFDu;  // (likewise) a pair proven by settle_kernel; the rasteriser expands it and writes NONE
 __global__ __launch_bounds__(256) void settle_kernel(const TriRec *__restrict__ recs, uint32_t cap, uint32_t n_poses, int width, int height,
                                                      int tiles_x, int tiles_y, const uint2 *__restrict__ tile_hdr,
                                                      const uint32_t *__restrict__ entries, uint32_t entry_cap,
-                                                     const uint32_t *__restrict__ overflow, uint32_t *__restrict__ qtab, uint32_t max_list) {
+                                                     const uint32_t *__restrict__ overflow, uint32_t *__restrict__ qtab, uint32_t max_list,
+                                                     uint2 *__restrict__ qpair, uint32_t pairs) {
   const uint32_t T = (uint32_t)(tiles_x * tiles_y);
   const uint32_t pose = blockIdx.z * 8u + (blockIdx.x & 7u);  // a pose's tiles on one XCD, like the rasteriser's
   const uint32_t idx = (blockIdx.x >> 3) * 256u + threadIdx.x, tile = idx >> 2, q = idx & 3u;
@@ -417,7 +433,7 @@ __global__ __launch_bounds__(256) void settle_kernel(const TriRec *__restrict__ 
   if ((hdr.y & TILE_SPLIT) == 0u && hdr.y != 0u && hdr.y <= max_list) {
     const uint32_t *pent = entries + (size_t)pose * entry_cap + hdr.x;
     const float xl = (float)rx0 + 0.5f, xh = (float)rx0 + 31.5f, yl = (float)ry0 + 0.5f, yh = (float)ry0 + 31.5f;
-    uint32_t m1 = NONE, m2 = NONE, best = NONE;
+    uint32_t m1 = NONE, m2 = NONE, m3 = NONE, best = NONE, second = NONE;  // nearest depths: A's, B's, of all the others
     // four entries at a time: their words first, then the depth planes of those that touch my quadrant -- the loads of a group
     // are in flight together (a lane that walked its list one entry at a time spent its life in two dependent round trips per entry)
     for (uint32_t i = 0; i < hdr.y; i += 4u) {
@@ -435,9 +451,11 @@ __global__ __launch_bounds__(256) void settle_kernel(const TriRec *__restrict__ 
         const float zn = fmaf(za, pos(za) ? xl : xh, fmaf(zb, pos(zb) ? yl : yh, zc));
         const uint32_t dn = zn <= 1.0f ? __float2uint_rz(fmaf(fminf(fmaxf(zn, 0.0f), 1.0f), 16777215.0f, 0.5f)) : NONE;
         if (dn < m1) {
-          m2 = m1, m1 = dn, best = e[k] & ENTRY_REC_MASK;
+          m3 = m2, m2 = m1, second = best, m1 = dn, best = e[k] & ENTRY_REC_MASK;
+        } else if (dn < m2) {  // (dn == m1: a tie of the two nearest -- m2 = m1 cannot be strictly behind anything)
+          m3 = m2, m2 = dn, second = e[k] & ENTRY_REC_MASK;
         } else {
-          m2 = min(m2, dn);  // (dn == m1: a tie of the two nearest -- m2 = m1 cannot be strictly behind anything)
+          m3 = min(m3, dn);
         }
       }
     }
@@ -460,15 +478,91 @@ __global__ __launch_bounds__(256) void settle_kernel(const TriRec *__restrict__ 
       const float n2 = fmaf(e2a, pos(e2a) ? xl : xh, fmaf(e2b, pos(e2b) ? yl : yh, e2c));
       const float rwn = fmaf(wa, pos(wa) ? xl : xh, fmaf(wb, pos(wb) ? yl : yh, wc));
       const int qx1 = min(rx0 + 31, width - 1), qy1 = min(ry0 + 31, height - 1);
-      const bool cover = (zn >= 0.0f) & (zf <= 1.0f) & (rwn > 0.0f) & (x0 <= rx0) & (x1 >= qx1) & (y0 <= ry0) & (y1 >= qy1) &
-                         ((c4.y & RASTER_MASKED_INTERIOR) == 0u) & (n0 > 0.0f) & (n1 > 0.0f) & (n2 > 0.0f);
-      if (cover) {
+      const bool common = (zn >= 0.0f) & (zf <= 1.0f) & (rwn > 0.0f) & (x0 <= rx0) & (x1 >= qx1) & (y0 <= ry0) & (y1 >= qy1) &
+                          ((c4.y & RASTER_MASKED_INTERIOR) == 0u);
+      const bool p0 = n0 > 0.0f, p1 = n1 > 0.0f, p2 = n2 > 0.0f;
+      if (common & p0 & p1 & p2) {
         const uint32_t df0 = __float2uint_rz(fmaf(zf, 16777215.0f, 0.5f));  // zf in [0, 1]: the entry covers
         if (m2 > df0) out = best;  // everything else strictly behind its farthest depth: it wins all 1024 pixels
+      } else if (pairs != 0u && second != NONE && common && ((p1 & p2) | (p0 & p2) | (p0 & p1))) {
+        // A covers but for ONE edge (exactly one of p0, p1, p2 fails).  What the pair needs of A: the open edge's three words, its
+        // tie flag, A's farthest depth
+        const uint32_t ei = !p0 ? 0u : (!p1 ? 1u : 2u);
+        const uint32_t a0 = ei == 0u ? c0.x : (ei == 1u ? c0.w : c1.z), a1 = ei == 0u ? c0.y : (ei == 1u ? c1.x : c1.w),
+                       a2 = ei == 0u ? c0.z : (ei == 1u ? c1.y : c2.x);
+        const bool tlA = ((c4.y >> (24u + ei)) & 1u) != 0u;
+        const uint32_t dfA = __float2uint_rz(fmaf(zf, 16777215.0f, 0.5f));  // zf in [0, 1]: the depth range holds over the quadrant
+        // the shared edge function is finite at the four corners, hence (fmaf is monotone in each argument) at every pixel
+        const float fa = __uint_as_float(a0), fb = __uint_as_float(a1), fc = __uint_as_float(a2);
+        const float tl_ = fmaf(fb, yl, fc), th_ = fmaf(fb, yh, fc);
+        const bool finite = ((__float_as_uint(fmaf(fa, xl, tl_)) & 0x7F800000u) != 0x7F800000u) & ((__float_as_uint(fmaf(fa, xh, tl_)) & 0x7F800000u) != 0x7F800000u) &
+                            ((__float_as_uint(fmaf(fa, xl, th_)) & 0x7F800000u) != 0x7F800000u) & ((__float_as_uint(fmaf(fa, xh, th_)) & 0x7F800000u) != 0x7F800000u);
+        // B, by the same tests: covers but for its edge ej, which is A's open edge negated, with the other tie flag
+        uint4 b0, b1, b2, b3;
+        uint2 b4;
+        raster_words(&prec[second], b0, b1, b2, b3, b4);
+        const uint32_t eb[9] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w, b2.x};
+        auto negated = [](uint32_t x, uint32_t y) { return ((x ^ y) == 0x80000000u) | (((x | y) << 1) == 0u); };  // y = -x, or both are zeros
+        bool pB[3], mB[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          const float a = __uint_as_float(eb[3 * k]), b = __uint_as_float(eb[3 * k + 1]), c = __uint_as_float(eb[3 * k + 2]);
+          pB[k] = fmaf(a, pos(a) ? xl : xh, fmaf(b, pos(b) ? yl : yh, c)) > 0.0f;
+          mB[k] = negated(a0, eb[3 * k]) & negated(a1, eb[3 * k + 1]) & negated(a2, eb[3 * k + 2]) & (tlA != (((b4.y >> (24 + k)) & 1u) != 0u));
+        }
+        const bool shared = (mB[0] & pB[1] & pB[2]) | (mB[1] & pB[2] & pB[0]) | (mB[2] & pB[0] & pB[1]);
+        const float zaB = __uint_as_float(b2.y), zbB = __uint_as_float(b2.z), zcB = __uint_as_float(b2.w);
+        const float waB = __uint_as_float(b3.x), wbB = __uint_as_float(b3.y), wcB = __uint_as_float(b3.z);
+        const int x0B = (int)(b3.w & 0xFFFFu), y0B = (int)(b3.w >> 16), x1B = (int)(b4.x & 0xFFFFu), y1B = (int)(b4.x >> 16);
+        const float znB = fmaf(zaB, pos(zaB) ? xl : xh, fmaf(zbB, pos(zbB) ? yl : yh, zcB));
+        const float zfB = fmaf(zaB, pos(zaB) ? xh : xl, fmaf(zbB, pos(zbB) ? yh : yl, zcB));
+        const float rwnB = fmaf(waB, pos(waB) ? xl : xh, fmaf(wbB, pos(wbB) ? yl : yh, wcB));
+        const bool commonB = (znB >= 0.0f) & (zfB <= 1.0f) & (rwnB > 0.0f) & (x0B <= rx0) & (x1B >= qx1) & (y0B <= ry0) & (y1B >= qy1) &
+                             ((b4.y & RASTER_MASKED_INTERIOR) == 0u);
+        if (shared & commonB & finite) {
+          // the farther of the two farthest depths over the quadrant (both in [0, 1]); everything else strictly behind it
+          const uint32_t dfar = max(dfA, __float2uint_rz(fmaf(zfB, 16777215.0f, 0.5f)));
+          if (m3 > dfar) {
+            out = QTAB_PAIR;
+            qpair[((size_t)pose * T + tile) * 4u + q] = make_uint2(best | (ei << 24) | (tlA ? 1u << 26 : 0u), second);
+          }
+        }
       }
     }
   }
   qtab[((size_t)pose * T + tile) * 4u + q] = out;
+}
+
+// The per-pixel part of the two-entry shortcut (see raster_wave_kernel): records A and B cover the lane's 4x4 block but for the
+// edge (ea, eb, ec) they share, so R1 for A's side of that edge names each pixel's winner.  One body for the pair the tile's
+// wave finds itself and for the pair settle_kernel has proven (QTAB_PAIR): the same expression writes the same words.
+template <bool VIS16, bool PRIM>
+__device__ __forceinline__ void pair_pixels(float ea, float eb, float ec, bool tlA, uint32_t rA, uint32_t rB, uint32_t pA, uint32_t pB,
+                                            uint32_t pose, int width, int height, int bx, int by, float pxlo, float pylo,
+                                            uint32_t *__restrict__ vis, uint32_t *__restrict__ prim_out) {
+  if (bx >= width) return;
+  const size_t o0 = ((size_t)pose * (size_t)height + (size_t)by) * (size_t)width + (size_t)bx;
+#pragma unroll
+  for (int ry = 0; ry < 4; ry++) {
+    const float trow = fmaf(eb, pylo + (float)ry, ec);
+    uint32_t w[4];
+    bool in[4];
+#pragma unroll
+    for (int rx = 0; rx < 4; rx++) {
+      const float e = fmaf(ea, pxlo + (float)rx, trow);  // R1 for A's side of the shared edge
+      in[rx] = (e > 0.0f) | ((e == 0.0f) & tlA);
+      w[rx] = in[rx] ? rA : rB;
+    }
+    if (by + ry < height) {
+      const size_t o = o0 + (size_t)(ry * width);
+      if (VIS16)
+        *reinterpret_cast<uint2 *>(reinterpret_cast<uint16_t *>(vis) + o) =
+            make_uint2(__builtin_amdgcn_perm(w[1], w[0], 0x05040100u), __builtin_amdgcn_perm(w[3], w[2], 0x05040100u));
+      else
+        *reinterpret_cast<uint4 *>(vis + o) = make_uint4(w[0], w[1], w[2], w[3]);
+      if (PRIM) *reinterpret_cast<uint4 *>(prim_out + o) = make_uint4(in[0] ? pA : pB, in[1] ? pA : pB, in[2] ? pA : pB, in[3] ? pA : pB);
+    }
+  }
 }
 
 constexpr uint32_t SETTLE_MAX = 32;  // settle_kernel examines whole lists of at most this many entries (a lane walks the list: longer ones are the rasteriser's)
@@ -495,6 +589,7 @@ __global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_ker
                                                              uint32_t *__restrict__ vis,
                                                              uint32_t *__restrict__ prim_out, uint32_t no_cover,
                                                              uint32_t *__restrict__ qtab, uint32_t settled,
+                                                             const uint2 *__restrict__ qpair,
                                                              unsigned long long *__restrict__ stats) {
   unsigned long long st[RASTER_NSTAT] = {};
   __shared__ uint32_t wq[RASTER_WAVES][64];
@@ -530,8 +625,35 @@ __global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_ker
   uint32_t todo = 0xFu;
   if (SKIPVIS && !PRIM && settled != 0u && binned) {
     const uint4 qt = *reinterpret_cast<const uint4 *>(qtab + ((size_t)pose * T + tile) * 4u);  // (uniform address: a scalar load)
+    // Half of the tiles at 1080p end here, so the test is ONE chain: e + 3 wraps the two markers to 1 and 0, NONE to 2 and leaves a
+    // record index at 3 or more -- the smallest of the four is 2 or more iff nothing is TODO and nothing is a PAIR
+    static_assert(QTAB_TODO == NONE - 1u && QTAB_PAIR == NONE - 2u, "the markers sit right below NONE");
+    if (min(min(qt.x + 3u, qt.y + 3u), min(qt.z + 3u, qt.w + 3u)) >= 2u) return;
     todo = (qt.x == QTAB_TODO ? 1u : 0u) | (qt.y == QTAB_TODO ? 2u : 0u) | (qt.z == QTAB_TODO ? 4u : 0u) | (qt.w == QTAB_TODO ? 8u : 0u);
-    if (todo == 0u) return;
+    // Pairs proven by settle_kernel (see there) are expanded HERE, before the wave decides whether to gather: the descriptor and
+    // the three words of A's open edge by scalar loads, then the shortcut's own per-pixel body.  A tile whose undecided quadrants
+    // were all pairs ends without a gather, like a settled one.  (Few values are live yet: the walk's registers are not touched.)
+    const uint32_t pairs = (qt.x == QTAB_PAIR ? 1u : 0u) | (qt.y == QTAB_PAIR ? 2u : 0u) | (qt.z == QTAB_PAIR ? 4u : 0u) | (qt.w == QTAB_PAIR ? 8u : 0u);
+    if (pairs != 0u) {
+#pragma unroll 1
+      for (uint32_t q = 0; q < 4u; q++) {
+        if (((pairs >> q) & 1u) == 0u) continue;
+        const uint2 d = qpair[((size_t)pose * T + tile) * 4u + q];  // (uniform address, as the table's)
+        const uint32_t rA = d.x & ENTRY_REC_MASK, rB = d.y, ei = (d.x >> 24) & 3u;
+        const float *pe = prec[rA].r.e + 3u * ei;
+        const float ea = pe[0], eb = pe[1], ec = pe[2];
+        const int bx = tx0 + (int)(q & 1u) * 32 + lx, by = ty0 + (int)(q >> 1) * 32 + ly;
+        pair_pixels<VIS16, false>(ea, eb, ec, ((d.x >> 26) & 1u) != 0u, rA, rB, 0u, 0u, pose, width, height, bx, by, (float)bx + 0.5f, (float)by + 0.5f, vis,
+                                  nullptr);
+        if (lane == 0) qtab[((size_t)pose * T + tile) * 4u + q] = NONE;  // two records: not described
+      }
+      if (STATS) st[30] += (unsigned long long)__popc(pairs);
+      if (todo == 0u) {
+        if (STATS && lane == 0)
+          for (int k = 0; k < RASTER_NSTAT; k++) atomicAdd(&stats[k], st[k]);
+        return;
+      }
+    }
   }
   // A tile with a long list (more than 64 entries: far geometry, small triangles that touch one quadrant each) comes with a list
   // PER QUADRANT (bin.hip, "split lists"): each quadrant's pass starts with the gather of ITS list -- most of those fit one
@@ -542,6 +664,10 @@ __global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_ker
   const uint32_t *pent = entries + (size_t)pose * entry_cap + hdr.x;  // (a split tile: set per quadrant)
   uint32_t count = split ? 0u : hdr.y;
   bool single = count <= 64u;  // the usual case: one gather serves all four quadrants
+  // STATS: this tile's quadrants inside the frame, those that took the one-entry shortcut (or came settled) and the two-entry one;
+  // no_cover's bits 8.. carry the longest list settle_kernel examines
+  const bool examined = STATS && binned && (hdr_binned.y & TILE_SPLIT) == 0u && hdr_binned.y != 0u && hdr_binned.y <= (no_cover >> 8);
+  uint32_t c_in = 0u, c_one = 0u, c_pair = 0u;
   uint32_t *myq = wq[wave];
   // what lane s keeps of the s-th entry of the current batch: record index, quadrant bits (touches: 0..3, covers:
   // 4..7), the depth plane, the nearest depth over each quadrant
@@ -703,6 +829,7 @@ __global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_ker
   for (int q = 0; q < 4; q++) {
     const int qx0 = tx0 + (q & 1) * 32, qy0 = ty0 + (q >> 1) * 32;  // this quadrant
     if (qx0 >= width || qy0 >= height) continue;                    // entirely outside the frame (partial tiles)
+    if (STATS) c_in++, c_one += ((todo >> q) & 1u) ^ 1u;
     if (((todo >> q) & 1u) == 0u) continue;                         // settled by settle_kernel: its table entry stands
     const int bx = qx0 + lx, by = qy0 + ly;                         // this lane's 4x4 block
     const float pxlo = (float)bx + 0.5f, pxhi = (float)bx + 3.5f, pylo = (float)by + 0.5f, pyhi = (float)by + 3.5f;
@@ -737,7 +864,7 @@ __global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_ker
           const uint32_t df0 = __float2uint_rz(fmaf(zf0, 16777215.0f, 0.5f));
           if ((__ballot(dnq_s <= df0) & touch_s & ~(1ull << s0)) == 0ull) {
             const uint32_t r0 = (uint32_t)__builtin_amdgcn_readlane((int)myrq, (int)s0) & 0xFFFFFFu;
-            if (STATS) st[0] += (unsigned long long)__popcll(touch_s), st[9]++;
+            if (STATS) st[0] += (unsigned long long)__popcll(touch_s), st[9]++, c_one++;
             // the quadrant table: "all 1024 pixels show record r0" -- the fragment kernel's waves then take the record
             // by scalar loads without reading (or comparing) the visibility words of this quadrant
             if (qtab && lane == 0) qtab[((size_t)pose * T + tile) * 4u + (uint32_t)q] = r0;
@@ -820,33 +947,10 @@ __global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_ker
             if (!ok) continue;
             paired = true;
             const uint32_t rA = (uint32_t)__builtin_amdgcn_readlane((int)myrq, (int)s0) & 0xFFFFFFu, rB = (uint32_t)__builtin_amdgcn_readlane((int)myrq, (int)sB) & 0xFFFFFFu;
-            if (STATS) st[0] += (unsigned long long)__popcll(touch_s), st[8]++;
+            if (STATS) st[0] += (unsigned long long)__popcll(touch_s), st[8]++, c_pair++;
             if (qtab && lane == 0) qtab[((size_t)pose * T + tile) * 4u + (uint32_t)q] = NONE;  // two records: not described
-            if (bx < width) {
-              const size_t o0 = ((size_t)pose * (size_t)height + (size_t)by) * (size_t)width + (size_t)bx;
-              const uint32_t pA = PRIM ? (fA & 0xFFFFFFu) : 0u, pB = PRIM ? (fB & 0xFFFFFFu) : 0u;
-#pragma unroll
-              for (int ry = 0; ry < 4; ry++) {
-                const float trow = fmaf(eb, pylo + (float)ry, ec);
-                uint32_t w[4];
-                bool in[4];
-#pragma unroll
-                for (int rx = 0; rx < 4; rx++) {
-                  const float e = fmaf(ea, pxlo + (float)rx, trow);  // R1 for A's side of the shared edge
-                  in[rx] = (e > 0.0f) | ((e == 0.0f) & tlA);
-                  w[rx] = in[rx] ? rA : rB;
-                }
-                if (by + ry < height) {
-                  const size_t o = o0 + (size_t)(ry * width);
-                  if (VIS16)
-                    *reinterpret_cast<uint2 *>(reinterpret_cast<uint16_t *>(vis) + o) =
-                        make_uint2(__builtin_amdgcn_perm(w[1], w[0], 0x05040100u), __builtin_amdgcn_perm(w[3], w[2], 0x05040100u));
-                  else
-                    *reinterpret_cast<uint4 *>(vis + o) = make_uint4(w[0], w[1], w[2], w[3]);
-                  if (PRIM) *reinterpret_cast<uint4 *>(prim_out + o) = make_uint4(in[0] ? pA : pB, in[1] ? pA : pB, in[2] ? pA : pB, in[3] ? pA : pB);
-                }
-              }
-            }
+            pair_pixels<VIS16, PRIM>(ea, eb, ec, tlA, rA, rB, PRIM ? (fA & 0xFFFFFFu) : 0u, PRIM ? (fB & 0xFFFFFFu) : 0u, pose, width, height, bx, by,
+                                     pxlo, pylo, vis, prim_out);
           }
           if (paired) continue;
         }
@@ -1015,6 +1119,7 @@ __global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_ker
       }
     }
   }
+  if (STATS && examined) st[31] += (unsigned long long)c_pair, st[32] += c_pair + c_one == c_in ? (unsigned long long)c_pair : 0ull;
   if (STATS && lane == 0)
     for (int k = 0; k < RASTER_NSTAT; k++) atomicAdd(&stats[k], st[k]);
 }
@@ -1024,9 +1129,9 @@ __global__ __launch_bounds__(64 * RASTER_WAVES, RASTER_OCC) void raster_wave_ker
 rdoom_status launch_raster(hipStream_t st, uint32_t n_poses, const DeviceLevelView &lv, const TriRec *recs,
                            const uint32_t *counts, uint32_t cap, int width, int height, int tiles_x,
                            int tiles_y, const uint2 *tile_hdr, const uint32_t *entries, uint32_t entry_cap,
-                           const uint32_t *overflow, uint32_t *vis, bool vis16, uint32_t *prim_out, uint32_t *qtab,
-                           bool skip_described_vis, bool split_lists, bool bins_launched, uint64_t (&masked_census)[4]) {
-  masked_census[0] = masked_census[1] = masked_census[2] = masked_census[3] = 0u;
+                           const uint32_t *overflow, uint32_t *vis, bool vis16, uint32_t *prim_out, uint32_t *qtab, uint2 *qpair,
+                           bool skip_described_vis, bool split_lists, bool bins_launched, uint64_t (&census)[RASTER_CENSUS]) {
+  for (uint64_t &c : census) c = 0u;
   const uint32_t n = n_poses;
   const uint32_t groups = (n + 7u) / 8u;  // pose groups of eight: one pose per XCD
   if (groups > 65535u || tiles_y > 65535 || (uint64_t)tiles_x * 8ull > 0x7FFFFFFFull)
@@ -1051,20 +1156,22 @@ rdoom_status launch_raster(hipStream_t st, uint32_t n_poses, const DeviceLevelVi
   // settle_kernel first (see there): only where the rasteriser may skip what it settles -- the table is in use, no visibility
   // words or primitive ids are owed for described quadrants, the one-entry shortcut is not switched off by a hook
   const uint32_t max_list = dbg.settle_max > 0 ? (uint32_t)dbg.settle_max : SETTLE_MAX;
-  const bool settle = skip && !prim_out && !dbg.no_settle && !dbg.no_cover && !dbg.raster_stats && bins_launched;
+  // (raster_stats = 1 is the census of EVERY quadrant: no settle_kernel; 2 that of the default routing)
+  const bool settle = skip && !prim_out && !dbg.no_settle && !dbg.no_cover && dbg.raster_stats != 1 && bins_launched;
+  const bool settle_pairs = !dbg.no_pair && !dbg.no_settle_pairs && qpair != nullptr;
   if (settle) {
     const uint32_t T4 = (uint32_t)(tiles_x * tiles_y) * 4u;
     hipLaunchKernelGGL(settle_kernel, dim3(((T4 + 255u) / 256u) * 8u, 1, groups), dim3(256), 0, st, recs, cap, n, width, height, tiles_x, tiles_y, tile_hdr,
-                       entries, entry_cap, overflow, qtab, max_list);
+                       entries, entry_cap, overflow, qtab, max_list, qpair, settle_pairs ? 1u : 0u);
   }
   const dim3 rgrid((uint32_t)tiles_x * 8u, groups, (uint32_t)tiles_y);  // tile rows the slowest dimension (raster_wave_kernel)
   hipLaunchKernelGGL(rk, rgrid, dim3(64 * RASTER_WAVES), 0, st, lv, recs, counts, cap, n, width, height, tiles_x,
-                     tiles_y, tile_hdr, entries, entry_cap, overflow, vis, prim_out, (dbg.no_cover ? 1u : 0u) | (dbg.no_pair ? 2u : 0u) | (dbg.no_masked_fast ? 4u : 0u),
-                     qtab, settle ? 1u : 0u, d_stats.get());
+                     tiles_y, tile_hdr, entries, entry_cap, overflow, vis, prim_out, (dbg.no_cover ? 1u : 0u) | (dbg.no_pair ? 2u : 0u) | (dbg.no_masked_fast ? 4u : 0u) | (max_list << 8),
+                     qtab, settle ? 1u : 0u, qpair, d_stats.get());
   if (d_stats) {
     unsigned long long h[RASTER_NSTAT];
     HIP_TRY(hipMemcpy(h, d_stats.get(), sizeof h, hipMemcpyDeviceToHost));
-    masked_census[0] = h[25], masked_census[1] = h[27], masked_census[2] = h[28], masked_census[3] = h[20];
+    census[0] = h[25], census[1] = h[27], census[2] = h[28], census[3] = h[20], census[4] = h[30], census[5] = h[8];
     {  // census of the tile lists' lengths (a tile with more than 64 entries gets a list per quadrant: bin.hip)
       const size_t nt = (size_t)n * (size_t)(tiles_x * tiles_y);
       std::vector<uint2> hdrs(nt);
@@ -1097,6 +1204,10 @@ rdoom_status launch_raster(hipStream_t st, uint32_t n_poses, const DeviceLevelVi
     fprintf(stderr, "[rdoom stats] sixteen-pixel bodies: %llu in %llu passes that ran any (%.2f per such pass, %.1f lanes each); the most ONE lane needed, summed over those passes: %llu (%.2f per pass) -- "
             "what a body with a per-lane choice of entry would run; all needs / 64: %.2f per pass\n",
             h[2], h[18], h[18] ? (double)h[2] / h[18] : 0.0, h[2] ? (double)h[3] / h[2] : 0.0, h[17], h[18] ? (double)h[17] / h[18] : 0.0, h[18] ? (double)h[3] / 64.0 / h[18] : 0.0);
+    fprintf(stderr, "[rdoom stats] shared-edge pairs: %llu found by the tiles' waves, of which %llu in tiles whose list settle_kernel examines (at most %u entries, "
+            "not split) and %llu of those in tiles where every other quadrant inside the frame took a shortcut or came settled (no gather once the pairs are settled); "
+            "settled pairs expanded %llu (settle_kernel %s)\n",
+            h[8], h[31], max_list, h[32], h[30], settle ? (settle_pairs ? "ran, pairs on" : "ran, pairs off") : "did not run");
     fprintf(stderr, "[rdoom stats] masked-interior records: general bodies %llu (%.4f per pass), rows that ran the alpha part %llu (%.2f per body), pixels alpha-tested %llu, "
             "fetched %llu | fast bodies %llu, of which some lane's block straddles the bbox %llu (%.3f) | fast masked bodies %llu (lanes %llu), winners alpha-tested %llu, "
             "survived %llu, lanes replayed %llu\n",

@@ -74,7 +74,8 @@ struct rdoom_batch {
   bool vis16 = false;  // record indices fit 16 bits: visibility words are u16
   // the last render's FragmentPlan::skip_described_vis: a described quadrant's visibility words are another render's (resolve reads the table)
   bool last_skip_vis = false;
-  uint64_t last_masked_census[4] = {0, 0, 0, 0};  // the last render's census of the rasteriser's masked bodies (hook raster_stats; else zeros)
+  // the last render's census of the rasteriser (hook raster_stats; else zeros): its masked bodies [0..3], settle_kernel's pairs it expanded [4], its own pairs [5]
+  uint64_t last_raster_census[RASTER_CENSUS] = {};
   bool last_frag_count = false;  // the last render's FragmentPlan::count: the fragment kernel counted its half lanes and listed quads
   size_t rgb_bytes = 0;          // of d_rgb
   // the last render was rdoom_batch_render_players: its levels are on the device only (the pinned staging is an older render's)
@@ -124,6 +125,7 @@ struct rdoom_batch {
   DeviceArray<uint32_t> d_vis;       // (u16 words when vis16)
   DeviceArray<uint8_t> d_fb;
   DeviceArray<uint8_t> d_frag_const;  // the fragment kernel's rarely read constants (fragment.hip: FragConst), written on first use
+  DeviceArray<uint2> d_qpair;    // per (pose, tile, quadrant): the pair settle_kernel proved where the table says so (raster.hip: QTAB_PAIR); never cleared
   DeviceArray<uint32_t> d_qtab;  // per (pose, tile, quadrant): the record every pixel of the quadrant shows, or NONE (rasteriser -> fragment kernel)
   DeviceArray<float> d_ndc;  // (ix + 0.5) / (width / 2) - 1 for every column, then (iy + 0.5) / (height / 2) - 1 for every row
   DeviceArray<uint32_t> d_prim;        // allocated by rdoom_batch_enable_primitive_ids
@@ -505,6 +507,7 @@ static rdoom_status batch_create_impl(const rdoom_level *level, uint32_t width, 
   if (rdoom_status rs = b->d_fb.alloc(npx)) return rs;
   if (rdoom_status rs = b->d_frag_const.alloc(fragment_const_bytes())) return rs;
   if (rdoom_status rs = b->d_qtab.alloc(4u * (size_t)b->n_tiles * max_poses)) return rs;
+  if (rdoom_status rs = b->d_qpair.alloc(4u * (size_t)b->n_tiles * max_poses)) return rs;
   // (the rasteriser never writes the entries of quadrants that lie outside the frame: NONE from the start, so that the
   // table is self-consistent for every reader)
   HIP_TRY(hipMemset(b->d_qtab.get(), 0xFF, sizeof(uint32_t) * 4u * (size_t)b->n_tiles * max_poses));
@@ -610,7 +613,7 @@ static rdoom_status queue_pipeline(rdoom_batch *b, uint32_t n, uint32_t kinds_ma
   // bounding box reaches -- they stay uncovered, and the quadrants they lie in simply never count as covered)
   if (rdoom_status rs = launch_raster(st, n, lv->view, b->d_recs.get(), b->d_counts, b->cap, PITCH, H, tiles_x, tiles_y,
                                       b->d_tile_hdr.get(), b->d_entries.get(), b->entry_cap, b->d_overflow.get(), b->d_vis.get(), b->vis16, prim_out, b->d_qtab.get(),
-                                      plan.skip_described_vis, split_lists, bins, b->last_masked_census))
+                                      b->d_qpair.get(), plan.skip_described_vis, split_lists, bins, b->last_raster_census))
     return rs;
   if (marks) HIP_TRY(hipEventRecord(ev[2].get(), st));
   if (rdoom_status rs = launch_fragment(st, n, lv->view, b->d_recs.get(), b->d_counts, b->cap, b->d_poses.get(), W, PITCH, H, tiles_x,
@@ -964,8 +967,9 @@ rdoom_status rdoom_batch_path_stats(rdoom_batch *b, rdoom_path_stats *out) {
       }
     }
     out->tiles = (uint64_t)n * T;
-    out->masked_fast_bodies = b->last_masked_census[0], out->masked_fast_pixels = b->last_masked_census[1];
-    out->masked_fast_replays = b->last_masked_census[2], out->masked_general_bodies = b->last_masked_census[3];
+    out->masked_fast_bodies = b->last_raster_census[0], out->masked_fast_pixels = b->last_raster_census[1];
+    out->masked_fast_replays = b->last_raster_census[2], out->masked_general_bodies = b->last_raster_census[3];
+    out->settled_pairs = b->last_raster_census[4], out->raster_pairs = b->last_raster_census[5];
     if (b->last_frag_count) {  // (rendered under the hook frag_count; zero otherwise)
       uint32_t fc[3];
       HIP_TRY(read_back(b, fc, b->d_frag_const.get() + fragment_counts_offset(), sizeof fc));

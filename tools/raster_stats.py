@@ -30,3 +30,12 @@ batch.render(poses, lights, timed=True)
 print('plain   ', batch.render(poses, lights, timed=True))
 rd.debug_set('raster_stats', 1)
 print('census  ', batch.render(poses, lights, timed=True))
+# shared-edge pairs under the default routing (raster_stats=2: settle_kernel runs) and with settle_kernel proving none
+keys = ('settled_pairs', 'raster_pairs', 'described_quadrants', 'quadrants')
+print("pairs, every quadrant the rasteriser's:", {k: batch.path_stats()[k] for k in keys})
+rd.debug_set('raster_stats', 2)
+print('census 2', batch.render(poses, lights, timed=True))
+print('pairs, default routing:', {k: batch.path_stats()[k] for k in keys})
+rd.debug_set('no_settle_pairs', 1)
+print('census 2', batch.render(poses, lights, timed=True))
+print('pairs, no_settle_pairs=1:', {k: batch.path_stats()[k] for k in keys})
