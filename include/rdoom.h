@@ -1829,11 +1829,69 @@ rdoom_status rdoom_thingset_draw_maps(const rdoom_thingset *things, const rdoom_
  * order -- says obstacle = true; a thing without metadata has a clear bit.  *out_n_words = max(1, ceil(T / 32)) for the level's T
  * things, and the bits at and above T are zero.  rdoom_thing stays as it is: solidity travels in bit rows.  Both work on
  * RDOOM_WORLD_HOST_ONLY handles.  Errors (RDOOM_BAD_ARG): a NULL argument; a slot outside the set.
- * Nothing on the device reads these bits yet: the player step does not see things (DESIGN section 31 has the contract of the step
- * that will, and why it is not here). */
+ * rdoom_world_stamp_things below reads these bits on the device; the player step does not see things (DESIGN section 31 has the
+ * contract of the step that will, and why it is not here). */
 rdoom_status rdoom_world_thing_obstacles(const rdoom_world *world, const uint32_t **out_words, uint32_t *out_n_words);
 rdoom_status rdoom_worldset_level_thing_obstacles(const rdoom_worldset *set, uint32_t slot, const uint32_t **out_words,
                                                   uint32_t *out_n_words);
+
+/* ---- solid things on the grid: a level's obstacles stamped into the area planes -------------------------------
+ * The planes of rdoom_world_draw_area_planes with the cells a solid thing stands on made void, per row and in the row's own game,
+ * so that rdoom_flood_grids, rdoom_flood_grids_octile, rdoom_wall_distance, rdoom_flood_descend*, rdoom_grid_walk_lines,
+ * rdoom_path_straighten and rdoom_world_area_frontiers route round them.  The reference has no counterpart: this header is the
+ * authority.  Every float below is binary32, every operation is rounded once and none is contracted.
+ * rdoom_world_stamp_things / rdoom_worldset_stamp_things.  n rows.  Row p is level L: the world's one level, or slot d_levels[p]
+ * of the set and level L of `things` (the relation of handle and thing set is rdoom_world_sense_things'); L has T things.  cell,
+ * width, height: as rdoom_world_draw_area_planes takes them, and the extents are checked as it checks them.  d_floor, d_ceiling:
+ * n x height x width floats each, the planes of rdoom_world_draw_area_planes at this cell (or any planes of that layout).  The grid
+ * (ix0, iz0, gw, gh) of L is the explored-area contract's.  Cell (ix, iz) with ix < gw and iz < gh has the centre
+ *   xc = ((float)(ix0 + (int32_t)ix) + 0.5f) * cell;   zc = ((float)(iz0 + (int32_t)iz) + 0.5f) * cell
+ * -- rdoom_world_draw_area_planes' own expression.
+ * Candidates.  Thing i < T is a candidate for row p when its bit is set in row L of d_solid (levels x stride words, the bits of
+ * rdoom_world_thing_obstacles; NULL: every thing is solid) and clear in row p of d_hidden (n x stride words, rdoom_world_sense_things'
+ * d_collected as it stands; NULL: nothing is hidden).  Bit i is bit i % 32 of word row * stride + i / 32; only words
+ * [0, ceil(T / 32)) of a row are read, and none is written.
+ * Coverage.  A candidate covers a cell when either holds: with r = radius + grow, ex = xc - x, ez = zc - z,
+ *   ex * ex + ez * ez <= r * r;
+ * or the cell is the thing's own, the one the point (x, z) lies in by the explored-area contract ("Point (x, z) lies in cell"); a
+ * point that lies in no cell has none.  So a solid thing always closes the cell it stands in, however coarse the grid.  An r * r
+ * that overflows to +inf covers every cell.
+ * Blocking.  A covering candidate blocks the cell when dy = f - (base + off(object_id)) satisfies dy >= -block_below and
+ * dy <= block_above: f is the cell's input floor, off() the map contract's on row p of d_object_offsets (NULL: at rest).  Both bounds
+ * are >= 0 and may be +inf: then there is no vertical test for any floor that is a number.  A comparison with a NaN is false: a cell
+ * whose floor is a NaN is never blocked.
+ * Outputs.  d_floor_out and d_ceiling_out (n x height x width floats; both or neither): +inf / -inf where some thing blocks the
+ * cell, elsewhere the input's 32-bit word untouched, NaN payloads and -0 included.  d_index_out (n x height x width int32, may be
+ * NULL): the lowest blocking i, -1 where nothing blocks.  At least one of the planes or the index is given.  Being blocked is an OR
+ * and the index a minimum: neither depends on the order things are visited in, on culling or on how the work is cut.  Elements
+ * outside the level's own gw x gh, and rows whose slot is >= the set's size (seen on the device only), are passed through, index -1.
+ * In place.  A cell's output depends on its own input only: d_floor_out == d_floor together with d_ceiling_out == d_ceiling is
+ * allowed.  Any other overlap of an output's bytes (n x height x width x 4 each) with an input's or another output's is an error.
+ * One launch, asynchronous on `stream`; nothing is allocated, nothing is copied to the host and nothing waits, so the call can be
+ * captured into a graph.  n == 0 queues nothing.
+ * Errors, all RDOOM_BAD_ARG and all checked before anything is queued, in this order.  What needs no handle: NULL params; grow,
+ * block_below or block_above a NaN or negative, or grow not finite; flags not 0; no output at all, or one plane without the other;
+ * (n > 0) a NULL d_floor or d_ceiling; the overlap rule; a zero side; a side above RDOOM_AREA_MAX_SIDE.  Then what reads the handle:
+ * a NULL handle; one created with RDOOM_WORLD_HOST_ONLY or living on another device; a cell the explored-area grid calls reject
+ * (not finite or not > 0, a grid over its limits); width or height below the grid's; (n > 0) NULL d_levels; n x the planes' 64 x 16
+ * cell tiles above 2^31 - 1.  Then what reads the thing set: a NULL set; a set whose levels are not as many as the handle's or that
+ * lives on another device; a stride smaller than the set's words while d_solid or d_hidden is given; n_objects smaller than the
+ * game's objects, or not above the set's largest object_id, while d_object_offsets is given. */
+typedef struct rdoom_stamp_params {
+  float grow;                          /* finite, >= 0: added to every radius (0.19, the body's, stamps inflated obstacles) */
+  float block_below, block_above;      /* >= 0, +inf allowed: how far the floor may lie below / above the thing's live height */
+  uint32_t flags;                      /* 0 */
+} rdoom_stamp_params;
+rdoom_status rdoom_world_stamp_things(const rdoom_world *world, const rdoom_thingset *things, uint32_t n, const float *d_object_offsets,
+                                      uint32_t n_objects, float cell, uint32_t width, uint32_t height, const uint32_t *d_solid,
+                                      const uint32_t *d_hidden, uint32_t stride, const rdoom_stamp_params *params, const float *d_floor,
+                                      const float *d_ceiling, float *d_floor_out, float *d_ceiling_out, int32_t *d_index_out,
+                                      void *stream);
+rdoom_status rdoom_worldset_stamp_things(const rdoom_worldset *set, const rdoom_thingset *things, const uint32_t *d_levels, uint32_t n,
+                                         const float *d_object_offsets, uint32_t n_objects, float cell, uint32_t width, uint32_t height,
+                                         const uint32_t *d_solid, const uint32_t *d_hidden, uint32_t stride,
+                                         const rdoom_stamp_params *params, const float *d_floor, const float *d_ceiling,
+                                         float *d_floor_out, float *d_ceiling_out, int32_t *d_index_out, void *stream);
 
 #ifdef __cplusplus
 }

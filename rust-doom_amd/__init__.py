@@ -123,6 +123,9 @@ MAP_COLORS = _map_colors()  # (256, 3) uint8: torch.from_numpy(MAP_COLORS).cuda(
 MAP_THING = 16
 THING_MARKS_OVER = 1
 THING_MARKS = np.dtype([('min_radius', '<f4'), ('codes', 'u1', 8), ('flags', '<u4')])
+# rdoom_world_stamp_things (World.stamp_things): its parameters, and the cells (across, down) of the tile one workgroup takes (kernels.hpp)
+STAMP_PARAMS = np.dtype([('grow', '<f4'), ('block_below', '<f4'), ('block_above', '<f4'), ('flags', '<u4')])
+STAMP_TILE = (64, 16)
 assert THING_MARKS.itemsize == 16
 
 
@@ -231,7 +234,8 @@ API_SYMBOLS = [
     'rdoom_world_map_things', 'rdoom_worldset_level_map_things', 'rdoom_thingset_create', 'rdoom_thingset_destroy', 'rdoom_thingset_info',
     'rdoom_world_sense_things', 'rdoom_worldset_sense_things',
     'rdoom_built_decor_things', 'rdoom_level_set_decor_things', 'rdoom_batch_set_hidden_things', 'rdoom_thingset_draw_maps',
-    'rdoom_world_thing_obstacles', 'rdoom_worldset_level_thing_obstacles']
+    'rdoom_world_thing_obstacles', 'rdoom_worldset_level_thing_obstacles',
+    'rdoom_world_stamp_things', 'rdoom_worldset_stamp_things']
 
 _lib = None
 
@@ -2322,6 +2326,97 @@ def inflate_grids(floor, ceiling, radius, cell, clearance=0.56, edge_open=False,
     return (floor_out, ceiling_out) if pd is None else (floor_out, ceiling_out, dist2_out)
 
 
+class StampParams(ctypes.Structure):
+    """rdoom_stamp_params (STAMP_PARAMS is the same record for numpy)"""
+    _fields_ = [('grow', ctypes.c_float), ('block_below', ctypes.c_float), ('block_above', ctypes.c_float), ('flags', ctypes.c_uint32)]
+
+
+def _stamp_things(call, levels, floor, ceiling, things, cell, solid, hidden, offsets, grow, block_below, block_above, floor_out, ceiling_out,
+                  index_out, stream, n, n_objects, stride):
+    """World.stamp_things / WorldSet.stamp_things: the checks and the launch; call(levels, n, offsets, n_objects, cell, width, height,
+    solid, hidden, stride, params, floor, ceiling, floor_out, ceiling_out, index_out, stream) is the C entry point with its handle and
+    the thing set bound"""
+    import torch
+    if not isinstance(things, DeviceThings):
+        raise ValueError('things must be a DeviceThings')
+    rows, height, width = _flood_inputs(floor, ceiling, None)
+    n = rows if n is None else int(n)
+    if not 0 <= n <= rows:
+        raise ValueError('n = %d, but the planes have %d rows' % (n, rows))
+    raw = lambda t: isinstance(t, (int, np.integer)) and not isinstance(t, bool)
+    if levels is not None and not raw(levels) and (levels.element_size() != 4 or levels.numel() < n):
+        raise ValueError('levels must hold one 32-bit slot per row (%d), got %s %s' % (n, levels.dtype, tuple(levels.shape)))
+    if solid is not None and not raw(solid) and solid.dim() == 1:
+        solid = solid.reshape(1, -1)
+    for r, what, need in ((solid, 'solid', things.n_levels), (hidden, 'hidden', n)):
+        if r is None:
+            continue
+        if raw(r):
+            if stride is None:
+                raise ValueError('stride is needed with a raw %s pointer' % what)
+            continue
+        if r.element_size() != 4 or r.dtype.is_floating_point or r.dim() != 2:
+            raise ValueError('%s must be a 32-bit integer (rows, words) tensor' % what)
+        if int(r.shape[0]) < need:
+            raise ValueError('the %s tensor has %d rows, the call needs %d' % (what, int(r.shape[0]), need))
+        if stride is not None and int(stride) != int(r.shape[1]):
+            raise ValueError('stride %d, but the %s rows are %d words long' % (int(stride), what, int(r.shape[1])))
+        stride = int(r.shape[1])
+    stride = 0 if stride is None else int(stride)
+    n_obj = 0
+    if offsets is not None:
+        if raw(offsets):
+            if n_objects is None:
+                raise ValueError('n_objects is needed with a raw offsets pointer')
+            n_obj = int(n_objects)
+        else:
+            if offsets.dim() != 3 or int(offsets.shape[0]) < n or offsets.shape[2] != 3 or offsets.dtype != torch.float32:
+                raise ValueError('offsets must be a float32 (n, n_objects, 3) tensor for %d rows, got %s' % (n, tuple(offsets.shape)))
+            n_obj = int(offsets.shape[1])
+    wants_index = index_out is not None and index_out is not False
+    if (floor_out is False) != (ceiling_out is False) or (floor_out is None) != (ceiling_out is None):
+        raise ValueError('floor_out and ceiling_out go together: both given, both None (allocated) or both False (no planes)')
+    if floor_out is False:
+        if not wants_index:
+            raise ValueError('nothing asked for: no planes and no index_out')
+        floor_out = ceiling_out = pf = pc = None
+    else:
+        floor_out, pf = _plane_out(floor_out, floor, 'floor_out')
+        ceiling_out, pc = _plane_out(ceiling_out, ceiling, 'ceiling_out')
+    if index_out is True:
+        index_out = torch.empty((rows, height, width), dtype=torch.int32, device=floor.device)
+    elif not wants_index:
+        index_out = None
+    elif not raw(index_out) and (not isinstance(index_out, torch.Tensor) or index_out.dtype != torch.int32):
+        raise ValueError('index_out must be True, an int32 (n, height, width) tensor or a device pointer')
+    cells = n * height * width
+    params = StampParams(grow, block_below, block_above, 0)
+    v = ctypes.c_void_p
+    _check(call(v(_pointer(levels, n * 4, 'levels')), n, v(_pointer(offsets, n * n_obj * 12, 'offsets')), n_obj, ctypes.c_float(cell), width, height,
+                v(_pointer(solid, things.n_levels * stride * 4, 'solid')), v(_pointer(hidden, n * stride * 4, 'hidden')), stride, ctypes.byref(params),
+                v(floor.data_ptr()), v(ceiling.data_ptr()), v(pf), v(pc), v(_pointer(index_out, cells * 4, 'index_out')), v(_stream_handle(stream))))
+    if floor_out is None:
+        return index_out
+    return (floor_out, ceiling_out, index_out) if index_out is not None else (floor_out, ceiling_out)
+
+
+_STAMP_DOC = """makes void (+inf / -inf) the cells of floor and ceiling -- draw_area_planes' float32 (n, H, W) tensors at
+        this `cell` -- that a solid thing of `things` (a DeviceThings) stands on, per row and in the row's own game, so that
+        inflate_grids, flood_grids, flood_grids_octile, descend_grids, walk_lines, straighten_paths and area_frontiers route round
+        them.  A thing covers the cells whose centre lies within radius + grow of it, and always the cell it stands in.  solid: None
+        (every thing) or an int32 (levels, words >= things.words()) GPU tensor of obstacle bits, one row a level of the set --
+        torch.from_numpy(pack_things(world.thing_obstacles())).cuda(); hidden: None or sense_things' `collected` (n, words) tensor as it
+        stands: a thing row p has collected no longer blocks row p, and only row p.  offsets: None (at rest) or step_game's tensor:
+        a thing on a lift rides it.  block_below / block_above: how far the cell's floor may lie below / above the thing's live
+        height for the thing to block it (inf: no vertical test).  floor_out / ceiling_out: None allocates; the inputs themselves
+        stamp in place (no other overlap is allowed); False for both: no planes, the index alone.  index_out: None / False, True
+        (allocated) or an int32 (n, H, W) tensor: the lowest blocking thing of each cell, -1 where none blocks.  Every other word
+        passes through untouched.  solid, hidden, offsets and the outputs may instead be raw device pointers (ints; then stride,
+        and with offsets n_objects, must be given); n: the rows to stamp when fewer than the planes'.  Stamp with grow=0 before
+        inflate_grids, or with grow=0.19 (the body's radius) without it.  Returns what was asked for: (floor, ceiling),
+        (floor, ceiling, index) or index.  One launch, asynchronous on `stream`; it can be captured into a graph."""
+
+
 def _area_frontiers(call, words, levels, area, dist, cell, cell_out, dist_out, count_out, mask_out, stream):
     """World.area_frontiers / WorldSet.area_frontiers: the checks and the launch; call(levels, n, cell, width, height, area, stride,
     dist, cell_out, dist_out, count_out, mask_out, stream) is the C entry point with its handle bound.  Returns cell_out, or a tuple
@@ -2666,6 +2761,14 @@ class World:
             raise ValueError('things must be a DeviceThings')
         return things.draw_maps(states, width, height, scale, **kw)
 
+    def stamp_things(self, floor, ceiling, things, cell, solid=None, hidden=None, offsets=None, grow=0.0, block_below=math.inf,
+                     block_above=math.inf, floor_out=None, ceiling_out=None, index_out=None, stream=None, n=None, n_objects=None, stride=None):
+        L = lib()
+        return _stamp_things(lambda lv, *rest: L.rdoom_world_stamp_things(self._h, getattr(things, '_h', None), *rest), None, floor, ceiling,
+                             things, cell, solid, hidden, offsets, grow, block_below, block_above, floor_out, ceiling_out, index_out, stream, n,
+                             n_objects, stride)
+    stamp_things.__doc__ = 'rdoom_world_stamp_things: ' + _STAMP_DOC
+
     # ---- sectors -----------------------------------------------------------------------------------------------------------
     def map_sectors(self):
         """a copy of rdoom_world_map_sectors: the level's sector table, a MapSectors of (sectors, leaf_sector, leaf_edges, edges)"""
@@ -2966,6 +3069,15 @@ class WorldSet:
         if not isinstance(things, DeviceThings):
             raise ValueError('things must be a DeviceThings')
         return things.draw_maps(states, width, height, scale, levels=levels, **kw)
+
+    def stamp_things(self, levels, floor, ceiling, things, cell, solid=None, hidden=None, offsets=None, grow=0.0, block_below=math.inf,
+                     block_above=math.inf, floor_out=None, ceiling_out=None, index_out=None, stream=None, n=None, n_objects=None, stride=None):
+        L = lib()
+        return _stamp_things(lambda *rest: L.rdoom_worldset_stamp_things(self._h, getattr(things, '_h', None), *rest), levels, floor, ceiling,
+                             things, cell, solid, hidden, offsets, grow, block_below, block_above, floor_out, ceiling_out, index_out, stream, n,
+                             n_objects, stride)
+    stamp_things.__doc__ = 'rdoom_worldset_stamp_things (levels: a GPU tensor of one 32-bit slot per row; slot l of `things` and row l of ' \
+        '`solid` are the level in slot l; a row whose slot is outside the set passes through): ' + _STAMP_DOC
 
     def map_sectors(self, slot):
         """a copy of rdoom_worldset_level_map_sectors: the level's sector table, a MapSectors of (sectors, leaf_sector, leaf_edges, edges)"""

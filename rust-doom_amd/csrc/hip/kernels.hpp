@@ -339,4 +339,20 @@ struct ThingSenseArgs {
   uint32_t collect_mask;
 };
 
+// Kernel 26: a level's solid things stamped into the area planes (stamp.hip; include/rdoom.h "solid things on the grid" has the
+// contract).  One 256-thread workgroup per STAMP_TILE_X x STAMP_TILE_Y tile of one row's planes; a lane is a column, a thread takes
+// four cells of it.
+constexpr uint32_t STAMP_TILE_X = 64, STAMP_TILE_Y = 16;
+struct StampArgs {
+  const rdoom_thing *things;      // the set's records, level after level
+  const float *offsets;           // n x n_objects x xyz, or null
+  const uint32_t *solid;          // levels x stride words, or null: every thing is solid
+  const uint32_t *hidden;         // n x stride words, or null: nothing is hidden
+  const uint32_t *floor, *ceiling;       // n x height x width words each: the planes, read as the words they are
+  uint32_t *floor_out, *ceiling_out;     // n x height x width each, or both null; the inputs themselves: in place
+  int32_t *index_out;             // n x height x width, or null
+  uint32_t n_objects, stride, width, height, tiles_x, tiles;  // tiles: per row of planes
+  float cell, grow, below, above; // below = -block_below
+};
+
 }  // namespace rdoom_dev

@@ -1,5 +1,6 @@
 // The device thing set (include/rdoom.h "things"): the handle things.hip creates and destroys, and that the sensing launches
-// (things.hip) and the thing maps (thingmap.hip) read.  One definition, for player_quat.hpp's reason.
+// (things.hip), the thing maps (thingmap.hip) and the stamp into the area planes (stamp.hip) read.  One definition, for
+// player_quat.hpp's reason.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-// What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip), the explored area's (area.hip), the sectors' (sectors.hip), the spawn's (spawn.hip), the floods' (flood.hip), the goal distance's (goal.hip), the path unit's (path.hip) and the thing maps' (thingmap.hip) share: the pick of a lane's level,
+// What the world's kernels (world.hip), the map's (automap.hip), the seen lines' (reveal.hip), the explored area's (area.hip), the sectors' (sectors.hip), the spawn's (spawn.hip), the floods' (flood.hip), the goal distance's (goal.hip), the path unit's (path.hip), the thing maps' (thingmap.hip) and the stamp's (stamp.hip) share: the pick of a lane's level,
 // a wave's maximum and sum and the append into a list in LDS, what the map units read of a line, the checked launch, the device
 // check of a handle, the checks of a fan, of a row of offsets and of a map view, and the map's side of a world handle (its
 // tables own their device memory: device_memory.hpp).  (The sight pass of reveal.hip and area.hip is sight.hpp's.)
