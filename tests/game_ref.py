@@ -16,25 +16,37 @@ from util import restatement_lib
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, 'game_restatement.c')
 F = np.float32
-_lib = None
+_libs = {}
 _lock = threading.Lock()
 TYPES = {'WalkOver': rd.TRIGGER_WALK_OVER, 'Push': rd.TRIGGER_PUSH, 'Switch': rd.TRIGGER_SWITCH, 'Gun': rd.TRIGGER_GUN,
          'Any': rd.TRIGGER_ANY}
 
 
-def lib():
-    """the restatement as a shared library, its prototypes declared"""
-    global _lib
+def census(reset=False):
+    """{outcome: count}: what the ticks stepped through lib(census=True) took since the last reset (a table of its own: this
+    library carries its own copy of world_restatement.c)"""
+    out = world_ref.census_read(lib(census=True))
+    if reset:
+        lib(census=True).rs_census_reset()
+    return out
+
+
+def lib(census=False):
+    """the restatement as a shared library, its prototypes declared; census=True: the build with world_restatement.c's census"""
     with _lock:
-        if _lib is None:
-            L = restatement_lib(SRC, [world_ref.SRC, os.path.join(HERE, 'sincos_restatement.h')])
+        if census not in _libs:
+            deps = [world_ref.SRC, os.path.join(HERE, 'sincos_restatement.h')]
+            L = restatement_lib(SRC, deps, flags=world_ref.CENSUS_FLAGS, tag=world_ref.CENSUS_TAG) if census else \
+                restatement_lib(SRC, deps)
+            if census:
+                world_ref.declare_census(L)
             L.rs_game_step.restype = None
             L.rs_game_step.argtypes = [ctypes.c_void_p] * 2 + [ctypes.c_uint32] + [ctypes.c_void_p] * 4 + [ctypes.c_uint32] * 4 + \
                 [ctypes.c_void_p, ctypes.c_float, ctypes.c_void_p, ctypes.c_uint32] + [ctypes.c_void_p] * 4
             L.rs_object_modelview.restype = None
             L.rs_object_modelview.argtypes = [ctypes.c_void_p, ctypes.c_float, ctypes.c_float, ctypes.c_void_p, ctypes.c_void_p]
-            _lib = L
-    return _lib
+            _libs[census] = L
+    return _libs[census]
 
 
 def _line(a, b):  # Line2f::from_two_points (math/src/line.rs:12-33) in binary32
@@ -111,9 +123,11 @@ def triggers(wad_path, meta_path, index):
 
 
 class RefGame:
-    """N games of the restatement on a RefWorld; state arrays are numpy, advanced by step()"""
+    """N games of the restatement on a RefWorld; state arrays are numpy, advanced by step(); census=True: stepped in the build
+    that counts the step's branch outcomes (read them with game_ref.census())"""
 
-    def __init__(self, ref_world, trig, effs, n, n_objects):
+    def __init__(self, ref_world, trig, effs, n, n_objects, census=False):
+        self.L = lib(census)
         self.w, self.trig, self.effs, self.n, self.n_objects = ref_world, np.ascontiguousarray(trig), np.ascontiguousarray(effs), n, n_objects
         self.order = np.tile(np.arange(len(trig), dtype=np.uint32), (n, 1)).copy()
         self.counts = np.full(n, len(trig), np.uint32)
@@ -131,7 +145,7 @@ class RefGame:
 
         def run(r):
             a, b = r
-            lib().rs_game_step(ctypes.c_void_p(self.w.h.value), p(self.trig), len(self.trig), p(self.effs), p(states), p(inputs), p(acts),
+            self.L.rs_game_step(ctypes.c_void_p(self.w.h.value), p(self.trig), len(self.trig), p(self.effs), p(states), p(inputs), p(acts),
                                n, a, b - a, len(inputs), p(cfg), dt, p(self.offsets), self.n_objects, p(self.order), p(self.counts),
                                p(self.act), p(self.aflags))
         world_ref._chunked(run, n, threads)

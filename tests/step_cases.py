@@ -1,7 +1,9 @@
 """The shared cases of the player step away from its default config and tick length: the configs, the tick lengths, the scripted
 inputs and players of tests/test_gpu_world.py (moved here; that file imports them back), and the cases of the float64 model
 (tests/step_model.py) in room A of the analytic level.  Used by tests/test_step_configs_host.py, tests/test_step_model_host.py,
-tests/gpu_step_child.py and tests/golden/make_step_model_error.py.  Nothing here needs torch or a device."""
+tests/gpu_step_child.py and tests/golden/make_step_model_error.py.  Also the players of tests/test_gpu_game.py and
+tests/test_gpu_worldset.py, and the `rare` family: the branch outcomes of the step that none of those inputs takes
+(tests/step_census.py, tests/test_gpu_step_rare.py).  Nothing here needs torch or a device."""
 import os
 
 import numpy as np
@@ -379,6 +381,30 @@ def game_setup(directory, n, seed):
     return wad, ref, trig, effs, n_obj, st, inp, act
 
 
+SET = [0, 1, 2]  # the three-level set of tests/test_gpu_worldset.py
+
+
+def set_players(exits, n, seed, slots=SET, device=True):
+    """n players: a third walking at an exit from 0.45 in front of it, the rest at their level's start; random slots of `slots`.
+    The players of tests/test_gpu_worldset.py (moved here; that file imports them back); device=False builds the set on the host"""
+    wad_path, meta_path, lines = exits
+    rng = np.random.default_rng(seed)
+    lv = rng.choice(np.arange(len(slots)), n)
+    ws = rd.Wad(wad_path, meta_path).build_world_set(slots, device=device)
+    st = ws.start_states(lv)
+    at_exit = rng.random(n) < 0.35
+    for p in np.nonzero(at_exit)[0]:
+        _, xz, yaw, y = lines[slots[lv[p]]]
+        st[p]['pos'] = (xz[0], y + F(0.25), xz[1])
+        st[p]['yaw'] = yaw + F(rng.normal(scale=0.05))
+    inp, act = game_script(n, 600, seed + 1)
+    walk = at_exit[None, :] & (np.arange(600) < 40)[:, None]  # the exit walkers go forward for 40 ticks first
+    inp['movement'][..., 0] = np.where(walk, 0.0, inp['movement'][..., 0])
+    inp['movement'][..., 1] = np.where(walk, -1.0, inp['movement'][..., 1])
+    inp['look'] = np.where(walk[..., None], 0.0, inp['look'])
+    return ws, st, lv, inp, act
+
+
 def door_setup(directory, key):
     """Players 0.45 in front of the patched E1M1's manual doors (a Push line with one rising effect), four a door, facing it;
     each pushes once, on tick 3, and stands.  The run ends when the lowest door is half open.  By the restatement alone, a tick
@@ -418,3 +444,82 @@ def door_setup(directory, key):
     moving = (fired >= 0) & ((rg.aflags[np.arange(n), obj] & 1) != 0) & (speed * (n_ticks - fired - 1) * dt < first)
     return dict(wad=wad, trig=trig, effs=effs, pick=pick, obj=obj, states=st, inputs=inp, actions=act, config=cfg, fired=fired,
                 moving=moving, final=s, offsets=rg.offsets.copy(), speed=speed, first=first)
+
+
+# ---- the rare family: one small constructed case per branch outcome of the step that the inputs above never take ---------------
+# (the census of tests/world_restatement.c under -DRS_CENSUS says which: tests/test_step_census_host.py).  Every case is at most 65
+# players and 120 ticks, is placed on E1M1 (level 0) or the analytic level (level 1) of the test IWAD, and names the outcomes it
+# exists for; tests/test_gpu_step_rare.py steps each on the device.
+RARE_DT = DTS['30']
+# Players that run clip()'s 100 sweeps out (RDOOM_PLAYER_DIVERGED) on E1M1 at dt = 1/30: (pos, vel, yaw).  Found by the
+# restatement alone: 400 000 players at floor centroids + (N(0, 0.3), 0.33, N(0, 0.3)) with a horizontal velocity of 8, 10 or 30
+# units a second in a random direction, one tick of 1/30 s; 237 set the flag in their first tick and 153 more within three.  What
+# they have in common: the sphere comes to rest against two edges of a stair or a corner whose contact normals are 6 to 10 degrees
+# apart, each sweep ends 0.001 short of one of them after a contact time of about 0.002 -- so time_left hardly shrinks -- and the
+# velocity loses only the factor cos(angle) a sweep: after 100 sweeps two thirds of the speed and half of the tick are left.
+DIVERGING = [
+    ((-18.5654202, 0.810000002, -26.778595), (-1.32662141, 0, -7.88923788), -2.85607004),     # speed 8
+    ((-9.6081028, 0.0100000203, -12.2565155), (3.6876936, 0, -7.09936047), 0.0372912399),     # speed 8
+    ((-12.2681561, 0.170000017, -8.18871498), (-6.15717983, 0, -7.87966633), 0.364877284),    # speed 10
+    ((-21.9377422, 0.810000002, -4.54011774), (-7.68394756, 0, 6.39976168), -1.62300634),     # speed 10
+    ((-10.9672194, 0.649999976, -18.4684296), (-26.8451271, 0, -13.3917561), -1.35087621),    # speed 30
+    ((-18.3714523, 0.810000002, -26.0473499), (27.3320084, 0, -12.367754), -1.19544041),      # speed 30
+]
+# ... and players that set it in their second or third tick, not their first
+DIVERGING_LATE = [
+    ((-7.62000036, 0.810000002, -6.49035549), (7.99831438, 0, 0.164220482), -0.435841709),    # speed 8
+    ((-10.9794731, 0.649999976, -18.2424927), (-5.77771616, 0, -8.1619854), -0.0327656679),   # speed 10
+    ((-5.59885693, 0.810000002, -12.0516033), (-28.0457478, 0, 10.6506329), -1.94203734),     # speed 30
+]
+
+
+class Rare:
+    """a case of the rare family: `states` stepped over `inputs` (ticks, n) on level `level` of the test IWAD with the config
+    `config` (a name of CONFIGS) at tick length `dt`; `outcomes` the census names it exists for"""
+
+    def __init__(self, name, outcomes, level, states, inputs, config='default', dt=RARE_DT):
+        self.name, self.outcomes, self.level, self.states, self.inputs = name, tuple(outcomes), level, states, inputs
+        self.config_name, self.dt = config, dt
+        assert len(states) <= 65 and len(inputs) <= 120 and inputs.shape[1] == len(states), name
+
+    @property
+    def config(self):
+        return config(CONFIGS[self.config_name])
+
+
+def _placed(rows, flags=None):
+    """PLAYER_STATE records of (pos, vel, yaw) rows"""
+    st = rd.player_states(np.array([r[0] for r in rows], F), np.array([r[2] for r in rows], F),
+                          flags=rd.PLAYER_CLIP if flags is None else np.asarray(flags, np.uint32))
+    st['vel'] = np.array([r[1] for r in rows], F)
+    return st
+
+
+def diverging_states():
+    """the players of DIVERGING on E1M1: each sets RDOOM_PLAYER_DIVERGED in its first tick of 1/30 s"""
+    return _placed(DIVERGING)
+
+
+def rare():
+    """[Rare]: the family, in a fixed order"""
+    out = []
+    # clip()'s loop runs its 100 sweeps: in the first tick, and in a later one; then ordinary ticks with the flag set
+    st = _placed(DIVERGING + DIVERGING_LATE)
+    # (their sweeps end on the vertices and edges of triangles whose planes the sphere overlaps: those winners, inside a tick)
+    out.append(Rare('diverged', ['clip_diverged', 'clip_diverged_already', 'sweep_vertex_wins', 'sweep_edge_wins', 'tri_overlap'], 0,
+                    st, np.zeros((6, len(st)), rd.PLAYER_INPUT)))
+    # looking down until the pitch stops at -(pi/2 - 1e-2) (looking up: the scripts above), walking, flying and with clipping off
+    centre = (ROOM_CENTRE, ROOM_FLOOR + 0.325, ROOM_CENTRE)
+    st = _placed([(centre, (0, 0, 0), 0.3 * k) for k in range(6)],
+                 flags=[rd.PLAYER_CLIP, rd.PLAYER_CLIP | rd.PLAYER_FLY, 0, rd.PLAYER_CLIP, rd.PLAYER_CLIP | rd.PLAYER_FLY, 0])
+    inp = np.zeros((40, 6), rd.PLAYER_INPUT)
+    inp['look'][:, :3, 1], inp['look'][:, 3:, 1] = 0.09, -0.09  # 18 ticks to the limit, then held against it
+    inp['movement'][:, :, 1] = -1.0
+    out.append(Rare('pitch_low', ['pitch_clamped_low', 'pitch_clamped_high'], MODEL_LEVEL, st, inp))
+    # a config without air drag: a player in the air (walking or with clipping off) has no slowdown at all while it moves
+    st = _placed([((ROOM_CENTRE, ROOM_FLOOR + 0.85, ROOM_CENTRE), (1.0, 0.0, 0.5), 0.4 * k) for k in range(4)],
+                 flags=[rd.PLAYER_CLIP, 0, rd.PLAYER_CLIP, 0])
+    inp = np.zeros((30, 4), rd.PLAYER_INPUT)
+    inp['movement'][:, 2:, 1] = -1.0
+    out.append(Rare('no_drag', ['drag_norm_zero'], MODEL_LEVEL, st, inp, config='all_b'))
+    return out

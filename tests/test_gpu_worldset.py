@@ -12,6 +12,7 @@ import rust_doom_amd as rd
 import world_ref
 import worldset_ref
 from test_game_host import patched_variant
+from step_cases import set_players as _set_players
 from test_gpu_game import _script, _seed
 from util import ROOT, render_checked
 
@@ -32,23 +33,7 @@ def _u32(a):
 
 
 def _players(exits, n, seed, slots=SET):
-    """n players: a third walking at an exit from 0.45 in front of it, the rest at their level's start; random slots of `slots`"""
-    wad_path, meta_path, lines = exits
-    rng = np.random.default_rng(seed)
-    lv = rng.choice(np.arange(len(slots)), n)
-    ws = rd.Wad(wad_path, meta_path).build_world_set(slots)
-    st = ws.start_states(lv)
-    at_exit = rng.random(n) < 0.35
-    for p in np.nonzero(at_exit)[0]:
-        _, xz, yaw, y = lines[slots[lv[p]]]
-        st[p]['pos'] = (xz[0], y + F(0.25), xz[1])
-        st[p]['yaw'] = yaw + F(rng.normal(scale=0.05))
-    inp, act = _script(n, 600, seed + 1)
-    walk = at_exit[None, :] & (np.arange(600) < 40)[:, None]  # the exit walkers go forward for 40 ticks first
-    inp['movement'][..., 0] = np.where(walk, 0.0, inp['movement'][..., 0])
-    inp['movement'][..., 1] = np.where(walk, -1.0, inp['movement'][..., 1])
-    inp['look'] = np.where(walk[..., None], 0.0, inp['look'])
-    return ws, st, lv, inp, act
+    return _set_players(exits, n, seed, slots)  # (moved to step_cases; the same bytes)
 
 
 def test_set_step_matches_the_restatement(exits):

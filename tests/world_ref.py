@@ -13,19 +13,48 @@ from util import restatement_lib
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, 'world_restatement.c')
-_lib = None
+_libs = {}
 _lock = threading.Lock()
+CENSUS_FLAGS, CENSUS_TAG = ['-DRS_CENSUS'], '_census'  # the build that counts the step's branch outcomes (world_restatement.c)
 
 NODE = np.dtype([('origin', '<f4', 2), ('displace', '<f4', 2), ('length', '<f4'), ('positive', '<i4'), ('negative', '<i4')])
 assert NODE == rd.WORLD_NODE
 
 
-def lib():
-    """the restatement as a shared library, its prototypes declared"""
-    global _lib
+def declare_census(L):
+    """the prototypes of a census build's table"""
+    L.rs_census_count.restype = ctypes.c_uint32
+    L.rs_census_name.restype = ctypes.c_char_p
+    L.rs_census_name.argtypes = [ctypes.c_uint32]
+    L.rs_census_read.restype = L.rs_census_reset.restype = None
+    L.rs_census_read.argtypes = [ctypes.c_void_p]
+
+
+def census_read(L):
+    """{outcome: count} of a census build's table"""
+    n = L.rs_census_count()
+    counts = np.zeros(n, np.uint64)
+    L.rs_census_read(ctypes.c_void_p(counts.ctypes.data))
+    return {L.rs_census_name(i).decode(): int(counts[i]) for i in range(n)}
+
+
+def census(reset=False):
+    """{outcome: count}: what the ticks stepped through lib(census=True) took since the last reset"""
+    out = census_read(lib(census=True))
+    if reset:
+        lib(census=True).rs_census_reset()
+    return out
+
+
+def lib(census=False):
+    """the restatement as a shared library, its prototypes declared; census=True: the build with the census table, a library of
+    its own with the same arithmetic"""
     with _lock:
-        if _lib is None:
-            L = restatement_lib(SRC, [os.path.join(HERE, 'sincos_restatement.h')])
+        if census not in _libs:
+            deps = [os.path.join(HERE, 'sincos_restatement.h')]
+            L = restatement_lib(SRC, deps, flags=CENSUS_FLAGS, tag=CENSUS_TAG) if census else restatement_lib(SRC, deps)
+            if census:
+                declare_census(L)
             L.wb_new.restype = ctypes.c_void_p
             for name in ('wb_free', 'wb_leaf_end', 'wb_node_end', 'wb_build', 'wb_counts', 'wb_copy', 'rs_sweep', 'rs_step'):
                 getattr(L, name).restype = None
@@ -41,8 +70,8 @@ def lib():
                 getattr(L, name).argtypes = [ctypes.c_void_p]
             L.rs_sincos.argtypes = [f, ctypes.POINTER(f), ctypes.POINTER(f)]
             L.rs_sincos.restype = None
-            _lib = L
-    return _lib
+            _libs[census] = L
+    return _libs[census]
 
 
 def sincos(x):
@@ -54,8 +83,8 @@ def sincos(x):
 class _Feeder:
     """LevelVisitor (rd.make_visitor) that forwards the events WorldBuilder listens to, and counts the geometry it sees"""
 
-    def __init__(self, h):
-        self.h, self.L, self.ok = h, lib(), True
+    def __init__(self, h, L):
+        self.h, self.L, self.ok = h, L, True
         self.blocker_quads = self.sky_quads = self.other_quads = 0
         self.flat_vertex_counts = []
 
@@ -106,12 +135,14 @@ class _Feeder:
 
 
 class RefWorld:
-    """WorldBuilder + World + Player of the restatement, built from `wad`'s level `index` (an rd.Wad)"""
+    """WorldBuilder + World + Player of the restatement, built from `wad`'s level `index` (an rd.Wad); census=True: in the build
+    that counts the step's branch outcomes (read them with world_ref.census())"""
 
-    def __init__(self, wad, index):
-        L = lib()
+    def __init__(self, wad, index, census=False):
+        L = self.L = lib(census)
+        self.census = census
         self.h = ctypes.c_void_p(L.wb_new())
-        self.feed = _Feeder(self.h)
+        self.feed = _Feeder(self.h, L)
         wad.walk(index, self.feed)
         assert self.feed.ok, 'the walk broke one of WorldBuilder\'s asserts'
         L.wb_build(self.h)
@@ -128,7 +159,7 @@ class RefWorld:
 
     def __del__(self):
         try:
-            lib().wb_free(self.h)
+            self.L.wb_free(self.h)
         except Exception:
             pass
 
@@ -149,7 +180,7 @@ class RefWorld:
         def run(r):
             a, b = r
             off = ctypes.c_void_p(offsets[a:b].ctypes.data) if offsets is not None else None
-            lib().rs_sweep(self.h, ctypes.c_void_p(spheres[a:b].ctypes.data), ctypes.c_void_p(vels[a:b].ctypes.data), b - a, off, n_obj,
+            self.L.rs_sweep(self.h, ctypes.c_void_p(spheres[a:b].ctypes.data), ctypes.c_void_p(vels[a:b].ctypes.data), b - a, off, n_obj,
                            ctypes.c_void_p(out[a:b].ctypes.data))
         _chunked(run, n, threads)
         return out
@@ -168,7 +199,7 @@ class RefWorld:
 
         def run(r):
             a, b = r
-            lib().rs_step(self.h, ctypes.c_void_p(states.ctypes.data), ctypes.c_void_p(inputs.ctypes.data), n, a, b - a, len(inputs),
+            self.L.rs_step(self.h, ctypes.c_void_p(states.ctypes.data), ctypes.c_void_p(inputs.ctypes.data), n, a, b - a, len(inputs),
                           ctypes.c_void_p(cfg.ctypes.data), ctypes.c_float(dt),
                           ctypes.c_void_p(offsets.ctypes.data) if offsets is not None else None, n_obj)
         _chunked(run, n, threads)

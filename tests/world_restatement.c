@@ -10,6 +10,43 @@
 
 #include "sincos_restatement.h"
 
+/* ---- the census: which branch outcomes the step takes (tests/test_step_census_host.py), compiled only under -DRS_CENSUS.  A
+ * fixed table of named 64-bit counters; the sweep's outcomes are counted only while a tick() runs on the calling thread, so that
+ * sweeps asked for through rs_sweep stay out.  Without RS_CENSUS every macro below is empty: the default library carries no counter
+ * and the same arithmetic. */
+#define RS_CENSUS_NAMES(X) \
+  X(feet_grounded) X(feet_airborne) \
+  X(clip_free_first) X(clip_free_after_slide) X(clip_slide) X(clip_contact_beyond) X(clip_two_slides) X(clip_backs_off) \
+  X(clip_time_clamped_low) X(clip_time_clamped_high) X(clip_diverged) X(clip_diverged_already) \
+  X(noclip_probe_hit) X(noclip_probe_miss) X(noclip_land_falling) X(noclip_land_rising) X(noclip_no_landing) \
+  X(drag_speed_zero) X(drag_grounded_tangent_zero) X(drag_norm_zero) X(drag_clamped) X(drag_unclamped) \
+  X(jump_taken) X(jump_refused_rising) X(jump_held_in_air) \
+  X(fly_jump) X(fly_no_jump) \
+  X(pitch_clamped_low) X(pitch_clamped_high) \
+  X(tri_plane_wins) X(tri_vertex_wins) X(tri_edge_wins) X(tri_overlap) X(tri_behind) X(tri_leaving) X(tri_no_contact) \
+  X(sweep_plane_wins) X(sweep_vertex_wins) X(sweep_edge_wins) \
+  X(root_negative) X(root_nonnegative) X(root_first_lower) X(line_denom_zero) X(axis_yz) X(axis_xz) X(axis_xy) \
+  X(node_both_children) X(node_unlinked_child) X(node_stack_full) X(dyn_with_offsets) X(dyn_without_offsets)
+#ifdef RS_CENSUS
+#define RS_ENUM(n) RS_##n,
+enum { RS_CENSUS_NAMES(RS_ENUM) RS_N };
+#define RS_STR(n) #n,
+static const char *const rs_names[RS_N] = {RS_CENSUS_NAMES(RS_STR)};
+static uint64_t rs_counts[RS_N];
+static __thread int rs_in_tick;
+#define CENSUS(n) do { if (rs_in_tick) __atomic_fetch_add(&rs_counts[RS_##n], 1, __ATOMIC_RELAXED); } while (0)
+#define CENSUS_IF(cond, n) do { if (cond) CENSUS(n); } while (0)
+#define CENSUS_ONLY(...) __VA_ARGS__
+uint32_t rs_census_count(void) { return RS_N; }
+const char *rs_census_name(uint32_t i) { return i < RS_N ? rs_names[i] : ""; }
+void rs_census_read(uint64_t *out) { for (int i = 0; i < RS_N; i++) out[i] = __atomic_load_n(&rs_counts[i], __ATOMIC_RELAXED); }
+void rs_census_reset(void) { for (int i = 0; i < RS_N; i++) __atomic_store_n(&rs_counts[i], 0, __ATOMIC_RELAXED); }
+#else
+#define CENSUS(n) ((void)0)
+#define CENSUS_IF(cond, n) ((void)0)
+#define CENSUS_ONLY(...)
+#endif
+
 typedef struct { float ox, oy, dx, dy, len; int32_t pos, neg; } node_t;  /* Node + packed children */
 typedef struct { uint32_t start, end; } chunk_t;
 typedef struct { uint32_t a, b, c, n; } tri_t;
@@ -182,7 +219,7 @@ static vec vnorm0(vec a) { float m = vlen(a); return vdiv(a, m > 1.1920929e-7f ?
 static float vget(vec a, int i) { return i == 0 ? a.x : i == 1 ? a.y : a.z; }
 static vec vat(const world_t *w, uint32_t i) { return mk(w->verts[3 * i], w->verts[3 * i + 1], w->verts[3 * i + 2]); }
 
-typedef struct { float time; vec normal; } contact;
+typedef struct { float time; vec normal; CENSUS_ONLY(int kind;) } contact;  /* kind (census): 0 plane, 1 vertex, 2 edge */
 
 static int in_range01(float x) { return 0.0f <= x && x <= 1.0f; }
 
@@ -197,10 +234,12 @@ static int point_in_triangle(vec a, vec b, vec c, vec p) {
 
 static int lowest_root(float a, float b, float c, float *out) {
   float i = b * b - 4.0f * a * c;
-  if (i < 0.0f) return 0;
+  if (i < 0.0f) { CENSUS(root_negative); return 0; }
+  CENSUS(root_nonnegative);
   i = sqrtf(i);
   float a2 = 2.0f * a;
   float i1 = (-b + i) / a2, i2 = (-b - i) / a2;
+  CENSUS_IF(i1 < i2, root_first_lower);
   *out = i1 < i2 ? i1 : i2;
   return 1;
 }
@@ -217,7 +256,7 @@ static int line_line(float p1x, float p1y, float p2x, float p2y, float p3x, floa
   float d1x = p2x - p1x, d1y = p2y - p1y;
   float d2x = p3x - p4x, d2y = p3y - p4y;
   float denom = d2y * d1x - d2x * d1y;
-  if (denom == 0.0f) return 0;
+  if (denom == 0.0f) { CENSUS(line_denom_zero); return 0; }
   float dist = d2x * (p1y - p3y) - d2y * (p1x - p3x);
   *out = dist / denom;
   return 1;
@@ -228,13 +267,15 @@ static int sweep_tri(vec t[3], vec normal, vec center, float radius, vec vel, co
   if (speed == 0.0f) return 0;
   vec nvel = vdiv(vel, speed);
   float ndn = vdot(normal, nvel);
-  if (ndn >= 0.0f) return 0;
+  if (ndn >= 0.0f) { CENSUS(tri_leaving); return 0; }
+  CENSUS_ONLY(int kind = 0;)
   vec cn = mk(0.0f, 0.0f, 0.0f);
   int hit = 0;
   float best = 1e4f;
   float intercept = -vdot(t[0], normal);
   float spd = vdot(center, normal) + intercept;
-  if (spd < -radius) return 0;
+  if (spd < -radius) { CENSUS(tri_behind); return 0; }
+  CENSUS_IF(spd < radius, tri_overlap);
   if (spd >= radius) {
     float distance = -(spd - radius) / ndn;
     vec on_plane = vadd(center, vmul(nvel, distance));
@@ -246,6 +287,7 @@ static int sweep_tri(vec t[3], vec normal, vec center, float radius, vec vel, co
       best = d;
       cn = vsub(center, vadd(t[k], vmul(nvel, -d)));
       hit = 1;
+      CENSUS_ONLY(kind = 1;)
     }
   }
   for (int k = 0; k < 3; k++) {
@@ -267,6 +309,9 @@ static int sweep_tri(vec t[3], vec normal, vec center, float radius, vec vel, co
     if (ax > ay && ax > az) d1 = 1, d2 = 2;
     else if (ay > az) d1 = 0, d2 = 2;
     else d1 = 0, d2 = 1;
+    CENSUS_IF(d1 == 1, axis_yz);
+    CENSUS_IF(d1 == 0 && d2 == 2, axis_xz);
+    CENSUS_IF(d2 == 1, axis_xy);
     vec cpn = vadd(cand, nvel);
     float tt;
     if (!line_line(vget(cand, d1), vget(cand, d2), vget(cpn, d1), vget(cpn, d2), vget(e1, d1), vget(e1, d2), vget(e2, d1), vget(e2, d2), &tt))
@@ -277,8 +322,13 @@ static int sweep_tri(vec t[3], vec normal, vec center, float radius, vec vel, co
     best = tt;
     cn = vsub(center, cand);
     hit = 1;
+    CENSUS_ONLY(kind = 2;)
   }
-  if (!hit) return 0;
+  if (!hit) { CENSUS(tri_no_contact); return 0; }
+  CENSUS_IF(kind == 0, tri_plane_wins);
+  CENSUS_IF(kind == 1, tri_vertex_wins);
+  CENSUS_IF(kind == 2, tri_edge_wins);
+  CENSUS_ONLY(out->kind = kind;)
   out->normal = vnorm0(cn);
   out->time = best / speed;
   return 1;
@@ -294,7 +344,7 @@ static void sweep_range(const world_t *w, contact *first, uint32_t start, uint32
 }
 
 static contact sweep_sphere(const world_t *w, vec center, float radius, vec vel, const float *offsets) {
-  contact first = {INFINITY, {0.0f, 0.0f, 0.0f}};
+  contact first = {INFINITY, {0.0f, 0.0f, 0.0f} CENSUS_ONLY(, 0)};
   uint32_t stack[4096], sp = 0;
   stack[sp++] = 0;
   while (sp) {
@@ -307,8 +357,11 @@ static contact sweep_sphere(const world_t *w, vec center, float radius, vec vel,
     int nk = 0;
     if (d1 >= -radius || d2 >= -radius) kids[nk++] = nd->pos;
     if (d1 <= radius || d2 <= radius) kids[nk++] = nd->neg;
+    CENSUS_IF(nk == 2, node_both_children);
     for (int k = 0; k < nk; k++) {
+      CENSUS_IF(kids[k] == 0, node_unlinked_child);
       if (kids[k] > 0) {
+        CENSUS_IF(!(sp < 4096), node_stack_full);
         if (sp < 4096) stack[sp++] = (uint32_t)kids[k];
       } else {
         const chunk_t *c = &w->chunks[(uint32_t)(-kids[k])];
@@ -319,8 +372,13 @@ static contact sweep_sphere(const world_t *w, vec center, float radius, vec vel,
   for (uint32_t d = 0; d < w->n_dyn; d++) {
     vec off = mk(0.0f, 0.0f, 0.0f);
     if (offsets) off = mk(offsets[3 * w->dyn[d].obj], offsets[3 * w->dyn[d].obj + 1], offsets[3 * w->dyn[d].obj + 2]);
+    CENSUS_IF(offsets != NULL, dyn_with_offsets);
+    CENSUS_IF(offsets == NULL, dyn_without_offsets);
     sweep_range(w, &first, w->dyn[d].start, w->dyn[d].end, vadd(center, vneg(off)), radius, vel);
   }
+  CENSUS_IF(first.time < INFINITY && first.kind == 0, sweep_plane_wins);
+  CENSUS_IF(first.time < INFINITY && first.kind == 1, sweep_vertex_wins);
+  CENSUS_IF(first.time < INFINITY && first.kind == 2, sweep_edge_wins);
   return first;
 }
 
@@ -345,6 +403,7 @@ static float clampf_(float v, float lo, float hi) { return v < lo ? lo : v > hi 
 
 static void tick(const world_t *w, pstate *s, const pinput *in, const pconfig *cfg, float dt, const float *offsets) {
   int fly = (s->flags & 1u) != 0, clip = (s->flags & 2u) != 0;
+  CENSUS_ONLY(rs_in_tick = 1;)
   vec head = mk(s->pos[0], s->pos[1], s->pos[2]);
   vec vel = mk(s->vel[0], s->vel[1], s->vel[2]);
   /* force(): feet probe */
@@ -353,15 +412,21 @@ static void tick(const world_t *w, pstate *s, const pinput *in, const pconfig *c
   int grounded = 0;
   vec gn = mk(0.0f, 0.0f, 0.0f);
   if (feet.time < INFINITY && feet.time < 1.0f) height = cfg->height * feet.time, gn = feet.normal, grounded = 1;
+  CENSUS_IF(grounded, feet_grounded);
+  CENSUS_IF(!grounded, feet_airborne);
   /* move_force() */
   float lim = 1.57079637f - 1e-2f;
   s->yaw = s->yaw - in->look[0];
+  CENSUS_IF(s->pitch - in->look[1] < -lim, pitch_clamped_low);
+  CENSUS_IF(s->pitch - in->look[1] > lim, pitch_clamped_high);
   s->pitch = clampf_(s->pitch - in->look[1], -lim, lim);
   float sy, cy, sp, cp;
   rs_sincos(s->yaw, &sy, &cy);
   rs_sincos(s->pitch, &sp, &cp);
   vec force;
   if (fly) {
+    CENSUS_IF(in->jump, fly_jump);
+    CENSUS_IF(!in->jump, fly_no_jump);
     vec m = vmul(vnorm0(mk(in->mv[0], in->jump ? 0.5f : 0.0f, in->mv[1])), cfg->move_force);
     float y1 = m.y * cp - m.z * sp;
     float z1 = m.y * sp + m.z * cp;
@@ -370,13 +435,17 @@ static void tick(const world_t *w, pstate *s, const pinput *in, const pconfig *c
     float fz = in->mv[1] * cp;
     vec m = vmul(vnorm0(mk(in->mv[0] * cy + fz * sy, 0.0f, fz * cy - in->mv[0] * sy)), cfg->move_force);
     if (grounded) {
+      CENSUS_IF(in->jump && vel.y < 0.1f, jump_taken);
+      CENSUS_IF(in->jump && !(vel.y < 0.1f), jump_refused_rising);
       if (in->jump && vel.y < 0.1f) m = mk(m.x, 5.0f / dt, m.z);
     } else {
+      CENSUS_IF(in->jump, jump_held_in_air);
       m = vmul(m, 0.1f);
     }
     force = m;
   }
   float speed = vlen(vel);
+  CENSUS_IF(!(speed > 0.0f), drag_speed_zero);
   if (speed > 0.0f) {
     vec slow = mk(0.0f, 0.0f, 0.0f);
     if (fly) {
@@ -384,12 +453,16 @@ static void tick(const world_t *w, pstate *s, const pinput *in, const pconfig *c
     } else if (grounded) {
       vec tang = vsub(vel, vmul(gn, vdot(vel, gn)));
       float ts = vlen(tang);
+      CENSUS_IF(!(ts > 0.0f), drag_grounded_tangent_zero);
       if (ts > 0.0f) slow = vmul(vneg(tang), cfg->friction / ts + cfg->ground_drag * ts);
     }
     slow = vsub(slow, vmul(vmul(vel, cfg->air_drag), speed));
     float sn = vlen(slow);
+    CENSUS_IF(!(sn > 0.0f), drag_norm_zero);
     if (sn > 0.0f) {
       float mx = -vdot(vel, slow) / sn / dt;
+      CENSUS_IF(sn >= mx, drag_clamped);
+      CENSUS_IF(!(sn >= mx), drag_unclamped);
       if (sn >= mx) slow = vmul(vdiv(slow, sn), mx);
       force = vadd(force, slow);
     }
@@ -402,12 +475,19 @@ static void tick(const world_t *w, pstate *s, const pinput *in, const pconfig *c
   if (clip) {
     float left = dt;
     int armed = 1;
+    CENSUS_ONLY(int slides = 0;)
     for (int i = 0; i < 100; i++) {
       vec disp = vmul(vel, left);
       contact c = sweep_sphere(w, head, cfg->radius, disp, offsets);
       if (c.time < INFINITY) {
         float adj = c.time - 0.001f / vlen(disp);
+        CENSUS_IF(!(adj < 1.0f), clip_contact_beyond);
         if (adj < 1.0f) {
+          CENSUS(clip_slide);
+          CENSUS_ONLY(if (++slides == 2) CENSUS(clip_two_slides);)
+          CENSUS_IF(adj < 0.0f, clip_backs_off);
+          CENSUS_IF(c.time < 0.0f, clip_time_clamped_low);
+          CENSUS_IF(c.time > 1.0f, clip_time_clamped_high);
           float tm = clampf_(c.time, 0.0f, 1.0f);
           head = vadd(head, vmul(disp, adj));
           vel = vsub(vel, vmul(c.normal, vdot(c.normal, vel)));
@@ -415,10 +495,14 @@ static void tick(const world_t *w, pstate *s, const pinput *in, const pconfig *c
           continue;
         }
       }
+      CENSUS_IF(!(c.time < INFINITY) && slides == 0, clip_free_first);
+      CENSUS_IF(!(c.time < INFINITY) && slides > 0, clip_free_after_slide);
       head = vadd(head, disp);
       armed = 0;
       break;
     }
+    CENSUS_IF(armed && (s->flags & 0x100u), clip_diverged_already);
+    CENSUS_IF(armed, clip_diverged);
     if (armed) s->flags |= 0x100u;
   } else {
     float old = head.y;
@@ -427,6 +511,11 @@ static void tick(const world_t *w, pstate *s, const pinput *in, const pconfig *c
       float H = 2000.0f;
       contact c = sweep_sphere(w, vadd(head, mk(0.0f, H / 2.0f, 0.0f)), cfg->radius, mk(0.0f, -H, 0.0f), offsets);
       float h = c.time < INFINITY ? head.y + H * (0.5f - c.time) : old;
+      CENSUS_IF(c.time < INFINITY, noclip_probe_hit);
+      CENSUS_IF(!(c.time < INFINITY), noclip_probe_miss);
+      CENSUS_IF(head.y <= h && vel.y < 0.0f, noclip_land_falling);
+      CENSUS_IF(head.y <= h && !(vel.y < 0.0f), noclip_land_rising);
+      CENSUS_IF(!(head.y <= h), noclip_no_landing);
       if (head.y <= h) {
         head.y = h;
         if (vel.y < 0.0f) vel.y = 0.0f;
@@ -436,6 +525,7 @@ static void tick(const world_t *w, pstate *s, const pinput *in, const pconfig *c
   vel = vadd(vel, vmul(force, dt));
   s->pos[0] = head.x, s->pos[1] = head.y, s->pos[2] = head.z;
   s->vel[0] = vel.x, s->vel[1] = vel.y, s->vel[2] = vel.z;
+  CENSUS_ONLY(rs_in_tick = 0;)
 }
 
 /* players [first, first + count) of n, n_ticks ticks; inputs[t * n + p]; offsets per player (n_objects x xyz) or NULL */

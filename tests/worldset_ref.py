@@ -99,7 +99,7 @@ class RefWorldSet:
     """N players over the levels `indices` of a WAD: per level a world_ref.RefWorld and a game_ref.RefGame with a row for every
     player (only the rows of the players in that level are stepped), the players' slots, and the change stage of each"""
 
-    def __init__(self, wad_path, meta_path, indices, levels):
+    def __init__(self, wad_path, meta_path, indices, levels, census=False):
         self.wad = rd.Wad(wad_path, meta_path)
         self.indices = list(indices)
         self.levels = np.array(levels, np.int64)
@@ -107,9 +107,9 @@ class RefWorldSet:
         self.worlds, self.games, self.starts = [], [], []
         for index in self.indices:
             trig, effs, n_obj = game_ref.triggers(wad_path, meta_path, index)
-            ref = world_ref.RefWorld(self.wad, index)
+            ref = world_ref.RefWorld(self.wad, index, census=census)
             self.worlds.append(ref)
-            self.games.append(game_ref.RefGame(ref, trig, effs, n, n_obj))
+            self.games.append(game_ref.RefGame(ref, trig, effs, n, n_obj, census=census))
             pos, yaw = self.wad.build_level(index).start()
             self.starts.append((np.asarray(pos, F), F(yaw)))
         self.dest = [self.indices.index(i + 1) if i + 1 in self.indices else None for i in self.indices]
@@ -144,6 +144,7 @@ class RefWorldSet:
                     continue
                 sub = game_ref.RefGame.__new__(game_ref.RefGame)
                 sub.w, sub.trig, sub.effs, sub.n, sub.n_objects = g.w, g.trig, g.effs, len(sel), g.n_objects
+                sub.L = g.L
                 sub.order, sub.counts, sub.act = g.order[sel].copy(), g.counts[sel].copy(), g.act[sel].copy()
                 sub.aflags, sub.offsets = g.aflags[sel].copy(), g.offsets[sel].copy()
                 before = states[sel].copy()
