@@ -126,7 +126,9 @@ THING_MARKS = np.dtype([('min_radius', '<f4'), ('codes', 'u1', 8), ('flags', '<u
 # rdoom_world_stamp_things (World.stamp_things): its parameters, and the cells (across, down) of the tile one workgroup takes (kernels.hpp)
 STAMP_PARAMS = np.dtype([('grow', '<f4'), ('block_below', '<f4'), ('block_above', '<f4'), ('flags', '<u4')])
 STAMP_TILE = (64, 16)
-assert THING_MARKS.itemsize == 16
+# rdoom_ray_things (include/rdoom_rays.h; World.cast_rays_things): its parameters
+RAY_THINGS = np.dtype([('height', '<f4', 8), ('grow', '<f4'), ('category_mask', '<u4'), ('flags', '<u4')])
+assert THING_MARKS.itemsize == 16 and RAY_THINGS.itemsize == 44
 
 
 def _thing_map_colors():
@@ -236,6 +238,8 @@ API_SYMBOLS = [
     'rdoom_built_decor_things', 'rdoom_level_set_decor_things', 'rdoom_batch_set_hidden_things', 'rdoom_thingset_draw_maps',
     'rdoom_world_thing_obstacles', 'rdoom_worldset_level_thing_obstacles',
     'rdoom_world_stamp_things', 'rdoom_worldset_stamp_things']
+# every symbol include/rdoom_rays.h declares: the same library exports them
+RAY_API_SYMBOLS = ['rdoom_world_cast_rays_things', 'rdoom_worldset_cast_rays_things']
 
 _lib = None
 
@@ -257,6 +261,8 @@ def lib():
                 fn.restype = ctypes.c_int32
             elif name != 'rdoom_last_error':
                 fn.restype = None
+        for name in RAY_API_SYMBOLS:
+            getattr(L, name).restype = ctypes.c_int32
         _lib = L
     return _lib
 
@@ -2417,6 +2423,106 @@ _STAMP_DOC = """makes void (+inf / -inf) the cells of floor and ceiling -- draw_
         (floor, ceiling, index) or index.  One launch, asynchronous on `stream`; it can be captured into a graph."""
 
 
+class RayThings(ctypes.Structure):
+    """rdoom_ray_things (RAY_THINGS is the same record for numpy)"""
+    _fields_ = [('height', ctypes.c_float * 8), ('grow', ctypes.c_float), ('category_mask', ctypes.c_uint32), ('flags', ctypes.c_uint32)]
+
+
+def _cast_rays_things(call, states, levels, things, dirs, max_range, heights, grow, categories, select, hidden, offsets, frac, frac_out,
+                      thing_out, stream, n, n_objects, stride):
+    """World.cast_rays_things / WorldSet.cast_rays_things: the checks and the launch; call(states, levels, n, dirs, n_rays, max_range,
+    offsets, n_objects, params, select, hidden, stride, frac_in, frac_out, thing_out, stream) is the C entry point with its handle and
+    the thing set bound"""
+    import torch
+    if not isinstance(things, DeviceThings):
+        raise ValueError('things must be a DeviceThings')
+    raw = lambda t: isinstance(t, (int, np.integer)) and not isinstance(t, bool)
+    if not isinstance(dirs, torch.Tensor) or dirs.device.type != 'cuda' or not dirs.is_contiguous() or dirs.dtype != torch.float32 or \
+            dirs.dim() != 2 or dirs.shape[1] != 3 or dirs.shape[0] == 0:
+        raise ValueError('dirs must be a contiguous float32 (n_rays, 3) tensor on the GPU with n_rays >= 1')
+    n_rays = int(dirs.shape[0])
+    if raw(states):
+        if n is None:
+            raise ValueError('n is needed with raw pointers')
+        n = int(n)
+    else:
+        n = _n_players(states) if n is None else int(n)
+    if levels is not None and not raw(levels) and (levels.element_size() != 4 or levels.numel() < n):
+        raise ValueError('levels must hold one 32-bit slot per player (%d), got %s %s' % (n, levels.dtype, tuple(levels.shape)))
+    if select is not None and not raw(select) and select.dim() == 1:
+        select = select.reshape(1, -1)
+    for r, what, need in ((select, 'select', things.n_levels), (hidden, 'hidden', n)):
+        if r is None:
+            continue
+        if raw(r):
+            if stride is None:
+                raise ValueError('stride is needed with a raw %s pointer' % what)
+            continue
+        if r.element_size() != 4 or r.dtype.is_floating_point or r.dim() != 2:
+            raise ValueError('%s must be a 32-bit integer (rows, words) tensor' % what)
+        if int(r.shape[0]) < need:
+            raise ValueError('the %s tensor has %d rows, the call needs %d' % (what, int(r.shape[0]), need))
+        if stride is not None and int(stride) != int(r.shape[1]):
+            raise ValueError('stride %d, but the %s rows are %d words long' % (int(stride), what, int(r.shape[1])))
+        stride = int(r.shape[1])
+    stride = 0 if stride is None else int(stride)
+    n_obj = 0
+    if offsets is not None:
+        if raw(offsets):
+            if n_objects is None:
+                raise ValueError('n_objects is needed with a raw offsets pointer')
+            n_obj = int(n_objects)
+        else:
+            if offsets.dim() != 3 or int(offsets.shape[0]) < n or offsets.shape[2] != 3 or offsets.dtype != torch.float32:
+                raise ValueError('offsets must be a float32 (n, n_objects, 3) tensor for %d players, got %s' % (n, tuple(offsets.shape)))
+            n_obj = int(offsets.shape[1])
+    heights = [float(heights)] * THING_CATEGORIES if np.isscalar(heights) else [float(h) for h in heights]
+    if len(heights) != THING_CATEGORIES:
+        raise ValueError('heights must be a number or eight, one per category, got %d' % len(heights))
+    mask = 0
+    for c in (range(THING_CATEGORIES) if categories is None else ((categories,) if isinstance(categories, (int, np.integer)) else categories)):
+        if not 0 <= int(c) < THING_CATEGORIES:
+            raise ValueError('categories names categories 0 .. 7, not %r' % (c,))
+        mask |= 1 << int(c)
+    for t, what in ((frac, 'frac'), (frac_out, 'frac_out')):
+        if t is not None and not raw(t) and (not isinstance(t, torch.Tensor) or t.dtype != torch.float32):
+            raise ValueError('%s must be a float32 tensor or a device pointer' % what)
+    rays = n * n_rays
+    if frac_out is None:
+        if raw(states):
+            raise ValueError('frac_out is needed with raw pointers')
+        frac_out = torch.empty((n, n_rays), dtype=torch.float32, device=dirs.device)
+    if thing_out is True:
+        thing_out = torch.empty((n, n_rays), dtype=torch.int32, device=dirs.device)
+    elif thing_out is None or thing_out is False:
+        thing_out = None
+    elif not raw(thing_out) and (not isinstance(thing_out, torch.Tensor) or thing_out.dtype != torch.int32):
+        raise ValueError('thing_out must be True, an int32 (n, n_rays) tensor or a device pointer')
+    params = RayThings((ctypes.c_float * 8)(*heights), grow, mask, 0)
+    v = ctypes.c_void_p
+    _check(call(v(_pointer(states, n * PLAYER_STATE.itemsize, 'states')), v(_pointer(levels, n * 4, 'levels')), n, v(dirs.data_ptr()), n_rays,
+                ctypes.c_float(max_range), v(_pointer(offsets, n * n_obj * 12, 'offsets')), n_obj, ctypes.byref(params),
+                v(_pointer(select, things.n_levels * stride * 4, 'select')), v(_pointer(hidden, n * stride * 4, 'hidden')), stride,
+                v(_pointer(frac, rays * 4, 'frac')), v(_pointer(frac_out, rays * 4, 'frac_out')), v(_pointer(thing_out, rays * 4, 'thing_out')),
+                v(_stream_handle(stream))))
+    return frac_out, thing_out
+
+
+_RAY_THINGS_DOC = """shortens the rays of cast_rays(states, dirs, max_range) that meet a thing of `things` (a
+        DeviceThings) before they meet the world, per player and in that player's own game: a second pass after cast_rays, one
+        launch.  A thing is a vertical cylinder of its radius + grow, heights[category] tall (a number, or eight; inf: no top),
+        standing on its live base, or hanging from it.  categories: None (all) or an iterable of THING_*; select: None (every thing)
+        or an int32 (levels, words >= things.words()) GPU tensor of bits, one row a level of the set --
+        torch.from_numpy(pack_things(world.thing_obstacles())).cuda() gives the obstacles only; hidden: None or sense_things'
+        `collected` (n, words) tensor as it stands: a thing player p has collected is passed by p's rays, and only p's.  offsets:
+        None (at rest) or step_game's tensor: a barrel on a lift rides it.  frac: None (every ray starts at +inf) or the float32
+        (n, n_rays) fractions cast_rays wrote; the thing wins only when strictly nearer.  frac_out: None allocates; frac itself runs
+        in place (no other overlap is allowed).  thing_out: None / False, True (allocated) or an int32 (n, n_rays) tensor: the index
+        of the thing each ray ends on, -1 where it ends on the world or on nothing.  states, levels, select, hidden, offsets, frac and
+        the outputs may instead be raw device pointers (ints; then n, stride, and with offsets n_objects, must be given).  Returns
+        (frac_out, thing_out).  Asynchronous on `stream`; it can be captured into a graph."""
+
+
 def _area_frontiers(call, words, levels, area, dist, cell, cell_out, dist_out, count_out, mask_out, stream):
     """World.area_frontiers / WorldSet.area_frontiers: the checks and the launch; call(levels, n, cell, width, height, area, stride,
     dist, cell_out, dist_out, count_out, mask_out, stream) is the C entry point with its handle bound.  Returns cell_out, or a tuple
@@ -2769,6 +2875,14 @@ class World:
                              n_objects, stride)
     stamp_things.__doc__ = 'rdoom_world_stamp_things: ' + _STAMP_DOC
 
+    def cast_rays_things(self, states, things, dirs, max_range, heights=0.56, grow=0.0, categories=None, select=None, hidden=None,
+                         offsets=None, frac=None, frac_out=None, thing_out=None, stream=None, n=None, n_objects=None, stride=None):
+        L = lib()
+        return _cast_rays_things(lambda st, lv, *rest: L.rdoom_world_cast_rays_things(self._h, getattr(things, '_h', None), st, *rest), states,
+                                 None, things, dirs, max_range, heights, grow, categories, select, hidden, offsets, frac, frac_out, thing_out,
+                                 stream, n, n_objects, stride)
+    cast_rays_things.__doc__ = 'rdoom_world_cast_rays_things: ' + _RAY_THINGS_DOC
+
     # ---- sectors -----------------------------------------------------------------------------------------------------------
     def map_sectors(self):
         """a copy of rdoom_world_map_sectors: the level's sector table, a MapSectors of (sectors, leaf_sector, leaf_edges, edges)"""
@@ -3078,6 +3192,15 @@ class WorldSet:
                              n_objects, stride)
     stamp_things.__doc__ = 'rdoom_worldset_stamp_things (levels: a GPU tensor of one 32-bit slot per row; slot l of `things` and row l of ' \
         '`solid` are the level in slot l; a row whose slot is outside the set passes through): ' + _STAMP_DOC
+
+    def cast_rays_things(self, states, levels, things, dirs, max_range, heights=0.56, grow=0.0, categories=None, select=None, hidden=None,
+                         offsets=None, frac=None, frac_out=None, thing_out=None, stream=None, n=None, n_objects=None, stride=None):
+        L = lib()
+        return _cast_rays_things(lambda *rest: L.rdoom_worldset_cast_rays_things(self._h, getattr(things, '_h', None), *rest), states, levels,
+                                 things, dirs, max_range, heights, grow, categories, select, hidden, offsets, frac, frac_out, thing_out, stream,
+                                 n, n_objects, stride)
+    cast_rays_things.__doc__ = 'rdoom_worldset_cast_rays_things (levels: a GPU tensor of one 32-bit slot per player; slot l of `things` and ' \
+        'row l of `select` are the level in slot l; a player whose slot is outside the set keeps its fractions, index -1): ' + _RAY_THINGS_DOC
 
     def map_sectors(self, slot):
         """a copy of rdoom_worldset_level_map_sectors: the level's sector table, a MapSectors of (sectors, leaf_sector, leaf_edges, edges)"""

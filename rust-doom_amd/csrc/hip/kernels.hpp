@@ -355,4 +355,22 @@ struct StampArgs {
   float cell, grow, below, above; // below = -block_below
 };
 
+// Kernel 27: the range sensor's rays against a level's things as vertical cylinders, after the world cast (raythings.hip;
+// include/rdoom_rays.h has the contract).  One 256-thread workgroup per player; a thread takes one thing of a pass of 256, the
+// things in reach go into a list in LDS, and the list is folded over the rays 64 at a time, a quarter of it per wave.
+struct RayThingArgs {
+  const rdoom_player_state *states;
+  const float *dirs;              // n_rays x xyz, camera frame
+  const float *offsets;           // n x n_objects x xyz, or null
+  const rdoom_thing *things;      // the set's records, level after level
+  const uint32_t *select;         // levels x stride words, or null: every thing
+  const uint32_t *hidden;         // n x stride words, or null: nothing is hidden
+  const float *frac_in;           // n x n_rays, or null: +inf; may be frac_out itself
+  float *frac_out;                // n x n_rays
+  int32_t *thing_out;             // n x n_rays, or null
+  uint32_t n_rays, n_objects, stride, category_mask;
+  float max_range, grow;
+  float height[8];
+};
+
 }  // namespace rdoom_dev
