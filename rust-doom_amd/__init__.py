@@ -129,6 +129,9 @@ STAMP_TILE = (64, 16)
 # rdoom_ray_things (include/rdoom_rays.h; World.cast_rays_things): its parameters
 RAY_THINGS = np.dtype([('height', '<f4', 8), ('grow', '<f4'), ('category_mask', '<u4'), ('flags', '<u4')])
 assert THING_MARKS.itemsize == 16 and RAY_THINGS.itemsize == 44
+# rdoom_frame_thing (include/rdoom_frame_things.h; frame_things): what one frame shows of one thing
+FRAME_THING = np.dtype([('count', '<u4'), ('x0', '<i4'), ('y0', '<i4'), ('x1', '<i4'), ('y1', '<i4'), ('depth_min', '<f4')])
+assert FRAME_THING.itemsize == 24
 
 
 def _thing_map_colors():
@@ -240,6 +243,8 @@ API_SYMBOLS = [
     'rdoom_world_stamp_things', 'rdoom_worldset_stamp_things']
 # every symbol include/rdoom_rays.h declares: the same library exports them
 RAY_API_SYMBOLS = ['rdoom_world_cast_rays_things', 'rdoom_worldset_cast_rays_things']
+# every symbol include/rdoom_frame_things.h declares: the same library exports them
+FRAME_THINGS_API_SYMBOLS = ['rdoom_batch_resolve_thing_plane', 'rdoom_batch_read_thing_plane', 'rdoom_frame_things']
 
 _lib = None
 
@@ -261,7 +266,7 @@ def lib():
                 fn.restype = ctypes.c_int32
             elif name != 'rdoom_last_error':
                 fn.restype = None
-        for name in RAY_API_SYMBOLS:
+        for name in RAY_API_SYMBOLS + FRAME_THINGS_API_SYMBOLS:
             getattr(L, name).restype = ctypes.c_int32
         _lib = L
     return _lib
@@ -1039,6 +1044,41 @@ class Batch:
         _check(lib().rdoom_batch_resolve_plane(self._h, first, count, arg, ctypes.c_void_p(ptr or None), ctypes.c_void_p(stream or 0)))
         return out
 
+    def read_thing_plane(self, first=0, count=None, top_down=False):
+        """rdoom_batch_read_thing_plane (include/rdoom_frame_things.h): per pixel of frames [first, first+count) of the last render
+        the index, in the thing table of the pose's level, of the thing whose decor quad shows there, -1 everywhere else (flats,
+        walls, sky, nothing drawn, decor of NO_THING, a level handle without set_decor_things) as (count, H, W) int32; row 0 =
+        the bottom row unless top_down.  Things hidden by set_hidden_things were not drawn and do not appear."""
+        count = self.last_n - first if count is None else count
+        out = np.zeros((int(count), self.height, self.width), np.int32)
+        _check(lib().rdoom_batch_read_thing_plane(self._h, int(first), int(count), RGB_TOP_DOWN if top_down else 0,
+                                                  out.ctypes.data_as(ctypes.c_void_p)))
+        return out
+
+    def resolve_thing_plane(self, out, first=0, count=None, top_down=False, stream=None):
+        """rdoom_batch_resolve_thing_plane: the same plane written to device memory, asynchronously on `stream` (a hipStream_t
+        handle, or a torch stream; None = the null stream).  out: a raw device pointer (int) of count*H*W int32, or a contiguous
+        torch.int32 tensor with that many elements on the batch's device.  Returns out; frame_things reduces it."""
+        count = self.last_n - first if count is None else count
+        first, count = int(first), int(count)
+        if isinstance(out, int):
+            ptr = out
+        else:
+            import torch  # (only here: the package imports without torch)
+            if not isinstance(out, torch.Tensor):
+                raise TypeError('out must be a device pointer (int) or a torch tensor, not %s' % type(out).__name__)
+            if out.dtype != torch.int32 or not out.is_contiguous() or out.device.type != 'cuda':
+                raise ValueError('out must be a contiguous torch.int32 tensor on the GPU (got %s, %s, contiguous=%s)'
+                                 % (out.dtype, out.device, out.is_contiguous()))
+            need = count * self.height * self.width
+            if out.numel() != need:
+                raise ValueError('out has %d elements, frames %d..%d need %s = %d'
+                                 % (out.numel(), first, first + count, (count, self.height, self.width), need))
+            ptr = out.data_ptr()  # (the library checks that it lives on the batch's device)
+        _check(lib().rdoom_batch_resolve_thing_plane(self._h, first, count, RGB_TOP_DOWN if top_down else 0, ctypes.c_void_p(ptr or None),
+                                                     ctypes.c_void_p(_stream_handle(stream))))
+        return out
+
     def read_depth(self, first=0, count=None, top_down=False):
         """read_plane(PLANE_DEPTH, ...): (count, H, W) float32"""
         return self.read_plane(PLANE_DEPTH, first, count, top_down)
@@ -1675,6 +1715,67 @@ def pack_things(bools, words=None):
     padded = np.zeros(words * 32, np.uint8)
     padded[:len(bits)] = bits
     return np.packbits(padded.reshape(words, 32), axis=1, bitorder='little').view('<u4').reshape(words).astype(np.uint32).view(np.int32)
+
+
+def frame_things(ids, depth=None, max_things=None, min_pixels=1, table_out=None, bits_out=None, stream=None, shape=None):
+    """rdoom_frame_things (include/rdoom_frame_things.h): what each frame of an id plane shows of each thing.  ids: a contiguous
+    int32 (n, H, W) GPU tensor -- Batch.resolve_thing_plane's, or any other plane of ids -- or a raw device pointer with shape =
+    (n, H, W); depth: None, or the float32 plane of the same shape and row order (Batch.resolve_depth's), tensor or pointer.
+    Returns (table, bits).  table: an int32 (n, max_things, 6) GPU tensor of FRAME_THING records -- count, x0, y0, x1, y1 (the
+    inclusive box in columns and rows of the plane as given) and the bits of depth_min (frame_things_depth(table) views them),
+    the smallest finite non-negative depth of the thing's pixels; a thing with no pixel has count 0, x0 = y0 = INT32_MAX, x1 = y1
+    = -1 and depth_min = +inf; ids below 0 or at or above max_things are ignored.  bits: an int32 (n, words) tensor, words =
+    ceil(max_things / 32), bit i % 32 of word i // 32 set exactly when thing i has at least min_pixels pixels -- the layout of
+    sense_things' rows, so `known |= bits` works as it stands -- or None with bits_out=False.  table_out, bits_out: tensors (32-bit
+    integer; bits_out (n, stride) with any stride >= 1) or raw device pointers (bits_out then with the stride `words`) to write
+    instead of new ones.  Three launches, asynchronous on `stream` (None, a torch stream or a raw handle); it can be captured into
+    a graph."""
+    import torch
+    if max_things is None:
+        raise ValueError('max_things must be given: the number of records per frame, for instance 32 * things.words()')
+    max_things, min_pixels = int(max_things), int(min_pixels)
+    raw = isinstance(ids, int) and not isinstance(ids, bool)
+    if raw:
+        if shape is None or len(shape) != 3:
+            raise ValueError('a raw ids pointer needs shape=(n, H, W)')
+        pi, device = ids, None
+    else:
+        if not isinstance(ids, torch.Tensor) or ids.dtype != torch.int32 or ids.device.type != 'cuda' or not ids.is_contiguous() or ids.dim() != 3:
+            raise ValueError('ids must be a contiguous int32 (n, H, W) tensor on the GPU, or a device pointer with shape=')
+        if shape is not None and tuple(shape) != tuple(ids.shape):
+            raise ValueError('shape %r, but ids is %r' % (tuple(shape), tuple(ids.shape)))
+        shape, pi, device = tuple(ids.shape), ids.data_ptr(), ids.device
+    n, height, width = (int(s) for s in shape)
+    if depth is None or (isinstance(depth, int) and not isinstance(depth, bool)):
+        pd = depth
+    elif not isinstance(depth, torch.Tensor) or depth.dtype != torch.float32:
+        raise ValueError('depth must be None, a float32 tensor of the shape of ids, or a device pointer')
+    else:
+        pd = _out_tensor(depth, n * height * width * 4, 'depth')
+    if device is None and (table_out is None or bits_out is None or bits_out is True):
+        raise ValueError('with a raw ids pointer give table_out, and bits_out or bits_out=False')
+    table, pt = _int32_out(table_out, (n, max_things, 6), device, 'table_out')
+    words = (max_things + 31) // 32
+    if bits_out is False:
+        bits, pb, stride = None, None, 0
+    elif isinstance(bits_out, torch.Tensor):
+        if bits_out.dim() != 2 or bits_out.shape[0] != n or bits_out.shape[1] < 1:
+            raise ValueError('bits_out must be an (n, stride) tensor with stride >= 1')
+        stride = int(bits_out.shape[1])
+        bits, pb = _int32_out(bits_out, (n, stride), device, 'bits_out')
+    else:
+        stride = words
+        bits, pb = _int32_out(bits_out, (n, stride), device, 'bits_out')
+    v = ctypes.c_void_p
+    _check(lib().rdoom_frame_things(v(pi or None), v(pd or None), n, width, height, max_things, min_pixels, v(pt or None), v(pb or None), stride,
+                                    v(_stream_handle(stream))))
+    return table, bits
+
+
+def frame_things_depth(table):
+    """column 5 of frame_things' table, depth_min, viewed as float32: (n, max_things)"""
+    import torch
+    return table[..., 5].view(torch.float32) if isinstance(table, torch.Tensor) else np.asarray(table)[..., 5].view(np.float32)
 
 
 def _thing_obstacles(get, n_things):

@@ -373,4 +373,14 @@ struct RayThingArgs {
   float height[8];
 };
 
+// Kernels 28 and 29: the thing plane of frames [first, first + count) of the last render -- per pixel the thing of the winning decor
+// triangle, -1 elsewhere -- found as kernels 7 and 8 find the record, then the pixels of the fixup list (framethings.hip;
+// include/rdoom_frame_things.h has the contract).  PlaneArgs' `tris` and `plane` are not read; `out`: count x height x width int32.
+// Kernels 30 to 32, rdoom_frame_things' three (the table's empty records, the reduction of an id plane with a 64-slot table in LDS
+// per workgroup, the bit rows), take no handle: their arguments are the entry point's, in the same file.
+struct ThingPlaneArgs : PlaneArgs {
+  const uint32_t *tri_thing;  // DeviceLevelView::tri_thing, or null: every element is -1
+};
+rdoom_status launch_thing_plane(hipStream_t st, const ThingPlaneArgs &args);
+
 }  // namespace rdoom_dev

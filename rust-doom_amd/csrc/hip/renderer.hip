@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "kernels.hpp"
+#include "rdoom_frame_things.h"
 
 #pragma clang fp contract(off)
 
@@ -1166,6 +1167,55 @@ rdoom_status rdoom_batch_read_plane(rdoom_batch *b, uint32_t first, uint32_t cou
   for (uint32_t f = first; f < first + count; f += chunk) {
     const uint32_t n = std::min(chunk, first + count - f);
     if (rdoom_status rs = plane_impl(b, f, n, plane, b->d_rgb.get(), b->copy_stream.get())) return rs;
+    HIP_TRY(hipMemcpyAsync((uint8_t *)host_out + (size_t)(f - first) * frame, b->d_rgb.get(), n * frame, hipMemcpyDeviceToHost, b->copy_stream.get()));
+    HIP_TRY(hipStreamSynchronize(b->copy_stream.get()));
+  }
+  return RDOOM_OK;
+}
+
+// ---- the thing plane (framethings.hip; include/rdoom_frame_things.h) ---------------------------------------------------------------
+// what both thing-plane entry points reject before they touch the device or wait for anything
+static rdoom_status thing_plane_args(const rdoom_batch *b, uint32_t first, uint32_t count, uint32_t flags, const void *out) {
+  if (flags & ~(uint32_t)RDOOM_RGB_TOP_DOWN) return rdoom::fail(RDOOM_BAD_ARG, "unknown flag bits 0x%x: 0 or RDOOM_RGB_TOP_DOWN", flags);
+  if (!b || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (b->last_n == 0) return rdoom::fail(RDOOM_BAD_ARG, "nothing rendered yet");
+  if ((uint64_t)first + count > b->last_n) return rdoom::fail(RDOOM_BAD_ARG, "frame range outside the last render");
+  if ((uintptr_t)out % 4u) return rdoom::fail(RDOOM_BAD_ARG, "output is not aligned to the plane's 4-byte element");
+  return RDOOM_OK;
+}
+
+// queues the two thing-plane kernels on st behind the last render; ev_done then marks their end, as resolve_impl
+static rdoom_status thing_plane_impl(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t flags, void *out, hipStream_t st) {
+  HIP_TRY(hipStreamWaitEvent(st, b->ev_done.get(), 0));
+  ThingPlaneArgs a{};
+  a.vis = b->d_vis.get(), a.vis16 = b->vis16, a.qtab = b->d_qtab.get(), a.use_qtab = b->last_skip_vis, a.poses = b->d_poses.get();
+  a.recs = b->d_recs.get(), a.cap = b->cap, a.tris = b->level->view.tris, a.slices = b->level->view.slices;
+  a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list.get(), a.fix_cap = b->fix_cap;
+  a.first = first, a.count = count, a.width = (int)b->width, a.pitch = (int)b->pitch, a.height = (int)b->height;
+  a.top_down = (flags & RDOOM_RGB_TOP_DOWN) != 0u, a.out = out, a.tri_thing = b->level->view.tri_thing;
+  const rdoom_status rs = launch_thing_plane(st, a);
+  HIP_TRY(hipEventRecord(b->ev_done.get(), st));
+  return rs;
+}
+
+rdoom_status rdoom_batch_resolve_thing_plane(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t flags, int32_t *d_out, void *stream) {
+  if (rdoom_status rs = thing_plane_args(b, first, count, flags, d_out)) return rs;
+  HIP_TRY(bind_device(b));
+  if (rdoom_status rs = device_out_check(b, d_out, (size_t)count * b->height * b->width * sizeof(int32_t))) return rs;
+  return thing_plane_impl(b, first, count, flags, d_out, (hipStream_t)stream);
+}
+
+rdoom_status rdoom_batch_read_thing_plane(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t flags, int32_t *host_out) {
+  if (rdoom_status rs = thing_plane_args(b, first, count, flags, host_out)) return rs;
+  HIP_TRY(bind_device(b));
+  if (rdoom_status fs = device_flags(b)) return fs;
+  if (count == 0) return RDOOM_OK;
+  const size_t frame = (size_t)b->height * b->width * sizeof(int32_t);
+  const uint32_t chunk = (uint32_t)std::max<size_t>(1u, std::min<size_t>(count, RGB_STAGING_BYTES / frame));
+  if (rdoom_status rs = staging(b, chunk * frame)) return rs;
+  for (uint32_t f = first; f < first + count; f += chunk) {
+    const uint32_t n = std::min(chunk, first + count - f);
+    if (rdoom_status rs = thing_plane_impl(b, f, n, flags, b->d_rgb.get(), b->copy_stream.get())) return rs;
     HIP_TRY(hipMemcpyAsync((uint8_t *)host_out + (size_t)(f - first) * frame, b->d_rgb.get(), n * frame, hipMemcpyDeviceToHost, b->copy_stream.get()));
     HIP_TRY(hipStreamSynchronize(b->copy_stream.get()));
   }
