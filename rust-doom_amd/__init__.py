@@ -984,22 +984,8 @@ class Batch:
         or a torch stream; None = the null stream).  out: a raw device pointer (int) of count*H*W*(3|4) bytes, or a contiguous
         uint8 torch tensor of that many elements on the batch's device.  Returns out."""
         first, count, fmt, shape = self._rgb_args(first, count, alpha, top_down)
-        if isinstance(out, int):
-            ptr = out
-        else:
-            import torch  # (only here: the package imports without torch)
-            if not isinstance(out, torch.Tensor):
-                raise TypeError('out must be a device pointer (int) or a torch tensor, not %s' % type(out).__name__)
-            if out.dtype != torch.uint8 or not out.is_contiguous() or out.device.type != 'cuda':
-                raise ValueError('out must be a contiguous torch.uint8 tensor on the GPU (got %s, %s, contiguous=%s)'
-                                 % (out.dtype, out.device, out.is_contiguous()))
-            need = int(np.prod(shape))
-            if out.numel() != need:
-                raise ValueError('out has %d elements, frames %d..%d need %s = %d' % (out.numel(), first, first + count, shape, need))
-            ptr = out.data_ptr()  # (the library checks that it lives on the batch's device)
-        if stream is not None and not isinstance(stream, int):
-            stream = stream.cuda_stream
-        _check(lib().rdoom_batch_resolve_rgb(self._h, first, count, fmt, ctypes.c_void_p(ptr or None), ctypes.c_void_p(stream or 0)))
+        ptr = _resolve_out(out, ('uint8',), shape, first, count)
+        _check(lib().rdoom_batch_resolve_rgb(self._h, first, count, fmt, ctypes.c_void_p(ptr or None), ctypes.c_void_p(_stream_handle(stream))))
         return out
 
     def _plane_args(self, plane, first, count, top_down):
@@ -1024,24 +1010,9 @@ class Batch:
         tensor of the plane's dtype (float32 / uint16 / uint32; int16 / int32 are taken as their bits) with that many elements
         on the batch's device.  Returns out."""
         first, count, arg, shape = self._plane_args(plane, first, count, top_down)
-        if isinstance(out, int):
-            ptr = out
-        else:
-            import torch  # (only here: the package imports without torch)
-            if not isinstance(out, torch.Tensor):
-                raise TypeError('out must be a device pointer (int) or a torch tensor, not %s' % type(out).__name__)
-            names = {PLANE_DEPTH: ('float32',), PLANE_LABEL: ('uint16', 'int16'), PLANE_PRIMITIVE: ('uint32', 'int32')}[plane]
-            ok = [getattr(torch, n) for n in names if hasattr(torch, n)]
-            if out.dtype not in ok or not out.is_contiguous() or out.device.type != 'cuda':
-                raise ValueError('out must be a contiguous %s tensor on the GPU (got %s, %s, contiguous=%s)'
-                                 % (' / '.join('torch.' + n for n in names), out.dtype, out.device, out.is_contiguous()))
-            need = int(np.prod(shape))
-            if out.numel() != need:
-                raise ValueError('out has %d elements, frames %d..%d need %s = %d' % (out.numel(), first, first + count, shape, need))
-            ptr = out.data_ptr()  # (the library checks that it lives on the batch's device)
-        if stream is not None and not isinstance(stream, int):
-            stream = stream.cuda_stream
-        _check(lib().rdoom_batch_resolve_plane(self._h, first, count, arg, ctypes.c_void_p(ptr or None), ctypes.c_void_p(stream or 0)))
+        names = {PLANE_DEPTH: ('float32',), PLANE_LABEL: ('uint16', 'int16'), PLANE_PRIMITIVE: ('uint32', 'int32')}[plane]
+        ptr = _resolve_out(out, names, shape, first, count)
+        _check(lib().rdoom_batch_resolve_plane(self._h, first, count, arg, ctypes.c_void_p(ptr or None), ctypes.c_void_p(_stream_handle(stream))))
         return out
 
     def read_thing_plane(self, first=0, count=None, top_down=False):
@@ -1061,20 +1032,7 @@ class Batch:
         torch.int32 tensor with that many elements on the batch's device.  Returns out; frame_things reduces it."""
         count = self.last_n - first if count is None else count
         first, count = int(first), int(count)
-        if isinstance(out, int):
-            ptr = out
-        else:
-            import torch  # (only here: the package imports without torch)
-            if not isinstance(out, torch.Tensor):
-                raise TypeError('out must be a device pointer (int) or a torch tensor, not %s' % type(out).__name__)
-            if out.dtype != torch.int32 or not out.is_contiguous() or out.device.type != 'cuda':
-                raise ValueError('out must be a contiguous torch.int32 tensor on the GPU (got %s, %s, contiguous=%s)'
-                                 % (out.dtype, out.device, out.is_contiguous()))
-            need = count * self.height * self.width
-            if out.numel() != need:
-                raise ValueError('out has %d elements, frames %d..%d need %s = %d'
-                                 % (out.numel(), first, first + count, (count, self.height, self.width), need))
-            ptr = out.data_ptr()  # (the library checks that it lives on the batch's device)
+        ptr = _resolve_out(out, ('int32',), (count, self.height, self.width), first, count)
         _check(lib().rdoom_batch_resolve_thing_plane(self._h, first, count, RGB_TOP_DOWN if top_down else 0, ctypes.c_void_p(ptr or None),
                                                      ctypes.c_void_p(_stream_handle(stream))))
         return out
@@ -1109,24 +1067,9 @@ class Batch:
         tensor on the batch's device with count * prod(observation_shape(...)) elements -- uint8 for the colour formats, float32
         for OBS_DEPTH_MIN.  Returns out."""
         first, count, fmt, fx, fy, shape = self._observation_args(format, factor, first, count, top_down)
-        if isinstance(out, int):
-            ptr = out
-        else:
-            import torch  # (only here: the package imports without torch)
-            if not isinstance(out, torch.Tensor):
-                raise TypeError('out must be a device pointer (int) or a torch tensor, not %s' % type(out).__name__)
-            want = torch.float32 if format == OBS_DEPTH_MIN else torch.uint8
-            if out.dtype != want or not out.is_contiguous() or out.device.type != 'cuda':
-                raise ValueError('out must be a contiguous %s tensor on the GPU (got %s, %s, contiguous=%s)'
-                                 % (want, out.dtype, out.device, out.is_contiguous()))
-            need = int(np.prod(shape))
-            if out.numel() != need:
-                raise ValueError('out has %d elements, frames %d..%d need %s = %d' % (out.numel(), first, first + count, shape, need))
-            ptr = out.data_ptr()  # (the library checks that it lives on the batch's device)
-        if stream is not None and not isinstance(stream, int):
-            stream = stream.cuda_stream
+        ptr = _resolve_out(out, ('float32',) if format == OBS_DEPTH_MIN else ('uint8',), shape, first, count)
         _check(lib().rdoom_batch_resolve_observation(self._h, first, count, fmt, fx, fy, ctypes.c_void_p(ptr or None),
-                                                     ctypes.c_void_p(stream or 0)))
+                                                     ctypes.c_void_p(_stream_handle(stream))))
         return out
 
     def enable_primitive_ids(self):
@@ -1279,9 +1222,28 @@ def poses_from_players_device(states, width, height, time=0.0, offsets=None, str
 
 
 def _stream_handle(stream):
+    """a hipStream_t handle (int), a torch stream, or None: the null stream"""
     if stream is None or isinstance(stream, int):
         return stream or 0
     return stream.cuda_stream
+
+
+def _resolve_out(out, names, shape, first, count):
+    """The `out` of Batch.resolve_*, as a device pointer: an int as it stands, or a contiguous GPU tensor of one of the torch dtypes
+    `names` with prod(shape) elements -- what frames [first, first+count) need"""
+    if isinstance(out, int):
+        return out
+    import torch  # (only here: the package imports without torch)
+    if not isinstance(out, torch.Tensor):
+        raise TypeError('out must be a device pointer (int) or a torch tensor, not %s' % type(out).__name__)
+    ok = [getattr(torch, n) for n in names if hasattr(torch, n)]
+    if out.dtype not in ok or not out.is_contiguous() or out.device.type != 'cuda':
+        raise ValueError('out must be a contiguous %s tensor on the GPU (got %s, %s, contiguous=%s)'
+                         % (' / '.join('torch.' + n for n in names), out.dtype, out.device, out.is_contiguous()))
+    need = int(np.prod(shape))
+    if out.numel() != need:
+        raise ValueError('out has %d elements, frames %d..%d need %s = %d' % (out.numel(), first, first + count, shape, need))
+    return out.data_ptr()  # (the library checks that it lives on the batch's device)
 
 
 def _device_tensor(a, what):

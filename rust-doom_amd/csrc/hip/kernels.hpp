@@ -67,71 +67,55 @@ rdoom_status launch_fragment(hipStream_t st, uint32_t n_poses, const DeviceLevel
 size_t fragment_const_bytes();
 size_t fragment_counts_offset();  // in d_frag_const: three words the fragment kernel counts into under the hook frag_count (FragmentPlan::count)
 
-// Kernels 5 + 6: frames [first, first + count) of the last render -> RGB8 / RGBA8, then the pixels of the fixup list (resolve.hip)
-struct ResolveArgs {
+// What the read-back passes below take from a batch: the last render as it lies on the device and the frames asked for.
+// render_walk.hpp has the walk over it that they share.
+struct FrameSource {
   const uint8_t *fb;
   const void *vis;
   bool vis16;
   const uint32_t *qtab;
   bool use_qtab;  // the render's FragmentPlan::skip_described_vis: a described quadrant's visibility words are stale
   const PoseConst *poses;
-  const uint32_t *palettes;  // per level of the set: 256 words R | G << 8 | B << 16 | 0xFF << 24
+  const TriRec *recs;  // cap records per pose
+  uint32_t cap;
   const uint32_t *fix_count;
   const uint2 *fix_list;
   uint32_t fix_cap;
-  uint32_t first, count;
-  int width, pitch, height;
-  uint32_t bpp;  // 3 or 4
+  uint32_t width, pitch, height;
+  uint32_t first, count;  // frames [first, first + count) of the last render
   bool top_down;
+};
+
+// Kernels 5 + 6: those frames -> RGB8 / RGBA8, then the pixels of the fixup list (resolve.hip)
+struct ResolveArgs : FrameSource {
+  const uint32_t *palettes;  // per level of the set: 256 words R | G << 8 | B << 16 | 0xFF << 24
+  uint32_t bpp;  // 3 or 4
   uint8_t *out;  // count x height x width x bpp bytes
 };
 rdoom_status launch_resolve(hipStream_t st, const ResolveArgs &args);
 
-// Kernels 7 + 8: one per-pixel plane (RDOOM_PLANE_*) of frames [first, first + count) of the last render, from the quadrant table,
-// the visibility words and the pose's records, then the pixels of the fixup list (planes.hip)
-struct PlaneArgs {
-  const void *vis;
-  bool vis16;
-  const uint32_t *qtab;
-  bool use_qtab;  // the render's FragmentPlan::skip_described_vis, as ResolveArgs
-  const PoseConst *poses;
-  const TriRec *recs;  // cap records per pose
-  uint32_t cap;
+// Kernels 7 + 8: one per-pixel plane (RDOOM_PLANE_*, or PLANE_THING) of those frames, from the quadrant table, the visibility words
+// and the pose's records, then the pixels of the fixup list (planes.hip).  Kernels 28 and 29 were the thing plane's own pair; it is
+// a fourth instantiation of this one now.
+constexpr uint32_t PLANE_THING = 4u;  // internal (rdoom_batch_resolve_thing_plane; include/rdoom_frame_things.h has the contract): per
+                                      // pixel the thing of the winning decor triangle, -1 elsewhere
+struct PlaneArgs : FrameSource {
   const LevelTri *tris;  // the label's object ids: LevelTri::packed of slices[pose.level].first_tri + primitive id
   const LevelSlice *slices;
-  const uint32_t *fix_count;
-  const uint2 *fix_list;
-  uint32_t fix_cap;
-  uint32_t first, count;
-  int width, pitch, height;
-  uint32_t plane;  // RDOOM_PLANE_DEPTH / LABEL / PRIMITIVE
-  bool top_down;
+  const uint32_t *tri_thing;  // PLANE_THING only: DeviceLevelView::tri_thing, or null: every element is -1
+  uint32_t plane;  // RDOOM_PLANE_DEPTH / LABEL / PRIMITIVE, PLANE_THING
   void *out;  // count x height x width elements of plane_element_bytes(plane), aligned to the element
 };
 size_t plane_element_bytes(uint32_t plane);
 rdoom_status launch_plane(hipStream_t st, const PlaneArgs &args);
 
-// Kernels 10 + 11: reduced-size observations (RDOOM_OBS_*) of frames [first, first + count) of the last render -- the mean colour,
-// its grey value or the smallest depth of every fx x fy cell -- from what kernels 5 to 8 read, then the cells that hold a pixel of
-// the fixup list (observe.hip)
-struct ObserveArgs {
-  const uint8_t *fb;
-  const void *vis;
-  bool vis16;
-  const uint32_t *qtab;
-  bool use_qtab;  // the render's FragmentPlan::skip_described_vis, as ResolveArgs
-  const PoseConst *poses;
+// Kernels 10 + 11: reduced-size observations (RDOOM_OBS_*) of those frames -- the mean colour, its grey value or the smallest depth
+// of every fx x fy cell -- from what kernels 5 to 8 read, then the cells that hold a pixel of the fixup list (observe.hip).
+// `recs` is read by RDOOM_OBS_DEPTH_MIN only.
+struct ObserveArgs : FrameSource {
   const uint32_t *palettes;  // as ResolveArgs; not read by RDOOM_OBS_DEPTH_MIN
-  const TriRec *recs;        // cap records per pose; read by RDOOM_OBS_DEPTH_MIN only
-  uint32_t cap;
-  const uint32_t *fix_count;
-  const uint2 *fix_list;
-  uint32_t fix_cap;
-  uint32_t first, count;
-  int width, pitch, height;
   uint32_t format;  // RDOOM_OBS_*
   uint32_t fx, fy;  // 1, 2, 4 or 8 each
-  bool top_down;
   void *out;  // count frames of (height / fy) x (width / fx) cells, aligned to the element
 };
 size_t observation_cell_bytes(uint32_t format);  // bytes per cell: 3 (both RGB8 layouts), 1 (grey), 4 (depth)
@@ -373,14 +357,8 @@ struct RayThingArgs {
   float height[8];
 };
 
-// Kernels 28 and 29: the thing plane of frames [first, first + count) of the last render -- per pixel the thing of the winning decor
-// triangle, -1 elsewhere -- found as kernels 7 and 8 find the record, then the pixels of the fixup list (framethings.hip;
-// include/rdoom_frame_things.h has the contract).  PlaneArgs' `tris` and `plane` are not read; `out`: count x height x width int32.
 // Kernels 30 to 32, rdoom_frame_things' three (the table's empty records, the reduction of an id plane with a 64-slot table in LDS
-// per workgroup, the bit rows), take no handle: their arguments are the entry point's, in the same file.
-struct ThingPlaneArgs : PlaneArgs {
-  const uint32_t *tri_thing;  // DeviceLevelView::tri_thing, or null: every element is -1
-};
-rdoom_status launch_thing_plane(hipStream_t st, const ThingPlaneArgs &args);
+// per workgroup, the bit rows), take no handle: their arguments are the entry point's, in framethings.hip
+// (include/rdoom_frame_things.h has the contract).  The thing plane they reduce is kernels 7 + 8's PLANE_THING.
 
 }  // namespace rdoom_dev

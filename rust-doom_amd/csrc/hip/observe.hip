@@ -4,18 +4,15 @@
 // 640 x 400 render costs 1/16 of resolve_rgb's stores and no second pass over a full-size frame.
 //
 // A pixel's colour is resolve.hip's (PLAYPAL 0 where drawn, the clear colour where not), its depth planes.hip's (plane_record.hpp:
-// the same device functions, so the same bits), and both are found the same way:
-//   1. the quadrant table, when the render's plan left out the visibility words of described quadrants: every pixel of a described
-//      quadrant is drawn and shows the entry's record; the visibility words under it are another render's and are never read;
-//   2. otherwise the pixel's visibility word;
-//   3. then the alpha-leak fixup list.  fixup_kernel left the final record of exactly those pixels in vis[o] / fb[o], also inside
-//      described quadrants.  Outside described quadrants pass 2 has read them already.  Inside, a fix pixel changes its cell's sum
-//      or minimum, so a cell cannot be patched per pixel: observe_fix_kernel takes one fix item a thread and recomputes the item's
-//      WHOLE cell -- the pixels of the cell that are on the list (found by one walk over the list, which is short) from vis[o] /
-//      fb[o], the others as pass 1 -- and stores it over what observe_kernel wrote.  Two items of one cell store the same bytes.
+// the same device functions, so the same bits), and both are found by render_walk.hpp's walk: the quadrant table, the visibility
+// words, then the fixup list.  The list is where this unit differs.  Outside described quadrants the main pass has read the list's
+// pixels already.  Inside, a fix pixel changes its cell's sum or minimum, so a cell cannot be patched per pixel: observe_fix_kernel
+// takes one fix item a thread and recomputes the item's WHOLE cell -- the pixels of the cell that are on the list (found by one walk
+// over the list, which is short) from vis[o] / fb[o], the others from the table's record -- and stores it over what observe_kernel
+// wrote.  Two items of one cell store the same bytes.
 //
 // fx, fy are 1, 2, 4 or 8, so a cell never straddles a 32 x 32 quadrant and the table entry is uniform for every cell of a wave.
-// The decomposition is resolve.hip's: a wave per quadrant, two lanes a row, 16 pixels a lane (one 16-byte index load), the palette
+// The decomposition is the walk's: a wave per quadrant, two lanes a row, 16 pixels a lane (one 16-byte index load), the palette
 // staged once per workgroup in LDS.  Horizontal sums are lane-local (fx divides 16: the template parameter), vertical sums and
 // minima combine the fy rows by __shfl_xor steps of 2, 4, 8 lanes (fy: a kernel argument).  The lane of a cell row's first pixel
 // row stores the lane's cells as one contiguous run of the output row -- at fx = 8 the even lane takes the odd lane's two cells
@@ -25,6 +22,7 @@
 
 #include "kernels.hpp"
 #include "plane_record.hpp"
+#include "render_walk.hpp"
 
 #pragma clang fp contract(off)
 
@@ -32,13 +30,9 @@ namespace rdoom_dev {
 namespace {
 
 constexpr uint32_t CLEAR_WORD = RDOOM_CLEAR_R | (RDOOM_CLEAR_G << 8) | (RDOOM_CLEAR_B << 16);
-constexpr uint32_t OBS_QROWS = 4;  // quadrant rows per workgroup, as resolve.hip
-constexpr uint32_t OF_QTAB = 1u, OF_TOP_DOWN = 2u;
 
-typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
-typedef u32x4 u32x4_a4 __attribute__((aligned(4)));  // 16- and 8-byte accesses at dword alignment
-typedef u32x2 u32x2_a4 __attribute__((aligned(4)));
+typedef u32x2 u32x2_a4 __attribute__((aligned(4)));  // 8-byte accesses at dword alignment, beside the walk's 16-byte ones
 
 // what both kernels need of the frame and of the cells, in one kernel argument
 struct ObsGeom {
@@ -120,7 +114,6 @@ __device__ __forceinline__ void store_cells(void *out, uint32_t f, uint32_t yo, 
 }
 
 // ---- the main pass ----------------------------------------------------------------------------------------------------------
-// grid: per frame, groups_x x row_groups workgroups; a workgroup = 4 waves = 4 quadrants side by side, OBS_QROWS rows of them
 template <uint32_t FMT, int LFX, bool VIS16>
 __global__ __launch_bounds__(256) void observe_kernel(const uint8_t *__restrict__ fb, const void *__restrict__ vis,
                                                       const uint32_t *__restrict__ qtab, const PoseConst *__restrict__ poses,
@@ -129,32 +122,26 @@ __global__ __launch_bounds__(256) void observe_kernel(const uint8_t *__restrict_
   constexpr bool COLOUR = FMT != RDOOM_OBS_DEPTH_MIN;
   constexpr int FX = 1 << LFX, NC = 16 / FX;  // cells per lane
   constexpr int NS = LFX == 3 ? 4 : NC;       // cells per storing lane
-  constexpr uint32_t NONE_ID = VIS16 ? 0xFFFFu : NONE;
+  constexpr uint32_t NONE_ID = VisWord<VIS16>::none;
   __shared__ uint32_t pal[COLOUR ? 256 : 1];
-  const uint32_t f = blockIdx.x / g.groups_per_frame, gi = blockIdx.x - f * g.groups_per_frame;
-  const uint32_t pose = g.first + f;
+  const WalkLane l = walk_lane(g.first, g.groups_x, g.groups_per_frame);
+  const uint32_t f = l.f, pose = l.pose, lane = l.lane, qx = l.qx, x0 = l.x0;
   if (COLOUR) {
     pal[threadIdx.x] = palettes[(size_t)poses[pose].level * 256u + threadIdx.x];  // the pose's PLAYPAL 0, staged once
     __syncthreads();
   }
-  const uint32_t wave = (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63u;
-  const uint32_t gy = gi / g.groups_x, gx = gi - gy * g.groups_x;
-  const uint32_t qx = gx * 4u + wave;
   const uint32_t width = g.width, height = g.height, pitch = g.pitch;
   if (qx * 32u >= width) return;  // (wave-uniform; no barrier follows)
-  const uint32_t x0 = qx * 32u + (lane & 1u) * 16u;  // two lanes per row of the quadrant, 32 rows
   const size_t frame = (size_t)pitch * height;
   const uint8_t *pfb = fb + (size_t)pose * frame;
-  const uint16_t *pv16 = reinterpret_cast<const uint16_t *>(vis) + (size_t)pose * frame;
-  const uint32_t *pv32 = reinterpret_cast<const uint32_t *>(vis) + (size_t)pose * frame;
+  const void *pvis = vis_of_pose<VIS16>(vis, pose, frame);
   const TriRec *prec = recs + (size_t)pose * g.cap;
+  const LevelTables no_tables{};  // (depth reads none)
   const uint32_t lfy = g.lfy, lg = (uint32_t)LFX + lfy;
-  for (uint32_t k = 0; k < OBS_QROWS; k++) {
-    const uint32_t qy = gy * OBS_QROWS + k;
+  for (uint32_t k = 0; k < WALK_QROWS; k++) {
+    const uint32_t qy = l.gy * WALK_QROWS + k;
     if (qy * 32u >= height) break;
-    // the table first: a described quadrant has no visibility words of this render
-    uint32_t ent = NONE;
-    if (g.flags & OF_QTAB) ent = qtab[((size_t)pose * g.n_tiles + (qy >> 1) * g.tiles_x + (qx >> 1)) * 4u + (qy & 1u) * 2u + (qx & 1u)];
+    const uint32_t ent = quadrant_entry(qtab, g.flags, pose, g.n_tiles, g.tiles_x, qx, qy);
     const bool described = ent != NONE;
     const uint32_t y = qy * 32u + (lane >> 1);
     // Every lane stays in step to the shuffles below.  A lane outside the frame loads nothing; what it and the pixels past the
@@ -168,30 +155,13 @@ __global__ __launch_bounds__(256) void observe_kernel(const uint8_t *__restrict_
       uint32_t drawn = described ? 0xFFFFu : 0u;  // bit i: pixel x0 + i shows a primitive
       if (inside && whole) {
         idx = *reinterpret_cast<const u32x4_a4 *>(pfb + o);
-        if (!described) {
-          if (VIS16) {
-            const u32x4 a = *reinterpret_cast<const u32x4_a4 *>(pv16 + o), b = *reinterpret_cast<const u32x4_a4 *>(pv16 + o + 8);
-#pragma unroll
-            for (int i = 0; i < 8; i++) {
-              const uint32_t w = i < 4 ? a[i] : b[i - 4];
-              drawn |= ((w & 0xFFFFu) != NONE_ID ? 1u : 0u) << (2 * i);
-              drawn |= ((w >> 16) != NONE_ID ? 1u : 0u) << (2 * i + 1);
-            }
-          } else {
-#pragma unroll
-            for (int j = 0; j < 4; j++) {
-              const u32x4 w = *reinterpret_cast<const u32x4_a4 *>(pv32 + o + 4 * j);
-#pragma unroll
-              for (int i = 0; i < 4; i++) drawn |= (w[i] != NONE_ID ? 1u : 0u) << (4 * j + i);
-            }
-          }
-        }
+        if (!described) drawn = vis_run_drawn<VIS16>(pvis, o);
       } else if (inside) {  // the row's last pixels (a width that is not a multiple of 16)
 #pragma unroll
         for (int i = 0; i < 16; i++) {
           if ((uint32_t)i < npx) {
             idx[i >> 2] |= (uint32_t)pfb[o + i] << (8 * (i & 3));
-            if (!described) drawn |= ((VIS16 ? (uint32_t)pv16[o + i] : pv32[o + i]) != NONE_ID ? 1u : 0u) << i;
+            if (!described) drawn |= (vis_word<VIS16>(pvis, o + i) != NONE_ID ? 1u : 0u) << i;
           }
         }
       }
@@ -223,7 +193,7 @@ __global__ __launch_bounds__(256) void observe_kernel(const uint8_t *__restrict_
       RecVal qrec{0.0f, 0.0f, 0.0f, 0u};
       if (described) {  // wave-uniform: the record's words by scalar loads
         const uint32_t rec = min((uint32_t)__builtin_amdgcn_readfirstlane((int)(ent & ENTRY_REC_MASK)), g.cap - 1u);
-        qrec = fetch_record<RDOOM_PLANE_DEPTH>(prec, rec, nullptr);
+        qrec = fetch_record<RDOOM_PLANE_DEPTH>(prec, rec, no_tables);
       }
       if (inside) {
         const float py = (float)y + 0.5f;
@@ -233,31 +203,17 @@ __global__ __launch_bounds__(256) void observe_kernel(const uint8_t *__restrict_
         } else {
           uint32_t w[16];
           if (whole) {
-            if (VIS16) {
-              const u32x4 a = *reinterpret_cast<const u32x4_a4 *>(pv16 + o), b = *reinterpret_cast<const u32x4_a4 *>(pv16 + o + 8);
-#pragma unroll
-              for (int i = 0; i < 8; i++) {
-                const uint32_t ww = i < 4 ? a[i] : b[i - 4];
-                w[2 * i] = ww & 0xFFFFu, w[2 * i + 1] = ww >> 16;
-              }
-            } else {
-#pragma unroll
-              for (int j = 0; j < 4; j++) {
-                const u32x4 ww = *reinterpret_cast<const u32x4_a4 *>(pv32 + o + 4 * j);
-#pragma unroll
-                for (int i = 0; i < 4; i++) w[4 * j + i] = ww[i];
-              }
-            }
+            vis_run<VIS16>(pvis, o, w);
           } else {
 #pragma unroll
-            for (int i = 0; i < 16; i++) w[i] = (uint32_t)i < npx ? (VIS16 ? (uint32_t)pv16[o + i] : pv32[o + i]) : NONE_ID;
+            for (int i = 0; i < 16; i++) w[i] = (uint32_t)i < npx ? vis_word<VIS16>(pvis, o + i) : NONE_ID;
           }
           uint32_t prev = NONE_ID;  // neighbours mostly share a record: gathered only where the word changes (planes.hip)
           RecVal rv{0.0f, 0.0f, 0.0f, 0u};
 #pragma unroll
           for (int i = 0; i < 16; i++) {
             if (w[i] != NONE_ID && w[i] != prev) {
-              rv = fetch_record<RDOOM_PLANE_DEPTH>(prec, min(w[i], g.cap - 1u), nullptr);
+              rv = fetch_record<RDOOM_PLANE_DEPTH>(prec, min(w[i], g.cap - 1u), no_tables);
               prev = w[i];
             }
             d[i] = w[i] == NONE_ID ? DEPTH_FAR : plane_value<RDOOM_PLANE_DEPTH>(rv, (float)(x0 + i) + 0.5f, py);
@@ -291,7 +247,7 @@ __global__ __launch_bounds__(256) void observe_kernel(const uint8_t *__restrict_
     const uint32_t cy = y >> lfy, cx0 = x0 >> LFX;
     const bool first_row = ((lane >> 1) & ((1u << lfy) - 1u)) == 0u && (LFX != 3 || (lane & 1u) == 0u);
     if (first_row && cy < g.oh && cx0 < g.ow)
-      store_cells<FMT, NS>(out, f, (g.flags & OF_TOP_DOWN) ? g.oh - 1u - cy : cy, cx0, g.ow, g.oh, cs);
+      store_cells<FMT, NS>(out, f, (g.flags & WF_TOP_DOWN) ? g.oh - 1u - cy : cy, cx0, g.ow, g.oh, cs);
   }
 }
 
@@ -305,20 +261,14 @@ __global__ __launch_bounds__(256) void observe_fix_kernel(const uint8_t *__restr
                                                           const uint32_t *__restrict__ fix_count, const uint2 *__restrict__ fix_list,
                                                           uint32_t fix_cap, void *__restrict__ out, ObsGeom g, uint32_t lfx) {
   constexpr bool COLOUR = FMT != RDOOM_OBS_DEPTH_MIN;
-  constexpr uint32_t NONE_ID = VIS16 ? 0xFFFFu : NONE;
-  const uint32_t total = *fix_count;
-  if (total > fix_cap) return;  // fixup_kernel did not run: the render's status says so (device_flags)
+  constexpr uint32_t NONE_ID = VisWord<VIS16>::none;
   const uint32_t lfy = g.lfy, lg = lfx + lfy, fx = 1u << lfx, fy = 1u << lfy, pitch = g.pitch;
-  for (uint32_t item = blockIdx.x * 256u + threadIdx.x; item < total; item += gridDim.x * 256u) {
-    const uint2 it = fix_list[item];  // (pose, row * pitch + column)
-    if (it.x - g.first >= g.count) continue;
-    const uint32_t y = it.y / pitch, x = it.y - y * pitch;
-    if (x >= g.width || y >= g.height) continue;
+  const LevelTables no_tables{};  // (depth reads none)
+  walk_fix_list<VIS16>(vis, fix_count, fix_list, fix_cap, g.first, g.count, g.width, pitch, g.height,
+                       [&](uint32_t pose, uint32_t x, uint32_t y, uint32_t, bool) {
     const uint32_t cx = x >> lfx, cy = y >> lfy;
-    if (cx >= g.ow || cy >= g.oh) continue;  // a leftover column or row: in no cell
-    const uint32_t qx = x >> 5, qy = y >> 5;
-    uint32_t ent = NONE;
-    if (g.flags & OF_QTAB) ent = qtab[((size_t)it.x * g.n_tiles + (qy >> 1) * g.tiles_x + (qx >> 1)) * 4u + (qy & 1u) * 2u + (qx & 1u)];
+    if (cx >= g.ow || cy >= g.oh) return;  // a leftover column or row: in no cell
+    const uint32_t ent = quadrant_entry(qtab, g.flags, pose, g.n_tiles, g.tiles_x, x >> 5, y >> 5);
     const bool described = ent != NONE;
     const uint32_t base = (cy << lfy) * pitch + (cx << lfx);  // the cell's first pixel
     // bit r * fx + c: the pixel's record is in vis[o].  Outside described quadrants that is every pixel; inside, those on the list.
@@ -326,27 +276,27 @@ __global__ __launch_bounds__(256) void observe_fix_kernel(const uint8_t *__restr
     if (described) {
       from_vis = 1ull << ((y - (cy << lfy)) * fx + (x - (cx << lfx)));
       if (lg != 0u) {
+        const uint32_t total = *fix_count;  // (within fix_cap: the walk is under way)
         for (uint32_t j = 0; j < total; j++) {
           const uint2 other = fix_list[j];
           const uint32_t dd = other.y - base;  // (an item before the cell wraps to a large number)
-          if (other.x != it.x || dd > (fy - 1u) * pitch + fx - 1u) continue;
+          if (other.x != pose || dd > (fy - 1u) * pitch + fx - 1u) continue;
           const uint32_t r = dd / pitch, c = dd - r * pitch;
           if (c < fx) from_vis |= 1ull << (r * fx + c);
         }
       }
     }
-    const size_t po = (size_t)it.x * pitch * g.height + base;
-    const TriRec *prec = recs + (size_t)it.x * g.cap;
+    const size_t po = (size_t)pose * pitch * g.height + base;
+    const TriRec *prec = recs + (size_t)pose * g.cap;
     uint32_t cs[1];
     if (COLOUR) {
-      const uint32_t *ppal = palettes + (size_t)poses[it.x].level * 256u;
+      const uint32_t *ppal = palettes + (size_t)poses[pose].level * 256u;
       uint32_t sr = 0u, sg = 0u, sb = 0u;
       for (uint32_t r = 0; r < fy; r++) {
         for (uint32_t c = 0; c < fx; c++) {
           const size_t o = po + (size_t)r * pitch + c;
           bool drawn = true;
-          if ((from_vis >> (r * fx + c)) & 1ull)
-            drawn = (VIS16 ? (uint32_t)reinterpret_cast<const uint16_t *>(vis)[o] : reinterpret_cast<const uint32_t *>(vis)[o]) != NONE_ID;
+          if ((from_vis >> (r * fx + c)) & 1ull) drawn = vis_word<VIS16>(vis, o) != NONE_ID;
           const uint32_t col = drawn ? ppal[fb[o]] : CLEAR_WORD;
           sr += col & 0xFFu, sg += (col >> 8) & 0xFFu, sb += (col >> 16) & 0xFFu;
         }
@@ -354,25 +304,24 @@ __global__ __launch_bounds__(256) void observe_fix_kernel(const uint8_t *__restr
       cs[0] = cell_word<FMT>(sr, sg, sb, lg);
     } else {
       RecVal qrec{0.0f, 0.0f, 0.0f, 0u};
-      if (described) qrec = fetch_record<RDOOM_PLANE_DEPTH>(prec, min(ent & ENTRY_REC_MASK, g.cap - 1u), nullptr);
+      if (described) qrec = fetch_record<RDOOM_PLANE_DEPTH>(prec, min(ent & ENTRY_REC_MASK, g.cap - 1u), no_tables);
       float m = __uint_as_float(DEPTH_FAR);
       for (uint32_t r = 0; r < fy; r++) {
         for (uint32_t c = 0; c < fx; c++) {
           const float px = (float)((cx << lfx) + c) + 0.5f, py = (float)((cy << lfy) + r) + 0.5f;
           uint32_t d = plane_value<RDOOM_PLANE_DEPTH>(qrec, px, py);
           if ((from_vis >> (r * fx + c)) & 1ull) {
-            const size_t o = po + (size_t)r * pitch + c;
-            const uint32_t w = VIS16 ? (uint32_t)reinterpret_cast<const uint16_t *>(vis)[o] : reinterpret_cast<const uint32_t *>(vis)[o];
+            const uint32_t w = vis_word<VIS16>(vis, po + (size_t)r * pitch + c);
             d = DEPTH_FAR;
-            if (w != NONE_ID) d = plane_value<RDOOM_PLANE_DEPTH>(fetch_record<RDOOM_PLANE_DEPTH>(prec, min(w, g.cap - 1u), nullptr), px, py);
+            if (w != NONE_ID) d = plane_value<RDOOM_PLANE_DEPTH>(fetch_record<RDOOM_PLANE_DEPTH>(prec, min(w, g.cap - 1u), no_tables), px, py);
           }
           m = depth_min(__uint_as_float(d), m);
         }
       }
       cs[0] = __float_as_uint(m);
     }
-    store_cells<FMT, 1>(out, it.x - g.first, (g.flags & OF_TOP_DOWN) ? g.oh - 1u - cy : cy, cx, g.ow, g.oh, cs);
-  }
+    store_cells<FMT, 1>(out, pose - g.first, (g.flags & WF_TOP_DOWN) ? g.oh - 1u - cy : cy, cx, g.ow, g.oh, cs);
+  });
 }
 
 template <uint32_t FMT, int LFX, bool VIS16>
@@ -410,22 +359,17 @@ rdoom_status launch_observe(hipStream_t st, const ObserveArgs &a) {
   const uint32_t lfx = factor_log2(a.fx), lfy = factor_log2(a.fy);
   if (lfx > 3u || lfy > 3u) return rdoom::fail(RDOOM_BAD_ARG, "internal: observation factors %u x %u", a.fx, a.fy);
   if (a.format == RDOOM_OBS_DEPTH_MIN && a.cap == 0) return rdoom::fail(RDOOM_BAD_ARG, "internal: a batch without records");
-  const uint32_t tiles_x = ((uint32_t)a.width + TILE_W - 1u) / TILE_W, tiles_y = ((uint32_t)a.height + TILE_H - 1u) / TILE_H;
-  ObsGeom g{};
-  g.first = a.first, g.count = a.count, g.width = (uint32_t)a.width, g.pitch = (uint32_t)a.pitch, g.height = (uint32_t)a.height;
-  g.groups_x = (g.width + 127u) / 128u;
-  g.groups_per_frame = g.groups_x * ((g.height + 32u * OBS_QROWS - 1u) / (32u * OBS_QROWS));
-  g.tiles_x = tiles_x, g.n_tiles = tiles_x * tiles_y, g.cap = a.cap, g.lfy = lfy;
-  g.flags = (a.use_qtab ? OF_QTAB : 0u) | (a.top_down ? OF_TOP_DOWN : 0u);
-  g.ow = g.width >> lfx, g.oh = g.height >> lfy;
-  if (g.ow == 0 || g.oh == 0) return rdoom::fail(RDOOM_BAD_ARG, "internal: an observation without cells");
-  const uint64_t grid = (uint64_t)g.groups_per_frame * a.count;
-  if (grid > 0x7FFFFFFFull) return rdoom::fail(RDOOM_BAD_ARG, "observations of %u frames too large for one launch", a.count);
+  if ((a.width >> lfx) == 0 || (a.height >> lfy) == 0) return rdoom::fail(RDOOM_BAD_ARG, "internal: an observation without cells");
+  WalkLaunch wl;
+  if (rdoom_status rs = walk_launch(a, "observations", false, &wl)) return rs;
+  const ObsGeom g{a.first, a.count, wl.groups_x, wl.groups_per_frame, a.width, a.pitch, a.height, wl.tiles_x, wl.n_tiles, wl.flags, a.cap,
+                  lfy, a.width >> lfx, a.height >> lfy};
+  const uint32_t grid = wl.grid;
   switch (a.format) {
-    case RDOOM_OBS_RGB8: launch_format<RDOOM_OBS_RGB8>(st, (uint32_t)grid, a, g, lfx); break;
-    case RDOOM_OBS_RGB8_PLANAR: launch_format<RDOOM_OBS_RGB8_PLANAR>(st, (uint32_t)grid, a, g, lfx); break;
-    case RDOOM_OBS_GRAY8: launch_format<RDOOM_OBS_GRAY8>(st, (uint32_t)grid, a, g, lfx); break;
-    case RDOOM_OBS_DEPTH_MIN: launch_format<RDOOM_OBS_DEPTH_MIN>(st, (uint32_t)grid, a, g, lfx); break;
+    case RDOOM_OBS_RGB8: launch_format<RDOOM_OBS_RGB8>(st, grid, a, g, lfx); break;
+    case RDOOM_OBS_RGB8_PLANAR: launch_format<RDOOM_OBS_RGB8_PLANAR>(st, grid, a, g, lfx); break;
+    case RDOOM_OBS_GRAY8: launch_format<RDOOM_OBS_GRAY8>(st, grid, a, g, lfx); break;
+    case RDOOM_OBS_DEPTH_MIN: launch_format<RDOOM_OBS_DEPTH_MIN>(st, grid, a, g, lfx); break;
     default: return rdoom::fail(RDOOM_BAD_ARG, "unknown observation format %u", a.format);
   }
   HIP_TRY(hipGetLastError());

@@ -1046,15 +1046,97 @@ static rdoom_status playpal_check(const rdoom_batch *b, uint32_t first, uint32_t
   return RDOOM_OK;
 }
 
-// what both RGB entry points reject before they touch the device or wait for anything
+
+// ---- reading the last render back: RGB (resolve.hip), planes and the thing plane (planes.hip), observations (observe.hip) ----
+// One read-back pass over frames of the last render: which reader, and its entry point's argument as the caller gave it.
+struct ReadPass {
+  enum { RGB, PLANE, THING_PLANE, OBSERVATION } reader;
+  uint32_t arg;     // format / plane / flags, RDOOM_RGB_TOP_DOWN among them
+  uint32_t fx, fy;  // observations only
+};
+
+// what every such entry point rejects, after its own argument's checks, before it touches the device or waits for anything
+static rdoom_status last_render_check(const rdoom_batch *b, uint32_t first, uint32_t count, const void *out) {
+  if (!b || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
+  if (b->last_n == 0) return rdoom::fail(RDOOM_BAD_ARG, "nothing rendered yet");
+  if ((uint64_t)first + count > b->last_n) return rdoom::fail(RDOOM_BAD_ARG, "frame range outside the last render");
+  return RDOOM_OK;
+}
+
 static rdoom_status rgb_args(const rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, const void *out) {
   if (format & ~(0xFFu | (uint32_t)RDOOM_RGB_TOP_DOWN)) return rdoom::fail(RDOOM_BAD_ARG, "unknown format bits 0x%x", format);
   if ((format & 0xFFu) != RDOOM_RGB8 && (format & 0xFFu) != RDOOM_RGBA8)
     return rdoom::fail(RDOOM_BAD_ARG, "format 0x%x: RDOOM_RGB8 or RDOOM_RGBA8, optionally | RDOOM_RGB_TOP_DOWN", format);
-  if (!b || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
-  if (b->last_n == 0) return rdoom::fail(RDOOM_BAD_ARG, "nothing rendered yet");
-  if ((uint64_t)first + count > b->last_n) return rdoom::fail(RDOOM_BAD_ARG, "frame range outside the last render");
+  if (rdoom_status rs = last_render_check(b, first, count, out)) return rs;
   return playpal_check(b, first, count);
+}
+
+static rdoom_status plane_args(const rdoom_batch *b, uint32_t first, uint32_t count, uint32_t plane, const void *out) {
+  if (plane & ~(0xFFu | (uint32_t)RDOOM_RGB_TOP_DOWN)) return rdoom::fail(RDOOM_BAD_ARG, "unknown plane bits 0x%x", plane);
+  const uint32_t which = plane & 0xFFu;  // (PLANE_THING is not the caller's to name)
+  if (which != RDOOM_PLANE_DEPTH && which != RDOOM_PLANE_LABEL && which != RDOOM_PLANE_PRIMITIVE)
+    return rdoom::fail(RDOOM_BAD_ARG, "plane 0x%x: RDOOM_PLANE_DEPTH, _LABEL or _PRIMITIVE, optionally | RDOOM_RGB_TOP_DOWN", plane);
+  if (rdoom_status rs = last_render_check(b, first, count, out)) return rs;
+  if ((uintptr_t)out % plane_element_bytes(which)) return rdoom::fail(RDOOM_BAD_ARG, "output is not aligned to the plane's %zu-byte element", plane_element_bytes(which));
+  return RDOOM_OK;
+}
+
+static rdoom_status thing_plane_args(const rdoom_batch *b, uint32_t first, uint32_t count, uint32_t flags, const void *out) {
+  if (flags & ~(uint32_t)RDOOM_RGB_TOP_DOWN) return rdoom::fail(RDOOM_BAD_ARG, "unknown flag bits 0x%x: 0 or RDOOM_RGB_TOP_DOWN", flags);
+  if (rdoom_status rs = last_render_check(b, first, count, out)) return rs;
+  if ((uintptr_t)out % 4u) return rdoom::fail(RDOOM_BAD_ARG, "output is not aligned to the plane's 4-byte element");
+  return RDOOM_OK;
+}
+
+static rdoom_status observation_args(const rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint32_t fx, uint32_t fy,
+                                     const void *out) {
+  if (format & ~(0xFFu | (uint32_t)RDOOM_RGB_TOP_DOWN)) return rdoom::fail(RDOOM_BAD_ARG, "unknown format bits 0x%x", format);
+  const uint32_t which = format & 0xFFu;
+  if (which != RDOOM_OBS_RGB8 && which != RDOOM_OBS_RGB8_PLANAR && which != RDOOM_OBS_GRAY8 && which != RDOOM_OBS_DEPTH_MIN)
+    return rdoom::fail(RDOOM_BAD_ARG, "format 0x%x: RDOOM_OBS_RGB8, _RGB8_PLANAR, _GRAY8 or _DEPTH_MIN, optionally | RDOOM_RGB_TOP_DOWN", format);
+  for (uint32_t v : {fx, fy})
+    if (v != 1u && v != 2u && v != 4u && v != 8u) return rdoom::fail(RDOOM_BAD_ARG, "factors %u x %u: each must be 1, 2, 4 or 8", fx, fy);
+  if (rdoom_status rs = last_render_check(b, first, count, out)) return rs;
+  if (b->width / fx == 0 || b->height / fy == 0)
+    return rdoom::fail(RDOOM_BAD_ARG, "factors %u x %u leave no cell of a %u x %u frame", fx, fy, b->width, b->height);
+  if (which == RDOOM_OBS_DEPTH_MIN && (uintptr_t)out % 4u) return rdoom::fail(RDOOM_BAD_ARG, "output is not aligned to the format's 4-byte element");
+  return which == RDOOM_OBS_DEPTH_MIN ? RDOOM_OK : playpal_check(b, first, count);
+}
+
+// bytes of one frame as the pass stores it
+static size_t pass_frame_bytes(const rdoom_batch *b, const ReadPass &p) {
+  const size_t pixels = (size_t)b->height * b->width;
+  switch (p.reader) {
+    case ReadPass::RGB: return pixels * (p.arg & 0xFFu);
+    case ReadPass::PLANE: return pixels * plane_element_bytes(p.arg & 0xFFu);
+    case ReadPass::THING_PLANE: return pixels * sizeof(int32_t);
+    default: return (size_t)(b->height / p.fy) * (b->width / p.fx) * observation_cell_bytes(p.arg & 0xFFu);
+  }
+}
+
+static FrameSource frame_source(const rdoom_batch *b, uint32_t first, uint32_t count, bool top_down) {
+  FrameSource s{};
+  s.fb = b->d_fb.get(), s.vis = b->d_vis.get(), s.vis16 = b->vis16, s.qtab = b->d_qtab.get(), s.use_qtab = b->last_skip_vis;
+  s.poses = b->d_poses.get(), s.recs = b->d_recs.get(), s.cap = b->cap;
+  s.fix_count = b->d_fix_count, s.fix_list = b->d_fix_list.get(), s.fix_cap = b->fix_cap;
+  s.width = b->width, s.pitch = b->pitch, s.height = b->height, s.first = first, s.count = count, s.top_down = top_down;
+  return s;
+}
+
+// queues the pass's two kernels on st behind the last render; ev_done then marks their end (finish / read_* wait for it)
+static rdoom_status queue_pass(rdoom_batch *b, const ReadPass &p, uint32_t first, uint32_t count, void *out, hipStream_t st) {
+  HIP_TRY(hipStreamWaitEvent(st, b->ev_done.get(), 0));
+  const FrameSource src = frame_source(b, first, count, (p.arg & RDOOM_RGB_TOP_DOWN) != 0u);
+  const DeviceLevelView &lv = b->level->view;
+  rdoom_status rs = RDOOM_OK;
+  switch (p.reader) {
+    case ReadPass::RGB: rs = launch_resolve(st, ResolveArgs{src, b->level->d_palettes.get(), p.arg & 0xFFu, (uint8_t *)out}); break;
+    case ReadPass::PLANE: rs = launch_plane(st, PlaneArgs{src, lv.tris, lv.slices, nullptr, p.arg & 0xFFu, out}); break;
+    case ReadPass::THING_PLANE: rs = launch_plane(st, PlaneArgs{src, lv.tris, lv.slices, lv.tri_thing, PLANE_THING, out}); break;
+    case ReadPass::OBSERVATION: rs = launch_observe(st, ObserveArgs{src, b->level->d_palettes.get(), p.arg & 0xFFu, p.fx, p.fy, out}); break;
+  }
+  HIP_TRY(hipEventRecord(b->ev_done.get(), st));  // (also after a failed launch: nothing waits for a render that is not the last)
+  return rs;
 }
 
 // device_out of the resolve entry points must be device memory of the batch's device with room for what the kernels write there
@@ -1074,216 +1156,77 @@ static rdoom_status device_out_check(const rdoom_batch *b, const void *device_ou
   return RDOOM_OK;
 }
 
-// the batch's bounded staging buffer of the synchronous read functions: at least `bytes` of device memory
-static rdoom_status staging(rdoom_batch *b, size_t bytes) {
-  if (b->rgb_bytes < bytes) {
-    b->d_rgb.reset(), b->rgb_bytes = 0;
-    if (rdoom_status rs = b->d_rgb.alloc(bytes)) return rs;
-    b->rgb_bytes = bytes;
-  }
-  return RDOOM_OK;
+// the asynchronous entry points, their arguments checked: the pass into the caller's device memory on the caller's stream
+static rdoom_status resolve_to_device(rdoom_batch *b, const ReadPass &p, uint32_t first, uint32_t count, void *device_out, void *stream) {
+  HIP_TRY(bind_device(b));
+  if (rdoom_status rs = device_out_check(b, device_out, (size_t)count * pass_frame_bytes(b, p))) return rs;
+  return queue_pass(b, p, first, count, device_out, (hipStream_t)stream);
 }
 
-// queues the two resolve kernels on st behind the last render; ev_done then marks their end (finish / read_* wait for it)
-static rdoom_status resolve_impl(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint8_t *out, hipStream_t st) {
-  HIP_TRY(hipStreamWaitEvent(st, b->ev_done.get(), 0));
-  ResolveArgs a{};
-  a.fb = b->d_fb.get(), a.vis = b->d_vis.get(), a.vis16 = b->vis16, a.qtab = b->d_qtab.get(), a.use_qtab = b->last_skip_vis, a.poses = b->d_poses.get();
-  a.palettes = b->level->d_palettes.get(), a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list.get(), a.fix_cap = b->fix_cap;
-  a.first = first, a.count = count, a.width = (int)b->width, a.pitch = (int)b->pitch, a.height = (int)b->height;
-  a.bpp = format & 0xFFu, a.top_down = (format & RDOOM_RGB_TOP_DOWN) != 0u, a.out = out;
-  const rdoom_status rs = launch_resolve(st, a);
-  HIP_TRY(hipEventRecord(b->ev_done.get(), st));  // (also after a failed launch: nothing waits for a render that is not the last)
-  return rs;
+// The synchronous entry points, their arguments checked: the pass into the batch's bounded staging buffer -- as many whole frames
+// as fit in RGB_STAGING_BYTES, at least one; allocated on first use -- a chunk of frames at a time, each copied to the host on
+// copy_stream and waited for.
+static rdoom_status read_to_host(rdoom_batch *b, const ReadPass &p, uint32_t first, uint32_t count, void *host_out) {
+  HIP_TRY(bind_device(b));
+  if (rdoom_status fs = device_flags(b)) return fs;
+  if (count == 0) return RDOOM_OK;
+  const size_t frame = pass_frame_bytes(b, p);
+  const uint32_t chunk = (uint32_t)std::max<size_t>(1u, std::min<size_t>(count, RGB_STAGING_BYTES / frame));
+  if (b->rgb_bytes < chunk * frame) {
+    b->d_rgb.reset(), b->rgb_bytes = 0;
+    if (rdoom_status rs = b->d_rgb.alloc(chunk * frame)) return rs;
+    b->rgb_bytes = chunk * frame;
+  }
+  for (uint32_t f = first; f < first + count; f += chunk) {
+    const uint32_t n = std::min(chunk, first + count - f);
+    if (rdoom_status rs = queue_pass(b, p, f, n, b->d_rgb.get(), b->copy_stream.get())) return rs;
+    HIP_TRY(hipMemcpyAsync((uint8_t *)host_out + (size_t)(f - first) * frame, b->d_rgb.get(), n * frame, hipMemcpyDeviceToHost, b->copy_stream.get()));
+    HIP_TRY(hipStreamSynchronize(b->copy_stream.get()));
+  }
+  return RDOOM_OK;
 }
 
 rdoom_status rdoom_batch_resolve_rgb(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, void *device_out, void *stream) {
   if (rdoom_status rs = rgb_args(b, first, count, format, device_out)) return rs;
-  HIP_TRY(bind_device(b));
-  if (rdoom_status rs = device_out_check(b, device_out, (size_t)count * b->height * b->width * (format & 0xFFu))) return rs;
-  return resolve_impl(b, first, count, format, (uint8_t *)device_out, (hipStream_t)stream);
+  return resolve_to_device(b, ReadPass{ReadPass::RGB, format, 1u, 1u}, first, count, device_out, stream);
 }
 
 rdoom_status rdoom_batch_read_rgb(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint8_t *host_out) {
   if (rdoom_status rs = rgb_args(b, first, count, format, host_out)) return rs;
-  HIP_TRY(bind_device(b));
-  if (rdoom_status fs = device_flags(b)) return fs;
-  if (count == 0) return RDOOM_OK;
-  const size_t frame = (size_t)b->height * b->width * (format & 0xFFu);
-  const uint32_t chunk = (uint32_t)std::max<size_t>(1u, std::min<size_t>(count, RGB_STAGING_BYTES / frame));
-  if (rdoom_status rs = staging(b, chunk * frame)) return rs;
-  for (uint32_t f = first; f < first + count; f += chunk) {
-    const uint32_t n = std::min(chunk, first + count - f);
-    if (rdoom_status rs = resolve_impl(b, f, n, format, b->d_rgb.get(), b->copy_stream.get())) return rs;
-    HIP_TRY(hipMemcpyAsync(host_out + (size_t)(f - first) * frame, b->d_rgb.get(), n * frame, hipMemcpyDeviceToHost, b->copy_stream.get()));
-    HIP_TRY(hipStreamSynchronize(b->copy_stream.get()));
-  }
-  return RDOOM_OK;
-}
-
-// ---- depth / label / primitive planes (planes.hip) ------------------------------------------------------------------------
-// what both plane entry points reject before they touch the device or wait for anything
-static rdoom_status plane_args(const rdoom_batch *b, uint32_t first, uint32_t count, uint32_t plane, const void *out) {
-  if (plane & ~(0xFFu | (uint32_t)RDOOM_RGB_TOP_DOWN)) return rdoom::fail(RDOOM_BAD_ARG, "unknown plane bits 0x%x", plane);
-  const uint32_t which = plane & 0xFFu;
-  if (which != RDOOM_PLANE_DEPTH && which != RDOOM_PLANE_LABEL && which != RDOOM_PLANE_PRIMITIVE)
-    return rdoom::fail(RDOOM_BAD_ARG, "plane 0x%x: RDOOM_PLANE_DEPTH, _LABEL or _PRIMITIVE, optionally | RDOOM_RGB_TOP_DOWN", plane);
-  if (!b || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
-  if (b->last_n == 0) return rdoom::fail(RDOOM_BAD_ARG, "nothing rendered yet");
-  if ((uint64_t)first + count > b->last_n) return rdoom::fail(RDOOM_BAD_ARG, "frame range outside the last render");
-  if ((uintptr_t)out % plane_element_bytes(which)) return rdoom::fail(RDOOM_BAD_ARG, "output is not aligned to the plane's %zu-byte element", plane_element_bytes(which));
-  return RDOOM_OK;
-}
-
-// queues the two plane kernels on st behind the last render; ev_done then marks their end, as resolve_impl
-static rdoom_status plane_impl(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t plane, void *out, hipStream_t st) {
-  HIP_TRY(hipStreamWaitEvent(st, b->ev_done.get(), 0));
-  PlaneArgs a{};
-  a.vis = b->d_vis.get(), a.vis16 = b->vis16, a.qtab = b->d_qtab.get(), a.use_qtab = b->last_skip_vis, a.poses = b->d_poses.get();
-  a.recs = b->d_recs.get(), a.cap = b->cap, a.tris = b->level->view.tris, a.slices = b->level->view.slices;
-  a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list.get(), a.fix_cap = b->fix_cap;
-  a.first = first, a.count = count, a.width = (int)b->width, a.pitch = (int)b->pitch, a.height = (int)b->height;
-  a.plane = plane & 0xFFu, a.top_down = (plane & RDOOM_RGB_TOP_DOWN) != 0u, a.out = out;
-  const rdoom_status rs = launch_plane(st, a);
-  HIP_TRY(hipEventRecord(b->ev_done.get(), st));
-  return rs;
+  return read_to_host(b, ReadPass{ReadPass::RGB, format, 1u, 1u}, first, count, host_out);
 }
 
 rdoom_status rdoom_batch_resolve_plane(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t plane, void *device_out, void *stream) {
   if (rdoom_status rs = plane_args(b, first, count, plane, device_out)) return rs;
-  HIP_TRY(bind_device(b));
-  if (rdoom_status rs = device_out_check(b, device_out, (size_t)count * b->height * b->width * plane_element_bytes(plane & 0xFFu))) return rs;
-  return plane_impl(b, first, count, plane, device_out, (hipStream_t)stream);
+  return resolve_to_device(b, ReadPass{ReadPass::PLANE, plane, 1u, 1u}, first, count, device_out, stream);
 }
 
 rdoom_status rdoom_batch_read_plane(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t plane, void *host_out) {
   if (rdoom_status rs = plane_args(b, first, count, plane, host_out)) return rs;
-  HIP_TRY(bind_device(b));
-  if (rdoom_status fs = device_flags(b)) return fs;
-  if (count == 0) return RDOOM_OK;
-  const size_t frame = (size_t)b->height * b->width * plane_element_bytes(plane & 0xFFu);
-  const uint32_t chunk = (uint32_t)std::max<size_t>(1u, std::min<size_t>(count, RGB_STAGING_BYTES / frame));
-  if (rdoom_status rs = staging(b, chunk * frame)) return rs;
-  for (uint32_t f = first; f < first + count; f += chunk) {
-    const uint32_t n = std::min(chunk, first + count - f);
-    if (rdoom_status rs = plane_impl(b, f, n, plane, b->d_rgb.get(), b->copy_stream.get())) return rs;
-    HIP_TRY(hipMemcpyAsync((uint8_t *)host_out + (size_t)(f - first) * frame, b->d_rgb.get(), n * frame, hipMemcpyDeviceToHost, b->copy_stream.get()));
-    HIP_TRY(hipStreamSynchronize(b->copy_stream.get()));
-  }
-  return RDOOM_OK;
+  return read_to_host(b, ReadPass{ReadPass::PLANE, plane, 1u, 1u}, first, count, host_out);
 }
 
-// ---- the thing plane (framethings.hip; include/rdoom_frame_things.h) ---------------------------------------------------------------
-// what both thing-plane entry points reject before they touch the device or wait for anything
-static rdoom_status thing_plane_args(const rdoom_batch *b, uint32_t first, uint32_t count, uint32_t flags, const void *out) {
-  if (flags & ~(uint32_t)RDOOM_RGB_TOP_DOWN) return rdoom::fail(RDOOM_BAD_ARG, "unknown flag bits 0x%x: 0 or RDOOM_RGB_TOP_DOWN", flags);
-  if (!b || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
-  if (b->last_n == 0) return rdoom::fail(RDOOM_BAD_ARG, "nothing rendered yet");
-  if ((uint64_t)first + count > b->last_n) return rdoom::fail(RDOOM_BAD_ARG, "frame range outside the last render");
-  if ((uintptr_t)out % 4u) return rdoom::fail(RDOOM_BAD_ARG, "output is not aligned to the plane's 4-byte element");
-  return RDOOM_OK;
-}
-
-// queues the two thing-plane kernels on st behind the last render; ev_done then marks their end, as resolve_impl
-static rdoom_status thing_plane_impl(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t flags, void *out, hipStream_t st) {
-  HIP_TRY(hipStreamWaitEvent(st, b->ev_done.get(), 0));
-  ThingPlaneArgs a{};
-  a.vis = b->d_vis.get(), a.vis16 = b->vis16, a.qtab = b->d_qtab.get(), a.use_qtab = b->last_skip_vis, a.poses = b->d_poses.get();
-  a.recs = b->d_recs.get(), a.cap = b->cap, a.tris = b->level->view.tris, a.slices = b->level->view.slices;
-  a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list.get(), a.fix_cap = b->fix_cap;
-  a.first = first, a.count = count, a.width = (int)b->width, a.pitch = (int)b->pitch, a.height = (int)b->height;
-  a.top_down = (flags & RDOOM_RGB_TOP_DOWN) != 0u, a.out = out, a.tri_thing = b->level->view.tri_thing;
-  const rdoom_status rs = launch_thing_plane(st, a);
-  HIP_TRY(hipEventRecord(b->ev_done.get(), st));
-  return rs;
-}
-
+// (include/rdoom_frame_things.h)
 rdoom_status rdoom_batch_resolve_thing_plane(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t flags, int32_t *d_out, void *stream) {
   if (rdoom_status rs = thing_plane_args(b, first, count, flags, d_out)) return rs;
-  HIP_TRY(bind_device(b));
-  if (rdoom_status rs = device_out_check(b, d_out, (size_t)count * b->height * b->width * sizeof(int32_t))) return rs;
-  return thing_plane_impl(b, first, count, flags, d_out, (hipStream_t)stream);
+  return resolve_to_device(b, ReadPass{ReadPass::THING_PLANE, flags, 1u, 1u}, first, count, d_out, stream);
 }
 
 rdoom_status rdoom_batch_read_thing_plane(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t flags, int32_t *host_out) {
   if (rdoom_status rs = thing_plane_args(b, first, count, flags, host_out)) return rs;
-  HIP_TRY(bind_device(b));
-  if (rdoom_status fs = device_flags(b)) return fs;
-  if (count == 0) return RDOOM_OK;
-  const size_t frame = (size_t)b->height * b->width * sizeof(int32_t);
-  const uint32_t chunk = (uint32_t)std::max<size_t>(1u, std::min<size_t>(count, RGB_STAGING_BYTES / frame));
-  if (rdoom_status rs = staging(b, chunk * frame)) return rs;
-  for (uint32_t f = first; f < first + count; f += chunk) {
-    const uint32_t n = std::min(chunk, first + count - f);
-    if (rdoom_status rs = thing_plane_impl(b, f, n, flags, b->d_rgb.get(), b->copy_stream.get())) return rs;
-    HIP_TRY(hipMemcpyAsync((uint8_t *)host_out + (size_t)(f - first) * frame, b->d_rgb.get(), n * frame, hipMemcpyDeviceToHost, b->copy_stream.get()));
-    HIP_TRY(hipStreamSynchronize(b->copy_stream.get()));
-  }
-  return RDOOM_OK;
-}
-
-// ---- reduced-size observations (observe.hip) -------------------------------------------------------------------------------
-// what both observation entry points reject before they touch the device or wait for anything
-static rdoom_status observation_args(const rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint32_t fx, uint32_t fy,
-                                     const void *out) {
-  if (format & ~(0xFFu | (uint32_t)RDOOM_RGB_TOP_DOWN)) return rdoom::fail(RDOOM_BAD_ARG, "unknown format bits 0x%x", format);
-  const uint32_t which = format & 0xFFu;
-  if (which != RDOOM_OBS_RGB8 && which != RDOOM_OBS_RGB8_PLANAR && which != RDOOM_OBS_GRAY8 && which != RDOOM_OBS_DEPTH_MIN)
-    return rdoom::fail(RDOOM_BAD_ARG, "format 0x%x: RDOOM_OBS_RGB8, _RGB8_PLANAR, _GRAY8 or _DEPTH_MIN, optionally | RDOOM_RGB_TOP_DOWN", format);
-  for (uint32_t v : {fx, fy})
-    if (v != 1u && v != 2u && v != 4u && v != 8u) return rdoom::fail(RDOOM_BAD_ARG, "factors %u x %u: each must be 1, 2, 4 or 8", fx, fy);
-  if (!b || !out) return rdoom::fail(RDOOM_BAD_ARG, "null argument");
-  if (b->last_n == 0) return rdoom::fail(RDOOM_BAD_ARG, "nothing rendered yet");
-  if ((uint64_t)first + count > b->last_n) return rdoom::fail(RDOOM_BAD_ARG, "frame range outside the last render");
-  if (b->width / fx == 0 || b->height / fy == 0)
-    return rdoom::fail(RDOOM_BAD_ARG, "factors %u x %u leave no cell of a %u x %u frame", fx, fy, b->width, b->height);
-  if (which == RDOOM_OBS_DEPTH_MIN && (uintptr_t)out % 4u) return rdoom::fail(RDOOM_BAD_ARG, "output is not aligned to the format's 4-byte element");
-  return which == RDOOM_OBS_DEPTH_MIN ? RDOOM_OK : playpal_check(b, first, count);
-}
-
-static size_t observation_frame_bytes(const rdoom_batch *b, uint32_t format, uint32_t fx, uint32_t fy) {
-  return (size_t)(b->height / fy) * (b->width / fx) * observation_cell_bytes(format & 0xFFu);
-}
-
-// queues the two observation kernels on st behind the last render; ev_done then marks their end, as resolve_impl
-static rdoom_status observation_impl(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint32_t fx, uint32_t fy, void *out,
-                                     hipStream_t st) {
-  HIP_TRY(hipStreamWaitEvent(st, b->ev_done.get(), 0));
-  ObserveArgs a{};
-  a.fb = b->d_fb.get(), a.vis = b->d_vis.get(), a.vis16 = b->vis16, a.qtab = b->d_qtab.get(), a.use_qtab = b->last_skip_vis, a.poses = b->d_poses.get();
-  a.palettes = b->level->d_palettes.get(), a.recs = b->d_recs.get(), a.cap = b->cap;
-  a.fix_count = b->d_fix_count, a.fix_list = b->d_fix_list.get(), a.fix_cap = b->fix_cap;
-  a.first = first, a.count = count, a.width = (int)b->width, a.pitch = (int)b->pitch, a.height = (int)b->height;
-  a.format = format & 0xFFu, a.fx = fx, a.fy = fy, a.top_down = (format & RDOOM_RGB_TOP_DOWN) != 0u, a.out = out;
-  const rdoom_status rs = launch_observe(st, a);
-  HIP_TRY(hipEventRecord(b->ev_done.get(), st));
-  return rs;
+  return read_to_host(b, ReadPass{ReadPass::THING_PLANE, flags, 1u, 1u}, first, count, host_out);
 }
 
 rdoom_status rdoom_batch_resolve_observation(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint32_t fx, uint32_t fy,
                                              void *device_out, void *stream) {
   if (rdoom_status rs = observation_args(b, first, count, format, fx, fy, device_out)) return rs;
-  HIP_TRY(bind_device(b));
-  if (rdoom_status rs = device_out_check(b, device_out, (size_t)count * observation_frame_bytes(b, format, fx, fy))) return rs;
-  return observation_impl(b, first, count, format, fx, fy, device_out, (hipStream_t)stream);
+  return resolve_to_device(b, ReadPass{ReadPass::OBSERVATION, format, fx, fy}, first, count, device_out, stream);
 }
 
 rdoom_status rdoom_batch_read_observation(rdoom_batch *b, uint32_t first, uint32_t count, uint32_t format, uint32_t fx, uint32_t fy,
                                           void *host_out) {
   if (rdoom_status rs = observation_args(b, first, count, format, fx, fy, host_out)) return rs;
-  HIP_TRY(bind_device(b));
-  if (rdoom_status fs = device_flags(b)) return fs;
-  if (count == 0) return RDOOM_OK;
-  const size_t frame = observation_frame_bytes(b, format, fx, fy);
-  const uint32_t chunk = (uint32_t)std::max<size_t>(1u, std::min<size_t>(count, RGB_STAGING_BYTES / frame));
-  if (rdoom_status rs = staging(b, chunk * frame)) return rs;
-  for (uint32_t f = first; f < first + count; f += chunk) {
-    const uint32_t n = std::min(chunk, first + count - f);
-    if (rdoom_status rs = observation_impl(b, f, n, format, fx, fy, b->d_rgb.get(), b->copy_stream.get())) return rs;
-    HIP_TRY(hipMemcpyAsync((uint8_t *)host_out + (size_t)(f - first) * frame, b->d_rgb.get(), n * frame, hipMemcpyDeviceToHost, b->copy_stream.get()));
-    HIP_TRY(hipStreamSynchronize(b->copy_stream.get()));
-  }
-  return RDOOM_OK;
+  return read_to_host(b, ReadPass{ReadPass::OBSERVATION, format, fx, fy}, first, count, host_out);
 }
 
 }  // extern "C"

@@ -1,5 +1,6 @@
-"""The kernels of rust-doom_amd/csrc/hip/framethings.hip as shipped: they are in the library, use no scratch memory and spill no
-register; the thing-plane kernels use no LDS, as the plane kernels they are modelled on; the reduction keeps its 64-slot table in
+"""The kernels of things in the frame as shipped -- the thing plane's pair, planes.hip's instantiation for its fourth, internal plane
+(PLANE_THING = 4 in kernels.hpp), and the three of rust-doom_amd/csrc/hip/framethings.hip: they are in the library, use no scratch
+memory and spill no register; the thing-plane kernels use no LDS, as the other planes'; the reduction keeps its 64-slot table in
 well under 8 KiB of static LDS; all run 256 threads a workgroup.  These are conditions; the register counts recorded below are what
 the shipped build gave, and what DESIGN section 34 quotes.  Only the new kernels are named here."""
 import importlib.util
@@ -15,8 +16,8 @@ kr = importlib.util.module_from_spec(_spec)
 _spec.loader.exec_module(kr)
 
 TABLE = 7 * 64 * 4  # framethings.hip FrameThingTable: key, count, four box words and the depth bits of 64 slots
-RECORDED = {'thing_plane_kernel<false>': dict(vgpr_count=32, lds=0), 'thing_plane_kernel<true>': dict(vgpr_count=32, lds=0),
-            'thing_plane_fix_kernel<false>': dict(vgpr_count=14, lds=0), 'thing_plane_fix_kernel<true>': dict(vgpr_count=14, lds=0),
+RECORDED = {'plane_kernel<4u, false>': dict(vgpr_count=32, lds=0), 'plane_kernel<4u, true>': dict(vgpr_count=32, lds=0),
+            'plane_fix_kernel<4u, false>': dict(vgpr_count=14, lds=0), 'plane_fix_kernel<4u, true>': dict(vgpr_count=14, lds=0),
             'frame_things_init_kernel': dict(vgpr_count=6, lds=0), 'frame_things_reduce_kernel': dict(vgpr_count=23, lds=TABLE),
             'frame_things_bits_kernel': dict(vgpr_count=19, lds=0)}
 
