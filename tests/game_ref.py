@@ -136,6 +136,8 @@ class RefGame:
         self.offsets = np.zeros((n, n_objects, 3), np.float32)
 
     def step(self, states, inputs, actions=None, config=None, dt=1.0 / 60.0, threads=16):
+        """a stepped copy of `states`; dt 0 means 1/60 (include/rdoom.h), as in RefWorld.step"""
+        dt = float(np.float32(1.0) / np.float32(60.0)) if dt == 0 else dt
         states = np.array(states, rd.PLAYER_STATE).reshape(-1)
         n = self.n
         inputs = np.ascontiguousarray(inputs, rd.PLAYER_INPUT).reshape(-1, n)

@@ -111,6 +111,7 @@ def old_runs(scale=4, thin=False, libs=Libs):
         for key in ('0', '30'):
             runs.append(('model %s dt %s' % (name, key), model(name, key)))
 
+    # (key '0' is a tick length of 0, which the device and RefGame.step / RefWorldSet.step read as 1/60)
     def game(patched, n, seed, ticks, name='default', key='0', push=0.05):  # test_gpu_game.py: _bit_exact; gpu_step_child: case_game
         def run():
             from test_game_host import patched_variant

@@ -13,7 +13,8 @@ import world_ref
 from util import META_PATH, ensure_wad
 
 RARE = ('diverged', 'pitch_low', 'no_drag')  # the family by name: a case that leaves it fails here
-# what the old inputs alone never take, of what can be taken (tools/restatement_coverage.py, profiles/step_branch_census.txt)
+# what the old inputs alone never take, of what can be taken (tools/restatement_coverage.py, profiles/step_branch_census.txt);
+# derived again once the game and set replays stepped at 1/60 and not at a tick length of 0: the same one name
 OLD_MISS = ('pitch_clamped_low',)
 
 

@@ -27,11 +27,14 @@
   X(sweep_plane_wins) X(sweep_vertex_wins) X(sweep_edge_wins) \
   X(root_negative) X(root_nonnegative) X(root_first_lower) X(line_denom_zero) X(axis_yz) X(axis_xz) X(axis_xy) \
   X(node_both_children) X(node_unlinked_child) X(node_stack_full) X(dyn_with_offsets) X(dyn_without_offsets)
+#ifndef RS_CENSUS_MORE_NAMES /* a source that includes this one appends its own outcomes to the table (game_restatement.c) */
+#define RS_CENSUS_MORE_NAMES(X)
+#endif
 #ifdef RS_CENSUS
 #define RS_ENUM(n) RS_##n,
-enum { RS_CENSUS_NAMES(RS_ENUM) RS_N };
+enum { RS_CENSUS_NAMES(RS_ENUM) RS_CENSUS_MORE_NAMES(RS_ENUM) RS_N };
 #define RS_STR(n) #n,
-static const char *const rs_names[RS_N] = {RS_CENSUS_NAMES(RS_STR)};
+static const char *const rs_names[RS_N] = {RS_CENSUS_NAMES(RS_STR) RS_CENSUS_MORE_NAMES(RS_STR)};
 static uint64_t rs_counts[RS_N];
 static __thread int rs_in_tick;
 #define CENSUS(n) do { if (rs_in_tick) __atomic_fetch_add(&rs_counts[RS_##n], 1, __ATOMIC_RELAXED); } while (0)

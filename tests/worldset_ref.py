@@ -95,9 +95,17 @@ def exit_variant(directory):
     return path, meta, lines
 
 
+# the outcomes of the level change that RefWorldSet counts as it steps (tests/test_game_census_host.py)
+SET_CENSUS_NAMES = ('change_started', 'exit_no_destination', 'exit_during_change', 'change_with_effect_active',
+                    'change_with_trigger_removed', 'change_with_nonzero_offset')
+
+
 class RefWorldSet:
     """N players over the levels `indices` of a WAD: per level a world_ref.RefWorld and a game_ref.RefGame with a row for every
-    player (only the rows of the players in that level are stepped), the players' slots, and the change stage of each"""
+    player (only the rows of the players in that level are stepped), the players' slots, and the change stage of each.
+    `set_census` counts the level change's outcomes, {name of SET_CENSUS_NAMES: times taken}: an exit that starts a change, one
+    in a level without a destination, one fired while a change is under way; and a change that arrives (the old game is dropped)
+    with an effect active, with a trigger removed, with an object's offset not zero"""
 
     def __init__(self, wad_path, meta_path, indices, levels, census=False):
         self.wad = rd.Wad(wad_path, meta_path)
@@ -115,6 +123,7 @@ class RefWorldSet:
         self.dest = [self.indices.index(i + 1) if i + 1 in self.indices else None for i in self.indices]
         self.n_objects = max(g.n_objects for g in self.games)
         self.stage = np.zeros(n, np.int64)
+        self.set_census = dict.fromkeys(SET_CENSUS_NAMES, 0)
 
     def _fresh(self, slot, p):
         g = self.games[slot]
@@ -123,7 +132,9 @@ class RefWorldSet:
         g.act[p], g.aflags[p], g.offsets[p] = 0, 0, 0
 
     def step(self, states, inputs, actions=None, config=None, dt=1.0 / 60.0, threads=16):
-        """n_ticks ticks, one at a time: (states, inputs (n_ticks, n), actions (n_ticks, n) or None) -> the stepped states"""
+        """n_ticks ticks, one at a time: (states, inputs (n_ticks, n), actions (n_ticks, n) or None) -> the stepped states; dt 0
+        means 1/60 (include/rdoom.h), as in RefWorld.step"""
+        dt = float(np.float32(1.0) / np.float32(60.0)) if dt == 0 else dt
         states = np.array(states, rd.PLAYER_STATE).reshape(-1)
         n = len(states)
         inputs = np.asarray(inputs, rd.PLAYER_INPUT).reshape(-1, n)
@@ -133,6 +144,10 @@ class RefWorldSet:
             for p in requested:     # WadSystem::update loads it, Level is rebuilt, Player::update resets
                 self.stage[p] = 0
                 d = self.dest[self.levels[p]]
+                old = self.games[self.levels[p]]
+                self.set_census['change_with_effect_active'] += int((old.aflags[p] & 1).any())
+                self.set_census['change_with_trigger_removed'] += int(old.counts[p] < len(old.trig))
+                self.set_census['change_with_nonzero_offset'] += int((old.offsets[p] != 0).any())
                 self.levels[p] = d
                 self._fresh(d, p)
                 pos, yaw = self.starts[d]
@@ -158,6 +173,10 @@ class RefWorldSet:
                 if self.dest[slot] is not None:
                     start = sel[fired & (self.stage[sel] == 0)]
                     self.stage[start] = 1
+                    self.set_census['change_started'] += len(start)
+                    self.set_census['exit_during_change'] += int((fired & (self.stage[sel] != 0)).sum()) - len(start)
+                else:
+                    self.set_census['exit_no_destination'] += int(fired.sum())
         return states
 
     def offsets(self):
